@@ -27,6 +27,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 C5_GRAPHS, C5_NODES, C5_M = 1024, 4096, 8
+DUMP_MAX_ROWS = 1 << 20     # --dump-outputs: rows written per array (c3 default: 19M output rows, 456 MB in full)
+DUMP_MAX_BYTES = 64 << 20
 
 
 def parse_args(argv=None):
@@ -47,7 +49,13 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-runs", type=int, default=5, help="c3: full oracle runs the CPU baseline is the median of (SURVEY 8(d) says 10; five of the headline workload take about 25 s)")
     ap.add_argument("--no-gather", action="store_true")
     ap.add_argument("--master-port", type=int, default=29541)
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float64; rank 0; arrays of more than "
+                         f"{DUMP_MAX_ROWS} rows as a fixed seeded sample of rows, with the sampled row indices in DIR/<name>_sample_rows.npy)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_plan(args, argv, env):
@@ -140,6 +148,29 @@ def _c5_cpu_one(g):
     return time.perf_counter() - t0
 
 
+def dump_outputs(dirname, outs):
+    """--dump-outputs: every array of `outs` as dirname/<name>.npy in float64 (the ids and row pointers are exact below 2**53).
+    An array of more than DUMP_MAX_ROWS rows is written as the rows a generator seeded with 0 picks for that row count, in
+    order, beside their indices (<name>_sample_rows.npy): equal outputs give equal files from run to run and build to build."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, a in outs.items():
+        a = torch.as_tensor(a)
+        files = {}
+        if a.dim() > 0 and a.shape[0] > DUMP_MAX_ROWS:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], DUMP_MAX_ROWS, replace=False))
+            a = a.index_select(0, torch.from_numpy(rows).to(a.device))
+            files[name + "_sample_rows"] = rows.astype(np.float64)
+        files[name] = a.cpu().numpy().astype(np.float64)
+        for f, v in files.items():
+            path = os.path.join(dirname, f + ".npy")
+            np.save(path, v)
+            total += os.path.getsize(path)
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs wrote {total} bytes"
+
+
 def main():
     argv = sys.argv[1:]
     args = parse_args(argv)
@@ -186,7 +217,7 @@ def main():
         perm_dev = None if perm is None else perm.to(dev)
 
         def step():
-            return ops.approximate_cholesky(ei, w_dev, n, t, o_v, o_n, perm=perm_dev, seed=7, return_device="same", mode=args.mode)
+            return {"sc_edge_info": ops.approximate_cholesky(ei, w_dev, n, t, o_v, o_n, perm=perm_dev, seed=7, return_device="same", mode=args.mode)}
         units_per_rank_nominal = min(t, n - 1)
     else:
         Gtot, n, m = args.graphs, C5_NODES, C5_M
@@ -201,16 +232,17 @@ def main():
 
         def step():
             if hi == lo:
-                return torch.zeros((0, 3), dtype=torch.float64, device=dev)
-            sc, _ = ops.approximate_cholesky_batched(big, None, node_ptr, ts, o_v, o_n, perm=perm_dev, seed=7 + lo)
-            return sc
+                return {"sc_edge_info": torch.zeros((0, 3), dtype=torch.float64, device=dev), "row_ptr": torch.zeros(1, dtype=torch.int64)}
+            sc, rp = ops.approximate_cholesky_batched(big, None, node_ptr, ts, o_v, o_n, perm=perm_dev, seed=7 + lo)
+            return {"sc_edge_info": sc, "row_ptr": rp}
         units_per_rank_nominal = (hi - lo) * (n // 2)
 
     def full_step():
-        sc = step()
+        """The timed path: what its caller receives, by name (row_ptr: this rank's graphs; rows_per_rank: the all-gather's counts)."""
+        outs = step()
         if world > 1 and not args.no_gather:
-            sc, _ = all_gather_edge_rows(sc)
-        return sc
+            outs["sc_edge_info"], outs["rows_per_rank"] = all_gather_edge_rows(outs["sc_edge_info"])
+        return outs
 
     def sync():
         torch.cuda.synchronize(dev)
@@ -234,11 +266,14 @@ def main():
     t0 = time.perf_counter()
     kstats = []
     for _ in range(args.steps):
-        sc = full_step()
+        outs = full_step()
         if ops.last_stats:
             kstats.append(dict(ops.last_stats))
     sync()
     elapsed = time.perf_counter() - t0
+    sc = outs["sc_edge_info"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs)
     tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     units = torch.tensor([float(kstats[-1]["n_eliminated"]) if kstats else 0.0, float(kstats[-1]["out_rows"]) if kstats else 0.0],
                          dtype=torch.float64, device=dev)

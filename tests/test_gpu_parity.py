@@ -803,13 +803,35 @@ def _load_edge_list(path):
     return a if a.shape[0] == 2 else a.T
 
 
+def _write_raw_standin(tmp_path, env):
+    """A seeded raw edge list shaped like the dataset `env` names (Cora: 2,708 nodes, two-column text; ogbn-arxiv in
+    miniature: a (2,E) .npz), with what to_undirected cleans up in the real files: one direction per edge as collected,
+    the reverse of some edges listed again, repeated edges and self loops."""
+    n, m, seed, ext = (2708, 2, 31, ".txt") if env == "RLAP_CORA_EDGES" else (6000, 6, 32, ".npz")
+    ei = ba_graph(n, m, seed)
+    a, b = ei[:, ei[0] < ei[1]]
+    rs = np.random.RandomState(seed)
+    flip = rs.rand(a.size) < 0.5
+    a, b = np.where(flip, b, a), np.where(flip, a, b)
+    rev = rs.choice(a.size, a.size // 20, replace=False)
+    rep = rs.choice(a.size, a.size // 50, replace=False)
+    loops = rs.choice(n, 12, replace=False)
+    raw = np.stack([np.concatenate([a, b[rev], a[rep], loops]), np.concatenate([b, a[rev], b[rep], loops])])
+    path = str(tmp_path / (env.lower() + ext))
+    if ext == ".txt":
+        np.savetxt(path, raw.T, fmt="%d")
+    else:
+        np.savez(path, edge_index=raw)
+    return path
+
+
 @pytest.mark.parametrize("env,o_v", [("RLAP_CORA_EDGES", "random"), ("RLAP_ARXIV_EDGES", "coarsen")])
-def test_real_datasets_if_present(ops, env, o_v):
-    """BASELINE configs 2 (Cora) and 4 (ogbn-arxiv): the datasets are not in the image; point the environment variable
-    at an edge list (.npy/.npz/.txt, either orientation) to run them.  The BA stand-ins above cover the same modes."""
+def test_real_datasets_if_present(ops, env, o_v, tmp_path):
+    """BASELINE configs 2 (Cora) and 4 (ogbn-arxiv): point the environment variable at the dataset's edge list
+    (.npy/.npz/.txt, either orientation) to run it; without one the same path runs on a seeded stand-in file."""
     path = os.environ.get(env)
     if not path or not os.path.exists(path):
-        pytest.skip(f"{env} not set: dataset absent from this image")
+        path = _write_raw_standin(tmp_path, env)
     from util import symmetrize
     raw = _load_edge_list(path)
     keep = raw[0] != raw[1]
