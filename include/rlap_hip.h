@@ -149,6 +149,27 @@ int rlap_approx_chol_batched(rlap_handle h, const int64_t* d_row, const int64_t*
                              const int64_t* d_perm, uint64_t shuffle_seed, double* d_out, int64_t out_cap_rows,
                              int64_t* h_out_row_ptr, rlap_stats* h_stats);
 
+/* Views: K independent Schur complements of one input (a single graph, G = 1, or a batch of G graphs given by h_node_ptr as
+ * for rlap_approx_chol_batched) in one call -- what graph-contrastive training asks for at every step (two or more views).
+ * (view k, graph g) equals graph k*G + g of rlap_approx_chol_batched on the K-fold disjoint union of the input, with the same
+ * shuffle_seed, ids shifted back: by the batched contract that is rlap_approx_chol on graph g with shuffle_seed + k*G + g and
+ * perm slice (k, g).  K = 1, G = 1 is rlap_approx_chol.  Holds in both rng modes (rlap_set_rng_mode).
+ *   h_num_remove : [K*G], view-major: num_remove of (view k, graph g) at k*G + g
+ *   d_perm       : o_v=random only, [K*N] (N = h_node_ptr[G]) or NULL: at k*N + node_ptr[g], a permutation of graph g's LOCAL ids
+ *   d_out        : rows grouped view-major (all graphs of view 0, then view 1, ...), node ids in the INPUT's id space [0, N)
+ *   h_out_ptr    : [K*G+1] row offsets of (view k, graph g) at k*G + g
+ *   h_stats      : of the union: counts summed over views (n_draws: max over views and graphs)
+ * The input is read, sorted, symmetry-checked and linked once (an asymmetric input fails once, RLAP_E_NOT_SYMMETRIC); its CSR is
+ * then replicated K times on the device.  Note: in mode "exact", o_v = degree with o_n = asc / desc draws nothing that depends on
+ * the seed (the reference's default-seeded std::mt19937_64, preconditioner.cc:356), so two views with equal num_remove are equal;
+ * mode "frontier" gives distinct samples.
+ * Workspace: as a batched call on the union, rlap_workspace_query(h, K*E, K*N, K*G, 0, ...).
+ * K < 1: RLAP_E_BAD_ARG; K*N, K*E and K*G are subject to the limits of a batched call of that size (RLAP_E_TOO_LARGE). */
+int rlap_approx_chol_views(rlap_handle h, const int64_t* d_row, const int64_t* d_col, const double* d_w, int64_t E,
+                           int64_t G, const int64_t* h_node_ptr, int64_t K, const int64_t* h_num_remove, int o_v, int o_n,
+                           const int64_t* d_perm, uint64_t shuffle_seed, double* d_out, int64_t out_cap_rows, int64_t* h_out_ptr,
+                           rlap_stats* h_stats);
+
 /* The op with the step BEFORE the path fused in (scripts/node_shared.py:326-327,
  * scripts/augmentor_benchmarks.py:77-78):
  *   symmetrize != 0 : the input holds every undirected edge in one or both directions; (b,a) is

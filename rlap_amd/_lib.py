@@ -18,7 +18,7 @@ EXPORTS = [
     "rlap_rng_uniforms", "rlap_util_ba_graph", "rlap_debug_wave_sort",
     "rlap_approx_chol_from_edges", "rlap_debug_set_limits", "rlap_pack_rows", "rlap_unpack_rows",
     "rlap_workspace_bytes", "rlap_workspace_query", "rlap_set_workspace", "rlap_workspace_needed", "rlap_debug_set_poison", "rlap_debug_set_jitter",
-    "rlap_set_rng_mode",
+    "rlap_set_rng_mode", "rlap_approx_chol_views",
 ]
 
 E_WORKSPACE = 11   # RLAP_E_WORKSPACE
@@ -69,6 +69,9 @@ def load():
     lib.rlap_approx_chol_batched.restype = ci
     lib.rlap_approx_chol_batched.argtypes = [vp, vp, vp, vp, i64, i64, vp, vp, ci, ci, vp, u64, vp, i64, vp,
                                              ctypes.POINTER(Stats)]
+    lib.rlap_approx_chol_views.restype = ci
+    lib.rlap_approx_chol_views.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, vp, ci, ci, vp, u64, vp, i64, vp,
+                                           ctypes.POINTER(Stats)]
     lib.rlap_approx_chol_from_edges.restype = ci
     lib.rlap_approx_chol_from_edges.argtypes = [vp, vp, vp, vp, i64, i64, i64, ctypes.c_double, ci, ci, ci, vp, u64, vp, i64,
                                                 ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(Stats)]

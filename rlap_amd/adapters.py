@@ -3,6 +3,8 @@
 Mirrors of the reference's L2 adapters that keep everything on the GPU:
   * `rLap`     -- PyGCL-style augmentor, scripts/augmentor_benchmarks.py:68-96
   * `rLapDGL`  -- DGL-style augmentor, CCA-SSG/aug.py:33-63
+  * `rLapViews` -- K rLap views of one graph from one library call, with PyGCL-style
+                  siblings for the `(aug1, aug2)` pair of scripts/node_shared.py:488-498
 PyGCL / DGL are optional: with them installed the classes return their graph types,
 without them a small named tuple with the same fields.
 """
@@ -55,6 +57,79 @@ class rLap:
             return A.Graph(x=x, edge_index=sampled_edge_index, edge_weights=w)
         except Exception:
             return Graph(x, sampled_edge_index, w)
+
+    def __call__(self, x, edge_index, edge_weight=None):
+        return self.augment(Graph(x, edge_index, edge_weight))
+
+
+def _as_graph(x, edge_index, w):
+    try:  # PyGCL present: return its Graph type
+        import GCL.augmentors as A  # type: ignore
+        return A.Graph(x=x, edge_index=edge_index, edge_weights=w)
+    except Exception:
+        return Graph(x, edge_index, w)
+
+
+class rLapViews:
+    """K views of a graph from ONE call of ops.approximate_cholesky_views (setup once, K eliminations side by side).
+
+    View k removes int(fracs[k] * num_nodes) vertices, num_nodes = edge_index.max() + 1 (scripts/augmentor_benchmarks.py:77-78).
+    `.augment(g)` returns the list of K graphs.  `.augmentors()` returns K PyGCL-style callables that fit the `(aug1, aug2)` tuple
+    of the training scripts unchanged: the first one called on an input makes the one call, the others then take their views.
+    """
+
+    def __init__(self, fracs=(0.5, 0.5), o_v: str = "random", o_n: str = "asc", keep_weights: bool = False, seed: Optional[int] = None,
+                 mode: str = "exact"):
+        self.fracs = tuple(float(f) for f in fracs)
+        assert len(self.fracs) >= 1
+        self.o_v, self.o_n, self.keep_weights, self.seed, self.mode = o_v, o_n, keep_weights, seed, mode
+        self._pending = None   # (input key, list of K graphs, list of views not yet handed out)
+
+    def augment(self, g):
+        x, edge_index, edge_weights = g.unfold() if hasattr(g, "unfold") else g
+        num_nodes = int(edge_index.max().item()) + 1 if edge_index.numel() else 0
+        self.num_remove = [int(f * num_nodes) for f in self.fracs]
+        sc, ptr = ops.approximate_cholesky_views(edge_index, edge_weights, num_nodes, self.num_remove, self.o_v, self.o_n,
+                                                 seed=self.seed, return_device="same", mode=self.mode)
+        out = []
+        for k in range(len(self.fracs)):
+            part = sc[int(ptr[k]):int(ptr[k + 1])]
+            ei = part[:, :2].long().t().contiguous()
+            out.append(_as_graph(x, ei, part[:, 2].contiguous() if self.keep_weights else None))
+        return out
+
+    @staticmethod
+    def _key(edge_index):
+        return (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), str(edge_index.device))
+
+    def _view(self, k, g):
+        """View k of input g: taken from the pending call when that call was made on this very input and view k has not been
+        handed out yet; otherwise a fresh call (whose other views are then pending)."""
+        edge_index = g.unfold()[1] if hasattr(g, "unfold") else g[1]
+        key = self._key(edge_index)
+        p = self._pending
+        if p is None or p[0] != key or k not in p[2]:
+            graphs = self.augment(g)
+            # (the input is held while views are pending: its memory cannot be reused by another tensor with the same key)
+            p = self._pending = (key, graphs, set(range(len(graphs))), edge_index)
+        p[2].discard(k)
+        res = p[1][k]
+        if not p[2]:
+            self._pending = None
+        return res
+
+    def augmentors(self):
+        return [_ViewAugmentor(self, k) for k in range(len(self.fracs))]
+
+
+class _ViewAugmentor:
+    """One sibling of rLapViews.augmentors(): `aug(x, edge_index, edge_weight)` or `aug.augment(g)`."""
+
+    def __init__(self, parent: rLapViews, k: int):
+        self.parent, self.k = parent, k
+
+    def augment(self, g):
+        return self.parent._view(self.k, g)
 
     def __call__(self, x, edge_index, edge_weight=None):
         return self.augment(Graph(x, edge_index, edge_weight))

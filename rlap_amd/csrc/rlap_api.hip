@@ -325,6 +325,7 @@ struct Call {
     int o_v, o_n; const int64_t* d_perm; uint64_t seed;
     double* d_out; int64_t out_cap; int64_t* h_out_row_ptr; rlap_stats* st;
     int symmetrize;
+    int64_t K = 1;   // views (rlap_approx_chol_views): h_node_ptr / h_t describe the K-fold union, the device input is ONE copy of it
 };
 
 // One attempt.  No host synchronisation until the single read-back at the end: every size is an upper bound
@@ -337,7 +338,11 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need)
     const int64_t N = c.h_node_ptr[G];
     if (c.h_node_ptr[0] != 0) return RLAP_E_BAD_ARG;
     for (int64_t g = 0; g < G; ++g) if (c.h_node_ptr[g + 1] < c.h_node_ptr[g]) return RLAP_E_BAD_ARG;
-    const int64_t Eeff = c.symmetrize ? 2 * E : E;
+    // A views call is the batch of K copies of the input (G1 graphs, N1 vertices, E1eff entries): the COO -> CSR setup runs on the
+    // one copy the caller gave, k_views_replicate then writes the union's CSR; everything after it sees the K * G1-graph batch.
+    const int64_t K = c.K, G1 = G / K, N1 = N / K;
+    const int64_t E1eff = c.symmetrize ? 2 * E : E;
+    const int64_t Eeff = K * E1eff;
     if (N >= (int64_t)1 << 30 || Eeff >= (int64_t)1 << 31 || G >= (int64_t)1 << 30) return RLAP_E_TOO_LARGE;
     if (h->timing) HIPCHK(hipEventRecord(h->ev[0], s));
 
@@ -442,13 +447,13 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need)
     }
     if (G > 1) hipLaunchKernelGGL(k_vertex_graph, dim3(nblk(N, 256)), dim3(256), 0, s, W.node_ptr_d.as<int64_t>(), (int)G, W.vgraph.as<int32_t>(), N);
 
-    const int kbits = (int)bits_for((uint64_t)(N > 1 ? N - 1 : 1));
+    const int kbits = (int)bits_for((uint64_t)(N1 > 1 ? N1 - 1 : 1));
     bool swapped = false;   // the input was in (row, col) order and is read transposed (same matrix when it is exactly symmetric)
     uint64_t* keys_sorted = W.keys1.as<uint64_t>();
     uint32_t* idx_sorted = W.idx1.as<uint32_t>();
     uint32_t* rowid = W.idx0.as<uint32_t>();   // dense row ids of the slots (key of the twin sort); a buffer the COO sort has left free
-    if (Eeff > 0) {
-        hipLaunchKernelGGL(k_edge_keys, dim3(nblk(Eeff, 256)), dim3(256), 0, s, c.d_row, c.d_col, c.d_w, E, N, G > 1 ? W.vgraph.as<int32_t>() : (const int32_t*)nullptr,
+    if (E1eff > 0) {
+        hipLaunchKernelGGL(k_edge_keys, dim3(nblk(E1eff, 256)), dim3(256), 0, s, c.d_row, c.d_col, c.d_w, E, N1, G1 > 1 ? W.vgraph.as<int32_t>() : (const int32_t*)nullptr,
                            c.symmetrize, kbits, W.keys0.as<uint64_t>(), W.idx0.as<uint32_t>(), flags);
         // Large inputs: one early look at the order flags (the call's only other host synchronisation) -- a COO that is sorted by
         // (col, row) needs no sort, one sorted by (row, col) (PyG coalesce) is read transposed and needs none either; exact symmetry,
@@ -456,13 +461,13 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need)
         bool skip_sort = false;
         int64_t skip_min = SORT_SKIP_MIN;
         if (const char* e = std::getenv("RLAP_SORT_SKIP_MIN")) skip_min = std::atoll(e);   // (tests: exercise the order check on small inputs)
-        if (Eeff >= skip_min && !c.symmetrize && !h->force_sort) {
+        if (E1eff >= skip_min && !c.symmetrize && !h->force_sort) {
             int32_t fl[FLAG_COUNT];
             HIPCHK(hipMemcpyAsync(fl, flags, sizeof(fl), hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
             if (!fl[FLAG_UNSORTED_CR]) skip_sort = true;
             else if (!fl[FLAG_UNSORTED_RC] && !fl[FLAG_RANGE]) {
-                hipLaunchKernelGGL(k_edge_keys, dim3(nblk(Eeff, 256)), dim3(256), 0, s, c.d_col, c.d_row, c.d_w, E, N, G > 1 ? W.vgraph.as<int32_t>() : (const int32_t*)nullptr,
+                hipLaunchKernelGGL(k_edge_keys, dim3(nblk(E1eff, 256)), dim3(256), 0, s, c.d_col, c.d_row, c.d_w, E, N1, G1 > 1 ? W.vgraph.as<int32_t>() : (const int32_t*)nullptr,
                                    0, kbits, W.keys0.as<uint64_t>(), W.idx0.as<uint32_t>(), flags);
                 skip_sort = true; swapped = true;
             }
@@ -473,34 +478,38 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need)
             rowid = W.idx1.as<uint32_t>();
         } else {
             // keys are (col << kbits | row) with ids < N, or all ones for dropped entries (bit 2 * kbits makes these sort last)
-            int rc = sort_pairs(h, ST, W.keys0.as<uint64_t>(), W.keys1.as<uint64_t>(), W.idx0.as<uint32_t>(), W.idx1.as<uint32_t>(), Eeff, 0,
+            int rc = sort_pairs(h, ST, W.keys0.as<uint64_t>(), W.keys1.as<uint64_t>(), W.idx0.as<uint32_t>(), W.idx1.as<uint32_t>(), E1eff, 0,
                                 (unsigned)std::min(64, 2 * kbits + 1));
             if (rc) return rc;
         }
-        { Fills F2; F2.add(rowid, Eeff, (int32_t)N); F2.launch(s); }   // dense row-id array: slots beyond nnz hold N (sorts last)
-        hipLaunchKernelGGL(k_heads, dim3(nblk(Eeff + 1, 256)), dim3(256), 0, s, keys_sorted, Eeff, W.head.as<int32_t>());
-        int rc = excl_scan(h, ST, W.head.as<int32_t>(), W.pos.as<int32_t>(), Eeff + 1);
+        { Fills F2; F2.add(rowid, E1eff, (int32_t)N1); F2.launch(s); }   // dense row-id array: slots beyond nnz hold N1 (sorts last)
+        hipLaunchKernelGGL(k_heads, dim3(nblk(E1eff + 1, 256)), dim3(256), 0, s, keys_sorted, E1eff, W.head.as<int32_t>());
+        int rc = excl_scan(h, ST, W.head.as<int32_t>(), W.pos.as<int32_t>(), E1eff + 1);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_fill_csr, dim3(nblk(Eeff, 256)), dim3(256), 0, s, keys_sorted, idx_sorted, W.head.as<int32_t>(),
-                           W.pos.as<int32_t>(), c.d_w, Eeff, (c.symmetrize && !c.d_w) ? 1 : 0, kbits, W.ent.as<Slot>(), W.slot_col.as<int32_t>(),
+        hipLaunchKernelGGL(k_fill_csr, dim3(nblk(E1eff, 256)), dim3(256), 0, s, keys_sorted, idx_sorted, W.head.as<int32_t>(),
+                           W.pos.as<int32_t>(), c.d_w, E1eff, (c.symmetrize && !c.d_w) ? 1 : 0, kbits, W.ent.as<Slot>(), W.slot_col.as<int32_t>(),
                            reinterpret_cast<int32_t*>(rowid));
     }
-    // (nnz = pos[Eeff]: k_colptr reads it there and files it in the scalar block and as the pool's first free slot)
-    hipLaunchKernelGGL(k_colptr, dim3(nblk(N + 1, 256)), dim3(256), 0, s, W.slot_col.as<int32_t>(), Eeff > 0 ? W.pos.as<int32_t>() + Eeff : (const int32_t*)&SC->pad, (int32_t)N,   // (no entries: a zeroed word of its own, not the output word -- both are __restrict__)
+    // (nnz = pos[E1eff]: k_colptr reads it there and files it in the scalar block and as the pool's first free slot)
+    const int32_t* nnz_src = E1eff > 0 ? W.pos.as<int32_t>() + E1eff : (const int32_t*)&SC->pad;   // (no entries: a zeroed word of its own, not the output word -- both are __restrict__)
+    hipLaunchKernelGGL(k_colptr, dim3(nblk(N1 + 1, 256)), dim3(256), 0, s, W.slot_col.as<int32_t>(), nnz_src, (int32_t)N1,
                        W.colptr.as<int32_t>(), nnz_p, W.pool_top.as<int32_t>());
-    if (Eeff > 0) {
+    if (E1eff > 0) {
         // twins: stable sort of the slots by row id (keys0 is free again: sorted keys in its first half, the slot order T in its second)
         uint32_t* skeys = W.keys0.as<uint32_t>();
         uint32_t* T = skeys + Eeff;
         rocprim::counting_iterator<uint32_t> iota(0u);
         size_t bytes = 0;
-        HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, rowid, skeys, iota, T, (size_t)Eeff, 0u, (unsigned)std::min(32, kbits + 1), s));
+        HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, rowid, skeys, iota, T, (size_t)E1eff, 0u, (unsigned)std::min(32, kbits + 1), s));
         if (bytes > ST.bytes) return RLAP_E_INTERNAL;
         bytes = ST.bytes;
-        HIPCHK(rocprim::radix_sort_pairs(ST.p, bytes, rowid, skeys, iota, T, (size_t)Eeff, 0u, (unsigned)std::min(32, kbits + 1), s));
-        hipLaunchKernelGGL(k_twin_sorted, dim3((unsigned)std::min<int64_t>(nblk(Eeff, 256), 4096)), dim3(256), 0, s, W.ent.as<Slot>(), T, nnz_p, acc);
-        hipLaunchKernelGGL(k_twin_store, dim3((unsigned)std::min<int64_t>(nblk(Eeff, 256), 4096)), dim3(256), 0, s, W.ent.as<Slot>(), T, nnz_p);
+        HIPCHK(rocprim::radix_sort_pairs(ST.p, bytes, rowid, skeys, iota, T, (size_t)E1eff, 0u, (unsigned)std::min(32, kbits + 1), s));
+        hipLaunchKernelGGL(k_twin_sorted, dim3((unsigned)std::min<int64_t>(nblk(E1eff, 256), 4096)), dim3(256), 0, s, W.ent.as<Slot>(), T, nnz_p, acc);
+        hipLaunchKernelGGL(k_twin_store, dim3((unsigned)std::min<int64_t>(nblk(E1eff, 256), 4096)), dim3(256), 0, s, W.ent.as<Slot>(), T, nnz_p);
     }
+    if (K > 1)   // the union's CSR: copy k of every slot, column start and slot column, shifted by k * nnz / k * N1 (nnz read on the device)
+        hipLaunchKernelGGL(k_views_replicate, dim3((unsigned)std::min<int64_t>(nblk(E1eff, 256), 2048)), dim3(256), 0, s, W.ent.as<Slot>(),
+                           W.slot_col.as<int32_t>(), W.colptr.as<int32_t>(), nnz_src, (int32_t)N1, (int32_t)K, nnz_p, W.pool_top.as<int32_t>());
     // per-graph scratch of the long-column fall-backs (needs the per-graph nnz: filled on the device)
     hipLaunchKernelGGL(k_gd_scratch, dim3(1), dim3(256), 0, s, W.colptr.as<int32_t>(), W.node_ptr_d.as<int64_t>(), (int32_t)G, W.gd_d.as<GraphDesc>());
 
@@ -660,7 +669,7 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need)
         const int64_t rows_ub = std::min<int64_t>(c.out_cap, slot_cap);
         unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows_ub + 255) / 256, 256 * 8));
         hipLaunchKernelGGL(k_sc_compact, dim3(grid), dim3(256), 0, s, order, W.cnt.as<int32_t>(), W.row_off.as<int64_t>(), W.tmp_off.as<int64_t>(),
-                           W.tmp_nbr.as<int32_t>(), W.tmp_val.as<double>(), (int32_t)S, c.d_out, c.out_cap);
+                           W.tmp_nbr.as<int32_t>(), W.tmp_val.as<double>(), (int32_t)S, c.d_out, c.out_cap, K > 1 ? (int32_t)N1 : 0);
         HIPCHK(hipGetLastError());
     }
     if (h->timing) HIPCHK(hipEventRecord(h->ev[6], s));
@@ -948,6 +957,28 @@ int rlap_approx_chol_batched(rlap_handle h, const int64_t* d_row, const int64_t*
     if (E > 0 && (!d_row || !d_col)) return RLAP_E_BAD_ARG;
     if (out_cap_rows > 0 && !d_out) return RLAP_E_BAD_ARG;
     Call c{d_row, d_col, d_w, E, G, h_node_ptr, h_num_remove, o_v, o_n, d_perm, shuffle_seed, d_out, out_cap_rows, h_out_row_ptr, h_stats, 0};
+    return run_call(h, c);
+}
+
+int rlap_approx_chol_views(rlap_handle h, const int64_t* d_row, const int64_t* d_col, const double* d_w, int64_t E, int64_t G,
+                           const int64_t* h_node_ptr, int64_t K, const int64_t* h_num_remove, int o_v, int o_n, const int64_t* d_perm,
+                           uint64_t shuffle_seed, double* d_out, int64_t out_cap_rows, int64_t* h_out_ptr, rlap_stats* h_stats) {
+    if (!h || G < 1 || K < 1 || E < 0 || !h_node_ptr || !h_num_remove || !h_out_ptr) return RLAP_E_BAD_ARG;
+    if (o_v < 0 || o_v > 2 || o_n < 0 || o_n > 2) return RLAP_E_BAD_ARG;
+    if (E > 0 && (!d_row || !d_col)) return RLAP_E_BAD_ARG;
+    if (out_cap_rows > 0 && !d_out) return RLAP_E_BAD_ARG;
+    if (h_node_ptr[0] != 0) return RLAP_E_BAD_ARG;
+    for (int64_t g = 0; g < G; ++g) if (h_node_ptr[g + 1] < h_node_ptr[g]) return RLAP_E_BAD_ARG;
+    const int64_t N = h_node_ptr[G];
+    // the union's sizes must respect the limits of a batched call of that size (run_once checks K * E and the slot ids)
+    if (K >= (int64_t)1 << 30 || G >= (int64_t)1 << 30 || K * G >= (int64_t)1 << 30 || (N > 0 && K >= ((int64_t)1 << 30) / N)) return RLAP_E_TOO_LARGE;
+    if (K * (E > 0 ? E : 1) >= (int64_t)1 << 31) return RLAP_E_TOO_LARGE;
+    // graph k * G + g of the union: ids [k * N + node_ptr[g], k * N + node_ptr[g + 1]), num_remove h_num_remove[k * G + g]
+    std::vector<int64_t> np((size_t)(K * G + 1));
+    for (int64_t k = 0; k < K; ++k)
+        for (int64_t g = 0; g < G; ++g) np[(size_t)(k * G + g)] = k * N + h_node_ptr[g];
+    np[(size_t)(K * G)] = K * N;
+    Call c{d_row, d_col, d_w, E, K * G, np.data(), h_num_remove, o_v, o_n, d_perm, shuffle_seed, d_out, out_cap_rows, h_out_ptr, h_stats, 0, K};
     return run_call(h, c);
 }
 

@@ -104,6 +104,8 @@ __global__ void k_fill_csr(const uint64_t* keys, const uint32_t* idx, const int3
                            int64_t E, int set_semantics, int kbits, Slot* ent, int32_t* slot_col, int32_t* nbr32);
 __global__ void k_twin_sorted(const Slot* ent, const uint32_t* T, const int32_t* nnz_p, double* acc);
 __global__ void k_twin_store(Slot* ent, const uint32_t* T, const int32_t* nnz_p);
+__global__ void k_views_replicate(Slot* ent, int32_t* slot_col, int32_t* colptr, const int32_t* nnz_src, int32_t N, int32_t K,
+                                  int32_t* nnz_out, int32_t* pool_top_out);
 __global__ void k_colptr(const int32_t* slot_col, const int32_t* nnz_p, int32_t N, int32_t* colptr, int32_t* nnz_out, int32_t* pool_top_out);
 __global__ void k_pq_init(const int32_t* colptr, const int32_t* vgraph, int32_t N, VRec* vr, uint64_t* skey, uint32_t* sval);
 __global__ void k_bucket_bounds(const uint32_t* order, const VRec* vr, const int32_t* vgraph, const GraphDesc* gd, int32_t N,
@@ -162,7 +164,7 @@ __global__ void k_sc_merge_huge(Arrays A, const GraphDesc* gd, const int32_t* vg
                                 int32_t* tmp_nbr, double* tmp_val, int32_t* cnt_out, unsigned long long* live_total, uint16_t* lists, SRec* scratch,
                                 unsigned long long* scratch_top, int64_t scratch_cap, int32_t* flags);
 __global__ void k_sc_compact(const uint32_t* order, const int32_t* cnt, const int64_t* row_off, const int64_t* tmp_off,
-                             const int32_t* tmp_nbr, const double* tmp_val, int32_t S, double* out, int64_t out_cap);
+                             const int32_t* tmp_nbr, const double* tmp_val, int32_t S, double* out, int64_t out_cap, int32_t id_mod);
 __global__ void k_graph_rows(const int64_t* surv_base, const int64_t* row_off, int32_t G, int64_t* out_ptr);
 
 }  // namespace rlap

@@ -346,6 +346,33 @@ __global__ void k_twin_store(Slot* __restrict__ ent, const uint32_t* __restrict_
     for (int32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < nnz; p += gridDim.x * blockDim.x) ent[p].twin = (int32_t)T[p];
 }
 
+// Views (rlap_approx_chol_views): the CSR of the K-fold disjoint union of the input is the input's CSR shifted by view --
+// columns are sorted by global id and rows within a column too, so copy k's slots come after copy k-1's, in the same order,
+// with the same twin links.  The setup ran on copy 0; this writes copies 1..K-1 of every slot (16-byte records), slot column
+// and column start, and sets the entry count and the append pool's first free slot to K * nnz.  A streaming copy: each source
+// element is read once and stored K-1 times, grid-stride, no LDS.  Reads [0, nnz) / [0, N) and writes [nnz, K nnz) / [N, K N].
+__global__ __launch_bounds__(256) void k_views_replicate(Slot* ent, int32_t* slot_col, int32_t* colptr, const int32_t* __restrict__ nnz_src,
+                                                         int32_t N, int32_t K, int32_t* __restrict__ nnz_out, int32_t* __restrict__ pool_top_out) {
+    const int32_t nnz = *nnz_src;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    if (tid == 0) { const int32_t z = K * nnz; *nnz_out = z; *pool_top_out = z; colptr[(int64_t)K * N] = z; }
+    uint4* e4 = reinterpret_cast<uint4*>(ent);   // Slot = {double val; int32 nbr; int32 twin}: words x,y = val, z = nbr, w = twin
+    for (int64_t p = tid; p < nnz; p += stride) {
+        uint4 v = e4[p];
+        const uint32_t nbr = v.z, twin = v.w;
+        const int32_t c = slot_col[p];
+        for (int32_t k = 1; k < K; ++k) {
+            v.z = nbr + (uint32_t)(k * N); v.w = twin + (uint32_t)(k * nnz);
+            e4[(int64_t)k * nnz + p] = v;
+            slot_col[(int64_t)k * nnz + p] = c + k * N;
+        }
+    }
+    for (int64_t v = tid; v < N; v += stride) {
+        const int32_t c0 = colptr[v];
+        for (int32_t k = 1; k < K; ++k) colptr[(int64_t)k * N + v] = c0 + k * nnz;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // K4: PQ init.  Keys = degree; never-moved vertices of a bucket are listed in
 // descending id (= LIFO order after ascending insertion, :137-157).
@@ -3867,11 +3894,12 @@ __global__ __launch_bounds__(64) void k_sc_merge_huge(Arrays A, const GraphDesc*
 // contiguous run of tiles per wave), so lanes stay busy whatever the column lengths are; the
 // owner of each row is found in the tile's window of row_off by a 6-step search over lane
 // registers, and the 64x3 doubles are staged through LDS so that every store is a contiguous
-// 512-byte wave store.
+// 512-byte wave store.  id_mod > 0 (views call): view k's global ids [k N, (k+1) N) go back to the input's [0, N) (N = id_mod);
+// 0 = ids as they are.
 __global__ __launch_bounds__(256) void k_sc_compact(const uint32_t* __restrict__ order, const int32_t* __restrict__ cnt,
                                                     const int64_t* __restrict__ row_off, const int64_t* __restrict__ tmp_off,
                                                     const int32_t* __restrict__ tmp_nbr, const double* __restrict__ tmp_val,
-                                                    int32_t S, double* __restrict__ out, int64_t out_cap) {
+                                                    int32_t S, double* __restrict__ out, int64_t out_cap, int32_t id_mod) {
     (void)cnt;
     __shared__ double stage[4][192];
     const int lane = threadIdx.x & 63;
@@ -3925,8 +3953,14 @@ __global__ __launch_bounds__(256) void k_sc_compact(const uint32_t* __restrict__
         double f0 = 0, f1 = 0, f2 = 0;
         if (valid) {
             const int64_t src = tmp_off[owner] + (r - obase);
-            f0 = (double)tmp_nbr[src];
-            f1 = (double)order[owner];
+            int32_t a = tmp_nbr[src];
+            uint32_t b = order[owner];
+            if (id_mod > 0) {   // (edges never cross views: the owner's view is the neighbour's, one division per row)
+                const uint32_t sh = (b / (uint32_t)id_mod) * (uint32_t)id_mod;
+                a -= (int32_t)sh; b -= sh;
+            }
+            f0 = (double)a;
+            f1 = (double)b;
             f2 = tmp_val[src];
         }
         double* st = stage[wv];

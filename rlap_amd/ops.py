@@ -382,6 +382,80 @@ def approximate_cholesky_batched(
     return res, row_ptr
 
 
+def approximate_cholesky_views(
+    edge_index: Tensor,
+    edge_weights: Optional[Tensor],
+    num_nodes: int,
+    num_remove: Union[int, Tensor, Sequence[int], Sequence[Sequence[int]]],
+    o_v: str,
+    o_n: str,
+    *,
+    node_ptr: Optional[Union[Tensor, Sequence[int]]] = None,
+    perm: Optional[Tensor] = None,
+    seed: Optional[int] = None,
+    return_device: Optional[Union[str, torch.device]] = None,
+    mode: str = "exact",
+) -> Tuple[Tensor, Tensor]:
+    """K independent Schur complements ("views") of one input in one call -- the two augmentations of a graph-contrastive
+    training step (scripts/node_shared.py:260-262) without K setups.
+
+    The input is one graph of `num_nodes` vertices, or with `node_ptr` a batch of G graphs as in approximate_cholesky_batched
+    (then `num_nodes` must equal node_ptr[-1]).  `num_remove` gives K: an int is K = 1, a length-K sequence one value per view
+    (every graph of the view), a (K, G) tensor or nested sequence one value per (view, graph).
+    Returns (sc_edge_info, ptr[K*G+1]): rows grouped view-major (all graphs of view 0, then view 1, ...), node ids in the
+    INPUT's id space.  (view k, graph g) equals `approximate_cholesky(graph g, ..., perm=perm slice (k, g), seed=seed + k*G + g)`
+    -- graph k*G + g of approximate_cholesky_batched on the K-fold disjoint union, ids shifted back.  `perm` (o_v="random") holds
+    K*N entries: per view, per graph, a permutation of local ids.
+
+    In mode "exact", o_v="degree" with o_n "asc" or "desc" draws no seeded randomness (the reference uses a default-seeded
+    std::mt19937_64, preconditioner.cc:356), so two views with equal num_remove are identical -- as in the reference.
+    mode="frontier" gives distinct samples.
+    """
+    assert edge_index.shape[0] == 2
+    assert o_v in ["random", "degree", "coarsen"]
+    assert o_n in ["asc", "desc", "random"]
+    global last_stats
+    n = int(num_nodes)
+    np_ = torch.as_tensor([0, n] if node_ptr is None else node_ptr, dtype=torch.int64).cpu().contiguous()
+    G = np_.numel() - 1
+    assert G >= 1 and int(np_[-1]) == n, "node_ptr[-1] must equal num_nodes"
+    nr_ = torch.as_tensor(num_remove, dtype=torch.int64).cpu()
+    if nr_.dim() == 0:
+        nr_ = nr_.reshape(1, 1).expand(1, G)
+    elif nr_.dim() == 1:
+        nr_ = nr_.reshape(-1, 1).expand(nr_.numel(), G)
+    assert nr_.dim() == 2 and nr_.shape[1] == G and nr_.shape[0] >= 1, "num_remove: an int, K values, or (K, G)"
+    K = int(nr_.shape[0])
+    nr_ = nr_.contiguous()
+    dev = _device_for(edge_index)
+    lib, hobj = _handle_obj(dev)
+    h = hobj.ptr
+    _set_mode(lib, h, mode)
+    with torch.cuda.device(dev):
+        row, col, w, E = _prep_edges(edge_index, edge_weights, dev)
+        d_perm = None
+        if o_v == "random" and perm is not None:
+            d_perm = perm.to(device=dev, dtype=torch.int64).contiguous()
+            assert d_perm.numel() == K * n, "perm must hold K * num_nodes entries"
+        shuffle_seed = _seed_from(seed) if (o_n == "random" or o_v != "degree" or mode == "frontier") else 0
+        out = torch.empty((max(K * E, 1), 3), dtype=torch.float64, device=dev)
+        ptr = torch.zeros(K * G + 1, dtype=torch.int64)
+        st = _lib.Stats()
+        # the arena of a batched call on the K-fold union (include/rlap_hip.h)
+        rc = _run(hobj, dev, K * E, K * n, K * G, False, lambda: lib.rlap_approx_chol_views(
+            h, row.data_ptr(), col.data_ptr(), w.data_ptr() if w is not None else None, E, G,
+            np_.data_ptr(), K, nr_.data_ptr(), O_V[o_v], O_N[o_n],
+            d_perm.data_ptr() if d_perm is not None else None, shuffle_seed,
+            out.data_ptr(), out.shape[0], ptr.data_ptr(), ctypes.byref(st)), st)
+        if rc != 0:
+            _raise(rc)
+        last_stats = st.as_dict()
+        res = _trim(out, int(ptr[-1]))
+    if return_device is not None and return_device != "same":
+        res = res.to(return_device)
+    return res, ptr
+
+
 def identity(a: Tensor) -> Tensor:
     """Boundary self-test (reference: rlap/ops.py:61-63): tensor -> column-major
     staging -> tensor, on the GPU; returns a tensor on `a`'s device."""
