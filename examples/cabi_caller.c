@@ -68,8 +68,9 @@ int main(int argc, char** argv) {
     if (!f) { perror(argv[7]); return 5; }
     fwrite(h_out, sizeof(double), 3 * (size_t)rows, f);
     fclose(f);
-    printf("rows=%lld eliminated=%lld draws=%lld workspace=%zu bytes, %lld uniforms, regrown %d times\n", (long long)rows,
-           (long long)st.n_eliminated, (long long)st.n_draws, ws_bytes, (long long)rng_entries, grows);
+    printf("rows=%lld eliminated=%lld draws=%lld workspace=%zu bytes, %lld uniforms, regrown %d times, elimination kernel %d, retry causes %#x\n",
+           (long long)rows, (long long)st.n_eliminated, (long long)st.n_draws, ws_bytes, (long long)rng_entries, grows, (int)st.elim_kernel,
+           (unsigned)st.retry_causes);
 
     CHECK_RLAP(rlap_destroy(h));
     CHECK_HIP(hipFree(d_ws)); CHECK_HIP(hipFree(d_rng)); CHECK_HIP(hipFree(d_row)); CHECK_HIP(hipFree(d_col)); CHECK_HIP(hipFree(d_out));

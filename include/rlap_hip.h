@@ -67,6 +67,14 @@ typedef struct {
     int32_t reserved;     /* COO sort: 0 done, 1 skipped (input in (col,row) order), 2 skipped, input in (row,col) order read transposed */
     int64_t n_rounds;     /* elimination: batch rounds, summed over graphs              */
     int64_t n_singles;    /* elimination: vertices that took the single-vertex path     */
+    /* (appended fields: the offsets above are unchanged) */
+    int32_t elim_kernel;  /* elimination kernel of the final attempt: 0 none ran (t = 0, empty graph), 1 round kernel, 2 dataflow kernel */
+    int32_t retry_causes; /* bit k set: an attempt of the call was repeated for retry kind k (1 append pool, 2 PQ log, 3 uniform table,
+                             4 output-pass scratch, 5 input read transposed was not exactly symmetric, 6 dataflow long-column scratch,
+                             7 dataflow reorder buffer too small, 8 the dataflow kernel gave up); 7 and 8 repeat on the round kernel */
+    int32_t flow_abort;   /* why the dataflow kernel gave up (retry kind 8): 0 it did not, 1 stall watchdog, 2 sorted-index check,
+                             3 appended count over 2^22, 4 column longer than its buffer */
+    int32_t pad;          /* (8-byte alignment) */
 } rlap_stats;
 
 /* Lifetime.  A handle binds to the HIP device current at creation.  It owns a few KB of tables (allocated in
@@ -188,6 +196,11 @@ int rlap_approx_chol_from_edges(rlap_handle h, const int64_t* d_src, const int64
  * PQ-log factor, length of the uniform table the kernels may use, entries of the output pass's long-column
  * scratch.  A call that runs into one of them repeats itself with the regular sizes (rlap_stats.n_retries). */
 int rlap_debug_set_limits(rlap_handle h, double pool_factor, double log_factor, int64_t rng_len, int64_t scratch_entries);
+
+/* Test hook: entries of the dataflow kernel's reorder buffer (the tag order of the surviving columns) for the first attempt of the
+ * next call on this handle (negative = default).  A call whose out-of-order appended entries do not fit repeats itself on the round
+ * kernel (rlap_stats.retry_causes bit 7). */
+int rlap_debug_set_flow_limits(rlap_handle h, int64_t reorder_cap);
 
 /* Debug aid (also: environment RLAP_DEBUG_POISON=<byte> at rlap_create): before every attempt of the next calls the whole
  * workspace arena, the caller's output buffer and the elimination kernel's LDS are filled with `byte` (0..255; negative = off),

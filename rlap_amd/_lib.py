@@ -18,10 +18,17 @@ EXPORTS = [
     "rlap_rng_uniforms", "rlap_util_ba_graph", "rlap_debug_wave_sort",
     "rlap_approx_chol_from_edges", "rlap_debug_set_limits", "rlap_pack_rows", "rlap_unpack_rows",
     "rlap_workspace_bytes", "rlap_workspace_query", "rlap_set_workspace", "rlap_workspace_needed", "rlap_debug_set_poison", "rlap_debug_set_jitter",
-    "rlap_set_rng_mode", "rlap_approx_chol_views",
+    "rlap_set_rng_mode", "rlap_approx_chol_views", "rlap_debug_set_flow_limits",
 ]
 
 E_WORKSPACE = 11   # RLAP_E_WORKSPACE
+
+# rlap_stats.elim_kernel
+KERNEL_NONE, KERNEL_ROUND, KERNEL_FLOW = 0, 1, 2
+# rlap_stats.retry_causes: bit k = retry kind k (include/rlap_hip.h)
+RETRY_POOL, RETRY_LOG, RETRY_RNG, RETRY_SCRATCH, RETRY_SORT, RETRY_FLOW_SCRATCH, RETRY_FLOW_REORDER, RETRY_FLOW_GAVE_UP = (1 << k for k in range(1, 9))
+# rlap_stats.flow_abort
+FLOW_ABORT_REASONS = {0: "none", 1: "stall watchdog", 2: "sorted-index check", 3: "appended count over 2^22", 4: "column longer than its buffer"}
 
 
 class Stats(ctypes.Structure):
@@ -32,6 +39,7 @@ class Stats(ctypes.Structure):
         ("ms_sc_merge", ctypes.c_float), ("ms_sc_compact", ctypes.c_float), ("ms_total", ctypes.c_float),
         ("n_retries", ctypes.c_int32), ("reserved", ctypes.c_int32),
         ("n_rounds", ctypes.c_int64), ("n_singles", ctypes.c_int64),
+        ("elim_kernel", ctypes.c_int32), ("retry_causes", ctypes.c_int32), ("flow_abort", ctypes.c_int32), ("pad", ctypes.c_int32),
     ]
 
     def as_dict(self):
@@ -77,6 +85,8 @@ def load():
                                                 ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(Stats)]
     lib.rlap_debug_set_limits.restype = ci
     lib.rlap_debug_set_limits.argtypes = [vp, ctypes.c_double, ctypes.c_double, i64, i64]
+    lib.rlap_debug_set_flow_limits.restype = ci
+    lib.rlap_debug_set_flow_limits.argtypes = [vp, i64]
     lib.rlap_pack_rows.restype = ci
     lib.rlap_pack_rows.argtypes = [vp, vp, i64, vp]
     lib.rlap_unpack_rows.restype = ci

@@ -90,10 +90,11 @@ struct rlap_handle_s {
     int64_t rng_min = 0;          // lower bound of the uniform table (grown after an overflow)
     int64_t scr_budget = 1 << 18; // output pass: entries of global scratch for columns beyond 8192 slots
     double flow_scr_factor = 1.0; // dataflow elimination: working storage of the long columns (grown after ST_FLOW_SCRATCH)
-    bool flow_off_once = false;   // the next attempt uses the round kernel (set after ST_FLOW_REORDER)
+    bool flow_off_once = false;   // the next attempt uses the round kernel (set after ST_FLOW_REORDER, or after the dataflow kernel gave up)
     int rng_mode = 0;             // 0 the reference's one stream (mode "exact"), 1 counter-based uniforms (mode "frontier", rlap_set_rng_mode)
     // test hooks (rlap_debug_set_limits): tiny first sizes so that the retry path runs
     double dbg_pool = -1.0, dbg_log = -1.0; int64_t dbg_rng = -1, dbg_scr = -1;
+    int64_t dbg_ro_cap = -1;      // (rlap_debug_set_flow_limits) entries of the dataflow reorder buffer, first attempt of the next call only
     int64_t total_retries = 0;
     bool force_sort = false;      // the next attempt sorts the COO whatever order it is in (set when a skipped sort cannot be trusted)
     int jitter = 0;               // RLAP_DEBUG_JITTER=<n>: waves of the elimination kernel sleep n x 0.25 us behind its barriers (a different set each time)
@@ -331,8 +332,8 @@ struct Call {
 // One attempt.  No host synchronisation until the single read-back at the end: every size is an upper bound
 // known on the host (E, N, G); what only the device knows (nnz, row counts, overflows, input checks) is read
 // by the kernels from device memory and reported once.
-int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need) {
-    *retry_kind = 0; *retry_need = 0;
+int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need, int32_t* flow_abort) {
+    *retry_kind = 0; *retry_need = 0; *flow_abort = 0;
     hipStream_t s = h->stream;
     const int64_t G = c.G, E = c.E;
     const int64_t N = c.h_node_ptr[G];
@@ -376,6 +377,7 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need)
     st.n_eliminated = nelim_total;
     Sizes z;
     const bool flow = flow_wanted(h, c.o_v, G, N);
+    st.elim_kernel = nelim_total > 0 ? (flow ? 2 : 1) : 0;
     { int rc = call_sizes(h, Eeff, N, G, bucket_total, S, c.o_v == OV_RANDOM && !c.d_perm, flow, nelim_total, &z); if (rc) return rc; }
     const int64_t slot_cap = z.slot_cap, log_total = z.log_total, scr_total = z.scr_total, scr_budget = z.scr_budget;
     const size_t res_bytes = z.res_bytes;
@@ -622,13 +624,13 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need)
         order = W.sval1.as<uint32_t>();
         if (flow && S > 0 && Eeff > 0) {
             // tag order of the surviving columns: concurrent eliminations pushed into them out of order (rlap_flow.h)
-            const int32_t ro_cap = (int32_t)Eeff;
+            const int32_t ro_cap = (int32_t)(h->dbg_ro_cap >= 0 ? std::max<int64_t>(1, std::min<int64_t>(h->dbg_ro_cap, Eeff)) : Eeff);   // (test hook: smaller)
             launch_flow_ro_count(s, A, FA, order, (int32_t)S, W.f_rocnt.as<int32_t>());
             { int rc = excl_scan(h, ST, W.f_rocnt.as<int32_t>(), W.f_rooff.as<int32_t>(), S + 1); if (rc) return rc; }
             uint32_t* home = reinterpret_cast<uint32_t*>(W.head.p);
             launch_flow_ro_emit(s, A, FA, order, (int32_t)S, W.f_rooff.as<int32_t>(), W.keys0.as<uint64_t>(), W.idx0.as<uint32_t>(), home, ro_cap, &W.gd_d.as<GraphDesc>()[0].status);
             const unsigned kb = bits_for((uint64_t)std::max<int64_t>(S - 1, 1)) + 32u;
-            { int rc = sort_pairs(h, ST, W.keys0.as<uint64_t>(), W.keys1.as<uint64_t>(), W.idx0.as<uint32_t>(), W.idx1.as<uint32_t>(), Eeff, 0, std::min(64u, kb)); if (rc) return rc; }
+            { int rc = sort_pairs(h, ST, W.keys0.as<uint64_t>(), W.keys1.as<uint64_t>(), W.idx0.as<uint32_t>(), W.idx1.as<uint32_t>(), ro_cap, 0, std::min(64u, kb)); if (rc) return rc; }
             launch_flow_ro_permute(s, A, FA, W.f_rooff.as<int32_t>(), (int32_t)S, W.idx1.as<uint32_t>(), W.keys1.as<uint64_t>(), home, ro_cap, reinterpret_cast<Slot*>(W.tmp_val.p));
             HIPCHK(hipGetLastError());
         }
@@ -678,7 +680,7 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need)
     int64_t* out_ptr_d = reinterpret_cast<int64_t*>(res_d + 1);
     hipLaunchKernelGGL(k_graph_rows, dim3(nblk(G + 1, 256)), dim3(256), 0, s, W.surv_base_d.as<int64_t>(), W.row_off.as<int64_t>(), (int32_t)G, out_ptr_d);
     hipLaunchKernelGGL(k_collect, dim3(1), dim3(256), 0, s, flags, acc, nnz_p, counters, live, W.tmp_off.as<int64_t>(), W.row_off.as<int64_t>(), (int32_t)S,
-                       W.gd_d.as<GraphDesc>(), (int32_t)G, W.pool_top.as<int32_t>(), W.bs_pool_top.as<int32_t>(), res_d);
+                       W.gd_d.as<GraphDesc>(), (int32_t)G, W.pool_top.as<int32_t>(), W.bs_pool_top.as<int32_t>(), flow ? W.f_ctrl.as<int32_t>() + FC_REASON : nullptr, res_d);
     HIPCHK(hipMemcpyAsync(h->h_results, W.results.p, res_bytes, hipMemcpyDeviceToHost, s));
     if (h->timing) HIPCHK(hipEventRecord(h->ev[7], s));
     HIPCHK(hipStreamSynchronize(s));
@@ -716,6 +718,7 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need)
     st.n_rounds = R.rounds; st.n_singles = R.singles;
     st.out_rows = R.m_total;
     st.live_entries = R.live_total;
+    if (flow && R.status == ST_INTERNAL) *flow_abort = R.flow_abort;
     if (h->timing) {
         float t = 0;
         (void)hipEventElapsedTime(&t, h->ev[0], h->ev[1]); st.ms_setup = t;
@@ -736,7 +739,7 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need)
         else if (R.status == ST_RNG_OVERFLOW) *retry_kind = 3;
         else if (R.status == ST_FLOW_SCRATCH) *retry_kind = 6;
         else if (R.status == ST_FLOW_REORDER) *retry_kind = 7;
-        else if (R.status == ST_INTERNAL && flow) *retry_kind = 7;   // the dataflow kernel gave up (stall watchdog, index check): once more on the round kernel
+        else if (R.status == ST_INTERNAL && flow) *retry_kind = 8;   // the dataflow kernel gave up (stall watchdog, index check, ...: *flow_abort): once more on the round kernel
         return R.status;
     }
     if (R.flags[FLAG_SCR]) { *retry_kind = 4; *retry_need = R.scr_need; return RLAP_E_INTERNAL; }
@@ -757,10 +760,14 @@ int run_call(rlap_handle h, const Call& c) {
     DeviceGuard dg(h->device);
     int rc = RLAP_E_INTERNAL;
     int retries = 0;
+    int32_t causes = 0, abort_reason = 0;   // (rlap_stats.retry_causes / flow_abort)
     for (int attempt = 0; attempt < 10; ++attempt) {
-        int kind = 0; int64_t need = 0;
-        rc = run_once(h, c, &kind, &need);
+        int kind = 0; int64_t need = 0; int32_t fa = 0;
+        rc = run_once(h, c, &kind, &need, &fa);
+        h->dbg_ro_cap = -1;   // (test hook: the first attempt only)
+        if (fa) abort_reason = fa;
         if (kind == 0) break;
+        causes |= 1 << kind;
         ++retries;
         // a test hook's tiny limit applies to the first attempt only; afterwards the regular growth takes over
         if (kind == 1) { if (h->dbg_pool >= 0) h->dbg_pool = -1.0; else h->pool_factor = h->pool_factor * 2 + 1; }
@@ -769,11 +776,11 @@ int run_call(rlap_handle h, const Call& c) {
         else if (kind == 4) { if (h->dbg_scr >= 0) h->dbg_scr = -1; h->scr_budget = std::max<int64_t>(h->scr_budget, need + 8); }
         else if (kind == 5) h->force_sort = true;
         else if (kind == 6) { if (h->dbg_scr >= 0) h->dbg_scr = -1; else h->flow_scr_factor *= 4; }
-        else if (kind == 7) h->flow_off_once = true;
+        else if (kind == 7 || kind == 8) h->flow_off_once = true;
     }
     h->force_sort = false; h->flow_off_once = false;
     h->total_retries += retries;
-    if (c.st) c.st->n_retries = retries;
+    if (c.st) { c.st->n_retries = retries; c.st->retry_causes = causes; c.st->flow_abort = abort_reason; }
     return rc;
 }
 
@@ -1032,6 +1039,13 @@ int rlap_debug_set_limits(rlap_handle h, double pool_factor, double log_factor, 
     if (!h) return RLAP_E_BAD_ARG;
     std::lock_guard<std::mutex> lock(h->mu);
     h->dbg_pool = pool_factor; h->dbg_log = log_factor; h->dbg_rng = rng_len; h->dbg_scr = scratch_entries;
+    return RLAP_OK;
+}
+
+int rlap_debug_set_flow_limits(rlap_handle h, int64_t reorder_cap) {
+    if (!h) return RLAP_E_BAD_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    h->dbg_ro_cap = reorder_cap;
     return RLAP_OK;
 }
 

@@ -36,8 +36,10 @@ constexpr int32_t FPOS_NONE = 0x7FFFFFFF;  // VRec::pqpos of a vertex that is no
 constexpr unsigned long long LB_VALID = 1ull << 63, LB_PREFIX = 1ull << 62, LB_MASK = (1ull << 62) - 1ull;
 
 // control words (index into FlowArrays::ctrl): next claim, abort status, long-column scratch top (entries), long columns met, committed positions,
-// very long columns being worked on (no stall is declared meanwhile)
-enum { FC_CLAIM = 0, FC_ABORT = 32, FC_SCR = 64, FC_LONG = 96, FC_PROGRESS = 128, FC_HEAVY = 160, FC_WORDS = 192 };
+// very long columns being worked on (no stall is declared meanwhile), why the launch gave up (FA_*, the first reason recorded)
+enum { FC_CLAIM = 0, FC_ABORT = 32, FC_SCR = 64, FC_LONG = 96, FC_PROGRESS = 128, FC_HEAVY = 160, FC_REASON = 192, FC_WORDS = 224 };
+// reasons of a give-up (ST_INTERNAL; rlap_stats.flow_abort): stall watchdog, sorted-index check, appended count over 2^22, column longer than its buffer
+enum { FA_NONE = 0, FA_STALL = 1, FA_SORT_INDEX = 2, FA_APPEND_COUNT = 3, FA_COLUMN_LEN = 4 };
 
 struct FlowArrays {
     int32_t* cdir;              // [N * FDIR]

@@ -411,6 +411,12 @@ __device__ __forceinline__ int flow_has_dup(BUF& B, int len0, int lane, int* dis
 
 __device__ __forceinline__ bool flow_abort(const FlowArrays& F) { return ag_ld(&F.ctrl[FC_ABORT]) != 0; }
 __device__ __forceinline__ void flow_fail(const FlowArrays& F, int32_t st) { __hip_atomic_fetch_max(&F.ctrl[FC_ABORT], st, RLX, AGT); }
+// the launch gives up (ST_INTERNAL: the call repeats on the round kernel); `reason` (FA_*) is kept in a word of its own, first one wins
+__device__ __forceinline__ void flow_giveup(const FlowArrays& F, int32_t reason) {
+    int32_t expect = FA_NONE;
+    __hip_atomic_compare_exchange_strong(&F.ctrl[FC_REASON], &expect, reason, RLX, RLX, AGT);
+    flow_fail(F, ST_INTERNAL);
+}
 // A wait may last as long as the elimination itself (the last position of a clique waits for all the others), so it is not the
 // number of polls that is bounded but the time WITHOUT PROGRESS anywhere: ctrl[4] counts committed positions; a waiter gives up
 // (ST_INTERNAL: never a result) when that counter has stood still for `stall_ticks` of the 100 MHz clock.  Called every 64 polls.
@@ -447,7 +453,7 @@ __device__ __forceinline__ int32_t flow_chunk_base(const Arrays& A, const FlowAr
         for (int sp = 1; ob == FD_BUSY; ++sp) {
             __builtin_amdgcn_s_sleep(2);
             ob = ag_ld(ow);
-            if ((sp & 63) == 0 && flow_stalled(F, P, fw)) { flow_fail(F, ST_INTERNAL); return FD_FAIL; }
+            if ((sp & 63) == 0 && flow_stalled(F, P, fw)) { flow_giveup(F, FA_STALL); return FD_FAIL; }
         }
         if (ob < 0) return FD_FAIL;
         word = reinterpret_cast<int32_t*>(A.e + ob) + (c - (FDIR - 1));
@@ -466,7 +472,7 @@ __device__ __forceinline__ int32_t flow_chunk_base(const Arrays& A, const FlowAr
     for (int sp = 1; b == FD_BUSY; ++sp) {
         __builtin_amdgcn_s_sleep(2);
         b = ag_ld(word);
-        if ((sp & 63) == 0 && flow_stalled(F, P, fw)) { flow_fail(F, ST_INTERNAL); return FD_FAIL; }
+        if ((sp & 63) == 0 && flow_stalled(F, P, fw)) { flow_giveup(F, FA_STALL); return FD_FAIL; }
     }
     return b < 0 ? FD_FAIL : b;
 }
@@ -559,7 +565,7 @@ __device__ __forceinline__ bool flow_eliminate(int32_t* const cmd, const int ON,
             len0 += popc64(mask);
         }
         napp = len0;
-        if (acnt > (1 << 22)) { flow_fail(F, ST_INTERNAL); return false; }   // (the list-order key below holds 22 bits of appended index)
+        if (acnt > (1 << 22)) { flow_giveup(F, FA_APPEND_COUNT); return false; }   // (the list-order key below holds 22 bits of appended index)
         for (int32_t s0 = cp1 - 1; s0 >= cp0; s0 -= 64) {
             const int32_t s = s0 - lane;
             const bool valid = s >= cp0;
@@ -572,7 +578,7 @@ __device__ __forceinline__ bool flow_eliminate(int32_t* const cmd, const int ON,
             len0 += popc64(mask);
         }
     }
-    if (len0 > cap) { flow_fail(F, ST_INTERNAL); return false; }
+    if (len0 > cap) { flow_giveup(F, FA_COLUMN_LEN); return false; }
     WAVE_SYNC();
     FSTAMP(1);
 
@@ -679,7 +685,7 @@ __device__ __forceinline__ bool flow_eliminate(int32_t* const cmd, const int ON,
         const uint64_t bm3 = __ballot(bad3);
         if (bm && B.xdbg && lane == 0) { B.xdbg[3] += 1; B.xdbg[0] = 1; B.xdbg[1] = (long long)bm; B.xdbg[2] = (long long)bm3; }
 #endif
-        if (bm) { flow_fail(F, ST_INTERNAL); return false; }
+        if (bm) { flow_giveup(F, FA_SORT_INDEX); return false; }
     }
     for (int j = lane; j < m; j += 64) {
         const int x = B.R(j).idx;
@@ -748,7 +754,7 @@ __device__ __forceinline__ bool flow_eliminate(int32_t* const cmd, const int ON,
             __builtin_amdgcn_s_sleep(1);
             if ((++spins & 63) == 0) {
                 if (flow_abort(F)) { if (helped) __syncthreads(); return false; }
-                if (flow_stalled(F, P, fw)) { flow_fail(F, ST_INTERNAL); if (helped) __syncthreads(); return false; }
+                if (flow_stalled(F, P, fw)) { flow_giveup(F, FA_STALL); if (helped) __syncthreads(); return false; }
             }
         }
         D = sum;
@@ -989,7 +995,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_eliminate_flow(Arrays A, Flow
                     ++spins;
                     if ((spins & 63) == 0) {
                         if (flow_abort(F)) { pend = -1; break; }
-                        if (flow_stalled(F, P, fw)) { flow_fail(F, ST_INTERNAL); pend = -1; break; }
+                        if (flow_stalled(F, P, fw)) { flow_giveup(F, FA_STALL); pend = -1; break; }
                     }
                 }
                 if (pend != 0) break;

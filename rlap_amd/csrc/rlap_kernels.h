@@ -21,6 +21,7 @@ struct CallResults {
     int64_t n_draws, rounds, singles;
     int64_t live_total, scr_need, ext_total, m_total;
     int32_t pool_used, log_used;
+    int32_t flow_abort, pad;   // dataflow elimination: why the launch gave up (FA_*, rlap_flow.h), 0 otherwise
 };
 constexpr int ECAP = 384;  // elimination: column extent handled in LDS; longer -> sequential form in global scratch
 constexpr int ECAP_SMALL = 320;   // the same for the 256-thread shape (four workgroups per CU: 40 KB of LDS each)
@@ -98,7 +99,7 @@ __global__ void k_perm_check(const int64_t* perm, const int32_t* vgraph, const G
 __global__ void k_gd_scratch(const int32_t* colptr, const int64_t* node_ptr, int32_t G, GraphDesc* gd);
 __global__ void k_collect(const int32_t* flags, const double* acc, const int32_t* nnz_p, const unsigned long long* counters,
                           const unsigned long long* live, const int64_t* tmp_off, const int64_t* row_off, int32_t S, const GraphDesc* gd, int32_t G,
-                          const int32_t* pool_top, const int32_t* bs_pool_top, CallResults* out);
+                          const int32_t* pool_top, const int32_t* bs_pool_top, const int32_t* flow_reason, CallResults* out);
 __global__ void k_heads(const uint64_t* keys, int64_t E, int32_t* head);
 __global__ void k_fill_csr(const uint64_t* keys, const uint32_t* idx, const int32_t* head, const int32_t* pos, const double* w,
                            int64_t E, int set_semantics, int kbits, Slot* ent, int32_t* slot_col, int32_t* nbr32);

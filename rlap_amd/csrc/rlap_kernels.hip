@@ -227,7 +227,7 @@ __global__ __launch_bounds__(256) void k_collect(const int32_t* __restrict__ fla
                           const unsigned long long* __restrict__ counters, const unsigned long long* __restrict__ live,
                           const int64_t* __restrict__ tmp_off, const int64_t* __restrict__ row_off,
                           int32_t S, const GraphDesc* __restrict__ gd, int32_t G, const int32_t* __restrict__ pool_top,
-                          const int32_t* __restrict__ bs_pool_top, CallResults* __restrict__ out) {
+                          const int32_t* __restrict__ bs_pool_top, const int32_t* __restrict__ flow_reason, CallResults* __restrict__ out) {
     __shared__ int32_t s_st;
     __shared__ unsigned long long s_nd, s_rounds, s_singles;
     const int tid = threadIdx.x;
@@ -258,6 +258,7 @@ __global__ __launch_bounds__(256) void k_collect(const int32_t* __restrict__ fla
     R.pool_used = *pool_top;
     R.log_used = *bs_pool_top;
     R.status = s_st; R.n_draws = (int64_t)s_nd; R.rounds = (int64_t)s_rounds; R.singles = (int64_t)s_singles;
+    R.flow_abort = flow_reason ? *flow_reason : 0; R.pad = 0;
     *out = R;
 }
 

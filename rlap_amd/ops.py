@@ -14,6 +14,7 @@ Same positional signature, same asserts, same return contract ((m,3) float64
 from typing import Optional, Sequence, Tuple, Union
 import ctypes
 import threading
+import warnings
 
 import torch
 from torch import Tensor
@@ -29,6 +30,11 @@ O_N = {"asc": 0, "desc": 1, "random": 2}
 _tls = threading.local()
 _timing = False
 last_stats = None  # rlap_stats of the most recent call (dict), for benches/tests
+
+
+class DataflowFallbackWarning(RuntimeWarning):
+    """The dataflow elimination kernel (o_v="random") gave up inside a call (rlap_stats.flow_abort says why) and the call was
+    repeated on the round kernel.  The rows are still the right ones; the warning says that the fast path did not produce them."""
 
 
 class _Handle:
@@ -135,10 +141,12 @@ def _run(hobj, dev, E: int, n_total: int, G: int, symmetrize: bool, call, st):
         if rc != 0:
             _raise(rc)
         hobj.fit(dev, ws_b.value, rng_n.value)
-    retries = 0
+    retries, causes, abort = 0, 0, 0
     for _ in range(8):
         rc = call()
         retries += int(st.n_retries)
+        causes |= int(st.retry_causes)
+        abort = int(st.flow_abort) or abort
         if rc != _lib.E_WORKSPACE:
             break
         rc2 = lib.rlap_workspace_needed(hobj.ptr, ctypes.byref(ws_b), ctypes.byref(rng_n))
@@ -146,6 +154,12 @@ def _run(hobj, dev, E: int, n_total: int, G: int, symmetrize: bool, call, st):
             _raise(rc2)
         hobj.fit(dev, ws_b.value, rng_n.value)
     st.n_retries = retries
+    st.retry_causes = causes
+    st.flow_abort = abort
+    if causes & _lib.RETRY_FLOW_GAVE_UP:
+        # (bit 7, a reorder buffer too small, is a designed fall-back and stays quiet)
+        warnings.warn(f"rlap: the dataflow elimination kernel gave up ({_lib.FLOW_ABORT_REASONS.get(abort, abort)}); "
+                      "the call was repeated on the round kernel", DataflowFallbackWarning, stacklevel=3)
     return rc
 
 
@@ -161,6 +175,16 @@ def debug_set_limits(pool_factor: float = -1.0, log_factor: float = -1.0, rng_le
     dev = _device_for(None) if device is None else torch.device(device)
     lib, h = _handle(dev)
     rc = lib.rlap_debug_set_limits(h, float(pool_factor), float(log_factor), int(rng_len), int(scratch_entries))
+    if rc != 0:
+        _raise(rc)
+
+
+def debug_set_flow_limits(reorder_cap: int = -1, device=None):
+    """Test hook: entries of the dataflow kernel's reorder buffer for the first attempt of the calling thread's next call
+    (negative = default), so that the fall-back to the round kernel runs (last_stats["retry_causes"] bit 7)."""
+    dev = _device_for(None) if device is None else torch.device(device)
+    lib, h = _handle(dev)
+    rc = lib.rlap_debug_set_flow_limits(h, int(reorder_cap))
     if rc != 0:
         _raise(rc)
 

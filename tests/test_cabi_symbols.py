@@ -122,3 +122,29 @@ def test_size_query_rejects_what_int32_slot_ids_cannot_hold():
     assert q(1000, 1 << 30, 1) == 9
     assert q(-5, 10, 1) == 3             # RLAP_E_BAD_ARG
     assert lib.rlap_status_string(9).decode() == "problem exceeds int32 slot ids"
+
+
+def test_stats_layout_matches_the_header(tmp_path):
+    """`_lib.Stats` (ctypes) and `rlap_stats` of include/rlap_hip.h describe the same bytes: a C99 program compiled against the
+    header prints sizeof and every offsetof, compared with what ctypes computes for the Python structure."""
+    import shutil
+    import subprocess
+    gcc = shutil.which("gcc")
+    assert gcc, "gcc is needed to check the C layout"
+    fields = [f for f, _ in _lib.Stats._fields_]
+    hdr = open(os.path.join(ROOT, "include", "rlap_hip.h")).read()
+    body = hdr[hdr.index("typedef struct {", hdr.index("RLAP_E_WORKSPACE")):hdr.index("} rlap_stats;")]
+    declared = re.findall(r"\b(?:int32_t|int64_t|float|double)\s+([a-z_0-9]+)\s*;", body)
+    assert declared == fields, "the header's fields and _lib.Stats differ in name or order"
+    src = tmp_path / "layout.c"
+    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "rlap_hip.h"', "int main(void) {",
+             '    printf("sizeof %zu\\n", sizeof(rlap_stats));']
+    lines += [f'    printf("{f} %zu\\n", offsetof(rlap_stats, {f}));' for f in fields]
+    lines += ["    return 0;", "}"]
+    src.write_text("\n".join(lines) + "\n")
+    exe = tmp_path / "layout"
+    subprocess.check_call([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = dict(line.split() for line in subprocess.check_output([str(exe)], text=True).splitlines())
+    assert int(got.pop("sizeof")) == ctypes.sizeof(_lib.Stats)
+    assert {f: int(v) for f, v in got.items()} == {f: getattr(_lib.Stats, f).offset for f in fields}
+    assert ctypes.sizeof(_lib.Stats) % 8 == 0

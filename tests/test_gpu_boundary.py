@@ -13,7 +13,7 @@ import torch
 import oracle
 from util import ba_graph, sym_weights
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.filterwarnings("error::rlap_amd.ops.DataflowFallbackWarning")]
 
 
 def test_unpack_edge_info_then_approx_chol_through_the_c_abi():

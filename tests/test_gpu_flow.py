@@ -1,16 +1,19 @@
 """GPU parity of the multi-CU ("dataflow") elimination for o_v = "random" (rlap_amd/csrc/rlap_flow.hip, RLAP_FLOW=1) against the CPU
 oracle: row order, indices and weights bit for bit; its long-column sorts against libstdc++'s std::sort itself; schedule jitter and
-poisoned memory; the same rows as the round kernel."""
+poisoned memory; the same rows as the round kernel.  Every call asserts the elimination kernel that produced its rows
+(rlap_stats.elim_kernel), and a dataflow launch that gives up (DataflowFallbackWarning) fails the test it happens in."""
 import os
+import warnings
 
 import numpy as np
 import pytest
 import torch
 
 import oracle
-from util import ba_graph, clique, grid2d, introsort_killer, path, star, sym_weights, symmetrize
+from rlap_amd import _lib
+from util import assert_kernel, ba_graph, clique, grid2d, introsort_killer, kernel_for, path, star, sym_weights, symmetrize, wide_weights
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.filterwarnings("error::rlap_amd.ops.DataflowFallbackWarning")]
 
 
 @pytest.fixture(scope="module")
@@ -32,9 +35,10 @@ def flow_env():
             os.environ[k] = v
 
 
-def call(ops, ei, w, n, t, o_n, perm, seed=3):
+def call(ops, ei, w, n, t, o_n, perm, seed=3, kernel=_lib.KERNEL_FLOW):
     out = ops.approximate_cholesky(torch.from_numpy(np.ascontiguousarray(ei)).cuda(), None if w is None else torch.from_numpy(w).cuda(), n, t,
                                    "random", o_n, perm=torch.from_numpy(np.asarray(perm, dtype=np.int64)), seed=seed)
+    assert_kernel(ops, kernel_for(kernel, n, t), f"n={n} t={t} {o_n}")
     return out.numpy()
 
 
@@ -124,14 +128,15 @@ GRAPHS = [("K4", clique(4), 4), ("K6", clique(6), 6), ("P9", path(9), 9), ("star
 @pytest.mark.parametrize("shape", ["1", "2", "3"])
 @pytest.mark.parametrize("o_n", ["asc", "desc", "random"])
 def test_flow_matches_oracle(ops, flow_env, o_n, shape):
-    """All graph families x weights x num_remove, both workgroup shapes (large LDS block / small blocks)."""
+    """All graph families x weights x num_remove, both workgroup shapes (large LDS block / small blocks).  Weights: unit, tie-free
+    U(0.5, 1.5), and log-uniform over 10^+-6 and 10^+-30 (f close to 1, new weights that round to <= 0: the dead-entry rules)."""
     flow_env["RLAP_FLOW_SHAPE"] = shape
     rng = np.random.RandomState(7)
     for nm, ei, n in GRAPHS:
         perm = rng.permutation(n)
-        for wts in (None, sym_weights(ei, n, 5)):
+        for wk, wts in (("unit", None), ("sym", sym_weights(ei, n, 5)), ("wide6", wide_weights(ei, n, 5, 6)), ("wide30", wide_weights(ei, n, 6, 30))):
             for t in sorted({0, 1, n // 2, n - 1, n + 5}):
-                check(ops, ei, wts, n, t, o_n, perm, (nm, o_n, t, wts is not None))
+                check(ops, ei, wts, n, t, o_n, perm, (nm, o_n, t, wk))
 
 
 def test_flow_long_columns_and_hubs(ops, flow_env):
@@ -169,14 +174,15 @@ def test_flow_equals_round_kernel_on_a_medium_graph(ops, flow_env):
     perm = torch.from_numpy(np.random.RandomState(3).permutation(n))
     flow_env["RLAP_FLOW"] = "0"
     a = ops.approximate_cholesky(ei, None, n, n // 2, "random", "asc", perm=perm, return_device="same")
-    assert ops.last_stats["n_rounds"] > 0
+    assert_kernel(ops, _lib.KERNEL_ROUND, "RLAP_FLOW=0")
     flow_env["RLAP_FLOW"] = "1"
     b = ops.approximate_cholesky(ei, None, n, n // 2, "random", "asc", perm=perm, return_device="same")
-    assert ops.last_stats["n_rounds"] == 0, "the dataflow kernel did not run"
+    assert_kernel(ops, _lib.KERNEL_FLOW, "RLAP_FLOW=1")
     assert a.shape == b.shape and torch.equal(a, b)
     for waves in ("7", "300"):   # any number of waves in flight gives the same rows
         flow_env["RLAP_FLOW_WAVES"] = waves
         c = ops.approximate_cholesky(ei, None, n, n // 2, "random", "asc", perm=perm, return_device="same")
+        assert_kernel(ops, _lib.KERNEL_FLOW, f"{waves} waves")
         assert torch.equal(a, c), waves
     flow_env.pop("RLAP_FLOW_WAVES", None)
     # one wave: the sequential order itself (a smaller graph: one wave is slow)
@@ -198,6 +204,7 @@ def test_flow_batched_equals_single_calls(ops, flow_env):
     ts = [s // 2 for s in sizes]
     for o_n in ("asc", "random"):
         sc, rp = ops.approximate_cholesky_batched(big.cuda(), None, node_ptr, ts, "random", o_n, perm=torch.from_numpy(perm), seed=5)
+        assert_kernel(ops, _lib.KERNEL_FLOW, o_n)
         sc = sc.cpu().numpy()
         off = 0
         for g, s in enumerate(sizes):
@@ -229,14 +236,20 @@ def test_flow_under_jitter_and_poison(ops, flow_env):
 
 
 def test_flow_growth_retries(ops, flow_env):
-    """Tiny pool / uniform table / long-column scratch: the call repeats itself with more and returns the same rows."""
+    """Tiny pool / uniform table / long-column scratch: the call repeats itself with more, every limit once, on the dataflow kernel,
+    and returns the same rows.  (The dataflow kernel keeps no priority-queue log: the log limit is never met and is cleared after.)"""
     n = 3000
     ei = ba_graph(n, 10, 2)
     perm = np.random.RandomState(8).permutation(n)
     a = oracle.approximate_cholesky(ei, None, n, n - 1, "random", "asc", perm=perm, shuffle_seed=3)
-    ops.debug_set_limits(pool_factor=0.05, log_factor=0.05, rng_len=1000, scratch_entries=16)
-    b = call(ops, ei, None, n, n - 1, "asc", perm)
-    assert ops.last_stats["n_retries"] >= 1
+    try:
+        ops.debug_set_limits(pool_factor=0.05, log_factor=0.05, rng_len=1000, scratch_entries=16)
+        b = call(ops, ei, None, n, n - 1, "asc", perm)
+    finally:
+        ops.debug_set_limits()
+    st = ops.last_stats
+    assert st["retry_causes"] == _lib.RETRY_POOL | _lib.RETRY_RNG | _lib.RETRY_FLOW_SCRATCH, st
+    assert st["n_retries"] == 3 and st["flow_abort"] == 0, st
     assert a.shape == b.shape and np.array_equal(a, b)
 
 
@@ -259,14 +272,14 @@ def test_abandoned_launch_with_appends_in_flight(ops, flow_env):
     perm = np.concatenate([rng.permutation(n) for _ in range(G)]).astype(np.int64)
     try:
         ops.debug_set_jitter(9)
-        for limits in (dict(pool_factor=0.3), dict(pool_factor=0.6, scratch_entries=20000), dict()):
+        for limits, causes in ((dict(pool_factor=0.3), _lib.RETRY_POOL), (dict(pool_factor=0.6, scratch_entries=20000), _lib.RETRY_POOL | _lib.RETRY_FLOW_SCRATCH),
+                               (dict(), 0)):
             flow_env["RLAP_FLOW_SHAPE"] = "1"
-            if limits:
-                ops.debug_set_limits(**limits)
+            ops.debug_set_limits(**limits)
             sc, rp = ops.approximate_cholesky_batched(big.cuda(), None, node_ptr, [n] * G, "random", "random", perm=torch.from_numpy(perm), seed=21)
             sc = sc.cpu().numpy()
-            if limits:
-                assert ops.last_stats["n_retries"] >= 1, limits
+            assert_kernel(ops, _lib.KERNEL_FLOW, str(limits))
+            assert ops.last_stats["retry_causes"] == causes and ops.last_stats["flow_abort"] == 0, (limits, ops.last_stats)
             for g in range(G):
                 a = oracle.approximate_cholesky(eis[g], None, n, n, "random", "random", perm=perm[g * n:(g + 1) * n], shuffle_seed=21 + g)
                 b = sc[rp[g]:rp[g + 1]].copy()
@@ -274,12 +287,13 @@ def test_abandoned_launch_with_appends_in_flight(ops, flow_env):
                 assert a.shape == b.shape and np.array_equal(a, b), (limits, g)
     finally:
         ops.debug_set_jitter(0)
+        ops.debug_set_limits()
 
 
 def test_a_flow_launch_that_gives_up_is_repeated_on_the_round_kernel(ops, flow_env):
     """The stall watchdog set to 1 ms on a star of 16,001 vertices (its centre's column of 13,000 entries keeps one wave busy for
     milliseconds while every later leaf waits): the dataflow launch ends with ST_INTERNAL, the call runs once more on the round kernel,
-    the rows are the oracle's."""
+    the rows are the oracle's -- and the call says so: DataflowFallbackWarning, flow_abort = stall watchdog, retry kind 8."""
     n = 16001
     ei = star(n)
     perm = np.random.RandomState(4).permutation(n)
@@ -288,8 +302,10 @@ def test_a_flow_launch_that_gives_up_is_repeated_on_the_round_kernel(ops, flow_e
     old = os.environ.get("RLAP_FLOW_STALL_MS")
     os.environ["RLAP_FLOW_STALL_MS"] = "1"
     try:
-        b = call(ops, ei, None, n, n - 1, "asc", perm)
-        assert ops.last_stats["n_retries"] >= 1 and ops.last_stats["n_rounds"] > 0   # (rounds: the round kernel produced the result)
+        with pytest.warns(ops.DataflowFallbackWarning, match="stall watchdog"):
+            b = call(ops, ei, None, n, n - 1, "asc", perm, kernel=_lib.KERNEL_ROUND)
+        st = ops.last_stats
+        assert st["flow_abort"] == 1 and st["retry_causes"] == _lib.RETRY_FLOW_GAVE_UP and st["n_retries"] == 1, st
     finally:
         if old is None:
             os.environ.pop("RLAP_FLOW_STALL_MS", None)
@@ -312,6 +328,7 @@ def test_frontier_mode_matches_the_oracle_in_that_mode(ops, flow_env, o_v):
                 a = oracle.approximate_cholesky(ei, wts, n, t, o_v, o_n, perm=perm if o_v == "random" else None, shuffle_seed=9, mode="frontier")
                 b = ops.approximate_cholesky(torch.from_numpy(np.ascontiguousarray(ei)).cuda(), None if wts is None else torch.from_numpy(wts).cuda(), n, t, o_v, o_n,
                                              perm=torch.from_numpy(perm) if o_v == "random" else None, seed=9, mode="frontier").numpy()
+                assert_kernel(ops, _lib.KERNEL_FLOW if o_v == "random" else _lib.KERNEL_ROUND, (nm, o_v, o_n))
                 assert a.shape == b.shape and np.array_equal(a, b), (nm, o_v, o_n, wts is not None)
     n = 3000
     ei = ba_graph(n, 10, 2)
@@ -320,6 +337,7 @@ def test_frontier_mode_matches_the_oracle_in_that_mode(ops, flow_env, o_v):
     fr = oracle.approximate_cholesky(ei, None, n, n // 2, o_v, "asc", perm=perm if o_v == "random" else None, shuffle_seed=9, mode="frontier")
     assert ex.shape != fr.shape or not np.array_equal(ex, fr)
     b = ops.approximate_cholesky(torch.from_numpy(ei).cuda(), None, n, n // 2, o_v, "asc", perm=torch.from_numpy(perm) if o_v == "random" else None, seed=9).numpy()
+    assert_kernel(ops, _lib.KERNEL_FLOW if o_v == "random" else _lib.KERNEL_ROUND, o_v)
     assert ex.shape == b.shape and np.array_equal(ex, b), "the default mode is exact again"
 
 
@@ -334,6 +352,7 @@ def test_frontier_mode_batched_and_hubs(ops, flow_env):
     for flow in ("0", "1"):   # the round kernel and the dataflow kernel draw the same numbers
         flow_env["RLAP_FLOW"] = flow
         sc, rp = ops.approximate_cholesky_batched(big.cuda(), None, node_ptr, ts, "random", "asc", perm=torch.from_numpy(perm), seed=5, mode="frontier")
+        assert_kernel(ops, _lib.KERNEL_FLOW if flow == "1" else _lib.KERNEL_ROUND, f"RLAP_FLOW={flow}")
         sc = sc.cpu().numpy()
         off = 0
         for g, s in enumerate(sizes):
@@ -351,4 +370,56 @@ def test_frontier_mode_batched_and_hubs(ops, flow_env):
     for t in (n - 3, n - 1):
         a = oracle.approximate_cholesky(ei, None, n, t, "random", "asc", perm=perm, shuffle_seed=3, mode="frontier")
         b = ops.approximate_cholesky(torch.from_numpy(ei).cuda(), None, n, t, "random", "asc", perm=torch.from_numpy(perm), seed=3, mode="frontier").numpy()
+        assert_kernel(ops, _lib.KERNEL_FLOW, t)
         assert a.shape == b.shape and np.array_equal(a, b), t
+
+
+def test_default_kernel_choice(ops, monkeypatch):
+    """The host's default dispatch (flow_wanted, rlap_api.hip), t > 0, no RLAP_FLOW: o_v = random runs the dataflow kernel on single
+    graphs, pairs, and batches of up to 64 graphs of 1,024 or more vertices on average; everything else runs the round kernel.  A change
+    to the rule shows up here, not as a silent change in what the other tests cover."""
+    from rlap_amd import graphs
+    monkeypatch.delenv("RLAP_FLOW", raising=False)
+
+    def batch(G, n):
+        big, node_ptr = graphs.batch_disjoint([graphs.barabasi_albert(n, 2, 40 + g) for g in range(G)], [n] * G)
+        return big.cuda(), node_ptr
+
+    ei = graphs.barabasi_albert(500, 3, 1).cuda()
+    for o_v, kernel in (("random", _lib.KERNEL_FLOW), ("degree", _lib.KERNEL_ROUND), ("coarsen", _lib.KERNEL_ROUND)):
+        ops.approximate_cholesky(ei, None, 500, 250, o_v, "asc", seed=1, return_device="same")
+        assert_kernel(ops, kernel, f"single graph, {o_v}")
+    for G, n, kernel in ((2, 40, _lib.KERNEL_FLOW), (64, 1024, _lib.KERNEL_FLOW), (64, 1000, _lib.KERNEL_ROUND), (65, 4096, _lib.KERNEL_ROUND)):
+        big, node_ptr = batch(G, n)
+        ops.approximate_cholesky_batched(big, None, node_ptr, [n // 2] * G, "random", "asc", seed=1)
+        assert_kernel(ops, kernel, f"batch of {G} x {n}")
+    ops.approximate_cholesky_views(ei, None, 500, [250, 250], "random", "asc", seed=1)
+    assert_kernel(ops, _lib.KERNEL_FLOW, "views, K = 2, one graph")
+    big, node_ptr = batch(40, 4096)
+    ops.approximate_cholesky_views(big, None, 40 * 4096, [2048, 2048], "random", "asc", node_ptr=node_ptr, seed=1)
+    assert_kernel(ops, _lib.KERNEL_ROUND, "views, K = 2, 40 graphs of 4096 (K * G = 80)")
+    ops.approximate_cholesky(ei, None, 500, 0, "random", "asc", seed=1)
+    assert_kernel(ops, _lib.KERNEL_NONE, "t = 0")
+
+
+def test_reorder_buffer_fallback(ops, flow_env):
+    """Hubs that collect thousands of out-of-order appended entries and survive, with a reorder buffer of one entry
+    (rlap_debug_set_flow_limits): the tag-order pass cannot hold them (ST_FLOW_REORDER, retry kind 7), the call is repeated on the round
+    kernel -- a designed fall-back: no DataflowFallbackWarning -- and the rows are the oracle's.  The next call is back on the dataflow kernel."""
+    rng = np.random.RandomState(12)
+    n = 3000
+    a0 = np.concatenate([np.zeros(n - 2, dtype=np.int64), np.ones(n - 2, dtype=np.int64), np.arange(2, n - 1)])
+    b0 = np.concatenate([np.arange(2, n), np.arange(2, n), np.arange(3, n)])
+    ei = symmetrize(a0, b0, n)
+    perm = np.concatenate([[0, 1], 2 + rng.permutation(n - 2)])   # the hubs go last
+    for t, w in ((n // 2, None), (n - 3, wide_weights(ei, n, 3, 6))):
+        a = oracle.approximate_cholesky(ei, w, n, t, "random", "asc", perm=perm, shuffle_seed=3)
+        ops.debug_set_flow_limits(1)
+        with warnings.catch_warnings():
+            warnings.simplefilter("error")
+            b = call(ops, ei, w, n, t, "asc", perm, kernel=_lib.KERNEL_ROUND)
+        st = ops.last_stats
+        assert st["retry_causes"] == _lib.RETRY_FLOW_REORDER and st["flow_abort"] == 0 and st["n_retries"] == 1, st
+        assert a.shape == b.shape and np.array_equal(a, b), t
+        b = call(ops, ei, w, n, t, "asc", perm)   # (the limit held for one attempt only)
+        assert ops.last_stats["retry_causes"] == 0 and np.array_equal(a, b), t

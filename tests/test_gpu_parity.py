@@ -1,6 +1,8 @@
 """GPU parity: the HIP path (through the C ABI, rlap_amd.ops) against the CPU oracle
 on the same seeded inputs.  Bar: indices and row order bit-exact, weights bit-exact
-(the kernels reproduce the reference's operation order; -ffp-contract=off)."""
+(the kernels reproduce the reference's operation order; -ffp-contract=off).  o_v = "random" has two elimination kernels (the round
+kernel and the dataflow kernel, chosen per call by the host); the single-graph random-order tests run under both, selected with
+RLAP_FLOW, and every call asserts the kernel that produced its rows."""
 import json
 import os
 import struct
@@ -10,9 +12,10 @@ import pytest
 import torch
 
 import oracle
-from util import ba_graph, canonical, clique, grid2d, path, star, sym_weights
+from rlap_amd import _lib
+from util import assert_kernel, ba_graph, canonical, clique, default_kernel, grid2d, kernel_for, path, star, sym_weights, wide_weights
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.filterwarnings("error::rlap_amd.ops.DataflowFallbackWarning")]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = json.load(open(os.path.join(HERE, "golden", "survey_appendix_c.json")))
@@ -26,12 +29,25 @@ def ops():
     return _ops
 
 
-def gpu_call(ops, ei, w, n, t, o_v, o_n, perm=None, seed=0):
+# RLAP_FLOW values that select each elimination kernel for o_v = "random" (the PQ orders always run the round kernel)
+KERNELS = (("0", _lib.KERNEL_ROUND), ("1", _lib.KERNEL_FLOW))
+
+
+def kernels_for(o_v):
+    return KERNELS if o_v == "random" else ((None, _lib.KERNEL_ROUND),)
+
+
+def gpu_call(ops, ei, w, n, t, o_v, o_n, perm=None, seed=0, kernel=None):
+    """One single-graph call; `kernel` (elim_kernel expected when some vertex is eliminated): the default rule's choice if None."""
     ei_t = torch.from_numpy(np.ascontiguousarray(ei)).cuda()
     w_t = None if w is None else torch.from_numpy(np.asarray(w, dtype=np.float64)).cuda()
     p_t = None if perm is None else torch.from_numpy(np.asarray(perm, dtype=np.int64))
     out = ops.approximate_cholesky(ei_t, w_t, n, t, o_v, o_n, perm=p_t, seed=seed)
     assert out.dtype == torch.float64 and out.device.type == "cpu"   # reference contract
+    if kernel is None and os.environ.get("RLAP_FLOW") is None:
+        kernel = _lib.KERNEL_FLOW if o_v == "random" else _lib.KERNEL_ROUND   # (single graphs: test_gpu_flow.py::test_default_kernel_choice)
+    if kernel is not None:
+        assert_kernel(ops, kernel_for(kernel, n, t), f"n={n} t={t} {o_v}/{o_n}")
     return out.numpy()
 
 
@@ -183,17 +199,22 @@ SMALL = [("K6", clique(6), 6), ("P9", path(9), 9), ("star7", star(7), 7), ("grid
 
 @pytest.mark.parametrize("o_v", ["degree", "random", "coarsen"])
 @pytest.mark.parametrize("o_n", ["asc", "desc", "random"])
-def test_small_graphs_all_modes(ops, o_v, o_n):
-    for name, ei, n in SMALL:
-        perm = np.random.RandomState(7).permutation(n) if o_v == "random" else None
-        for t in sorted({0, 1, n // 2, n - 1, n + 5}):
-            a = oracle.approximate_cholesky(ei, None, n, t, o_v, o_n, perm=perm, shuffle_seed=3)
-            b = gpu_call(ops, ei, None, n, t, o_v, o_n, perm=perm, seed=3)
-            assert_same(b, a, f"{name} t={t}")
-        w = sym_weights(ei, n, 5)
-        a = oracle.approximate_cholesky(ei, w, n, n // 2, o_v, o_n, perm=perm, shuffle_seed=4)
-        b = gpu_call(ops, ei, w, n, n // 2, o_v, o_n, perm=perm, seed=4)
-        assert_same(b, a, f"{name} weighted")
+def test_small_graphs_all_modes(ops, monkeypatch, o_v, o_n):
+    """Unit weights at every num_remove; tie-free weights U(0.5, 1.5) and log-uniform over 10^+-6 / 10^+-30 (f close to 1, new weights
+    that round to <= 0: the dead-entry rules) at n // 2; o_v = "random" on both kernels."""
+    for flow, kernel in kernels_for(o_v):
+        if flow is not None:
+            monkeypatch.setenv("RLAP_FLOW", flow)
+        for name, ei, n in SMALL:
+            perm = np.random.RandomState(7).permutation(n) if o_v == "random" else None
+            for t in sorted({0, 1, n // 2, n - 1, n + 5}):
+                a = oracle.approximate_cholesky(ei, None, n, t, o_v, o_n, perm=perm, shuffle_seed=3)
+                b = gpu_call(ops, ei, None, n, t, o_v, o_n, perm=perm, seed=3, kernel=kernel)
+                assert_same(b, a, f"{name} t={t} kernel {kernel}")
+            for wk, w in (("sym", sym_weights(ei, n, 5)), ("wide6", wide_weights(ei, n, 5, 6)), ("wide30", wide_weights(ei, n, 5, 30))):
+                a = oracle.approximate_cholesky(ei, w, n, n // 2, o_v, o_n, perm=perm, shuffle_seed=4)
+                b = gpu_call(ops, ei, w, n, n // 2, o_v, o_n, perm=perm, seed=4, kernel=kernel)
+                assert_same(b, a, f"{name} weighted {wk} kernel {kernel}")
 
 
 @pytest.mark.parametrize("n,m,o_v,o_n", [
@@ -203,22 +224,25 @@ def test_small_graphs_all_modes(ops, o_v, o_n):
     (20000, 10, "degree", "asc"),    # config 3's shape, oracle-sized
     (20000, 10, "degree", "desc"),
     (20000, 7, "coarsen", "asc"),    # config 4's mode
-    (5000, 40, "random", "random"),  # long columns: exercises the sequential fallback
+    (5000, 40, "random", "random"),  # long columns: the round kernel's sequential fallback, the dataflow kernel's long-column path
 ])
-def test_medium_ba_graphs(ops, n, m, o_v, o_n):
+def test_medium_ba_graphs(ops, monkeypatch, n, m, o_v, o_n):
     ei = ba_graph(n, m, 100 + m)
     perm = np.random.RandomState(11).permutation(n) if o_v == "random" else None
     for w in (None, sym_weights(ei, n, 3)):
         a = oracle.approximate_cholesky(ei, w, n, n // 2, o_v, o_n, perm=perm, shuffle_seed=21)
-        b = gpu_call(ops, ei, w, n, n // 2, o_v, o_n, perm=perm, seed=21)
-        assert_same(b, a, f"BA({n},{m}) {o_v}/{o_n} weighted={w is not None}")
+        for flow, kernel in kernels_for(o_v):
+            if flow is not None:
+                monkeypatch.setenv("RLAP_FLOW", flow)
+            b = gpu_call(ops, ei, w, n, n // 2, o_v, o_n, perm=perm, seed=21, kernel=kernel)
+            assert_same(b, a, f"BA({n},{m}) {o_v}/{o_n} weighted={w is not None} kernel {kernel}")
 
 
 @pytest.mark.parametrize("o_n", ["asc", "desc", "random"])
-def test_long_columns_random_order(ops, o_n):
+def test_long_columns_random_order(ops, monkeypatch, o_n):
     """o_v="random" meets hubs early: columns beyond the 64-slot batch candidates (wave path, <= 384 entries)
     and beyond the wave path (long-column path, LDS sort records + global scratch), with multi-edges
-    created by earlier eliminations."""
+    created by earlier eliminations -- on the round kernel, and the same graphs on the dataflow kernel."""
     cases = []
     n = 1500
     ei = star(n)
@@ -239,8 +263,10 @@ def test_long_columns_random_order(ops, o_n):
         for w in (None, sym_weights(ei, n, 9)):
             t = n // 2
             a = oracle.approximate_cholesky(ei, w, n, t, "random", o_n, perm=perm, shuffle_seed=6)
-            b = gpu_call(ops, ei, w, n, t, "random", o_n, perm=perm, seed=6)
-            assert_same(b, a, f"{name} {o_n} {'unit' if w is None else 'weighted'}")
+            for flow, kernel in KERNELS:
+                monkeypatch.setenv("RLAP_FLOW", flow)
+                b = gpu_call(ops, ei, w, n, t, "random", o_n, perm=perm, seed=6, kernel=kernel)
+                assert_same(b, a, f"{name} {o_n} {'unit' if w is None else 'weighted'} kernel {kernel}")
 
 
 @pytest.mark.parametrize("o_v", ["degree", "coarsen"])
@@ -256,14 +282,18 @@ def test_long_serial_column_under_the_pq_orders(ops, o_v):
         assert_same(b, a, f"K{n} {o_v} {'unit' if w is None else 'weighted'}")
 
 
-@pytest.mark.parametrize("wide", ["1", "0"])
+@pytest.mark.parametrize("wide", ["1", "0", "flow"])
 @pytest.mark.parametrize("o_n", ["asc", "desc", "random"])
 def test_wide_candidates_random_order(ops, monkeypatch, o_n, wide):
-    """o_v="random", 128-slot candidates (chosen for graphs with 8 or more entries per vertex; RLAP_WIDE forces the choice either
-    way here): columns of 65..128 entries stay inside the round -- two entries per lane, multi-edges folded in the candidate,
-    both orders by the level-synchronous std::sort restatement over an index array.  Dense, sparse, weighted (tie-free) and
-    unit-weight (all ties) graphs, a star (the hub takes the long-column path), a grid."""
-    monkeypatch.setenv("RLAP_WIDE", wide)
+    """o_v="random" on the round kernel, 128-slot candidates (chosen for graphs with 8 or more entries per vertex; RLAP_WIDE forces the
+    choice either way here, "1" / "0"): columns of 65..128 entries stay inside the round -- two entries per lane, multi-edges folded in
+    the candidate, both orders by the level-synchronous std::sort restatement over an index array.  Dense, sparse, weighted (tie-free)
+    and unit-weight (all ties) graphs, a star (the hub takes the long-column path), a grid.  "flow": the same graphs on the dataflow
+    kernel (which has no candidate slots: RLAP_WIDE is not set)."""
+    kernel = _lib.KERNEL_FLOW if wide == "flow" else _lib.KERNEL_ROUND
+    monkeypatch.setenv("RLAP_FLOW", "1" if wide == "flow" else "0")
+    if wide != "flow":
+        monkeypatch.setenv("RLAP_WIDE", wide)
     cases = [("BA3000_12", ba_graph(3000, 12, 1), 3000), ("BA700_60", ba_graph(700, 60, 3), 700), ("BA260_100", ba_graph(260, 100, 4), 260),
              ("BA20000_7", ba_graph(20000, 7, 5), 20000), ("BA2708_2", ba_graph(2708, 2, 6), 2708), ("star900", star(900), 900),
              ("grid40x30", grid2d(40, 30), 1200), ("K90", clique(90), 90)]
@@ -272,7 +302,7 @@ def test_wide_candidates_random_order(ops, monkeypatch, o_n, wide):
         for w in (None, sym_weights(ei, n, 9)):
             for t in sorted({n // 2, n - 1}):
                 a = oracle.approximate_cholesky(ei, w, n, t, "random", o_n, perm=perm, shuffle_seed=6)
-                b = gpu_call(ops, ei, w, n, t, "random", o_n, perm=perm, seed=6)
+                b = gpu_call(ops, ei, w, n, t, "random", o_n, perm=perm, seed=6, kernel=kernel)
                 assert_same(b, a, f"{name} t={t} {o_n} {'unit' if w is None else 'weighted'} wide={wide}")
     if o_n != "random":
         # a hub of 65..128 neighbours whose weights are an introsort killer with ties: the level-synchronous sort of the candidate
@@ -291,7 +321,7 @@ def test_wide_candidates_random_order(ops, monkeypatch, o_n, wide):
                 rest = [v for v in range(n) if v != hub]
                 perm = np.array((rest[:first] + [hub] + rest[first:])[::-1])
                 a = oracle.approximate_cholesky(ei, w, n, 10, "random", o_n, perm=perm, shuffle_seed=6)
-                b = gpu_call(ops, ei, w, n, 10, "random", o_n, perm=perm, seed=6)
+                b = gpu_call(ops, ei, w, n, 10, "random", o_n, perm=perm, seed=6, kernel=kernel)
                 assert_same(b, a, f"killer star{n} hub@{first} {o_n} wide={wide}")
 
 
@@ -309,6 +339,7 @@ def test_wide_candidates_batched(ops):
     for o_n in ("asc", "random"):
         sc, rp = ops.approximate_cholesky_batched(big.cuda(), None, node_ptr, [n // 2 for n in ns], "random", o_n,
                                                   perm=torch.from_numpy(np.concatenate(perms)), seed=9)
+        assert_kernel(ops, _lib.KERNEL_ROUND, f"40 graphs of {sum(ns) // G} vertices on average")
         sc = sc.cpu().numpy()
         for g in range(G):
             ref = oracle.approximate_cholesky(eis[g].numpy(), None, ns[g], ns[g] // 2, "random", o_n, perm=perms[g], shuffle_seed=9 + g)
@@ -372,9 +403,9 @@ def _random_graph(rs, n, p, dense_hub):
 
 
 @pytest.mark.parametrize("block", range(6))
-def test_fuzz_small_graphs_against_oracle(ops, block):
+def test_fuzz_small_graphs_against_oracle(ops, monkeypatch, block):
     """Seeded random graphs (sparse to dense, with and without a hub), random mode, num_remove, unit / tie-heavy /
-    tie-free weights: every result bit-exact against the oracle."""
+    tie-free weights: every result bit-exact against the oracle (o_v = "random": on both kernels)."""
     rs = np.random.RandomState(1000 + block)
     for trial in range(40):
         n = int(rs.choice([1, 2, 3, 5, 8, 17, 33, 40, 65, 90, 130, 200]))
@@ -394,8 +425,11 @@ def test_fuzz_small_graphs_against_oracle(ops, block):
         perm = rs.permutation(n) if o_v == "random" else None
         seed = int(rs.randint(1 << 30))
         a = oracle.approximate_cholesky(ei, w, n, t, o_v, o_n, perm=perm, shuffle_seed=seed)
-        b = gpu_call(ops, ei, w, n, t, o_v, o_n, perm=perm, seed=seed)
-        assert_same(b, a, f"block {block} trial {trial}: n={n} p={p} {o_v}/{o_n} t={t} w={wkind}")
+        for flow, kernel in kernels_for(o_v):
+            if flow is not None:
+                monkeypatch.setenv("RLAP_FLOW", flow)
+            b = gpu_call(ops, ei, w, n, t, o_v, o_n, perm=perm, seed=seed, kernel=kernel)
+            assert_same(b, a, f"block {block} trial {trial}: n={n} p={p} {o_v}/{o_n} t={t} w={wkind} kernel {kernel}")
 
 
 def test_reference_unit_test_shape(ops):
@@ -453,21 +487,30 @@ def test_batched_equals_separate_calls(ops):
         ei = ba_graph(n, m, 40 + g) if n > m else np.zeros((2, 0), dtype=np.int64)
         eis.append(torch.from_numpy(ei)); ns.append(n); ts.append(n // 2)
     big, node_ptr = graphs.batch_disjoint(eis, ns)
-    for o_v, o_n in [("degree", "asc"), ("random", "desc"), ("coarsen", "asc"), ("degree", "random"), ("random", "random")]:
+    big_np = big.numpy()
+    # log-uniform weights over 10^+-30 (the dead-entry rules), drawn on the union: graph g's are the entries inside its id range
+    w_wide = wide_weights(big_np, int(node_ptr[-1]), 17, 30)
+    for wk, o_v, o_n in [("unit", "degree", "asc"), ("unit", "random", "desc"), ("unit", "coarsen", "asc"), ("unit", "degree", "random"),
+                         ("unit", "random", "random"), ("wide30", "random", "asc"), ("wide30", "degree", "desc"), ("wide30", "coarsen", "random")]:
+        w = None if wk == "unit" else w_wide
         perms = [np.random.RandomState(g).permutation(n) for g, n in enumerate(ns)]
         perm = torch.from_numpy(np.concatenate(perms)) if o_v == "random" else None
-        sc, row_ptr = ops.approximate_cholesky_batched(big.cuda(), None, node_ptr, ts, o_v, o_n, perm=perm, seed=5)
+        sc, row_ptr = ops.approximate_cholesky_batched(big.cuda(), None if w is None else torch.from_numpy(w).cuda(), node_ptr, ts, o_v, o_n,
+                                                       perm=perm, seed=5)
+        assert_kernel(ops, default_kernel(o_v, 12, int(node_ptr[-1])), f"{o_v}/{o_n}")
         sc = sc.cpu().numpy()
         for g in range(12):
             # the batched contract (include/rlap_hip.h): graph g == a separate call on graph g with seed + g
             off = int(node_ptr[g])
-            a = oracle.approximate_cholesky(eis[g].numpy(), None, ns[g], ts[g], o_v, o_n, perm=perms[g], shuffle_seed=5 + g)
+            inside = (big_np[0] >= off) & (big_np[0] < off + ns[g])
+            ei_g, w_g = big_np[:, inside] - off, None if w is None else w[inside]
+            a = oracle.approximate_cholesky(ei_g, w_g, ns[g], ts[g], o_v, o_n, perm=perms[g], shuffle_seed=5 + g)
             b = sc[int(row_ptr[g]):int(row_ptr[g + 1])].copy()
             b[:, :2] -= off
-            assert_same(b, a, f"graph {g} {o_v}/{o_n}")
+            assert_same(b, a, f"graph {g} {o_v}/{o_n} {wk}")
             if g in (3, 7):   # ... and == a separate call of the op itself
-                c = gpu_call(ops, eis[g].numpy(), None, ns[g], ts[g], o_v, o_n, perm=perms[g], seed=5 + g)
-                assert_same(b, c, f"graph {g} {o_v}/{o_n} vs single call")
+                c = gpu_call(ops, ei_g, w_g, ns[g], ts[g], o_v, o_n, perm=perms[g], seed=5 + g)
+                assert_same(b, c, f"graph {g} {o_v}/{o_n} {wk} vs single call")
         # whole-batch invariants for every mode: symmetric edge set inside each graph's id range
         for g in range(12):
             b = sc[int(row_ptr[g]):int(row_ptr[g + 1])]
@@ -499,6 +542,7 @@ def test_batched_many_graphs(ops, o_v, o_n):
     perms = [np.random.RandomState(g).permutation(n) for g, n in enumerate(ns)]
     perm = torch.from_numpy(np.concatenate(perms)) if o_v == "random" else None
     sc, row_ptr = ops.approximate_cholesky_batched(big.cuda(), None, node_ptr, ts, o_v, o_n, perm=perm, seed=5)
+    assert_kernel(ops, _lib.KERNEL_ROUND, f"{G} graphs")
     sc = sc.cpu().numpy()
     for g in list(range(0, G, 16)) + list(range(1, G, 16)) + list(range(2, G, 37)):
         off = int(node_ptr[g])
@@ -621,6 +665,7 @@ def test_config5_full_size(ops, config5, o_v, o_n, every):
     perm = torch.from_numpy(np.concatenate(perms)) if o_v == "random" else None
     sc, rp = ops.approximate_cholesky_batched(big, None, node_ptr, [n // 2] * G, o_v, o_n, perm=perm, seed=5)
     assert ops.last_stats["n_eliminated"] == G * (n // 2)
+    assert_kernel(ops, _lib.KERNEL_ROUND, f"config 5 {o_v}/{o_n}")
     sc = sc.cpu().numpy()
     for g in range(0, G, every):
         ref = oracle.approximate_cholesky(eis[g].numpy(), None, n, n // 2, o_v, o_n, perm=perms[g], shuffle_seed=5 + g)
@@ -703,6 +748,7 @@ def test_overflow_retry_path_batched(ops, config5, o_v):
         try:
             sc, rp = ops.approximate_cholesky_batched(big, None, node_ptr, [n // 2] * G, o_v, "asc", perm=perm, seed=5, return_device="same")
             retries = ops.last_stats["n_retries"]
+            assert_kernel(ops, _lib.KERNEL_ROUND, f"config 5 {o_v} {lim}")
         finally:
             ops.debug_set_limits()
         assert retries > 0, f"{lim}: the limit was not hit"

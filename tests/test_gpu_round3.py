@@ -8,10 +8,11 @@ import pytest
 import torch
 
 import oracle
-from util import ba_graph, star, sym_weights
-from test_gpu_parity import assert_same, gpu_call, _where
+from rlap_amd import _lib
+from util import assert_kernel, ba_graph, star, sym_weights
+from test_gpu_parity import assert_same, gpu_call, kernels_for, _where
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.filterwarnings("error::rlap_amd.ops.DataflowFallbackWarning")]
 
 
 @pytest.fixture(scope="module")
@@ -224,10 +225,11 @@ def test_from_edges_negative_ids(ops):
 
 
 @pytest.mark.parametrize("byte", [0xFF, 0x00, 0x3C])
-def test_poisoned_workspace_gives_the_same_rows(ops, byte):
+def test_poisoned_workspace_gives_the_same_rows(ops, monkeypatch, byte):
     """Debug poison (rlap_debug_set_poison): the arena, the output buffer and the elimination kernel's LDS start as one byte
     pattern.  A kernel that reads what it was never given then reads the pattern, not the previous call's data, and the rows
-    change -- for every mode and both workgroup shapes they must not."""
+    change -- for every mode and both workgroup shapes they must not.  Single graphs of o_v = random run on both kernels; the
+    batch of 300 graphs runs on the round kernel."""
     from rlap_amd import graphs
     cases = [(2500, 6, "degree", "asc"), (2500, 6, "degree", "random"), (2500, 6, "random", "asc"), (1500, 12, "random", "desc"),
              (2500, 6, "coarsen", "asc"), (300, 40, "random", "asc"), (300, 40, "degree", "desc")]
@@ -246,11 +248,16 @@ def test_poisoned_workspace_gives_the_same_rows(ops, byte):
     ops.debug_set_poison(byte)
     try:
         for (n, m, o_v, o_n), (ei, perm, ref) in zip(cases, refs):
-            got = gpu_call(ops, ei, None, n, n // 2, o_v, o_n, perm=perm, seed=9)
-            assert_same(got, ref, f"poison {byte:#x} BA({n},{m}) {o_v}/{o_n}")
+            for flow, kernel in kernels_for(o_v):
+                if flow is not None:
+                    monkeypatch.setenv("RLAP_FLOW", flow)
+                got = gpu_call(ops, ei, None, n, n // 2, o_v, o_n, perm=perm, seed=9, kernel=kernel)
+                assert_same(got, ref, f"poison {byte:#x} BA({n},{m}) {o_v}/{o_n} kernel {kernel}")
+            monkeypatch.delenv("RLAP_FLOW", raising=False)
         for o_v in ("degree", "random", "coarsen"):
             sc, _ = ops.approximate_cholesky_batched(big, None, node_ptr, [n5 // 2] * G, o_v, "asc", perm=perms if o_v == "random" else None, seed=5,
                                                      return_device="same")
+            assert_kernel(ops, _lib.KERNEL_ROUND, f"poison {byte:#x} batched {o_v}")
             assert sc.shape == clean[o_v].shape and bool(torch.equal(sc, clean[o_v])), f"poison {byte:#x} batched {o_v}" + _where(sc.cpu().numpy(), clean[o_v].cpu().numpy())
     finally:
         ops.debug_set_poison(-1)
@@ -286,6 +293,7 @@ def test_schedule_jitter_does_not_change_the_rows(ops, monkeypatch, o_v):
     perms = [np.random.RandomState(g).permutation(n) for g in range(G)]
     perm = torch.from_numpy(np.concatenate(perms)) if o_v == "random" else None
     clean, rp = ops.approximate_cholesky_batched(big, None, node_ptr, [n // 2] * G, o_v, "asc", perm=perm, seed=5, return_device="same")
+    assert_kernel(ops, _lib.KERNEL_ROUND, f"{G} graphs, {o_v}")   # (RLAP_BATCH_SHAPE below is a round-kernel knob)
     for g in range(0, G, 48):
         ref = oracle.approximate_cholesky(eis[g].numpy(), None, n, n // 2, o_v, "asc", perm=perms[g], shuffle_seed=5 + g)
         got = clean[int(rp[g]):int(rp[g + 1])].cpu().numpy().copy()
@@ -297,6 +305,7 @@ def test_schedule_jitter_does_not_change_the_rows(ops, monkeypatch, o_v):
             monkeypatch.setenv("RLAP_BATCH_SHAPE", shape)
             for rep in range(2):
                 sc, _ = ops.approximate_cholesky_batched(big, None, node_ptr, [n // 2] * G, o_v, "asc", perm=perm, seed=5, return_device="same")
+                assert_kernel(ops, _lib.KERNEL_ROUND, f"jitter, shape {shape}")
                 assert sc.shape == clean.shape and bool(torch.equal(sc, clean)), f"jitter, shape {shape}, rep {rep}" + _where(sc.cpu().numpy(), clean.cpu().numpy())
     finally:
         ops.debug_set_jitter(0)

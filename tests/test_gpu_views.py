@@ -8,10 +8,12 @@ import numpy as np
 import pytest
 import torch
 
-import oracle
-from util import ba_graph, clique, sym_weights
+import os
 
-pytestmark = pytest.mark.gpu
+import oracle
+from util import assert_kernel, ba_graph, clique, default_kernel, sym_weights, wide_weights
+
+pytestmark = [pytest.mark.gpu, pytest.mark.filterwarnings("error::rlap_amd.ops.DataflowFallbackWarning")]
 
 PAIRS = [(a, b) for a in ("random", "degree", "coarsen") for b in ("asc", "desc", "random")]
 
@@ -30,13 +32,19 @@ def assert_same(a, b, what=""):
     assert np.array_equal(a[:, 2], b[:, 2]), f"{what}: weights differ"
 
 
-def views(ops, ei, w, n, ts, o_v, o_n, *, node_ptr=None, perm=None, seed=7, mode="exact", retries_ok=False):
+def views(ops, ei, w, n, ts, o_v, o_n, *, node_ptr=None, perm=None, seed=7, mode="exact", retries_ok=False, kernel=None):
+    """One views call; `kernel`: the elim_kernel expected (None: the default rule's choice for the K * G graphs of the union, unless
+    RLAP_FLOW overrides it)."""
     ei_t = torch.from_numpy(np.ascontiguousarray(ei)).cuda()
     w_t = None if w is None else torch.from_numpy(np.asarray(w, dtype=np.float64)).cuda()
     p_t = None if perm is None else torch.from_numpy(np.ascontiguousarray(perm, dtype=np.int64))
     sc, ptr = ops.approximate_cholesky_views(ei_t, w_t, n, ts, o_v, o_n, node_ptr=node_ptr, perm=p_t, seed=seed, mode=mode)
     if not retries_ok:
         assert ops.last_stats["n_retries"] == 0, f"{o_v}/{o_n}: the call was repeated ({ops.last_stats})"
+    if kernel is None and os.environ.get("RLAP_FLOW") is None:
+        kernel = default_kernel(o_v, len(ptr) - 1, (len(ptr) - 1) // (1 if node_ptr is None else len(node_ptr) - 1) * n)
+    if kernel is not None and ops.last_stats["n_eliminated"] > 0:
+        assert_kernel(ops, kernel, f"views {o_v}/{o_n}")
     return sc.cpu().numpy(), ptr.numpy()
 
 
@@ -109,17 +117,21 @@ def union_reference(ops, ei, w, n, K, ts, o_v, o_n, perm, seed):
 
 @pytest.mark.parametrize("flow", ["default", "0"])
 def test_views_equal_the_batched_union_random_order(ops, monkeypatch, flow):
-    """o_v = random on BA(20000, 5), K = 2: the dataflow kernel is chosen by default (a pair of graphs); RLAP_FLOW=0 the round kernel."""
+    """o_v = random on BA(20000, 5), K = 2: the dataflow kernel is chosen by default (a pair of graphs); RLAP_FLOW=0 the round kernel.
+    Unit weights, and log-uniform weights over 10^+-30 (the dead-entry rules)."""
+    kernel = 2 if flow == "default" else 1
     if flow == "0":
         monkeypatch.setenv("RLAP_FLOW", "0")
     n, K = 20000, 2
     ei = ba_graph(n, 5, 21)
     ts = [n // 2, n // 3]
-    for perm in (None, np.concatenate(perms_for(K, n, 5))):
-        got, ptr = views(ops, ei, None, n, ts, "random", "asc", perm=perm, seed=123)
-        ref = union_reference(ops, ei, None, n, K, ts, "random", "asc", perm, 123)
+    given = np.concatenate(perms_for(K, n, 5))
+    for perm, w in ((None, None), (given, wide_weights(ei, n, 8, 30)), (given, None)):
+        got, ptr = views(ops, ei, w, n, ts, "random", "asc", perm=perm, seed=123, kernel=kernel)
+        ref = union_reference(ops, ei, w, n, K, ts, "random", "asc", perm, 123)
+        assert_kernel(ops, kernel, f"the batched union, flow={flow}")
         for k, v in enumerate(split(got, ptr)):
-            assert_same(v, ref[k], f"view {k} flow={flow} perm={'given' if perm is not None else 'drawn'}")
+            assert_same(v, ref[k], f"view {k} flow={flow} perm={'given' if perm is not None else 'drawn'} weighted={w is not None}")
     # one view against the oracle at this size too
     perms = perms_for(K, n, 5)
     a = oracle.approximate_cholesky(ei, None, n, ts[1], "random", "asc", perm=perms[1], shuffle_seed=124)

@@ -6,6 +6,7 @@ REPEAT > 0 runs only FIRST_CASE, that many times, and counts the mismatches"""
 import os
 import sys
 import time
+import warnings
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, _ROOT)
@@ -97,7 +98,8 @@ def make_graph(c, g):
 
 def describe(c):
     return (f"{c.get('topo', 'ba')} {c['o_v']}/{c['o_n']} n={c['n']} m={c['m']} G={c['G']} t={c['t']} weighted={c['weighted']} jitter={c['jitter']} "
-            f"poison={c['poison']} shape={c['shape'] or 'auto'} seed={c['seed']}" + (" from_edges" if c.get("from_edges") else ""))
+            f"poison={c['poison']} shape={c['shape'] or 'auto'} seed={c['seed']}" + (" from_edges" if c.get("from_edges") else "")
+            + (f" elim_kernel={c['elim_kernel']}" if "elim_kernel" in c else ""))
 
 
 def run_case(c, check_all=False):
@@ -156,6 +158,8 @@ def main():
     rs = np.random.RandomState(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
     first = int(sys.argv[3]) if len(sys.argv) > 3 else 0
     repeat = int(sys.argv[4]) if len(sys.argv) > 4 else 0
+    from rlap_amd import ops
+    warnings.simplefilter("error", ops.DataflowFallbackWarning)   # a dataflow launch that gives up ends the run
     for _ in range(first):
         draw(rs)
     if repeat > 0:
@@ -165,7 +169,7 @@ def main():
         for r in range(repeat):
             bad = run_case(c, check_all=True)
             n_bad += bool(bad)
-            print(f"  run {r}: {'ok' if not bad else bad}", flush=True)
+            print(f"  run {r}: {'ok' if not bad else bad} (elim_kernel {ops.last_stats['elim_kernel']})", flush=True)
         print(f"{n_bad} of {repeat} runs differ from the oracle")
         sys.exit(1 if n_bad else 0)
     t_end = time.time() + budget
@@ -173,6 +177,7 @@ def main():
     while time.time() < t_end:
         c = draw(rs)
         bad = run_case(c)
+        c["elim_kernel"] = ops.last_stats["elim_kernel"]   # (of the case's last call)
         if bad:
             print("MISMATCH case", n_cases, describe(c), bad, flush=True)
             sys.exit(1)
@@ -180,7 +185,6 @@ def main():
         n_cases += 1
         if n_cases % 10 == 0:
             print(f"[{n_cases} cases, {n_graphs} graphs checked] last: {describe(c)}", flush=True)
-    from rlap_amd import ops
     ops.debug_set_jitter(0)
     ops.debug_set_poison(-1)
     print(f"soak ok: cases {first}..{n_cases - 1}, {n_graphs} graphs bit-exact against the oracle in {budget:.0f} s")

@@ -4,6 +4,7 @@ poisoned memory -- every result against the oracle.  usage: soak_flow.py SECONDS
 import os
 import sys
 import time
+import warnings
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, _ROOT)
@@ -17,6 +18,8 @@ def main():
     budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
     rs = np.random.RandomState(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
     os.environ["RLAP_FLOW"] = "1"
+    from rlap_amd import ops
+    warnings.simplefilter("error", ops.DataflowFallbackWarning)   # a dataflow launch that gives up ends the run
     t_end = time.time() + budget
     n_cases = n_graphs = 0
     while time.time() < t_end:
@@ -35,6 +38,7 @@ def main():
         if os.environ.get("SOAK_VERBOSE"):
             print("case", n_cases, soak.describe(c), "flow shape", shape, "waves", os.environ.get("RLAP_FLOW_WAVES", "auto"), flush=True)
         bad = soak.run_case(c)
+        c["elim_kernel"] = ops.last_stats["elim_kernel"]   # (of the case's last call)
         if bad:
             print("MISMATCH case", n_cases, soak.describe(c), "flow shape", shape, "waves", waves or "auto", bad, flush=True)
             sys.exit(1)
@@ -42,7 +46,6 @@ def main():
         n_cases += 1
         if n_cases % 10 == 0:
             print(f"[{n_cases} cases, {n_graphs} graphs checked] last: {soak.describe(c)} flow shape {shape} waves {waves or 'auto'}", flush=True)
-    from rlap_amd import ops
     ops.debug_set_jitter(0)
     ops.debug_set_poison(-1)
     print(f"flow soak ok: {n_cases} cases, {n_graphs} graphs bit-exact against the oracle in {budget:.0f} s")

@@ -6,6 +6,7 @@ import hashlib
 import os
 import sys
 import time
+import warnings
 from concurrent.futures import ThreadPoolExecutor
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -56,6 +57,7 @@ def main():
     pool = ThreadPoolExecutor(max_workers=threads)
     pending = []
     n_ok = 0
+    warnings.simplefilter("error", ops.DataflowFallbackWarning)   # a dataflow launch that gives up ends the run
 
     def settle(block):
         nonlocal n_ok
@@ -86,6 +88,7 @@ def main():
         ops.debug_set_poison(c["poison"])
         got = ops.approximate_cholesky(torch.from_numpy(ei).cuda(), None if w is None else torch.from_numpy(w).cuda(), n, c["t"], c["o_v"], c["o_n"],
                                        perm=None if perm is None else torch.from_numpy(perm), seed=c["seed"]).numpy()
+        c["elim_kernel"] = ops.last_stats["elim_kernel"]
         pending.append((c, digest(got), fut))
         settle(False)
     settle(True)

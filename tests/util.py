@@ -134,3 +134,32 @@ def introsort_killer(n):
             val[i] = state["nsolid"]
             state["nsolid"] += 1
     return np.array(val, dtype=np.float64), hit
+
+
+def wide_weights(edge_index, n, seed, decades):
+    """Tie-free symmetric weights spread over many orders of magnitude: w(a,b) = w(b,a) = 10^u, u ~ U(-decades, decades) per
+    undirected edge.  Eliminations then meet f close to 1 and new weights that round to <= 0 (the dead-entry rules) on small graphs."""
+    r, c = edge_index
+    und = np.minimum(r, c) * n + np.maximum(r, c)
+    uniq, inv = np.unique(und, return_inverse=True)
+    w = 10.0 ** np.random.RandomState(seed).uniform(-decades, decades, size=uniq.shape[0])
+    assert np.unique(w).size == w.size
+    return w[inv]
+
+
+def assert_kernel(ops, expected, what=""):
+    """The elimination kernel that produced the last call's rows (rlap_stats.elim_kernel: 0 none, 1 round kernel, 2 dataflow)."""
+    st = ops.last_stats
+    assert st["elim_kernel"] == expected, (f"{what}: elimination kernel {st['elim_kernel']}, expected {expected} "
+                                           f"(retry_causes {st['retry_causes']:#x}, flow_abort {st['flow_abort']}, n_retries {st['n_retries']})")
+
+
+def default_kernel(o_v, G, n_total):
+    """The kernel the host's default rule picks for a call of G graphs (a views call: K * G) and n_total vertices
+    (test_gpu_flow.py::test_default_kernel_choice pins the rule itself)."""
+    return 2 if o_v == "random" and (G <= 2 or (G <= 64 and n_total >= 1024 * G)) else 1
+
+
+def kernel_for(kernel, n, t):
+    """What elim_kernel reports for a single graph of n vertices with num_remove t run on `kernel`: nothing runs when no vertex goes."""
+    return kernel if min(t, n - 1) > 0 else 0
