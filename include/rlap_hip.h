@@ -178,6 +178,19 @@ int rlap_approx_chol_views(rlap_handle h, const int64_t* d_row, const int64_t* d
                            const int64_t* d_perm, uint64_t shuffle_seed, double* d_out, int64_t out_cap_rows, int64_t* h_out_ptr,
                            rlap_stats* h_stats);
 
+/* Depths: K nested Schur complements of ONE graph from one elimination.  h_num_remove[K] must be non-decreasing (zero and equal
+ * neighbours allowed; each value is clamped to n-1 as in rlap_approx_chol).  Snapshot k goes to rows [h_out_ptr[k], h_out_ptr[k+1])
+ * of d_out and equals rlap_approx_chol(..., t = h_num_remove[k]) with the same d_perm / shuffle_seed / rng mode: indices, row order
+ * and weights.  The elimination runs once, in segments [t_{k-1}, t_k), each followed by the output pass of its snapshot.
+ *   h_out_ptr    : [K+1]; out_cap_rows: K*E rows always suffice (an elimination never adds entries)
+ *   h_stats      : n_eliminated, n_draws and live_entries of the deepest snapshot, out_rows the sum over snapshots, elim_kernel
+ *                  the one kernel that ran every segment; a retry in any segment repeats the whole call
+ * Decreasing depths, K < 1 or a null pointer: RLAP_E_BAD_ARG.  Workspace: may want more than rlap_workspace_query(h, E, n, 1, 0, ...)
+ * reports for a single call -- RLAP_E_WORKSPACE then, with rlap_workspace_needed() telling how much. */
+int rlap_approx_chol_depths(rlap_handle h, const int64_t* d_row, const int64_t* d_col, const double* d_w, int64_t E, int64_t n,
+                            int64_t K, const int64_t* h_num_remove, int o_v, int o_n, const int64_t* d_perm, uint64_t shuffle_seed,
+                            double* d_out, int64_t out_cap_rows, int64_t* h_out_ptr, rlap_stats* h_stats);
+
 /* The op with the step BEFORE the path fused in (scripts/node_shared.py:326-327,
  * scripts/augmentor_benchmarks.py:77-78):
  *   symmetrize != 0 : the input holds every undirected edge in one or both directions; (b,a) is

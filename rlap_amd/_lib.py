@@ -18,7 +18,7 @@ EXPORTS = [
     "rlap_rng_uniforms", "rlap_util_ba_graph", "rlap_debug_wave_sort",
     "rlap_approx_chol_from_edges", "rlap_debug_set_limits", "rlap_pack_rows", "rlap_unpack_rows",
     "rlap_workspace_bytes", "rlap_workspace_query", "rlap_set_workspace", "rlap_workspace_needed", "rlap_debug_set_poison", "rlap_debug_set_jitter",
-    "rlap_set_rng_mode", "rlap_approx_chol_views", "rlap_debug_set_flow_limits",
+    "rlap_set_rng_mode", "rlap_approx_chol_views", "rlap_approx_chol_depths", "rlap_debug_set_flow_limits",
 ]
 
 E_WORKSPACE = 11   # RLAP_E_WORKSPACE
@@ -77,6 +77,8 @@ def load():
     lib.rlap_approx_chol_batched.restype = ci
     lib.rlap_approx_chol_batched.argtypes = [vp, vp, vp, vp, i64, i64, vp, vp, ci, ci, vp, u64, vp, i64, vp,
                                              ctypes.POINTER(Stats)]
+    lib.rlap_approx_chol_depths.restype = ci
+    lib.rlap_approx_chol_depths.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, ci, ci, vp, u64, vp, i64, vp, ctypes.POINTER(Stats)]
     lib.rlap_approx_chol_views.restype = ci
     lib.rlap_approx_chol_views.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, vp, ci, ci, vp, u64, vp, i64, vp,
                                            ctypes.POINTER(Stats)]

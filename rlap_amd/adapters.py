@@ -5,6 +5,8 @@ Mirrors of the reference's L2 adapters that keep everything on the GPU:
   * `rLapDGL`  -- DGL-style augmentor, CCA-SSG/aug.py:33-63
   * `rLapViews` -- K rLap views of one graph from one library call, with PyGCL-style
                   siblings for the `(aug1, aug2)` pair of scripts/node_shared.py:488-498
+  * `rLapDepths` -- the same graph at K removed fractions from one elimination
+                  (the sweeps of scripts/rlap_vc_spectral.py, scripts/rlap_ppr_edge_plots.py)
 PyGCL / DGL are optional: with them installed the classes return their graph types,
 without them a small named tuple with the same fields.
 """
@@ -120,6 +122,36 @@ class rLapViews:
 
     def augmentors(self):
         return [_ViewAugmentor(self, k) for k in range(len(self.fracs))]
+
+
+class rLapDepths:
+    """The graph at K removed fractions from ONE call of ops.approximate_cholesky_depths (one elimination, a snapshot at every
+    depth).  Depth k removes int(fracs[k] * num_nodes) vertices, num_nodes = edge_index.max() + 1, as rLap does; the fractions
+    are taken in the order given and must not decrease.  `.augment(g)` returns the K graphs; node ids stay in the input's space,
+    so no relabel is needed between depths.  Graph k equals rLap(fracs[k], ...).augment(g) with the same seed.
+    """
+
+    def __init__(self, fracs=(0.1, 0.2, 0.3), o_v: str = "random", o_n: str = "asc", keep_weights: bool = False, seed: Optional[int] = None,
+                 mode: str = "exact"):
+        self.fracs = tuple(float(f) for f in fracs)
+        assert len(self.fracs) >= 1
+        self.o_v, self.o_n, self.keep_weights, self.seed, self.mode = o_v, o_n, keep_weights, seed, mode
+
+    def augment(self, g):
+        x, edge_index, edge_weights = g.unfold() if hasattr(g, "unfold") else g
+        num_nodes = int(edge_index.max().item()) + 1 if edge_index.numel() else 0
+        self.num_remove = [int(f * num_nodes) for f in self.fracs]
+        sc, ptr = ops.approximate_cholesky_depths(edge_index, edge_weights, num_nodes, self.num_remove, self.o_v, self.o_n,
+                                                  seed=self.seed, return_device="same", mode=self.mode)
+        out = []
+        for k in range(len(self.fracs)):
+            part = sc[int(ptr[k]):int(ptr[k + 1])]
+            ei = part[:, :2].long().t().contiguous()
+            out.append(_as_graph(x, ei, part[:, 2].contiguous() if self.keep_weights else None))
+        return out
+
+    def __call__(self, x, edge_index, edge_weight=None):
+        return self.augment(Graph(x, edge_index, edge_weight))
 
 
 class _ViewAugmentor:

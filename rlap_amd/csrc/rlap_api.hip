@@ -228,6 +228,30 @@ __global__ void k_widen_u32(const uint32_t* __restrict__ in, int32_t N, int64_t*
     if (i < N) out[i] = (int64_t)in[i];
 }
 
+// Depths call (rlap_approx_chol_depths): before segment k, graph 0's num_remove becomes t_k (the round kernel runs to it) and, for the
+// dataflow kernel, whose positions were all queued up front, n_elim becomes the snapshot's (k_sc_perm_order reads it); -1 keeps n_elim.
+// `resume` (round kernel): 0 for the first segment, 1 for the later ones, which continue from the n_elim the previous one left.
+__global__ void k_depth_set(GraphDesc* __restrict__ gd, int64_t t, int64_t n_elim, int32_t resume) {
+    if (threadIdx.x == 0) { gd[0].t = t; if (n_elim >= 0) gd[0].n_elim = (int32_t)n_elim; gd[0].resume = resume; }
+}
+// After snapshot k's output pass: its rows end at ptr[k + 1] = ptr[k] + row_off[S]; the output pass's counters (scratch top, tier
+// counts, live entries) start from 0 for the next snapshot, whose ext / cnt sentinels (index S_next) are zeroed.  The largest scratch
+// top any snapshot asked for is kept and handed to k_collect by the last one (S_next < 0), so that a scratch retry grows enough.
+__global__ void k_depth_close(const int64_t* __restrict__ row_off, int32_t S, int64_t* __restrict__ out_ptr, int32_t k,
+                              unsigned long long* __restrict__ counters, unsigned long long* __restrict__ live, unsigned long long* __restrict__ scr_max,
+                              int32_t S_next, int32_t* __restrict__ ext, int32_t* __restrict__ cnt) {
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        out_ptr[k + 1] = out_ptr[k] + row_off[S];
+        const unsigned long long m = counters[0] > *scr_max ? counters[0] : *scr_max;
+        if (S_next >= 0) {
+            *scr_max = m;
+            for (int q = 0; q < 8; ++q) counters[q] = 0ull;
+            ext[S_next] = 0; cnt[S_next] = 0;
+        } else counters[0] = m;
+    }
+    if (S_next >= 0) for (int q = tid; q < LIVE_SLOTS * LIVE_STRIDE; q += blockDim.x) live[q] = 0ull;
+}
 
 // Host-known sizes of one call (upper bounds; what only the device knows -- nnz, row counts -- never sizes a buffer).
 struct Sizes {
@@ -292,11 +316,14 @@ size_t carve(Carver& C, const Sizes& z, WS& W) {
 }
 
 // sizes of a call on (E directed input entries, N vertices, G graphs, S surviving vertices) under the handle's growth factors
-int call_sizes(const rlap_handle h, int64_t Eeff, int64_t N, int64_t G, int64_t bucket_total, int64_t S, bool want_genperm, bool flow, int64_t nelim_total, Sizes* z) {
+// `segs` > 0 (depths call, one graph, that many segments): the round kernel reserves a fresh block of pool slots in every segment, and
+// the read-back block holds segs + 1 row pointers and the scratch maximum
+int call_sizes(const rlap_handle h, int64_t Eeff, int64_t N, int64_t G, int64_t bucket_total, int64_t S, bool want_genperm, bool flow, int64_t nelim_total, Sizes* z,
+               int64_t segs = 0) {
     const double pool_factor = h->dbg_pool >= 0 ? h->dbg_pool : h->pool_factor;
     const double log_factor = h->dbg_log >= 0 ? h->dbg_log : h->log_factor;
     const int64_t nnz_ub = Eeff;
-    const int64_t pool = (int64_t)(pool_factor * nnz_ub) + (h->dbg_pool >= 0 ? 0 : 16 * N + 1024) + G * (G <= 512 ? (int64_t)POOL_GRAB_BIG : (int64_t)POOL_GRAB_SMALL);
+    const int64_t pool = (int64_t)(pool_factor * nnz_ub) + (h->dbg_pool >= 0 ? 0 : 16 * N + 1024) + (G + std::max<int64_t>(segs - 1, 0)) * (G <= 512 ? (int64_t)POOL_GRAB_BIG : (int64_t)POOL_GRAB_SMALL);
     z->G = G; z->N = N; z->Eeff = Eeff; z->S = S; z->bucket_total = bucket_total;
     z->slot_cap = nnz_ub + pool;
     if (z->slot_cap >= ((int64_t)1 << 31) - 64) return RLAP_E_TOO_LARGE;
@@ -304,7 +331,7 @@ int call_sizes(const rlap_handle h, int64_t Eeff, int64_t N, int64_t G, int64_t 
     z->scr_total = nnz_ub / 2 + 8 * G + 8;
     if (bucket_total * BDIR >= ((int64_t)1 << 40) || bucket_total >= ((int64_t)1 << 31) || z->log_total >= ((int64_t)1 << 31)) return RLAP_E_TOO_LARGE;
     z->scr_budget = h->dbg_scr >= 0 ? h->dbg_scr : h->scr_budget;
-    z->res_bytes = sizeof(CallResults) + 8 * (size_t)(G + 1);
+    z->res_bytes = sizeof(CallResults) + 8 * (size_t)(G + 1) + (segs > 0 ? 8 * (size_t)(segs + 1) : 0);
     z->want_genperm = want_genperm;
     z->flow = flow;
     z->flow_Q = nelim_total + G;
@@ -327,6 +354,7 @@ struct Call {
     double* d_out; int64_t out_cap; int64_t* h_out_row_ptr; rlap_stats* st;
     int symmetrize;
     int64_t K = 1;   // views (rlap_approx_chol_views): h_node_ptr / h_t describe the K-fold union, the device input is ONE copy of it
+    const int64_t* h_depths = nullptr; int64_t D = 0;   // depths (rlap_approx_chol_depths): one graph, D non-decreasing num_remove (h_t = the last)
 };
 
 // One attempt.  No host synchronisation until the single read-back at the end: every size is an upper bound
@@ -374,11 +402,20 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
         surv_base[g + 1] = surv_base[g] + (n - ne);
     }
     const int64_t S = surv_base[G];
+    // depths call: segment k eliminates positions [ne[k-1], ne[k]) and snapshot k has S_k = n - ne[k] survivors (the first is the largest)
+    const bool depths = c.D > 0;
+    const int64_t nseg = depths ? c.D : 1;
+    std::vector<int64_t> seg_ne((size_t)nseg, nelim_total);
+    if (depths) {
+        if (G != 1) return RLAP_E_BAD_ARG;
+        for (int64_t k = 0; k < nseg; ++k) seg_ne[(size_t)k] = std::max<int64_t>(0, std::min<int64_t>(c.h_depths[k], N - 1));
+    }
+    const int64_t S0 = depths ? N - seg_ne[0] : S;
     st.n_eliminated = nelim_total;
     Sizes z;
     const bool flow = flow_wanted(h, c.o_v, G, N);
     st.elim_kernel = nelim_total > 0 ? (flow ? 2 : 1) : 0;
-    { int rc = call_sizes(h, Eeff, N, G, bucket_total, S, c.o_v == OV_RANDOM && !c.d_perm, flow, nelim_total, &z); if (rc) return rc; }
+    { int rc = call_sizes(h, Eeff, N, G, bucket_total, S0, c.o_v == OV_RANDOM && !c.d_perm, flow, nelim_total, &z, depths ? nseg : 0); if (rc) return rc; }
     const int64_t slot_cap = z.slot_cap, log_total = z.log_total, scr_total = z.scr_total, scr_budget = z.scr_budget;
     const size_t res_bytes = z.res_bytes;
 
@@ -443,7 +480,8 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
         }
         F.add(W.bs_pool_top.p, 1, 0);
         F.add(W.batch_pos.p, N, -1);
-        F.add(W.ext.as<int32_t>() + S, 1, 0); F.add(W.cnt.as<int32_t>() + S, 1, 0);
+        F.add(W.ext.as<int32_t>() + S0, 1, 0); F.add(W.cnt.as<int32_t>() + S0, 1, 0);
+        if (depths) F.add(reinterpret_cast<CallResults*>(W.results.p) + 1, 2 * (nseg + 2), 0);   // row pointers of the snapshots, scratch maximum
         if (G == 1) F.add(W.vgraph.p, N, 0);
         F.launch(s);
     }
@@ -578,12 +616,16 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
     const bool wide = c.o_v == OV_RANDOM && nnz_ub >= 12 * N && N >= 512;
     FlowArrays FA;
     std::memset(&FA, 0, sizeof(FA));
+    FlowParams FP;
+    std::memset(&FP, 0, sizeof(FP));
+    int shape = 1;
+    unsigned grid = 0;
+    GraphDesc* gd_d = W.gd_d.as<GraphDesc>();
     if (flow) {
         // dataflow elimination (rlap_flow.hip): every position of the order is one wave's, on any compute unit
         FA.cdir = W.f_cdir.as<int32_t>(); FA.atag = W.f_atag.as<int32_t>(); FA.lb = W.f_lb.as<unsigned long long>();
         FA.qv = W.f_qv.as<int32_t>(); FA.qg = W.f_qg.as<int32_t>(); FA.ctrl = W.f_ctrl.as<int32_t>(); FA.Q = (int32_t)z.flow_Q;
-        FlowParams FP;
-        FP.vgraph = W.vgraph.as<int32_t>(); FP.gd = W.gd_d.as<GraphDesc>(); FP.in_flags = flags; FP.in_acc = acc;
+        FP.vgraph = W.vgraph.as<int32_t>(); FP.gd = gd_d; FP.in_flags = flags; FP.in_acc = acc;
         FP.scr = W.f_scr.as<char>(); FP.scr_entries = (int32_t)z.flow_scr;
         FP.spin_limit = 4000; FP.jitter = h->jitter; FP.poison = h->poison;
         FP.prof = ES.prof;
@@ -605,80 +647,117 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
             if (rc) return rc;
             FA.qorder = W.sval1.as<uint32_t>(); FA.Qclaim = (int32_t)nelim_total;
         }
-        int shape = G >= 48 ? 3 : 1;   // 1: 76 KB of LDS, two workgroups per CU, four waves each (three help with long sorts); 4: the same with one wave; 3: 40 KB, four; 2: 17 KB, eight
+        shape = G >= 48 ? 3 : 1;   // 1: 76 KB of LDS, two workgroups per CU, four waves each (three help with long sorts); 4: the same with one wave; 3: 40 KB, four; 2: 17 KB, eight
         if (const char* e = std::getenv("RLAP_FLOW_SHAPE")) { if (e[0] >= '1' && e[0] <= '4') shape = e[0] - '0'; }   // diagnostic override
-        unsigned grid = (shape == 2 ? 8u : shape == 3 ? 4u : 2u) * (unsigned)h->n_cu;   // (workgroups: one position each)
+        grid = (shape == 2 ? 8u : shape == 3 ? 4u : 2u) * (unsigned)h->n_cu;   // (workgroups: one position each)
         if (const char* e = std::getenv("RLAP_FLOW_WAVES")) grid = (unsigned)std::max(1, std::atoi(e));
-        launch_flow_eliminate(shape, grid, s, A, FA, FP);
-        launch_flow_finish(s, A, FA, W.gd_d.as<GraphDesc>(), (int32_t)N, (int32_t)G);
-    } else
-    launch_eliminate_batch(c.o_v, c.o_n, (unsigned)G, h->n_cu, s, A, W.gd_d.as<GraphDesc>(), ES, W.batch_pos.as<int32_t>(), flags, acc, wide);
-    HIPCHK(hipGetLastError());
-    if (h->timing) HIPCHK(hipEventRecord(h->ev[2], s));
-
-    // ---------------- output ----------------
-    uint32_t* order = nullptr;
-    if (c.o_v == OV_RANDOM) {
-        hipLaunchKernelGGL(k_sc_perm_order, dim3(nblk(N, 256)), dim3(256), 0, s, d_perm, W.vgraph.as<int32_t>(), W.gd_d.as<GraphDesc>(),
-                           W.surv_base_d.as<int64_t>(), (int32_t)N, W.sval1.as<uint32_t>());
-        order = W.sval1.as<uint32_t>();
-        if (flow && S > 0 && Eeff > 0) {
-            // tag order of the surviving columns: concurrent eliminations pushed into them out of order (rlap_flow.h)
-            const int32_t ro_cap = (int32_t)(h->dbg_ro_cap >= 0 ? std::max<int64_t>(1, std::min<int64_t>(h->dbg_ro_cap, Eeff)) : Eeff);   // (test hook: smaller)
-            launch_flow_ro_count(s, A, FA, order, (int32_t)S, W.f_rocnt.as<int32_t>());
-            { int rc = excl_scan(h, ST, W.f_rocnt.as<int32_t>(), W.f_rooff.as<int32_t>(), S + 1); if (rc) return rc; }
-            uint32_t* home = reinterpret_cast<uint32_t*>(W.head.p);
-            launch_flow_ro_emit(s, A, FA, order, (int32_t)S, W.f_rooff.as<int32_t>(), W.keys0.as<uint64_t>(), W.idx0.as<uint32_t>(), home, ro_cap, &W.gd_d.as<GraphDesc>()[0].status);
-            const unsigned kb = bits_for((uint64_t)std::max<int64_t>(S - 1, 1)) + 32u;
-            { int rc = sort_pairs(h, ST, W.keys0.as<uint64_t>(), W.keys1.as<uint64_t>(), W.idx0.as<uint32_t>(), W.idx1.as<uint32_t>(), ro_cap, 0, std::min(64u, kb)); if (rc) return rc; }
-            launch_flow_ro_permute(s, A, FA, W.f_rooff.as<int32_t>(), (int32_t)S, W.idx1.as<uint32_t>(), W.keys1.as<uint64_t>(), home, ro_cap, reinterpret_cast<Slot*>(W.tmp_val.p));
-            HIPCHK(hipGetLastError());
-        }
-    } else {
-        hipLaunchKernelGGL(k_sc_keys, dim3(nblk(N, 256)), dim3(256), 0, s, W.vrec.as<VRec>(), W.origpos.as<int32_t>(),
-                           W.vgraph.as<int32_t>(), W.gd_d.as<GraphDesc>(), (int32_t)N, W.skey0.as<uint64_t>(), W.sval0.as<uint32_t>());
-        // key = bucket << 32 | order, all ones for eliminated vertices
-        int rc = sort_pairs(h, ST, W.skey0.as<uint64_t>(), W.skey1.as<uint64_t>(), W.sval0.as<uint32_t>(), W.sval1.as<uint32_t>(), N, 0, 64);
-        if (rc) return rc;
-        order = W.sval1.as<uint32_t>();
     }
-    if (S > 0)
-        hipLaunchKernelGGL(k_sc_ext, dim3(nblk(S, 256)), dim3(256), 0, s, order, W.colptr.as<int32_t>(), W.vrec.as<VRec>(), (int32_t)S, flags, acc, W.ext.as<int32_t>());
-    { int rc = excl_scan(h, ST, W.ext.as<int32_t>(), W.tmp_off.as<int64_t>(), S + 1); if (rc) return rc; }
-    ScScratch SS;
-    SS.rec = W.sc_rec.as<SRec>(); SS.i32 = W.sc_i32.as<int32_t>(); SS.f64 = W.sc_f64.as<double>(); SS.cap = scr_budget; SS.top = counters + 0; SS.flags = flags;
-    if (h->timing) HIPCHK(hipEventRecord(h->ev[3], s));
-    if (S > 0) {
-        int32_t* tiercounts = reinterpret_cast<int32_t*>(counters + 4);   // 8 ints: tiers 0..7
-        if (!h->big_attr_set) {
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sc_merge_big), hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS_BYTES));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sc_merge_mw<8>), hipFuncAttributeMaxDynamicSharedMemorySize, MW_BIG_LDS_BYTES));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sc_merge_mw<4>), hipFuncAttributeMaxDynamicSharedMemorySize, MW_MID_LDS_BYTES));
-            h->big_attr_set = true;
-        }
-        ScLaunch X;
-        X.main = s; X.side[0] = h->side[0]; X.side[1] = h->side[1];
-        for (int q = 0; q < 3; ++q) X.ev[q] = h->fork_ev[q];
-        launch_sc_merge(X, A, W.gd_d.as<GraphDesc>(), W.vgraph.as<int32_t>(), order, W.ext.as<int32_t>(), W.tmp_off.as<int64_t>(), (int32_t)S,
-                        W.tmp_nbr.as<int32_t>(), W.tmp_val.as<double>(), W.cnt.as<int32_t>(), SS, live, W.biglist.as<int32_t>(), tiercounts,
-                        W.hugelists.as<uint16_t>());
-        HIPCHK(hipGetLastError());
-    }
-    if (h->timing) HIPCHK(hipEventRecord(h->ev[4], s));
-    { int rc = excl_scan(h, ST, W.cnt.as<int32_t>(), W.row_off.as<int64_t>(), S + 1); if (rc) return rc; }
-    if (h->timing) HIPCHK(hipEventRecord(h->ev[5], s));
-    if (S > 0 && c.out_cap > 0) {
-        const int64_t rows_ub = std::min<int64_t>(c.out_cap, slot_cap);
-        unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows_ub + 255) / 256, 256 * 8));
-        hipLaunchKernelGGL(k_sc_compact, dim3(grid), dim3(256), 0, s, order, W.cnt.as<int32_t>(), W.row_off.as<int64_t>(), W.tmp_off.as<int64_t>(),
-                           W.tmp_nbr.as<int32_t>(), W.tmp_val.as<double>(), (int32_t)S, c.d_out, c.out_cap, K > 1 ? (int32_t)N1 : 0);
-        HIPCHK(hipGetLastError());
-    }
-    if (h->timing) HIPCHK(hipEventRecord(h->ev[6], s));
-    // ---------------- the one read-back ----------------
     CallResults* res_d = W.results.as<CallResults>();
     int64_t* out_ptr_d = reinterpret_cast<int64_t*>(res_d + 1);
-    hipLaunchKernelGGL(k_graph_rows, dim3(nblk(G + 1, 256)), dim3(256), 0, s, W.surv_base_d.as<int64_t>(), W.row_off.as<int64_t>(), (int32_t)G, out_ptr_d);
+    unsigned long long* scr_max_d = reinterpret_cast<unsigned long long*>(out_ptr_d + nseg + 1);   // (depths call only)
+    ScScratch SS;
+    SS.rec = W.sc_rec.as<SRec>(); SS.i32 = W.sc_i32.as<int32_t>(); SS.f64 = W.sc_f64.as<double>(); SS.cap = scr_budget; SS.top = counters + 0; SS.flags = flags;
+    const int32_t* stop_d = depths ? &gd_d[0].status : nullptr;
+    // One segment for the other calls.  A depths call runs the elimination in segments [ne[k-1], ne[k]), each followed by the output
+    // pass of its snapshot: the state a segment stops in is the state the next one starts from.
+    for (int64_t seg = 0; seg < nseg; ++seg) {
+        const int64_t ne_lo = seg > 0 ? seg_ne[(size_t)seg - 1] : 0, ne_hi = seg_ne[(size_t)seg];
+        const int64_t Sk = depths ? N - ne_hi : S;
+        const bool last = seg + 1 == nseg;
+        const bool run_seg = seg == 0 || ne_hi > ne_lo;   // (an equal depth: the state is already the snapshot's)
+        if (depths && run_seg)
+            hipLaunchKernelGGL(k_depth_set, dim3(1), dim3(64), 0, s, gd_d, c.h_depths[seg], flow ? ne_hi : (int64_t)-1, seg > 0 ? 1 : 0);
+        if (run_seg) {
+            if (flow) {
+                if (depths) {
+                    FA.Qclaim = (int32_t)(ne_hi + 1);   // look-back index of position p: p + 1 (graph 0's sentinel first)
+                    if (seg > 0) launch_flow_segment(s, FA, (int32_t)(ne_lo + 1), &gd_d[0].status);
+                }
+                launch_flow_eliminate(shape, grid, s, A, FA, FP);
+                launch_flow_finish(s, A, FA, gd_d, (int32_t)N, (int32_t)G);
+            } else {
+                launch_eliminate_batch(c.o_v, c.o_n, (unsigned)G, h->n_cu, s, A, gd_d, ES, W.batch_pos.as<int32_t>(), flags, acc, wide);
+            }
+            HIPCHK(hipGetLastError());
+        }
+        if (h->timing) HIPCHK(hipEventRecord(h->ev[2], s));
+
+        // ---------------- output ----------------
+        uint32_t* order = nullptr;
+        bool permuted = false;   // the dataflow kernel's surviving columns were put into tag order in place
+        const int32_t ro_cap = (int32_t)(h->dbg_ro_cap >= 0 ? std::max<int64_t>(1, std::min<int64_t>(h->dbg_ro_cap, Eeff)) : Eeff);   // (test hook: smaller)
+        uint32_t* home = reinterpret_cast<uint32_t*>(W.head.p);
+        if (c.o_v == OV_RANDOM) {
+            hipLaunchKernelGGL(k_sc_perm_order, dim3(nblk(N, 256)), dim3(256), 0, s, d_perm, W.vgraph.as<int32_t>(), gd_d,
+                               W.surv_base_d.as<int64_t>(), (int32_t)N, W.sval1.as<uint32_t>());
+            order = W.sval1.as<uint32_t>();
+            if (flow && Sk > 0 && Eeff > 0) {
+                // tag order of the surviving columns: concurrent eliminations pushed into them out of order (rlap_flow.h)
+                launch_flow_ro_count(s, A, FA, order, (int32_t)Sk, W.f_rocnt.as<int32_t>());
+                { int rc = excl_scan(h, ST, W.f_rocnt.as<int32_t>(), W.f_rooff.as<int32_t>(), Sk + 1); if (rc) return rc; }
+                launch_flow_ro_emit(s, A, FA, order, (int32_t)Sk, W.f_rooff.as<int32_t>(), W.keys0.as<uint64_t>(), W.idx0.as<uint32_t>(), home, ro_cap, &gd_d[0].status);
+                const unsigned kb = bits_for((uint64_t)std::max<int64_t>(Sk - 1, 1)) + 32u;
+                { int rc = sort_pairs(h, ST, W.keys0.as<uint64_t>(), W.keys1.as<uint64_t>(), W.idx0.as<uint32_t>(), W.idx1.as<uint32_t>(), ro_cap, 0, std::min(64u, kb)); if (rc) return rc; }
+                launch_flow_ro_permute(s, A, FA, W.f_rooff.as<int32_t>(), (int32_t)Sk, W.idx1.as<uint32_t>(), W.keys1.as<uint64_t>(), home, ro_cap, reinterpret_cast<Slot*>(W.tmp_val.p));
+                HIPCHK(hipGetLastError());
+                permuted = true;
+            }
+        } else {
+            hipLaunchKernelGGL(k_sc_keys, dim3(nblk(N, 256)), dim3(256), 0, s, W.vrec.as<VRec>(), W.origpos.as<int32_t>(),
+                               W.vgraph.as<int32_t>(), gd_d, (int32_t)N, W.skey0.as<uint64_t>(), W.sval0.as<uint32_t>());
+            // key = bucket << 32 | order, all ones for eliminated vertices
+            int rc = sort_pairs(h, ST, W.skey0.as<uint64_t>(), W.skey1.as<uint64_t>(), W.sval0.as<uint32_t>(), W.sval1.as<uint32_t>(), N, 0, 64);
+            if (rc) return rc;
+            order = W.sval1.as<uint32_t>();
+        }
+        if (Sk > 0)
+            hipLaunchKernelGGL(k_sc_ext, dim3(nblk(Sk, 256)), dim3(256), 0, s, order, W.colptr.as<int32_t>(), W.vrec.as<VRec>(), (int32_t)Sk, flags, acc, W.ext.as<int32_t>(), stop_d);
+        { int rc = excl_scan(h, ST, W.ext.as<int32_t>(), W.tmp_off.as<int64_t>(), Sk + 1); if (rc) return rc; }
+        if (h->timing) HIPCHK(hipEventRecord(h->ev[3], s));
+        if (Sk > 0) {
+            int32_t* tiercounts = reinterpret_cast<int32_t*>(counters + 4);   // 8 ints: tiers 0..7
+            if (!h->big_attr_set) {
+                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sc_merge_big), hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS_BYTES));
+                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sc_merge_mw<8>), hipFuncAttributeMaxDynamicSharedMemorySize, MW_BIG_LDS_BYTES));
+                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sc_merge_mw<4>), hipFuncAttributeMaxDynamicSharedMemorySize, MW_MID_LDS_BYTES));
+                h->big_attr_set = true;
+            }
+            ScLaunch X;
+            X.main = s; X.side[0] = h->side[0]; X.side[1] = h->side[1];
+            for (int q = 0; q < 3; ++q) X.ev[q] = h->fork_ev[q];
+            launch_sc_merge(X, A, gd_d, W.vgraph.as<int32_t>(), order, W.ext.as<int32_t>(), W.tmp_off.as<int64_t>(), (int32_t)Sk,
+                            W.tmp_nbr.as<int32_t>(), W.tmp_val.as<double>(), W.cnt.as<int32_t>(), SS, live, W.biglist.as<int32_t>(), tiercounts,
+                            W.hugelists.as<uint16_t>());
+            HIPCHK(hipGetLastError());
+        }
+        if (h->timing) HIPCHK(hipEventRecord(h->ev[4], s));
+        { int rc = excl_scan(h, ST, W.cnt.as<int32_t>(), W.row_off.as<int64_t>(), Sk + 1); if (rc) return rc; }
+        if (h->timing) HIPCHK(hipEventRecord(h->ev[5], s));
+        if (Sk > 0 && c.out_cap > 0) {
+            const int64_t rows_ub = std::min<int64_t>(c.out_cap, slot_cap);
+            unsigned cgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows_ub + 255) / 256, 256 * 8));
+            hipLaunchKernelGGL(k_sc_compact, dim3(cgrid), dim3(256), 0, s, order, W.cnt.as<int32_t>(), W.row_off.as<int64_t>(), W.tmp_off.as<int64_t>(),
+                               W.tmp_nbr.as<int32_t>(), W.tmp_val.as<double>(), (int32_t)Sk, c.d_out, c.out_cap, K > 1 ? (int32_t)N1 : 0,
+                               depths ? (const int64_t*)(out_ptr_d + seg) : (const int64_t*)nullptr);
+            HIPCHK(hipGetLastError());
+        }
+        if (depths) {
+            // the next segment continues from the elimination's own state: the tag-order permutation is undone (the same kernels with
+            // source and destination swapped; home, the sorted slots and their tags are buffers the output pass leaves alone, and the
+            // staging copy is free again), so that every twin link points where it did
+            if (permuted && !last) {
+                launch_flow_ro_permute(s, A, FA, W.f_rooff.as<int32_t>(), (int32_t)Sk, home, W.keys1.as<uint64_t>(), W.idx1.as<uint32_t>(), ro_cap, reinterpret_cast<Slot*>(W.tmp_val.p));
+                HIPCHK(hipGetLastError());
+            }
+            hipLaunchKernelGGL(k_depth_close, dim3(1), dim3(256), 0, s, W.row_off.as<int64_t>(), (int32_t)Sk, out_ptr_d, (int32_t)seg, counters, live, scr_max_d,
+                               last ? -1 : (int32_t)(N - seg_ne[(size_t)seg + 1]), W.ext.as<int32_t>(), W.cnt.as<int32_t>());
+            HIPCHK(hipGetLastError());
+        }
+        if (h->timing) HIPCHK(hipEventRecord(h->ev[6], s));
+    }
+    // ---------------- the one read-back ----------------
+    if (!depths)
+        hipLaunchKernelGGL(k_graph_rows, dim3(nblk(G + 1, 256)), dim3(256), 0, s, W.surv_base_d.as<int64_t>(), W.row_off.as<int64_t>(), (int32_t)G, out_ptr_d);
     hipLaunchKernelGGL(k_collect, dim3(1), dim3(256), 0, s, flags, acc, nnz_p, counters, live, W.tmp_off.as<int64_t>(), W.row_off.as<int64_t>(), (int32_t)S,
                        W.gd_d.as<GraphDesc>(), (int32_t)G, W.pool_top.as<int32_t>(), W.bs_pool_top.as<int32_t>(), flow ? W.f_ctrl.as<int32_t>() + FC_REASON : nullptr, res_d);
     HIPCHK(hipMemcpyAsync(h->h_results, W.results.p, res_bytes, hipMemcpyDeviceToHost, s));
@@ -716,7 +795,8 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
     st.nnz = R.nnz;
     st.n_draws = R.n_draws;
     st.n_rounds = R.rounds; st.n_singles = R.singles;
-    st.out_rows = R.m_total;
+    const int64_t m_total = depths ? out_ptr_h[nseg] : R.m_total;   // (depths: the rows of all snapshots)
+    st.out_rows = m_total;
     st.live_entries = R.live_total;
     if (flow && R.status == ST_INTERNAL) *flow_abort = R.flow_abort;
     if (h->timing) {
@@ -744,8 +824,9 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
     }
     if (R.flags[FLAG_SCR]) { *retry_kind = 4; *retry_need = R.scr_need; return RLAP_E_INTERNAL; }
     if (swapped && R.acc[0] != 0.0) { *retry_kind = 5; return RLAP_E_INTERNAL; }   // symmetric only within the tolerance: repeat, reading the input as given
-    for (int64_t g = 0; g <= G; ++g) c.h_out_row_ptr[g] = out_ptr_h[g];
-    if (R.m_total > c.out_cap) { c.h_out_row_ptr[G] = R.m_total; return RLAP_E_OUT_OVERFLOW; }
+    const int64_t nptr = depths ? nseg : G;
+    for (int64_t g = 0; g <= nptr; ++g) c.h_out_row_ptr[g] = out_ptr_h[g];
+    if (m_total > c.out_cap) { c.h_out_row_ptr[nptr] = m_total; return RLAP_E_OUT_OVERFLOW; }
     return RLAP_OK;
 }
 
@@ -986,6 +1067,26 @@ int rlap_approx_chol_views(rlap_handle h, const int64_t* d_row, const int64_t* d
         for (int64_t g = 0; g < G; ++g) np[(size_t)(k * G + g)] = k * N + h_node_ptr[g];
     np[(size_t)(K * G)] = K * N;
     Call c{d_row, d_col, d_w, E, K * G, np.data(), h_num_remove, o_v, o_n, d_perm, shuffle_seed, d_out, out_cap_rows, h_out_ptr, h_stats, 0, K};
+    return run_call(h, c);
+}
+
+int rlap_approx_chol_depths(rlap_handle h, const int64_t* d_row, const int64_t* d_col, const double* d_w, int64_t E, int64_t n,
+                            int64_t K, const int64_t* h_num_remove, int o_v, int o_n, const int64_t* d_perm, uint64_t shuffle_seed,
+                            double* d_out, int64_t out_cap_rows, int64_t* h_out_ptr, rlap_stats* h_stats) {
+    if (!h || K < 1 || E < 0 || n < 0 || !h_num_remove || !h_out_ptr) return RLAP_E_BAD_ARG;
+    if (o_v < 0 || o_v > 2 || o_n < 0 || o_n > 2) return RLAP_E_BAD_ARG;
+    if (E > 0 && (!d_row || !d_col)) return RLAP_E_BAD_ARG;
+    if (out_cap_rows > 0 && !d_out) return RLAP_E_BAD_ARG;
+    for (int64_t k = 1; k < K; ++k) if (h_num_remove[k] < h_num_remove[k - 1]) return RLAP_E_BAD_ARG;
+    if (K >= (int64_t)1 << 30) return RLAP_E_TOO_LARGE;
+    if (n == 0) {   // (no vertices: K empty snapshots)
+        for (int64_t k = 0; k <= K; ++k) h_out_ptr[k] = 0;
+        if (h_stats) std::memset(h_stats, 0, sizeof(*h_stats));
+        return RLAP_OK;
+    }
+    int64_t node_ptr[2] = {0, n};
+    Call c{d_row, d_col, d_w, E, 1, node_ptr, h_num_remove + (K - 1), o_v, o_n, d_perm, shuffle_seed, d_out, out_cap_rows, h_out_ptr, h_stats, 0, 1,
+           h_num_remove, K};
     return run_call(h, c);
 }
 

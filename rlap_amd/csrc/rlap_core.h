@@ -322,7 +322,7 @@ struct GraphDesc {      // one per graph of a batch
     int64_t n_draws;
     int64_t out_rows;   // rows this graph emits (filled by the output pass)
     int32_t flow_base;  // dataflow elimination (rlap_flow.h): look-back index of this graph's sentinel; its positions follow
-    int32_t pad2;
+    int32_t resume;     // 0: the round kernel starts at position 0; 1: a later segment of a depths call, continuing from n_elim
 };
 
 struct ColBuf {         // working storage for one column (LDS or global scratch)

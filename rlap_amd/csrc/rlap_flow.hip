@@ -1056,6 +1056,16 @@ __global__ void k_flow_pending(const Slot* __restrict__ ent, const int32_t* __re
         if (pu < pa && pa != FPOS_NONE) atomicAdd(&vr[e.nbr].key, 1);
     }
 }
+// a depths call's segment [claim_start - 1, Qclaim - 1) of positions (look-back index = position + 1 behind graph 0's sentinel):
+// claims continue at its first position.  The long-column scratch is free again (nothing is in flight between launches) and no
+// very long column is being worked on.  Kept: FC_ABORT and FC_REASON, FC_LONG (counted over the call), FC_PROGRESS (the stall
+// watchdog only compares it with itself).  Pending counters, look-back words, the chunk directory and the tags persist in their
+// own arrays.  After a failed segment (graph 0's status: k_flow_finish files FC_ABORT there, the reorder pass its own) the claim
+// counter starts beyond every position: each wave's first claim ends its loop, through the kernel's one way out.
+__global__ void k_flow_segment(int32_t* __restrict__ ctrl, int32_t claim_start, const int32_t* __restrict__ status) {
+    if (threadIdx.x == 0) { ctrl[FC_CLAIM] = *status != 0 ? FLOW_CLAIM_STOP : claim_start; ctrl[FC_SCR] = 0; ctrl[FC_HEAVY] = 0; }
+}
+
 // afterwards: header links + VRec::app_chunk (the layout the output pass reads), per-graph status
 __global__ void k_flow_finish(Arrays A, FlowArrays F, GraphDesc* __restrict__ gd, int32_t N, int32_t G) {
     const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1193,6 +1203,10 @@ void launch_flow_eliminate(int shape, unsigned grid, hipStream_t stream, const A
     else if (shape == 3) hipLaunchKernelGGL((k_eliminate_flow<FLOW_EC_MID, 1, 1>), dim3(grid), dim3(64), 0, stream, A, F, P);
     else if (shape == 4) hipLaunchKernelGGL((k_eliminate_flow<FLOW_EC, 1, 1>), dim3(grid), dim3(64), 0, stream, A, F, P);
     else hipLaunchKernelGGL((k_eliminate_flow<FLOW_EC, 1, FLOW_NW>), dim3(grid), dim3(64 * FLOW_NW), 0, stream, A, F, P);
+}
+
+void launch_flow_segment(hipStream_t s, const FlowArrays& F, int32_t claim_start, const int32_t* status) {
+    hipLaunchKernelGGL(k_flow_segment, dim3(1), dim3(64), 0, s, F.ctrl, claim_start, status);
 }
 
 void launch_flow_finish(hipStream_t s, const Arrays& A, const FlowArrays& F, GraphDesc* gd, int32_t N, int32_t G) {

@@ -138,6 +138,8 @@ void launch_flow_setup(hipStream_t s, const Arrays& A, const FlowArrays& F, cons
                        uint64_t* okey, uint32_t* oval, int gbits);
 void launch_flow_eliminate(int shape, unsigned grid, hipStream_t stream, const Arrays& A, const FlowArrays& F, const FlowParams& P);
 void launch_debug_flow_sort(hipStream_t s, const double* keys, const int32_t* offs, int32_t narr, int32_t desc, int32_t* perm_out, char* scr);
+constexpr int32_t FLOW_CLAIM_STOP = 1 << 30;   // a claim counter beyond every position (N < 2^30; at most a few thousand waves add to it)
+void launch_flow_segment(hipStream_t s, const FlowArrays& F, int32_t claim_start, const int32_t* status);
 void launch_flow_finish(hipStream_t s, const Arrays& A, const FlowArrays& F, GraphDesc* gd, int32_t N, int32_t G);
 void launch_flow_ro_count(hipStream_t s, const Arrays& A, const FlowArrays& F, const uint32_t* order, int32_t S, int32_t* cnt);
 void launch_flow_ro_emit(hipStream_t s, const Arrays& A, const FlowArrays& F, const uint32_t* order, int32_t S, const int32_t* off, uint64_t* keys, uint32_t* vals,
@@ -148,7 +150,8 @@ __global__ void k_sc_keys(const VRec* vr, const int32_t* origpos, const int32_t*
                           int32_t N, uint64_t* skey, uint32_t* sval);
 __global__ void k_sc_perm_order(const int64_t* perm, const int32_t* vgraph, const GraphDesc* gd, const int64_t* surv_base, int32_t N,
                                 uint32_t* order);
-__global__ void k_sc_ext(const uint32_t* order, const int32_t* colptr, const VRec* vr, int32_t S, const int32_t* in_flags, const double* in_acc, int32_t* ext);
+__global__ void k_sc_ext(const uint32_t* order, const int32_t* colptr, const VRec* vr, int32_t S, const int32_t* in_flags, const double* in_acc, int32_t* ext,
+                         const int32_t* stop);
 constexpr unsigned NHUGE = 32;   // workgroups of k_sc_merge_huge
 struct ScLaunch { hipStream_t main; hipStream_t side[2]; hipEvent_t ev[3]; };   // side streams may be null: everything on `main`
 template <int NW>
@@ -165,7 +168,8 @@ __global__ void k_sc_merge_huge(Arrays A, const GraphDesc* gd, const int32_t* vg
                                 int32_t* tmp_nbr, double* tmp_val, int32_t* cnt_out, unsigned long long* live_total, uint16_t* lists, SRec* scratch,
                                 unsigned long long* scratch_top, int64_t scratch_cap, int32_t* flags);
 __global__ void k_sc_compact(const uint32_t* order, const int32_t* cnt, const int64_t* row_off, const int64_t* tmp_off,
-                             const int32_t* tmp_nbr, const double* tmp_val, int32_t S, double* out, int64_t out_cap, int32_t id_mod);
+                             const int32_t* tmp_nbr, const double* tmp_val, int32_t S, double* out, int64_t out_cap, int32_t id_mod,
+                             const int64_t* row_base);
 __global__ void k_graph_rows(const int64_t* surv_base, const int64_t* row_off, int32_t G, int64_t* out_ptr);
 
 }  // namespace rlap

@@ -1646,6 +1646,15 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
     if (nelim < 0 || s_status != 0) nelim = 0;
     int64_t done = 0;
     int32_t rounds = 0, singles = 0;
+    if (G.resume) {
+        // a later segment of a depths call: every round ends in a state the next round starts from (the PQ cursors move only for
+        // committed pops and empty buckets, uncommitted candidates leave nothing behind but batch_pos, cleared in the epilogue), so
+        // the loop picks up at the previous launch's n_elim.  The LDS-only state starts afresh: the pool reservation (its unused
+        // slots are lost: the depths call sizes the pool for it), the chunk directory cache, and `pending_long` -- a long column
+        // that cut the last round is popped first again and goes to the single-vertex path as first_is_big.
+        done = G.n_elim; rounds = G.pad0; singles = G.pad1;
+        if (G.status != 0 || nelim < done) nelim = done;   // an earlier segment failed (or the depth did not grow): nothing to do
+    }
     bool pending_long = false;   // o_v = random: the last round was cut by a long column, which is therefore the next vertex
     long long t_prev = 0;
     __shared__ long long s_prof[40];   // diagnostic build only (S.prof != nullptr)
@@ -2999,10 +3008,13 @@ __global__ void k_sc_perm_order(const int64_t* __restrict__ perm, const int32_t*
 // the extent 0: the output pass then stages and writes nothing -- an invalid node_id vector can name one hub S times, which would
 // run past the staging arrays (sized one row per slot in use).
 __global__ void k_sc_ext(const uint32_t* __restrict__ order, const int32_t* __restrict__ colptr, const VRec* __restrict__ vr,
-                         int32_t S, const int32_t* __restrict__ in_flags, const double* __restrict__ in_acc, int32_t* __restrict__ ext) {
+                         int32_t S, const int32_t* __restrict__ in_flags, const double* __restrict__ in_acc, int32_t* __restrict__ ext,
+                         const int32_t* __restrict__ stop) {
     int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= S) return;
-    const bool bad = in_flags[FLAG_RANGE] || in_flags[FLAG_CROSS] || in_flags[FLAG_PERM] || in_acc[2] != 0.0 || !(in_acc[0] <= 1e-24 * in_acc[1]);
+    // (stop: a depths call's status word -- after a failed segment the later snapshots stage nothing either)
+    const bool bad = in_flags[FLAG_RANGE] || in_flags[FLAG_CROSS] || in_flags[FLAG_PERM] || in_acc[2] != 0.0 || !(in_acc[0] <= 1e-24 * in_acc[1]) ||
+                     (stop && *stop != 0);
     int32_t v = (int32_t)order[i];
     ext[i] = bad ? 0 : (colptr[v + 1] - colptr[v]) + vr[v].app_cnt;
 }
@@ -3896,12 +3908,14 @@ __global__ __launch_bounds__(64) void k_sc_merge_huge(Arrays A, const GraphDesc*
 // owner of each row is found in the tile's window of row_off by a 6-step search over lane
 // registers, and the 64x3 doubles are staged through LDS so that every store is a contiguous
 // 512-byte wave store.  id_mod > 0 (views call): view k's global ids [k N, (k+1) N) go back to the input's [0, N) (N = id_mod);
-// 0 = ids as they are.
+// 0 = ids as they are.  row_base (depths call): the rows go behind the *row_base rows of the earlier snapshots; nullptr = 0.
 __global__ __launch_bounds__(256) void k_sc_compact(const uint32_t* __restrict__ order, const int32_t* __restrict__ cnt,
                                                     const int64_t* __restrict__ row_off, const int64_t* __restrict__ tmp_off,
                                                     const int32_t* __restrict__ tmp_nbr, const double* __restrict__ tmp_val,
-                                                    int32_t S, double* __restrict__ out, int64_t out_cap, int32_t id_mod) {
+                                                    int32_t S, double* __restrict__ out, int64_t out_cap, int32_t id_mod,
+                                                    const int64_t* __restrict__ row_base) {
     (void)cnt;
+    if (row_base) { const int64_t b = *row_base; out += 3 * b; out_cap -= b; }
     __shared__ double stage[4][192];
     const int lane = threadIdx.x & 63;
     const int wv = threadIdx.x >> 6;

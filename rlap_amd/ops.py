@@ -480,6 +480,87 @@ def approximate_cholesky_views(
     return res, ptr
 
 
+def _depths_list(num_remove) -> list:
+    """num_remove of approximate_cholesky_depths as a list of ints: non-empty, non-decreasing (checked here, before any device
+    or library call)."""
+    if isinstance(num_remove, Tensor):
+        if num_remove.dtype.is_floating_point or num_remove.dtype == torch.bool or num_remove.dim() > 1:
+            raise ValueError("num_remove: a sequence of integers")
+        vals = [int(v) for v in num_remove.reshape(-1).tolist()]
+    else:
+        try:
+            vals = list(num_remove)
+        except TypeError:
+            raise ValueError("num_remove: a sequence of integers, one depth per snapshot") from None
+        for v in vals:
+            if isinstance(v, bool) or not hasattr(v, "__index__"):   # (ints and numpy integers; not floats, not bools)
+                raise ValueError(f"num_remove: integers only, got {v!r}")
+        vals = [v.__index__() for v in vals]
+    if not vals:
+        raise ValueError("num_remove: at least one depth")
+    if any(b < a for a, b in zip(vals, vals[1:])):
+        raise ValueError(f"num_remove must be non-decreasing, got {vals}")
+    return vals
+
+
+def approximate_cholesky_depths(
+    edge_index: Tensor,
+    edge_weights: Optional[Tensor],
+    num_nodes: int,
+    num_remove: Sequence[int],
+    o_v: str,
+    o_n: str,
+    *,
+    perm: Optional[Tensor] = None,
+    seed: Optional[int] = None,
+    return_device: Optional[Union[str, torch.device]] = None,
+    mode: str = "exact",
+) -> Tuple[Tensor, Tensor]:
+    """K nested Schur complements ("depths") of one graph from ONE elimination -- the sweep over the removed fraction of the
+    reference's analysis scripts (scripts/rlap_ppr_edge_plots.py:37, scripts/rlap_vc_spectral.py:14-58) without K calls.
+
+    `num_remove` is a non-decreasing sequence t_0 <= ... <= t_{K-1} (zero and repeated values allowed; each value is clamped to
+    num_nodes - 1 as in approximate_cholesky).  Returns (sc_edge_info, ptr[K+1]): snapshot k is rows [ptr[k], ptr[k+1]) and equals
+    `approximate_cholesky(..., num_remove=t_k, perm=perm, seed=seed, mode=mode)` -- indices, row order and weights -- because the
+    elimination to t_k passes through exactly the state a call with a smaller num_remove stops in.  Node ids stay in the input's
+    space (no relabel between depths).  The elimination runs once, in segments [t_{k-1}, t_k), each followed by the output pass
+    of its snapshot.
+    """
+    assert edge_index.shape[0] == 2
+    assert o_v in ["random", "degree", "coarsen"]
+    assert o_n in ["asc", "desc", "random"]
+    depths = _depths_list(num_remove)
+    K = len(depths)
+    global last_stats
+    dev = _device_for(edge_index)
+    lib, hobj = _handle_obj(dev)
+    h = hobj.ptr
+    _set_mode(lib, h, mode)
+    nr_ = torch.tensor(depths, dtype=torch.int64)
+    with torch.cuda.device(dev):
+        row, col, w, E = _prep_edges(edge_index, edge_weights, dev)
+        n = int(num_nodes)
+        d_perm = None
+        if o_v == "random" and perm is not None:
+            d_perm = perm.to(device=dev, dtype=torch.int64).contiguous()
+            assert d_perm.numel() == n
+        shuffle_seed = _seed_from(seed) if (o_n == "random" or o_v != "degree" or mode == "frontier") else 0
+        out = torch.empty((max(K * E, 1), 3), dtype=torch.float64, device=dev)   # (an elimination never adds entries)
+        ptr = torch.zeros(K + 1, dtype=torch.int64)
+        st = _lib.Stats()
+        rc = _run(hobj, dev, E, n, 1, False, lambda: lib.rlap_approx_chol_depths(
+            h, row.data_ptr(), col.data_ptr(), w.data_ptr() if w is not None else None, E, n, K, nr_.data_ptr(),
+            O_V[o_v], O_N[o_n], d_perm.data_ptr() if d_perm is not None else None, shuffle_seed,
+            out.data_ptr(), out.shape[0], ptr.data_ptr(), ctypes.byref(st)), st)
+        if rc != 0:
+            _raise(rc)
+        last_stats = st.as_dict()
+        res = _trim(out, int(ptr[-1]))
+    if return_device is not None and return_device != "same":
+        res = res.to(return_device)
+    return res, ptr
+
+
 def identity(a: Tensor) -> Tensor:
     """Boundary self-test (reference: rlap/ops.py:61-63): tensor -> column-major
     staging -> tensor, on the GPU; returns a tensor on `a`'s device."""
