@@ -191,6 +191,28 @@ int rlap_approx_chol_depths(rlap_handle h, const int64_t* d_row, const int64_t* 
                             int64_t K, const int64_t* h_num_remove, int o_v, int o_n, const int64_t* d_perm, uint64_t shuffle_seed,
                             double* d_out, int64_t out_cap_rows, int64_t* h_out_ptr, rlap_stats* h_stats);
 
+/* Views x depths: D nested snapshots of every (view k, graph g) of a views call, from one elimination of the K-fold union (G = 1:
+ * one graph; K = 1: a batch; K = G = 1 is rlap_approx_chol_depths, D = 1 is rlap_approx_chol_views).
+ *   h_num_remove : [D][K*G], row-major; column k*G + g is the depth list of (view k, graph g): non-decreasing down the column (zero
+ *                  and repeated values allowed), each value clamped to n_g - 1 as in every other call
+ *   d_perm       : o_v=random only, [K*N] laid out as in rlap_approx_chol_views, or NULL; every depth uses the same perm
+ *   h_out_ptr    : [D*K*G + 1]; rows are depth-major, then view, then graph: snapshot (d, k, g) is rows
+ *                  [h_out_ptr[(d*K + k)*G + g], h_out_ptr[(d*K + k)*G + g + 1]), node ids in the INPUT's id space
+ *   out_cap_rows : D*K*E rows always suffice
+ *   h_stats      : as for rlap_approx_chol_depths, over the union
+ * Contract: snapshot (d, k, g) equals rlap_approx_chol on graph g alone with t = h_num_remove[d][k*G + g], shuffle_seed + k*G + g
+ * and perm slice (k, g), ids shifted by node_ptr[g] -- indices, row order and weights, in both rng modes.  Equivalently depth row d
+ * of the output equals rlap_approx_chol_views(..., h_num_remove = row d), h_out_ptr included up to a base offset.  The elimination
+ * runs once, segment d covering positions [t_{d-1}, t_d) of every graph; one host synchronisation per call (two for inputs of at
+ * least 2^21 entries), as for the other calls.
+ * A decreasing column, D, K or G < 1, or a null pointer: RLAP_E_BAD_ARG; limits as for rlap_approx_chol_views, and D*K*G < 2^30
+ * (RLAP_E_TOO_LARGE).  Workspace: may want more than rlap_workspace_query(h, K*E, K*N, K*G, 0, ...) reports -- RLAP_E_WORKSPACE
+ * then, with rlap_workspace_needed() telling how much. */
+int rlap_approx_chol_views_depths(rlap_handle h, const int64_t* d_row, const int64_t* d_col, const double* d_w, int64_t E,
+                                  int64_t G, const int64_t* h_node_ptr, int64_t K, int64_t D, const int64_t* h_num_remove,
+                                  int o_v, int o_n, const int64_t* d_perm, uint64_t shuffle_seed,
+                                  double* d_out, int64_t out_cap_rows, int64_t* h_out_ptr, rlap_stats* h_stats);
+
 /* The op with the step BEFORE the path fused in (scripts/node_shared.py:326-327,
  * scripts/augmentor_benchmarks.py:77-78):
  *   symmetrize != 0 : the input holds every undirected edge in one or both directions; (b,a) is

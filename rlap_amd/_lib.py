@@ -19,6 +19,7 @@ EXPORTS = [
     "rlap_approx_chol_from_edges", "rlap_debug_set_limits", "rlap_pack_rows", "rlap_unpack_rows",
     "rlap_workspace_bytes", "rlap_workspace_query", "rlap_set_workspace", "rlap_workspace_needed", "rlap_debug_set_poison", "rlap_debug_set_jitter",
     "rlap_set_rng_mode", "rlap_approx_chol_views", "rlap_approx_chol_depths", "rlap_debug_set_flow_limits",
+    "rlap_approx_chol_views_depths",
 ]
 
 E_WORKSPACE = 11   # RLAP_E_WORKSPACE
@@ -79,6 +80,9 @@ def load():
                                              ctypes.POINTER(Stats)]
     lib.rlap_approx_chol_depths.restype = ci
     lib.rlap_approx_chol_depths.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, ci, ci, vp, u64, vp, i64, vp, ctypes.POINTER(Stats)]
+    lib.rlap_approx_chol_views_depths.restype = ci
+    lib.rlap_approx_chol_views_depths.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, i64, vp, ci, ci, vp, u64, vp, i64, vp,
+                                                  ctypes.POINTER(Stats)]
     lib.rlap_approx_chol_views.restype = ci
     lib.rlap_approx_chol_views.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, vp, ci, ci, vp, u64, vp, i64, vp,
                                            ctypes.POINTER(Stats)]

@@ -129,26 +129,36 @@ class rLapDepths:
     depth).  Depth k removes int(fracs[k] * num_nodes) vertices, num_nodes = edge_index.max() + 1, as rLap does; the fractions
     are taken in the order given and must not decrease.  `.augment(g)` returns the K graphs; node ids stay in the input's space,
     so no relabel is needed between depths.  Graph k equals rLap(fracs[k], ...).augment(g) with the same seed.
+
+    `views=R` (an int): R independent runs of the sweep (the `num_runs` loop of scripts/rlap_vc_spectral.py) from the same ONE
+    call, as R views side by side; `.augment(g)` then returns R lists of K graphs, list r being run r (view r of
+    ops.approximate_cholesky_depths(..., views=R)).  `views=None` keeps the flat list of K graphs.
     """
 
     def __init__(self, fracs=(0.1, 0.2, 0.3), o_v: str = "random", o_n: str = "asc", keep_weights: bool = False, seed: Optional[int] = None,
-                 mode: str = "exact"):
+                 mode: str = "exact", views: Optional[int] = None):
         self.fracs = tuple(float(f) for f in fracs)
         assert len(self.fracs) >= 1
-        self.o_v, self.o_n, self.keep_weights, self.seed, self.mode = o_v, o_n, keep_weights, seed, mode
+        assert views is None or (int(views) == views and views >= 1), "views: None or a positive int"
+        self.o_v, self.o_n, self.keep_weights, self.seed, self.mode, self.views = o_v, o_n, keep_weights, seed, mode, views
 
     def augment(self, g):
         x, edge_index, edge_weights = g.unfold() if hasattr(g, "unfold") else g
         num_nodes = int(edge_index.max().item()) + 1 if edge_index.numel() else 0
         self.num_remove = [int(f * num_nodes) for f in self.fracs]
+        extra = {} if self.views is None else {"views": int(self.views)}
         sc, ptr = ops.approximate_cholesky_depths(edge_index, edge_weights, num_nodes, self.num_remove, self.o_v, self.o_n,
-                                                  seed=self.seed, return_device="same", mode=self.mode)
-        out = []
-        for k in range(len(self.fracs)):
-            part = sc[int(ptr[k]):int(ptr[k + 1])]
+                                                  seed=self.seed, return_device="same", mode=self.mode, **extra)
+
+        def graph(i):
+            part = sc[int(ptr[i]):int(ptr[i + 1])]
             ei = part[:, :2].long().t().contiguous()
-            out.append(_as_graph(x, ei, part[:, 2].contiguous() if self.keep_weights else None))
-        return out
+            return _as_graph(x, ei, part[:, 2].contiguous() if self.keep_weights else None)
+        K = len(self.fracs)
+        if self.views is None:
+            return [graph(k) for k in range(K)]
+        R = int(self.views)
+        return [[graph(k * R + r) for k in range(K)] for r in range(R)]   # (rows depth-major, then view)
 
     def __call__(self, x, edge_index, edge_weight=None):
         return self.augment(Graph(x, edge_index, edge_weight))

@@ -228,21 +228,57 @@ __global__ void k_widen_u32(const uint32_t* __restrict__ in, int32_t N, int64_t*
     if (i < N) out[i] = (int64_t)in[i];
 }
 
-// Depths call (rlap_approx_chol_depths): before segment k, graph 0's num_remove becomes t_k (the round kernel runs to it) and, for the
-// dataflow kernel, whose positions were all queued up front, n_elim becomes the snapshot's (k_sc_perm_order reads it); -1 keeps n_elim.
-// `resume` (round kernel): 0 for the first segment, 1 for the later ones, which continue from the n_elim the previous one left.
-__global__ void k_depth_set(GraphDesc* __restrict__ gd, int64_t t, int64_t n_elim, int32_t resume) {
-    if (threadIdx.x == 0) { gd[0].t = t; if (n_elim >= 0) gd[0].n_elim = (int32_t)n_elim; gd[0].resume = resume; }
+// Depths call (rlap_approx_chol_depths, rlap_approx_chol_views_depths): before segment k, graph j's num_remove becomes t_k[j] (row k
+// of the depth table, [D][G]; the round kernel runs to it) and, for the dataflow kernel, whose positions were all queued up front,
+// n_elim becomes the snapshot's, min(t_k[j], n_j - 1) (k_sc_perm_order reads it).  `resume` (round kernel): 0 for the first segment,
+// 1 for the later ones, which continue from the n_elim the previous one left.  One thread per graph.
+__global__ void k_depth_set(GraphDesc* __restrict__ gd, const int64_t* __restrict__ t_row, int32_t G, int32_t set_n_elim, int32_t resume) {
+    const int32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= G) return;
+    const int64_t t = t_row[j];
+    gd[j].t = t;
+    if (set_n_elim) { const int64_t n = gd[j].n; gd[j].n_elim = (int32_t)(t < 0 ? 0 : (t < n - 1 ? t : (n > 0 ? n - 1 : 0))); }
+    gd[j].resume = resume;
 }
-// After snapshot k's output pass: its rows end at ptr[k + 1] = ptr[k] + row_off[S]; the output pass's counters (scratch top, tier
-// counts, live entries) start from 0 for the next snapshot, whose ext / cnt sentinels (index S_next) are zeroed.  The largest scratch
-// top any snapshot asked for is kept and handed to k_collect by the last one (S_next < 0), so that a scratch retry grows enough.
-__global__ void k_depth_close(const int64_t* __restrict__ row_off, int32_t S, int64_t* __restrict__ out_ptr, int32_t k,
+// After a segment's elimination: any graph's failure stops the call's later work (sticky; k_sc_ext stages nothing, k_flow_segment
+// starts no claim).  A graph that failed keeps the n_elim of the segment it failed in, so the host's survivor bases of later
+// snapshots no longer describe it.
+__global__ void k_depth_stop(const GraphDesc* __restrict__ gd, int32_t G, int32_t* __restrict__ stop) {
+    int32_t st = 0;
+    for (int32_t j = threadIdx.x; j < G; j += blockDim.x) st |= gd[j].status;
+    if (st) atomicOr(stop, 1);
+}
+// Dataflow kernel, batches: the claim order sorted by (position, graph) is regrouped by segment, so that segment k is the contiguous
+// claim range [Q_{k-1}, Q_k).  Key of a claim = the segment its position falls in (first k with p < n_elim of depth k); the radix
+// sort over it is stable, so each segment keeps the interleaved (position, graph) order, and with it each graph's own order.
+__global__ void k_flow_seg_keys(const uint32_t* __restrict__ qorder, int32_t Q, const int32_t* __restrict__ qg, const GraphDesc* __restrict__ gd,
+                                const int64_t* __restrict__ t_tab, int32_t D, int32_t G, uint64_t* __restrict__ keys) {
+    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= Q) return;
+    const int32_t li = (int32_t)qorder[i];
+    const int32_t g = qg[li];
+    const int64_t p = (int64_t)(li - gd[g].flow_base - 1);
+    const int64_t n = gd[g].n;
+    int32_t lo = 0, hi = D - 1;   // the deepest depth queued every position: the answer is in [0, D-1]
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) >> 1;
+        const int64_t t = t_tab[(int64_t)mid * G + g];
+        const int64_t ne = t < 0 ? 0 : (t < n - 1 ? t : n - 1);
+        if (p < ne) hi = mid; else lo = mid + 1;
+    }
+    keys[i] = (uint64_t)lo;
+}
+// After snapshot k's output pass: graph j's rows end at ptr[kG + j + 1] = ptr[kG] + row_off[sb[j + 1]] (sb: the snapshot's survivor
+// bases, ptr[kG] filed by the previous snapshot); the output pass's counters (scratch top, tier counts, live entries) start from 0
+// for the next snapshot, whose ext / cnt sentinels (index S_next) are zeroed.  The largest scratch top any snapshot asked for is kept
+// and handed to k_collect by the last one (S_next < 0), so that a scratch retry grows enough.
+__global__ void k_depth_close(const int64_t* __restrict__ row_off, const int64_t* __restrict__ sb, int32_t G, int64_t* __restrict__ out_ptr,
                               unsigned long long* __restrict__ counters, unsigned long long* __restrict__ live, unsigned long long* __restrict__ scr_max,
                               int32_t S_next, int32_t* __restrict__ ext, int32_t* __restrict__ cnt) {
     const int tid = threadIdx.x;
+    const int64_t base = out_ptr[0];
+    for (int32_t j = tid; j < G; j += blockDim.x) out_ptr[j + 1] = base + row_off[sb[j + 1]];
     if (tid == 0) {
-        out_ptr[k + 1] = out_ptr[k] + row_off[S];
         const unsigned long long m = counters[0] > *scr_max ? counters[0] : *scr_max;
         if (S_next >= 0) {
             *scr_max = m;
@@ -260,23 +296,31 @@ struct Sizes {
     bool want_genperm;
     bool flow;                    // dataflow elimination (o_v = random): its arrays are part of the arena
     int64_t flow_Q, flow_scr;     // look-back words (positions + one sentinel per graph); entries of long-column working storage
+    int64_t D;                    // depths call: snapshots (0 otherwise)
 };
 struct WBuf { void* p = nullptr; template <class T> T* as() const { return reinterpret_cast<T*>(p); } };
 struct WS {
-    WBuf node_ptr_d, vgraph, scal, keys0, keys1, idx0, idx1, head, pos, sorttmp, colptr, slot_col, permchk, genperm, ent, vrec, ocur, oend, origpos, orig_order, gd_d, pool_top, bs_cnt, bs_alloc, bs_dir, bs_v, bs_id, bs_pool_top, batch_pos, skey0, skey1, sval0, sval1, scr_rec, scr_i32, scr_f64, surv_base_d, ext, tmp_off, tmp_nbr, tmp_val, cnt, row_off, sc_rec, sc_i32, sc_f64, biglist, hugelists, results,
+    WBuf node_ptr_d, depth_t, depth_sb, vgraph, scal, keys0, keys1, idx0, idx1, head, pos, sorttmp, colptr, slot_col, permchk, genperm, ent, vrec, ocur, oend, origpos, orig_order, gd_d, pool_top, bs_cnt, bs_alloc, bs_dir, bs_v, bs_id, bs_pool_top, batch_pos, skey0, skey1, sval0, sval1, scr_rec, scr_i32, scr_f64, surv_base_d, ext, tmp_off, tmp_nbr, tmp_val, cnt, row_off, sc_rec, sc_i32, sc_f64, biglist, hugelists, results,
          f_cdir, f_atag, f_lb, f_qv, f_qg, f_ctrl, f_scr, f_rocnt, f_rooff;
 };
-inline size_t host_block_bytes(int64_t G) { return 16 * (size_t)(G + 1) + sizeof(GraphDesc) * (size_t)G; }
+// depths call (D > 0): the depth table t[D][G] and every snapshot's survivor bases sb[D][G + 1] follow
+inline size_t host_block_bytes(int64_t G, int64_t D) {
+    return 16 * (size_t)(G + 1) + sizeof(GraphDesc) * (size_t)G + (D > 0 ? 8 * (size_t)D * (size_t)(2 * G + 1) : 0);
+}
 // the arena's layout: run once with a null base to learn the size, once more to place the buffers
 size_t carve(Carver& C, const Sizes& z, WS& W) {
     const int64_t G = z.G, N = z.N, S = z.S, Ealloc = std::max<int64_t>(z.Eeff, 1), BT = z.bucket_total;
     W.scal.p = C.take<Scalars>(1);
     W.results.p = C.take<char>((int64_t)z.res_bytes);
     {   // what the host hands over per call, one block (one H2D copy from the pinned staging buffer): node_ptr | surv_base | gd
-        char* hp = C.take<char>((int64_t)host_block_bytes(G));
+        // (| depth table | snapshot survivor bases)
+        char* hp = C.take<char>((int64_t)host_block_bytes(G, z.D));
         W.node_ptr_d.p = hp;
         W.surv_base_d.p = hp ? hp + 8 * (G + 1) : nullptr;
         W.gd_d.p = hp ? hp + 16 * (G + 1) : nullptr;
+        char* dp = hp ? hp + 16 * (G + 1) + sizeof(GraphDesc) * G : nullptr;
+        W.depth_t.p = z.D > 0 ? dp : nullptr;
+        W.depth_sb.p = z.D > 0 && dp ? dp + 8 * z.D * G : nullptr;
     }
     W.pool_top.p = C.take<int32_t>(1);
     W.bs_pool_top.p = C.take<int32_t>(1);
@@ -316,14 +360,15 @@ size_t carve(Carver& C, const Sizes& z, WS& W) {
 }
 
 // sizes of a call on (E directed input entries, N vertices, G graphs, S surviving vertices) under the handle's growth factors
-// `segs` > 0 (depths call, one graph, that many segments): the round kernel reserves a fresh block of pool slots in every segment, and
-// the read-back block holds segs + 1 row pointers and the scratch maximum
+// `segs` > 0 (depths call, that many segments): the round kernel reserves a fresh block of pool slots per graph in every segment, the
+// host block carries the depth table and the snapshots' survivor bases, and the read-back block holds segs * G + 1 row pointers, the
+// scratch maximum and the stop word
 int call_sizes(const rlap_handle h, int64_t Eeff, int64_t N, int64_t G, int64_t bucket_total, int64_t S, bool want_genperm, bool flow, int64_t nelim_total, Sizes* z,
                int64_t segs = 0) {
     const double pool_factor = h->dbg_pool >= 0 ? h->dbg_pool : h->pool_factor;
     const double log_factor = h->dbg_log >= 0 ? h->dbg_log : h->log_factor;
     const int64_t nnz_ub = Eeff;
-    const int64_t pool = (int64_t)(pool_factor * nnz_ub) + (h->dbg_pool >= 0 ? 0 : 16 * N + 1024) + (G + std::max<int64_t>(segs - 1, 0)) * (G <= 512 ? (int64_t)POOL_GRAB_BIG : (int64_t)POOL_GRAB_SMALL);
+    const int64_t pool = (int64_t)(pool_factor * nnz_ub) + (h->dbg_pool >= 0 ? 0 : 16 * N + 1024) + G * std::max<int64_t>(segs, 1) * (G <= 512 ? (int64_t)POOL_GRAB_BIG : (int64_t)POOL_GRAB_SMALL);
     z->G = G; z->N = N; z->Eeff = Eeff; z->S = S; z->bucket_total = bucket_total;
     z->slot_cap = nnz_ub + pool;
     if (z->slot_cap >= ((int64_t)1 << 31) - 64) return RLAP_E_TOO_LARGE;
@@ -331,7 +376,8 @@ int call_sizes(const rlap_handle h, int64_t Eeff, int64_t N, int64_t G, int64_t 
     z->scr_total = nnz_ub / 2 + 8 * G + 8;
     if (bucket_total * BDIR >= ((int64_t)1 << 40) || bucket_total >= ((int64_t)1 << 31) || z->log_total >= ((int64_t)1 << 31)) return RLAP_E_TOO_LARGE;
     z->scr_budget = h->dbg_scr >= 0 ? h->dbg_scr : h->scr_budget;
-    z->res_bytes = sizeof(CallResults) + 8 * (size_t)(G + 1) + (segs > 0 ? 8 * (size_t)(segs + 1) : 0);
+    z->res_bytes = sizeof(CallResults) + 8 * (size_t)(G + 1) + (segs > 0 ? 8 * (size_t)(segs * G + 3) : 0);
+    z->D = segs;
     z->want_genperm = want_genperm;
     z->flow = flow;
     z->flow_Q = nelim_total + G;
@@ -354,7 +400,8 @@ struct Call {
     double* d_out; int64_t out_cap; int64_t* h_out_row_ptr; rlap_stats* st;
     int symmetrize;
     int64_t K = 1;   // views (rlap_approx_chol_views): h_node_ptr / h_t describe the K-fold union, the device input is ONE copy of it
-    const int64_t* h_depths = nullptr; int64_t D = 0;   // depths (rlap_approx_chol_depths): one graph, D non-decreasing num_remove (h_t = the last)
+    // depths (rlap_approx_chol_depths / _views_depths): h_depths[D][G], each column non-decreasing, h_t = its last row
+    const int64_t* h_depths = nullptr; int64_t D = 0;
 };
 
 // One attempt.  No host synchronisation until the single read-back at the end: every size is an upper bound
@@ -379,7 +426,8 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
     std::memset(&st, 0, sizeof(st));
 
     if (N == 0) {
-        for (int64_t g = 0; g <= G; ++g) c.h_out_row_ptr[g] = 0;
+        const int64_t nptr = c.D > 0 ? c.D * G : G;
+        for (int64_t g = 0; g <= nptr; ++g) c.h_out_row_ptr[g] = 0;
         if (c.st) *c.st = st;
         return RLAP_OK;
     }
@@ -402,15 +450,27 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
         surv_base[g + 1] = surv_base[g] + (n - ne);
     }
     const int64_t S = surv_base[G];
-    // depths call: segment k eliminates positions [ne[k-1], ne[k]) and snapshot k has S_k = n - ne[k] survivors (the first is the largest)
+    // depths call: segment k eliminates positions [ne[k-1][j], ne[k][j]) of every graph j; snapshot k has the survivor bases
+    // sb[k][j] (sb[k][G] = S_k = N - Q_k, Q_k = the positions of depth k over all graphs; the first snapshot is the largest)
     const bool depths = c.D > 0;
     const int64_t nseg = depths ? c.D : 1;
-    std::vector<int64_t> seg_ne((size_t)nseg, nelim_total);
+    std::vector<int64_t> seg_Q((size_t)nseg, nelim_total), seg_sb;
     if (depths) {
-        if (G != 1) return RLAP_E_BAD_ARG;
-        for (int64_t k = 0; k < nseg; ++k) seg_ne[(size_t)k] = std::max<int64_t>(0, std::min<int64_t>(c.h_depths[k], N - 1));
+        seg_sb.assign((size_t)(nseg * (G + 1)), 0);
+        for (int64_t k = 0; k < nseg; ++k) {
+            int64_t q = 0;
+            int64_t* sb = seg_sb.data() + k * (G + 1);
+            for (int64_t g = 0; g < G; ++g) {
+                const int64_t n = c.h_node_ptr[g + 1] - c.h_node_ptr[g];
+                const int64_t ne = std::max<int64_t>(0, std::min<int64_t>(c.h_depths[k * G + g], n - 1));
+                if (k > 0 && ne < std::max<int64_t>(0, std::min<int64_t>(c.h_depths[(k - 1) * G + g], n - 1))) return RLAP_E_BAD_ARG;
+                q += ne;
+                sb[g + 1] = sb[g] + (n - ne);
+            }
+            seg_Q[(size_t)k] = q;
+        }
     }
-    const int64_t S0 = depths ? N - seg_ne[0] : S;
+    const int64_t S0 = depths ? N - seg_Q[0] : S;
     st.n_eliminated = nelim_total;
     Sizes z;
     const bool flow = flow_wanted(h, c.o_v, G, N);
@@ -441,7 +501,7 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
         }
     }
     {
-        const size_t pinned_need = ((res_bytes + 255) & ~(size_t)255) + host_block_bytes(G);   // read-back block + staging of the host parameters
+        const size_t pinned_need = ((res_bytes + 255) & ~(size_t)255) + host_block_bytes(G, z.D);   // read-back block + staging of the host parameters
         if (pinned_need > h->h_results_cap) {
             if (h->h_results) (void)hipHostFree(h->h_results);
             h->h_results = nullptr; h->h_results_cap = 0;
@@ -469,7 +529,12 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
         std::memcpy(stage, c.h_node_ptr, 8 * (size_t)(G + 1));
         std::memcpy(stage + 8 * (G + 1), surv_base.data(), 8 * (size_t)(G + 1));
         std::memcpy(stage + 16 * (G + 1), gd.data(), sizeof(GraphDesc) * (size_t)G);
-        HIPCHK(hipMemcpyAsync(W.node_ptr_d.p, stage, host_block_bytes(G), hipMemcpyHostToDevice, s));
+        if (depths) {
+            char* dp = stage + 16 * (G + 1) + sizeof(GraphDesc) * (size_t)G;
+            std::memcpy(dp, c.h_depths, 8 * (size_t)(nseg * G));
+            std::memcpy(dp + 8 * nseg * G, seg_sb.data(), 8 * seg_sb.size());
+        }
+        HIPCHK(hipMemcpyAsync(W.node_ptr_d.p, stage, host_block_bytes(G, z.D), hipMemcpyHostToDevice, s));
     }
     {
         Fills F;
@@ -481,7 +546,7 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
         F.add(W.bs_pool_top.p, 1, 0);
         F.add(W.batch_pos.p, N, -1);
         F.add(W.ext.as<int32_t>() + S0, 1, 0); F.add(W.cnt.as<int32_t>() + S0, 1, 0);
-        if (depths) F.add(reinterpret_cast<CallResults*>(W.results.p) + 1, 2 * (nseg + 2), 0);   // row pointers of the snapshots, scratch maximum
+        if (depths) F.add(reinterpret_cast<CallResults*>(W.results.p) + 1, 2 * (nseg * G + 3), 0);   // row pointers of the snapshots, scratch maximum, stop word
         if (G == 1) F.add(W.vgraph.p, N, 0);
         F.launch(s);
     }
@@ -646,6 +711,16 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
             int rc = sort_pairs(h, ST, W.skey0.as<uint64_t>(), W.skey1.as<uint64_t>(), W.sval0.as<uint32_t>(), W.sval1.as<uint32_t>(), nelim_total, 0, std::min(64u, 32u + gbits));
             if (rc) return rc;
             FA.qorder = W.sval1.as<uint32_t>(); FA.Qclaim = (int32_t)nelim_total;
+            if (depths && nseg > 1) {
+                // segments as contiguous claim ranges (stable regrouping by segment), in sval0: the output pass of every snapshot
+                // writes its order into sval1, and o_v = random leaves sval0 alone from here on
+                hipLaunchKernelGGL(k_flow_seg_keys, dim3(nblk(nelim_total, 256)), dim3(256), 0, s, W.sval1.as<uint32_t>(), (int32_t)nelim_total, FA.qg, gd_d,
+                                   W.depth_t.as<int64_t>(), (int32_t)nseg, (int32_t)G, W.skey0.as<uint64_t>());
+                rc = sort_pairs(h, ST, W.skey0.as<uint64_t>(), W.skey1.as<uint64_t>(), W.sval1.as<uint32_t>(), W.sval0.as<uint32_t>(), nelim_total, 0,
+                                bits_for((uint64_t)(nseg - 1)));
+                if (rc) return rc;
+                FA.qorder = W.sval0.as<uint32_t>();
+            }
         }
         shape = G >= 48 ? 3 : 1;   // 1: 76 KB of LDS, two workgroups per CU, four waves each (three help with long sorts); 4: the same with one wave; 3: 40 KB, four; 2: 17 KB, eight
         if (const char* e = std::getenv("RLAP_FLOW_SHAPE")) { if (e[0] >= '1' && e[0] <= '4') shape = e[0] - '0'; }   // diagnostic override
@@ -654,24 +729,28 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
     }
     CallResults* res_d = W.results.as<CallResults>();
     int64_t* out_ptr_d = reinterpret_cast<int64_t*>(res_d + 1);
-    unsigned long long* scr_max_d = reinterpret_cast<unsigned long long*>(out_ptr_d + nseg + 1);   // (depths call only)
+    unsigned long long* scr_max_d = reinterpret_cast<unsigned long long*>(out_ptr_d + nseg * G + 1);   // (depths call only)
+    int32_t* stop_d = depths ? reinterpret_cast<int32_t*>(scr_max_d + 1) : nullptr;                    // (depths call only: k_depth_stop)
     ScScratch SS;
     SS.rec = W.sc_rec.as<SRec>(); SS.i32 = W.sc_i32.as<int32_t>(); SS.f64 = W.sc_f64.as<double>(); SS.cap = scr_budget; SS.top = counters + 0; SS.flags = flags;
-    const int32_t* stop_d = depths ? &gd_d[0].status : nullptr;
-    // One segment for the other calls.  A depths call runs the elimination in segments [ne[k-1], ne[k]), each followed by the output
-    // pass of its snapshot: the state a segment stops in is the state the next one starts from.
+    // One segment for the other calls.  A depths call runs the elimination in segments [ne[k-1][j], ne[k][j]) of every graph j, each
+    // followed by the output pass of its snapshot: the state a segment stops in is the state the next one starts from.
     for (int64_t seg = 0; seg < nseg; ++seg) {
-        const int64_t ne_lo = seg > 0 ? seg_ne[(size_t)seg - 1] : 0, ne_hi = seg_ne[(size_t)seg];
-        const int64_t Sk = depths ? N - ne_hi : S;
+        const int64_t Q_lo = seg > 0 ? seg_Q[(size_t)seg - 1] : 0, Q_hi = seg_Q[(size_t)seg];
+        const int64_t Sk = depths ? N - Q_hi : S;
         const bool last = seg + 1 == nseg;
-        const bool run_seg = seg == 0 || ne_hi > ne_lo;   // (an equal depth: the state is already the snapshot's)
+        const bool run_seg = seg == 0 || Q_hi > Q_lo;   // (no graph advances: the state is already the snapshot's)
         if (depths && run_seg)
-            hipLaunchKernelGGL(k_depth_set, dim3(1), dim3(64), 0, s, gd_d, c.h_depths[seg], flow ? ne_hi : (int64_t)-1, seg > 0 ? 1 : 0);
+            hipLaunchKernelGGL(k_depth_set, dim3(nblk(G, 256)), dim3(256), 0, s, gd_d, W.depth_t.as<int64_t>() + seg * G, (int32_t)G, flow ? 1 : 0,
+                               seg > 0 ? 1 : 0);
         if (run_seg) {
             if (flow) {
                 if (depths) {
-                    FA.Qclaim = (int32_t)(ne_hi + 1);   // look-back index of position p: p + 1 (graph 0's sentinel first)
-                    if (seg > 0) launch_flow_segment(s, FA, (int32_t)(ne_lo + 1), &gd_d[0].status);
+                    // claims of the segment: with a claim order (batches), its range [Q_{k-1}, Q_k) of it; without (one graph), look-back
+                    // indices p + 1 (graph 0's sentinel first)
+                    const int64_t off = FA.qorder ? 0 : 1;
+                    FA.Qclaim = (int32_t)(Q_hi + off);
+                    if (seg > 0) launch_flow_segment(s, FA, (int32_t)(Q_lo + off), stop_d);
                 }
                 launch_flow_eliminate(shape, grid, s, A, FA, FP);
                 launch_flow_finish(s, A, FA, gd_d, (int32_t)N, (int32_t)G);
@@ -679,6 +758,7 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
                 launch_eliminate_batch(c.o_v, c.o_n, (unsigned)G, h->n_cu, s, A, gd_d, ES, W.batch_pos.as<int32_t>(), flags, acc, wide);
             }
             HIPCHK(hipGetLastError());
+            if (depths) hipLaunchKernelGGL(k_depth_stop, dim3(1), dim3(256), 0, s, gd_d, (int32_t)G, stop_d);
         }
         if (h->timing) HIPCHK(hipEventRecord(h->ev[2], s));
 
@@ -689,7 +769,7 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
         uint32_t* home = reinterpret_cast<uint32_t*>(W.head.p);
         if (c.o_v == OV_RANDOM) {
             hipLaunchKernelGGL(k_sc_perm_order, dim3(nblk(N, 256)), dim3(256), 0, s, d_perm, W.vgraph.as<int32_t>(), gd_d,
-                               W.surv_base_d.as<int64_t>(), (int32_t)N, W.sval1.as<uint32_t>());
+                               depths ? W.depth_sb.as<int64_t>() + seg * (G + 1) : W.surv_base_d.as<int64_t>(), (int32_t)N, W.sval1.as<uint32_t>());
             order = W.sval1.as<uint32_t>();
             if (flow && Sk > 0 && Eeff > 0) {
                 // tag order of the surviving columns: concurrent eliminations pushed into them out of order (rlap_flow.h)
@@ -738,7 +818,7 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
             unsigned cgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows_ub + 255) / 256, 256 * 8));
             hipLaunchKernelGGL(k_sc_compact, dim3(cgrid), dim3(256), 0, s, order, W.cnt.as<int32_t>(), W.row_off.as<int64_t>(), W.tmp_off.as<int64_t>(),
                                W.tmp_nbr.as<int32_t>(), W.tmp_val.as<double>(), (int32_t)Sk, c.d_out, c.out_cap, K > 1 ? (int32_t)N1 : 0,
-                               depths ? (const int64_t*)(out_ptr_d + seg) : (const int64_t*)nullptr);
+                               depths ? (const int64_t*)(out_ptr_d + seg * G) : (const int64_t*)nullptr);
             HIPCHK(hipGetLastError());
         }
         if (depths) {
@@ -749,8 +829,9 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
                 launch_flow_ro_permute(s, A, FA, W.f_rooff.as<int32_t>(), (int32_t)Sk, home, W.keys1.as<uint64_t>(), W.idx1.as<uint32_t>(), ro_cap, reinterpret_cast<Slot*>(W.tmp_val.p));
                 HIPCHK(hipGetLastError());
             }
-            hipLaunchKernelGGL(k_depth_close, dim3(1), dim3(256), 0, s, W.row_off.as<int64_t>(), (int32_t)Sk, out_ptr_d, (int32_t)seg, counters, live, scr_max_d,
-                               last ? -1 : (int32_t)(N - seg_ne[(size_t)seg + 1]), W.ext.as<int32_t>(), W.cnt.as<int32_t>());
+            hipLaunchKernelGGL(k_depth_close, dim3(1), dim3(256), 0, s, W.row_off.as<int64_t>(), W.depth_sb.as<int64_t>() + seg * (G + 1), (int32_t)G,
+                               out_ptr_d + seg * G, counters, live, scr_max_d, last ? -1 : (int32_t)(N - seg_Q[(size_t)seg + 1]), W.ext.as<int32_t>(),
+                               W.cnt.as<int32_t>());
             HIPCHK(hipGetLastError());
         }
         if (h->timing) HIPCHK(hipEventRecord(h->ev[6], s));
@@ -795,7 +876,7 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
     st.nnz = R.nnz;
     st.n_draws = R.n_draws;
     st.n_rounds = R.rounds; st.n_singles = R.singles;
-    const int64_t m_total = depths ? out_ptr_h[nseg] : R.m_total;   // (depths: the rows of all snapshots)
+    const int64_t m_total = depths ? out_ptr_h[nseg * G] : R.m_total;   // (depths: the rows of all snapshots)
     st.out_rows = m_total;
     st.live_entries = R.live_total;
     if (flow && R.status == ST_INTERNAL) *flow_abort = R.flow_abort;
@@ -824,7 +905,7 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
     }
     if (R.flags[FLAG_SCR]) { *retry_kind = 4; *retry_need = R.scr_need; return RLAP_E_INTERNAL; }
     if (swapped && R.acc[0] != 0.0) { *retry_kind = 5; return RLAP_E_INTERNAL; }   // symmetric only within the tolerance: repeat, reading the input as given
-    const int64_t nptr = depths ? nseg : G;
+    const int64_t nptr = depths ? nseg * G : G;
     for (int64_t g = 0; g <= nptr; ++g) c.h_out_row_ptr[g] = out_ptr_h[g];
     if (m_total > c.out_cap) { c.h_out_row_ptr[nptr] = m_total; return RLAP_E_OUT_OVERFLOW; }
     return RLAP_OK;
@@ -1087,6 +1168,34 @@ int rlap_approx_chol_depths(rlap_handle h, const int64_t* d_row, const int64_t* 
     int64_t node_ptr[2] = {0, n};
     Call c{d_row, d_col, d_w, E, 1, node_ptr, h_num_remove + (K - 1), o_v, o_n, d_perm, shuffle_seed, d_out, out_cap_rows, h_out_ptr, h_stats, 0, 1,
            h_num_remove, K};
+    return run_call(h, c);
+}
+
+int rlap_approx_chol_views_depths(rlap_handle h, const int64_t* d_row, const int64_t* d_col, const double* d_w, int64_t E,
+                                  int64_t G, const int64_t* h_node_ptr, int64_t K, int64_t D, const int64_t* h_num_remove,
+                                  int o_v, int o_n, const int64_t* d_perm, uint64_t shuffle_seed,
+                                  double* d_out, int64_t out_cap_rows, int64_t* h_out_ptr, rlap_stats* h_stats) {
+    if (!h || G < 1 || K < 1 || D < 1 || E < 0 || !h_node_ptr || !h_num_remove || !h_out_ptr) return RLAP_E_BAD_ARG;
+    if (o_v < 0 || o_v > 2 || o_n < 0 || o_n > 2) return RLAP_E_BAD_ARG;
+    if (E > 0 && (!d_row || !d_col)) return RLAP_E_BAD_ARG;
+    if (out_cap_rows > 0 && !d_out) return RLAP_E_BAD_ARG;
+    if (h_node_ptr[0] != 0) return RLAP_E_BAD_ARG;
+    for (int64_t g = 0; g < G; ++g) if (h_node_ptr[g + 1] < h_node_ptr[g]) return RLAP_E_BAD_ARG;
+    const int64_t N = h_node_ptr[G];
+    // the union's limits are the views call's; the row pointers ([D * K * G + 1]) and the depth table live on the host and in the arena
+    if (K >= (int64_t)1 << 30 || G >= (int64_t)1 << 30 || K * G >= (int64_t)1 << 30 || (N > 0 && K >= ((int64_t)1 << 30) / N)) return RLAP_E_TOO_LARGE;
+    if (K * (E > 0 ? E : 1) >= (int64_t)1 << 31) return RLAP_E_TOO_LARGE;
+    const int64_t P = K * G;
+    if (D >= ((int64_t)1 << 30) / P) return RLAP_E_TOO_LARGE;
+    for (int64_t d = 1; d < D; ++d)
+        for (int64_t j = 0; j < P; ++j) if (h_num_remove[d * P + j] < h_num_remove[(d - 1) * P + j]) return RLAP_E_BAD_ARG;
+    // graph k * G + g of the union: ids [k * N + node_ptr[g], k * N + node_ptr[g + 1]); depth d of it is h_num_remove[d][k * G + g]
+    std::vector<int64_t> np((size_t)(P + 1));
+    for (int64_t k = 0; k < K; ++k)
+        for (int64_t g = 0; g < G; ++g) np[(size_t)(k * G + g)] = k * N + h_node_ptr[g];
+    np[(size_t)P] = K * N;
+    Call c{d_row, d_col, d_w, E, P, np.data(), h_num_remove + (D - 1) * P, o_v, o_n, d_perm, shuffle_seed, d_out, out_cap_rows, h_out_ptr, h_stats, 0, K,
+           h_num_remove, D};
     return run_call(h, c);
 }
 

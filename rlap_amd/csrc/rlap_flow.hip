@@ -1056,12 +1056,13 @@ __global__ void k_flow_pending(const Slot* __restrict__ ent, const int32_t* __re
         if (pu < pa && pa != FPOS_NONE) atomicAdd(&vr[e.nbr].key, 1);
     }
 }
-// a depths call's segment [claim_start - 1, Qclaim - 1) of positions (look-back index = position + 1 behind graph 0's sentinel):
-// claims continue at its first position.  The long-column scratch is free again (nothing is in flight between launches) and no
-// very long column is being worked on.  Kept: FC_ABORT and FC_REASON, FC_LONG (counted over the call), FC_PROGRESS (the stall
-// watchdog only compares it with itself).  Pending counters, look-back words, the chunk directory and the tags persist in their
-// own arrays.  After a failed segment (graph 0's status: k_flow_finish files FC_ABORT there, the reorder pass its own) the claim
-// counter starts beyond every position: each wave's first claim ends its loop, through the kernel's one way out.
+// a depths call's segment: claims [claim_start, Qclaim) -- one graph: look-back indices, position + 1 behind graph 0's sentinel; a
+// batch: the range of the claim order regrouped by segment (rlap_api.hip, k_flow_seg_keys).  Claims continue at its first position.
+// The long-column scratch is free again (nothing is in flight between launches) and no very long column is being worked on.  Kept:
+// FC_ABORT and FC_REASON, FC_LONG (counted over the call), FC_PROGRESS (the stall watchdog only compares it with itself).  Pending
+// counters, look-back words, the chunk directory and the tags persist in their own arrays.  After a failed segment (the call's stop
+// word: any graph's status after the segment, k_flow_finish files FC_ABORT into every graph's) the claim counter starts beyond every
+// position: each wave's first claim ends its loop, through the kernel's one way out.
 __global__ void k_flow_segment(int32_t* __restrict__ ctrl, int32_t claim_start, const int32_t* __restrict__ status) {
     if (threadIdx.x == 0) { ctrl[FC_CLAIM] = *status != 0 ? FLOW_CLAIM_STOP : claim_start; ctrl[FC_SCR] = 0; ctrl[FC_HEAVY] = 0; }
 }

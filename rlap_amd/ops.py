@@ -503,6 +503,67 @@ def _depths_list(num_remove) -> list:
     return vals
 
 
+def _int_tensor(x, what: str) -> Tensor:
+    """`x` (a tensor, or a possibly nested sequence of ints / numpy integers) as an int64 CPU tensor; ValueError for floats, bools,
+    strings or ragged nesting -- torch.as_tensor would convert some of them silently."""
+    if isinstance(x, Tensor):
+        if x.dtype.is_floating_point or x.dtype.is_complex or x.dtype == torch.bool:
+            raise ValueError(f"{what}: integers only")
+        return x.detach().to(device="cpu", dtype=torch.int64)
+
+    def bad(v) -> bool:
+        if isinstance(v, (bool, str, bytes, float)):
+            return True
+        if hasattr(v, "__index__"):
+            return False
+        try:
+            return any(bad(u) for u in v)
+        except TypeError:
+            return True
+    if bad(x):
+        raise ValueError(f"{what}: integers only")
+    try:
+        return torch.as_tensor(x, dtype=torch.int64)
+    except (TypeError, ValueError, RuntimeError, OverflowError):
+        raise ValueError(f"{what}: a regular array of integers") from None
+
+
+def _depths_table(num_remove, num_nodes: int, node_ptr, views) -> Tuple[Tensor, Tensor, int, int]:
+    """Arguments of a batched / views depths call, checked before any device or library call: (node_ptr, table[D, K*G], K, G),
+    table[d, k*G + g] = depth d of (view k, graph g).  num_remove is (D,), every (view, graph) alike, or (D, K, G)."""
+    if isinstance(views, bool) or not hasattr(views, "__index__") or views.__index__() < 1:
+        raise ValueError(f"views: a positive integer, got {views!r}")
+    K = views.__index__()
+    n = int(num_nodes)
+    np_ = torch.tensor([0, n], dtype=torch.int64) if node_ptr is None else _int_tensor(node_ptr, "node_ptr")
+    if np_.dim() != 1 or np_.numel() < 2 or int(np_[0]) != 0 or bool((np_[1:] < np_[:-1]).any()):
+        raise ValueError("node_ptr: non-decreasing offsets starting at 0, at least one graph")
+    if int(np_[-1]) != n:
+        raise ValueError(f"node_ptr[-1] ({int(np_[-1])}) must equal num_nodes ({n})")
+    G = np_.numel() - 1
+    t = _int_tensor(num_remove, "num_remove")
+    if t.dim() == 1 and t.numel() >= 1:
+        t = t.reshape(-1, 1, 1).expand(t.numel(), K, G)
+    elif t.dim() != 3 or tuple(t.shape[1:]) != (K, G) or t.shape[0] < 1:
+        raise ValueError(f"num_remove: (D,) or (D, K={K}, G={G}) integers, got shape {tuple(t.shape)}")
+    t = t.reshape(t.shape[0], K * G).contiguous()
+    if bool((t[1:] < t[:-1]).any()):
+        raise ValueError("num_remove must be non-decreasing down every (view, graph) column")
+    return np_.contiguous(), t, K, G
+
+
+def _one_graph_depths(num_remove, node_ptr, views) -> bool:
+    """The call of a depths list for one graph, one view: today's path through rlap_approx_chol_depths."""
+    if node_ptr is not None or isinstance(views, bool) or not hasattr(views, "__index__") or views.__index__() != 1:
+        return False
+    if isinstance(num_remove, Tensor):
+        return num_remove.dim() <= 1
+    try:
+        return torch.as_tensor(num_remove).dim() <= 1
+    except Exception:
+        return True   # (ragged or not numeric: _depths_list says what is wrong)
+
+
 def approximate_cholesky_depths(
     edge_index: Tensor,
     edge_weights: Optional[Tensor],
@@ -511,6 +572,8 @@ def approximate_cholesky_depths(
     o_v: str,
     o_n: str,
     *,
+    node_ptr: Optional[Union[Tensor, Sequence[int]]] = None,
+    views: int = 1,
     perm: Optional[Tensor] = None,
     seed: Optional[int] = None,
     return_device: Optional[Union[str, torch.device]] = None,
@@ -525,10 +588,20 @@ def approximate_cholesky_depths(
     elimination to t_k passes through exactly the state a call with a smaller num_remove stops in.  Node ids stay in the input's
     space (no relabel between depths).  The elimination runs once, in segments [t_{k-1}, t_k), each followed by the output pass
     of its snapshot.
+
+    Batches and views: `node_ptr` (a batch of G graphs, as in approximate_cholesky_batched) and `views` (K independent views, as
+    in approximate_cholesky_views) take the depths of every (view, graph) from one elimination of the K-fold union.  Then
+    `num_remove` is (D,), the same depths for every (view, graph), or a (D, K, G) tensor / nested sequence, non-decreasing down
+    every (view, graph) column.  Returns (sc_edge_info, ptr[D*K*G+1]): rows depth-major, then view, then graph; snapshot
+    (d, k, g) is rows [ptr[(d*K + k)*G + g], ptr[(d*K + k)*G + g + 1]) and equals depth row d of
+    `approximate_cholesky_views(..., num_remove=t[d], node_ptr=node_ptr)`.  `perm` (o_v="random") then holds K*N entries laid
+    out as for the views call; every depth uses it.
     """
     assert edge_index.shape[0] == 2
     assert o_v in ["random", "degree", "coarsen"]
     assert o_n in ["asc", "desc", "random"]
+    if not _one_graph_depths(num_remove, node_ptr, views):
+        return _depths_views(edge_index, edge_weights, num_nodes, num_remove, o_v, o_n, node_ptr, views, perm, seed, return_device, mode)
     depths = _depths_list(num_remove)
     K = len(depths)
     global last_stats
@@ -551,6 +624,41 @@ def approximate_cholesky_depths(
         rc = _run(hobj, dev, E, n, 1, False, lambda: lib.rlap_approx_chol_depths(
             h, row.data_ptr(), col.data_ptr(), w.data_ptr() if w is not None else None, E, n, K, nr_.data_ptr(),
             O_V[o_v], O_N[o_n], d_perm.data_ptr() if d_perm is not None else None, shuffle_seed,
+            out.data_ptr(), out.shape[0], ptr.data_ptr(), ctypes.byref(st)), st)
+        if rc != 0:
+            _raise(rc)
+        last_stats = st.as_dict()
+        res = _trim(out, int(ptr[-1]))
+    if return_device is not None and return_device != "same":
+        res = res.to(return_device)
+    return res, ptr
+
+
+def _depths_views(edge_index, edge_weights, num_nodes, num_remove, o_v, o_n, node_ptr, views, perm, seed, return_device, mode):
+    """approximate_cholesky_depths with `node_ptr` and / or `views`: one rlap_approx_chol_views_depths call."""
+    np_, nr_, K, G = _depths_table(num_remove, num_nodes, node_ptr, views)
+    D = int(nr_.shape[0])
+    n = int(num_nodes)
+    global last_stats
+    dev = _device_for(edge_index)
+    lib, hobj = _handle_obj(dev)
+    h = hobj.ptr
+    _set_mode(lib, h, mode)
+    with torch.cuda.device(dev):
+        row, col, w, E = _prep_edges(edge_index, edge_weights, dev)
+        d_perm = None
+        if o_v == "random" and perm is not None:
+            d_perm = perm.to(device=dev, dtype=torch.int64).contiguous()
+            assert d_perm.numel() == K * n, "perm must hold K * num_nodes entries"
+        shuffle_seed = _seed_from(seed) if (o_n == "random" or o_v != "degree" or mode == "frontier") else 0
+        out = torch.empty((max(D * K * E, 1), 3), dtype=torch.float64, device=dev)   # (an elimination never adds entries)
+        ptr = torch.zeros(D * K * G + 1, dtype=torch.int64)
+        st = _lib.Stats()
+        # the arena of a batched call on the K-fold union (include/rlap_hip.h)
+        rc = _run(hobj, dev, K * E, K * n, K * G, False, lambda: lib.rlap_approx_chol_views_depths(
+            h, row.data_ptr(), col.data_ptr(), w.data_ptr() if w is not None else None, E, G,
+            np_.data_ptr(), K, D, nr_.data_ptr(), O_V[o_v], O_N[o_n],
+            d_perm.data_ptr() if d_perm is not None else None, shuffle_seed,
             out.data_ptr(), out.shape[0], ptr.data_ptr(), ctypes.byref(st)), st)
         if rc != 0:
             _raise(rc)
