@@ -48,7 +48,8 @@ enum {
     RLAP_E_HIP = 8,
     RLAP_E_TOO_LARGE = 9,     /* nnz + growth pool exceeds int32 slot ids */
     RLAP_E_INTERNAL = 10,
-    RLAP_E_WORKSPACE = 11     /* caller-provided workspace / uniform table too small: rlap_workspace_needed() says how much */
+    RLAP_E_WORKSPACE = 11,    /* caller-provided workspace / uniform table too small: rlap_workspace_needed() says how much */
+    RLAP_E_NOT_GROUPED = 12   /* rlap_snapshot_stats: a column id starts two separate blocks of rows in one segment */
 };
 
 typedef struct {
@@ -212,6 +213,38 @@ int rlap_approx_chol_views_depths(rlap_handle h, const int64_t* d_row, const int
                                   int64_t G, const int64_t* h_node_ptr, int64_t K, int64_t D, const int64_t* h_num_remove,
                                   int o_v, int o_n, const int64_t* d_perm, uint64_t shuffle_seed,
                                   double* d_out, int64_t out_cap_rows, int64_t* h_out_ptr, rlap_stats* h_stats);
+
+/* Snapshot statistics: for every segment s of a result of the calls above (rows [ptr[s], ptr[s+1]) of d_sc, S segments), its node
+ * count and the largest eigenvalue of its symmetric adjacency matrix A -- what scripts/rlap_vc_spectral.py records per snapshot
+ * (torch.unique, the row count, svd_lowrank of to_dense_adj) without a dense matrix.
+ *   d_sc, m       : (m, 3) f64 rows [row, col, w] as the calls return them: every column's rows contiguous, the matrix symmetric
+ *   d_ptr         : [S+1] row offsets (0 = ptr[0] <= ... <= ptr[S] = m)
+ *   d_node_ptr    : NULL: every id lies in [0, num_nodes); else [G+1] offsets with G dividing S: segment s is graph s % G and its ids
+ *                   lie in [node_ptr[s % G], node_ptr[s % G + 1]) (batched, views and depths results all put the graph fastest)
+ *   weighted      : 0: A has unit entries (to_dense_adj without edge_attr); else the rows' weights
+ *   tol, max_iter : Lanczos stops at step j when beta_j |y_j| <= tol * theta_j (theta_j the largest eigenvalue of T_j, y its unit
+ *                   eigenvector); 0 < tol, 1 <= max_iter <= 1024
+ *   d_nodes       : [S] distinct ids of the segment's rows
+ *   d_lambda_max  : [S] the largest eigenvalue of A (0 for a segment without rows); for non-negative A its spectral radius
+ *   d_iters, d_converged : [S] Lanczos steps taken, and whether the bound was met within max_iter (1 for an empty segment)
+ *   h_info        : (nullable) what the call did
+ * Deterministic: the same input gives the same bits.  d_sc and d_ptr are only read.  Scratch comes from the arena (RLAP_E_WORKSPACE
+ * when a caller-provided one is too small, rlap_workspace_needed() saying how much).  Layout errors: an id out of its segment's range
+ * RLAP_E_INDEX_RANGE, a column id that starts two blocks of one segment RLAP_E_NOT_GROUPED, a row id without a column of its own
+ * RLAP_E_NOT_SYMMETRIC; a bad ptr / node_ptr RLAP_E_BAD_ARG. */
+typedef struct {
+    int64_t small_segments;   /* segments that ran in one workgroup each (up to 7,168 nodes) */
+    int64_t large_segments;   /* segments whose Lanczos steps ran as device-wide launches    */
+    int64_t lanczos_steps;    /* steps of the longest segment                                */
+    int64_t large_steps;      /* steps enqueued for the large segments (in chunks of 32)     */
+    int64_t large_launches;   /* device-wide launches of those steps                         */
+    int32_t host_syncs;       /* host synchronisations of the call                           */
+    int32_t not_converged;    /* segments that stopped without meeting the bound             */
+} rlap_snapshot_info;
+
+int rlap_snapshot_stats(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
+                        int64_t G, int64_t num_nodes, int weighted, double tol, int32_t max_iter, int64_t* d_nodes,
+                        double* d_lambda_max, int32_t* d_iters, int32_t* d_converged, rlap_snapshot_info* h_info);
 
 /* The op with the step BEFORE the path fused in (scripts/node_shared.py:326-327,
  * scripts/augmentor_benchmarks.py:77-78):

@@ -19,10 +19,11 @@ EXPORTS = [
     "rlap_approx_chol_from_edges", "rlap_debug_set_limits", "rlap_pack_rows", "rlap_unpack_rows",
     "rlap_workspace_bytes", "rlap_workspace_query", "rlap_set_workspace", "rlap_workspace_needed", "rlap_debug_set_poison", "rlap_debug_set_jitter",
     "rlap_set_rng_mode", "rlap_approx_chol_views", "rlap_approx_chol_depths", "rlap_debug_set_flow_limits",
-    "rlap_approx_chol_views_depths",
+    "rlap_approx_chol_views_depths", "rlap_snapshot_stats",
 ]
 
 E_WORKSPACE = 11   # RLAP_E_WORKSPACE
+E_NOT_GROUPED = 12   # RLAP_E_NOT_GROUPED
 
 # rlap_stats.elim_kernel
 KERNEL_NONE, KERNEL_ROUND, KERNEL_FLOW = 0, 1, 2
@@ -41,6 +42,18 @@ class Stats(ctypes.Structure):
         ("n_retries", ctypes.c_int32), ("reserved", ctypes.c_int32),
         ("n_rounds", ctypes.c_int64), ("n_singles", ctypes.c_int64),
         ("elim_kernel", ctypes.c_int32), ("retry_causes", ctypes.c_int32), ("flow_abort", ctypes.c_int32), ("pad", ctypes.c_int32),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class SnapshotInfo(ctypes.Structure):
+    """rlap_snapshot_info (include/rlap_hip.h)."""
+    _fields_ = [
+        ("small_segments", ctypes.c_int64), ("large_segments", ctypes.c_int64), ("lanczos_steps", ctypes.c_int64),
+        ("large_steps", ctypes.c_int64), ("large_launches", ctypes.c_int64), ("host_syncs", ctypes.c_int32),
+        ("not_converged", ctypes.c_int32),
     ]
 
     def as_dict(self):
@@ -83,6 +96,9 @@ def load():
     lib.rlap_approx_chol_views_depths.restype = ci
     lib.rlap_approx_chol_views_depths.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, i64, vp, ci, ci, vp, u64, vp, i64, vp,
                                                   ctypes.POINTER(Stats)]
+    lib.rlap_snapshot_stats.restype = ci
+    lib.rlap_snapshot_stats.argtypes = [vp, vp, i64, vp, i64, vp, i64, i64, ci, ctypes.c_double, ctypes.c_int32, vp, vp, vp, vp,
+                                        ctypes.POINTER(SnapshotInfo)]
     lib.rlap_approx_chol_views.restype = ci
     lib.rlap_approx_chol_views.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, vp, ci, ci, vp, u64, vp, i64, vp,
                                            ctypes.POINTER(Stats)]

@@ -142,13 +142,32 @@ class rLapDepths:
         assert views is None or (int(views) == views and views >= 1), "views: None or a positive int"
         self.o_v, self.o_n, self.keep_weights, self.seed, self.mode, self.views = o_v, o_n, keep_weights, seed, mode, views
 
-    def augment(self, g):
+    def _snapshots(self, g):
         x, edge_index, edge_weights = g.unfold() if hasattr(g, "unfold") else g
         num_nodes = int(edge_index.max().item()) + 1 if edge_index.numel() else 0
         self.num_remove = [int(f * num_nodes) for f in self.fracs]
         extra = {} if self.views is None else {"views": int(self.views)}
         sc, ptr = ops.approximate_cholesky_depths(edge_index, edge_weights, num_nodes, self.num_remove, self.o_v, self.o_n,
                                                   seed=self.seed, return_device="same", mode=self.mode, **extra)
+        return x, sc, ptr, num_nodes
+
+    def stats(self, g, weighted: bool = False, tol: float = 1e-10, max_iter: int = 1000):
+        """The three lists scripts/rlap_vc_spectral.py records per snapshot (get_rlap_sc_stats: max_sv, num_unique_nodes, num_edges)
+        for every run and depth of ONE call, computed on the device by ops.snapshot_stats: a dict of (runs, depths) tensors
+        `max_sv` (float64: the largest eigenvalue of the unweighted adjacency, or with `weighted` of the Schur-complement weights),
+        `node_count` and `edge_count` (int64: distinct ids and directed rows), plus `converged` (bool).  runs = views (1 with
+        views=None): row r is run r, column k depth fracs[k] -- the layout plot_sv_trend / plot_edge_count_trend average over."""
+        _, sc, ptr, num_nodes = self._snapshots(g)
+        st = ops.snapshot_stats(sc, ptr, num_nodes, weighted=weighted, tol=tol, max_iter=max_iter)
+        D, R = len(self.fracs), 1 if self.views is None else int(self.views)
+
+        def grid(t):   # (snapshots are depth-major, then view)
+            return t.reshape(D, R).t().contiguous()
+        return {"max_sv": grid(st["lambda_max"]), "node_count": grid(st["nodes"]), "edge_count": grid(st["rows"]),
+                "converged": grid(st["converged"])}
+
+    def augment(self, g):
+        x, sc, ptr, num_nodes = self._snapshots(g)
 
         def graph(i):
             part = sc[int(ptr[i]):int(ptr[i + 1])]

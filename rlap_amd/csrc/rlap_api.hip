@@ -4,6 +4,7 @@
 // rocPRIM (AMD's native primitives, header-only) supplies the device radix sort
 // and prefix sums used for plumbing (COO ordering, offsets).
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,6 +17,7 @@
 #include "../../include/rlap_hip.h"
 #include "rlap_core.h"
 #include "rlap_kernels.h"
+#include "rlap_stats.h"
 
 using namespace rlap;
 
@@ -1077,6 +1079,7 @@ const char* rlap_status_string(int status) {
         case RLAP_E_HIP: return "HIP runtime error";
         case RLAP_E_TOO_LARGE: return "problem exceeds int32 slot ids";
         case RLAP_E_WORKSPACE: return "caller-provided workspace too small (see rlap_workspace_needed)";
+        case RLAP_E_NOT_GROUPED: return "a column's rows are not contiguous within a segment";
         default: return "internal error";
     }
 }
@@ -1242,6 +1245,38 @@ int rlap_approx_chol_from_edges(rlap_handle h, const int64_t* d_src, const int64
     Call c{d_src, d_dst, d_w, E, 1, node_ptr, tt, o_v, o_n, d_perm, shuffle_seed, d_out, out_cap_rows, rp, h_stats, symmetrize ? 1 : 0};
     int rc = run_call(h, c);
     *h_out_rows = rp[1];
+    return rc;
+}
+
+int rlap_snapshot_stats(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
+                        int64_t G, int64_t num_nodes, int weighted, double tol, int32_t max_iter, int64_t* d_nodes,
+                        double* d_lambda_max, int32_t* d_iters, int32_t* d_converged, rlap_snapshot_info* h_info) {
+    if (!h || !d_ptr || S < 1 || m < 0 || num_nodes < 0 || (m > 0 && !d_sc) || !d_nodes || !d_lambda_max || !d_iters || !d_converged) return RLAP_E_BAD_ARG;
+    if (!(tol > 0.0) || !std::isfinite(tol) || max_iter < 1 || max_iter > STATS_MAX_ITER) return RLAP_E_BAD_ARG;
+    if (d_node_ptr ? (G < 1 || S % G != 0) : false) return RLAP_E_BAD_ARG;
+    if (!d_node_ptr) G = 1;
+    if (m >= INT32_MAX || S >= (int64_t)1 << 30) return RLAP_E_TOO_LARGE;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device);
+    const size_t need = snapshot_stats_bytes(m, S, G, num_nodes, max_iter);
+    h->ws_needed = need;
+    void* base = nullptr;
+    size_t have = 0;
+    if (h->ext_ws) {
+        if (need > h->ext_ws_bytes) return RLAP_E_WORKSPACE;
+        base = h->ext_ws; have = h->ext_ws_bytes;
+    } else {
+        ENSURE(h->own_ws, need);
+        base = h->own_ws.p; have = h->own_ws.cap;
+    }
+    SnapshotStatsArgs a{d_sc, m, d_ptr, S, d_node_ptr, G, num_nodes, weighted, tol, max_iter, d_nodes, d_lambda_max, d_iters, d_converged};
+    SnapshotStatsReport rep;
+    const int rc = snapshot_stats_run(h->stream, base, have, a, &rep);
+    if (h_info) {
+        h_info->small_segments = rep.small_segments; h_info->large_segments = rep.large_segments;
+        h_info->lanczos_steps = rep.lanczos_steps; h_info->large_steps = rep.large_steps; h_info->large_launches = rep.large_launches;
+        h_info->host_syncs = rep.host_syncs; h_info->not_converged = rep.not_converged;
+    }
     return rc;
 }
 

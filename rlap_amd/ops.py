@@ -669,6 +669,106 @@ def _depths_views(edge_index, edge_weights, num_nodes, num_remove, o_v, o_n, nod
     return res, ptr
 
 
+SNAPSHOT_MAX_ITER = 1024   # bound of max_iter (include/rlap_hip.h::rlap_snapshot_stats)
+
+
+def _ptr_table(x, what: str, first: int, last: Optional[int]) -> Tensor:
+    """A 1-D int64 CPU offset table: at least two entries, x[0] == first, non-decreasing, x[-1] == last (when given)."""
+    t = _int_tensor(x, what)
+    if t.dim() != 1 or t.numel() < 2:
+        raise ValueError(f"{what}: a 1-D table of at least two offsets")
+    if int(t[0]) != first or bool((t[1:] < t[:-1]).any()):
+        raise ValueError(f"{what}: non-decreasing offsets starting at {first}")
+    if last is not None and int(t[-1]) != last:
+        raise ValueError(f"{what}[-1] ({int(t[-1])}) must equal {last}")
+    return t.contiguous()
+
+
+def _snapshot_args(sc: Tensor, ptr, num_nodes: int, node_ptr, tol: float, max_iter: int) -> Tuple[Tensor, Optional[Tensor]]:
+    """Host-side checks of snapshot_stats, made before anything is launched: (ptr, node_ptr) as int64 CPU tensors."""
+    if not isinstance(sc, Tensor) or sc.dim() != 2 or sc.shape[1] != 3:
+        raise ValueError("sc: an (m, 3) tensor of rows [row, col, w]")
+    if isinstance(num_nodes, bool) or not hasattr(num_nodes, "__index__") or num_nodes.__index__() < 0:
+        raise ValueError(f"num_nodes: a non-negative integer, got {num_nodes!r}")
+    n = num_nodes.__index__()
+    p = _ptr_table(ptr, "ptr", 0, int(sc.shape[0]))
+    S = p.numel() - 1
+    np_ = None
+    if node_ptr is not None:
+        np_ = _ptr_table(node_ptr, "node_ptr", 0, n)
+        G = np_.numel() - 1
+        if S % G != 0:
+            raise ValueError(f"node_ptr has {G} graphs, which does not divide the {S} segments of ptr")
+    if isinstance(tol, bool) or not isinstance(tol, (int, float)) or not (0.0 < float(tol) < float("inf")):
+        raise ValueError(f"tol: a positive number, got {tol!r}")
+    if isinstance(max_iter, bool) or not hasattr(max_iter, "__index__") or not 1 <= max_iter.__index__() <= SNAPSHOT_MAX_ITER:
+        raise ValueError(f"max_iter: an integer in [1, {SNAPSHOT_MAX_ITER}], got {max_iter!r}")
+    return p, np_
+
+
+def snapshot_stats(
+    sc: Tensor,
+    ptr: Union[Tensor, Sequence[int]],
+    num_nodes: int,
+    *,
+    node_ptr: Optional[Union[Tensor, Sequence[int]]] = None,
+    weighted: bool = False,
+    tol: float = 1e-10,
+    max_iter: int = 1000,
+) -> dict:
+    """Per-snapshot statistics of a result of the calls above -- what scripts/rlap_vc_spectral.py:14-55 (get_rlap_sc_stats)
+    records for every snapshot, computed on the device for all snapshots at once and without a dense matrix.
+
+    `sc` is an (m, 3) [row, col, w] result and `ptr` its S+1 row offsets: segment s is rows [ptr[s], ptr[s+1]).  Id ranges: with
+    node_ptr=None every id lies in [0, num_nodes) (single, views and depths results); with `node_ptr` (G+1 offsets, G dividing S)
+    segment s is graph g = s % G and its ids lie in [node_ptr[g], node_ptr[g+1]) -- batched (g), views (k, g) and depths (d, k, g)
+    results all put the graph index fastest.
+
+    Returns a dict of (S,) tensors on sc's device:
+      nodes      : distinct ids in the segment's rows, torch.unique(sc[ptr[s]:ptr[s+1], :2]).numel()  (num_unique_nodes)
+      rows       : ptr[s+1] - ptr[s]                                                                    (num_edges)
+      lambda_max : the largest eigenvalue of the segment's symmetric adjacency A, unweighted (unit entries, as to_dense_adj without
+                   edge_attr) or with `weighted` the rows' weights; 0 for a segment without rows.  For A >= 0 (Perron-Frobenius)
+                   it is the spectral radius and the largest singular value, the script's max_sv without svd_lowrank's estimate
+      iters      : Lanczos steps taken (float64 plain three-term recurrence from the normalised all-ones vector on the segment's
+                   ids; the largest eigenvalue theta of T_j found by Sturm bisection every 4 steps)
+      converged  : whether beta_j |y_j| <= tol * theta (some eigenvalue of A lies within tol * theta of theta) held within max_iter
+    The same input gives the same bits.  `sc` and `ptr` are only read; the scratch is the handle's arena, so the call does not
+    change later results of any other.  A column whose rows are not contiguous within its segment, a row id without a column, or
+    an id outside its segment's range raise ValueError.  `last_stats` then holds what the call did (rlap_snapshot_info).
+    """
+    p, np_ = _snapshot_args(sc, ptr, num_nodes, node_ptr, tol, max_iter)
+    global last_stats
+    S = p.numel() - 1
+    n = int(num_nodes)
+    dev = _device_for(sc)
+    lib, hobj = _handle_obj(dev)
+    h = hobj.ptr
+    with torch.cuda.device(dev):
+        x = sc.to(device=dev, dtype=torch.float64).contiguous()
+        d_ptr = p.to(dev)
+        d_np = np_.to(dev) if np_ is not None else None
+        G = np_.numel() - 1 if np_ is not None else 1
+        nodes = torch.empty(S, dtype=torch.int64, device=dev)
+        lam = torch.empty(S, dtype=torch.float64, device=dev)
+        iters = torch.empty(S, dtype=torch.int32, device=dev)
+        conv = torch.empty(S, dtype=torch.int32, device=dev)
+        info = _lib.SnapshotInfo()
+        st = _lib.Stats()
+        m = int(x.shape[0])
+        rc = _run(hobj, dev, m, None, G, False, lambda: lib.rlap_snapshot_stats(
+            h, x.data_ptr() if m else None, m, d_ptr.data_ptr(), S, d_np.data_ptr() if d_np is not None else None, G, n,
+            1 if weighted else 0, float(tol), int(max_iter), nodes.data_ptr(), lam.data_ptr(), iters.data_ptr(), conv.data_ptr(),
+            ctypes.byref(info)), st)
+        if rc == _lib.E_NOT_GROUPED:
+            raise ValueError(f"rlap: {_lib.status_string(rc)}")
+        if rc != 0:
+            _raise(rc)
+        last_stats = info.as_dict()
+        rows = d_ptr[1:] - d_ptr[:-1]
+    return {"nodes": nodes, "rows": rows, "lambda_max": lam, "iters": iters, "converged": conv.bool()}
+
+
 def identity(a: Tensor) -> Tensor:
     """Boundary self-test (reference: rlap/ops.py:61-63): tensor -> column-major
     staging -> tensor, on the GPU; returns a tensor on `a`'s device."""
