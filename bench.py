@@ -14,6 +14,10 @@ One "step" = one full pass of the hot path (COO in HBM -> sc_edge_info in HBM).
 
 `python bench.py --gpus N` without a torchrun environment starts the N ranks itself (one child process per
 GPU, before anything touches the GPU in this process).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line.  `--full` adds what
+takes runs of its own: the CPU port baseline with its parity check against the timed output, and on one GPU the
+unsorted-input and reference-order lines (c3) or one GPU's shard of the 8-GPU batch (c5).
 """
 import argparse
 import hashlib
@@ -45,8 +49,11 @@ def parse_args(argv=None):
     ap.add_argument("--weighted", action="store_true", help="SURVEY 8(d) variant: w ~ U(0.5,1.5) per undirected edge, seed 3 (tie-free path)")
     ap.add_argument("--mode", choices=["exact", "frontier"], default="exact",
                     help="c3: 'frontier' = counter-based uniforms (rlap_set_rng_mode; not the reference's stream: never the headline line)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-runs", type=int, default=5, help="c3: full oracle runs the CPU baseline is the median of (SURVEY 8(d) says 10; five of the headline workload take about 25 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: CPU port baseline and parity, unsorted-input, "
+                         "reference-order and shard-of-8 lines (one GPU)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU port baseline and its parity check")
+    ap.add_argument("--cpu-runs", type=int, default=5, help="c3 --full: full oracle runs the CPU baseline is the median of (SURVEY 8(d) says 10; five of the headline workload take about 25 s)")
     ap.add_argument("--no-gather", action="store_true")
     ap.add_argument("--master-port", type=int, default=29541)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -284,7 +291,7 @@ def main():
     n_elim_all, rows_all = float(units[0].item()), float(units[1].item())
 
     extra = {}
-    if world == 1 and not c5:
+    if args.full and world == 1 and not c5:
         # the same graph with its COO rows in random order (what a caller that did not coalesce hands over): the call then sorts
         # (the timed steps above are fed a (col,row)-sorted COO -- like torch_geometric's coalesced graphs -- and skip the sort)
         shuf = torch.randperm(ei.shape[1], device=dev, generator=torch.Generator(device=dev).manual_seed(11))
@@ -301,9 +308,9 @@ def main():
         extra["unsorted_input_same_rows"] = bool(sc_u.shape == sc.shape and torch.equal(sc_u, sc))
         del ei_u, w_u, sc_u, shuf
     rand_line = None
-    if world == 1 and not c5 and o_v == "degree" and args.mode == "exact":
+    if args.full and world == 1 and not c5 and o_v == "degree" and args.mode == "exact":
         # the same graph in the reference's DEFAULT order (o_v="random", rlap/ops.py:7-14): the multi-CU dataflow kernel; reported beside
-        # the headline (never instead of it) so that the driver's record carries it -- three timed calls, parity against the oracle below
+        # the headline (never instead of it) in the --full line -- three timed calls, parity against the oracle below
         gr = torch.Generator(); gr.manual_seed(1234)
         perm_r = torch.randperm(n, generator=gr)
         perm_r_dev = perm_r.to(dev)
@@ -319,7 +326,7 @@ def main():
                      "n_eliminated": rs[-1]["n_eliminated"], "out_rows": rs[-1]["out_rows"], "n_retries": sum(x["n_retries"] for x in rs),
                      "elimination_kernel": "k_eliminate_flow" if rs[-1]["n_rounds"] == 0 else "k_eliminate_batch"}
         rand_line["value"] = rand_line["n_eliminated"] / (rand_line["ms_per_step"] * 1e-3)
-    if world == 1 and c5 and args.graphs >= 8:
+    if args.full and world == 1 and c5 and args.graphs >= 8:
         # one GPU's share of the 8-GPU run (BASELINE config 5: 128 graphs per GPU), measured here: the strong-scaling floor
         # of the configuration is this call's latency, projected scaling at 8 GPUs = full batch / shard (exchange not included)
         Gs = args.graphs // 8
@@ -394,7 +401,7 @@ def main():
             "roofline_sc_merge": roof("k_sc_merge", merge_bytes, ms_merge),
             "roofline_sc_compact": roof("k_sc_compact", compact_bytes, ms_compact),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             import oracle  # cpu_baseline leg only
             if not c5:
                 # median of `cpu_runs` full runs of the oracle (the reference's own harness repeats its timing too,

@@ -41,7 +41,7 @@ for r in rows:
     a[0] += int(r["Calls"]); a[1] += int(r["TotalDurationNs"])
 tot = sum(v[1] for v in agg.values())
 with open(os.path.join(PROF, f"{rnd}_kernel_stats_bench_c3.csv"), "w") as f:
-    f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline (7 calls of the op: 1 warm-up + 3 timed + 3 of the unsorted-input line; rocPRIM template names shortened)\n")
+    f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline (7 calls of the op: 1 warm-up + 3 timed + 3 of the unsorted-input line; rocPRIM template names shortened)\n")
     f.write("kernel,calls,total_ms,avg_us,percent\n")
     for k, (c, t) in sorted(agg.items(), key=lambda kv: -kv[1][1]):
         f.write(f"{k},{c},{t/1e6:.3f},{t/c/1e3:.1f},{100*t/tot:.3f}\n")
@@ -55,7 +55,7 @@ if hits_c5:
         a[0] += int(r["Calls"]); a[1] += int(r["TotalDurationNs"])
     tot5 = sum(v[1] for v in agg5.values())
     with open(os.path.join(PROF, f"{rnd}_kernel_stats_bench_c5.csv"), "w") as f:
-        f.write(f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --workload c5 --steps 5 --warmup 2 --no-cpu-baseline (7 calls of the 1024-graph batch + 7 of its 128-graph shard: BA(4096,8), o_v=random; measured at {os.environ.get('RLAP_COMMIT', '?')}; rocPRIM template names shortened)\n")
+        f.write(f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --workload c5 --steps 5 --warmup 2 --no-cpu-baseline (7 calls of the 1024-graph batch + 7 of its 128-graph shard: BA(4096,8), o_v=random; measured at {os.environ.get('RLAP_COMMIT', '?')}; rocPRIM template names shortened)\n")
         f.write("kernel,calls,total_ms,avg_us,percent\n")
         for k, (c, t) in sorted(agg5.items(), key=lambda kv: -kv[1][1]):
             f.write(f"{k},{c},{t/1e6:.3f},{t/c/1e3:.1f},{100*t/tot5:.3f}\n")
@@ -74,7 +74,7 @@ fz = load(one("fetch/**/*counter_collection.csv"), "FETCH_SIZE")
 wz = load(one("write/**/*counter_collection.csv"), "WRITE_SIZE")
 per = {}
 with open(os.path.join(PROF, f"{rnd}_pmc_fetch_write_bench_c3.csv"), "w") as f:
-    f.write("# rocprofv3 --kernel-trace --pmc FETCH_SIZE | --pmc WRITE_SIZE (separate passes) -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline; KB as reported\n")
+    f.write("# rocprofv3 --kernel-trace --pmc FETCH_SIZE | --pmc WRITE_SIZE (separate passes) -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline; KB as reported\n")
     f.write("kernel,launches,fetch_KB_per_launch,write_KB_per_launch,ms_per_launch(profiled)\n")
     for k in sorted(set(fz) | set(wz), key=lambda k: -sum(v for v, _ in fz.get(k, [(0, 0)]))):
         if not k.startswith("rlap::"):
@@ -100,7 +100,7 @@ for _f in ("rlap_kernels.hip", "rlap_flow.hip", "rlap_flow.h", "rlap_wave_sort.h
 traffic = {
     "_kernels_sha": _h.hexdigest()[:16],   # bench.py reports these figures only while the kernel sources are the profiled ones
     "_commit": os.environ.get("RLAP_COMMIT"),
-    "_source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on `python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline`, "
+    "_source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on `python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline`, "
                f"profiles/{rnd}_pmc_fetch_write_bench_c3.csv; bytes = KB*1024, summed over the instantiations of a kernel; FETCH_SIZE is uncorrected "
                "(gfx950 reports 1/2 of wide coalesced reads, MI355X_MICROARCH.md HBM section; narrower accesses uncalibrated)",
     "k_eliminate_batch": pick("rlap::k_eliminate_batch_t"),
@@ -115,7 +115,7 @@ try:
     _fb = sum(sum(v for v, _ in _fr[k]) / len(_fr[k]) for k in _fr if k.startswith("rlap::k_eliminate_flow")) * 1024.0
     _wb = sum(sum(v for v, _ in _wr[k]) / len(_wr[k]) for k in _wr if k.startswith("rlap::k_eliminate_flow")) * 1024.0
     if _fb > 0:
-        traffic["k_eliminate_flow"] = {"fetch_bytes": _fb, "write_bytes": _wb, "command": "bench.py --o_v random --steps 1 --warmup 0 --no-cpu-baseline (separate FETCH_SIZE / WRITE_SIZE passes), per launch"}
+        traffic["k_eliminate_flow"] = {"fetch_bytes": _fb, "write_bytes": _wb, "command": "bench.py --full --o_v random --steps 1 --warmup 0 --no-cpu-baseline (separate FETCH_SIZE / WRITE_SIZE passes), per launch"}
 except SystemExit:
     pass
 json.dump(traffic, open(os.path.join(PROF, f"{rnd}_pmc_traffic.json"), "w"), indent=1)
@@ -128,7 +128,7 @@ for r in csv.DictReader(open(one("sq/**/*counter_collection.csv"))):
         sq[r["Counter_Name"]] += float(r["Counter_Value"])
         nlaunch.add(r.get("Dispatch_Id", r.get("Correlation_Id", "")))
 with open(os.path.join(PROF, f"{rnd}_sq_counters_k_eliminate_batch.csv"), "w") as f:
-    f.write(f"# rocprofv3 --kernel-trace --pmc SQ_* -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline; SUM over the {len(nlaunch)} launches of k_eliminate_batch_t<1,0,32> "
+    f.write(f"# rocprofv3 --kernel-trace --pmc SQ_* -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline; SUM over the {len(nlaunch)} launches of k_eliminate_batch_t<1,0,32> "
             "in that command (1 timed + 3 of the unsorted-input line): divide by the launch count for one launch\n")
     for k in sorted(sq):
         f.write(f"\"{k}\",{sq[k]:.6f}\n")
@@ -142,7 +142,7 @@ if hits_r:
         a[0] += int(r["Calls"]); a[1] += int(r["TotalDurationNs"])
     totr = sum(v[1] for v in aggr.values())
     with open(os.path.join(PROF, f"{rnd}_kernel_stats_bench_c3_random.csv"), "w") as f:
-        f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --o_v random --steps 3 --warmup 1 --no-cpu-baseline (7 calls of the op; rocPRIM template names shortened)\n")
+        f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --o_v random --steps 3 --warmup 1 --no-cpu-baseline (7 calls of the op; rocPRIM template names shortened)\n")
         f.write("kernel,calls,total_ms,avg_us,percent\n")
         for k, (c, t) in sorted(aggr.items(), key=lambda kv: -kv[1][1]):
             f.write(f"{k},{c},{t/1e6:.3f},{t/c/1e3:.1f},{100*t/totr:.3f}\n")
@@ -160,7 +160,7 @@ if hits_s:
     except SystemExit:
         pass
     with open(os.path.join(PROF, f"{rnd}_sq_counters_k_eliminate_flow.csv"), "w") as f:
-        f.write(f"# rocprofv3 --kernel-trace --pmc SQ_* -- python3 bench.py --o_v random --steps 1 --warmup 0 --no-cpu-baseline; SUM over the {len(nl)} launches of k_eliminate_flow "
+        f.write(f"# rocprofv3 --kernel-trace --pmc SQ_* -- python3 bench.py --full --o_v random --steps 1 --warmup 0 --no-cpu-baseline; SUM over the {len(nl)} launches of k_eliminate_flow "
                 f"(grid {grid} threads in workgroups of {wg}: the eliminating wave and its helper, two workgroups per CU on every CU); SQ_BUSY_CU_CYCLES / SQ_BUSY_CYCLES = compute units busy on average\n")
         for k in sorted(sqr):
             f.write(f"\"{k}\",{sqr[k]:.6f}\n")
