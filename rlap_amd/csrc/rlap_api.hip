@@ -414,8 +414,6 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
     hipStream_t s = h->stream;
     const int64_t G = c.G, E = c.E;
     const int64_t N = c.h_node_ptr[G];
-    if (c.h_node_ptr[0] != 0) return RLAP_E_BAD_ARG;
-    for (int64_t g = 0; g < G; ++g) if (c.h_node_ptr[g + 1] < c.h_node_ptr[g]) return RLAP_E_BAD_ARG;
     // A views call is the batch of K copies of the input (G1 graphs, N1 vertices, E1eff entries): the COO -> CSR setup runs on the
     // one copy the caller gave, k_views_replicate then writes the union's CSR; everything after it sees the K * G1-graph batch.
     const int64_t K = c.K, G1 = G / K, N1 = N / K;
@@ -465,7 +463,6 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
             for (int64_t g = 0; g < G; ++g) {
                 const int64_t n = c.h_node_ptr[g + 1] - c.h_node_ptr[g];
                 const int64_t ne = std::max<int64_t>(0, std::min<int64_t>(c.h_depths[k * G + g], n - 1));
-                if (k > 0 && ne < std::max<int64_t>(0, std::min<int64_t>(c.h_depths[(k - 1) * G + g], n - 1))) return RLAP_E_BAD_ARG;
                 q += ne;
                 sb[g + 1] = sb[g] + (n - ne);
             }
@@ -948,6 +945,44 @@ int run_call(rlap_handle h, const Call& c) {
     return rc;
 }
 
+// One elimination as the exports ask for it: K views (1: one) of a batch of G graphs given by the caller's h_node_ptr[G+1], with D
+// nested depths each (0: not a depths call) from h_num_remove[max(D, 1)][K*G].
+struct Request {
+    const int64_t* d_row = nullptr; const int64_t* d_col = nullptr; const double* d_w = nullptr; int64_t E = 0;
+    int64_t G = 1; const int64_t* h_node_ptr = nullptr; int64_t K = 1, D = 0; const int64_t* h_num_remove = nullptr;
+    int o_v = 0, o_n = 0; const int64_t* d_perm = nullptr; uint64_t seed = 0;
+    double* d_out = nullptr; int64_t out_cap = 0; int64_t* h_out_ptr = nullptr; int symmetrize = 0; rlap_stats* st = nullptr;
+};
+
+// Every argument check of the exports, in this order: null pointers and counts, o_v / o_n, the COO, the output, node_ptr (starts
+// at 0, never decreases), the size limits of a batched call on the K-fold union (K*G and K*N below 2^30, K*E below 2^31; D*K*G
+// below 2^30), the depth columns (never decrease).  Then the call runs on the union.
+int eliminate(rlap_handle h, const Request& r) {
+    const int64_t E = r.E, G = r.G, K = r.K, D = r.D;
+    if (!h || E < 0 || G < 1 || K < 1 || D < 0 || !r.h_node_ptr || !r.h_num_remove || !r.h_out_ptr) return RLAP_E_BAD_ARG;
+    if (r.o_v < 0 || r.o_v > 2 || r.o_n < 0 || r.o_n > 2) return RLAP_E_BAD_ARG;
+    if (E > 0 && (!r.d_row || !r.d_col)) return RLAP_E_BAD_ARG;
+    if (r.out_cap > 0 && !r.d_out) return RLAP_E_BAD_ARG;
+    if (r.h_node_ptr[0] != 0) return RLAP_E_BAD_ARG;
+    for (int64_t g = 0; g < G; ++g) if (r.h_node_ptr[g + 1] < r.h_node_ptr[g]) return RLAP_E_BAD_ARG;
+    const int64_t N = r.h_node_ptr[G], L30 = (int64_t)1 << 30, L31 = (int64_t)1 << 31;
+    if (K >= L30 || G >= L30 || K * G >= L30 || N > (L30 - 1) / K || E > (L31 - 1) / K) return RLAP_E_TOO_LARGE;
+    const int64_t P = K * G;
+    if (D > 0 && D >= L30 / P) return RLAP_E_TOO_LARGE;
+    for (int64_t d = 1; d < D; ++d)
+        for (int64_t j = 0; j < P; ++j) if (r.h_num_remove[d * P + j] < r.h_num_remove[(d - 1) * P + j]) return RLAP_E_BAD_ARG;
+    // graph k * G + g of the union: ids [k * N + node_ptr[g], k * N + node_ptr[g + 1]); depth d of it is h_num_remove[d][k * G + g]
+    std::vector<int64_t> np((size_t)(P + 1));
+    for (int64_t k = 0; k < K; ++k)
+        for (int64_t g = 0; g < G; ++g) np[(size_t)(k * G + g)] = k * N + r.h_node_ptr[g];
+    np[(size_t)P] = K * N;
+    const Call c{.d_row = r.d_row, .d_col = r.d_col, .d_w = r.d_w, .E = E, .G = P, .h_node_ptr = np.data(),
+                 .h_t = r.h_num_remove + (D > 0 ? D - 1 : 0) * P, .o_v = r.o_v, .o_n = r.o_n, .d_perm = r.d_perm, .seed = r.seed,
+                 .d_out = r.d_out, .out_cap = r.out_cap, .h_out_row_ptr = r.h_out_ptr, .st = r.st, .symmetrize = r.symmetrize,
+                 .K = K, .h_depths = D > 0 ? r.h_num_remove : nullptr, .D = D};
+    return run_call(h, c);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1124,92 +1159,48 @@ int rlap_unpack_rows(rlap_handle h, const void* d_packed, int64_t rows, double* 
 int rlap_approx_chol_batched(rlap_handle h, const int64_t* d_row, const int64_t* d_col, const double* d_w, int64_t E, int64_t G,
                              const int64_t* h_node_ptr, const int64_t* h_num_remove, int o_v, int o_n, const int64_t* d_perm,
                              uint64_t shuffle_seed, double* d_out, int64_t out_cap_rows, int64_t* h_out_row_ptr, rlap_stats* h_stats) {
-    if (!h || G < 1 || E < 0 || !h_node_ptr || !h_num_remove || !h_out_row_ptr) return RLAP_E_BAD_ARG;
-    if (o_v < 0 || o_v > 2 || o_n < 0 || o_n > 2) return RLAP_E_BAD_ARG;
-    if (E > 0 && (!d_row || !d_col)) return RLAP_E_BAD_ARG;
-    if (out_cap_rows > 0 && !d_out) return RLAP_E_BAD_ARG;
-    Call c{d_row, d_col, d_w, E, G, h_node_ptr, h_num_remove, o_v, o_n, d_perm, shuffle_seed, d_out, out_cap_rows, h_out_row_ptr, h_stats, 0};
-    return run_call(h, c);
+    return eliminate(h, {.d_row = d_row, .d_col = d_col, .d_w = d_w, .E = E, .G = G, .h_node_ptr = h_node_ptr, .h_num_remove = h_num_remove,
+                         .o_v = o_v, .o_n = o_n, .d_perm = d_perm, .seed = shuffle_seed, .d_out = d_out, .out_cap = out_cap_rows,
+                         .h_out_ptr = h_out_row_ptr, .st = h_stats});
 }
 
 int rlap_approx_chol_views(rlap_handle h, const int64_t* d_row, const int64_t* d_col, const double* d_w, int64_t E, int64_t G,
                            const int64_t* h_node_ptr, int64_t K, const int64_t* h_num_remove, int o_v, int o_n, const int64_t* d_perm,
                            uint64_t shuffle_seed, double* d_out, int64_t out_cap_rows, int64_t* h_out_ptr, rlap_stats* h_stats) {
-    if (!h || G < 1 || K < 1 || E < 0 || !h_node_ptr || !h_num_remove || !h_out_ptr) return RLAP_E_BAD_ARG;
-    if (o_v < 0 || o_v > 2 || o_n < 0 || o_n > 2) return RLAP_E_BAD_ARG;
-    if (E > 0 && (!d_row || !d_col)) return RLAP_E_BAD_ARG;
-    if (out_cap_rows > 0 && !d_out) return RLAP_E_BAD_ARG;
-    if (h_node_ptr[0] != 0) return RLAP_E_BAD_ARG;
-    for (int64_t g = 0; g < G; ++g) if (h_node_ptr[g + 1] < h_node_ptr[g]) return RLAP_E_BAD_ARG;
-    const int64_t N = h_node_ptr[G];
-    // the union's sizes must respect the limits of a batched call of that size (run_once checks K * E and the slot ids)
-    if (K >= (int64_t)1 << 30 || G >= (int64_t)1 << 30 || K * G >= (int64_t)1 << 30 || (N > 0 && K >= ((int64_t)1 << 30) / N)) return RLAP_E_TOO_LARGE;
-    if (K * (E > 0 ? E : 1) >= (int64_t)1 << 31) return RLAP_E_TOO_LARGE;
-    // graph k * G + g of the union: ids [k * N + node_ptr[g], k * N + node_ptr[g + 1]), num_remove h_num_remove[k * G + g]
-    std::vector<int64_t> np((size_t)(K * G + 1));
-    for (int64_t k = 0; k < K; ++k)
-        for (int64_t g = 0; g < G; ++g) np[(size_t)(k * G + g)] = k * N + h_node_ptr[g];
-    np[(size_t)(K * G)] = K * N;
-    Call c{d_row, d_col, d_w, E, K * G, np.data(), h_num_remove, o_v, o_n, d_perm, shuffle_seed, d_out, out_cap_rows, h_out_ptr, h_stats, 0, K};
-    return run_call(h, c);
+    return eliminate(h, {.d_row = d_row, .d_col = d_col, .d_w = d_w, .E = E, .G = G, .h_node_ptr = h_node_ptr, .K = K,
+                         .h_num_remove = h_num_remove, .o_v = o_v, .o_n = o_n, .d_perm = d_perm, .seed = shuffle_seed, .d_out = d_out,
+                         .out_cap = out_cap_rows, .h_out_ptr = h_out_ptr, .st = h_stats});
 }
 
 int rlap_approx_chol_depths(rlap_handle h, const int64_t* d_row, const int64_t* d_col, const double* d_w, int64_t E, int64_t n,
                             int64_t K, const int64_t* h_num_remove, int o_v, int o_n, const int64_t* d_perm, uint64_t shuffle_seed,
                             double* d_out, int64_t out_cap_rows, int64_t* h_out_ptr, rlap_stats* h_stats) {
-    if (!h || K < 1 || E < 0 || n < 0 || !h_num_remove || !h_out_ptr) return RLAP_E_BAD_ARG;
-    if (o_v < 0 || o_v > 2 || o_n < 0 || o_n > 2) return RLAP_E_BAD_ARG;
-    if (E > 0 && (!d_row || !d_col)) return RLAP_E_BAD_ARG;
-    if (out_cap_rows > 0 && !d_out) return RLAP_E_BAD_ARG;
-    for (int64_t k = 1; k < K; ++k) if (h_num_remove[k] < h_num_remove[k - 1]) return RLAP_E_BAD_ARG;
-    if (K >= (int64_t)1 << 30) return RLAP_E_TOO_LARGE;
-    if (n == 0) {   // (no vertices: K empty snapshots)
-        for (int64_t k = 0; k <= K; ++k) h_out_ptr[k] = 0;
-        if (h_stats) std::memset(h_stats, 0, sizeof(*h_stats));
-        return RLAP_OK;
-    }
-    int64_t node_ptr[2] = {0, n};
-    Call c{d_row, d_col, d_w, E, 1, node_ptr, h_num_remove + (K - 1), o_v, o_n, d_perm, shuffle_seed, d_out, out_cap_rows, h_out_ptr, h_stats, 0, 1,
-           h_num_remove, K};
-    return run_call(h, c);
+    if (K < 1) return RLAP_E_BAD_ARG;   // (D = 0 is a call without depths)
+    const int64_t node_ptr[2] = {0, n};
+    return eliminate(h, {.d_row = d_row, .d_col = d_col, .d_w = d_w, .E = E, .h_node_ptr = node_ptr, .D = K, .h_num_remove = h_num_remove,
+                         .o_v = o_v, .o_n = o_n, .d_perm = d_perm, .seed = shuffle_seed, .d_out = d_out, .out_cap = out_cap_rows,
+                         .h_out_ptr = h_out_ptr, .st = h_stats});
 }
 
 int rlap_approx_chol_views_depths(rlap_handle h, const int64_t* d_row, const int64_t* d_col, const double* d_w, int64_t E,
                                   int64_t G, const int64_t* h_node_ptr, int64_t K, int64_t D, const int64_t* h_num_remove,
                                   int o_v, int o_n, const int64_t* d_perm, uint64_t shuffle_seed,
                                   double* d_out, int64_t out_cap_rows, int64_t* h_out_ptr, rlap_stats* h_stats) {
-    if (!h || G < 1 || K < 1 || D < 1 || E < 0 || !h_node_ptr || !h_num_remove || !h_out_ptr) return RLAP_E_BAD_ARG;
-    if (o_v < 0 || o_v > 2 || o_n < 0 || o_n > 2) return RLAP_E_BAD_ARG;
-    if (E > 0 && (!d_row || !d_col)) return RLAP_E_BAD_ARG;
-    if (out_cap_rows > 0 && !d_out) return RLAP_E_BAD_ARG;
-    if (h_node_ptr[0] != 0) return RLAP_E_BAD_ARG;
-    for (int64_t g = 0; g < G; ++g) if (h_node_ptr[g + 1] < h_node_ptr[g]) return RLAP_E_BAD_ARG;
-    const int64_t N = h_node_ptr[G];
-    // the union's limits are the views call's; the row pointers ([D * K * G + 1]) and the depth table live on the host and in the arena
-    if (K >= (int64_t)1 << 30 || G >= (int64_t)1 << 30 || K * G >= (int64_t)1 << 30 || (N > 0 && K >= ((int64_t)1 << 30) / N)) return RLAP_E_TOO_LARGE;
-    if (K * (E > 0 ? E : 1) >= (int64_t)1 << 31) return RLAP_E_TOO_LARGE;
-    const int64_t P = K * G;
-    if (D >= ((int64_t)1 << 30) / P) return RLAP_E_TOO_LARGE;
-    for (int64_t d = 1; d < D; ++d)
-        for (int64_t j = 0; j < P; ++j) if (h_num_remove[d * P + j] < h_num_remove[(d - 1) * P + j]) return RLAP_E_BAD_ARG;
-    // graph k * G + g of the union: ids [k * N + node_ptr[g], k * N + node_ptr[g + 1]); depth d of it is h_num_remove[d][k * G + g]
-    std::vector<int64_t> np((size_t)(P + 1));
-    for (int64_t k = 0; k < K; ++k)
-        for (int64_t g = 0; g < G; ++g) np[(size_t)(k * G + g)] = k * N + h_node_ptr[g];
-    np[(size_t)P] = K * N;
-    Call c{d_row, d_col, d_w, E, P, np.data(), h_num_remove + (D - 1) * P, o_v, o_n, d_perm, shuffle_seed, d_out, out_cap_rows, h_out_ptr, h_stats, 0, K,
-           h_num_remove, D};
-    return run_call(h, c);
+    if (D < 1) return RLAP_E_BAD_ARG;
+    return eliminate(h, {.d_row = d_row, .d_col = d_col, .d_w = d_w, .E = E, .G = G, .h_node_ptr = h_node_ptr, .K = K, .D = D,
+                         .h_num_remove = h_num_remove, .o_v = o_v, .o_n = o_n, .d_perm = d_perm, .seed = shuffle_seed, .d_out = d_out,
+                         .out_cap = out_cap_rows, .h_out_ptr = h_out_ptr, .st = h_stats});
 }
 
 int rlap_approx_chol(rlap_handle h, const int64_t* d_row, const int64_t* d_col, const double* d_w, int64_t E, int64_t n, int64_t t,
                      int o_v, int o_n, const int64_t* d_perm, uint64_t shuffle_seed, double* d_out, int64_t out_cap_rows,
                      int64_t* h_out_rows, rlap_stats* h_stats) {
-    if (n < 0 || !h_out_rows) return RLAP_E_BAD_ARG;
-    int64_t node_ptr[2] = {0, n};
-    int64_t tt[1] = {t};
+    if (!h_out_rows) return RLAP_E_BAD_ARG;
+    const int64_t node_ptr[2] = {0, n};
     int64_t rp[2] = {0, 0};
-    int rc = rlap_approx_chol_batched(h, d_row, d_col, d_w, E, 1, node_ptr, tt, o_v, o_n, d_perm, shuffle_seed, d_out, out_cap_rows, rp, h_stats);
+    const int rc = eliminate(h, {.d_row = d_row, .d_col = d_col, .d_w = d_w, .E = E, .h_node_ptr = node_ptr, .h_num_remove = &t, .o_v = o_v,
+                                 .o_n = o_n, .d_perm = d_perm, .seed = shuffle_seed, .d_out = d_out, .out_cap = out_cap_rows,
+                                 .h_out_ptr = rp, .st = h_stats});
     *h_out_rows = rp[1];
     return rc;
 }
@@ -1217,13 +1208,11 @@ int rlap_approx_chol(rlap_handle h, const int64_t* d_row, const int64_t* d_col, 
 int rlap_approx_chol_from_edges(rlap_handle h, const int64_t* d_src, const int64_t* d_dst, const double* d_w, int64_t E, int64_t n, int64_t t,
                                 double remove_frac, int symmetrize, int o_v, int o_n, const int64_t* d_perm, uint64_t shuffle_seed,
                                 double* d_out, int64_t out_cap_rows, int64_t* h_out_rows, int64_t* h_num_nodes, rlap_stats* h_stats) {
-    if (!h || E < 0 || !h_out_rows) return RLAP_E_BAD_ARG;
-    if (o_v < 0 || o_v > 2 || o_n < 0 || o_n > 2) return RLAP_E_BAD_ARG;
-    if (E > 0 && (!d_src || !d_dst)) return RLAP_E_BAD_ARG;
-    if (out_cap_rows > 0 && !d_out) return RLAP_E_BAD_ARG;
-    if (n < 0 && d_perm) return RLAP_E_BAD_ARG;   // an injected node_id vector needs a known num_nodes
+    if (!h_out_rows) return RLAP_E_BAD_ARG;
     if (n < 0) {
-        // num_nodes = edge_index.max() + 1 (augmentor_benchmarks.py:77): one reduction + one 8-byte read-back
+        // num_nodes = edge_index.max() + 1 (augmentor_benchmarks.py:77): one reduction + one 8-byte read-back, after the checks of
+        // what it reads (an injected node_id vector needs a known num_nodes); the other checks follow in eliminate()
+        if (!h || E < 0 || (E > 0 && (!d_src || !d_dst)) || d_perm) return RLAP_E_BAD_ARG;
         std::lock_guard<std::mutex> lock(h->mu);
         DeviceGuard dg(h->device);
         unsigned long long mx[2] = {0ull, 0ull};   // max id + 1, any id negative
@@ -1239,11 +1228,11 @@ int rlap_approx_chol_from_edges(rlap_handle h, const int64_t* d_src, const int64
     }
     if (t < 0) t = (int64_t)(remove_frac * (double)n);   // int(frac * num_nodes), augmentor_benchmarks.py:78
     if (h_num_nodes) *h_num_nodes = n;
-    int64_t node_ptr[2] = {0, n};
-    int64_t tt[1] = {t};
+    const int64_t node_ptr[2] = {0, n};
     int64_t rp[2] = {0, 0};
-    Call c{d_src, d_dst, d_w, E, 1, node_ptr, tt, o_v, o_n, d_perm, shuffle_seed, d_out, out_cap_rows, rp, h_stats, symmetrize ? 1 : 0};
-    int rc = run_call(h, c);
+    const int rc = eliminate(h, {.d_row = d_src, .d_col = d_dst, .d_w = d_w, .E = E, .h_node_ptr = node_ptr, .h_num_remove = &t, .o_v = o_v,
+                                 .o_n = o_n, .d_perm = d_perm, .seed = shuffle_seed, .d_out = d_out, .out_cap = out_cap_rows,
+                                 .h_out_ptr = rp, .symmetrize = symmetrize ? 1 : 0, .st = h_stats});
     *h_out_rows = rp[1];
     return rc;
 }

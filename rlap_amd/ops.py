@@ -159,7 +159,7 @@ def _run(hobj, dev, E: int, n_total: int, G: int, symmetrize: bool, call, st):
     if causes & _lib.RETRY_FLOW_GAVE_UP:
         # (bit 7, a reorder buffer too small, is a designed fall-back and stays quiet)
         warnings.warn(f"rlap: the dataflow elimination kernel gave up ({_lib.FLOW_ABORT_REASONS.get(abort, abort)}); "
-                      "the call was repeated on the round kernel", DataflowFallbackWarning, stacklevel=3)
+                      "the call was repeated on the round kernel", DataflowFallbackWarning, stacklevel=4)
     return rc
 
 
@@ -235,6 +235,49 @@ def _seed_from(seed: Optional[int]) -> int:
     return int(seed) & (2**64 - 1)
 
 
+def _eliminate(export: str, args: tuple, edge_index: Tensor, edge_weights: Optional[Tensor], o_v: str, o_n: str, perm, seed,
+               mode: str, return_device, *, n: Optional[int], G: int = 1, K: int = 1, D: int = 1, symmetrize: bool = False,
+               rows_only: bool = False, outs: tuple = ()):
+    """The body every elimination entry point shares: one call of the C export `export`, whose own arguments are `args` (those
+    between E and o_v) and `outs` (outputs between the row offsets and the stats).  The call is K views of a batch of G graphs of
+    n vertices in all (None: found by the call), D nested depths each, of the input as given or with both directions of every edge
+    (symmetrize).  That sizes the output (D*K*E rows, twice that for symmetrize: an elimination never adds entries), the row
+    offsets (D*K*G+1, or with rows_only the one row count the export writes), the arena (_run) and `perm` (K*n entries).
+    Returns (sc_edge_info, ptr): ptr the row offsets, a c_int64 with rows_only."""
+    assert edge_index.shape[0] == 2
+    assert o_v in ["random", "degree", "coarsen"]
+    assert o_n in ["asc", "desc", "random"]
+    global last_stats
+    dev = _device_for(edge_index)
+    lib, hobj = _handle_obj(dev)
+    _set_mode(lib, hobj.ptr, mode)
+    fn = getattr(lib, export)
+    with torch.cuda.device(dev):
+        row, col, w, E = _prep_edges(edge_index, edge_weights, dev)
+        d_perm = None
+        if o_v == "random" and perm is not None:
+            d_perm = perm.to(device=dev, dtype=torch.int64).contiguous()
+            assert n is not None and d_perm.numel() == K * n, "perm must hold views * num_nodes entries"
+        # perm None: the reference shuffles 0..n-1 with std::random_device (preconditioner.cc:594-596); here every node_id vector is
+        # drawn on the device from `seed` by the C ABI's keyed shuffle (ONE meaning of `seed` in this module)
+        shuffle_seed = _seed_from(seed) if (o_n == "random" or o_v != "degree" or mode == "frontier") else 0
+        out = torch.empty((max(D * K * (2 if symmetrize else 1) * E, 1), 3), dtype=torch.float64, device=dev)
+        ptr = ctypes.c_int64(0) if rows_only else torch.zeros(D * K * G + 1, dtype=torch.int64)
+        st = _lib.Stats()
+        # (views: the arena of a batched call on the K-fold union, include/rlap_hip.h)
+        rc = _run(hobj, dev, K * E, None if n is None else K * n, K * G, symmetrize, lambda: fn(
+            hobj.ptr, row.data_ptr(), col.data_ptr(), w.data_ptr() if w is not None else None, E, *args, O_V[o_v], O_N[o_n],
+            d_perm.data_ptr() if d_perm is not None else None, shuffle_seed, out.data_ptr(), out.shape[0],
+            ctypes.byref(ptr) if rows_only else ptr.data_ptr(), *outs, ctypes.byref(st)), st)
+        if rc != 0:
+            _raise(rc)
+        last_stats = st.as_dict()
+        res = _trim(out, ptr.value if rows_only else int(ptr[-1]))
+    if return_device is not None and return_device != "same":
+        res = res.to(return_device)
+    return res, ptr
+
+
 def approximate_cholesky(
     edge_index: Tensor,
     edge_weights: Optional[Tensor],
@@ -255,39 +298,10 @@ def approximate_cholesky(
     shuffles reproducibly), `return_device` ("cpu" as the reference, None/"same" to
     keep the result on the GPU).
     """
-    assert edge_index.shape[0] == 2
-    assert o_v in ["random", "degree", "coarsen"]
-    assert o_n in ["asc", "desc", "random"]
-    global last_stats
-    dev = _device_for(edge_index)
-    lib, hobj = _handle_obj(dev)
-    h = hobj.ptr
-    _set_mode(lib, h, mode)
-    with torch.cuda.device(dev):
-        row, col, w, E = _prep_edges(edge_index, edge_weights, dev)
-        n = int(num_nodes)
-        d_perm = None
-        if o_v == "random" and perm is not None:
-            d_perm = perm.to(device=dev, dtype=torch.int64).contiguous()
-            assert d_perm.numel() == n
-        # perm None: the reference shuffles 0..n-1 with std::random_device (preconditioner.cc:594-596); here the node_id vector is
-        # drawn on the device from `seed` by the C ABI's keyed shuffle -- the same draw as approximate_cholesky_from_edges and as
-        # graph 0 of approximate_cholesky_batched with that seed (ONE meaning of `seed` in this module)
-        shuffle_seed = _seed_from(seed) if (o_n == "random" or o_v != "degree" or mode == "frontier") else 0
-        out = torch.empty((max(E, 1), 3), dtype=torch.float64, device=dev)
-        rows = ctypes.c_int64(0)
-        st = _lib.Stats()
-        rc = _run(hobj, dev, E, n, 1, False, lambda: lib.rlap_approx_chol(
-            h, row.data_ptr(), col.data_ptr(), w.data_ptr() if w is not None else None, E, n, int(num_remove),
-            O_V[o_v], O_N[o_n], d_perm.data_ptr() if d_perm is not None else None, shuffle_seed,
-            out.data_ptr(), out.shape[0], ctypes.byref(rows), ctypes.byref(st)), st)
-        if rc != 0:
-            _raise(rc)
-        last_stats = st.as_dict()
-        res = _trim(out, rows.value)
-    if return_device is None or return_device == "same":
-        return res
-    return res.to(return_device)
+    n = int(num_nodes)
+    res, _ = _eliminate("rlap_approx_chol", (n, int(num_remove)), edge_index, edge_weights, o_v, o_n, perm, seed, mode,
+                        return_device, n=n, rows_only=True)
+    return res
 
 
 def approximate_cholesky_from_edges(
@@ -310,40 +324,12 @@ def approximate_cholesky_from_edges(
     `num_nodes = edge_index.max() + 1`, `num_remove = int(remove_frac * num_nodes)`
     (scripts/augmentor_benchmarks.py:77-78) when they are None -- found on the device, without a
     torch reduction + `.item()`.  Returns (sc_edge_info on the device, num_nodes)."""
-    assert edge_index.shape[0] == 2
-    assert o_v in ["random", "degree", "coarsen"]
-    assert o_n in ["asc", "desc", "random"]
-    global last_stats
-    dev = _device_for(edge_index)
-    lib, hobj = _handle_obj(dev)
-    h = hobj.ptr
-    _set_mode(lib, h, mode)
-    with torch.cuda.device(dev):
-        row, col, w, E = _prep_edges(edge_index, edge_weights, dev)
-        n = -1 if num_nodes is None else int(num_nodes)
-        t = -1 if num_remove is None else int(num_remove)
-        d_perm = None
-        if o_v == "random" and perm is not None:
-            assert n >= 0, "an injected perm needs num_nodes"
-            d_perm = perm.to(device=dev, dtype=torch.int64).contiguous()
-            assert d_perm.numel() == n
-        # (perm None: the node_id vector is drawn on the device from the seed)
-        shuffle_seed = _seed_from(seed) if (o_n == "random" or o_v != "degree" or mode == "frontier") else 0
-        cap = max((2 * E) if symmetrize else E, 1)
-        out = torch.empty((cap, 3), dtype=torch.float64, device=dev)
-        rows = ctypes.c_int64(0)
-        nn = ctypes.c_int64(0)
-        st = _lib.Stats()
-        rc = _run(hobj, dev, E, n if n >= 0 else None, 1, bool(symmetrize), lambda: lib.rlap_approx_chol_from_edges(
-            h, row.data_ptr(), col.data_ptr(), w.data_ptr() if w is not None else None, E, n, t, float(remove_frac),
-            1 if symmetrize else 0, O_V[o_v], O_N[o_n], d_perm.data_ptr() if d_perm is not None else None, shuffle_seed,
-            out.data_ptr(), out.shape[0], ctypes.byref(rows), ctypes.byref(nn), ctypes.byref(st)), st)
-        if rc != 0:
-            _raise(rc)
-        last_stats = st.as_dict()
-        res = _trim(out, rows.value)
-    if return_device is not None and return_device != "same":
-        res = res.to(return_device)
+    n = -1 if num_nodes is None else int(num_nodes)   # (n < 0: found on the device)
+    t = -1 if num_remove is None else int(num_remove)
+    nn = ctypes.c_int64(0)
+    res, _ = _eliminate("rlap_approx_chol_from_edges", (n, t, float(remove_frac), 1 if symmetrize else 0), edge_index, edge_weights,
+                        o_v, o_n, perm, seed, mode, return_device, n=n if n >= 0 else None, symmetrize=bool(symmetrize),
+                        rows_only=True, outs=(ctypes.byref(nn),))
     return res, int(nn.value)
 
 
@@ -367,43 +353,12 @@ def approximate_cholesky_batched(
     `approximate_cholesky(graph g, ..., perm=perm[g], seed=seed + g)` shifted by node_ptr[g].
     Returns (sc_edge_info, row_ptr[G+1]).  `perm` concatenates per-graph permutations of LOCAL ids.
     """
-    assert edge_index.shape[0] == 2
-    assert o_v in ["random", "degree", "coarsen"]
-    assert o_n in ["asc", "desc", "random"]
-    global last_stats
-    dev = _device_for(edge_index)
-    lib, hobj = _handle_obj(dev)
-    _set_mode(lib, hobj.ptr, mode)
-    h = hobj.ptr
     np_ = torch.as_tensor(node_ptr, dtype=torch.int64).cpu().contiguous()
     nr_ = torch.as_tensor(num_remove, dtype=torch.int64).cpu().contiguous()
     G = np_.numel() - 1
     assert nr_.numel() == G
-    with torch.cuda.device(dev):
-        row, col, w, E = _prep_edges(edge_index, edge_weights, dev)
-        N = int(np_[-1])
-        d_perm = None
-        if o_v == "random":
-            # perm None: every graph's node_id vector is drawn on the device from the seed (keyed shuffle, C ABI)
-            if perm is not None:
-                d_perm = perm.to(device=dev, dtype=torch.int64).contiguous()
-                assert d_perm.numel() == N
-        shuffle_seed = _seed_from(seed) if (o_n == "random" or o_v != "degree" or mode == "frontier") else 0
-        out = torch.empty((max(E, 1), 3), dtype=torch.float64, device=dev)
-        row_ptr = torch.zeros(G + 1, dtype=torch.int64)
-        st = _lib.Stats()
-        rc = _run(hobj, dev, E, N, G, False, lambda: lib.rlap_approx_chol_batched(
-            h, row.data_ptr(), col.data_ptr(), w.data_ptr() if w is not None else None, E, G,
-            np_.data_ptr(), nr_.data_ptr(), O_V[o_v], O_N[o_n],
-            d_perm.data_ptr() if d_perm is not None else None, shuffle_seed,
-            out.data_ptr(), out.shape[0], row_ptr.data_ptr(), ctypes.byref(st)), st)
-        if rc != 0:
-            _raise(rc)
-        last_stats = st.as_dict()
-        res = _trim(out, int(row_ptr[-1]))
-    if return_device is not None and return_device != "same":
-        res = res.to(return_device)
-    return res, row_ptr
+    return _eliminate("rlap_approx_chol_batched", (G, np_.data_ptr(), nr_.data_ptr()), edge_index, edge_weights, o_v, o_n, perm,
+                      seed, mode, return_device, n=int(np_[-1]), G=G)
 
 
 def approximate_cholesky_views(
@@ -435,10 +390,6 @@ def approximate_cholesky_views(
     std::mt19937_64, preconditioner.cc:356), so two views with equal num_remove are identical -- as in the reference.
     mode="frontier" gives distinct samples.
     """
-    assert edge_index.shape[0] == 2
-    assert o_v in ["random", "degree", "coarsen"]
-    assert o_n in ["asc", "desc", "random"]
-    global last_stats
     n = int(num_nodes)
     np_ = torch.as_tensor([0, n] if node_ptr is None else node_ptr, dtype=torch.int64).cpu().contiguous()
     G = np_.numel() - 1
@@ -451,33 +402,8 @@ def approximate_cholesky_views(
     assert nr_.dim() == 2 and nr_.shape[1] == G and nr_.shape[0] >= 1, "num_remove: an int, K values, or (K, G)"
     K = int(nr_.shape[0])
     nr_ = nr_.contiguous()
-    dev = _device_for(edge_index)
-    lib, hobj = _handle_obj(dev)
-    h = hobj.ptr
-    _set_mode(lib, h, mode)
-    with torch.cuda.device(dev):
-        row, col, w, E = _prep_edges(edge_index, edge_weights, dev)
-        d_perm = None
-        if o_v == "random" and perm is not None:
-            d_perm = perm.to(device=dev, dtype=torch.int64).contiguous()
-            assert d_perm.numel() == K * n, "perm must hold K * num_nodes entries"
-        shuffle_seed = _seed_from(seed) if (o_n == "random" or o_v != "degree" or mode == "frontier") else 0
-        out = torch.empty((max(K * E, 1), 3), dtype=torch.float64, device=dev)
-        ptr = torch.zeros(K * G + 1, dtype=torch.int64)
-        st = _lib.Stats()
-        # the arena of a batched call on the K-fold union (include/rlap_hip.h)
-        rc = _run(hobj, dev, K * E, K * n, K * G, False, lambda: lib.rlap_approx_chol_views(
-            h, row.data_ptr(), col.data_ptr(), w.data_ptr() if w is not None else None, E, G,
-            np_.data_ptr(), K, nr_.data_ptr(), O_V[o_v], O_N[o_n],
-            d_perm.data_ptr() if d_perm is not None else None, shuffle_seed,
-            out.data_ptr(), out.shape[0], ptr.data_ptr(), ctypes.byref(st)), st)
-        if rc != 0:
-            _raise(rc)
-        last_stats = st.as_dict()
-        res = _trim(out, int(ptr[-1]))
-    if return_device is not None and return_device != "same":
-        res = res.to(return_device)
-    return res, ptr
+    return _eliminate("rlap_approx_chol_views", (G, np_.data_ptr(), K, nr_.data_ptr()), edge_index, edge_weights, o_v, o_n, perm,
+                      seed, mode, return_device, n=n, G=G, K=K)
 
 
 def _depths_list(num_remove) -> list:
@@ -597,76 +523,22 @@ def approximate_cholesky_depths(
     `approximate_cholesky_views(..., num_remove=t[d], node_ptr=node_ptr)`.  `perm` (o_v="random") then holds K*N entries laid
     out as for the views call; every depth uses it.
     """
-    assert edge_index.shape[0] == 2
-    assert o_v in ["random", "degree", "coarsen"]
-    assert o_n in ["asc", "desc", "random"]
     if not _one_graph_depths(num_remove, node_ptr, views):
         return _depths_views(edge_index, edge_weights, num_nodes, num_remove, o_v, o_n, node_ptr, views, perm, seed, return_device, mode)
-    depths = _depths_list(num_remove)
-    K = len(depths)
-    global last_stats
-    dev = _device_for(edge_index)
-    lib, hobj = _handle_obj(dev)
-    h = hobj.ptr
-    _set_mode(lib, h, mode)
-    nr_ = torch.tensor(depths, dtype=torch.int64)
-    with torch.cuda.device(dev):
-        row, col, w, E = _prep_edges(edge_index, edge_weights, dev)
-        n = int(num_nodes)
-        d_perm = None
-        if o_v == "random" and perm is not None:
-            d_perm = perm.to(device=dev, dtype=torch.int64).contiguous()
-            assert d_perm.numel() == n
-        shuffle_seed = _seed_from(seed) if (o_n == "random" or o_v != "degree" or mode == "frontier") else 0
-        out = torch.empty((max(K * E, 1), 3), dtype=torch.float64, device=dev)   # (an elimination never adds entries)
-        ptr = torch.zeros(K + 1, dtype=torch.int64)
-        st = _lib.Stats()
-        rc = _run(hobj, dev, E, n, 1, False, lambda: lib.rlap_approx_chol_depths(
-            h, row.data_ptr(), col.data_ptr(), w.data_ptr() if w is not None else None, E, n, K, nr_.data_ptr(),
-            O_V[o_v], O_N[o_n], d_perm.data_ptr() if d_perm is not None else None, shuffle_seed,
-            out.data_ptr(), out.shape[0], ptr.data_ptr(), ctypes.byref(st)), st)
-        if rc != 0:
-            _raise(rc)
-        last_stats = st.as_dict()
-        res = _trim(out, int(ptr[-1]))
-    if return_device is not None and return_device != "same":
-        res = res.to(return_device)
-    return res, ptr
+    n = int(num_nodes)
+    nr_ = torch.tensor(_depths_list(num_remove), dtype=torch.int64)
+    D = nr_.numel()
+    return _eliminate("rlap_approx_chol_depths", (n, D, nr_.data_ptr()), edge_index, edge_weights, o_v, o_n, perm, seed, mode,
+                      return_device, n=n, D=D)
 
 
 def _depths_views(edge_index, edge_weights, num_nodes, num_remove, o_v, o_n, node_ptr, views, perm, seed, return_device, mode):
     """approximate_cholesky_depths with `node_ptr` and / or `views`: one rlap_approx_chol_views_depths call."""
-    np_, nr_, K, G = _depths_table(num_remove, num_nodes, node_ptr, views)
-    D = int(nr_.shape[0])
     n = int(num_nodes)
-    global last_stats
-    dev = _device_for(edge_index)
-    lib, hobj = _handle_obj(dev)
-    h = hobj.ptr
-    _set_mode(lib, h, mode)
-    with torch.cuda.device(dev):
-        row, col, w, E = _prep_edges(edge_index, edge_weights, dev)
-        d_perm = None
-        if o_v == "random" and perm is not None:
-            d_perm = perm.to(device=dev, dtype=torch.int64).contiguous()
-            assert d_perm.numel() == K * n, "perm must hold K * num_nodes entries"
-        shuffle_seed = _seed_from(seed) if (o_n == "random" or o_v != "degree" or mode == "frontier") else 0
-        out = torch.empty((max(D * K * E, 1), 3), dtype=torch.float64, device=dev)   # (an elimination never adds entries)
-        ptr = torch.zeros(D * K * G + 1, dtype=torch.int64)
-        st = _lib.Stats()
-        # the arena of a batched call on the K-fold union (include/rlap_hip.h)
-        rc = _run(hobj, dev, K * E, K * n, K * G, False, lambda: lib.rlap_approx_chol_views_depths(
-            h, row.data_ptr(), col.data_ptr(), w.data_ptr() if w is not None else None, E, G,
-            np_.data_ptr(), K, D, nr_.data_ptr(), O_V[o_v], O_N[o_n],
-            d_perm.data_ptr() if d_perm is not None else None, shuffle_seed,
-            out.data_ptr(), out.shape[0], ptr.data_ptr(), ctypes.byref(st)), st)
-        if rc != 0:
-            _raise(rc)
-        last_stats = st.as_dict()
-        res = _trim(out, int(ptr[-1]))
-    if return_device is not None and return_device != "same":
-        res = res.to(return_device)
-    return res, ptr
+    np_, nr_, K, G = _depths_table(num_remove, n, node_ptr, views)
+    D = int(nr_.shape[0])
+    return _eliminate("rlap_approx_chol_views_depths", (G, np_.data_ptr(), K, D, nr_.data_ptr()), edge_index, edge_weights, o_v, o_n,
+                      perm, seed, mode, return_device, n=n, G=G, K=K, D=D)
 
 
 SNAPSHOT_MAX_ITER = 1024   # bound of max_iter (include/rlap_hip.h::rlap_snapshot_stats)
