@@ -49,7 +49,8 @@ enum {
     RLAP_E_TOO_LARGE = 9,     /* nnz + growth pool exceeds int32 slot ids */
     RLAP_E_INTERNAL = 10,
     RLAP_E_WORKSPACE = 11,    /* caller-provided workspace / uniform table too small: rlap_workspace_needed() says how much */
-    RLAP_E_NOT_GROUPED = 12   /* rlap_snapshot_stats: a column id starts two separate blocks of rows in one segment */
+    RLAP_E_NOT_GROUPED = 12,  /* rlap_snapshot_stats: a column id starts two separate blocks of rows in one segment */
+    RLAP_E_OUT_CAPACITY = 13  /* rlap_snapshot_ppr: the kept entries exceed out_cap_rows; nothing written, rows_needed reported */
 };
 
 typedef struct {
@@ -245,6 +246,42 @@ typedef struct {
 int rlap_snapshot_stats(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
                         int64_t G, int64_t num_nodes, int weighted, double tol, int32_t max_iter, int64_t* d_nodes,
                         double* d_lambda_max, int32_t* d_iters, int32_t* d_converged, rlap_snapshot_info* h_info);
+
+/* PPR diffusion of snapshots: for every segment s (as for rlap_snapshot_stats: d_sc, m, d_ptr, S, d_node_ptr, G, num_nodes), with
+ * V_s its distinct ids, A its symmetric adjacency on V_s (duplicate rows summed; the rows' weights, or unit entries), A + I with a self
+ * loop, d = A 1:
+ *     S = alpha (I - (1 - alpha) D^-1/2 A D^-1/2)^-1,  entries S_ij >= eps kept,  then (normalize_out) D_S^-1/2 S D_S^-1/2
+ * with D_S the row sums of the kept entries -- PyGCL's compute_ppr (transition_matrix('sym'), diffusion_matrix_exact('ppr'),
+ * sparsify_dense('threshold'), transition_matrix('sym')) without a dense matrix.
+ *   alpha, eps, tol : 0 < alpha < 1, eps > 0, tol > 0.  S is found by K fixed Chebyshev steps, K = min{K : T_K(1/(1-alpha)) >= 1/tol}
+ *                     (include: rlap_amd/csrc/rlap_cheb.h, at most 4096): every entry lies within tol of exact before normalisation
+ *   flags           : RLAP_PPR_WEIGHTED (the rows' weights, else unit entries), RLAP_PPR_SELF_LOOP (A + I), RLAP_PPR_NORMALIZE
+ *                     (the closing D_S^-1/2 . D_S^-1/2), RLAP_PPR_ZERO_ROWS (rows of weight 0 are allowed: an id whose only row is
+ *                     (i, i, 0) is a node without edges)
+ *   d_out           : (out_cap_rows, 3) f64 rows [i, j, value] in the input's id space, segment-major, then ascending i, then j
+ *   d_out_ptr       : [S+1] row offsets of the segments in d_out
+ *   h_info          : (nullable) what the call did; rows_needed = the kept entries
+ * Exactly symmetric (the pair {i, j} takes its value from the column of the smaller id); the same input gives the same bits, and a
+ * segment's rows do not depend on the other segments of the call.  More kept entries than out_cap_rows: RLAP_E_OUT_CAPACITY, nothing
+ * written, h_info->rows_needed says how many (call again with that capacity).  Layout errors as for rlap_snapshot_stats; a weight
+ * <= 0 (< 0 with RLAP_PPR_ZERO_ROWS) or not finite with RLAP_PPR_WEIGHTED, or alpha / eps / tol out of range: RLAP_E_BAD_ARG.
+ * Scratch from the arena (grows with out_cap_rows; RLAP_E_WORKSPACE when a caller-provided one is too small). */
+enum { RLAP_PPR_WEIGHTED = 1, RLAP_PPR_SELF_LOOP = 2, RLAP_PPR_NORMALIZE = 4, RLAP_PPR_ZERO_ROWS = 8 };
+typedef struct {
+    int64_t steps;            /* K, the Chebyshev steps                                              */
+    int64_t small_tiles;      /* tiles (segment, 64 sources) that ran their K steps in one workgroup */
+    int64_t large_tiles;      /* tiles that stepped with device-wide launches                         */
+    int64_t groups;           /* tile groups (live tile bytes within the budget of DESIGN 4.8)        */
+    int64_t launches;         /* kernel launches of the sweeps                                        */
+    int64_t rows_needed;      /* kept entries: the rows of d_out (written, or needed)                 */
+    int64_t arena_bytes;      /* scratch bytes of the call                                            */
+    int32_t host_syncs;       /* host synchronisations of the call                                    */
+    int32_t pad;
+} rlap_ppr_info;
+
+int rlap_snapshot_ppr(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
+                      int64_t G, int64_t num_nodes, double alpha, double eps, double tol, int flags, double* d_out,
+                      int64_t out_cap_rows, int64_t* d_out_ptr, rlap_ppr_info* h_info);
 
 /* The op with the step BEFORE the path fused in (scripts/node_shared.py:326-327,
  * scripts/augmentor_benchmarks.py:77-78):

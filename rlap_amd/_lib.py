@@ -19,11 +19,14 @@ EXPORTS = [
     "rlap_approx_chol_from_edges", "rlap_debug_set_limits", "rlap_pack_rows", "rlap_unpack_rows",
     "rlap_workspace_bytes", "rlap_workspace_query", "rlap_set_workspace", "rlap_workspace_needed", "rlap_debug_set_poison", "rlap_debug_set_jitter",
     "rlap_set_rng_mode", "rlap_approx_chol_views", "rlap_approx_chol_depths", "rlap_debug_set_flow_limits",
-    "rlap_approx_chol_views_depths", "rlap_snapshot_stats",
+    "rlap_approx_chol_views_depths", "rlap_snapshot_stats", "rlap_snapshot_ppr",
 ]
 
 E_WORKSPACE = 11   # RLAP_E_WORKSPACE
 E_NOT_GROUPED = 12   # RLAP_E_NOT_GROUPED
+E_OUT_CAPACITY = 13   # RLAP_E_OUT_CAPACITY
+# rlap_snapshot_ppr flags
+PPR_WEIGHTED, PPR_SELF_LOOP, PPR_NORMALIZE, PPR_ZERO_ROWS = 1, 2, 4, 8
 
 # rlap_stats.elim_kernel
 KERNEL_NONE, KERNEL_ROUND, KERNEL_FLOW = 0, 1, 2
@@ -58,6 +61,18 @@ class SnapshotInfo(ctypes.Structure):
 
     def as_dict(self):
         return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class PprInfo(ctypes.Structure):
+    """rlap_ppr_info (include/rlap_hip.h)."""
+    _fields_ = [
+        ("steps", ctypes.c_int64), ("small_tiles", ctypes.c_int64), ("large_tiles", ctypes.c_int64), ("groups", ctypes.c_int64),
+        ("launches", ctypes.c_int64), ("rows_needed", ctypes.c_int64), ("arena_bytes", ctypes.c_int64), ("host_syncs", ctypes.c_int32),
+        ("pad", ctypes.c_int32),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_ if f != "pad"}
 
 
 def load():
@@ -99,6 +114,9 @@ def load():
     lib.rlap_snapshot_stats.restype = ci
     lib.rlap_snapshot_stats.argtypes = [vp, vp, i64, vp, i64, vp, i64, i64, ci, ctypes.c_double, ctypes.c_int32, vp, vp, vp, vp,
                                         ctypes.POINTER(SnapshotInfo)]
+    lib.rlap_snapshot_ppr.restype = ci
+    lib.rlap_snapshot_ppr.argtypes = [vp, vp, i64, vp, i64, vp, i64, i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, ci, vp, i64,
+                                      vp, ctypes.POINTER(PprInfo)]
     lib.rlap_approx_chol_views.restype = ci
     lib.rlap_approx_chol_views.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, vp, ci, ci, vp, u64, vp, i64, vp,
                                            ctypes.POINTER(Stats)]

@@ -6,7 +6,8 @@ Mirrors of the reference's L2 adapters that keep everything on the GPU:
   * `rLapViews` -- K rLap views of one graph from one library call, with PyGCL-style
                   siblings for the `(aug1, aug2)` pair of scripts/node_shared.py:488-498
   * `rLapDepths` -- the same graph at K removed fractions from one elimination
-                  (the sweeps of scripts/rlap_vc_spectral.py, scripts/rlap_ppr_edge_plots.py)
+                  (the sweeps of scripts/rlap_vc_spectral.py, scripts/rlap_ppr_edge_plots.py); `.diffuse`
+                  gives their PPR diffusions from one ops.snapshot_ppr call
 PyGCL / DGL are optional: with them installed the classes return their graph types,
 without them a small named tuple with the same fields.
 """
@@ -165,6 +166,24 @@ class rLapDepths:
             return t.reshape(D, R).t().contiguous()
         return {"max_sv": grid(st["lambda_max"]), "node_count": grid(st["nodes"]), "edge_count": grid(st["rows"]),
                 "converged": grid(st["converged"])}
+
+    def diffuse(self, g, alpha: float = 0.2, eps: float = 1e-4, tol: float = 1e-10):
+        """rLapPPRDiffusion's graph (Schur-complement weights -> PPR diffusion, normalised) for every run and depth of ONE call: one
+        depths call and one ops.snapshot_ppr call -- the fraction sweep of scripts/rlap_ppr_edge_plots.py from one elimination.
+        Returns the layout of `augment`: K graphs, or R lists of K with views=R; each is Graph(x, edge_index, edge_weights) with
+        ids in the input's space, as rLapPPRDiffusion returns."""
+        x, sc, ptr, num_nodes = self._snapshots(g)
+        out, pptr = ops.snapshot_ppr(sc, ptr, num_nodes, alpha=alpha, eps=eps, tol=tol)
+        pp = pptr.cpu()
+
+        def graph(i):
+            part = out[int(pp[i]):int(pp[i + 1])]
+            return Graph(x, part[:, :2].long().t().contiguous(), part[:, 2].contiguous())
+        K = len(self.fracs)
+        if self.views is None:
+            return [graph(k) for k in range(K)]
+        R = int(self.views)
+        return [[graph(k * R + r) for k in range(K)] for r in range(R)]
 
     def augment(self, g):
         x, sc, ptr, num_nodes = self._snapshots(g)

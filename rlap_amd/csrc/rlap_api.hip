@@ -17,6 +17,8 @@
 #include "../../include/rlap_hip.h"
 #include "rlap_core.h"
 #include "rlap_kernels.h"
+#include "rlap_cheb.h"
+#include "rlap_ppr.h"
 #include "rlap_stats.h"
 
 using namespace rlap;
@@ -1115,6 +1117,7 @@ const char* rlap_status_string(int status) {
         case RLAP_E_TOO_LARGE: return "problem exceeds int32 slot ids";
         case RLAP_E_WORKSPACE: return "caller-provided workspace too small (see rlap_workspace_needed)";
         case RLAP_E_NOT_GROUPED: return "a column's rows are not contiguous within a segment";
+        case RLAP_E_OUT_CAPACITY: return "output capacity too small (rlap_ppr_info.rows_needed says how many rows)";
         default: return "internal error";
     }
 }
@@ -1265,6 +1268,43 @@ int rlap_snapshot_stats(rlap_handle h, const double* d_sc, int64_t m, const int6
         h_info->small_segments = rep.small_segments; h_info->large_segments = rep.large_segments;
         h_info->lanczos_steps = rep.lanczos_steps; h_info->large_steps = rep.large_steps; h_info->large_launches = rep.large_launches;
         h_info->host_syncs = rep.host_syncs; h_info->not_converged = rep.not_converged;
+    }
+    return rc;
+}
+
+int rlap_snapshot_ppr(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
+                      int64_t G, int64_t num_nodes, double alpha, double eps, double tol, int flags, double* d_out,
+                      int64_t out_cap_rows, int64_t* d_out_ptr, rlap_ppr_info* h_info) {
+    if (h_info) *h_info = rlap_ppr_info{};
+    if (!h || !d_ptr || S < 1 || m < 0 || num_nodes < 0 || (m > 0 && !d_sc) || !d_out_ptr || out_cap_rows < 0 || (out_cap_rows > 0 && !d_out))
+        return RLAP_E_BAD_ARG;
+    if (flags & ~(RLAP_PPR_WEIGHTED | RLAP_PPR_SELF_LOOP | RLAP_PPR_NORMALIZE | RLAP_PPR_ZERO_ROWS)) return RLAP_E_BAD_ARG;
+    if (!(eps > 0.0) || !std::isfinite(eps)) return RLAP_E_BAD_ARG;
+    const int K = cheb::steps(alpha, tol, cheb::MAX_STEPS);
+    if (K < 0) return RLAP_E_BAD_ARG;
+    if (d_node_ptr ? (G < 1 || S % G != 0) : false) return RLAP_E_BAD_ARG;
+    if (!d_node_ptr) G = 1;
+    if (m >= INT32_MAX || S >= (int64_t)1 << 30 || num_nodes >= INT32_MAX) return RLAP_E_TOO_LARGE;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device);
+    const size_t need = snapshot_ppr_bytes(m, S, G, num_nodes, out_cap_rows, K);
+    h->ws_needed = need;
+    void* base = nullptr;
+    size_t have = 0;
+    if (h->ext_ws) {
+        if (need > h->ext_ws_bytes) return RLAP_E_WORKSPACE;
+        base = h->ext_ws; have = h->ext_ws_bytes;
+    } else {
+        ENSURE(h->own_ws, need);
+        base = h->own_ws.p; have = h->own_ws.cap;
+    }
+    SnapshotPprArgs a{d_sc, m, d_ptr, S, d_node_ptr, G, num_nodes, alpha, eps, K, flags, d_out, out_cap_rows, d_out_ptr};
+    SnapshotPprReport rep;
+    const int rc = snapshot_ppr_run(h->stream, base, have, a, &rep);
+    if (h_info) {
+        h_info->steps = K; h_info->small_tiles = rep.small_tiles; h_info->large_tiles = rep.large_tiles; h_info->groups = rep.groups;
+        h_info->launches = rep.launches; h_info->rows_needed = rep.kept; h_info->arena_bytes = (int64_t)need;
+        h_info->host_syncs = rep.host_syncs;
     }
     return rc;
 }

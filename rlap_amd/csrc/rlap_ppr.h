@@ -1,0 +1,37 @@
+// rlap_ppr.h -- PPR diffusion of snapshots (rlap_snapshot_ppr): the interface between rlap_ppr.hip, which holds the
+// kernels and their orchestration, and the C ABI in rlap_api.hip, which owns the handle, its lock and its arena.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+namespace rlap {
+
+struct SnapshotPprArgs {
+    const double* sc; int64_t m;              // (m, 3) rows [row, col, w]
+    const int64_t* ptr; int64_t S;            // [S+1] segment offsets
+    const int64_t* node_ptr; int64_t G;       // [G+1] or nullptr (then G = 1 and every id range is [0, N))
+    int64_t N;                                // num_nodes
+    double alpha, eps; int32_t K;             // K: Chebyshev steps (rlap_cheb.h)
+    int flags;                                // RLAP_PPR_* (include/rlap_hip.h)
+    double* out; int64_t out_cap;             // (out_cap, 3) rows [i, j, value]
+    int64_t* out_ptr;                         // [S+1]
+};
+
+struct SnapshotPprReport {
+    int64_t small_tiles, large_tiles, groups, launches;
+    int64_t kept;                             // rows of the output (written, or needed when they exceed out_cap)
+    int32_t host_syncs;
+};
+
+constexpr int PPR_TILE = 64;                  // sources per tile: one lane each
+constexpr int PPR_SMALL_MAX = 4096;           // segments of up to this many nodes run each tile's K steps in one workgroup
+constexpr size_t PPR_TILE_BUDGET = (size_t)1 << 30;   // bytes of live tiles (two n_s x 64 float64 copies each) per group
+
+// arena bytes of a call (an upper bound from the host-known sizes)
+size_t snapshot_ppr_bytes(int64_t m, int64_t S, int64_t G, int64_t N, int64_t out_cap, int32_t K);
+// the call on `stream`, with `ws` (snapshot_ppr_bytes) as its scratch; returns an RLAP_* status (RLAP_E_OUT_CAPACITY with
+// rep->kept the rows it needs)
+int snapshot_ppr_run(hipStream_t stream, void* ws, size_t ws_bytes, const SnapshotPprArgs& a, SnapshotPprReport* rep);
+
+}  // namespace rlap

@@ -1,0 +1,494 @@
+// rlap_ppr.hip -- PPR diffusion of snapshots (rlap_snapshot_ppr): for every segment s of a Schur-complement result,
+//     S = alpha (I - (1 - alpha) D^-1/2 A D^-1/2)^-1 on the segment's ids, entries >= eps kept, then (normalize_out) D_S^-1/2 S D_S^-1/2
+// as sparse rows [i, j, value], row-major per segment -- without an n_s x n_s buffer anywhere.
+//
+// The column pass of rlap_stats.hip numbers the segment's blocks (one per column id) and maps every row to the block of its row id.
+// Columns of S are found 64 at a time: a tile is (segment, 64 source blocks), an n_s x 64 float64 matrix with one row per node and
+// one lane per source, run through the K fixed Chebyshev steps of rlap_cheb.h (two live copies for the three-term recurrence; the
+// new iterate overwrites x_{k-1} in place).  One wave per node computes sum_r a_r X[rb[r], lane] over the rows of its block in row
+// order: a wave-uniform (a_r, rb[r]) and one 512-byte row gather per row.  Tiles of segments up to PPR_SMALL_MAX nodes run their K
+// steps in one workgroup each; larger segments step together, one device-wide launch per step over a group of tiles.  Groups keep
+// the live tile bytes within PPR_TILE_BUDGET (or one tile, when a single tile is larger).
+//
+// After step K every tile keeps its entries with rank(row id) >= rank(source id) and value >= eps: the pair {i, j} takes its value
+// from the column of the smaller id, and both directions are staged with it (key (position of i, rank of j), value).  One radix sort
+// puts them in (segment, i, j) order; row sums run over each sorted row in a fixed order, and the output pass normalises with
+// v * (D_i^-1/2 D_j^-1/2) -- exactly symmetric.  No atomics touch a floating-point value, so a call gives the same bits every time,
+// and a segment's arithmetic does not depend on the other segments of the call.
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+#include <rocprim/rocprim.hpp>
+
+#include "../../include/rlap_hip.h"
+#include "rlap_cheb.h"
+#include "rlap_ppr.h"
+#include "rlap_stats.h"
+
+namespace rlap {
+namespace {
+
+constexpr int PP_SMALL_THREADS = 512;   // small regime: 8 waves per tile
+constexpr int PP_THREADS = 256;         // every other kernel
+constexpr int64_t PP_GROUP_TILES = 65535;   // tiles per group (k_pp_init's grid.y)
+enum { PERR_WEIGHT = COL_ERR_WORDS, PERR_WORDS = 8 };
+enum { T_SEG = 0, T_C0 = 1, T_XOFF = 2, T_ROFF = 3, T_FIELDS = 4 };   // tile table: int64 fields per tile
+
+#define PP_HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { std::fprintf(stderr, "[rlap_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(_e), __FILE__, __LINE__); return RLAP_E_HIP; } } while (0)
+
+inline unsigned pp_blocks(int64_t n, int bs) { return (unsigned)std::max<int64_t>(1, (n + bs - 1) / bs); }
+
+// last s with sb[s] <= b (empty segments share their sb value with the next one and are skipped)
+__device__ inline int64_t seg_of_block(const int64_t* __restrict__ sb, int64_t S, int64_t b) {
+    int64_t lo = 0, hi = S;
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (sb[mid] <= b) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ void k_pp_weights(const double* __restrict__ sc, int64_t m, int zero_ok, int32_t* __restrict__ err) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= m) return;
+    const double w = sc[3 * r + 2];
+    const bool ok = (zero_ok ? w >= 0.0 : w > 0.0) && w < INFINITY;
+    if (!ok) atomicOr(&err[PERR_WEIGHT], 1);
+}
+
+// per block: D^-1/2 (0 for a zero degree, as the dense path) and the self loop's diagonal term (1 - alpha) / d
+__global__ void k_pp_degrees(const double* __restrict__ sc, const int32_t* __restrict__ bstart, int64_t B, int weighted, int self_loop,
+                             double alpha, double* __restrict__ dinv, double* __restrict__ cdiag) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double d = 0.0;
+    for (int32_t r = bstart[b]; r < bstart[b + 1]; ++r) d += weighted ? sc[3 * (int64_t)r + 2] : 1.0;
+    if (self_loop) d += 1.0;
+    const double di = d > 0.0 ? 1.0 / sqrt(d) : 0.0;
+    dinv[b] = di;
+    cdiag[b] = self_loop ? (1.0 - alpha) * (di * di) : 0.0;
+}
+
+// a_r = (1 - alpha) w_r D_b^-1/2 D_rb^-1/2, once per row (blk: the inclusive scan of the block starts, block of row r = blk[r] - 1)
+__global__ void k_pp_norm(const double* __restrict__ sc, int64_t m, int weighted, double alpha, const int32_t* __restrict__ blk,
+                          const int32_t* __restrict__ rb, const double* __restrict__ dinv, double* __restrict__ a) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= m) return;
+    const double w = weighted ? sc[3 * r + 2] : 1.0;
+    a[r] = ((1.0 - alpha) * w) * (dinv[blk[r] - 1] * dinv[rb[r]]);
+}
+
+// block sort keys: (segment << 32) | id -- sorted, they give every block its rank among its segment's ids
+__global__ void k_pp_bkeys(const double* __restrict__ sc, const int32_t* __restrict__ bstart, const int64_t* __restrict__ sb, int64_t S,
+                           int64_t B, uint64_t* __restrict__ key, int32_t* __restrict__ val) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int64_t s = seg_of_block(sb, S, b);
+    key[b] = ((uint64_t)s << 32) | (uint64_t)(int64_t)sc[3 * (int64_t)bstart[b] + 1];
+    val[b] = (int32_t)b;
+}
+
+__global__ void k_pp_ranks(const uint64_t* __restrict__ key, const int32_t* __restrict__ pos_blk, const int64_t* __restrict__ sb, int64_t B,
+                           int32_t* __restrict__ rank) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= B) return;
+    rank[pos_blk[p]] = (int32_t)(p - sb[key[p] >> 32]);
+}
+
+struct Tiles {
+    const int64_t* tab;       // [tiles][T_FIELDS]
+    const double* om;         // [K] Chebyshev weights
+    const double* sc; const int32_t* bstart; const int32_t* rb; const int64_t* sb; const double* a; const double* cdiag;
+    const int32_t* rank;
+    double* x;                // the tile area
+    double alpha, eps;
+    int32_t K;
+};
+
+// one step of one node row i of a tile (segment blocks from b0, sources from c0): x_{k+1} = om (B x_k + f - x_{k-1}) + x_{k-1},
+// written over x_{k-1}.  i is wave-uniform.
+__device__ inline void tile_row_step(const Tiles& T, int64_t b0, int64_t c0, int64_t i, double om, const double* __restrict__ cur,
+                                     double* __restrict__ prv, int lane) {
+    const int32_t r0 = T.bstart[b0 + i], r1 = T.bstart[b0 + i + 1];
+    double acc = 0.0;
+    int32_t r = r0;
+    for (; r + 4 <= r1; r += 4) {   // (four gathers in flight, summed in row order)
+        const double x0 = cur[(int64_t)(T.rb[r] - b0) * PPR_TILE + lane];
+        const double x1 = cur[(int64_t)(T.rb[r + 1] - b0) * PPR_TILE + lane];
+        const double x2 = cur[(int64_t)(T.rb[r + 2] - b0) * PPR_TILE + lane];
+        const double x3 = cur[(int64_t)(T.rb[r + 3] - b0) * PPR_TILE + lane];
+        acc += T.a[r] * x0;
+        acc += T.a[r + 1] * x1;
+        acc += T.a[r + 2] * x2;
+        acc += T.a[r + 3] * x3;
+    }
+    for (; r < r1; ++r) acc += T.a[r] * cur[(int64_t)(T.rb[r] - b0) * PPR_TILE + lane];
+    const int64_t e = i * PPR_TILE + lane;
+    acc += T.cdiag[b0 + i] * cur[e];
+    if (c0 + lane == i) acc += T.alpha;
+    prv[e] = cheb::step(om, acc, prv[e]);
+}
+
+// x_1 = f (alpha at (source row, source lane); zero when K = 0) and x_0 = 0 for every tile of a group
+__global__ void k_pp_init(Tiles T, const int64_t* __restrict__ gt, int64_t nt) {
+    const int64_t t = gt[0] + blockIdx.y;
+    if (blockIdx.y >= nt) return;
+    const int64_t* d = T.tab + t * T_FIELDS;
+    const int64_t s = d[T_SEG], c0 = d[T_C0];
+    const int64_t n = T.sb[s + 1] - T.sb[s];
+    double* x0 = T.x + d[T_XOFF];
+    double* x1 = x0 + n * PPR_TILE;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n * PPR_TILE; e += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = e / PPR_TILE, l = e % PPR_TILE;
+        x0[e] = (T.K > 0 && c0 + l == i) ? T.alpha : 0.0;
+        x1[e] = 0.0;
+    }
+}
+
+// small regime: one workgroup runs all steps of one tile
+__global__ __launch_bounds__(PP_SMALL_THREADS) void k_pp_small(Tiles T, const int64_t* __restrict__ gt) {
+    const int64_t t = gt[0] + blockIdx.x;
+    const int64_t* d = T.tab + t * T_FIELDS;
+    const int64_t s = d[T_SEG], c0 = d[T_C0];
+    const int64_t b0 = T.sb[s], n = T.sb[s + 1] - b0;
+    double* xa = T.x + d[T_XOFF];
+    double* xb = xa + n * PPR_TILE;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (int32_t k = 1; k < T.K; ++k) {
+        const double* cur = (k & 1) ? xa : xb;
+        double* prv = (k & 1) ? xb : xa;
+        const double om = T.om[k];
+        for (int64_t i = wave; i < n; i += PP_SMALL_THREADS / 64) tile_row_step(T, b0, c0, i, om, cur, prv, lane);
+        __syncthreads();
+    }
+}
+
+// large regime, step k over the rows of a group: wave q of the launch is row q of the group (tiles in order, T_ROFF ascending)
+__global__ __launch_bounds__(PP_THREADS) void k_pp_large(Tiles T, const int64_t* __restrict__ gt, int64_t nt, int64_t rows, int32_t k) {
+    const int64_t q = (int64_t)blockIdx.x * (PP_THREADS / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (q >= rows) return;
+    int64_t lo = 0, hi = nt;   // tile of row q: the last u with roff[u] <= q
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (T.tab[(gt[0] + mid) * T_FIELDS + T_ROFF] <= q) lo = mid; else hi = mid;
+    }
+    const int64_t* d = T.tab + (gt[0] + lo) * T_FIELDS;
+    const int64_t s = d[T_SEG], c0 = d[T_C0];
+    const int64_t b0 = T.sb[s], n = T.sb[s + 1] - b0;
+    double* xa = T.x + d[T_XOFF];
+    double* xb = xa + n * PPR_TILE;
+    const int lane = threadIdx.x & 63;
+    const double* cur = (k & 1) ? xa : xb;
+    double* prv = (k & 1) ? xb : xa;
+    tile_row_step(T, b0, c0, q - d[T_ROFF], T.om[k], cur, prv, lane);
+}
+
+// after step K: the kept entries of row q of a group, counted (pass 0) or staged (pass 1) at top + (scan[q] - cnt[q]) + lane prefix
+__global__ __launch_bounds__(PP_THREADS) void k_pp_keep(Tiles T, const int64_t* __restrict__ gt, int64_t nt, int64_t rows, int pass,
+                                                        int32_t* __restrict__ cnt, const int64_t* __restrict__ scan,
+                                                        const int64_t* __restrict__ top, uint64_t* __restrict__ key,
+                                                        double* __restrict__ val, int64_t cap) {
+    const int64_t q = (int64_t)blockIdx.x * (PP_THREADS / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (q >= rows) return;
+    int64_t lo = 0, hi = nt;
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (T.tab[(gt[0] + mid) * T_FIELDS + T_ROFF] <= q) lo = mid; else hi = mid;
+    }
+    const int64_t* d = T.tab + (gt[0] + lo) * T_FIELDS;
+    const int64_t s = d[T_SEG], c0 = d[T_C0];
+    const int64_t b0 = T.sb[s], n = T.sb[s + 1] - b0;
+    const int64_t i = q - d[T_ROFF];
+    const int lane = threadIdx.x & 63;
+    const double* xk = T.x + d[T_XOFF] + ((T.K & 1) ? 0 : n * PPR_TILE);   // x_K (K = 0: the zero copy)
+    const int64_t src = c0 + lane;
+    const int32_t ri = T.rank[b0 + i];
+    const int32_t rj = src < n ? T.rank[b0 + src] : 0;
+    const double v = src < n ? xk[i * PPR_TILE + lane] : 0.0;
+    const bool keep = src < n && ri >= rj && v >= T.eps;
+    const bool mirror = keep && ri != rj;
+    const unsigned long long mk = __ballot(keep), mm = __ballot(mirror);
+    if (pass == 0) {
+        if (lane == 0) cnt[q] = __popcll(mk) + __popcll(mm);
+        return;
+    }
+    if (!keep) return;
+    const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
+    int64_t o = top[0] + (scan[q] - cnt[q]) + __popcll(mk & below) + __popcll(mm & below);
+    const uint64_t pi = (uint64_t)(b0 + ri), pj = (uint64_t)(b0 + rj);
+    if (o < cap) { key[o] = (pi << 32) | (uint64_t)rj; val[o] = v; }
+    if (mirror && o + 1 < cap) { key[o + 1] = (pj << 32) | (uint64_t)ri; val[o + 1] = v; }
+}
+
+__global__ void k_pp_top(int64_t* __restrict__ top, const int64_t* __restrict__ scan, int64_t rows) {
+    if (threadIdx.x == 0 && blockIdx.x == 0 && rows > 0) top[0] += scan[rows - 1];
+}
+
+// rowptr[p] = first sorted entry of position p (rows of positions without entries are empty)
+__global__ void k_pp_rowptr(const uint64_t* __restrict__ key, int64_t P, int64_t B, int64_t* __restrict__ rowptr) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= P) return;
+    const int64_t p = (int64_t)(key[e] >> 32);
+    const int64_t pp = e == 0 ? -1 : (int64_t)(key[e - 1] >> 32);
+    for (int64_t u = pp + 1; u <= p; ++u) rowptr[u] = e;
+    if (e == P - 1) for (int64_t u = p + 1; u <= B; ++u) rowptr[u] = P;
+}
+
+// D_S^-1/2 per position: one wave per row, lane strides then an xor butterfly (a fixed order)
+__global__ __launch_bounds__(PP_THREADS) void k_pp_rowsum(const double* __restrict__ val, const int64_t* __restrict__ rowptr, int64_t B,
+                                                          double* __restrict__ dsinv) {
+    const int64_t p = (int64_t)blockIdx.x * (PP_THREADS / 64) + (threadIdx.x >> 6);
+    if (p >= B) return;
+    const int lane = threadIdx.x & 63;
+    double acc = 0.0;
+    for (int64_t e = rowptr[p] + lane; e < rowptr[p + 1]; e += 64) acc += val[e];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if (lane == 0) dsinv[p] = acc > 0.0 ? 1.0 / sqrt(acc) : 0.0;
+}
+
+__global__ void k_pp_out(const uint64_t* __restrict__ key, const double* __restrict__ val, int64_t P, const int64_t* __restrict__ sb,
+                         int64_t S, const int32_t* __restrict__ pos_blk, const int32_t* __restrict__ bstart, const double* __restrict__ sc,
+                         const double* __restrict__ dsinv, int normalize, double* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= P) return;
+    const int64_t p = (int64_t)(key[e] >> 32);
+    const int64_t s = seg_of_block(sb, S, p);
+    const int64_t pj = sb[s] + (int64_t)(key[e] & 0xffffffffull);
+    const double v = val[e];
+    out[3 * e] = sc[3 * (int64_t)bstart[pos_blk[p]] + 1];
+    out[3 * e + 1] = sc[3 * (int64_t)bstart[pos_blk[pj]] + 1];
+    out[3 * e + 2] = normalize ? v * (dsinv[p] * dsinv[pj]) : v;
+}
+
+__global__ void k_pp_outptr(const int64_t* __restrict__ sb, int64_t S, const int64_t* __restrict__ rowptr, int64_t* __restrict__ out_ptr) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s <= S) out_ptr[s] = rowptr[sb[s]];
+}
+
+struct Carve {
+    char* base; size_t off;
+    template <class T> T* take(int64_t count) {
+        off = (off + 255) & ~(size_t)255;
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += sizeof(T) * (size_t)(count > 0 ? count : 0);
+        return p;
+    }
+};
+
+struct Bufs {
+    ColumnBufs col;
+    double *dinv, *cdiag, *a, *dsinv, *x, *om, *vin, *vout;
+    uint64_t *bkey, *bkey_out, *kin, *kout;
+    int32_t *bval, *pos_blk, *rank, *cnt;
+    int64_t *tab, *gt, *scan, *rowptr, *top, *nodes;
+    void* tmp; size_t tmp_bytes;
+    int64_t tcap, area, area_rows;
+};
+
+// the tile area: one tile of the largest possible segment, or the budget when the tiles of all segments could exceed it
+int64_t area_elems(int64_t bcap) {
+    const int64_t one = 2 * PPR_TILE * bcap;
+    const int64_t all = one * ((bcap + PPR_TILE - 1) / PPR_TILE);
+    return std::max<int64_t>(one, std::min<int64_t>((int64_t)(PPR_TILE_BUDGET / sizeof(double)), all));
+}
+
+size_t carve_ppr(Carve& C, int64_t m, int64_t S, int64_t G, int64_t N, int64_t cap, int32_t K, Bufs& B) {
+    C.off = column_pass_carve(C.base, C.off, m, S, G, N, PERR_WORDS, &B.col);
+    const int64_t bc = B.col.bcap;
+    B.tcap = bc / PPR_TILE + std::min<int64_t>(S, bc) + 1;
+    B.area = area_elems(bc);
+    B.area_rows = B.area / (2 * PPR_TILE) + 1;
+    B.dinv = C.take<double>(bc);
+    B.cdiag = C.take<double>(bc);
+    B.a = C.take<double>(m);
+    B.dsinv = C.take<double>(bc);
+    B.bkey = C.take<uint64_t>(bc);
+    B.bkey_out = C.take<uint64_t>(bc);
+    B.bval = C.take<int32_t>(bc);
+    B.pos_blk = C.take<int32_t>(bc);
+    B.rank = C.take<int32_t>(bc);
+    B.tab = C.take<int64_t>(T_FIELDS * B.tcap + B.tcap + 1);   // tiles, then the group starts
+    B.gt = B.tab + T_FIELDS * B.tcap;
+    B.om = C.take<double>(std::max<int32_t>(K, 1));
+    B.cnt = C.take<int32_t>(B.area_rows);
+    B.scan = C.take<int64_t>(B.area_rows);
+    B.top = C.take<int64_t>(1);
+    B.nodes = C.take<int64_t>(S);
+    B.rowptr = C.take<int64_t>(bc + 1);
+    B.kin = C.take<uint64_t>(cap);
+    B.vin = C.take<double>(cap);
+    B.kout = C.take<uint64_t>(cap);
+    B.vout = C.take<double>(cap);
+    size_t t1 = 0, t2 = 0, t3 = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, t1, (uint64_t*)nullptr, (uint64_t*)nullptr, (double*)nullptr, (double*)nullptr,
+                                    (size_t)std::max<int64_t>(cap, 1), 0, 64, (hipStream_t)0);
+    (void)rocprim::radix_sort_pairs(nullptr, t2, (uint64_t*)nullptr, (uint64_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr,
+                                    (size_t)std::max<int64_t>(bc, 1), 0, 64, (hipStream_t)0);
+    (void)rocprim::inclusive_scan(nullptr, t3, (const int32_t*)nullptr, (int64_t*)nullptr, (size_t)B.area_rows, rocprim::plus<int64_t>(),
+                                  (hipStream_t)0);
+    B.tmp_bytes = std::max(t1, std::max(t2, t3));
+    B.tmp = C.take<char>((int64_t)B.tmp_bytes);
+    B.x = C.take<double>(B.area);
+    return C.off + 256;
+}
+
+int bits_for(int64_t v) { int b = 1; while (b < 62 && ((int64_t)1 << b) <= v) ++b; return b; }
+
+}  // namespace
+
+size_t snapshot_ppr_bytes(int64_t m, int64_t S, int64_t G, int64_t N, int64_t out_cap, int32_t K) {
+    Carve C{nullptr, 0};
+    Bufs B;
+    return carve_ppr(C, m, S, G, N, out_cap, K, B);
+}
+
+int snapshot_ppr_run(hipStream_t st, void* ws, size_t ws_bytes, const SnapshotPprArgs& a, SnapshotPprReport* rep) {
+    *rep = SnapshotPprReport{};
+    const int64_t m = a.m, S = a.S, G = a.G, N = a.N;
+    const int weighted = (a.flags & RLAP_PPR_WEIGHTED) ? 1 : 0, self_loop = (a.flags & RLAP_PPR_SELF_LOOP) ? 1 : 0;
+    const int normalize = (a.flags & RLAP_PPR_NORMALIZE) ? 1 : 0, zero_ok = (a.flags & RLAP_PPR_ZERO_ROWS) ? 1 : 0;
+    // 1. the segment table, read back once (the host groups the tiles)
+    std::vector<int64_t> hptr((size_t)S + 1), hnp((size_t)G + 1, 0);
+    PP_HIPCHK(hipMemcpyAsync(hptr.data(), a.ptr, sizeof(int64_t) * (size_t)(S + 1), hipMemcpyDeviceToHost, st));
+    if (a.node_ptr) PP_HIPCHK(hipMemcpyAsync(hnp.data(), a.node_ptr, sizeof(int64_t) * (size_t)(G + 1), hipMemcpyDeviceToHost, st));
+    PP_HIPCHK(hipStreamSynchronize(st));
+    rep->host_syncs = 1;
+    if (hptr[0] != 0 || hptr[(size_t)S] != m) return RLAP_E_BAD_ARG;
+    for (int64_t s = 0; s < S; ++s) if (hptr[(size_t)s + 1] < hptr[(size_t)s]) return RLAP_E_BAD_ARG;
+    if (a.node_ptr) {
+        if (hnp[0] != 0 || hnp[(size_t)G] != N) return RLAP_E_BAD_ARG;
+        for (int64_t g = 0; g < G; ++g) if (hnp[(size_t)g + 1] < hnp[(size_t)g]) return RLAP_E_BAD_ARG;
+    }
+    Bufs B;
+    Carve C{static_cast<char*>(ws), 0};
+    if (carve_ppr(C, m, S, G, N, a.out_cap, a.K, B) > ws_bytes) return RLAP_E_WORKSPACE;
+    if (m == 0) {
+        PP_HIPCHK(hipMemsetAsync(a.out_ptr, 0, sizeof(int64_t) * (size_t)(S + 1), st));
+        return RLAP_OK;
+    }
+    // 2. the column pass, the weights, the degrees, read back once
+    PP_HIPCHK(hipMemsetAsync(B.col.err, 0, sizeof(int32_t) * PERR_WORDS, st));
+    std::vector<int64_t> hnodes((size_t)S);
+    int64_t* d_nodes = B.nodes;
+    int rc = column_pass_enqueue(st, a.sc, m, a.ptr, S, a.node_ptr, G, N, B.col, d_nodes);
+    if (rc != RLAP_OK) return rc;
+    hipLaunchKernelGGL(k_pp_weights, dim3(pp_blocks(m, 256)), dim3(256), 0, st, a.sc, m, zero_ok, B.col.err);
+    PP_HIPCHK(hipGetLastError());
+    int32_t herr[PERR_WORDS];
+    PP_HIPCHK(hipMemcpyAsync(hnodes.data(), d_nodes, sizeof(int64_t) * (size_t)S, hipMemcpyDeviceToHost, st));
+    PP_HIPCHK(hipMemcpyAsync(herr, B.col.err, sizeof(herr), hipMemcpyDeviceToHost, st));
+    PP_HIPCHK(hipStreamSynchronize(st));
+    rep->host_syncs += 1;
+    if (herr[COL_ERR_RANGE]) return RLAP_E_INDEX_RANGE;
+    if (herr[COL_ERR_GROUP]) return RLAP_E_NOT_GROUPED;
+    if (herr[COL_ERR_NOCOL]) return RLAP_E_NOT_SYMMETRIC;
+    if (weighted && herr[PERR_WEIGHT]) return RLAP_E_BAD_ARG;
+    int64_t Btot = 0;
+    for (int64_t s = 0; s < S; ++s) Btot += hnodes[(size_t)s];
+    if (Btot > B.col.bcap) return RLAP_E_INTERNAL;
+    // 3. per block and per row: degrees, normalised weights, ranks by id
+    hipLaunchKernelGGL(k_pp_degrees, dim3(pp_blocks(Btot, 256)), dim3(256), 0, st, a.sc, B.col.bstart, Btot, weighted, self_loop, a.alpha,
+                       B.dinv, B.cdiag);
+    hipLaunchKernelGGL(k_pp_norm, dim3(pp_blocks(m, 256)), dim3(256), 0, st, a.sc, m, weighted, a.alpha, B.col.blk, B.col.rb, B.dinv, B.a);
+    hipLaunchKernelGGL(k_pp_bkeys, dim3(pp_blocks(Btot, 256)), dim3(256), 0, st, a.sc, B.col.bstart, B.col.sb, S, Btot, B.bkey, B.bval);
+    PP_HIPCHK(hipGetLastError());
+    size_t tb = B.tmp_bytes;
+    PP_HIPCHK(rocprim::radix_sort_pairs(B.tmp, tb, B.bkey, B.bkey_out, B.bval, B.pos_blk, (size_t)Btot, 0, 32 + bits_for(S), st));
+    hipLaunchKernelGGL(k_pp_ranks, dim3(pp_blocks(Btot, 256)), dim3(256), 0, st, B.bkey_out, B.pos_blk, B.col.sb, Btot, B.rank);
+    PP_HIPCHK(hipGetLastError());
+    // 4. tiles and groups (small segments' tiles first), uploaded with the Chebyshev weights
+    std::vector<int64_t> tab;
+    std::vector<int64_t> gstart;   // first tile of each group
+    std::vector<int> gsmall;
+    std::vector<int64_t> grows;
+    for (int pass = 0; pass < 2; ++pass) {
+        int64_t gbytes = 0, groff = 0, ntile_g = 0;
+        bool open = false;
+        for (int64_t s = 0; s < S; ++s) {
+            const int64_t n = hnodes[(size_t)s];
+            if (n == 0 || (pass == 0) != (n <= PPR_SMALL_MAX)) continue;
+            const int64_t tbytes = 2 * PPR_TILE * n * (int64_t)sizeof(double);
+            for (int64_t c0 = 0; c0 < n; c0 += PPR_TILE) {
+                if (!open || gbytes + tbytes > (int64_t)PPR_TILE_BUDGET || ntile_g >= PP_GROUP_TILES) {
+                    if (open) grows.push_back(groff);
+                    gstart.push_back((int64_t)tab.size() / T_FIELDS);
+                    gsmall.push_back(pass == 0);
+                    gbytes = 0; groff = 0; ntile_g = 0; open = true;
+                }
+                tab.push_back(s); tab.push_back(c0); tab.push_back(gbytes / (int64_t)sizeof(double)); tab.push_back(groff);
+                gbytes += tbytes; groff += n; ++ntile_g;
+                if (pass == 0) rep->small_tiles += 1; else rep->large_tiles += 1;
+            }
+        }
+        if (open) grows.push_back(groff);
+    }
+    const int64_t ntiles = (int64_t)tab.size() / T_FIELDS;
+    const int64_t ngroups = (int64_t)gstart.size();
+    if (ntiles > B.tcap) return RLAP_E_INTERNAL;
+    for (int64_t g = 0; g < ngroups; ++g) if (grows[(size_t)g] > B.area_rows) return RLAP_E_INTERNAL;
+    tab.resize((size_t)(T_FIELDS * B.tcap), 0);
+    for (int64_t g = 0; g < ngroups; ++g) tab.push_back(gstart[(size_t)g]);
+    tab.push_back(ntiles);
+    std::vector<double> om((size_t)std::max<int32_t>(a.K, 1));
+    cheb::omegas(a.alpha, a.K, om.data());
+    PP_HIPCHK(hipMemcpyAsync(B.tab, tab.data(), sizeof(int64_t) * tab.size(), hipMemcpyHostToDevice, st));
+    PP_HIPCHK(hipMemcpyAsync(B.om, om.data(), sizeof(double) * om.size(), hipMemcpyHostToDevice, st));
+    PP_HIPCHK(hipMemsetAsync(B.top, 0, sizeof(int64_t), st));
+    rep->groups = ngroups;
+    Tiles T{B.tab, B.om, a.sc, B.col.bstart, B.col.rb, B.col.sb, B.a, B.cdiag, B.rank, B.x, a.alpha, a.eps, a.K};
+    // 5. the sweeps, group by group; after step K each group's kept entries are counted, scanned and staged
+    for (int64_t g = 0; g < ngroups; ++g) {
+        const int64_t* gt = B.gt + g;
+        const int64_t nt = (g + 1 < ngroups ? gstart[(size_t)g + 1] : ntiles) - gstart[(size_t)g];
+        const int64_t rows = grows[(size_t)g];
+        hipLaunchKernelGGL(k_pp_init, dim3(64, (unsigned)nt), dim3(PP_THREADS), 0, st, T, gt, nt);
+        rep->launches += 1;
+        if (gsmall[(size_t)g]) {
+            hipLaunchKernelGGL(k_pp_small, dim3((unsigned)nt), dim3(PP_SMALL_THREADS), 0, st, T, gt);
+            rep->launches += 1;
+        } else {
+            for (int32_t k = 1; k < a.K; ++k) {
+                hipLaunchKernelGGL(k_pp_large, dim3(pp_blocks(rows, PP_THREADS / 64)), dim3(PP_THREADS), 0, st, T, gt, nt, rows, k);
+                rep->launches += 1;
+            }
+        }
+        hipLaunchKernelGGL(k_pp_keep, dim3(pp_blocks(rows, PP_THREADS / 64)), dim3(PP_THREADS), 0, st, T, gt, nt, rows, 0, B.cnt, B.scan,
+                           B.top, B.kin, B.vin, a.out_cap);
+        PP_HIPCHK(hipGetLastError());
+        size_t sbytes = B.tmp_bytes;
+        PP_HIPCHK(rocprim::inclusive_scan(B.tmp, sbytes, B.cnt, B.scan, (size_t)rows, rocprim::plus<int64_t>(), st));
+        hipLaunchKernelGGL(k_pp_keep, dim3(pp_blocks(rows, PP_THREADS / 64)), dim3(PP_THREADS), 0, st, T, gt, nt, rows, 1, B.cnt, B.scan,
+                           B.top, B.kin, B.vin, a.out_cap);
+        hipLaunchKernelGGL(k_pp_top, dim3(1), dim3(64), 0, st, B.top, B.scan, rows);
+        PP_HIPCHK(hipGetLastError());
+        rep->launches += 4;
+    }
+    // 6. the kept count, read back once: too many for the caller's buffer -> nothing is written, the count is reported
+    int64_t P = 0;
+    PP_HIPCHK(hipMemcpyAsync(&P, B.top, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    PP_HIPCHK(hipStreamSynchronize(st));
+    rep->host_syncs += 1;
+    rep->kept = P;
+    if (P > a.out_cap) return RLAP_E_OUT_CAPACITY;
+    // 7. (segment, i, j) order, row sums, the output rows and offsets
+    if (P > 0) {
+        tb = B.tmp_bytes;
+        PP_HIPCHK(rocprim::radix_sort_pairs(B.tmp, tb, B.kin, B.kout, B.vin, B.vout, (size_t)P, 0, 32 + bits_for(Btot), st));
+    }
+    PP_HIPCHK(hipMemsetAsync(B.rowptr, 0, sizeof(int64_t) * (size_t)(Btot + 1), st));
+    hipLaunchKernelGGL(k_pp_rowptr, dim3(pp_blocks(P, 256)), dim3(256), 0, st, B.kout, P, Btot, B.rowptr);
+    hipLaunchKernelGGL(k_pp_rowsum, dim3(pp_blocks(Btot, PP_THREADS / 64)), dim3(PP_THREADS), 0, st, B.vout, B.rowptr, Btot, B.dsinv);
+    hipLaunchKernelGGL(k_pp_out, dim3(pp_blocks(P, 256)), dim3(256), 0, st, B.kout, B.vout, P, B.col.sb, S, B.pos_blk, B.col.bstart, a.sc,
+                       B.dsinv, normalize, a.out);
+    hipLaunchKernelGGL(k_pp_outptr, dim3(pp_blocks(S + 1, 256)), dim3(256), 0, st, B.col.sb, S, B.rowptr, a.out_ptr);
+    PP_HIPCHK(hipGetLastError());
+    return RLAP_OK;
+}
+
+}  // namespace rlap

@@ -378,17 +378,11 @@ Dims dims_of(int64_t m, int64_t S, int64_t G, int64_t N) {
 
 size_t carve_stats(Carve& C, int64_t m, int64_t S, int64_t G, int64_t N, int32_t max_iter, Bufs& B) {
     const Dims d = dims_of(m, S, G, N);
-    B.f = C.take<int32_t>(m);
-    B.blk = C.take<int32_t>(m);
-    B.bstart = C.take<int32_t>(d.bcap + 1);
-    B.sb = C.take<int64_t>(S + 1);
-    B.idx = C.take<int32_t>(d.idx_n);
-    B.err = C.take<int32_t>(ERR_WORDS);
+    ColumnBufs cb;
+    C.off = column_pass_carve(C.base, C.off, m, S, G, N, ERR_WORDS, &cb);
+    B.f = cb.rb; B.blk = cb.blk; B.bstart = cb.bstart; B.sb = cb.sb; B.idx = cb.idx; B.err = cb.err;
+    B.scan_tmp = cb.scan_tmp; B.scan_bytes = cb.scan_bytes;
     B.stage = C.take<int32_t>(d.stage_n);
-    B.scan_bytes = 0;
-    (void)rocprim::inclusive_scan(nullptr, B.scan_bytes, (const int32_t*)nullptr, (int32_t*)nullptr, (size_t)std::max<int64_t>(m, 1),
-                                  rocprim::plus<int32_t>(), (hipStream_t)0);
-    B.scan_tmp = C.take<char>((int64_t)B.scan_bytes);
     const int64_t vb = d.lcap > 0 ? d.bcap : 0;   // (vectors of the large regime only)
     B.v0 = C.take<double>(vb);
     B.v1 = C.take<double>(vb);
@@ -414,6 +408,42 @@ __global__ void k_st_fill_large(const int32_t* __restrict__ lseg, int32_t nlarge
 }
 
 }  // namespace
+
+static_assert(COL_ERR_RANGE == ERR_RANGE && COL_ERR_GROUP == ERR_GROUP && COL_ERR_NOCOL == ERR_NOCOL && COL_ERR_WORDS <= ERR_WORDS, "");
+
+size_t column_pass_carve(char* base, size_t off, int64_t m, int64_t S, int64_t G, int64_t N, int err_words, ColumnBufs* B) {
+    Carve C{base, off};
+    B->idx_n = (S / G) * N;
+    B->bcap = std::min<int64_t>(m, B->idx_n);
+    B->rb = C.take<int32_t>(m);   // (the block-start flags first, then rb)
+    B->blk = C.take<int32_t>(m);
+    B->bstart = C.take<int32_t>(B->bcap + 1);
+    B->sb = C.take<int64_t>(S + 1);
+    B->idx = C.take<int32_t>(B->idx_n);
+    B->err = C.take<int32_t>(std::max<int>(err_words, COL_ERR_WORDS));
+    B->scan_bytes = 0;
+    (void)rocprim::inclusive_scan(nullptr, B->scan_bytes, (const int32_t*)nullptr, (int32_t*)nullptr, (size_t)std::max<int64_t>(m, 1),
+                                  rocprim::plus<int32_t>(), (hipStream_t)0);
+    B->scan_tmp = C.take<char>((int64_t)B->scan_bytes);
+    return C.off;
+}
+
+int column_pass_enqueue(hipStream_t st, const double* sc, int64_t m, const int64_t* ptr, int64_t S, const int64_t* node_ptr, int64_t G,
+                        int64_t N, const ColumnBufs& B, int64_t* nodes) {
+    int32_t* f = B.rb;   // block-start flags, then (k_st_rows) the row -> block map
+    hipLaunchKernelGGL(k_st_flags, dim3(st_blocks(m, 256)), dim3(256), 0, st, sc, m, f);
+    hipLaunchKernelGGL(k_st_segmark, dim3(st_blocks(S, 256)), dim3(256), 0, st, ptr, S, f);
+    hipLaunchKernelGGL(k_st_index_fill, dim3((unsigned)std::min<int64_t>(4096, st_blocks(B.idx_n, 256))), dim3(256), 0, st, B.idx, B.idx_n);
+    ST_HIPCHK(hipGetLastError());
+    size_t sb_bytes = B.scan_bytes;
+    ST_HIPCHK(rocprim::inclusive_scan(B.scan_tmp, sb_bytes, f, B.blk, (size_t)m, rocprim::plus<int32_t>(), st));
+    hipLaunchKernelGGL(k_st_blocks, dim3(st_blocks(m, 256)), dim3(256), 0, st, sc, m, f, B.blk, ptr, S, node_ptr, G, N,
+                       B.idx, B.bstart, B.bcap, B.err);
+    hipLaunchKernelGGL(k_st_segblocks, dim3(st_blocks(S + 1, 256)), dim3(256), 0, st, ptr, S, B.blk, B.sb, nodes);
+    hipLaunchKernelGGL(k_st_rows, dim3(st_blocks(m, 256)), dim3(256), 0, st, sc, m, ptr, S, node_ptr, G, N, B.idx, B.sb, f, B.err);
+    ST_HIPCHK(hipGetLastError());
+    return RLAP_OK;
+}
 
 size_t snapshot_stats_bytes(int64_t m, int64_t S, int64_t G, int64_t N, int32_t max_iter) {
     Carve C{nullptr, 0};
@@ -452,18 +482,10 @@ int snapshot_stats_run(hipStream_t st, void* ws, size_t ws_bytes, const Snapshot
     }
     // 2. the column pass
     ST_HIPCHK(hipMemsetAsync(B.err, 0, sizeof(int32_t) * ERR_WORDS, st));
-    hipLaunchKernelGGL(k_st_flags, dim3(st_blocks(m, 256)), dim3(256), 0, st, a.sc, m, B.f);
-    hipLaunchKernelGGL(k_st_segmark, dim3(st_blocks(S, 256)), dim3(256), 0, st, a.ptr, S, B.f);
-    hipLaunchKernelGGL(k_st_index_fill, dim3((unsigned)std::min<int64_t>(4096, st_blocks(d.idx_n, 256))), dim3(256), 0, st, B.idx, d.idx_n);
-    ST_HIPCHK(hipGetLastError());
-    size_t sb_bytes = B.scan_bytes;
-    ST_HIPCHK(rocprim::inclusive_scan(B.scan_tmp, sb_bytes, B.f, B.blk, (size_t)m, rocprim::plus<int32_t>(), st));
-    hipLaunchKernelGGL(k_st_blocks, dim3(st_blocks(m, 256)), dim3(256), 0, st, a.sc, m, B.f, B.blk, a.ptr, S, a.node_ptr, G, N,
-                       B.idx, B.bstart, d.bcap, B.err);
-    hipLaunchKernelGGL(k_st_segblocks, dim3(st_blocks(S + 1, 256)), dim3(256), 0, st, a.ptr, S, B.blk, B.sb, a.nodes);
+    const ColumnBufs cb{B.f, B.blk, B.bstart, B.sb, B.idx, B.err, B.scan_tmp, B.scan_bytes, d.bcap, d.idx_n};
+    const int crc = column_pass_enqueue(st, a.sc, m, a.ptr, S, a.node_ptr, G, N, cb, a.nodes);
+    if (crc != RLAP_OK) return crc;
     int32_t* rb = B.f;   // (the flags are read by k_st_blocks only)
-    hipLaunchKernelGGL(k_st_rows, dim3(st_blocks(m, 256)), dim3(256), 0, st, a.sc, m, a.ptr, S, a.node_ptr, G, N, B.idx, B.sb, rb, B.err);
-    ST_HIPCHK(hipGetLastError());
     // 3. node counts and the layout checks, read back once
     std::vector<int64_t> hnodes((size_t)S);
     int32_t herr[ERR_WORDS];

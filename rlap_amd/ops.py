@@ -641,6 +641,194 @@ def snapshot_stats(
     return {"nodes": nodes, "rows": rows, "lambda_max": lam, "iters": iters, "converged": conv.bool()}
 
 
+PPR_MAX_STEPS = 4096   # cap on the Chebyshev steps K (rlap_amd/csrc/rlap_cheb.h::MAX_STEPS)
+PPR_FIRST_CAP_PER_ROW = 16   # first output capacity of a PPR call: max(16 rows per input row + 64, PPR_FIRST_CAP_MIN), at most
+PPR_FIRST_CAP_MIN = 1 << 22  # S * min(num_nodes, m)^2 (every pair of every segment); one retry with the exact count beyond
+
+
+def ppr_steps(alpha: float, tol: float) -> int:
+    """K = min{K >= 0 : T_K(1/(1-alpha)) >= 1/tol}, T_K by its three-term recurrence (the arithmetic of rlap_cheb.h::steps), or -1
+    when K would exceed PPR_MAX_STEPS.  After K Chebyshev steps every entry of S lies within tol of exact."""
+    mu, goal = 1.0 / (1.0 - float(alpha)), 1.0 / float(tol)
+    if 1.0 >= goal:
+        return 0
+    tp, t = 1.0, mu
+    for k in range(1, PPR_MAX_STEPS + 1):
+        if t >= goal:
+            return k
+        tp, t = t, 2.0 * mu * t - tp
+    return -1
+
+
+def _real(x, what: str, lo: float, hi: float, lo_open: bool = True) -> float:
+    if isinstance(x, bool) or not isinstance(x, (int, float)):
+        raise ValueError(f"{what}: a number, got {x!r}")
+    v = float(x)
+    if not (v > lo if lo_open else v >= lo) or not v < hi:
+        raise ValueError(f"{what}: must lie in ({lo}, {hi}), got {x!r}")
+    return v
+
+
+def _ppr_params(alpha, eps, tol) -> Tuple[float, float, float, int]:
+    """Host-side checks of the PPR parameters, made before anything is launched."""
+    a = _real(alpha, "alpha", 0.0, 1.0)
+    e = _real(eps, "eps", 0.0, float("inf"))
+    t = _real(tol, "tol", 0.0, float("inf"))
+    K = ppr_steps(a, t)
+    if K < 0:
+        raise ValueError(f"alpha={a!r}, tol={t!r} need more than {PPR_MAX_STEPS} Chebyshev steps (T_K(1/(1-alpha)) >= 1/tol)")
+    return a, e, t, K
+
+
+def _ppr_call(x: Tensor, p: Tensor, np_: Optional[Tensor], n: int, alpha: float, eps: float, tol: float, flags: int,
+              dev: torch.device) -> Tuple[Tensor, Tensor]:
+    """One rlap_snapshot_ppr call inside torch-owned memory: the first output capacity is max(16 m + 64, 2^22) rows, at most
+    S min(n, m)^2; when the kept entries exceed it the call writes nothing and reports the count, and is made once more with
+    exactly that many."""
+    global last_stats
+    lib, hobj = _handle_obj(dev)
+    h = hobj.ptr
+    S = p.numel() - 1
+    m = int(x.shape[0])
+    d_ptr = p.to(dev)
+    d_np = np_.to(dev) if np_ is not None else None
+    G = np_.numel() - 1 if np_ is not None else 1
+    cap = first_cap = min(S * min(n, m) ** 2, max(PPR_FIRST_CAP_PER_ROW * m + 64, PPR_FIRST_CAP_MIN))
+    retries = 0
+    while True:
+        out = torch.empty((cap, 3), dtype=torch.float64, device=dev)
+        pptr = torch.empty(S + 1, dtype=torch.int64, device=dev)
+        info = _lib.PprInfo()
+        st = _lib.Stats()
+        rc = _run(hobj, dev, m, None, G, False, lambda: lib.rlap_snapshot_ppr(
+            h, x.data_ptr() if m else None, m, d_ptr.data_ptr(), S, d_np.data_ptr() if d_np is not None else None, G, n,
+            alpha, eps, tol, flags, out.data_ptr() if cap else None, cap, pptr.data_ptr(), ctypes.byref(info)), st)
+        if rc == _lib.E_OUT_CAPACITY and retries == 0:
+            cap = int(info.rows_needed)
+            retries += 1
+            continue
+        break
+    if rc in (_lib.E_NOT_GROUPED, 1, 2, 3):
+        raise ValueError(f"rlap: {_lib.status_string(rc)}" + (" (or a weight is <= 0)" if rc == 3 else ""))
+    if rc != 0:
+        _raise(rc)
+    P = int(info.rows_needed)
+    last_stats = dict(info.as_dict(), output_retries=retries, first_cap=first_cap)
+    return _trim(out, P), pptr
+
+
+def snapshot_ppr(
+    sc: Tensor,
+    ptr: Union[Tensor, Sequence[int]],
+    num_nodes: int,
+    *,
+    node_ptr: Optional[Union[Tensor, Sequence[int]]] = None,
+    alpha: float = 0.2,
+    eps: float = 1e-4,
+    tol: float = 1e-10,
+    weighted: bool = True,
+    add_self_loop: bool = False,
+    normalize_out: bool = True,
+) -> Tuple[Tensor, Tensor]:
+    """Personalised-PageRank diffusion of every snapshot of a result of the calls above, on the device and without a dense matrix --
+    rLapPPRDiffusion's compute_ppr (PyGCL: transition_matrix('sym'), diffusion_matrix_exact('ppr'), sparsify_dense('threshold'),
+    transition_matrix('sym')) for all snapshots of one call.  `sc`, `ptr`, `num_nodes` and `node_ptr` as for snapshot_stats.
+
+    For snapshot s with distinct ids V_s and symmetric adjacency A (the rows' weights, or unit entries with weighted=False; duplicate
+    rows summed; A + I with add_self_loop), d = A 1:
+        S = alpha (I - (1 - alpha) D^-1/2 A D^-1/2)^-1,  entries S_ij >= eps kept,  normalize_out: D_S^-1/2 S D_S^-1/2 (D_S: row sums)
+    Returns (out (P, 3) float64 rows [i, j, value] in the input's id space, pptr (S+1,) int64), both on sc's device: segment s is rows
+    [pptr[s], pptr[s+1]) in row-major order (ascending i, then j) -- the order of adapters.compute_ppr's nonzero() on the relabelled
+    snapshot.  S comes from K fixed Chebyshev steps, K = ppr_steps(alpha, tol) (35 for the defaults): every entry lies within `tol`
+    of exact before normalisation, so a keep decision can differ from the exact matrix only where |S_ij - eps| <= tol.  The result is
+    exactly symmetric, the same input gives the same bits, and segment s equals the same call on that segment alone, bit for bit.
+
+    alpha outside (0, 1), eps <= 0, tol <= 0, more than PPR_MAX_STEPS steps, malformed tables, a column not contiguous within its
+    segment, a row id without a column, an id out of range, or (weighted) a weight <= 0 raise ValueError.  `last_stats` then holds
+    what the call did (rlap_ppr_info: steps, small / large tiles, groups, launches, rows_needed, arena_bytes, host_syncs) and
+    `output_retries` (1 when the first capacity guess was short).
+    """
+    p, np_ = _snapshot_args(sc, ptr, num_nodes, node_ptr, 1.0, 1)
+    alpha, eps, tol, _ = _ppr_params(alpha, eps, tol)
+    if weighted and not sc.is_cuda and sc.shape[0] and not bool((sc[:, 2] > 0).all() and torch.isfinite(sc[:, 2]).all()):
+        raise ValueError("sc: every weight must be > 0 (the spectral bound of the iteration needs A >= 0)")
+    dev = _device_for(sc)
+    flags = ((_lib.PPR_WEIGHTED if weighted else 0) | (_lib.PPR_SELF_LOOP if add_self_loop else 0)
+             | (_lib.PPR_NORMALIZE if normalize_out else 0))
+    with torch.cuda.device(dev):
+        x = sc.to(device=dev, dtype=torch.float64).contiguous()
+        return _ppr_call(x, p, np_, int(num_nodes), alpha, eps, tol, flags, dev)
+
+
+def ppr_diffusion(
+    edge_index: Tensor,
+    edge_weights: Optional[Tensor],
+    num_nodes: int,
+    *,
+    alpha: float = 0.2,
+    eps: float = 1e-4,
+    tol: float = 1e-10,
+    add_self_loop: bool = False,
+    normalize_out: bool = True,
+) -> Tuple[Tensor, Tensor]:
+    """The diffusion of snapshot_ppr on a plain undirected edge list (both directions present), node set [0, num_nodes) -- what
+    adapters.compute_ppr(edge_index, edge_weights, num_nodes, ...) computes densely; PyGCL's A.PPRDiffusion uses add_self_loop=True.
+    Rows of weight 0 are dropped (as the op's reader does); a negative weight raises ValueError.  The rows are grouped by column with
+    a stable device sort and duplicates summed (in input order); a pattern or weights that are not exactly symmetric raise
+    ValueError("adjacency not symmetric").  An id without edges keeps its diagonal entry: alpha (1 with a self loop) before
+    normalisation.  Returns (edge_index (2, P) int64, edge_weights (P,) float64) in row-major order, on the input's device.
+    """
+    alpha, eps, tol, _ = _ppr_params(alpha, eps, tol)
+    if isinstance(num_nodes, bool) or not hasattr(num_nodes, "__index__") or num_nodes.__index__() < 0:
+        raise ValueError(f"num_nodes: a non-negative integer, got {num_nodes!r}")
+    n = num_nodes.__index__()
+    if not isinstance(edge_index, Tensor) or edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise ValueError("edge_index: a (2, E) tensor")
+    E = int(edge_index.shape[1])
+    w = edge_weights
+    if w is not None:
+        w = w.reshape(-1)
+        if w.numel() != E:
+            raise ValueError("edge_weights must have one entry per edge")
+        if E and not bool((w >= 0).all()):
+            raise ValueError("edge_weights: a weight is negative (or not a number)")
+    if E and not edge_index.is_cuda and (int(edge_index.min()) < 0 or int(edge_index.max()) >= n):
+        raise ValueError(f"edge_index: ids must lie in [0, {n})")
+    dev = _device_for(edge_index)
+    with torch.cuda.device(dev):
+        ei = edge_index.to(device=dev, dtype=torch.int64)
+        w = torch.ones(E, dtype=torch.float64, device=dev) if w is None else w.to(device=dev, dtype=torch.float64)
+        if E and (int(ei.min()) < 0 or int(ei.max()) >= n):
+            raise ValueError(f"edge_index: ids must lie in [0, {n})")
+        keep = w != 0
+        ei, w = ei[:, keep], w[keep]
+        key, order = torch.sort(ei[1] * n + ei[0], stable=True)            # (col, row), input order among duplicates
+        w = w[order]
+        uniq, inv, counts = torch.unique_consecutive(key, return_inverse=True, return_counts=True)
+        rank = torch.arange(key.numel(), device=dev) - (torch.cumsum(counts, 0) - counts)[inv]
+        ws = torch.zeros(uniq.numel(), dtype=torch.float64, device=dev)
+        for k in range(int(counts.max()) if counts.numel() else 0):   # duplicates summed in input order (one add per slot per pass)
+            sel = rank == k
+            ws.index_add_(0, inv[sel], w[sel])
+        row, col = uniq % n if n else uniq, uniq // n if n else uniq
+        kt, pt = torch.sort(row * n + col)
+        if not (torch.equal(kt, uniq) and torch.equal(ws[pt], ws)):
+            raise ValueError("adjacency not symmetric")
+        present = torch.zeros(n, dtype=torch.bool, device=dev)
+        present[col] = True
+        iso = torch.nonzero(~present).reshape(-1)
+        if iso.numel():   # (i, i, 0): the column of an id without edges
+            key2, o2 = torch.sort(torch.cat([uniq, iso * n + iso]))
+            row, col = torch.cat([row, iso])[o2], torch.cat([col, iso])[o2]
+            ws = torch.cat([ws, torch.zeros(iso.numel(), dtype=torch.float64, device=dev)])[o2]
+        sc = torch.stack([row.to(torch.float64), col.to(torch.float64), ws], 1).contiguous()
+        flags = (_lib.PPR_WEIGHTED | _lib.PPR_ZERO_ROWS | (_lib.PPR_SELF_LOOP if add_self_loop else 0)
+                 | (_lib.PPR_NORMALIZE if normalize_out else 0))
+        p = torch.tensor([0, sc.shape[0]], dtype=torch.int64)
+        out, _ = _ppr_call(sc, p, None, n, alpha, eps, tol, flags, dev)
+        return out[:, :2].long().t().contiguous(), out[:, 2].contiguous()
+
+
 def identity(a: Tensor) -> Tensor:
     """Boundary self-test (reference: rlap/ops.py:61-63): tensor -> column-major
     staging -> tensor, on the GPU; returns a tensor on `a`'s device."""
