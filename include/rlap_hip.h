@@ -283,6 +283,45 @@ int rlap_snapshot_ppr(rlap_handle h, const double* d_sc, int64_t m, const int64_
                       int64_t G, int64_t num_nodes, double alpha, double eps, double tol, int flags, double* d_out,
                       int64_t out_cap_rows, int64_t* d_out_ptr, rlap_ppr_info* h_info);
 
+/* Induced subgraphs and relabelling of snapshots: for every segment s (described as for rlap_snapshot_stats: d_sc, m, d_ptr, S,
+ * d_node_ptr, G, num_nodes; S = 0 with m = 0 is allowed) the rows whose two ids both lie in the segment's node set, in their input
+ * order -- torch.unique + PyG's subgraph() of every snapshot of a call, without a sort.  The call is a filter: it makes no assumption
+ * about the order or the symmetry of the rows of a segment, so a plain edge list is a valid input, as is the (out, out_ptr) of
+ * rlap_snapshot_ppr.
+ *   d_nodes, d_nodes_ptr, nodes_len : the node sets.  d_nodes == NULL: the set of segment s is the ids that appear in its rows
+ *                     (after the self-loop rule below).  d_nodes with d_nodes_ptr ([S+1], from 0 to nodes_len): the list
+ *                     d_nodes[d_nodes_ptr[s] .. d_nodes_ptr[s+1]) per segment.  d_nodes without d_nodes_ptr: one list of nodes_len
+ *                     ids for all segments; with d_node_ptr the set of segment s is the part of the list inside its graph's range.
+ *                     Lists are sets: any order, repeats allowed; an id that no row of the segment has still belongs to the set.
+ *   flags           : RLAP_SUB_RELABEL (the ids of the written rows become labels), RLAP_SUB_NO_SELF_LOOPS (rows with i == j are
+ *                     dropped, and with d_nodes == NULL they do not put i into the set: remove_self_loops before unique)
+ *   d_out           : (m, 3) f64, the kept rows segment by segment, the weight copied bit for bit.  The label of an id is its rank
+ *                     among the sorted distinct ids of the set, starting at 0 in every segment.  That equals PyG's
+ *                     subgraph(relabel_nodes=True) whenever the subset handed to it is sorted and distinct (a torch.unique result).
+ *   d_out_ptr       : [S+1] row offsets of the segments in d_out
+ *   d_ids, ids_cap  : the sorted distinct ids of every segment's set, segment by segment -- the map label -> id; ids_cap is the
+ *                     capacity of d_ids in entries and must be at least min(2 m, (S / G) num_nodes) for d_nodes == NULL, nodes_len
+ *                     with d_nodes_ptr, (S / G) nodes_len for a shared list
+ *   d_ids_ptr       : [S+1] offsets of the segments in d_ids: the id of label l of segment s is d_ids[d_ids_ptr[s] + l]
+ *   h_info          : (nullable) what the call did
+ * The same input gives the same bits.  An id of a row or of a segment's list outside the segment's range (of a shared list: outside
+ * [0, num_nodes)): RLAP_E_INDEX_RANGE; a bad ptr / node_ptr / nodes_ptr, or ids_cap below the bound: RLAP_E_BAD_ARG.  Scratch from
+ * the arena: (S / G) num_nodes flag bytes, the bitmap packed from them, its scan and one count per 1,024 rows (RLAP_E_WORKSPACE when
+ * a caller-provided one is too small, rlap_workspace_needed() saying how much).  One host synchronisation. */
+enum { RLAP_SUB_RELABEL = 1, RLAP_SUB_NO_SELF_LOOPS = 2 };
+typedef struct {
+    int64_t rows_kept;        /* rows written to d_out                */
+    int64_t ids_written;      /* ids written to d_ids                 */
+    int64_t arena_bytes;      /* scratch bytes of the call            */
+    int32_t host_syncs;       /* host synchronisations of the call    */
+    int32_t pad;
+} rlap_subgraph_info;
+
+int rlap_snapshot_subgraph(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
+                           int64_t G, int64_t num_nodes, const int64_t* d_nodes, const int64_t* d_nodes_ptr, int64_t nodes_len,
+                           int flags, double* d_out, int64_t* d_out_ptr, int64_t* d_ids, int64_t ids_cap, int64_t* d_ids_ptr,
+                           rlap_subgraph_info* h_info);
+
 /* The op with the step BEFORE the path fused in (scripts/node_shared.py:326-327,
  * scripts/augmentor_benchmarks.py:77-78):
  *   symmetrize != 0 : the input holds every undirected edge in one or both directions; (b,a) is

@@ -19,7 +19,7 @@ EXPORTS = [
     "rlap_approx_chol_from_edges", "rlap_debug_set_limits", "rlap_pack_rows", "rlap_unpack_rows",
     "rlap_workspace_bytes", "rlap_workspace_query", "rlap_set_workspace", "rlap_workspace_needed", "rlap_debug_set_poison", "rlap_debug_set_jitter",
     "rlap_set_rng_mode", "rlap_approx_chol_views", "rlap_approx_chol_depths", "rlap_debug_set_flow_limits",
-    "rlap_approx_chol_views_depths", "rlap_snapshot_stats", "rlap_snapshot_ppr",
+    "rlap_approx_chol_views_depths", "rlap_snapshot_stats", "rlap_snapshot_ppr", "rlap_snapshot_subgraph",
 ]
 
 E_WORKSPACE = 11   # RLAP_E_WORKSPACE
@@ -27,6 +27,8 @@ E_NOT_GROUPED = 12   # RLAP_E_NOT_GROUPED
 E_OUT_CAPACITY = 13   # RLAP_E_OUT_CAPACITY
 # rlap_snapshot_ppr flags
 PPR_WEIGHTED, PPR_SELF_LOOP, PPR_NORMALIZE, PPR_ZERO_ROWS = 1, 2, 4, 8
+# rlap_snapshot_subgraph flags
+SUB_RELABEL, SUB_NO_SELF_LOOPS = 1, 2
 
 # rlap_stats.elim_kernel
 KERNEL_NONE, KERNEL_ROUND, KERNEL_FLOW = 0, 1, 2
@@ -68,6 +70,17 @@ class PprInfo(ctypes.Structure):
     _fields_ = [
         ("steps", ctypes.c_int64), ("small_tiles", ctypes.c_int64), ("large_tiles", ctypes.c_int64), ("groups", ctypes.c_int64),
         ("launches", ctypes.c_int64), ("rows_needed", ctypes.c_int64), ("arena_bytes", ctypes.c_int64), ("host_syncs", ctypes.c_int32),
+        ("pad", ctypes.c_int32),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_ if f != "pad"}
+
+
+class SubgraphInfo(ctypes.Structure):
+    """rlap_subgraph_info (include/rlap_hip.h)."""
+    _fields_ = [
+        ("rows_kept", ctypes.c_int64), ("ids_written", ctypes.c_int64), ("arena_bytes", ctypes.c_int64), ("host_syncs", ctypes.c_int32),
         ("pad", ctypes.c_int32),
     ]
 
@@ -117,6 +130,9 @@ def load():
     lib.rlap_snapshot_ppr.restype = ci
     lib.rlap_snapshot_ppr.argtypes = [vp, vp, i64, vp, i64, vp, i64, i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, ci, vp, i64,
                                       vp, ctypes.POINTER(PprInfo)]
+    lib.rlap_snapshot_subgraph.restype = ci
+    lib.rlap_snapshot_subgraph.argtypes = [vp, vp, i64, vp, i64, vp, i64, i64, vp, vp, i64, ci, vp, vp, vp, i64, vp,
+                                           ctypes.POINTER(SubgraphInfo)]
     lib.rlap_approx_chol_views.restype = ci
     lib.rlap_approx_chol_views.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, vp, ci, ci, vp, u64, vp, i64, vp,
                                            ctypes.POINTER(Stats)]

@@ -7,7 +7,9 @@ Mirrors of the reference's L2 adapters that keep everything on the GPU:
                   siblings for the `(aug1, aug2)` pair of scripts/node_shared.py:488-498
   * `rLapDepths` -- the same graph at K removed fractions from one elimination
                   (the sweeps of scripts/rlap_vc_spectral.py, scripts/rlap_ppr_edge_plots.py); `.diffuse`
-                  gives their PPR diffusions from one ops.snapshot_ppr call
+                  gives their PPR diffusions from one ops.snapshot_ppr call, `.relabelled` their compact graphs and id maps and
+                  `.batch_edge_counts` the batch subgraph sizes from ops.snapshot_subgraph
+  * `rLapChain` -- the chain of scripts/rlap_vc_spectral.py: eliminate, relabel the survivors 0..k-1, eliminate again
 PyGCL / DGL are optional: with them installed the classes return their graph types,
 without them a small named tuple with the same fields.
 """
@@ -185,6 +187,49 @@ class rLapDepths:
         R = int(self.views)
         return [[graph(k * R + r) for k in range(K)] for r in range(R)]
 
+    def relabelled(self, g):
+        """The compact graph of every run and depth and its id map -- torch.unique + subgraph(relabel_nodes=True) of every snapshot
+        -- from ONE depths call and ONE ops.snapshot_subgraph call.  Returns the layout of `augment` with items
+        (Graph(None, edge_index, edge_weights), ids): edge_index holds labels 0..len(ids)-1 and ids[label] is the input's id."""
+        _, sc, ptr, num_nodes = self._snapshots(g)
+        out, optr, ids, iptr = ops.snapshot_subgraph(sc, ptr, num_nodes, relabel=True)
+        op, ip = optr.tolist(), iptr.tolist()
+
+        def item(i):
+            part = out[op[i]:op[i + 1]]
+            return Graph(None, part[:, :2].long().t().contiguous(), part[:, 2].contiguous()), ids[ip[i]:ip[i + 1]]
+        K = len(self.fracs)
+        if self.views is None:
+            return [item(k) for k in range(K)]
+        R = int(self.views)
+        return [[item(k * R + r) for k in range(K)] for r in range(R)]
+
+    def batch_edge_counts(self, g, batch_size: int, generator=None, alpha: float = 0.2, eps: float = 1e-4):
+        """The number scripts/rlap_ppr_edge_plots.py:61-76 plots, for every run and depth of ONE call: the diffusion of `diffuse`,
+        its nodes without self loops (ops.snapshot_subgraph(remove_self_loops=True): remove_self_loops + unique), a random batch of
+        up to `batch_size` of them (torch.randperm, seeded by `generator`, snapshot after snapshot in depth-major order) and the rows
+        of the diffused graph among the batch (ops.snapshot_subgraph(nodes=, nodes_ptr=); as in the script the self loops count).
+        Returns (counts, batches): counts a (runs, depths) int64 tensor, the layout of `stats`; batches the chosen node ids in
+        the layout of `augment`."""
+        _, sc, ptr, num_nodes = self._snapshots(g)
+        out, pptr = ops.snapshot_ppr(sc, ptr, num_nodes, alpha=alpha, eps=eps)
+        _, _, ids, iptr = ops.snapshot_subgraph(out, pptr, num_nodes, remove_self_loops=True)
+        ip = iptr.tolist()
+        gdev = generator.device if generator is not None else torch.device("cpu")
+        chosen = []
+        for s in range(len(ip) - 1):
+            perm = torch.randperm(ip[s + 1] - ip[s], generator=generator, device=gdev)[:int(batch_size)]
+            chosen.append(ids[ip[s]:ip[s + 1]][perm.to(ids.device)])
+        nodes_ptr = [0]
+        for c in chosen:
+            nodes_ptr.append(nodes_ptr[-1] + int(c.numel()))
+        _, optr, _, _ = ops.snapshot_subgraph(out, pptr, num_nodes, nodes=torch.cat(chosen), nodes_ptr=nodes_ptr)
+        D, R = len(self.fracs), 1 if self.views is None else int(self.views)
+        counts = (optr[1:] - optr[:-1]).reshape(D, R).t().contiguous()
+        if self.views is None:
+            return counts, chosen
+        return counts, [[chosen[k * R + r] for k in range(D)] for r in range(R)]
+
     def augment(self, g):
         x, sc, ptr, num_nodes = self._snapshots(g)
 
@@ -197,6 +242,75 @@ class rLapDepths:
             return [graph(k) for k in range(K)]
         R = int(self.views)
         return [[graph(k * R + r) for k in range(K)] for r in range(R)]   # (rows depth-major, then view)
+
+    def __call__(self, x, edge_index, edge_weight=None):
+        return self.augment(Graph(x, edge_index, edge_weight))
+
+
+class rLapChain:
+    """The chain of scripts/rlap_vc_spectral.py:14-58 (get_rlap_sc_stats): `batch_count` rounds, each an approximate_cholesky call on
+    the relabelled, weighted result of the round before.  num_nodes_0 = edge_index.max() + 1 and every round removes
+    t = int(batch_frac * num_nodes_0) vertices (the script's nodes_to_eliminate).  After a round the survivors that still have an
+    edge are relabelled 0..k-1 by ONE ops.snapshot_subgraph(relabel=True) call on the device (no torch.unique), survivors without
+    an edge drop out, num_nodes becomes k and the next round draws a fresh order: round k runs with `seed + k`.  This is not
+    rLapDepths, whose depths are nested stops of one elimination in the input's id space.
+
+    `perms` (o_v="random" only): an optional callable perms(k, num_nodes_k) returning round k's node_id vector, handed on as
+    `perm=`; without it every round's order is drawn on the device from seed + k.  Per round the host reads one number, the node
+    count the next call's arguments need.  A round whose result has no rows ends the chain: the remaining rounds are empty graphs.
+
+    `.augment(g)` returns the batch_count graphs Graph(x, edge_index, edge_weights), ids mapped back into the input's space (the
+    rounds' label -> id maps composed on the device) and the Schur-complement weights kept, as the next round uses them.
+    """
+
+    def __init__(self, batch_frac: float, batch_count: int, o_v: str = "random", o_n: str = "asc", seed: Optional[int] = None,
+                 mode: str = "exact", perms=None):
+        assert int(batch_count) == batch_count and batch_count >= 1, "batch_count: a positive int"
+        assert perms is None or o_v == "random", "perms: only for o_v='random'"
+        self.batch_frac, self.batch_count = float(batch_frac), int(batch_count)
+        self.o_v, self.o_n, self.seed, self.mode, self.perms = o_v, o_n, seed, mode, perms
+
+    def _rounds(self, g):
+        """[(relabelled rows (m_k, 3), ids_k -> input ids, num_nodes_k of the round's result)] for every round."""
+        x, edge_index, edge_weights = g.unfold() if hasattr(g, "unfold") else g
+        n = int(edge_index.max().item()) + 1 if edge_index.numel() else 0
+        self.num_remove = int(self.batch_frac * n)
+        seed = int(torch.randint(0, 2**62, (1,)).item()) if self.seed is None else int(self.seed)
+        ei, w, back, rounds = edge_index, edge_weights, None, []
+        if n == 0:
+            rounds.append((torch.zeros((0, 3), dtype=torch.float64, device=edge_index.device),
+                           torch.zeros(0, dtype=torch.int64, device=edge_index.device), 0))
+        for k in range(len(rounds), self.batch_count):
+            if rounds and rounds[-1][0].shape[0] == 0:      # nothing left to eliminate from: num_nodes would be 0
+                rounds.append(rounds[-1])
+                continue
+            perm = None
+            if self.perms is not None:
+                perm = torch.as_tensor(self.perms(k, n), dtype=torch.int64)
+            sc = ops.approximate_cholesky(ei, w, n, self.num_remove, self.o_v, self.o_n, perm=perm, seed=seed + k,
+                                          return_device="same", mode=self.mode)
+            out, _, ids, _ = ops.snapshot_subgraph(sc, [0, int(sc.shape[0])], n, relabel=True)
+            back = ids if back is None else back[ids]
+            n = int(ids.numel())
+            rounds.append((out, back, n))
+            ei, w = out[:, :2].long().t().contiguous(), out[:, 2].contiguous()
+        return x, rounds
+
+    def augment(self, g):
+        x, rounds = self._rounds(g)
+        return [_as_graph(x, back[out[:, :2].long()].t().contiguous(), out[:, 2].contiguous()) for out, back, _ in rounds]
+
+    def stats(self, g, weighted: bool = False, tol: float = 1e-10, max_iter: int = 1000):
+        """max_sv, node_count, edge_count (and converged) of every round through ONE ops.snapshot_stats call on the rounds'
+        relabelled results: (1, batch_count) tensors, the layout of rLapDepths.stats with one run."""
+        _, rounds = self._rounds(g)
+        ptr = [0]
+        for out, _, _ in rounds:
+            ptr.append(ptr[-1] + int(out.shape[0]))
+        st = ops.snapshot_stats(torch.cat([out for out, _, _ in rounds]), ptr, max(max(n for _, _, n in rounds), 1),
+                                weighted=weighted, tol=tol, max_iter=max_iter)
+        return {"max_sv": st["lambda_max"][None], "node_count": st["nodes"][None], "edge_count": st["rows"][None],
+                "converged": st["converged"][None]}
 
     def __call__(self, x, edge_index, edge_weight=None):
         return self.augment(Graph(x, edge_index, edge_weight))

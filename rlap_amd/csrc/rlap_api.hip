@@ -20,6 +20,7 @@
 #include "rlap_cheb.h"
 #include "rlap_ppr.h"
 #include "rlap_stats.h"
+#include "rlap_subgraph.h"
 
 using namespace rlap;
 
@@ -1305,6 +1306,44 @@ int rlap_snapshot_ppr(rlap_handle h, const double* d_sc, int64_t m, const int64_
         h_info->steps = K; h_info->small_tiles = rep.small_tiles; h_info->large_tiles = rep.large_tiles; h_info->groups = rep.groups;
         h_info->launches = rep.launches; h_info->rows_needed = rep.kept; h_info->arena_bytes = (int64_t)need;
         h_info->host_syncs = rep.host_syncs;
+    }
+    return rc;
+}
+
+int rlap_snapshot_subgraph(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
+                           int64_t G, int64_t num_nodes, const int64_t* d_nodes, const int64_t* d_nodes_ptr, int64_t nodes_len,
+                           int flags, double* d_out, int64_t* d_out_ptr, int64_t* d_ids, int64_t ids_cap, int64_t* d_ids_ptr,
+                           rlap_subgraph_info* h_info) {
+    if (h_info) *h_info = rlap_subgraph_info{};
+    if (!h || !d_ptr || S < 0 || m < 0 || num_nodes < 0 || (m > 0 && (!d_sc || !d_out || S < 1)) || !d_out_ptr || !d_ids_ptr) return RLAP_E_BAD_ARG;
+    if (flags & ~(RLAP_SUB_RELABEL | RLAP_SUB_NO_SELF_LOOPS)) return RLAP_E_BAD_ARG;
+    if (d_node_ptr ? (G < 1 || S % G != 0) : false) return RLAP_E_BAD_ARG;
+    if (!d_node_ptr) G = 1;
+    if (d_nodes ? nodes_len < 0 : (d_nodes_ptr != nullptr)) return RLAP_E_BAD_ARG;   // (nodes_ptr only together with nodes)
+    if (!d_nodes) nodes_len = 0;
+    if (m >= INT32_MAX || S >= (int64_t)1 << 30 || num_nodes >= INT32_MAX || nodes_len >= INT32_MAX) return RLAP_E_TOO_LARGE;
+    if ((S / G) * num_nodes >= (int64_t)1 << 40) return RLAP_E_TOO_LARGE;
+    const int64_t ids_need = snapshot_subgraph_ids_cap(m, S, G, num_nodes, d_nodes != nullptr, d_nodes_ptr != nullptr, nodes_len);
+    if (ids_cap < ids_need || (ids_need > 0 && !d_ids)) return RLAP_E_BAD_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device);
+    const size_t need = snapshot_subgraph_bytes(m, S, G, num_nodes);
+    h->ws_needed = need;
+    void* base = nullptr;
+    size_t have = 0;
+    if (h->ext_ws) {
+        if (need > h->ext_ws_bytes) return RLAP_E_WORKSPACE;
+        base = h->ext_ws; have = h->ext_ws_bytes;
+    } else {
+        ENSURE(h->own_ws, need);
+        base = h->own_ws.p; have = h->own_ws.cap;
+    }
+    SnapshotSubArgs a{d_sc, m, d_ptr, S, d_node_ptr, G, num_nodes, d_nodes, d_nodes_ptr, nodes_len, flags, d_out, d_out_ptr, d_ids, ids_cap,
+                      d_ids_ptr};
+    SnapshotSubReport rep;
+    const int rc = snapshot_subgraph_run(h->stream, base, have, a, &rep);
+    if (h_info) {
+        h_info->rows_kept = rep.kept; h_info->ids_written = rep.ids; h_info->arena_bytes = (int64_t)need; h_info->host_syncs = rep.host_syncs;
     }
     return rc;
 }

@@ -829,6 +829,110 @@ def ppr_diffusion(
         return out[:, :2].long().t().contiguous(), out[:, 2].contiguous()
 
 
+def _subgraph_args(sc: Tensor, ptr, num_nodes: int, nodes, nodes_ptr, node_ptr):
+    """Host-side checks of snapshot_subgraph, made before anything is launched: (ptr, node_ptr, nodes, nodes_ptr), the tables as
+    int64 CPU tensors, `nodes` as given (a tensor, on its device) or made from a sequence."""
+    try:
+        single = len(ptr) == 1
+    except TypeError:
+        single = False
+    if single:
+        # S = 0: no segment at all (ptr == [0], no rows); sc, num_nodes and node_ptr keep their rules
+        rows = int(sc.shape[0]) if isinstance(sc, Tensor) and sc.dim() == 2 else 0
+        _snapshot_args(sc, [0, rows], num_nodes, None, 1.0, 1)
+        p = _int_tensor(ptr, "ptr").reshape(-1).contiguous()
+        if p.numel() != 1 or int(p[0]) != 0 or rows != 0:
+            raise ValueError("ptr: a single offset describes no segment and needs ptr == [0] and no rows")
+        np_ = _ptr_table(node_ptr, "node_ptr", 0, num_nodes.__index__()) if node_ptr is not None else None
+    else:
+        p, np_ = _snapshot_args(sc, ptr, num_nodes, node_ptr, 1.0, 1)
+    S = p.numel() - 1
+    if nodes is None:
+        if nodes_ptr is not None:
+            raise ValueError("nodes_ptr: only together with nodes")
+        return p, np_, None, None
+    if isinstance(nodes, Tensor):
+        if nodes.dtype.is_floating_point or nodes.dtype.is_complex or nodes.dtype == torch.bool:
+            raise ValueError("nodes: integers only")
+        nd = nodes.detach()
+    else:
+        nd = _int_tensor(nodes, "nodes")
+    if nd.dim() != 1:
+        raise ValueError("nodes: a 1-D tensor of node ids")
+    q = None
+    if nodes_ptr is not None:
+        q = _ptr_table(nodes_ptr, "nodes_ptr", 0, int(nd.numel())) if S > 0 else _int_tensor(nodes_ptr, "nodes_ptr")
+        if q.dim() != 1 or q.numel() != S + 1:
+            raise ValueError(f"nodes_ptr: {S + 1} offsets (one list per segment), got {tuple(q.shape)}")
+        if S == 0 and (int(q[0]) != 0 or nd.numel() != 0):
+            raise ValueError("nodes_ptr: non-decreasing offsets from 0 to len(nodes)")
+    return p, np_, nd, q
+
+
+def snapshot_subgraph(
+    sc: Tensor,
+    ptr: Union[Tensor, Sequence[int]],
+    num_nodes: int,
+    nodes: Optional[Union[Tensor, Sequence[int]]] = None,
+    nodes_ptr: Optional[Union[Tensor, Sequence[int]]] = None,
+    node_ptr: Optional[Union[Tensor, Sequence[int]]] = None,
+    relabel: bool = False,
+    remove_self_loops: bool = False,
+) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """The induced subgraph of every snapshot on a node set, optionally with compact ids -- the torch.unique + subgraph(...,
+    relabel_nodes=True) step of the reference's scripts (scripts/rlap_vc_spectral.py:42-51, scripts/augmentor_benchmarks.py:121-171,
+    scripts/rlap_ppr_edge_plots.py:61-76) for all snapshots of one call, on the device and without a sort.  `sc`, `ptr`, `num_nodes`
+    and `node_ptr` as for snapshot_stats, but the rows of a segment may come in any order and need not be symmetric: the result of
+    every elimination entry point, of snapshot_ppr, or a plain edge list.  ptr == [0] (no segment) is allowed.
+
+    Node sets: `nodes=None` takes the ids that appear in the segment's rows (torch.unique of the snapshot).  `nodes` with
+    `nodes_ptr` (S+1 offsets) is one list per segment, `nodes` alone one list for all segments (with `node_ptr` a segment takes the
+    part of the list inside its graph's range).  Lists are sets: any order, repeats allowed, and an id that no row has still takes a
+    label.  `remove_self_loops` drops the rows with i == j, and with nodes=None they do not put i into the set (remove_self_loops
+    before unique).  `relabel` replaces the ids of the kept rows by their rank among the sorted ids of the set, from 0 in every
+    segment -- PyG's relabel_nodes=True for a sorted, distinct subset such as a torch.unique result.
+
+    Returns (out, optr, ids, iptr) on sc's device: out[optr[s]:optr[s+1]] the kept rows of segment s in their input order, the weight
+    column copied bit for bit; ids[iptr[s]:iptr[s+1]] its node set, sorted -- the map label -> id.  The same input gives the same
+    bits.  Malformed tables, or an id of a row or list outside its segment's range, raise ValueError.  `last_stats` then holds what the
+    call did (rlap_subgraph_info: rows_kept, ids_written, arena_bytes, host_syncs).
+    """
+    p, np_, nd, q = _subgraph_args(sc, ptr, num_nodes, nodes, nodes_ptr, node_ptr)
+    global last_stats
+    S = p.numel() - 1
+    n = int(num_nodes)
+    dev = _device_for(sc)
+    lib, hobj = _handle_obj(dev)
+    h = hobj.ptr
+    flags = (_lib.SUB_RELABEL if relabel else 0) | (_lib.SUB_NO_SELF_LOOPS if remove_self_loops else 0)
+    with torch.cuda.device(dev):
+        x = sc.to(device=dev, dtype=torch.float64).contiguous()
+        m = int(x.shape[0])
+        d_ptr = p.to(dev)
+        d_np = np_.to(dev) if np_ is not None else None
+        G = np_.numel() - 1 if np_ is not None else 1
+        d_nd = nd.to(device=dev, dtype=torch.int64).contiguous() if nd is not None else None
+        d_q = q.to(dev) if q is not None else None
+        L = len(d_nd) if d_nd is not None else 0
+        cap = min(2 * m, (S // G) * n) if d_nd is None else (L if d_q is not None else (S // G) * L)
+        out = torch.empty((m, 3), dtype=torch.float64, device=dev)
+        optr = torch.empty(S + 1, dtype=torch.int64, device=dev)
+        ids = torch.empty(cap, dtype=torch.int64, device=dev)
+        iptr = torch.empty(S + 1, dtype=torch.int64, device=dev)
+        info = _lib.SubgraphInfo()
+        st = _lib.Stats()
+        rc = _run(hobj, dev, m, None, G, False, lambda: lib.rlap_snapshot_subgraph(
+            h, x.data_ptr() if m else None, m, d_ptr.data_ptr(), S, d_np.data_ptr() if d_np is not None else None, G, n,
+            (d_nd.data_ptr() or iptr.data_ptr()) if d_nd is not None else None,   # (an empty list is still a list: not NULL)
+            d_q.data_ptr() if d_q is not None else None, L,
+            flags, out.data_ptr() if m else None, optr.data_ptr(), ids.data_ptr() if cap else None, cap, iptr.data_ptr(),
+            ctypes.byref(info)), st)
+        if rc != 0:
+            _raise(rc)
+        last_stats = info.as_dict()
+        return _trim(out, int(info.rows_kept)), optr, _trim(ids, int(info.ids_written)), iptr
+
+
 def identity(a: Tensor) -> Tensor:
     """Boundary self-test (reference: rlap/ops.py:61-63): tensor -> column-major
     staging -> tensor, on the GPU; returns a tensor on `a`'s device."""
