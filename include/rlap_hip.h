@@ -322,6 +322,47 @@ int rlap_snapshot_subgraph(rlap_handle h, const double* d_sc, int64_t m, const i
                            int flags, double* d_out, int64_t* d_out_ptr, int64_t* d_ids, int64_t ids_cap, int64_t* d_ids_ptr,
                            rlap_subgraph_info* h_info);
 
+/* Encoder-ready snapshots: for every segment s (described as for rlap_snapshot_stats: d_sc, m, d_ptr, S, d_node_ptr, G, num_nodes,
+ * and in the same layout: the rows of a segment grouped by column id, every row id with a column block of its own -- the result of
+ * every elimination entry point) the int64 edge_index, the self loops and the coefficients of PyG's
+ * gcn_norm(edge_index, edge_weight, num_nodes, improved, add_self_loops, flow="source_to_target") for
+ * edge_index = sc[:, :2].long().t(): row id = source, column id = target.  (Unpinned: PyG's published semantics, not a run of it.)
+ * With [lo, hi) the id range of segment s and n_s = hi - lo:
+ *   RLAP_GCN_WEIGHTED   : the rows' weights; without it every row weighs 1
+ *   RLAP_GCN_SELF_LOOPS : add_remaining_self_loops -- the rows with row == col leave the list, the others keep their input order,
+ *                         then one loop (i, i) for every i in [lo, hi) ascending follows.  The loop of i weighs fill_value (1; 2 is
+ *                         PyG's improved=True) unless the segment had loop rows of i: then the weight of the last of them in input
+ *                         order (1 when unweighted).  Segment s has rows_s - loops_s + n_s entries.  Without the flag the list is
+ *                         the rows as they are, loop rows included.
+ *   RLAP_GCN_NORMALIZE  : deg[i] = the sum of the weights of the list's entries whose target is i (a column block and the loop),
+ *                         dis[i] = deg[i]^-1/2, 0 where deg[i] == 0; the value of entry (i, j, w) is dis[i] * w * dis[j].  Without
+ *                         the flag the value is w itself: the call is the conversion alone, plus the loops if asked for.
+ *   RLAP_GCN_F32        : d_val is float32 (the float64 value rounded once); else float64
+ *   d_src, d_dst, d_val : [cap] each, the two rows of edge_index and the values, segment-major; ids stay in the input's id space
+ *   cap                 : at least m + (S / G) num_nodes with RLAP_GCN_SELF_LOOPS, m without; entries <= cap are written, and
+ *                         entries == cap whenever the input has no loop rows (every elimination result)
+ *   d_eptr              : [S+1] entry offsets of the segments
+ *   h_info              : (nullable) what the call did
+ * num_nodes may exceed the elimination's (ids without rows are legal: eliminated vertices, trailing isolated nodes); their loop has
+ * degree fill_value.  Every degree is summed in one fixed order that depends on the row's place in its block only, without atomics:
+ * the same input gives the same bits, and a segment's values do not depend on the other segments of the call.  Layout errors as for
+ * rlap_snapshot_stats; a bad ptr / node_ptr, cap below the bound, a fill_value that is not finite or <= 0 with RLAP_GCN_SELF_LOOPS, or
+ * with RLAP_GCN_WEIGHTED and RLAP_GCN_NORMALIZE a weight that is not finite or <= 0 (PyG would return NaN): RLAP_E_BAD_ARG.  Not in
+ * this layout: the (out, out_ptr) of rlap_snapshot_ppr (grouped by row id) and arbitrary edge lists.  Scratch from the arena
+ * (RLAP_E_WORKSPACE when a caller-provided one is too small, rlap_workspace_needed() saying how much).  One host synchronisation. */
+enum { RLAP_GCN_WEIGHTED = 1, RLAP_GCN_SELF_LOOPS = 2, RLAP_GCN_NORMALIZE = 4, RLAP_GCN_F32 = 8 };
+typedef struct {
+    int64_t entries;          /* entries written to d_src / d_dst / d_val        */
+    int64_t loops_removed;    /* loop rows of the input that left the list        */
+    int64_t arena_bytes;      /* scratch bytes of the call                        */
+    int32_t host_syncs;       /* host synchronisations of the call                */
+    int32_t pad;
+} rlap_gcn_info;
+
+int rlap_snapshot_gcn_norm(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
+                           int64_t G, int64_t num_nodes, int flags, double fill_value, int64_t* d_src, int64_t* d_dst, void* d_val,
+                           int64_t cap, int64_t* d_eptr, rlap_gcn_info* h_info);
+
 /* The op with the step BEFORE the path fused in (scripts/node_shared.py:326-327,
  * scripts/augmentor_benchmarks.py:77-78):
  *   symmetrize != 0 : the input holds every undirected edge in one or both directions; (b,a) is

@@ -9,6 +9,8 @@ Mirrors of the reference's L2 adapters that keep everything on the GPU:
                   (the sweeps of scripts/rlap_vc_spectral.py, scripts/rlap_ppr_edge_plots.py); `.diffuse`
                   gives their PPR diffusions from one ops.snapshot_ppr call, `.relabelled` their compact graphs and id maps and
                   `.batch_edge_counts` the batch subgraph sizes from ops.snapshot_subgraph
+  * `gcn_norm=True` on rLap / rLapViews / rLapDepths: the graphs come with self loops and GCN coefficients from one
+                  ops.snapshot_gcn_norm call, for GCNConv(..., normalize=False)
   * `rLapChain` -- the chain of scripts/rlap_vc_spectral.py: eliminate, relabel the survivors 0..k-1, eliminate again
 PyGCL / DGL are optional: with them installed the classes return their graph types,
 without them a small named tuple with the same fields.
@@ -42,7 +44,7 @@ class rLap:
     """
 
     def __init__(self, frac: float, o_v: str = "random", o_n: str = "asc", keep_weights: bool = False, seed: Optional[int] = None,
-                 num_nodes_from_x: bool = False, symmetrize: bool = False):
+                 num_nodes_from_x: bool = False, symmetrize: bool = False, gcn_norm: bool = False, fill_value: float = 1.0):
         self.frac = frac
         self.o_v = o_v
         self.o_n = o_n
@@ -50,11 +52,14 @@ class rLap:
         self.seed = seed
         self.num_nodes_from_x = num_nodes_from_x
         self.symmetrize = symmetrize      # True: one-directional input is made undirected inside the op (fused to_undirected)
+        self.gcn_norm, self.fill_value = gcn_norm, fill_value   # True: self loops and GCN coefficients (_gcn_graphs)
 
     def augment(self, g):
         x, edge_index, edge_weights = g.unfold() if hasattr(g, "unfold") else g
         sc, num_nodes = _schur(edge_index, edge_weights, x, self.frac, self.o_v, self.o_n, self.seed, self.num_nodes_from_x, self.symmetrize)
         self.num_remove = int(self.frac * num_nodes)
+        if self.gcn_norm:
+            return _gcn_graphs(x, sc, [0, int(sc.shape[0])], num_nodes, self.keep_weights, self.fill_value)[0]
         sampled_edge_index = sc[:, :2].long().t().contiguous()          # stays on the device
         w = sc[:, 2].contiguous() if self.keep_weights else None
         try:  # PyGCL present: return its Graph type
@@ -75,6 +80,17 @@ def _as_graph(x, edge_index, w):
         return Graph(x, edge_index, w)
 
 
+def _gcn_graphs(x, sc, ptr, num_nodes, keep_weights, fill_value):
+    """The snapshots of one call as GCNConv(..., normalize=False) takes them, from ONE ops.snapshot_gcn_norm call: for every segment
+    Graph(x, edge_index, edge_weights) with the self loops in edge_index (int64) and the float32 coefficients deg^-1/2 w deg^-1/2 as
+    edge_weights -- weighted iff keep_weights.  The loops cover x.shape[0] nodes when x is given (what GCNConv uses), else the call's
+    num_nodes.  Segment s is a slice of the call's one (2, M) tensor: nothing is copied."""
+    n = int(x.shape[0]) if x is not None else int(num_nodes)
+    ei, w, eptr = ops.snapshot_gcn_norm(sc, ptr, n, weighted=keep_weights, fill_value=fill_value)
+    e = eptr.tolist()
+    return [_as_graph(x, ei[:, e[i]:e[i + 1]], w[e[i]:e[i + 1]]) for i in range(len(e) - 1)]
+
+
 class rLapViews:
     """K views of a graph from ONE call of ops.approximate_cholesky_views (setup once, K eliminations side by side).
 
@@ -84,10 +100,11 @@ class rLapViews:
     """
 
     def __init__(self, fracs=(0.5, 0.5), o_v: str = "random", o_n: str = "asc", keep_weights: bool = False, seed: Optional[int] = None,
-                 mode: str = "exact"):
+                 mode: str = "exact", gcn_norm: bool = False, fill_value: float = 1.0):
         self.fracs = tuple(float(f) for f in fracs)
         assert len(self.fracs) >= 1
         self.o_v, self.o_n, self.keep_weights, self.seed, self.mode = o_v, o_n, keep_weights, seed, mode
+        self.gcn_norm, self.fill_value = gcn_norm, fill_value   # True: self loops and GCN coefficients (_gcn_graphs)
         self._pending = None   # (input key, list of K graphs, list of views not yet handed out)
 
     def augment(self, g):
@@ -96,6 +113,8 @@ class rLapViews:
         self.num_remove = [int(f * num_nodes) for f in self.fracs]
         sc, ptr = ops.approximate_cholesky_views(edge_index, edge_weights, num_nodes, self.num_remove, self.o_v, self.o_n,
                                                  seed=self.seed, return_device="same", mode=self.mode)
+        if self.gcn_norm:
+            return _gcn_graphs(x, sc, ptr, num_nodes, self.keep_weights, self.fill_value)
         out = []
         for k in range(len(self.fracs)):
             part = sc[int(ptr[k]):int(ptr[k + 1])]
@@ -139,11 +158,12 @@ class rLapDepths:
     """
 
     def __init__(self, fracs=(0.1, 0.2, 0.3), o_v: str = "random", o_n: str = "asc", keep_weights: bool = False, seed: Optional[int] = None,
-                 mode: str = "exact", views: Optional[int] = None):
+                 mode: str = "exact", views: Optional[int] = None, gcn_norm: bool = False, fill_value: float = 1.0):
         self.fracs = tuple(float(f) for f in fracs)
         assert len(self.fracs) >= 1
         assert views is None or (int(views) == views and views >= 1), "views: None or a positive int"
         self.o_v, self.o_n, self.keep_weights, self.seed, self.mode, self.views = o_v, o_n, keep_weights, seed, mode, views
+        self.gcn_norm, self.fill_value = gcn_norm, fill_value   # True: self loops and GCN coefficients (_gcn_graphs)
 
     def _snapshots(self, g):
         x, edge_index, edge_weights = g.unfold() if hasattr(g, "unfold") else g
@@ -237,6 +257,8 @@ class rLapDepths:
             part = sc[int(ptr[i]):int(ptr[i + 1])]
             ei = part[:, :2].long().t().contiguous()
             return _as_graph(x, ei, part[:, 2].contiguous() if self.keep_weights else None)
+        if self.gcn_norm:   # (one call for all snapshots; the same order)
+            graph = _gcn_graphs(x, sc, ptr, num_nodes, self.keep_weights, self.fill_value).__getitem__
         K = len(self.fracs)
         if self.views is None:
             return [graph(k) for k in range(K)]

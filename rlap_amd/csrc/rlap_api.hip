@@ -21,6 +21,7 @@
 #include "rlap_ppr.h"
 #include "rlap_stats.h"
 #include "rlap_subgraph.h"
+#include "rlap_gcn.h"
 
 using namespace rlap;
 
@@ -1344,6 +1345,42 @@ int rlap_snapshot_subgraph(rlap_handle h, const double* d_sc, int64_t m, const i
     const int rc = snapshot_subgraph_run(h->stream, base, have, a, &rep);
     if (h_info) {
         h_info->rows_kept = rep.kept; h_info->ids_written = rep.ids; h_info->arena_bytes = (int64_t)need; h_info->host_syncs = rep.host_syncs;
+    }
+    return rc;
+}
+
+int rlap_snapshot_gcn_norm(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
+                           int64_t G, int64_t num_nodes, int flags, double fill_value, int64_t* d_src, int64_t* d_dst, void* d_val,
+                           int64_t cap, int64_t* d_eptr, rlap_gcn_info* h_info) {
+    if (h_info) *h_info = rlap_gcn_info{};
+    if (!h || !d_ptr || S < 1 || m < 0 || num_nodes < 0 || (m > 0 && !d_sc) || !d_eptr || cap < 0) return RLAP_E_BAD_ARG;
+    if (flags & ~(RLAP_GCN_WEIGHTED | RLAP_GCN_SELF_LOOPS | RLAP_GCN_NORMALIZE | RLAP_GCN_F32)) return RLAP_E_BAD_ARG;
+    if ((flags & RLAP_GCN_SELF_LOOPS) && !(fill_value > 0.0 && std::isfinite(fill_value))) return RLAP_E_BAD_ARG;
+    if (d_node_ptr ? (G < 1 || S % G != 0) : false) return RLAP_E_BAD_ARG;
+    if (!d_node_ptr) G = 1;
+    if (m >= INT32_MAX || S >= (int64_t)1 << 30 || num_nodes >= INT32_MAX) return RLAP_E_TOO_LARGE;
+    if ((S / G) * num_nodes >= (int64_t)1 << 40) return RLAP_E_TOO_LARGE;
+    const int64_t cap_need = snapshot_gcn_cap(m, S, G, num_nodes, flags);
+    if (cap < cap_need || (cap_need > 0 && (!d_src || !d_dst || !d_val))) return RLAP_E_BAD_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device);
+    const size_t need = snapshot_gcn_bytes(m, S, G, num_nodes);
+    h->ws_needed = need;
+    void* base = nullptr;
+    size_t have = 0;
+    if (h->ext_ws) {
+        if (need > h->ext_ws_bytes) return RLAP_E_WORKSPACE;
+        base = h->ext_ws; have = h->ext_ws_bytes;
+    } else {
+        ENSURE(h->own_ws, need);
+        base = h->own_ws.p; have = h->own_ws.cap;
+    }
+    SnapshotGcnArgs a{d_sc, m, d_ptr, S, d_node_ptr, G, num_nodes, flags, fill_value, d_src, d_dst, d_val, d_eptr};
+    SnapshotGcnReport rep;
+    const int rc = snapshot_gcn_run(h->stream, base, have, a, &rep);
+    if (h_info) {
+        h_info->entries = rep.entries; h_info->loops_removed = rep.loops_removed; h_info->arena_bytes = (int64_t)need;
+        h_info->host_syncs = rep.host_syncs;
     }
     return rc;
 }

@@ -933,6 +933,80 @@ def snapshot_subgraph(
         return _trim(out, int(info.rows_kept)), optr, _trim(ids, int(info.ids_written)), iptr
 
 
+def snapshot_gcn_norm(
+    sc: Tensor,
+    ptr: Union[Tensor, Sequence[int]],
+    num_nodes: int,
+    node_ptr: Optional[Union[Tensor, Sequence[int]]] = None,
+    weighted: bool = False,
+    add_self_loops: bool = True,
+    fill_value: float = 1.0,
+    normalize: bool = True,
+    dtype: torch.dtype = torch.float32,
+) -> Tuple[Tensor, Tensor, Tensor]:
+    """Every snapshot of a call as the encoder eats it: the int64 `edge_index`, the self loops and the symmetric normalisation
+    coefficients -- sc[:, :2].long().t().contiguous() followed by what GCNConv does first with every view (PyG's gcn_norm:
+    add_remaining_self_loops, the degree scatter, deg^-1/2, one product per edge; scripts/node_shared.py:242-245), for all
+    snapshots at once, in one pass over the rows and without float atomics.  `sc`, `ptr`, `num_nodes` and `node_ptr` as for
+    snapshot_stats, in the same layout (rows of a segment grouped by column id, every row id with a column block of its own: the
+    result of every elimination entry point).  The (out, pptr) of snapshot_ppr (grouped by row id) and arbitrary edge lists are not
+    in that layout and are refused or out of scope.  `num_nodes` may exceed the elimination's (eliminated and isolated ids get a loop).
+
+    Row id = source, column id = target, as gcn_norm(flow="source_to_target") reads edge_index = sc[:, :2].long().t().  (Unpinned: PyG
+    is not installed here; this follows its published semantics, not a run of it.)  Per segment s with id range [lo, hi):
+      weighted        : the rows' weights, else every row weighs 1 (the reference's rLap returns edge_weights=None)
+      add_self_loops  : rows with row == col leave the list, the others keep their input order, then one loop (i, i) for every i in
+                        [lo, hi) ascending; it weighs `fill_value` (2.0 is PyG's improved=True) unless the segment had loop rows of i:
+                        then the last one's weight (1 when unweighted).  False: the rows as they are
+      normalize       : value (i, j, w) = dis[i] * w * dis[j], dis = deg^-1/2 (0 where deg == 0), deg[j] the sum of the weights of the
+                        entries whose target is j.  False: w itself -- the call is then the conversion alone, plus loops if asked
+      dtype           : torch.float32 (the float64 value rounded once) or torch.float64
+
+    Returns (edge_index, weight, eptr) on sc's device: ONE contiguous (2, M) int64 tensor, the (M,) values and the S+1 entry offsets;
+    snapshot s is edge_index[:, eptr[s]:eptr[s+1]], weight[eptr[s]:eptr[s+1]] -- feed it to GCNConv(..., normalize=False).  The same
+    input gives the same bits, and a segment's values do not depend on the other segments of the call.  Malformed tables, a layout
+    error, or (weighted and normalize) a weight that is not finite or <= 0 raise ValueError.  `last_stats` then holds what the call did
+    (rlap_gcn_info: entries, loops_removed, arena_bytes, host_syncs).
+    """
+    p, np_ = _snapshot_args(sc, ptr, num_nodes, node_ptr, 1.0, 1)
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"dtype: torch.float32 or torch.float64, got {dtype!r}")
+    fill = _real(fill_value, "fill_value", 0.0, float("inf"))
+    global last_stats
+    S = p.numel() - 1
+    n = int(num_nodes)
+    dev = _device_for(sc)
+    lib, hobj = _handle_obj(dev)
+    h = hobj.ptr
+    flags = ((_lib.GCN_WEIGHTED if weighted else 0) | (_lib.GCN_SELF_LOOPS if add_self_loops else 0)
+             | (_lib.GCN_NORMALIZE if normalize else 0) | (_lib.GCN_F32 if dtype == torch.float32 else 0))
+    with torch.cuda.device(dev):
+        x = sc.to(device=dev, dtype=torch.float64).contiguous()
+        m = int(x.shape[0])
+        d_ptr = p.to(dev)
+        d_np = np_.to(dev) if np_ is not None else None
+        G = np_.numel() - 1 if np_ is not None else 1
+        cap = m + ((S // G) * n if add_self_loops else 0)
+        ei = torch.empty((2, cap), dtype=torch.int64, device=dev)
+        val = torch.empty(cap, dtype=dtype, device=dev)
+        eptr = torch.empty(S + 1, dtype=torch.int64, device=dev)
+        info = _lib.GcnInfo()
+        st = _lib.Stats()
+        rc = _run(hobj, dev, m, None, G, False, lambda: lib.rlap_snapshot_gcn_norm(
+            h, x.data_ptr() if m else None, m, d_ptr.data_ptr(), S, d_np.data_ptr() if d_np is not None else None, G, n, flags, fill,
+            ei[0].data_ptr() if cap else None, ei[1].data_ptr() if cap else None, val.data_ptr() if cap else None, cap,
+            eptr.data_ptr(), ctypes.byref(info)), st)
+        if rc == _lib.E_NOT_GROUPED:
+            raise ValueError(f"rlap: {_lib.status_string(rc)}")
+        if rc != 0:
+            _raise(rc)
+        last_stats = info.as_dict()
+        M = int(info.entries)
+        if M != cap:   # (only an input with loop rows: the two rows of edge_index move together)
+            ei, val = ei[:, :M].contiguous(), val[:M].clone()
+        return ei, val, eptr
+
+
 def identity(a: Tensor) -> Tensor:
     """Boundary self-test (reference: rlap/ops.py:61-63): tensor -> column-major
     staging -> tensor, on the GPU; returns a tensor on `a`'s device."""
