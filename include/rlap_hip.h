@@ -76,7 +76,8 @@ typedef struct {
                              7 dataflow reorder buffer too small, 8 the dataflow kernel gave up); 7 and 8 repeat on the round kernel */
     int32_t flow_abort;   /* why the dataflow kernel gave up (retry kind 8): 0 it did not, 1 stall watchdog, 2 sorted-index check,
                              3 appended count over 2^22, 4 column longer than its buffer */
-    int32_t pad;          /* (8-byte alignment) */
+    int32_t n_rounds_narrow; /* degree order: the part of n_rounds that the 16-slot round kernel ran before it handed over to the
+                             32-slot one (0: it was not used, or the first column was already longer than 16 slots) */
 } rlap_stats;
 
 /* Lifetime.  A handle binds to the HIP device current at creation.  It owns a few KB of tables (allocated in

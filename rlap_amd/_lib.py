@@ -49,7 +49,7 @@ class Stats(ctypes.Structure):
         ("ms_sc_merge", ctypes.c_float), ("ms_sc_compact", ctypes.c_float), ("ms_total", ctypes.c_float),
         ("n_retries", ctypes.c_int32), ("reserved", ctypes.c_int32),
         ("n_rounds", ctypes.c_int64), ("n_singles", ctypes.c_int64),
-        ("elim_kernel", ctypes.c_int32), ("retry_causes", ctypes.c_int32), ("flow_abort", ctypes.c_int32), ("pad", ctypes.c_int32),
+        ("elim_kernel", ctypes.c_int32), ("retry_causes", ctypes.c_int32), ("flow_abort", ctypes.c_int32), ("n_rounds_narrow", ctypes.c_int32),
     ]
 
     def as_dict(self):

@@ -670,11 +670,13 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
     ES.prof = nullptr;
     const char* prof_env = std::getenv("RLAP_PHASE_PROFILE");   // diagnostic only: per-phase clock sums of graph 0
     if (prof_env && prof_env[0] == '1' && h->prof.p) {
-        HIPCHK(hipMemsetAsync(h->prof.p, 0, 8 * 40, s));
+        HIPCHK(hipMemsetAsync(h->prof.p, 0, 8 * 80, s));
         ES.prof = h->prof.as<long long>();
     }
     ES.poison = h->poison;
     ES.jitter = h->jitter;
+    ES.narrow_batch = NARROW_BATCH;
+    if (const char* e = std::getenv("RLAP_NARROW_BATCH")) ES.narrow_batch = std::min(256, std::max(1, std::atoi(e)));   // diagnostic override
 
     if (h->timing) HIPCHK(hipEventRecord(h->ev[1], s));
     // ---------------- elimination ----------------
@@ -865,8 +867,14 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
         std::fprintf(stderr, "  long columns: %lld (mean live %.0f, max %lld; %lld beyond 900, %lld beyond 1888, %lld beyond 3320 taking %.3f of %.3f ms)\n", pr[36], pr[36] ? (double)pr[37] / pr[36] : 0.0, pr[35], pr[38], pr[39], pr[32], pr[33] / 1e5, pr[34] / 1e5);
         for (int k = 1; k < 11; ++k) std::fprintf(stderr, "    %-32s %10.3f ms total  %8.2f us/col\n", names[k], pr[20 + k] / 1e5, pr[36] ? pr[20 + k] / 100.0 / (double)pr[36] : 0.0);
     } else if (ES.prof) {
-        long long pr[40];
-        HIPCHK(hipMemcpy(pr, h->prof.p, sizeof(pr), hipMemcpyDeviceToHost));
+        long long pr2[80];
+        HIPCHK(hipMemcpy(pr2, h->prof.p, sizeof(pr2), hipMemcpyDeviceToHost));
+        // two blocks: the 32/64/128-slot round kernel, then the 16-slot one of the degree order (printed first: it runs first)
+        for (int blk = 1; blk >= 0; --blk) {
+        const long long* pr = pr2 + 40 * blk;
+        if (blk == 1 && pr[21] == 0) continue;
+        if (blk == 1) std::fprintf(stderr, "[rlap phase profile] 16-slot round kernel:\n");
+        else if (pr2[40 + 21] != 0) std::fprintf(stderr, "[rlap phase profile] 32-slot round kernel behind it:\n");
         const char* names[20] = {"P0 select", "P1 permute + closing barrier", "P1b multi-edge cut + P2 offsets", "P3 sample", "P4 replay", "single path", "P5b slots + shared targets", "move order", "pushes", "P1 meta + loads + dependence", "P5a cursors + pool", "P5c rewire stores", "P1 id rank", "P1 (sync)", "P1 o_n order (sorts)", "P1 write pass", "P1 (sync)", "P1 o_n rank", "empty (cost of one stamp)", "P3b dependent candidates (patch)"};
         std::fprintf(stderr, "[rlap phase profile] rounds=%lld singles=%lld (100 MHz ticks); shader clock over the kernel: %.0f MHz\n", pr[22], pr[23], pr[21] > 0 ? 100.0 * (double)pr[20] / (double)pr[21] : 0.0);
         for (int k = 0; k < 20; ++k) std::fprintf(stderr, "  %-22s %10.3f ms\n", names[k], pr[k] / 1e5);
@@ -874,11 +882,12 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
         for (int k = 0; k < 9; ++k) std::fprintf(stderr, "  single/wave: %-20s %10.3f ms\n", wnames[k], pr[24 + k] / 1e5);
         const char* xnames[5] = {"P4.1 hash insert + key loads", "P4.2 replay (uncontended)", "P4.3 sort of the contended records", "P4.4 contended walk", "P5b uncontended slots (rest of P5b = contended walk)"};
         for (int k = 0; k < 5; ++k) std::fprintf(stderr, "  detail: %-52s %10.3f ms\n", xnames[k], pr[33 + k] / 1e5);
+        }
     }
 
     st.nnz = R.nnz;
     st.n_draws = R.n_draws;
-    st.n_rounds = R.rounds; st.n_singles = R.singles;
+    st.n_rounds = R.rounds; st.n_singles = R.singles; st.n_rounds_narrow = R.rounds_narrow;
     const int64_t m_total = depths ? out_ptr_h[nseg * G] : R.m_total;   // (depths: the rows of all snapshots)
     st.out_rows = m_total;
     st.live_entries = R.live_total;
@@ -1006,7 +1015,7 @@ static int create_into(rlap_handle h) {
     HIPCHK(hipStreamSynchronize(h->side[0]));
     HIPCHK(hipHostMalloc(&h->h_results, 1 << 17, hipHostMallocDefault));
     h->h_results_cap = 1 << 17;
-    if (const char* e = std::getenv("RLAP_PHASE_PROFILE")) { if (e[0] == '1') ENSURE(h->prof, 8 * 40); }
+    if (const char* e = std::getenv("RLAP_PHASE_PROFILE")) { if (e[0] == '1') ENSURE(h->prof, 8 * 80); }
     if (const char* e = std::getenv("RLAP_DEBUG_POISON")) { if (e[0]) h->poison = std::atoi(e) & 0xFF; }
     if (const char* e = std::getenv("RLAP_DEBUG_JITTER")) { if (e[0]) h->jitter = std::max(0, std::min(64, std::atoi(e))); }
     return RLAP_OK;

@@ -322,7 +322,12 @@ struct GraphDesc {      // one per graph of a batch
     int64_t n_draws;
     int64_t out_rows;   // rows this graph emits (filled by the output pass)
     int32_t flow_base;  // dataflow elimination (rlap_flow.h): look-back index of this graph's sentinel; its positions follow
-    int32_t resume;     // 0: the round kernel starts at position 0; 1: a later segment of a depths call, continuing from n_elim
+    int32_t resume;     // 0: the round kernel starts at position 0; 1: continue from n_elim (a later segment of a depths call, or the
+                        // 32-slot round kernel behind the 16-slot one of the degree order)
+    int32_t narrow;     // degree order: 1 once the 16-slot round kernel has handed over to the 32-slot one (one way; later segments skip it)
+    int32_t narrow_rounds;   // rounds the 16-slot round kernel ran (part of pad0)
+    int32_t pool_cur;   // append-pool reservation the round kernel held when it ended, [pool_cur, pool_end): the launch that resumes
+    int32_t pool_end;   // takes it over, so that neither a hand-over nor a segment boundary loses slots
 };
 
 struct ColBuf {         // working storage for one column (LDS or global scratch)
@@ -677,7 +682,7 @@ enum { CF_BIG = 1, CF_DUP = 2, CF_COMPLEX = 4, CF_DEP = 8, CF_TIE = 16, CF_NEQ =
 constexpr int DEPMAX = 4;   // dependent candidates with more earlier neighbours in the round than this cut it
 enum { TF_CONTENDED = 1 };
 
-// BC = live entries a candidate may hold (32: one half-wave per candidate, 64: one wave, 128: one wave, two entries per lane).
+// BC = live entries a candidate may hold (16: a quarter-wave per candidate, 32: half a wave, 64: one wave, 128: one wave, two entries per lane).
 template <int BC> struct CandPad {};
 template <> struct CandPad<64> { int64_t pad64; };   // keeps the LDS stride of CandT<64> off the 64-bank period
 template <> struct CandPad<128> { int64_t pad128; };
@@ -697,11 +702,12 @@ struct CandT : CandPad<BC> {
     int32_t ext;      // slots to read (appended + CSR), dead ones included
     int32_t nmv;      // PQ moves this candidate causes (counted during the replay; bounds the round's move list)
     int32_t nkill;    // merged multi-edges (o_v = random, 64-slot form): e[m .. m+nkill) hold the twins that die (:289)
-    int32_t cb[BC <= 32 ? 3 : (BC <= 64 ? 4 : 5)];   // bases of the appended chunks (chunk_of(BC - 1) + 1)
+    int32_t cb[BC <= 16 ? 2 : (BC <= 32 ? 3 : (BC <= 64 ? 4 : 5))];   // bases of the appended chunks (chunk_of(BC - 1) + 1)
     int32_t ndep;     // earlier candidates of the round this one is adjacent to (cand_patch), at most DEPMAX
     uint8_t dep[4];
     int64_t draw0;    // first uniform
-};   // 872 B (BC=32) / 1688 B (BC=64) / 3288 B (BC=128): word strides 218 / 422 / 822
+};   // 472 B (BC=16) / 872 B (BC=32) / 1688 B (BC=64) / 3288 B (BC=128): word strides 118 / 218 / 422 / 822
+static_assert(sizeof(CandT<16>) == 472 && sizeof(CandT<32>) == 872, "record sizes the LDS budget of the round kernel is counted with");
 typedef CandT<BCAP> Cand;
 
 RLAP_HD TRes& ent_tres(Ent& e) { return e.res; }
@@ -762,7 +768,7 @@ RLAP_HD void cand_meta(const Arrays& A, int32_t v, CT& C) {
     C.cp1 = cp1; C.acnt = acnt; C.ext = (cp1 - cp0) + acnt;
     if (C.ext > CT::CAP) { C.flags = CF_BIG; C.ext = 0; return; }
     if (acnt > 0) {
-        int ct = chunk_of(acnt - 1);            // <= 2 (CAP 32) / <= 3 (CAP 64) / <= 4 (CAP 128) because acnt <= CAP
+        int ct = chunk_of(acnt - 1);            // <= 1 (CAP 16) / <= 2 (CAP 32) / <= 3 (CAP 64) / <= 4 (CAP 128) because acnt <= CAP
         for (int c = ct; c >= 0; --c) { C.cb[c] = base; if (c > 0) base = A.e[base].nbr; }
     }
 }

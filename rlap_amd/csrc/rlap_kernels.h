@@ -21,7 +21,8 @@ struct CallResults {
     int64_t n_draws, rounds, singles;
     int64_t live_total, scr_need, ext_total, m_total;
     int32_t pool_used, log_used;
-    int32_t flow_abort, pad;   // dataflow elimination: why the launch gave up (FA_*, rlap_flow.h), 0 otherwise
+    int32_t flow_abort;        // dataflow elimination: why the launch gave up (FA_*, rlap_flow.h), 0 otherwise
+    int32_t rounds_narrow;     // degree order: the part of `rounds` the 16-slot round kernel ran
 };
 constexpr int ECAP = 384;  // elimination: column extent handled in LDS; longer -> sequential form in global scratch
 constexpr int ECAP_SMALL = 320;   // the same for the 256-thread shape (four workgroups per CU: 40 KB of LDS each)
@@ -41,6 +42,7 @@ constexpr int MID1CAP = 1024;  // ... and up to this many a sixth (seven per CU)
 constexpr int MID1_LDS_BYTES = MID1CAP * 16 + 2 * (MID1CAP + 2) * 2;
 constexpr int POOL_GRAB_BIG = 16384;   // append slots a 1024-thread workgroup reserves at a time (256-thread: POOL_GRAB_SMALL)
 constexpr int POOL_GRAB_SMALL = 2048;
+constexpr int NARROW_BATCH = 192;      // 16-slot round kernel: candidates predicted per round, of the 256 its LDS holds (rlap_kernels.hip)
 constexpr int LIVE_SLOTS = 64;   // the output pass sums its live-entry count into this many counters, LIVE_STRIDE words apart
 constexpr int LIVE_STRIDE = 16;
 constexpr int HUGECAP = 65535; // output pass, longer still: records in global scratch (uint16 stop lists)
@@ -52,9 +54,11 @@ struct ElimScratch {
     double* f64;    // 4 arrays of `cap` doubles
     int64_t cap;    // total entries over all graphs
     const uint8_t* eqtab;   // k_eq_tables (per handle)
-    long long* prof; // optional diagnostic build only: per-phase cycle sums of graph 0 (nullptr in production)
+    long long* prof; // optional diagnostic build only: per-phase cycle sums of graph 0, 40 words per round kernel: the 32/64/128-slot one, then
+                     // the 16-slot one of the degree order (nullptr in production)
     int32_t poison;  // debug (RLAP_DEBUG_POISON): >= 0 -> the workgroup's LDS is filled with this byte before anything else
     int32_t jitter;  // debug (RLAP_DEBUG_JITTER): > 0 -> waves sleep behind the elimination kernel's barriers (schedule perturbation)
+    int32_t narrow_batch;   // candidates a round of the degree order's 16-slot kernel predicts (NARROW_BATCH; diagnostic override RLAP_NARROW_BATCH)
     __host__ __device__ ColBuf colbuf(int64_t base) const {
         ColBuf B;
         B.rec = rec + base;

@@ -230,17 +230,20 @@ __global__ __launch_bounds__(256) void k_collect(const int32_t* __restrict__ fla
                           const int32_t* __restrict__ bs_pool_top, const int32_t* __restrict__ flow_reason, CallResults* __restrict__ out) {
     __shared__ int32_t s_st;
     __shared__ unsigned long long s_nd, s_rounds, s_singles;
+    __shared__ int32_t s_narrow;
     const int tid = threadIdx.x;
-    if (tid == 0) { s_st = 0; s_nd = 0ull; s_rounds = 0ull; s_singles = 0ull; }
+    if (tid == 0) { s_st = 0; s_nd = 0ull; s_rounds = 0ull; s_singles = 0ull; s_narrow = 0; }
     __syncthreads();
-    int32_t st = 0; unsigned long long nd = 0, rounds = 0, singles = 0;
+    int32_t st = 0, narrow = 0; unsigned long long nd = 0, rounds = 0, singles = 0;
     for (int32_t g = tid; g < G; g += blockDim.x) {
         const int32_t sg = gd[g].status;
         if (sg > st) st = sg;
         const unsigned long long d = (unsigned long long)gd[g].n_draws;
         nd = d > nd ? d : nd;
         rounds += (unsigned long long)gd[g].pad0; singles += (unsigned long long)gd[g].pad1;
+        narrow += gd[g].narrow_rounds;
     }
+    if (narrow) atomicAdd(&s_narrow, narrow);
     if (st) atomicMax(&s_st, st);
     if (nd) atomicMax(&s_nd, nd);
     if (rounds) atomicAdd(&s_rounds, rounds);
@@ -258,7 +261,7 @@ __global__ __launch_bounds__(256) void k_collect(const int32_t* __restrict__ fla
     R.pool_used = *pool_top;
     R.log_used = *bs_pool_top;
     R.status = s_st; R.n_draws = (int64_t)s_nd; R.rounds = (int64_t)s_rounds; R.singles = (int64_t)s_singles;
-    R.flow_abort = flow_reason ? *flow_reason : 0; R.pad = 0;
+    R.flow_abort = flow_reason ? *flow_reason : 0; R.rounds_narrow = s_narrow;
     *out = R;
 }
 
@@ -1089,6 +1092,9 @@ __device__ __noinline__ bool wave_eliminate_big(const Arrays& A, GraphDesc& G, B
 constexpr int PASSES = 4;     // (candidate, slot) pairs per thread: slots per round = 4 x threads
 
 struct CRec { int32_t x, i, j; };
+// contended (target, candidate) records a round may hold; more stop the round in front of the candidate.  The 16-slot shape gives
+// half of the list to its 256 candidate records (its rounds average some 50 contended records)
+constexpr int batch_ccap(int BC, int NTT) { return BC == 16 ? NTT / 4 : NTT / 2; }
 
 template <int BC, int NTT>
 struct BatchLdsT {
@@ -1103,8 +1109,8 @@ struct BatchLdsT {
     };
     int32_t pslot[4 * NTT];   // slot of the entry position p of candidate i appends (commit phase)
     unsigned long long cmask[4 * NTT / BC];   // per candidate: which op numbers (mv - m) end in a PQ move -> order of the moves
-    CRec cont[NTT / 2];       // contended (target, candidate) records per round
-    CRec csorted[NTT / 2];
+    CRec cont[batch_ccap(BC, NTT)];       // contended (target, candidate) records per round
+    CRec csorted[batch_ccap(BC, NTT)];
     int32_t scan[NTT / 64 + 8];
 };
 
@@ -1114,7 +1120,8 @@ union ElimSharedT {
     ElimLdsT<(NTT >= 1024 ? ECAP : ECAP_SMALL)> e;
     BigElimLdsT<(NTT >= 1024 ? 7168 : 1536)> g;
 };
-static_assert(sizeof(ElimSharedT<64, 1024>) == sizeof(BatchLdsT<64, 1024>) && sizeof(ElimSharedT<32, 1024>) == sizeof(BatchLdsT<32, 1024>),
+static_assert(sizeof(ElimSharedT<64, 1024>) == sizeof(BatchLdsT<64, 1024>) && sizeof(ElimSharedT<32, 1024>) == sizeof(BatchLdsT<32, 1024>) &&
+              sizeof(ElimSharedT<16, 1024>) == sizeof(BatchLdsT<16, 1024>),
               "the single-vertex paths borrow the batch round's LDS");
 
 // exclusive block scan over the workgroup's NWAVE waves; returns exclusive prefix, *total = sum
@@ -1192,7 +1199,7 @@ template <int ON, class CT>
 __device__ __noinline__ bool wave_patch(const int32_t o_v, const uint64_t shuffle_seed, const double* __restrict__ rng, const int32_t rng_mode, CT* cand, int32_t d, int32_t vbase, int32_t* tmp_wave) {
     Arrays A;            // (by value, like cand_prepare_wide: what the sampling helpers read of the argument block; lives in registers)
     A.o_v = o_v; A.o_n = ON; A.shuffle_seed = shuffle_seed; A.rng = rng; A.rng_mode = rng_mode; A.vbase = vbase;
-    static_assert(CT::CAP == 32 || CT::CAP == 64, "one entry per lane");
+    static_assert(CT::CAP == 16 || CT::CAP == 32 || CT::CAP == 64, "one entry per lane");
     const int lane = lane_id();
     CT& C = cand[d];
     const int32_t m = C.m, nd = C.ndep, v = C.v;
@@ -1239,7 +1246,17 @@ __device__ __noinline__ bool wave_patch(const int32_t o_v, const uint64_t shuffl
     constexpr bool keyed = (ON == ON_RANDOM);
     double key = keyed ? keyed_order_dkey(keyed_order_base(A.shuffle_seed, v - vbase, 0), my_nbr - vbase) : my_val;
     int idx = lane & (CT::CAP - 1), pos = lane & (CT::CAP - 1);
-    if (CT::CAP == 32) {
+    if constexpr (CT::CAP == 16) {
+        // m <= 16: std::sort is an insertion sort, hence stable -- the position is the stable rank of the key (the entries sit in
+        // lanes [0,m) in id order)
+        int32_t r = 0;
+        for (int32_t q = 0; q < m; ++q) {
+            const double kq = __shfl(key, q);
+            const bool before = (ON == ON_DESC) ? (kq > key) : (kq < key);
+            r += (before || (kq == key && q < lane)) ? 1 : 0;
+        }
+        idx = lane; pos = r;
+    } else if (CT::CAP == 32) {
         const bool want = lane < 32 && m > 1;
         const bool okg = (ON == ON_DESC) ? group_sort<true, 32>(key, idx, m, want, lane, tmp_wave, &pos) : group_sort<false, 32>(key, idx, m, want, lane, tmp_wave, &pos);
         if (__ballot(want && !okg) != 0ull) return false;   // depth limit of the introsort: leave it to the single-vertex path (conservative)
@@ -1566,7 +1583,15 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
     constexpr int NWAVE = NT / 64;
     constexpr int SLOTS = PASSES * NT; // candidates x slots per round
     constexpr int MCAP = NT;           // PQ moves per round
-    constexpr int CCAP = NT / 2;       // contended records per round
+    constexpr int CCAP = batch_ccap(BC, NTT);   // contended records per round
+    // 16 slots per candidate (degree order, while the columns at the head of the queue are short): 256 candidates per round, a
+    // quarter-wave each.  A round whose FIRST candidate is longer ends the kernel, and the 32-slot kernel launched behind it on the
+    // stream carries on from there (GraphDesc::resume).  m <= 16 throughout: std::sort is an insertion sort, no permutation tables.
+    constexpr bool NARROW = (BC == 16);
+    static_assert(!NARROW || (OV == OV_DEGREE && NTT == 1024), "the 16-slot shape exists for the degree order, 1024 threads");
+    // a move's place in (candidate, op) order: candidate << SEQSH | op number (op numbers run to 2 m <= 2 BC); 15 bits in all
+    constexpr int SEQSH = NARROW ? 6 : 8;
+    static_assert(((SLOTS / BC - 1) << SEQSH | ((1 << SEQSH) - 1)) <= 0x7FFF && (BC > 32 || 2 * BC < (1 << SEQSH)), "(candidate, op) fits 15 bits");
     constexpr int HBITS = (SLOTS == 4096) ? 12 : (SLOTS == 2048) ? 11 : 10;   // log2(SLOTS): size of the target hash table
     static_assert((1 << HBITS) == SLOTS, "hash table = one place per slot");
     // BC slots per candidate: a group of BC lanes (half a wave or a whole wave) works on one candidate
@@ -1580,7 +1605,7 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
     // fewer and no faster, and the coarsening order fills its rounds without it -- so only the degree order uses it.
     constexpr bool PATCH = (OV == OV_DEGREE);
     constexpr int GSH = BC >= 64 ? 0 : 64 - BC;                   // lane & GSH = first lane of my group
-    constexpr uint64_t GMASK = BC >= 64 ? ~0ull : 0xFFFFFFFFull;   // a group's part of a 64-bit ballot
+    constexpr uint64_t GMASK = BC >= 64 ? ~0ull : ((1ull << (BC & 63)) - 1ull);   // a group's part of a 64-bit ballot
     Arrays A = A_in;
     A.o_v = OV;
     A.o_n = ON;
@@ -1600,11 +1625,11 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
     // std::sort's permutation of n = 17..BC all-equal keys and its inverse (final position of the entry with id-rank r):
     // in LDS for the 1024-thread shape; the 256-thread shape reads the handle's tables (k_eq_tables) through the L1,
     // which leaves its LDS at 39 KB -- four workgroups per CU
-    constexpr bool EQG = NTT < 1024 || BC == 128;
+    constexpr bool EQG = NTT < 1024 || BC == 128 || NARROW;   // (16 slots: no tables at all)
     constexpr int EC1 = NTT >= 1024 ? ECAP : ECAP_SMALL;   // single-vertex path in LDS up to this extent
     __shared__ uint8_t s_eqperm[EQG ? 1 : BC - 16][EQG ? 1 : BC];
     __shared__ uint8_t s_eqinv[EQG ? 1 : BC - 16][EQG ? 1 : BC];
-    const uint8_t* __restrict__ eqg = S.eqtab + (BC == 64 ? 0 : (BC == 32 ? EQTAB_OFF32 : EQTAB_OFF128));
+    const uint8_t* __restrict__ eqg = S.eqtab + (BC == 64 ? 0 : (BC == 128 ? EQTAB_OFF128 : EQTAB_OFF32));
     BatchLds& L = sh.b;
     const int g = blockIdx.x;
     const int tid = threadIdx.x;
@@ -1617,6 +1642,7 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
     if (tid == 0) {
         G = gd[g]; s_nc = 0; s_pmax = BATCH + 1; s_p = BATCH + 1; s_ncont = 0; s_nmoves = 0; s_pool_cur = 0; s_pool_end = 0; s_anydep = 0; s_npatched = 0;
         s_help[0] = 0; s_help[1] = 0; s_help[2] = 0; s_dirb = -1;
+        if (G.resume) { s_pool_cur = G.pool_cur; s_pool_end = G.pool_end; }   // what the launch before this one had reserved and not used
         // the input checks of the setup kernels are read here, not on the host (no mid-call synchronisation): bad input -> nothing is eliminated
         int32_t bad = 0;
         if (in_flags[FLAG_RANGE]) bad = ST_INDEX_RANGE;
@@ -1649,12 +1675,15 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
     if (G.resume) {
         // a later segment of a depths call: every round ends in a state the next round starts from (the PQ cursors move only for
         // committed pops and empty buckets, uncommitted candidates leave nothing behind but batch_pos, cleared in the epilogue), so
-        // the loop picks up at the previous launch's n_elim.  The LDS-only state starts afresh: the pool reservation (its unused
-        // slots are lost: the depths call sizes the pool for it), the chunk directory cache, and `pending_long` -- a long column
+        // the loop picks up at the previous launch's n_elim.  The pool reservation comes along in the descriptor (pool_cur, pool_end);
+        // the rest of the LDS-only state starts afresh: the chunk directory cache, and `pending_long` -- a long column
         // that cut the last round is popped first again and goes to the single-vertex path as first_is_big.
         done = G.n_elim; rounds = G.pad0; singles = G.pad1;
         if (G.status != 0 || nelim < done) nelim = done;   // an earlier segment failed (or the depth did not grow): nothing to do
+        if (NARROW && G.narrow) nelim = done;              // handed over in an earlier segment: the 32-slot kernel behind this one goes on
     }
+    const int32_t rounds_in = rounds, singles_in = singles;
+    bool handover = false;     // 16-slot shape: the next vertex's column is longer than 16 slots
     bool pending_long = false;   // o_v = random: the last round was cut by a long column, which is therefore the next vertex
     long long t_prev = 0;
     __shared__ long long s_prof[40];   // diagnostic build only (S.prof != nullptr)
@@ -1708,7 +1737,10 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
             continue;
         }
         ++rounds;
-        const int32_t Bcur = (int32_t)((nelim - done) < (int64_t)BATCH ? (nelim - done) : (int64_t)BATCH);
+        // (16-slot shape: fewer candidates than the records hold -- the move list ends a round at about 160 committed, and what is
+        // prepared, sampled and replayed beyond that is thrown away; the target hash table also fills to 0.6 with all 256)
+        const int32_t bcap = NARROW ? (S.narrow_batch < BATCH ? S.narrow_batch : BATCH) : BATCH;
+        const int32_t Bcur = (int32_t)((nelim - done) < (int64_t)bcap ? (nelim - done) : (int64_t)bcap);
         // ================= P0: predict the next pops =================
         // (the round counters were reset before the barrier that ended the previous round)
         int32_t b = 0;
@@ -1782,9 +1814,19 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
         }
         BSYNC();
         const bool first_is_big = (L.cand[0].flags & CF_BIG) != 0;   // goes to the single-vertex path: skip this round's prepare
+        if constexpr (NARROW) {
+            if (first_is_big) {
+                // hand over: the queue is as the prediction found it (nothing popped), the marks of this round's candidates are taken
+                // back, and the round is not counted -- the 32-slot kernel predicts it again
+                if (tid < nc) batch_pos[L.cand[tid].v] = -1;
+                --rounds;
+                handover = true;
+                break;
+            }
+        }
         if (!first_is_big) {
             // BATCH*BCAP = 4*NT slots: issue every load before the first LDS store
-            static_assert(BATCH * BCAP == PASSES * NT && (BC == 32 || BC == 64 || BC == 128), "slot loops are unrolled for PASSES passes");
+            static_assert(BATCH * BCAP == PASSES * NT && (BC == 16 || BC == 32 || BC == 64 || BC == 128), "slot loops are unrolled for PASSES passes");
             // slot of pass k -> (candidate, entry).  128-slot candidates: a wave owns a candidate, its entries lane and 64 + lane are
             // the wave's passes 2c and 2c+1 (everything candidate-local stays inside one wave)
             auto SI = [&](int k) -> int32_t { return BC == 128 ? ((k >> 1) * NWAVE + (tid >> 6)) : (k * NT + tid) / BCAP; };
@@ -1836,7 +1878,7 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
                     const int32_t m = __popcll(half);
                     if (live) {
                         const int32_t r = __popcll(half & ~((2ull << e) - 1ull));
-                        const int32_t pos = (m <= 16) ? r : (int32_t)(EQG ? eqg[(BC - 16) * BC + (m - 17) * BC + r] : s_eqinv[EQG ? 0 : m - 17][EQG ? 0 : r]);
+                        const int32_t pos = (NARROW || m <= 16) ? r : (int32_t)(EQG ? eqg[(BC - 16) * BC + (m - 17) * BC + r] : s_eqinv[EQG ? 0 : m - 17][EQG ? 0 : r]);
                         Ent& E = C.e[pos];
                         E.val = lv[k]; E.nbr = ln[k]; E.twin = lt[k]; E.aux = 0;
                     }
@@ -2048,7 +2090,7 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
                     Cand& C = L.cand[i];
                     const int32_t m = C.m;
                     if (hdiff == 0) {
-                        C.ksel[j] = (m <= 16) ? (uint8_t)j : (EQG ? eqg[(m - 17) * BC + j] : s_eqperm[EQG ? 0 : m - 17][EQG ? 0 : j]);
+                        C.ksel[j] = (NARROW || m <= 16) ? (uint8_t)j : (EQG ? eqg[(m - 17) * BC + j] : s_eqperm[EQG ? 0 : m - 17][EQG ? 0 : j]);
                     } else {
                         int32_t r = 0; bool tie = false;
                         for (int32_t q = 0; q < m; ++q) {
@@ -2073,10 +2115,10 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
                 if (r2[k] >= 0) {
                     const int32_t idx = k * NT + tid;
                     Cand& C = L.cand[idx / BCAP];
-                    if (C.m <= 16 || !(C.flags & CF_TIE)) C.ksel[r2[k]] = (uint8_t)(idx % BCAP);
+                    if (NARROW || C.m <= 16 || !(C.flags & CF_TIE)) C.ksel[r2[k]] = (uint8_t)(idx % BCAP);
                 }
             }
-            if (BC == 64) {
+            if constexpr (BC == 64) {
                 // one wave = one candidate: std::sort's permutation with the elements in registers
                 WAVE_SYNC();   // candidate-local: producer and consumer are the same (half-)wave   // rank writes of ksel above vs. the sort's own
                 int32_t* tmp = L.pslot + (tid >> 6) * 256;   // pslot is not live before the commit
@@ -2096,7 +2138,7 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
                     else if (lane == 0) { Arrays A3 = A; cand_order_index_call(A3, C); }
                     WAVE_SYNC();
                 }
-            } else {
+            } else if constexpr (BC == 32) {
                 // half a wave = one candidate: the same with two independent sorts per wave
                 WAVE_SYNC();   // candidate-local: producer and consumer are the same (half-)wave   // rank writes of ksel above vs. the sort's own
                 int32_t* tmp = L.pslot + (tid >> 6) * 256;   // pslot is not live before the commit
@@ -2123,6 +2165,7 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
                     WAVE_SYNC();
                 }
             }
+            // (16 slots: m <= 16, the stable rank above is std::sort's order)
             WAVE_SYNC();   // candidate-local: producer and consumer are the same (half-)wave
             PHASE_STAMP(14);
             // apply the permutation: every position fetches its source entry, then all store
@@ -2195,8 +2238,9 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
                 // ---- dependent candidates: patched from the sampled records of the earlier candidates they are adjacent to, ordered
                 //      again and sampled, one wave each; a candidate waits until the ones it depends on are through (a chain of
                 //      dependent candidates takes one pass of this loop per link).  What cannot be patched cuts the round. ----
-                int32_t* const ptmp = reinterpret_cast<int32_t*>(L.cont) + (tid >> 6) * 160;   // the record lists are idle until the replay
-                static_assert(sizeof(CRec) * CCAP * 2 >= (size_t)NWAVE * 160 * 4, "sort scratch of the patching waves fits the record lists");
+                // (sort scratch: 16-slot candidates order with a stable rank in registers and need none)
+                int32_t* const ptmp = NARROW ? nullptr : reinterpret_cast<int32_t*>(L.cont) + (tid >> 6) * 160;   // the record lists are idle until the replay
+                static_assert(NARROW || sizeof(CRec) * CCAP * 2 >= (size_t)NWAVE * 160 * 4, "sort scratch of the patching waves fits the record lists");
                 // No workgroup barrier per link of a chain: a wave takes its candidates in increasing order and spins on the flags of
                 // the (smaller) dependent candidates it needs; the smallest unresolved one can always proceed, so every wave gets through.
                 #pragma unroll 1
@@ -2235,26 +2279,59 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
             PHASE_STAMP(3);
             // ================= P4: PQ replay; targets shared by several candidates go in candidate order =================
             int32_t key0k[PASSES];   // the targets' keys: fetched here, used after the barrier (their latency hides behind the table)
+            int32_t tck[PASSES];     // 16-slot shape: my targets' places in the table, then their counts
 #pragma unroll
             for (int k = 0; k < PASSES; ++k) {
                 const int32_t i = PI(k), j = PJ(k);
                 key0k[k] = 1;
+                if constexpr (NARROW) tck[k] = -1;
                 if (i >= Pmax) continue;
                 if (j < L.cand[i].m) {
                     const int32_t x = L.cand[i].e[j].nbr;
                     if (use_pq) key0k[k] = A.vr[x].key;
                     uint32_t hh = ((uint32_t)x * 2654435761u) >> (32 - HBITS);
-                    while (true) {   // linear probing; at most SLOTS distinct keys in SLOTS places
+                    uint32_t step = 0;
+                    while (true) {   // open addressing, at most SLOTS distinct keys in SLOTS places; linear probing except in the 16-slot shape
                         const int32_t cur = hkeys[hh];
                         if (cur == x) break;
                         if (cur == -1) { const int32_t old = atomicCAS(&hkeys[hh], -1, x); if (old == -1 || old == x) break; }
-                        hh = (hh + 1) & (SLOTS - 1);
+                        // (16-slot shape: 192 candidates fill the table to 0.47 and nobody looks a key up again -- the place is kept in tck --
+                        // so the probe sequence is the triangular one, which visits every place of a power-of-two table without
+                        // the runs linear probing builds)
+                        if constexpr (NARROW) { ++step; hh = (hh + step) & (SLOTS - 1); }
+                        else hh = (hh + 1) & (SLOTS - 1);
                     }
                     atomicAdd(&hcnt[hh], 1);
+                    if constexpr (NARROW) tck[k] = (int32_t)hh;
                 }
             }
             BSYNC();
             PHASE_STAMP(33);
+            // 16-slot shape: twice the candidates share half the record list, and small graphs (hubs) fill it in most rounds.  A
+            // record's place is therefore not the order of arrival (the first record that finds the list full may belong to ANY
+            // candidate, and the round ends in front of it) but the candidate order: the round keeps every candidate whose records
+            // fit.  Counts per thread -> per candidate (four adjacent lanes) -> prefix over the wave's 16 candidates -> over the waves.
+            int32_t crec = 0;   // place of my next contended record
+            if constexpr (NARROW) {
+                int mine_c = 0;
+#pragma unroll
+                for (int k = 0; k < PASSES; ++k) {
+                    tck[k] = tck[k] >= 0 ? hcnt[tck[k]] : 0;
+                    mine_c += tck[k] > 1 ? 1 : 0;
+                }
+                const int l4 = lane & 3, l0 = lane & ~3;
+                const int c0 = __shfl(mine_c, l0), c1 = __shfl(mine_c, l0 + 1), c2 = __shfl(mine_c, l0 + 2), c3 = __shfl(mine_c, l0 + 3);
+                const int csum = c0 + c1 + c2 + c3;
+                const int before_me = (l4 > 0 ? c0 : 0) + (l4 > 1 ? c1 : 0) + (l4 > 2 ? c2 : 0);
+                int incl = l4 == 0 ? csum : 0;
+                for (int off = 1; off < 64; off <<= 1) { int t = __shfl_up(incl, off); if (lane >= off) incl += t; }
+                if (lane == 63) L.scan[tid >> 6] = incl;
+                BSYNC();
+                int wbase = 0;
+                for (int w = 0; w < (tid >> 6); ++w) wbase += L.scan[w];
+                crec = wbase + incl - csum + before_me;
+                if (tid == NT - 1) s_ncont = wbase + incl;
+            }
 #pragma unroll
             for (int k = 0; k < PASSES; ++k) {
                 const int32_t i = PI(k), j = PJ(k);
@@ -2268,9 +2345,13 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
                 Cand& C = L.cand[i];
                 if (j >= C.m) continue;
                 const int32_t x = C.e[j].nbr;
-                uint32_t hh = ((uint32_t)x * 2654435761u) >> (32 - HBITS);
-                while (hkeys[hh] != x) hh = (hh + 1) & (SLOTS - 1);
-                const int32_t tc = hcnt[hh];
+                int32_t tc;
+                if constexpr (NARROW) tc = tck[k];
+                else {
+                    uint32_t hh = ((uint32_t)x * 2654435761u) >> (32 - HBITS);
+                    while (hkeys[hh] != x) hh = (hh + 1) & (SLOTS - 1);
+                    tc = hcnt[hh];
+                }
                 const int32_t key0 = key0k[k];
                 TRes& R = ent_tres(C.e[j]);
                 if (tc > 1) {
@@ -2279,7 +2360,8 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
                     if constexpr (GROUPED) { c0 = __popcll(pm); li0 = pm ? 63 - __builtin_clzll(pm) : -1; }
                     else cand_replay_pre(A, C, j, &c0, &li0);
                     R.flags = TF_CONTENDED; R.mv = (int16_t)li0; R.c = (uint8_t)c0; R.key_after = 0;
-                    int32_t q = atomicAdd(&s_ncont, 1);
+                    int32_t q;
+                    if constexpr (NARROW) q = crec++; else q = atomicAdd(&s_ncont, 1);
                     if (q < CCAP) { L.cont[q].x = x; L.cont[q].i = i; L.cont[q].j = j; }
                     else atomicMin(&s_p, i);     // record list full: stop the round before this candidate
                     continue;
@@ -2339,15 +2421,19 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
             BSYNC();
             // ================= P: the first pre-empting / complex candidate was noted during the replay; bound the
             PHASE_STAMP(36);
-            // number of moves (candidates sit in the first two waves: a wave scan and one word through LDS) =================
+            // number of moves (candidates sit in the first BATCH / 64 waves: a wave scan and their totals through LDS) =================
             {
                 const int mycnt = tid < Pmax ? L.cand[tid].nmv : 0;
                 int incl = mycnt;
                 for (int off = 1; off < 64; off <<= 1) { int t = __shfl_up(incl, off); if (lane >= off) incl += t; }
-                if (tid == 63) L.scan[0] = incl;
+                constexpr int CW = (BATCH + 63) / 64;   // waves that hold candidates
+                static_assert(CW <= 4 && CW <= NWAVE, "candidates live in the first waves");
+                if (lane == 63 && (tid >> 6) < CW - 1) L.scan[tid >> 6] = incl;
                 BSYNC();
-                static_assert(BATCH <= 128, "candidates live in waves 0 and 1");
-                if (tid < Pmax && incl + (tid >= 64 ? L.scan[0] : 0) > MCAP) atomicMin(&s_p, tid);
+                int before = 0;
+#pragma unroll
+                for (int w = 0; w < CW - 1; ++w) before += (w < (tid >> 6)) ? L.scan[w] : 0;
+                if (tid < Pmax && incl + before > MCAP) atomicMin(&s_p, tid);
             }
             BSYNC();
             P = s_p < Pmax ? s_p : Pmax;
@@ -2545,7 +2631,7 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
                     atomicOr(&L.cmask[i], 1ull << (Rk[k].mv - L.cand[i].m));
                     int32_t q = qbase + __popcll(mvmask & lanemask_lt(lane));
                     if (q < MCAP) {
-                        L.mkey[q] = ((uint64_t)(uint32_t)pq_list_of(Rk[k].key_after, n) << 32) | (uint32_t)((i << 8) | Rk[k].mv);
+                        L.mkey[q] = ((uint64_t)(uint32_t)pq_list_of(Rk[k].key_after, n) << 32) | (uint32_t)((i << SEQSH) | Rk[k].mv);
                         L.mval[q] = xk[k];
                     }
                 }
@@ -2573,13 +2659,13 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
                     }
                     TRes R = ent_tres(C.e[csorted[r].j]);
                     key_final = R.key_after;
-                    if (R.mv >= 0) mvseq = (csorted[r].i << 8) | R.mv;
+                    if (R.mv >= 0) mvseq = (csorted[r].i << SEQSH) | R.mv;
                 }
                 if (a != a_before) { A.vr[x].app_cnt = a; A.vr[x].app_chunk = chunk; }
                 if (use_pq) {
                     A.vr[x].key = key_final;
                     if (mvseq >= 0) {
-                        atomicOr(&L.cmask[mvseq >> 8], 1ull << ((mvseq & 0xFF) - L.cand[mvseq >> 8].m));
+                        atomicOr(&L.cmask[mvseq >> SEQSH], 1ull << ((mvseq & ((1 << SEQSH) - 1)) - L.cand[mvseq >> SEQSH].m));
                         int32_t qq = atomicAdd(&s_nmoves, 1);
                         if (qq < MCAP) {
                             L.mkey[qq] = ((uint64_t)(uint32_t)pq_list_of(key_final, n) << 32) | (uint32_t)mvseq;
@@ -2626,7 +2712,7 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
         const int32_t nmoves = s_nmoves;
         if (nmoves > MCAP) { if (tid == 0) s_status = ST_INTERNAL; BSYNC(); break; }
         if (use_pq && nmoves > 0) {
-            static_assert(BC == 32 || OV == OV_RANDOM, "op numbers mv - m fit a 64-bit mask for 32-slot candidates");
+            static_assert(BC <= 32 || OV == OV_RANDOM, "op numbers mv - m fit a 64-bit mask for candidates of up to 32 slots");
             // ---- order of the moves = (bucket, candidate, op).  No sort: a move's place in (candidate, op) order is
             //      the candidates' move counts summed before it plus the rank of its op bit in its candidate's mask;
             //      the moves are laid out in that order, then each finds its rank inside its bucket by counting
@@ -2641,17 +2727,21 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
                 const uint64_t kq0 = mine ? L.mkey[tid] : 0ull;
                 const int32_t x0 = mine ? L.mval[tid] : -1;
                 const int32_t seq = (int32_t)(kq0 & 0x7FFFull);
-                const int32_t ci = seq >> 8, cmv = seq & 0xFF;
+                const int32_t ci = seq >> SEQSH, cmv = seq & ((1 << SEQSH) - 1);
                 if (mine) bmin = (uint32_t)(kq0 >> 32);
                 for (int off = 32; off > 0; off >>= 1) bmin = min(bmin, (uint32_t)__shfl_xor((int)bmin, off));
                 if (lane == 0) L.scan[tid >> 6] = (int32_t)bmin;
                 const int cnt_i = tid < P ? __popcll(L.cmask[tid]) : 0;
                 int incl = cnt_i;
                 for (int off = 1; off < 64; off <<= 1) { int t = __shfl_up(incl, off); if (lane >= off) incl += t; }
-                if (tid == 63) L.scan[NWAVE] = incl;
+                constexpr int CW = (BATCH + 63) / 64;   // waves that hold candidates (their totals: L.scan[NWAVE ..])
+                if (lane == 63 && (tid >> 6) < CW - 1) L.scan[NWAVE + (tid >> 6)] = incl;
                 BSYNC();
                 for (int w = 0; w < NWAVE; ++w) bmin = min(bmin, (uint32_t)L.scan[w]);
-                if (tid < P) L.hidx[tid] = incl - cnt_i + (tid >= 64 ? L.scan[NWAVE] : 0);
+                int cbefore = 0;
+#pragma unroll
+                for (int w = 0; w < CW - 1; ++w) cbefore += (w < (tid >> 6)) ? L.scan[NWAVE + w] : 0;
+                if (tid < P) L.hidx[tid] = incl - cnt_i + cbefore;
                 // [NWAVE][RB] move counts per (wave, bucket above the lowest); pslot is idle now (SLOTS = NWAVE * 256 ints)
                 constexpr int RB = 256, HCAP = 128;
                 static_assert(NWAVE * RB <= SLOTS && 2 * RB + 2 * HCAP <= 3 * CCAP * 2, "tables fit pslot / the record lists");
@@ -2883,10 +2973,22 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
     }
     BSYNC();
     if (tid == 0) {
-        G.n_elim = (int32_t)nelim;
+        G.n_elim = (int32_t)(handover ? done : nelim);
         if (s_status) G.status = s_status;
         G.pad0 = rounds; G.pad1 = singles;
-        if (S.prof && g == 0) { for (int q = 0; q < 20; ++q) S.prof[q] = s_prof[q]; S.prof[20] = clock64() - clk0; S.prof[21] = wall_clock64() - wall0; S.prof[22] = rounds; S.prof[23] = singles; for (int q = 24; q < 40; ++q) S.prof[q] = s_prof[q]; }
+        G.pool_cur = s_pool_cur; G.pool_end = s_pool_end;
+        if constexpr (NARROW) {
+            // the 32-slot kernel that follows on the stream continues from n_elim: at once after a hand-over, with nothing to do otherwise
+            G.resume = 1;
+            if (handover) G.narrow = 1;
+            G.narrow_rounds += rounds - rounds_in;
+        }
+        if (S.prof && g == 0) {   // (the 16-slot kernel's sums go to a block of their own behind the other's; counts: this launch's)
+            long long* const pr = S.prof + (NARROW ? 40 : 0);
+            for (int q = 0; q < 20; ++q) pr[q] = s_prof[q];
+            pr[20] = clock64() - clk0; pr[21] = wall_clock64() - wall0; pr[22] = rounds - rounds_in; pr[23] = singles - singles_in;
+            for (int q = 24; q < 40; ++q) pr[q] = s_prof[q];
+        }
         gd[g] = G;
     }
 }
@@ -2957,6 +3059,16 @@ void launch_eliminate_batch(int o_v, int o_n, unsigned G, int n_cu, hipStream_t 
 #else   // RLAP_ELIM_PQ_TU
 void launch_eliminate_pq(int o_v, int o_n, unsigned G, bool many, hipStream_t stream, const Arrays& A, GraphDesc* gd, const ElimScratch& S,
                          int32_t* batch_pos, const int32_t* flags, const double* acc) {
+    // degree order, 1024-thread shape: the 16-slot kernel first (256 candidates per round while the columns at the head of the queue
+    // are short: BA(1M,10) has none longer than 16 slots among its first 300,000 pops); it stops in front of the first longer column
+    // and the 32-slot kernel below, launched right behind it, continues from there (GraphDesc::resume) -- or finds nothing left to do
+    bool narrow = o_v == OV_DEGREE && !many;
+    if (const char* e = std::getenv("RLAP_NARROW")) { if (e[0] == '0') narrow = false; }   // diagnostic override: the 32-slot kernel alone
+    if (narrow) {
+        if (o_n == ON_ASC) hipLaunchKernelGGL((k_eliminate_batch_t<OV_DEGREE, ON_ASC, 16, 1024>), dim3(G), dim3(1024), 0, stream, A, gd, S, batch_pos, flags, acc);
+        else if (o_n == ON_DESC) hipLaunchKernelGGL((k_eliminate_batch_t<OV_DEGREE, ON_DESC, 16, 1024>), dim3(G), dim3(1024), 0, stream, A, gd, S, batch_pos, flags, acc);
+        else hipLaunchKernelGGL((k_eliminate_batch_t<OV_DEGREE, ON_RANDOM, 16, 1024>), dim3(G), dim3(1024), 0, stream, A, gd, S, batch_pos, flags, acc);
+    }
 #define RLAP_CASE(OV, ON, BC) if (o_v == OV && o_n == ON) { \
         if (many) hipLaunchKernelGGL((k_eliminate_batch_t<OV, ON, BC, 256>), dim3(G), dim3(256), 0, stream, A, gd, S, batch_pos, flags, acc); \
         else hipLaunchKernelGGL((k_eliminate_batch_t<OV, ON, BC, 1024>), dim3(G), dim3(1024), 0, stream, A, gd, S, batch_pos, flags, acc); \
