@@ -364,6 +364,48 @@ int rlap_snapshot_gcn_norm(rlap_handle h, const double* d_sc, int64_t m, const i
                            int64_t G, int64_t num_nodes, int flags, double fill_value, int64_t* d_src, int64_t* d_dst, void* d_val,
                            int64_t cap, int64_t* d_eptr, rlap_gcn_info* h_info);
 
+/* GCN propagation of snapshots: y = A^ x for every layer of a result at once, A^ the entry list that rlap_snapshot_gcn_norm produces
+ * with the same flags and fill_value -- what GCNConv(normalize=False) does next with that list (a scatter-add of val * x[src] into
+ * dst), without the list, without float atomics and in a fixed order.  d_sc, m, d_ptr, S, d_node_ptr, G, num_nodes: exactly as for
+ * rlap_snapshot_gcn_norm, layout, checks and error codes included.  L = S / G is the number of layers (view x depth); the segments
+ * (l, g) of one layer cover disjoint id ranges.
+ *   flags     : RLAP_GCN_WEIGHTED, RLAP_GCN_SELF_LOOPS, RLAP_GCN_NORMALIZE as for rlap_snapshot_gcn_norm (RLAP_GCN_F32 is not one of
+ *               this call's), and
+ *               RLAP_SPMM_TRANSPOSE   : the transposed product (the backward pass: with o_v = random the two weights of a pair are
+ *                                       not always the same bits, so A^ is symmetric only up to that)
+ *               RLAP_SPMM_X_F32       : d_x and d_y are float32; without it float64
+ *               RLAP_SPMM_X_PER_LAYER : d_x is (L, num_nodes, F), one feature matrix per layer; without it (num_nodes, F), shared
+ *   d_x, F    : the features, row-major, F >= 1 columns
+ *   d_y       : (L, num_nodes, F) of d_x's type; every element is written, 0 for an id without entries and without a loop
+ *   h_info    : (nullable) what the call did
+ * With c_e the float64 value that rlap_snapshot_gcn_norm gives entry e of segment (l, g) -- the same bits --
+ *     forward    : y[l, j, :] = sum over the entries e with target j of c_e * x[l or shared, source(e), :]
+ *     transposed : y[l, i, :] = sum over the entries e with source i of c_e * x[l or shared, target(e), :]
+ * The order of every sum is fixed (rlap_amd/csrc/rlap_spmm.h, which a host mirror can compile): float64 throughout, the product
+ * rounded and then the add, no fma; the terms of one output element in list order -- the rows of the block (transposed: the rows with
+ * that source) in input order, the loop last; a list of more than 256 entries is cut into chunks of 256, each summed from 0, the
+ * chunk sums added in chunk order, then the loop.  A float32 result is the float64 sum rounded once.  So the same input gives the
+ * same bits, a segment's result does not depend on the other segments of the call, and nothing depends on what d_y or the arena held.
+ * Limits: F <= 65,536 and L * num_nodes * F < 2^40 (RLAP_E_TOO_LARGE); F < 1, a null pointer, a flag that is not this call's, a bad
+ * ptr / node_ptr, fill_value or weight as for rlap_snapshot_gcn_norm: RLAP_E_BAD_ARG.  Layout errors as for rlap_snapshot_stats; d_y
+ * is then unspecified.  Scratch from the arena (RLAP_E_WORKSPACE when a caller-provided one is too small, rlap_workspace_needed()
+ * saying how much); the transposed call also sorts the rows by source there.  One host synchronisation.  Test hook: a scratch_entries
+ * >= 0 of rlap_debug_set_limits is also the number of chunk sums this call may keep (lists past it are summed by one group of lanes,
+ * same bits), until it is set negative again. */
+enum { RLAP_SPMM_TRANSPOSE = 16, RLAP_SPMM_X_F32 = 32, RLAP_SPMM_X_PER_LAYER = 64 };
+typedef struct {
+    int64_t entries;          /* entries of the list the product ran over (rows that stay + loops)   */
+    int64_t blocks;           /* column blocks of the call: the ids with rows                         */
+    int64_t chunked_lists;    /* lists longer than one chunk                                          */
+    int64_t arena_bytes;      /* scratch bytes of the call                                            */
+    int32_t host_syncs;       /* host synchronisations of the call                                    */
+    int32_t pad;
+} rlap_spmm_info;
+
+int rlap_snapshot_propagate(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
+                            int64_t G, int64_t num_nodes, int flags, double fill_value, const void* d_x, int64_t F, void* d_y,
+                            rlap_spmm_info* h_info);
+
 /* The op with the step BEFORE the path fused in (scripts/node_shared.py:326-327,
  * scripts/augmentor_benchmarks.py:77-78):
  *   symmetrize != 0 : the input holds every undirected edge in one or both directions; (b,a) is

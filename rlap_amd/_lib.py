@@ -20,7 +20,7 @@ EXPORTS = [
     "rlap_workspace_bytes", "rlap_workspace_query", "rlap_set_workspace", "rlap_workspace_needed", "rlap_debug_set_poison", "rlap_debug_set_jitter",
     "rlap_set_rng_mode", "rlap_approx_chol_views", "rlap_approx_chol_depths", "rlap_debug_set_flow_limits",
     "rlap_approx_chol_views_depths", "rlap_snapshot_stats", "rlap_snapshot_ppr", "rlap_snapshot_subgraph",
-    "rlap_snapshot_gcn_norm",
+    "rlap_snapshot_gcn_norm", "rlap_snapshot_propagate",
 ]
 
 E_WORKSPACE = 11   # RLAP_E_WORKSPACE
@@ -32,6 +32,8 @@ PPR_WEIGHTED, PPR_SELF_LOOP, PPR_NORMALIZE, PPR_ZERO_ROWS = 1, 2, 4, 8
 SUB_RELABEL, SUB_NO_SELF_LOOPS = 1, 2
 # rlap_snapshot_gcn_norm flags
 GCN_WEIGHTED, GCN_SELF_LOOPS, GCN_NORMALIZE, GCN_F32 = 1, 2, 4, 8
+# rlap_snapshot_propagate flags (beside the first three above)
+SPMM_TRANSPOSE, SPMM_X_F32, SPMM_X_PER_LAYER = 16, 32, 64
 
 # rlap_stats.elim_kernel
 KERNEL_NONE, KERNEL_ROUND, KERNEL_FLOW = 0, 1, 2
@@ -102,6 +104,17 @@ class GcnInfo(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_ if f != "pad"}
 
 
+class SpmmInfo(ctypes.Structure):
+    """rlap_spmm_info (include/rlap_hip.h)."""
+    _fields_ = [
+        ("entries", ctypes.c_int64), ("blocks", ctypes.c_int64), ("chunked_lists", ctypes.c_int64), ("arena_bytes", ctypes.c_int64),
+        ("host_syncs", ctypes.c_int32), ("pad", ctypes.c_int32),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_ if f != "pad"}
+
+
 def load():
     """dlopen the library and declare prototypes. Raises if it is not built."""
     global _lib
@@ -150,6 +163,9 @@ def load():
     lib.rlap_snapshot_gcn_norm.restype = ci
     lib.rlap_snapshot_gcn_norm.argtypes = [vp, vp, i64, vp, i64, vp, i64, i64, ci, ctypes.c_double, vp, vp, vp, i64, vp,
                                            ctypes.POINTER(GcnInfo)]
+    lib.rlap_snapshot_propagate.restype = ci
+    lib.rlap_snapshot_propagate.argtypes = [vp, vp, i64, vp, i64, vp, i64, i64, ci, ctypes.c_double, vp, i64, vp,
+                                            ctypes.POINTER(SpmmInfo)]
     lib.rlap_approx_chol_views.restype = ci
     lib.rlap_approx_chol_views.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, vp, ci, ci, vp, u64, vp, i64, vp,
                                            ctypes.POINTER(Stats)]

@@ -11,6 +11,9 @@ Mirrors of the reference's L2 adapters that keep everything on the GPU:
                   `.batch_edge_counts` the batch subgraph sizes from ops.snapshot_subgraph
   * `gcn_norm=True` on rLap / rLapViews / rLapDepths: the graphs come with self loops and GCN coefficients from one
                   ops.snapshot_gcn_norm call, for GCNConv(..., normalize=False)
+  * `.snapshots(g)` on rLap / rLapViews / rLapDepths: the same one elimination call as a `Snapshots` holder, whose `.propagate(x)`
+                  is the sparse product of a GCN layer for all views at once (ops.snapshot_propagate); `SnapshotGCNConv` is the
+                  layer built on it
   * `rLapChain` -- the chain of scripts/rlap_vc_spectral.py: eliminate, relabel the survivors 0..k-1, eliminate again
 PyGCL / DGL are optional: with them installed the classes return their graph types,
 without them a small named tuple with the same fields.
@@ -33,6 +36,55 @@ def _schur(edge_index, edge_weights, x, frac, o_v, o_n, seed, num_nodes_from_x, 
     n = int(x.shape[0]) if (num_nodes_from_x and x is not None) else None
     return ops.approximate_cholesky_from_edges(edge_index, edge_weights, n, None, o_v, o_n, remove_frac=frac,
                                                symmetrize=symmetrize, seed=seed, return_device="same")
+
+
+class Snapshots:
+    """The snapshots of one elimination call as the propagation takes them: (sc, ptr, num_nodes, node_ptr, weighted, fill_value).
+    `.propagate(x)` is A^ x for every layer at once (ops.snapshot_propagate with self loops and the GCN normalisation -- the list
+    `gcn_norm=True` hands to GCNConv(..., normalize=False), never written out); `transpose=True` the transposed product."""
+
+    def __init__(self, sc, ptr, num_nodes: int, node_ptr=None, weighted: bool = False, fill_value: float = 1.0):
+        self.sc, self.ptr, self.num_nodes, self.node_ptr = sc, ptr, int(num_nodes), node_ptr
+        self.weighted, self.fill_value = bool(weighted), fill_value
+
+    @property
+    def layers(self) -> int:
+        graphs = 1 if self.node_ptr is None else len(self.node_ptr) - 1
+        return (len(self.ptr) - 1) // graphs
+
+    def propagate(self, x, transpose: bool = False):
+        return ops.snapshot_propagate(self.sc, self.ptr, self.num_nodes, x, node_ptr=self.node_ptr, weighted=self.weighted,
+                                      add_self_loops=True, fill_value=self.fill_value, normalize=True, transpose=transpose)
+
+
+def _snapshots_of(x, sc, ptr, num_nodes, keep_weights, fill_value):
+    """The holder of one call; like _gcn_graphs the loops cover x.shape[0] nodes when x is given, else the call's num_nodes."""
+    return Snapshots(sc, ptr, int(x.shape[0]) if x is not None else int(num_nodes), None, keep_weights, fill_value)
+
+
+class SnapshotGCNConv(torch.nn.Module):
+    """GCNConv for all views of a call at once: forward(x, snapshots) = snapshots.propagate(x @ W) + b, an (L, n, out_channels)
+    tensor for the L layers of `snapshots` (a `Snapshots`).  x is (n, in_channels), shared by the layers (the first GCN layer of
+    every view), or (L, n, in_channels) (the later ones).  The dense product is torch's, the sparse one ops.snapshot_propagate;
+    gradients reach W, b and x.  Glorot-uniform W and zero b, as PyG's GCNConv initialises them.  (Unpinned: PyG is not installed
+    here; this restates its published semantics -- linear without bias, propagate with gcn_norm's coefficients, then the bias --
+    not a run of it: DESIGN 4.10 and section 7.)"""
+
+    def __init__(self, in_channels: int, out_channels: int, bias: bool = True):
+        super().__init__()
+        self.in_channels, self.out_channels = int(in_channels), int(out_channels)
+        self.weight = torch.nn.Parameter(torch.empty(self.in_channels, self.out_channels))
+        self.bias = torch.nn.Parameter(torch.empty(self.out_channels)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        torch.nn.init.xavier_uniform_(self.weight)
+        if self.bias is not None:
+            torch.nn.init.zeros_(self.bias)
+
+    def forward(self, x, snapshots: Snapshots):
+        y = snapshots.propagate(x @ self.weight)
+        return y if self.bias is None else y + self.bias
 
 
 class rLap:
@@ -67,6 +119,13 @@ class rLap:
             return A.Graph(x=x, edge_index=sampled_edge_index, edge_weights=w)
         except Exception:
             return Graph(x, sampled_edge_index, w)
+
+    def snapshots(self, g) -> Snapshots:
+        """The one elimination call of `augment` as a `Snapshots` holder (one layer)."""
+        x, edge_index, edge_weights = g.unfold() if hasattr(g, "unfold") else g
+        sc, num_nodes = _schur(edge_index, edge_weights, x, self.frac, self.o_v, self.o_n, self.seed, self.num_nodes_from_x, self.symmetrize)
+        self.num_remove = int(self.frac * num_nodes)
+        return _snapshots_of(x, sc, [0, int(sc.shape[0])], num_nodes, self.keep_weights, self.fill_value)
 
     def __call__(self, x, edge_index, edge_weight=None):
         return self.augment(Graph(x, edge_index, edge_weight))
@@ -107,12 +166,21 @@ class rLapViews:
         self.gcn_norm, self.fill_value = gcn_norm, fill_value   # True: self loops and GCN coefficients (_gcn_graphs)
         self._pending = None   # (input key, list of K graphs, list of views not yet handed out)
 
-    def augment(self, g):
+    def _call(self, g):
         x, edge_index, edge_weights = g.unfold() if hasattr(g, "unfold") else g
         num_nodes = int(edge_index.max().item()) + 1 if edge_index.numel() else 0
         self.num_remove = [int(f * num_nodes) for f in self.fracs]
         sc, ptr = ops.approximate_cholesky_views(edge_index, edge_weights, num_nodes, self.num_remove, self.o_v, self.o_n,
                                                  seed=self.seed, return_device="same", mode=self.mode)
+        return x, sc, ptr, num_nodes
+
+    def snapshots(self, g) -> Snapshots:
+        """The one elimination call of `augment` as a `Snapshots` holder: layer k is view k."""
+        x, sc, ptr, num_nodes = self._call(g)
+        return _snapshots_of(x, sc, ptr, num_nodes, self.keep_weights, self.fill_value)
+
+    def augment(self, g):
+        x, sc, ptr, num_nodes = self._call(g)
         if self.gcn_norm:
             return _gcn_graphs(x, sc, ptr, num_nodes, self.keep_weights, self.fill_value)
         out = []
@@ -173,6 +241,12 @@ class rLapDepths:
         sc, ptr = ops.approximate_cholesky_depths(edge_index, edge_weights, num_nodes, self.num_remove, self.o_v, self.o_n,
                                                   seed=self.seed, return_device="same", mode=self.mode, **extra)
         return x, sc, ptr, num_nodes
+
+    def snapshots(self, g) -> Snapshots:
+        """The one elimination call of `augment` as a `Snapshots` holder: layer k * R + r is depth k of run r (depth-major, then
+        view, as the rows are)."""
+        x, sc, ptr, num_nodes = self._snapshots(g)
+        return _snapshots_of(x, sc, ptr, num_nodes, self.keep_weights, self.fill_value)
 
     def stats(self, g, weighted: bool = False, tol: float = 1e-10, max_iter: int = 1000):
         """The three lists scripts/rlap_vc_spectral.py records per snapshot (get_rlap_sc_stats: max_sv, num_unique_nodes, num_edges)

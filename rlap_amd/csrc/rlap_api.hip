@@ -22,6 +22,7 @@
 #include "rlap_stats.h"
 #include "rlap_subgraph.h"
 #include "rlap_gcn.h"
+#include "rlap_spmm_api.h"
 
 using namespace rlap;
 
@@ -1390,6 +1391,47 @@ int rlap_snapshot_gcn_norm(rlap_handle h, const double* d_sc, int64_t m, const i
     if (h_info) {
         h_info->entries = rep.entries; h_info->loops_removed = rep.loops_removed; h_info->arena_bytes = (int64_t)need;
         h_info->host_syncs = rep.host_syncs;
+    }
+    return rc;
+}
+
+int rlap_snapshot_propagate(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
+                            int64_t G, int64_t num_nodes, int flags, double fill_value, const void* d_x, int64_t F, void* d_y,
+                            rlap_spmm_info* h_info) {
+    if (h_info) *h_info = rlap_spmm_info{};
+    if (!h || !d_ptr || S < 1 || m < 0 || num_nodes < 0 || (m > 0 && !d_sc) || F < 1) return RLAP_E_BAD_ARG;
+    if (flags & ~(RLAP_GCN_WEIGHTED | RLAP_GCN_SELF_LOOPS | RLAP_GCN_NORMALIZE | RLAP_SPMM_TRANSPOSE | RLAP_SPMM_X_F32 | RLAP_SPMM_X_PER_LAYER))
+        return RLAP_E_BAD_ARG;
+    if ((flags & RLAP_GCN_SELF_LOOPS) && !(fill_value > 0.0 && std::isfinite(fill_value))) return RLAP_E_BAD_ARG;
+    if (d_node_ptr ? (G < 1 || S % G != 0) : false) return RLAP_E_BAD_ARG;
+    if (!d_node_ptr) G = 1;
+    if (m >= INT32_MAX || S >= (int64_t)1 << 30 || num_nodes >= INT32_MAX || F > SPMM_MAX_F) return RLAP_E_TOO_LARGE;
+    if ((S / G) * num_nodes >= SPMM_MAX_ELEMS || (S / G) * num_nodes * F >= SPMM_MAX_ELEMS) return RLAP_E_TOO_LARGE;
+    const int64_t elems = (S / G) * num_nodes * F;
+    if (elems > 0 && (!d_x || !d_y)) return RLAP_E_BAD_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device);
+    const size_t need = snapshot_spmm_bytes(m, S, G, num_nodes, F, flags, h->dbg_scr);
+    h->ws_needed = need;
+    void* base = nullptr;
+    size_t have = 0;
+    if (h->ext_ws) {
+        if (need > h->ext_ws_bytes) return RLAP_E_WORKSPACE;
+        base = h->ext_ws; have = h->ext_ws_bytes;
+    } else {
+        ENSURE(h->own_ws, need);
+        base = h->own_ws.p; have = h->own_ws.cap;
+    }
+    if (h->poison >= 0) {   // debug: the result must not depend on what the arena or the result buffer held
+        HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
+        if (elems > 0) HIPCHK(hipMemsetAsync(d_y, h->poison, (size_t)elems * ((flags & RLAP_SPMM_X_F32) ? 4 : 8), h->stream));
+    }
+    SnapshotSpmmArgs a{d_sc, m, d_ptr, S, d_node_ptr, G, num_nodes, flags, fill_value, d_x, F, d_y, h->dbg_scr};
+    SnapshotSpmmReport rep;
+    const int rc = snapshot_spmm_run(h->stream, base, have, a, &rep);
+    if (h_info) {
+        h_info->entries = rep.entries; h_info->blocks = rep.blocks; h_info->chunked_lists = rep.chunked_lists;
+        h_info->arena_bytes = (int64_t)need; h_info->host_syncs = rep.host_syncs;
     }
     return rc;
 }

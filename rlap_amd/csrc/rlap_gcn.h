@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "rlap_stats.h"
+
 namespace rlap {
 
 struct SnapshotGcnArgs {
@@ -31,5 +33,18 @@ int64_t snapshot_gcn_cap(int64_t m, int64_t S, int64_t G, int64_t N, int flags);
 size_t snapshot_gcn_bytes(int64_t m, int64_t S, int64_t G, int64_t N);
 // the call on `stream`, with `ws` (snapshot_gcn_bytes) as its scratch; returns an RLAP_* status
 int snapshot_gcn_run(hipStream_t stream, void* ws, size_t ws_bytes, const SnapshotGcnArgs& a, SnapshotGcnReport* rep);
+
+
+// The first steps of the call, shared with the propagation (rlap_spmm.hip), which must produce the same coefficients bit for bit.
+// Error words behind the column pass's: a weight the normalisation refuses, a malformed ptr / node_ptr.
+enum { GCN_ERR_WEIGHT = COL_ERR_WORDS, GCN_ERR_ARG = COL_ERR_WORDS + 1, GCN_ERR_WORDS = 8 };
+// checks ptr ([S+1], ending at m) and node_ptr ([G+1] ending at N, or nullptr) on the device and writes the copies every later
+// kernel indexes with (well-formed stand-ins and err[GCN_ERR_ARG] when they are malformed)
+int gcn_tables_enqueue(hipStream_t stream, const int64_t* ptr, int64_t S, int64_t m, const int64_t* node_ptr, int64_t G, int64_t N,
+                       int64_t* cptr, int64_t* cnp, int32_t* err);
+// after the column pass (m > 0): dis[b] = deg^-1/2 and lw[b] = the loop's weight of every block b, summed in the fixed order of
+// DESIGN 4.10; tot[0] (zeroed by the caller) += the loop rows when flags has RLAP_GCN_SELF_LOOPS; err = col.err
+int gcn_degree_enqueue(hipStream_t stream, const double* sc, int64_t m, int flags, double fill, const ColumnBufs& col, double* dis,
+                       double* lw, unsigned long long* tot);
 
 }  // namespace rlap

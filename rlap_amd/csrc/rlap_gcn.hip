@@ -37,7 +37,7 @@ constexpr int GC_THREADS = 256;
 constexpr int GC_WAVES = GC_THREADS / 64;
 constexpr int GC_RPT = GCN_TILE / GC_THREADS;   // rows per thread of an emit tile
 constexpr int GC_GROUP = 16;                    // lanes per block of the degree pass
-enum { GERR_WEIGHT = COL_ERR_WORDS, GERR_ARG = COL_ERR_WORDS + 1, GERR_WORDS = 8 };
+enum { GERR_WEIGHT = GCN_ERR_WEIGHT, GERR_ARG = GCN_ERR_ARG, GERR_WORDS = GCN_ERR_WORDS };
 
 static_assert(GC_RPT * GC_THREADS == GCN_TILE, "an emit tile is a whole number of turns");
 
@@ -314,6 +314,26 @@ int emit_and_tail(hipStream_t st, const Gcn& a, const SnapshotGcnArgs& g) {
 
 }  // namespace
 
+int gcn_tables_enqueue(hipStream_t st, const int64_t* ptr, int64_t S, int64_t m, const int64_t* node_ptr, int64_t G, int64_t N,
+                       int64_t* cptr, int64_t* cnp, int32_t* err) {
+    hipLaunchKernelGGL(k_gc_tables, dim3(1), dim3(1024), 0, st, ptr, S, m, node_ptr, G, N, cptr, cnp, err);
+    GC_HIPCHK(hipGetLastError());
+    return RLAP_OK;
+}
+
+int gcn_degree_enqueue(hipStream_t st, const double* sc, int64_t m, int flags, double fill, const ColumnBufs& col, double* dis,
+                       double* lw, unsigned long long* tot) {
+    const int weighted = (flags & RLAP_GCN_WEIGHTED) ? 1 : 0, loops = (flags & RLAP_GCN_SELF_LOOPS) ? 1 : 0;
+    const int normalize = (flags & RLAP_GCN_NORMALIZE) ? 1 : 0;
+    Gcn a{};
+    a.sc = sc; a.m = m; a.weighted = weighted; a.loops = loops; a.normalize = normalize; a.fill = fill;
+    a.rb = col.rb; a.blk = col.blk; a.bstart = col.bstart; a.idx = col.idx; a.bcap = col.bcap;
+    a.dis = dis; a.lw = lw; a.tot = tot; a.err = col.err;
+    hipLaunchKernelGGL(k_gc_degree, dim3(gc_blocks(col.bcap * GC_GROUP, GC_THREADS)), dim3(GC_THREADS), 0, st, a, weighted && normalize);
+    GC_HIPCHK(hipGetLastError());
+    return RLAP_OK;
+}
+
 int64_t snapshot_gcn_cap(int64_t m, int64_t S, int64_t G, int64_t N, int flags) {
     return m + ((flags & RLAP_GCN_SELF_LOOPS) ? (S / std::max<int64_t>(G, 1)) * N : 0);
 }
@@ -337,15 +357,17 @@ int snapshot_gcn_run(hipStream_t st, void* ws, size_t ws_bytes, const SnapshotGc
     // 1. the tables, checked and copied; the column pass on the copies
     GC_HIPCHK(hipMemsetAsync(B.col.err, 0, sizeof(int32_t) * GERR_WORDS, st));
     GC_HIPCHK(hipMemsetAsync(B.tot, 0, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_gc_tables, dim3(1), dim3(1024), 0, st, g.ptr, S, m, g.node_ptr, G, N, B.cptr, B.cnp, B.col.err);
-    GC_HIPCHK(hipGetLastError());
+    int trc = gcn_tables_enqueue(st, g.ptr, S, m, g.node_ptr, G, N, B.cptr, B.cnp, B.col.err);
+    if (trc != RLAP_OK) return trc;
     if (m > 0) {
         const int rc = column_pass_enqueue(st, g.sc, m, a.ptr, S, a.node_ptr, G, N, B.col, B.nodes);
         if (rc != RLAP_OK) return rc;
     }
     // 2. degrees; 3. the loop rows in front of every tile (zeros without a pass over the rows when the input has none)
-    if (m > 0 && (normalize || loops))
-        hipLaunchKernelGGL(k_gc_degree, dim3(gc_blocks(B.col.bcap * GC_GROUP, GC_THREADS)), dim3(GC_THREADS), 0, st, a, weighted && normalize);
+    if (m > 0 && (normalize || loops)) {
+        trc = gcn_degree_enqueue(st, g.sc, m, g.flags, g.fill, B.col, B.dis, B.lw, B.tot);
+        if (trc != RLAP_OK) return trc;
+    }
     if (loops) {
         GC_HIPCHK(hipMemsetAsync(B.cnt, 0, sizeof(int32_t) * (size_t)(B.tiles + 1), st));
         GC_HIPCHK(hipMemsetAsync(B.segl, 0, sizeof(int64_t) * (size_t)(S + 1), st));

@@ -1007,6 +1007,117 @@ def snapshot_gcn_norm(
         return ei, val, eptr
 
 
+def _propagate_args(sc, ptr, num_nodes, x, node_ptr, fill_value):
+    """Host-side checks of snapshot_propagate, made before the device is touched: (ptr, node_ptr, fill, layers, per_layer)."""
+    p, np_ = _snapshot_args(sc, ptr, num_nodes, node_ptr, 1.0, 1)
+    fill = _real(fill_value, "fill_value", 0.0, float("inf"))
+    S = p.numel() - 1
+    G = np_.numel() - 1 if np_ is not None else 1
+    if S < 1 or S % G != 0:
+        raise ValueError(f"ptr: {S} segments; at least one, and a multiple of the {G} graphs")
+    L, n = S // G, int(num_nodes)
+    if not isinstance(x, Tensor) or x.dim() not in (2, 3):
+        raise ValueError("x: a (num_nodes, F) or (layers, num_nodes, F) tensor")
+    if x.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"x: torch.float32 or torch.float64, got {x.dtype}")
+    if x.shape[-2] != n:
+        raise ValueError(f"x: {x.shape[-2]} rows, num_nodes is {n}")
+    if x.dim() == 3 and x.shape[0] != L:
+        raise ValueError(f"x: {x.shape[0]} layers, the call has {L} (segments / graphs)")
+    if x.shape[-1] < 1:
+        raise ValueError("x: at least one feature column")
+    return p, np_, fill, L, x.dim() == 3
+
+
+def _propagate(sc, p, np_, n, x, L, per_layer, weighted, add_self_loops, fill, normalize, transpose):
+    """One rlap_snapshot_propagate call; x is already checked."""
+    global last_stats
+    S = p.numel() - 1
+    dev = _device_for(sc)
+    lib, hobj = _handle_obj(dev)
+    h = hobj.ptr
+    flags = ((_lib.GCN_WEIGHTED if weighted else 0) | (_lib.GCN_SELF_LOOPS if add_self_loops else 0)
+             | (_lib.GCN_NORMALIZE if normalize else 0) | (_lib.SPMM_TRANSPOSE if transpose else 0)
+             | (_lib.SPMM_X_F32 if x.dtype == torch.float32 else 0) | (_lib.SPMM_X_PER_LAYER if per_layer else 0))
+    with torch.cuda.device(dev):
+        rows = sc.to(device=dev, dtype=torch.float64).contiguous()
+        m = int(rows.shape[0])
+        d_x = x.detach().to(device=dev).contiguous()
+        F = int(d_x.shape[-1])
+        d_ptr = p.to(dev)
+        d_np = np_.to(dev) if np_ is not None else None
+        G = np_.numel() - 1 if np_ is not None else 1
+        y = torch.empty((L, n, F), dtype=d_x.dtype, device=dev)
+        info = _lib.SpmmInfo()
+        st = _lib.Stats()
+        rc = _run(hobj, dev, m, None, G, False, lambda: lib.rlap_snapshot_propagate(
+            h, rows.data_ptr() if m else None, m, d_ptr.data_ptr(), S, d_np.data_ptr() if d_np is not None else None, G, n, flags, fill,
+            d_x.data_ptr() if d_x.numel() else None, F, y.data_ptr() if y.numel() else None, ctypes.byref(info)), st)
+        if rc == _lib.E_NOT_GROUPED:
+            raise ValueError(f"rlap: {_lib.status_string(rc)}")
+        if rc != 0:
+            _raise(rc)
+        last_stats = info.as_dict()
+        return y
+
+
+class _Propagate(torch.autograd.Function):
+    """y = A^ x; the gradient with respect to x is the transposed product of the gradient of y (summed over the layers when one x
+    serves them all).  sc is a sample and gets none."""
+
+    @staticmethod
+    def forward(ctx, x, call):
+        ctx.call = call
+        return _propagate(*call[:4], x, *call[4:])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        sc, p, np_, n, L, per_layer, weighted, loops, fill, normalize, transpose = ctx.call
+        gx = _propagate(sc, p, np_, n, gy.contiguous(), L, True, weighted, loops, fill, normalize, not transpose)
+        return (gx if per_layer else gx.sum(0)), None
+
+
+def snapshot_propagate(
+    sc: Tensor,
+    ptr: Union[Tensor, Sequence[int]],
+    num_nodes: int,
+    x: Tensor,
+    node_ptr: Optional[Union[Tensor, Sequence[int]]] = None,
+    weighted: bool = False,
+    add_self_loops: bool = True,
+    fill_value: float = 1.0,
+    normalize: bool = True,
+    transpose: bool = False,
+) -> Tensor:
+    """The sparse product of a GCN layer for every snapshot of a call at once: y[l] = A^_l x, with A^_l the list that
+    snapshot_gcn_norm(sc, ptr, num_nodes, node_ptr, weighted, add_self_loops, fill_value, normalize) produces for layer l -- what
+    GCNConv(..., normalize=False) does next with that list (scripts/node_shared.py: two views, three encodes a step) -- without the
+    list, without float atomics and in a fixed order.  `sc`, `ptr`, `num_nodes`, `node_ptr` and the four list arguments as for
+    snapshot_gcn_norm.  The S segments are L = S / G layers (view x depth) of G graphs each; the graphs of a layer cover disjoint ids.
+
+      x         : (num_nodes, F), one feature matrix for all layers (the first GCN layer of every view), or (L, num_nodes, F), one
+                  per layer (the later ones); float32 or float64, on any device (moved to sc's)
+      transpose : the transposed product, y[l, i] = the sum over the entries with SOURCE i of c_e x[target] (the backward pass; with
+                  o_v="random" the two weights of a pair may differ in the last bit, so A^ is symmetric only up to that)
+    Returns y, (L, num_nodes, F) of x's dtype on sc's device: y[l, j] = the sum over the entries e with target j of c_e x[source(e)],
+    c_e the float64 coefficient of snapshot_gcn_norm (the same bits), summed in float64 in list order -- the rows of j's block in
+    input order, then the loop; lists longer than 256 entries in chunks of 256 (rlap_amd/csrc/rlap_spmm.h) -- and rounded once for
+    float32.  The same input gives the same bits; a segment's result does not depend on the others.  An id without rows and
+    without a loop gets 0.
+
+    Differentiable in x (its backward is the same call with `transpose` flipped); `sc` gets no gradient, and double backward is not
+    supported.  Malformed arguments raise ValueError before the device is touched; layout errors raise ValueError as for
+    snapshot_gcn_norm.  `last_stats` then holds what the call did (rlap_spmm_info: entries, blocks, chunked_lists, arena_bytes,
+    host_syncs).
+    """
+    p, np_, fill, L, per_layer = _propagate_args(sc, ptr, num_nodes, x, node_ptr, fill_value)
+    call = (sc, p, np_, int(num_nodes), L, per_layer, bool(weighted), bool(add_self_loops), fill, bool(normalize), bool(transpose))
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _Propagate.apply(x, call)
+    return _propagate(sc, p, np_, int(num_nodes), x, L, per_layer, *call[6:])
+
+
 def identity(a: Tensor) -> Tensor:
     """Boundary self-test (reference: rlap/ops.py:61-63): tensor -> column-major
     staging -> tensor, on the GPU; returns a tensor on `a`'s device."""

@@ -1,0 +1,135 @@
+"""ops.snapshot_propagate against the same product in torch on the same tensors and the same device.  The torch
+product is what a GCNConv(normalize=False) does with the list of ops.snapshot_gcn_norm: per layer (the snapshots of one layer are one
+batch over disjoint ids) torch.zeros(N, F).index_add_(0, dst, val[:, None] * x[src]); the list itself is built outside the timed
+span, and the time of building it (ops.snapshot_gcn_norm) is reported beside it, since the call under test needs no list.  Where
+this ROCm supports it, torch.sparse.mm on a CSR matrix built outside the timed span is timed too.  float32 features, F = 64 and 256.
+Medians of 5 after a warm-up, host clock around a synchronise; the five times are printed too.  Prints one JSON line per graph and F
+(and appends it to --out).
+
+  ba1m : BA(1M, 10), depths [N/8, N/4, N/2], views=2, random (6 snapshots, 6 layers)
+  c5   : bench config 5, a node_ptr batch of 1024 x BA(4096, 8), depths [n/8, n/4, n/2] (3,072 snapshots, 3 layers)
+    python tools/propagate_latency.py --graphs ba1m,c5
+    python tools/propagate_latency.py --graphs ba1m --features 256 --no-torch     # the calls alone (for rocprofv3 --kernel-trace --stats)
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from rlap_amd import graphs, ops  # noqa: E402
+
+GRAPHS = {"ba1m": (1000000, 10, 1, 2), "c5": (4096, 8, 1024, 1)}   # (nodes per graph, m, graphs, views)
+
+
+def timed(fn, reps=5):
+    fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = fn()
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(ts), [round(t, 3) for t in ts], res
+
+
+def torch_product(ei, val, bounds, N, x, transpose=False):
+    """[y_l] per layer from the list of ops.snapshot_gcn_norm."""
+    out = []
+    for a, b in bounds:
+        src, dst = (ei[1, a:b], ei[0, a:b]) if transpose else (ei[0, a:b], ei[1, a:b])
+        out.append(torch.zeros(N, x.shape[1], dtype=x.dtype, device=x.device).index_add_(0, dst, val[a:b, None] * x[src]))
+    return out
+
+
+def run(name, F, args, fh):
+    n, m, G, K = GRAPHS[name]
+    e1 = graphs.barabasi_albert(n, m, 1)
+    ei = (torch.cat([e1 + g * n for g in range(G)], dim=1) if G > 1 else e1).cuda()
+    N = G * n
+    node_ptr = [g * n for g in range(G + 1)] if G > 1 else None
+    sc, ptr = ops.approximate_cholesky_depths(ei, None, N, [n // 8, n // 4, n // 2], "random", "asc", node_ptr=node_ptr, views=K, seed=1,
+                                              return_device="same")
+    del ei
+    S = ptr.numel() - 1
+    L = S // G
+    rows = int(sc.shape[0])
+    x = torch.randn(N, F, dtype=torch.float32, generator=torch.Generator().manual_seed(F)).cuda()
+    rec = {"graph": name, "F": F, "snapshots": S, "layers": L, "rows": rows}
+    t, ts, y = timed(lambda: ops.snapshot_propagate(sc, ptr, N, x, node_ptr=node_ptr), args.reps)
+    st = dict(ops.last_stats)
+    M = st["entries"]
+    # algorithmic bytes of the main kernel (k_sp_rows): per entry the gathered row of x, the 24-byte row, rb and blk and two dis; y
+    # written once.  Divide them by that kernel's time from a rocprofv3 --kernel-trace --stats run of this tool with --no-torch
+    # for its achieved rate (the gathers are partly served from L2 and the Infinity Cache: a rate, not an HBM figure); divided by
+    # the whole call, column pass and host synchronisation included, they give the call's rate below.
+    sum_bytes = M * (4 * F + 24 + 4 + 4 + 16) + 4 * L * N * F
+    rec.update({"forward_ms": round(t, 3), "forward_runs_ms": ts, "entries": M, "blocks": st["blocks"], "chunked_lists": st["chunked_lists"],
+                "host_syncs": st["host_syncs"], "arena_bytes": st["arena_bytes"], "main_kernel_bytes": sum_bytes,
+                "whole_call_bytes_per_s": round(sum_bytes / (t * 1e-3), 1)})
+
+    def both():
+        out = ops.snapshot_propagate(sc, ptr, N, x, node_ptr=node_ptr)
+        return ops.snapshot_propagate(sc, ptr, N, out, node_ptr=node_ptr, transpose=True)
+    t2, ts2, _ = timed(both, args.reps)
+    rec.update({"forward_transpose_ms": round(t2, 3), "forward_transpose_runs_ms": ts2})
+    if not args.no_torch:
+        tl, tsl, (eidx, val, eptr) = timed(lambda: ops.snapshot_gcn_norm(sc, ptr, N, node_ptr=node_ptr), args.reps)
+        e = eptr.tolist()
+        bounds = [(e[l * G], e[(l + 1) * G]) for l in range(L)]
+        tt, tst, want = timed(lambda: torch_product(eidx, val, bounds, N, x), args.reps)
+        diff = max(float((y[l] - want[l]).abs().max()) for l in range(L))
+        scale = max(float(want[l].abs().max()) for l in range(L))
+        rec.update({"gcn_norm_ms": round(tl, 3), "torch_ms": round(tt, 3), "torch_runs_ms": tst, "torch_over_call": round(tt / t, 3),
+                    "torch_with_list_over_call": round((tt + tl) / t, 3), "max_abs_diff_to_torch_f32": diff, "max_abs_torch": scale})
+
+        def torch_both():
+            out = torch_product(eidx, val, bounds, N, x)
+            return [torch_product(eidx, val, [bounds[l]], N, out[l], transpose=True)[0] for l in range(L)]
+        del want
+        tt2, tst2, _ = timed(torch_both, args.reps)
+        rec.update({"torch_forward_transpose_ms": round(tt2, 3), "torch_forward_transpose_runs_ms": tst2,
+                    "torch_forward_transpose_over_call": round(tt2 / t2, 3)})
+        try:   # CSR per layer, built outside the timed span (row = target)
+            mats = [torch.sparse_coo_tensor(torch.stack([eidx[1, a:b], eidx[0, a:b]]), val[a:b], (N, N)).coalesce().to_sparse_csr()
+                    for a, b in bounds]
+            ts_, tss, got = timed(lambda: [torch.sparse.mm(mt, x) for mt in mats], args.reps)
+            rec.update({"torch_csr_ms": round(ts_, 3), "torch_csr_runs_ms": tss, "torch_csr_over_call": round(ts_ / t, 3),
+                        "max_abs_diff_to_csr_f32": max(float((y[l] - got[l]).abs().max()) for l in range(L))})
+            del mats, got
+        except Exception as exc:   # (not every ROCm build has the CSR product)
+            rec["torch_csr_ms"] = f"not available: {type(exc).__name__}"
+        del eidx, val
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if fh is not None:
+        fh.write(line + "\n")
+        fh.flush()
+    del sc, x, y
+    torch.cuda.empty_cache()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--graphs", default="ba1m,c5")
+    ap.add_argument("--features", default="64,256")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--no-torch", action="store_true", help="time the calls alone")
+    ap.add_argument("--out", default=None, help="append the JSON lines to this file")
+    args = ap.parse_args()
+    fh = open(args.out, "a") if args.out else None
+    for g in args.graphs.split(","):
+        for F in args.features.split(","):
+            run(g, int(F), args, fh)
+
+
+if __name__ == "__main__":
+    main()
