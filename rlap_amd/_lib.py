@@ -43,7 +43,14 @@ RETRY_POOL, RETRY_LOG, RETRY_RNG, RETRY_SCRATCH, RETRY_SORT, RETRY_FLOW_SCRATCH,
 FLOW_ABORT_REASONS = {0: "none", 1: "stall watchdog", 2: "sorted-index check", 3: "appended count over 2^22", 4: "column longer than its buffer"}
 
 
-class Stats(ctypes.Structure):
+class _Report(ctypes.Structure):
+    """What a call writes for its caller: rlap_stats and the info structures of the snapshot calls (include/rlap_hip.h)."""
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_ if f != "pad"}
+
+
+class Stats(_Report):
     _fields_ = [
         ("nnz", ctypes.c_int64), ("n_eliminated", ctypes.c_int64), ("n_draws", ctypes.c_int64),
         ("out_rows", ctypes.c_int64), ("live_entries", ctypes.c_int64),
@@ -54,11 +61,8 @@ class Stats(ctypes.Structure):
         ("elim_kernel", ctypes.c_int32), ("retry_causes", ctypes.c_int32), ("flow_abort", ctypes.c_int32), ("n_rounds_narrow", ctypes.c_int32),
     ]
 
-    def as_dict(self):
-        return {f: getattr(self, f) for f, _ in self._fields_}
 
-
-class SnapshotInfo(ctypes.Structure):
+class SnapshotInfo(_Report):
     """rlap_snapshot_info (include/rlap_hip.h)."""
     _fields_ = [
         ("small_segments", ctypes.c_int64), ("large_segments", ctypes.c_int64), ("lanczos_steps", ctypes.c_int64),
@@ -66,11 +70,8 @@ class SnapshotInfo(ctypes.Structure):
         ("not_converged", ctypes.c_int32),
     ]
 
-    def as_dict(self):
-        return {f: getattr(self, f) for f, _ in self._fields_}
 
-
-class PprInfo(ctypes.Structure):
+class PprInfo(_Report):
     """rlap_ppr_info (include/rlap_hip.h)."""
     _fields_ = [
         ("steps", ctypes.c_int64), ("small_tiles", ctypes.c_int64), ("large_tiles", ctypes.c_int64), ("groups", ctypes.c_int64),
@@ -78,41 +79,29 @@ class PprInfo(ctypes.Structure):
         ("pad", ctypes.c_int32),
     ]
 
-    def as_dict(self):
-        return {f: getattr(self, f) for f, _ in self._fields_ if f != "pad"}
 
-
-class SubgraphInfo(ctypes.Structure):
+class SubgraphInfo(_Report):
     """rlap_subgraph_info (include/rlap_hip.h)."""
     _fields_ = [
         ("rows_kept", ctypes.c_int64), ("ids_written", ctypes.c_int64), ("arena_bytes", ctypes.c_int64), ("host_syncs", ctypes.c_int32),
         ("pad", ctypes.c_int32),
     ]
 
-    def as_dict(self):
-        return {f: getattr(self, f) for f, _ in self._fields_ if f != "pad"}
 
-
-class GcnInfo(ctypes.Structure):
+class GcnInfo(_Report):
     """rlap_gcn_info (include/rlap_hip.h)."""
     _fields_ = [
         ("entries", ctypes.c_int64), ("loops_removed", ctypes.c_int64), ("arena_bytes", ctypes.c_int64), ("host_syncs", ctypes.c_int32),
         ("pad", ctypes.c_int32),
     ]
 
-    def as_dict(self):
-        return {f: getattr(self, f) for f, _ in self._fields_ if f != "pad"}
 
-
-class SpmmInfo(ctypes.Structure):
+class SpmmInfo(_Report):
     """rlap_spmm_info (include/rlap_hip.h)."""
     _fields_ = [
         ("entries", ctypes.c_int64), ("blocks", ctypes.c_int64), ("chunked_lists", ctypes.c_int64), ("arena_bytes", ctypes.c_int64),
         ("host_syncs", ctypes.c_int32), ("pad", ctypes.c_int32),
     ]
-
-    def as_dict(self):
-        return {f: getattr(self, f) for f, _ in self._fields_ if f != "pad"}
 
 
 def load():

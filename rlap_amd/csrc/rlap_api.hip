@@ -18,6 +18,7 @@
 #include "rlap_core.h"
 #include "rlap_kernels.h"
 #include "rlap_cheb.h"
+#include "rlap_snapshot.h"
 #include "rlap_ppr.h"
 #include "rlap_stats.h"
 #include "rlap_subgraph.h"
@@ -44,8 +45,7 @@ struct DevBuf {
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
-#define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { std::fprintf(stderr, "[rlap_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(_e), __FILE__, __LINE__); return RLAP_E_HIP; } } while (0)
-#define ENSURE(buf, bytes) HIPCHK((buf).ensure((size_t)(bytes)))
+#define ENSURE(buf, bytes) RLAP_HIPCHK((buf).ensure((size_t)(bytes)))
 
 inline unsigned nblk(int64_t n, int bs) { return (unsigned)std::max<int64_t>(1, (n + bs - 1) / bs); }
 
@@ -55,16 +55,6 @@ inline unsigned nblk(int64_t n, int bs) { return (unsigned)std::max<int64_t>(1, 
 // and the handle's growth factors).  The arena is either the caller's (rlap_set_workspace: torch's allocator in rlap_amd/ops.py -- the
 // reference lets torch allocate what the op needs, py_api_binder.cc:42) or the handle's own (one hipMalloc, grown only when a call needs
 // a larger size class than any before it).  The cached uniform table is a second, persistent buffer under the same rule.
-struct Carver {
-    char* base; size_t off;
-    template <class T> T* take(int64_t count) {
-        off = (off + 255) & ~(size_t)255;
-        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += sizeof(T) * (size_t)(count > 0 ? count : 0);
-        return p;
-    }
-};
-
 struct rlap_handle_s {
     int device = 0;
     int n_cu = 0;                 // compute units of `device`
@@ -110,6 +100,20 @@ struct rlap_handle_s {
 
 namespace {
 
+// The arena of a call that wants `need` bytes: the caller's (rlap_set_workspace) or the handle's own, grown when it is too small.
+// ws_needed is set first: RLAP_E_WORKSPACE is answered by rlap_workspace_needed().
+int arena(rlap_handle h, size_t need, void** base, size_t* have) {
+    h->ws_needed = need;
+    if (h->ext_ws) {
+        if (need > h->ext_ws_bytes) return RLAP_E_WORKSPACE;   // the caller allocates rlap_workspace_needed() bytes and calls again
+        *base = h->ext_ws; *have = h->ext_ws_bytes;
+    } else {
+        ENSURE(h->own_ws, need);
+        *base = h->own_ws.p; *have = h->own_ws.cap;
+    }
+    return RLAP_OK;
+}
+
 // device-side scalars of a call, zeroed by one memset
 struct Scalars {
     int32_t flags[FLAG_COUNT];
@@ -135,7 +139,7 @@ int ensure_rng(rlap_handle h, int64_t count) {
         buf = h->own_rng.as<double>(); want = (int64_t)(h->own_rng.cap / sizeof(double));
     }
     hipLaunchKernelGGL(k_mt19937_64_table, dim3(1), dim3(320), 0, h->stream, buf, want);
-    HIPCHK(hipGetLastError());
+    RLAP_HIPCHK(hipGetLastError());
     h->rng_ptr = buf; h->rng_len = want;
     return RLAP_OK;
 }
@@ -146,20 +150,20 @@ struct SortTmp { void* p; size_t bytes; };
 template <class K, class V>
 int sort_pairs(rlap_handle h, const SortTmp& T, K* k_in, K* k_out, V* v_in, V* v_out, int64_t n, unsigned begin_bit, unsigned end_bit) {
     size_t bytes = 0;
-    HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, k_in, k_out, v_in, v_out, (size_t)n, begin_bit, end_bit, h->stream));
+    RLAP_HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, k_in, k_out, v_in, v_out, (size_t)n, begin_bit, end_bit, h->stream));
     if (bytes > T.bytes) return RLAP_E_INTERNAL;   // (sort_tmp_bytes asks the same questions up front)
     bytes = T.bytes;
-    HIPCHK(rocprim::radix_sort_pairs(T.p, bytes, k_in, k_out, v_in, v_out, (size_t)n, begin_bit, end_bit, h->stream));
+    RLAP_HIPCHK(rocprim::radix_sort_pairs(T.p, bytes, k_in, k_out, v_in, v_out, (size_t)n, begin_bit, end_bit, h->stream));
     return RLAP_OK;
 }
 
 template <class In, class Out>
 int excl_scan(rlap_handle h, const SortTmp& T, In* in, Out* out, int64_t n) {
     size_t bytes = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, bytes, in, out, (Out)0, (size_t)n, rocprim::plus<Out>(), h->stream));
+    RLAP_HIPCHK(rocprim::exclusive_scan(nullptr, bytes, in, out, (Out)0, (size_t)n, rocprim::plus<Out>(), h->stream));
     if (bytes > T.bytes) return RLAP_E_INTERNAL;
     bytes = T.bytes;
-    HIPCHK(rocprim::exclusive_scan(T.p, bytes, in, out, (Out)0, (size_t)n, rocprim::plus<Out>(), h->stream));
+    RLAP_HIPCHK(rocprim::exclusive_scan(T.p, bytes, in, out, (Out)0, (size_t)n, rocprim::plus<Out>(), h->stream));
     return RLAP_OK;
 }
 
@@ -171,18 +175,18 @@ int sort_tmp_bytes(int64_t Eeff, int64_t N, int64_t G, int64_t S, bool flow, siz
     hipStream_t s0 = nullptr;
     const unsigned kbits = bits_for((uint64_t)(N > 1 ? N - 1 : 1)), gbits = bits_for((uint64_t)(G > 0 ? G - 1 : 0));
     if (Eeff > 0) {
-        b = 0; HIPCHK(rocprim::radix_sort_pairs(nullptr, b, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)Eeff, 0u, std::min(64u, 2 * kbits + 1), s0)); mx = std::max(mx, b);
+        b = 0; RLAP_HIPCHK(rocprim::radix_sort_pairs(nullptr, b, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)Eeff, 0u, std::min(64u, 2 * kbits + 1), s0)); mx = std::max(mx, b);
         rocprim::counting_iterator<uint32_t> iota(0u);
-        b = 0; HIPCHK(rocprim::radix_sort_pairs(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, iota, (uint32_t*)nullptr, (size_t)Eeff, 0u, std::min(32u, kbits + 1), s0)); mx = std::max(mx, b);
-        b = 0; HIPCHK(rocprim::exclusive_scan(nullptr, b, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t)0, (size_t)(Eeff + 1), rocprim::plus<int32_t>(), s0)); mx = std::max(mx, b);
+        b = 0; RLAP_HIPCHK(rocprim::radix_sort_pairs(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, iota, (uint32_t*)nullptr, (size_t)Eeff, 0u, std::min(32u, kbits + 1), s0)); mx = std::max(mx, b);
+        b = 0; RLAP_HIPCHK(rocprim::exclusive_scan(nullptr, b, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t)0, (size_t)(Eeff + 1), rocprim::plus<int32_t>(), s0)); mx = std::max(mx, b);
     }
     const size_t Nn = (size_t)std::max<int64_t>(N, 1);
-    b = 0; HIPCHK(rocprim::radix_sort_pairs(nullptr, b, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, Nn, 0u, 32u + gbits, s0)); mx = std::max(mx, b);
-    b = 0; HIPCHK(rocprim::radix_sort_pairs(nullptr, b, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, Nn, 0u, 64u, s0)); mx = std::max(mx, b);
-    b = 0; HIPCHK(rocprim::exclusive_scan(nullptr, b, (int32_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)(S + 1), rocprim::plus<int64_t>(), s0)); mx = std::max(mx, b);
+    b = 0; RLAP_HIPCHK(rocprim::radix_sort_pairs(nullptr, b, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, Nn, 0u, 32u + gbits, s0)); mx = std::max(mx, b);
+    b = 0; RLAP_HIPCHK(rocprim::radix_sort_pairs(nullptr, b, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, Nn, 0u, 64u, s0)); mx = std::max(mx, b);
+    b = 0; RLAP_HIPCHK(rocprim::exclusive_scan(nullptr, b, (int32_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)(S + 1), rocprim::plus<int64_t>(), s0)); mx = std::max(mx, b);
     if (flow && Eeff > 0) {   // tag order of the surviving columns (rlap_flow.hip): one (column, tag) sort over at most Eeff appended entries
-        b = 0; HIPCHK(rocprim::radix_sort_pairs(nullptr, b, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)Eeff, 0u, 64u, s0)); mx = std::max(mx, b);
-        b = 0; HIPCHK(rocprim::exclusive_scan(nullptr, b, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t)0, (size_t)(S + 1), rocprim::plus<int32_t>(), s0)); mx = std::max(mx, b);
+        b = 0; RLAP_HIPCHK(rocprim::radix_sort_pairs(nullptr, b, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)Eeff, 0u, 64u, s0)); mx = std::max(mx, b);
+        b = 0; RLAP_HIPCHK(rocprim::exclusive_scan(nullptr, b, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t)0, (size_t)(S + 1), rocprim::plus<int32_t>(), s0)); mx = std::max(mx, b);
     }
     *out = mx;
     return RLAP_OK;
@@ -315,7 +319,7 @@ inline size_t host_block_bytes(int64_t G, int64_t D) {
     return 16 * (size_t)(G + 1) + sizeof(GraphDesc) * (size_t)G + (D > 0 ? 8 * (size_t)D * (size_t)(2 * G + 1) : 0);
 }
 // the arena's layout: run once with a null base to learn the size, once more to place the buffers
-size_t carve(Carver& C, const Sizes& z, WS& W) {
+size_t carve(Carve& C, const Sizes& z, WS& W) {
     const int64_t G = z.G, N = z.N, S = z.S, Ealloc = std::max<int64_t>(z.Eeff, 1), BT = z.bucket_total;
     W.scal.p = C.take<Scalars>(1);
     W.results.p = C.take<char>((int64_t)z.res_bytes);
@@ -425,7 +429,7 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
     const int64_t E1eff = c.symmetrize ? 2 * E : E;
     const int64_t Eeff = K * E1eff;
     if (N >= (int64_t)1 << 30 || Eeff >= (int64_t)1 << 31 || G >= (int64_t)1 << 30) return RLAP_E_TOO_LARGE;
-    if (h->timing) HIPCHK(hipEventRecord(h->ev[0], s));
+    if (h->timing) RLAP_HIPCHK(hipEventRecord(h->ev[0], s));
 
     rlap_stats st;
     std::memset(&st, 0, sizeof(st));
@@ -486,22 +490,16 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
     // ---------------- workspace: one arena, no allocation unless this call is of a larger size class than any before ----------------
     WS W;
     {
-        Carver dry{nullptr, 0};
+        Carve dry{nullptr, 0};
         const size_t need = carve(dry, z, W);
-        h->ws_needed = need;
-        char* base = nullptr;
-        if (h->ext_ws) {
-            if (need > h->ext_ws_bytes) return RLAP_E_WORKSPACE;   // the caller allocates rlap_workspace_needed() bytes and calls again
-            base = static_cast<char*>(h->ext_ws);
-        } else {
-            ENSURE(h->own_ws, need);
-            base = h->own_ws.as<char>();
-        }
-        Carver real{base, 0};
+        void* base = nullptr;
+        size_t have = 0;
+        { int rc = arena(h, need, &base, &have); if (rc) return rc; }
+        Carve real{static_cast<char*>(base), 0};
         carve(real, z, W);
         if (h->poison >= 0) {   // debug: whatever a kernel reads without having been given it is this byte, not the previous call's data
-            HIPCHK(hipMemsetAsync(base, h->poison, need, s));
-            if (c.d_out && c.out_cap > 0) HIPCHK(hipMemsetAsync(c.d_out, h->poison, sizeof(double) * 3 * (size_t)c.out_cap, s));
+            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, s));
+            if (c.d_out && c.out_cap > 0) RLAP_HIPCHK(hipMemsetAsync(c.d_out, h->poison, sizeof(double) * 3 * (size_t)c.out_cap, s));
         }
     }
     {
@@ -509,7 +507,7 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
         if (pinned_need > h->h_results_cap) {
             if (h->h_results) (void)hipHostFree(h->h_results);
             h->h_results = nullptr; h->h_results_cap = 0;
-            HIPCHK(hipHostMalloc(&h->h_results, pinned_need + 65536, hipHostMallocDefault));
+            RLAP_HIPCHK(hipHostMalloc(&h->h_results, pinned_need + 65536, hipHostMallocDefault));
             h->h_results_cap = pinned_need + 65536;
         }
     }
@@ -538,7 +536,7 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
             std::memcpy(dp, c.h_depths, 8 * (size_t)(nseg * G));
             std::memcpy(dp + 8 * nseg * G, seg_sb.data(), 8 * seg_sb.size());
         }
-        HIPCHK(hipMemcpyAsync(W.node_ptr_d.p, stage, host_block_bytes(G, z.D), hipMemcpyHostToDevice, s));
+        RLAP_HIPCHK(hipMemcpyAsync(W.node_ptr_d.p, stage, host_block_bytes(G, z.D), hipMemcpyHostToDevice, s));
     }
     {
         Fills F;
@@ -572,8 +570,8 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
         if (const char* e = std::getenv("RLAP_SORT_SKIP_MIN")) skip_min = std::atoll(e);   // (tests: exercise the order check on small inputs)
         if (E1eff >= skip_min && !c.symmetrize && !h->force_sort) {
             int32_t fl[FLAG_COUNT];
-            HIPCHK(hipMemcpyAsync(fl, flags, sizeof(fl), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
+            RLAP_HIPCHK(hipMemcpyAsync(fl, flags, sizeof(fl), hipMemcpyDeviceToHost, s));
+            RLAP_HIPCHK(hipStreamSynchronize(s));
             if (!fl[FLAG_UNSORTED_CR]) skip_sort = true;
             else if (!fl[FLAG_UNSORTED_RC] && !fl[FLAG_RANGE]) {
                 hipLaunchKernelGGL(k_edge_keys, dim3(nblk(E1eff, 256)), dim3(256), 0, s, c.d_col, c.d_row, c.d_w, E, N1, G1 > 1 ? W.vgraph.as<int32_t>() : (const int32_t*)nullptr,
@@ -609,10 +607,10 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
         uint32_t* T = skeys + Eeff;
         rocprim::counting_iterator<uint32_t> iota(0u);
         size_t bytes = 0;
-        HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, rowid, skeys, iota, T, (size_t)E1eff, 0u, (unsigned)std::min(32, kbits + 1), s));
+        RLAP_HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, rowid, skeys, iota, T, (size_t)E1eff, 0u, (unsigned)std::min(32, kbits + 1), s));
         if (bytes > ST.bytes) return RLAP_E_INTERNAL;
         bytes = ST.bytes;
-        HIPCHK(rocprim::radix_sort_pairs(ST.p, bytes, rowid, skeys, iota, T, (size_t)E1eff, 0u, (unsigned)std::min(32, kbits + 1), s));
+        RLAP_HIPCHK(rocprim::radix_sort_pairs(ST.p, bytes, rowid, skeys, iota, T, (size_t)E1eff, 0u, (unsigned)std::min(32, kbits + 1), s));
         hipLaunchKernelGGL(k_twin_sorted, dim3((unsigned)std::min<int64_t>(nblk(E1eff, 256), 4096)), dim3(256), 0, s, W.ent.as<Slot>(), T, nnz_p, acc);
         hipLaunchKernelGGL(k_twin_store, dim3((unsigned)std::min<int64_t>(nblk(E1eff, 256), 4096)), dim3(256), 0, s, W.ent.as<Slot>(), T, nnz_p);
     }
@@ -645,7 +643,7 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
             hipLaunchKernelGGL(k_widen_u32, dim3(nblk(N, 256)), dim3(256), 0, s, W.sval1.as<uint32_t>(), (int32_t)N, W.genperm.as<int64_t>());
             d_perm = W.genperm.as<int64_t>();
         } else {
-            HIPCHK(hipMemsetAsync(W.permchk.p, 0, 4 * N, s));
+            RLAP_HIPCHK(hipMemsetAsync(W.permchk.p, 0, 4 * N, s));
             hipLaunchKernelGGL(k_perm_check, dim3(nblk(N, 256)), dim3(256), 0, s, d_perm, W.vgraph.as<int32_t>(), W.gd_d.as<GraphDesc>(), (int32_t)N,
                                W.permchk.as<int32_t>(), flags);
         }
@@ -671,7 +669,7 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
     ES.prof = nullptr;
     const char* prof_env = std::getenv("RLAP_PHASE_PROFILE");   // diagnostic only: per-phase clock sums of graph 0
     if (prof_env && prof_env[0] == '1' && h->prof.p) {
-        HIPCHK(hipMemsetAsync(h->prof.p, 0, 8 * 80, s));
+        RLAP_HIPCHK(hipMemsetAsync(h->prof.p, 0, 8 * 80, s));
         ES.prof = h->prof.as<long long>();
     }
     ES.poison = h->poison;
@@ -679,7 +677,7 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
     ES.narrow_batch = NARROW_BATCH;
     if (const char* e = std::getenv("RLAP_NARROW_BATCH")) ES.narrow_batch = std::min(256, std::max(1, std::atoi(e)));   // diagnostic override
 
-    if (h->timing) HIPCHK(hipEventRecord(h->ev[1], s));
+    if (h->timing) RLAP_HIPCHK(hipEventRecord(h->ev[1], s));
     // ---------------- elimination ----------------
     // 128-slot candidates for o_v = random when the columns run long: 12 or more entries per vertex on average (from the input
     // sizes: no read-back).  Measured (ms per call, 64 -> 128 slots): BA(1M,10) 2950 -> 2180, BA(169343,7) 260 -> 248, BA(4096,8)
@@ -704,11 +702,11 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
         const char* trace_env = std::getenv("RLAP_FLOW_TRACE");   // diagnostic only: per-position time stamps, written to the named file after the call
         if (trace_env && trace_env[0]) {
             ENSURE(h->trace, (size_t)z.flow_Q * 48);
-            HIPCHK(hipMemsetAsync(h->trace.p, 0, (size_t)z.flow_Q * 48, s));
+            RLAP_HIPCHK(hipMemsetAsync(h->trace.p, 0, (size_t)z.flow_Q * 48, s));
             FP.trace = h->trace.as<long long>();
         }
         if (const char* e = std::getenv("RLAP_FLOW_STALL_MS")) FP.spin_limit = std::max(1, std::atoi(e));
-        HIPCHK(hipMemsetAsync(W.f_ctrl.p, 0, FC_WORDS * 4, s));
+        RLAP_HIPCHK(hipMemsetAsync(W.f_ctrl.p, 0, FC_WORDS * 4, s));
         FA.qorder = nullptr; FA.Qclaim = FA.Q;
         const bool interleave = G > 1 && nelim_total > 0;   // a batch: claims run over the graphs' positions interleaved, so that every graph has waves
         launch_flow_setup(s, A, FA, FP, W.slot_col.as<int32_t>(), nnz_p, (int32_t)N, Eeff, interleave ? W.skey0.as<uint64_t>() : nullptr,
@@ -763,10 +761,10 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
             } else {
                 launch_eliminate_batch(c.o_v, c.o_n, (unsigned)G, h->n_cu, s, A, gd_d, ES, W.batch_pos.as<int32_t>(), flags, acc, wide);
             }
-            HIPCHK(hipGetLastError());
+            RLAP_HIPCHK(hipGetLastError());
             if (depths) hipLaunchKernelGGL(k_depth_stop, dim3(1), dim3(256), 0, s, gd_d, (int32_t)G, stop_d);
         }
-        if (h->timing) HIPCHK(hipEventRecord(h->ev[2], s));
+        if (h->timing) RLAP_HIPCHK(hipEventRecord(h->ev[2], s));
 
         // ---------------- output ----------------
         uint32_t* order = nullptr;
@@ -785,7 +783,7 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
                 const unsigned kb = bits_for((uint64_t)std::max<int64_t>(Sk - 1, 1)) + 32u;
                 { int rc = sort_pairs(h, ST, W.keys0.as<uint64_t>(), W.keys1.as<uint64_t>(), W.idx0.as<uint32_t>(), W.idx1.as<uint32_t>(), ro_cap, 0, std::min(64u, kb)); if (rc) return rc; }
                 launch_flow_ro_permute(s, A, FA, W.f_rooff.as<int32_t>(), (int32_t)Sk, W.idx1.as<uint32_t>(), W.keys1.as<uint64_t>(), home, ro_cap, reinterpret_cast<Slot*>(W.tmp_val.p));
-                HIPCHK(hipGetLastError());
+                RLAP_HIPCHK(hipGetLastError());
                 permuted = true;
             }
         } else {
@@ -799,13 +797,13 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
         if (Sk > 0)
             hipLaunchKernelGGL(k_sc_ext, dim3(nblk(Sk, 256)), dim3(256), 0, s, order, W.colptr.as<int32_t>(), W.vrec.as<VRec>(), (int32_t)Sk, flags, acc, W.ext.as<int32_t>(), stop_d);
         { int rc = excl_scan(h, ST, W.ext.as<int32_t>(), W.tmp_off.as<int64_t>(), Sk + 1); if (rc) return rc; }
-        if (h->timing) HIPCHK(hipEventRecord(h->ev[3], s));
+        if (h->timing) RLAP_HIPCHK(hipEventRecord(h->ev[3], s));
         if (Sk > 0) {
             int32_t* tiercounts = reinterpret_cast<int32_t*>(counters + 4);   // 8 ints: tiers 0..7
             if (!h->big_attr_set) {
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sc_merge_big), hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS_BYTES));
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sc_merge_mw<8>), hipFuncAttributeMaxDynamicSharedMemorySize, MW_BIG_LDS_BYTES));
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sc_merge_mw<4>), hipFuncAttributeMaxDynamicSharedMemorySize, MW_MID_LDS_BYTES));
+                RLAP_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sc_merge_big), hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS_BYTES));
+                RLAP_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sc_merge_mw<8>), hipFuncAttributeMaxDynamicSharedMemorySize, MW_BIG_LDS_BYTES));
+                RLAP_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sc_merge_mw<4>), hipFuncAttributeMaxDynamicSharedMemorySize, MW_MID_LDS_BYTES));
                 h->big_attr_set = true;
             }
             ScLaunch X;
@@ -814,18 +812,18 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
             launch_sc_merge(X, A, gd_d, W.vgraph.as<int32_t>(), order, W.ext.as<int32_t>(), W.tmp_off.as<int64_t>(), (int32_t)Sk,
                             W.tmp_nbr.as<int32_t>(), W.tmp_val.as<double>(), W.cnt.as<int32_t>(), SS, live, W.biglist.as<int32_t>(), tiercounts,
                             W.hugelists.as<uint16_t>());
-            HIPCHK(hipGetLastError());
+            RLAP_HIPCHK(hipGetLastError());
         }
-        if (h->timing) HIPCHK(hipEventRecord(h->ev[4], s));
+        if (h->timing) RLAP_HIPCHK(hipEventRecord(h->ev[4], s));
         { int rc = excl_scan(h, ST, W.cnt.as<int32_t>(), W.row_off.as<int64_t>(), Sk + 1); if (rc) return rc; }
-        if (h->timing) HIPCHK(hipEventRecord(h->ev[5], s));
+        if (h->timing) RLAP_HIPCHK(hipEventRecord(h->ev[5], s));
         if (Sk > 0 && c.out_cap > 0) {
             const int64_t rows_ub = std::min<int64_t>(c.out_cap, slot_cap);
             unsigned cgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows_ub + 255) / 256, 256 * 8));
             hipLaunchKernelGGL(k_sc_compact, dim3(cgrid), dim3(256), 0, s, order, W.cnt.as<int32_t>(), W.row_off.as<int64_t>(), W.tmp_off.as<int64_t>(),
                                W.tmp_nbr.as<int32_t>(), W.tmp_val.as<double>(), (int32_t)Sk, c.d_out, c.out_cap, K > 1 ? (int32_t)N1 : 0,
                                depths ? (const int64_t*)(out_ptr_d + seg * G) : (const int64_t*)nullptr);
-            HIPCHK(hipGetLastError());
+            RLAP_HIPCHK(hipGetLastError());
         }
         if (depths) {
             // the next segment continues from the elimination's own state: the tag-order permutation is undone (the same kernels with
@@ -833,34 +831,34 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
             // staging copy is free again), so that every twin link points where it did
             if (permuted && !last) {
                 launch_flow_ro_permute(s, A, FA, W.f_rooff.as<int32_t>(), (int32_t)Sk, home, W.keys1.as<uint64_t>(), W.idx1.as<uint32_t>(), ro_cap, reinterpret_cast<Slot*>(W.tmp_val.p));
-                HIPCHK(hipGetLastError());
+                RLAP_HIPCHK(hipGetLastError());
             }
             hipLaunchKernelGGL(k_depth_close, dim3(1), dim3(256), 0, s, W.row_off.as<int64_t>(), W.depth_sb.as<int64_t>() + seg * (G + 1), (int32_t)G,
                                out_ptr_d + seg * G, counters, live, scr_max_d, last ? -1 : (int32_t)(N - seg_Q[(size_t)seg + 1]), W.ext.as<int32_t>(),
                                W.cnt.as<int32_t>());
-            HIPCHK(hipGetLastError());
+            RLAP_HIPCHK(hipGetLastError());
         }
-        if (h->timing) HIPCHK(hipEventRecord(h->ev[6], s));
+        if (h->timing) RLAP_HIPCHK(hipEventRecord(h->ev[6], s));
     }
     // ---------------- the one read-back ----------------
     if (!depths)
         hipLaunchKernelGGL(k_graph_rows, dim3(nblk(G + 1, 256)), dim3(256), 0, s, W.surv_base_d.as<int64_t>(), W.row_off.as<int64_t>(), (int32_t)G, out_ptr_d);
     hipLaunchKernelGGL(k_collect, dim3(1), dim3(256), 0, s, flags, acc, nnz_p, counters, live, W.tmp_off.as<int64_t>(), W.row_off.as<int64_t>(), (int32_t)S,
                        W.gd_d.as<GraphDesc>(), (int32_t)G, W.pool_top.as<int32_t>(), W.bs_pool_top.as<int32_t>(), flow ? W.f_ctrl.as<int32_t>() + FC_REASON : nullptr, res_d);
-    HIPCHK(hipMemcpyAsync(h->h_results, W.results.p, res_bytes, hipMemcpyDeviceToHost, s));
-    if (h->timing) HIPCHK(hipEventRecord(h->ev[7], s));
-    HIPCHK(hipStreamSynchronize(s));
+    RLAP_HIPCHK(hipMemcpyAsync(h->h_results, W.results.p, res_bytes, hipMemcpyDeviceToHost, s));
+    if (h->timing) RLAP_HIPCHK(hipEventRecord(h->ev[7], s));
+    RLAP_HIPCHK(hipStreamSynchronize(s));
     const CallResults& R = *reinterpret_cast<const CallResults*>(h->h_results);
     const int64_t* out_ptr_h = reinterpret_cast<const int64_t*>(reinterpret_cast<const CallResults*>(h->h_results) + 1);
 
     if (flow) if (const char* trace_env = std::getenv("RLAP_FLOW_TRACE")) if (trace_env[0] && h->trace.p) {
         std::vector<long long> tr((size_t)z.flow_Q * 6);
-        HIPCHK(hipMemcpy(tr.data(), h->trace.p, tr.size() * 8, hipMemcpyDeviceToHost));
+        RLAP_HIPCHK(hipMemcpy(tr.data(), h->trace.p, tr.size() * 8, hipMemcpyDeviceToHost));
         if (FILE* f = std::fopen(trace_env, "wb")) { std::fwrite(tr.data(), 8, tr.size(), f); std::fclose(f); }
     }
     if (ES.prof && flow) {
         long long pr[40];
-        HIPCHK(hipMemcpy(pr, h->prof.p, sizeof(pr), hipMemcpyDeviceToHost));
+        RLAP_HIPCHK(hipMemcpy(pr, h->prof.p, sizeof(pr), hipMemcpyDeviceToHost));
         const char* names[11] = {"claim + wait for pend == 0", "gather", "sort by id (+ tag order)", "merge + publish", "o_n order", "cumsum + recurrence", "look-back wait", "sample", "commit (claims, chunks, stores)", "drain", "decrements"};
         std::fprintf(stderr, "[rlap flow profile] positions=%lld mean live=%.1f mean extent=%.1f; sums over all waves, us per position\n", pr[16], pr[16] ? (double)pr[17] / pr[16] : 0.0, pr[16] ? (double)pr[18] / pr[16] : 0.0);
         for (int k = 0; k < 11; ++k) std::fprintf(stderr, "  %-34s %10.3f ms total  %8.2f us/pos\n", names[k], pr[k] / 1e5, pr[16] ? pr[k] / 100.0 / (double)pr[16] : 0.0);
@@ -869,7 +867,7 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
         for (int k = 1; k < 11; ++k) std::fprintf(stderr, "    %-32s %10.3f ms total  %8.2f us/col\n", names[k], pr[20 + k] / 1e5, pr[36] ? pr[20 + k] / 100.0 / (double)pr[36] : 0.0);
     } else if (ES.prof) {
         long long pr2[80];
-        HIPCHK(hipMemcpy(pr2, h->prof.p, sizeof(pr2), hipMemcpyDeviceToHost));
+        RLAP_HIPCHK(hipMemcpy(pr2, h->prof.p, sizeof(pr2), hipMemcpyDeviceToHost));
         // two blocks: the 32/64/128-slot round kernel, then the 16-slot one of the degree order (printed first: it runs first)
         for (int blk = 1; blk >= 0; --blk) {
         const long long* pr = pr2 + 40 * blk;
@@ -1003,18 +1001,18 @@ extern "C" {
 
 // the body of rlap_create: any failure leaves a partly built handle that rlap_create hands to rlap_destroy
 static int create_into(rlap_handle h) {
-    for (auto& e : h->ev) HIPCHK(hipEventCreate(&e));
-    for (auto& e : h->fork_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (auto& st : h->side) HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    for (auto& e : h->ev) RLAP_HIPCHK(hipEventCreate(&e));
+    for (auto& e : h->fork_ev) RLAP_HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (auto& st : h->side) RLAP_HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     // everything a call needs besides its arena and the uniform table is allocated here, once: the equal-key permutation tables
     // (built on one of the handle's own non-blocking streams -- not the null stream, which would serialise against every blocking
     // stream of the caller -- and finished before rlap_create returns), the pinned read-back block, the diagnostic profile
     ENSURE(h->small, 256);
     ENSURE(h->eqtab, EQTAB_BYTES);
     launch_eq_tables(h->side[0], h->eqtab.as<uint8_t>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(h->side[0]));
-    HIPCHK(hipHostMalloc(&h->h_results, 1 << 17, hipHostMallocDefault));
+    RLAP_HIPCHK(hipGetLastError());
+    RLAP_HIPCHK(hipStreamSynchronize(h->side[0]));
+    RLAP_HIPCHK(hipHostMalloc(&h->h_results, 1 << 17, hipHostMallocDefault));
     h->h_results_cap = 1 << 17;
     if (const char* e = std::getenv("RLAP_PHASE_PROFILE")) { if (e[0] == '1') ENSURE(h->prof, 8 * 80); }
     if (const char* e = std::getenv("RLAP_DEBUG_POISON")) { if (e[0]) h->poison = std::atoi(e) & 0xFF; }
@@ -1025,7 +1023,7 @@ static int create_into(rlap_handle h) {
 int rlap_create(rlap_handle* out) {
     if (!out) return RLAP_E_BAD_ARG;
     int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
+    RLAP_HIPCHK(hipGetDevice(&dev));
     rlap_handle h = new rlap_handle_s();
     h->device = dev;
     if (hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || h->n_cu <= 0) h->n_cu = 256;
@@ -1060,7 +1058,7 @@ static int ws_query(const rlap_handle h, int64_t E, int64_t n_total, int64_t G, 
     // bounds that hold for every split of n_total over G graphs and every num_remove: 2n+1 buckets per graph, S <= n_total
     int rc = call_sizes(hh, Eeff, n_total, G, 2 * n_total + G, n_total, true, flow_wanted(hh, OV_RANDOM, G, n_total), n_total, &z);
     if (rc) return rc;
-    WS W; Carver dry{nullptr, 0};
+    WS W; Carve dry{nullptr, 0};
     *ws_bytes = carve(dry, z, W);
     *rng_entries = rng_guess(hh, Eeff, G);
     return RLAP_OK;
@@ -1140,8 +1138,8 @@ int rlap_identity(rlap_handle h, const double* d_in, double* d_tmp, double* d_ou
     if (total == 0) return RLAP_OK;
     hipLaunchKernelGGL(k_transpose_copy, dim3(nblk(total, 256)), dim3(256), 0, h->stream, d_in, d_tmp, rows, cols, 1);
     hipLaunchKernelGGL(k_transpose_copy, dim3(nblk(total, 256)), dim3(256), 0, h->stream, (const double*)d_tmp, d_out, rows, cols, 0);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(h->stream));
+    RLAP_HIPCHK(hipGetLastError());
+    RLAP_HIPCHK(hipStreamSynchronize(h->stream));
     return RLAP_OK;
 }
 
@@ -1149,7 +1147,7 @@ int rlap_unpack_edge_info(rlap_handle h, const double* d_edge_info, int64_t E, i
     if (!h || E < 0) return RLAP_E_BAD_ARG;
     if (E == 0) return RLAP_OK;
     hipLaunchKernelGGL(k_unpack_edge_info, dim3(nblk(E, 256)), dim3(256), 0, h->stream, d_edge_info, E, d_row, d_col, d_w);
-    HIPCHK(hipGetLastError());
+    RLAP_HIPCHK(hipGetLastError());
     return RLAP_OK;
 }
 
@@ -1158,7 +1156,7 @@ int rlap_pack_rows(rlap_handle h, const double* d_sc, int64_t rows, void* d_pack
     if (rows == 0) return RLAP_OK;
     DeviceGuard dg(h->device);
     hipLaunchKernelGGL(k_pack_rows, dim3(nblk(rows, 256)), dim3(256), 0, h->stream, d_sc, rows, reinterpret_cast<unsigned long long*>(d_packed));
-    HIPCHK(hipGetLastError());
+    RLAP_HIPCHK(hipGetLastError());
     return RLAP_OK;
 }
 
@@ -1167,7 +1165,7 @@ int rlap_unpack_rows(rlap_handle h, const void* d_packed, int64_t rows, double* 
     if (rows == 0) return RLAP_OK;
     DeviceGuard dg(h->device);
     hipLaunchKernelGGL(k_unpack_rows, dim3(nblk(rows, 256)), dim3(256), 0, h->stream, reinterpret_cast<const unsigned long long*>(d_packed), rows, d_sc);
-    HIPCHK(hipGetLastError());
+    RLAP_HIPCHK(hipGetLastError());
     return RLAP_OK;
 }
 
@@ -1233,10 +1231,10 @@ int rlap_approx_chol_from_edges(rlap_handle h, const int64_t* d_src, const int64
         unsigned long long mx[2] = {0ull, 0ull};   // max id + 1, any id negative
         if (E > 0) {
             unsigned long long* d_mx = h->small.as<unsigned long long>();
-            HIPCHK(hipMemsetAsync(d_mx, 0, 16, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_mx, 0, 16, h->stream));
             hipLaunchKernelGGL(k_max_id, dim3((unsigned)std::min<int64_t>((E + 255) / 256, 1024)), dim3(256), 0, h->stream, d_src, d_dst, E, d_mx);
-            HIPCHK(hipMemcpyAsync(mx, d_mx, 16, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
+            RLAP_HIPCHK(hipMemcpyAsync(mx, d_mx, 16, hipMemcpyDeviceToHost, h->stream));
+            RLAP_HIPCHK(hipStreamSynchronize(h->stream));
         }
         if (mx[1]) return RLAP_E_INDEX_RANGE;   // a negative id is out of range for every num_nodes (an explicit n reports the same)
         n = (int64_t)mx[0];
@@ -1252,73 +1250,80 @@ int rlap_approx_chol_from_edges(rlap_handle h, const int64_t* d_src, const int64
     return rc;
 }
 
+}  // extern "C"
+
+namespace {
+
+// The checks the five snapshot exports share (their own RLAP_E_BAD_ARG checks come before this, their own size limits behind it):
+// the handle and the tables are there, at least min_S segments, G graphs divide them (G = 1 without node_ptr), and m and S fit
+// the int32 row and block numbers.
+int snapshot_check(rlap_handle h, SnapshotSeg* g, int64_t min_S) {
+    if (!h || !g->ptr || g->S < min_S || g->m < 0 || g->N < 0 || (g->m > 0 && !g->sc)) return RLAP_E_BAD_ARG;
+    if (g->node_ptr ? (g->G < 1 || g->S % g->G != 0) : false) return RLAP_E_BAD_ARG;
+    if (!g->node_ptr) g->G = 1;
+    if (g->m >= INT32_MAX || g->S >= (int64_t)1 << 30) return RLAP_E_TOO_LARGE;
+    return RLAP_OK;
+}
+
+// One snapshot call on the handle: its lock, its device, an arena of bytes() bytes, then run(base, have, need) -> status.
+template <class Bytes, class Run>
+int snapshot_call(rlap_handle h, Bytes bytes, Run run) {
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device);
+    const size_t need = bytes();
+    void* base = nullptr;
+    size_t have = 0;
+    if (const int rc = arena(h, need, &base, &have)) return rc;
+    return run(base, have, need);
+}
+
+}  // namespace
+
+extern "C" {
+
 int rlap_snapshot_stats(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
                         int64_t G, int64_t num_nodes, int weighted, double tol, int32_t max_iter, int64_t* d_nodes,
                         double* d_lambda_max, int32_t* d_iters, int32_t* d_converged, rlap_snapshot_info* h_info) {
-    if (!h || !d_ptr || S < 1 || m < 0 || num_nodes < 0 || (m > 0 && !d_sc) || !d_nodes || !d_lambda_max || !d_iters || !d_converged) return RLAP_E_BAD_ARG;
+    if (!d_nodes || !d_lambda_max || !d_iters || !d_converged) return RLAP_E_BAD_ARG;
     if (!(tol > 0.0) || !std::isfinite(tol) || max_iter < 1 || max_iter > STATS_MAX_ITER) return RLAP_E_BAD_ARG;
-    if (d_node_ptr ? (G < 1 || S % G != 0) : false) return RLAP_E_BAD_ARG;
-    if (!d_node_ptr) G = 1;
-    if (m >= INT32_MAX || S >= (int64_t)1 << 30) return RLAP_E_TOO_LARGE;
-    std::lock_guard<std::mutex> lock(h->mu);
-    DeviceGuard dg(h->device);
-    const size_t need = snapshot_stats_bytes(m, S, G, num_nodes, max_iter);
-    h->ws_needed = need;
-    void* base = nullptr;
-    size_t have = 0;
-    if (h->ext_ws) {
-        if (need > h->ext_ws_bytes) return RLAP_E_WORKSPACE;
-        base = h->ext_ws; have = h->ext_ws_bytes;
-    } else {
-        ENSURE(h->own_ws, need);
-        base = h->own_ws.p; have = h->own_ws.cap;
-    }
-    SnapshotStatsArgs a{d_sc, m, d_ptr, S, d_node_ptr, G, num_nodes, weighted, tol, max_iter, d_nodes, d_lambda_max, d_iters, d_converged};
-    SnapshotStatsReport rep;
-    const int rc = snapshot_stats_run(h->stream, base, have, a, &rep);
-    if (h_info) {
-        h_info->small_segments = rep.small_segments; h_info->large_segments = rep.large_segments;
-        h_info->lanczos_steps = rep.lanczos_steps; h_info->large_steps = rep.large_steps; h_info->large_launches = rep.large_launches;
-        h_info->host_syncs = rep.host_syncs; h_info->not_converged = rep.not_converged;
-    }
-    return rc;
+    SnapshotSeg g{d_sc, m, d_ptr, S, d_node_ptr, G, num_nodes};
+    if (const int rc = snapshot_check(h, &g, 1)) return rc;   // (no limit on num_nodes: the id slots are counted in 64 bits)
+    const SnapshotStatsArgs a{g, weighted, tol, max_iter, d_nodes, d_lambda_max, d_iters, d_converged};
+    return snapshot_call(h, [&] { return snapshot_stats_bytes(g.m, g.S, g.G, g.N, max_iter); }, [&](void* base, size_t have, size_t) {
+        SnapshotStatsReport rep;
+        const int rc = snapshot_stats_run(h->stream, base, have, a, &rep);
+        if (h_info) {
+            h_info->small_segments = rep.small_segments; h_info->large_segments = rep.large_segments;
+            h_info->lanczos_steps = rep.lanczos_steps; h_info->large_steps = rep.large_steps; h_info->large_launches = rep.large_launches;
+            h_info->host_syncs = rep.host_syncs; h_info->not_converged = rep.not_converged;
+        }
+        return rc;
+    });
 }
 
 int rlap_snapshot_ppr(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
                       int64_t G, int64_t num_nodes, double alpha, double eps, double tol, int flags, double* d_out,
                       int64_t out_cap_rows, int64_t* d_out_ptr, rlap_ppr_info* h_info) {
     if (h_info) *h_info = rlap_ppr_info{};
-    if (!h || !d_ptr || S < 1 || m < 0 || num_nodes < 0 || (m > 0 && !d_sc) || !d_out_ptr || out_cap_rows < 0 || (out_cap_rows > 0 && !d_out))
-        return RLAP_E_BAD_ARG;
+    if (!d_out_ptr || out_cap_rows < 0 || (out_cap_rows > 0 && !d_out)) return RLAP_E_BAD_ARG;
     if (flags & ~(RLAP_PPR_WEIGHTED | RLAP_PPR_SELF_LOOP | RLAP_PPR_NORMALIZE | RLAP_PPR_ZERO_ROWS)) return RLAP_E_BAD_ARG;
     if (!(eps > 0.0) || !std::isfinite(eps)) return RLAP_E_BAD_ARG;
     const int K = cheb::steps(alpha, tol, cheb::MAX_STEPS);
     if (K < 0) return RLAP_E_BAD_ARG;
-    if (d_node_ptr ? (G < 1 || S % G != 0) : false) return RLAP_E_BAD_ARG;
-    if (!d_node_ptr) G = 1;
-    if (m >= INT32_MAX || S >= (int64_t)1 << 30 || num_nodes >= INT32_MAX) return RLAP_E_TOO_LARGE;
-    std::lock_guard<std::mutex> lock(h->mu);
-    DeviceGuard dg(h->device);
-    const size_t need = snapshot_ppr_bytes(m, S, G, num_nodes, out_cap_rows, K);
-    h->ws_needed = need;
-    void* base = nullptr;
-    size_t have = 0;
-    if (h->ext_ws) {
-        if (need > h->ext_ws_bytes) return RLAP_E_WORKSPACE;
-        base = h->ext_ws; have = h->ext_ws_bytes;
-    } else {
-        ENSURE(h->own_ws, need);
-        base = h->own_ws.p; have = h->own_ws.cap;
-    }
-    SnapshotPprArgs a{d_sc, m, d_ptr, S, d_node_ptr, G, num_nodes, alpha, eps, K, flags, d_out, out_cap_rows, d_out_ptr};
-    SnapshotPprReport rep;
-    const int rc = snapshot_ppr_run(h->stream, base, have, a, &rep);
-    if (h_info) {
-        h_info->steps = K; h_info->small_tiles = rep.small_tiles; h_info->large_tiles = rep.large_tiles; h_info->groups = rep.groups;
-        h_info->launches = rep.launches; h_info->rows_needed = rep.kept; h_info->arena_bytes = (int64_t)need;
-        h_info->host_syncs = rep.host_syncs;
-    }
-    return rc;
+    SnapshotSeg g{d_sc, m, d_ptr, S, d_node_ptr, G, num_nodes};
+    if (const int rc = snapshot_check(h, &g, 1)) return rc;
+    if (num_nodes >= INT32_MAX) return RLAP_E_TOO_LARGE;
+    const SnapshotPprArgs a{g, alpha, eps, K, flags, d_out, out_cap_rows, d_out_ptr};
+    return snapshot_call(h, [&] { return snapshot_ppr_bytes(g.m, g.S, g.G, g.N, out_cap_rows, K); }, [&](void* base, size_t have, size_t need) {
+        SnapshotPprReport rep;
+        const int rc = snapshot_ppr_run(h->stream, base, have, a, &rep);
+        if (h_info) {
+            h_info->steps = K; h_info->small_tiles = rep.small_tiles; h_info->large_tiles = rep.large_tiles; h_info->groups = rep.groups;
+            h_info->launches = rep.launches; h_info->rows_needed = rep.kept; h_info->arena_bytes = (int64_t)need;
+            h_info->host_syncs = rep.host_syncs;
+        }
+        return rc;
+    });
 }
 
 int rlap_snapshot_subgraph(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
@@ -1326,114 +1331,78 @@ int rlap_snapshot_subgraph(rlap_handle h, const double* d_sc, int64_t m, const i
                            int flags, double* d_out, int64_t* d_out_ptr, int64_t* d_ids, int64_t ids_cap, int64_t* d_ids_ptr,
                            rlap_subgraph_info* h_info) {
     if (h_info) *h_info = rlap_subgraph_info{};
-    if (!h || !d_ptr || S < 0 || m < 0 || num_nodes < 0 || (m > 0 && (!d_sc || !d_out || S < 1)) || !d_out_ptr || !d_ids_ptr) return RLAP_E_BAD_ARG;
+    if ((m > 0 && (!d_out || S < 1)) || !d_out_ptr || !d_ids_ptr) return RLAP_E_BAD_ARG;
     if (flags & ~(RLAP_SUB_RELABEL | RLAP_SUB_NO_SELF_LOOPS)) return RLAP_E_BAD_ARG;
-    if (d_node_ptr ? (G < 1 || S % G != 0) : false) return RLAP_E_BAD_ARG;
-    if (!d_node_ptr) G = 1;
     if (d_nodes ? nodes_len < 0 : (d_nodes_ptr != nullptr)) return RLAP_E_BAD_ARG;   // (nodes_ptr only together with nodes)
     if (!d_nodes) nodes_len = 0;
-    if (m >= INT32_MAX || S >= (int64_t)1 << 30 || num_nodes >= INT32_MAX || nodes_len >= INT32_MAX) return RLAP_E_TOO_LARGE;
-    if ((S / G) * num_nodes >= (int64_t)1 << 40) return RLAP_E_TOO_LARGE;
-    const int64_t ids_need = snapshot_subgraph_ids_cap(m, S, G, num_nodes, d_nodes != nullptr, d_nodes_ptr != nullptr, nodes_len);
+    SnapshotSeg g{d_sc, m, d_ptr, S, d_node_ptr, G, num_nodes};
+    if (const int rc = snapshot_check(h, &g, 0)) return rc;   // (S == 0: no segment at all, and then no rows)
+    if (num_nodes >= INT32_MAX || nodes_len >= INT32_MAX || (g.S / g.G) * num_nodes >= (int64_t)1 << 40) return RLAP_E_TOO_LARGE;
+    const int64_t ids_need = snapshot_subgraph_ids_cap(g.m, g.S, g.G, g.N, d_nodes != nullptr, d_nodes_ptr != nullptr, nodes_len);
     if (ids_cap < ids_need || (ids_need > 0 && !d_ids)) return RLAP_E_BAD_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    DeviceGuard dg(h->device);
-    const size_t need = snapshot_subgraph_bytes(m, S, G, num_nodes);
-    h->ws_needed = need;
-    void* base = nullptr;
-    size_t have = 0;
-    if (h->ext_ws) {
-        if (need > h->ext_ws_bytes) return RLAP_E_WORKSPACE;
-        base = h->ext_ws; have = h->ext_ws_bytes;
-    } else {
-        ENSURE(h->own_ws, need);
-        base = h->own_ws.p; have = h->own_ws.cap;
-    }
-    SnapshotSubArgs a{d_sc, m, d_ptr, S, d_node_ptr, G, num_nodes, d_nodes, d_nodes_ptr, nodes_len, flags, d_out, d_out_ptr, d_ids, ids_cap,
-                      d_ids_ptr};
-    SnapshotSubReport rep;
-    const int rc = snapshot_subgraph_run(h->stream, base, have, a, &rep);
-    if (h_info) {
-        h_info->rows_kept = rep.kept; h_info->ids_written = rep.ids; h_info->arena_bytes = (int64_t)need; h_info->host_syncs = rep.host_syncs;
-    }
-    return rc;
+    const SnapshotSubArgs a{g, d_nodes, d_nodes_ptr, nodes_len, flags, d_out, d_out_ptr, d_ids, ids_cap, d_ids_ptr};
+    return snapshot_call(h, [&] { return snapshot_subgraph_bytes(g.m, g.S, g.G, g.N); }, [&](void* base, size_t have, size_t need) {
+        SnapshotSubReport rep;
+        const int rc = snapshot_subgraph_run(h->stream, base, have, a, &rep);
+        if (h_info) {
+            h_info->rows_kept = rep.kept; h_info->ids_written = rep.ids; h_info->arena_bytes = (int64_t)need; h_info->host_syncs = rep.host_syncs;
+        }
+        return rc;
+    });
 }
 
 int rlap_snapshot_gcn_norm(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
                            int64_t G, int64_t num_nodes, int flags, double fill_value, int64_t* d_src, int64_t* d_dst, void* d_val,
                            int64_t cap, int64_t* d_eptr, rlap_gcn_info* h_info) {
     if (h_info) *h_info = rlap_gcn_info{};
-    if (!h || !d_ptr || S < 1 || m < 0 || num_nodes < 0 || (m > 0 && !d_sc) || !d_eptr || cap < 0) return RLAP_E_BAD_ARG;
+    if (!d_eptr || cap < 0) return RLAP_E_BAD_ARG;
     if (flags & ~(RLAP_GCN_WEIGHTED | RLAP_GCN_SELF_LOOPS | RLAP_GCN_NORMALIZE | RLAP_GCN_F32)) return RLAP_E_BAD_ARG;
     if ((flags & RLAP_GCN_SELF_LOOPS) && !(fill_value > 0.0 && std::isfinite(fill_value))) return RLAP_E_BAD_ARG;
-    if (d_node_ptr ? (G < 1 || S % G != 0) : false) return RLAP_E_BAD_ARG;
-    if (!d_node_ptr) G = 1;
-    if (m >= INT32_MAX || S >= (int64_t)1 << 30 || num_nodes >= INT32_MAX) return RLAP_E_TOO_LARGE;
-    if ((S / G) * num_nodes >= (int64_t)1 << 40) return RLAP_E_TOO_LARGE;
-    const int64_t cap_need = snapshot_gcn_cap(m, S, G, num_nodes, flags);
+    SnapshotSeg g{d_sc, m, d_ptr, S, d_node_ptr, G, num_nodes};
+    if (const int rc = snapshot_check(h, &g, 1)) return rc;
+    if (num_nodes >= INT32_MAX || (g.S / g.G) * num_nodes >= (int64_t)1 << 40) return RLAP_E_TOO_LARGE;
+    const int64_t cap_need = snapshot_gcn_cap(g.m, g.S, g.G, g.N, flags);
     if (cap < cap_need || (cap_need > 0 && (!d_src || !d_dst || !d_val))) return RLAP_E_BAD_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    DeviceGuard dg(h->device);
-    const size_t need = snapshot_gcn_bytes(m, S, G, num_nodes);
-    h->ws_needed = need;
-    void* base = nullptr;
-    size_t have = 0;
-    if (h->ext_ws) {
-        if (need > h->ext_ws_bytes) return RLAP_E_WORKSPACE;
-        base = h->ext_ws; have = h->ext_ws_bytes;
-    } else {
-        ENSURE(h->own_ws, need);
-        base = h->own_ws.p; have = h->own_ws.cap;
-    }
-    SnapshotGcnArgs a{d_sc, m, d_ptr, S, d_node_ptr, G, num_nodes, flags, fill_value, d_src, d_dst, d_val, d_eptr};
-    SnapshotGcnReport rep;
-    const int rc = snapshot_gcn_run(h->stream, base, have, a, &rep);
-    if (h_info) {
-        h_info->entries = rep.entries; h_info->loops_removed = rep.loops_removed; h_info->arena_bytes = (int64_t)need;
-        h_info->host_syncs = rep.host_syncs;
-    }
-    return rc;
+    const SnapshotGcnArgs a{g, flags, fill_value, d_src, d_dst, d_val, d_eptr};
+    return snapshot_call(h, [&] { return snapshot_gcn_bytes(g.m, g.S, g.G, g.N); }, [&](void* base, size_t have, size_t need) {
+        SnapshotGcnReport rep;
+        const int rc = snapshot_gcn_run(h->stream, base, have, a, &rep);
+        if (h_info) {
+            h_info->entries = rep.entries; h_info->loops_removed = rep.loops_removed; h_info->arena_bytes = (int64_t)need;
+            h_info->host_syncs = rep.host_syncs;
+        }
+        return rc;
+    });
 }
 
 int rlap_snapshot_propagate(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
                             int64_t G, int64_t num_nodes, int flags, double fill_value, const void* d_x, int64_t F, void* d_y,
                             rlap_spmm_info* h_info) {
     if (h_info) *h_info = rlap_spmm_info{};
-    if (!h || !d_ptr || S < 1 || m < 0 || num_nodes < 0 || (m > 0 && !d_sc) || F < 1) return RLAP_E_BAD_ARG;
+    if (F < 1) return RLAP_E_BAD_ARG;
     if (flags & ~(RLAP_GCN_WEIGHTED | RLAP_GCN_SELF_LOOPS | RLAP_GCN_NORMALIZE | RLAP_SPMM_TRANSPOSE | RLAP_SPMM_X_F32 | RLAP_SPMM_X_PER_LAYER))
         return RLAP_E_BAD_ARG;
     if ((flags & RLAP_GCN_SELF_LOOPS) && !(fill_value > 0.0 && std::isfinite(fill_value))) return RLAP_E_BAD_ARG;
-    if (d_node_ptr ? (G < 1 || S % G != 0) : false) return RLAP_E_BAD_ARG;
-    if (!d_node_ptr) G = 1;
-    if (m >= INT32_MAX || S >= (int64_t)1 << 30 || num_nodes >= INT32_MAX || F > SPMM_MAX_F) return RLAP_E_TOO_LARGE;
-    if ((S / G) * num_nodes >= SPMM_MAX_ELEMS || (S / G) * num_nodes * F >= SPMM_MAX_ELEMS) return RLAP_E_TOO_LARGE;
-    const int64_t elems = (S / G) * num_nodes * F;
+    SnapshotSeg g{d_sc, m, d_ptr, S, d_node_ptr, G, num_nodes};
+    if (const int rc = snapshot_check(h, &g, 1)) return rc;
+    if (num_nodes >= INT32_MAX || F > SPMM_MAX_F) return RLAP_E_TOO_LARGE;
+    if ((g.S / g.G) * num_nodes >= SPMM_MAX_ELEMS || (g.S / g.G) * num_nodes * F >= SPMM_MAX_ELEMS) return RLAP_E_TOO_LARGE;
+    const int64_t elems = (g.S / g.G) * num_nodes * F;
     if (elems > 0 && (!d_x || !d_y)) return RLAP_E_BAD_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    DeviceGuard dg(h->device);
-    const size_t need = snapshot_spmm_bytes(m, S, G, num_nodes, F, flags, h->dbg_scr);
-    h->ws_needed = need;
-    void* base = nullptr;
-    size_t have = 0;
-    if (h->ext_ws) {
-        if (need > h->ext_ws_bytes) return RLAP_E_WORKSPACE;
-        base = h->ext_ws; have = h->ext_ws_bytes;
-    } else {
-        ENSURE(h->own_ws, need);
-        base = h->own_ws.p; have = h->own_ws.cap;
-    }
-    if (h->poison >= 0) {   // debug: the result must not depend on what the arena or the result buffer held
-        HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
-        if (elems > 0) HIPCHK(hipMemsetAsync(d_y, h->poison, (size_t)elems * ((flags & RLAP_SPMM_X_F32) ? 4 : 8), h->stream));
-    }
-    SnapshotSpmmArgs a{d_sc, m, d_ptr, S, d_node_ptr, G, num_nodes, flags, fill_value, d_x, F, d_y, h->dbg_scr};
-    SnapshotSpmmReport rep;
-    const int rc = snapshot_spmm_run(h->stream, base, have, a, &rep);
-    if (h_info) {
-        h_info->entries = rep.entries; h_info->blocks = rep.blocks; h_info->chunked_lists = rep.chunked_lists;
-        h_info->arena_bytes = (int64_t)need; h_info->host_syncs = rep.host_syncs;
-    }
-    return rc;
+    return snapshot_call(h, [&] { return snapshot_spmm_bytes(g.m, g.S, g.G, g.N, F, flags, h->dbg_scr); }, [&](void* base, size_t have, size_t need) -> int {
+        if (h->poison >= 0) {   // debug: the result must not depend on what the arena or the result buffer held
+            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
+            if (elems > 0) RLAP_HIPCHK(hipMemsetAsync(d_y, h->poison, (size_t)elems * ((flags & RLAP_SPMM_X_F32) ? 4 : 8), h->stream));
+        }
+        const SnapshotSpmmArgs a{g, flags, fill_value, d_x, F, d_y, h->dbg_scr};
+        SnapshotSpmmReport rep;
+        const int rc = snapshot_spmm_run(h->stream, base, have, a, &rep);
+        if (h_info) {
+            h_info->entries = rep.entries; h_info->blocks = rep.blocks; h_info->chunked_lists = rep.chunked_lists;
+            h_info->arena_bytes = (int64_t)need; h_info->host_syncs = rep.host_syncs;
+        }
+        return rc;
+    });
 }
 
 int rlap_debug_set_limits(rlap_handle h, double pool_factor, double log_factor, int64_t rng_len, int64_t scratch_entries) {
@@ -1470,8 +1439,8 @@ int rlap_rng_uniforms(rlap_handle h, int64_t count, double* d_out) {
     DeviceGuard dg(h->device);
     int rc = ensure_rng(h, count);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(d_out, h->rng_ptr, sizeof(double) * (size_t)count, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    RLAP_HIPCHK(hipMemcpyAsync(d_out, h->rng_ptr, sizeof(double) * (size_t)count, hipMemcpyDeviceToDevice, h->stream));
+    RLAP_HIPCHK(hipStreamSynchronize(h->stream));
     return RLAP_OK;
 }
 
@@ -1480,18 +1449,18 @@ int rlap_debug_wave_sort(rlap_handle h, const double* d_keys, const int32_t* d_o
     if (narr == 0) return RLAP_OK;
     if (desc & 32) {   // the dataflow kernel's long-column sort (rlap_flow.hip)
         int32_t total = 0;
-        HIPCHK(hipMemcpy(&total, d_offs + narr, 4, hipMemcpyDeviceToHost));
+        RLAP_HIPCHK(hipMemcpy(&total, d_offs + narr, 4, hipMemcpyDeviceToHost));
         DevBuf scr;
         ENSURE(scr, 32 * (size_t)std::max(total, 1) + 64 * (size_t)narr + 256);
         launch_debug_flow_sort(h->stream, d_keys, d_offs, narr, desc, d_perm_out, scr.as<char>());
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(h->stream));
+        RLAP_HIPCHK(hipGetLastError());
+        RLAP_HIPCHK(hipStreamSynchronize(h->stream));
         scr.release();
         return RLAP_OK;
     }
     hipLaunchKernelGGL(k_debug_wave_sort, dim3((unsigned)std::min<int32_t>(narr, 2048)), dim3(64), 0, h->stream, d_keys, d_offs, narr, desc, d_perm_out);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(h->stream));
+    RLAP_HIPCHK(hipGetLastError());
+    RLAP_HIPCHK(hipStreamSynchronize(h->stream));
     return RLAP_OK;
 }
 

@@ -1,19 +1,12 @@
 // rlap_gcn.h -- encoder-ready snapshots (rlap_snapshot_gcn_norm): the interface between rlap_gcn.hip, which holds the
 // kernels and their orchestration, and the C ABI in rlap_api.hip, which owns the handle, its lock and its arena.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stddef.h>
-#include <stdint.h>
-
-#include "rlap_stats.h"
+#include "rlap_snapshot.h"
 
 namespace rlap {
 
 struct SnapshotGcnArgs {
-    const double* sc; int64_t m;              // (m, 3) rows [row, col, w]
-    const int64_t* ptr; int64_t S;            // [S+1] segment offsets
-    const int64_t* node_ptr; int64_t G;       // [G+1] or nullptr (then G = 1 and every id range is [0, N))
-    int64_t N;                                // num_nodes
+    SnapshotSeg seg;
     int flags;                                // RLAP_GCN_* (include/rlap_hip.h)
     double fill;                              // weight of an added self loop
     int64_t* src; int64_t* dst; void* val;    // [cap] each; val is float32 with RLAP_GCN_F32, else float64

@@ -7,7 +7,7 @@
 //   tables   one workgroup checks ptr / node_ptr and writes the copies every later kernel reads: the tables themselves, or, when they
 //            are malformed, well-formed stand-ins ([0, m, m, ...]) with the error word raised -- so nothing has to wait for the host
 //            before it may index with them.
-//   columns  the column pass of rlap_stats.hip: the blocks (one per column id and segment), bstart, rb[r] = block of row r's id,
+//   columns  the column pass (rlap_snapshot.hip): the blocks (one per column id and segment), bstart, rb[r] = block of row r's id,
 //            idx[slot of an id] = its block or -1, the layout error words.
 //   degrees  16 lanes per block: lane l sums rows l, l + 16, ... of the block into four accumulators in turn (row k of a lane goes to
 //            accumulator k % 4), adds them as (a0 + a1) + (a2 + a3), then an xor butterfly over 8, 4, 2, 1 lanes; with self loops the
@@ -28,7 +28,6 @@
 #include "../../include/rlap_hip.h"
 #include "rlap_gcn.h"
 #include "rlap_gcnmath.h"
-#include "rlap_stats.h"
 
 namespace rlap {
 namespace {
@@ -40,10 +39,6 @@ constexpr int GC_GROUP = 16;                    // lanes per block of the degree
 enum { GERR_WEIGHT = GCN_ERR_WEIGHT, GERR_ARG = GCN_ERR_ARG, GERR_WORDS = GCN_ERR_WORDS };
 
 static_assert(GC_RPT * GC_THREADS == GCN_TILE, "an emit tile is a whole number of turns");
-
-#define GC_HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { std::fprintf(stderr, "[rlap_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(_e), __FILE__, __LINE__); return RLAP_E_HIP; } } while (0)
-
-inline unsigned gc_blocks(int64_t n, int bs) { return (unsigned)std::max<int64_t>(1, (n + bs - 1) / bs); }
 
 // what the kernels share (ptr / node_ptr are the checked copies)
 struct Gcn {
@@ -60,20 +55,6 @@ struct Gcn {
     unsigned long long* tot;                  // [0] loop rows of the call
     int32_t* err;
 };
-
-// last s in [0, S) with tab[s] <= r (S >= 1): the segment of row r; equal offsets (empty segments) are skipped
-__device__ inline int64_t seg_of(const int64_t* __restrict__ tab, int64_t S, int64_t r) {
-    int64_t lo = 0, hi = S;
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (tab[mid] <= r) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ inline int64_t seg_near(const int64_t* __restrict__ tab, int64_t S, int64_t r, int64_t s0) {
-    return r < tab[s0 + 1] ? s0 : seg_of(tab, S, r);
-}
 
 // ids of the segments in front of segment s (s = S: of all segments): the loops written before those of s
 __device__ inline int64_t ids_before(const Gcn& a, int64_t s) {
@@ -258,16 +239,6 @@ __global__ __launch_bounds__(GC_THREADS) void k_gc_tail(Gcn a, const int64_t* __
     val[e] = (V)(a.normalize ? gcnmath::value(d, w, d) : w);
 }
 
-struct Carve {
-    char* base; size_t off;
-    template <class T> T* take(int64_t count) {
-        off = (off + 255) & ~(size_t)255;
-        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += sizeof(T) * (size_t)(count > 0 ? count : 0);
-        return p;
-    }
-};
-
 struct Bufs {
     ColumnBufs col;
     int64_t *cptr, *cnp, *nodes, *tbase, *segl;
@@ -304,11 +275,11 @@ int emit_and_tail(hipStream_t st, const Gcn& a, const SnapshotGcnArgs& g) {
         const int vec = (reinterpret_cast<uintptr_t>(a.sc) & 15) == 0 ? 1 : 0;
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gc_emit<V>), dim3((unsigned)a.tiles), dim3(GC_THREADS), 0, st, a, vec, g.src, g.dst, val);
     }
-    hipLaunchKernelGGL(k_gc_eptr, dim3(gc_blocks(a.S + 1, 256)), dim3(256), 0, st, a, g.eptr);
+    hipLaunchKernelGGL(k_gc_eptr, dim3(grid_blocks(a.S + 1, 256)), dim3(256), 0, st, a, g.eptr);
     const int64_t ids = (a.S / a.G) * a.N;
     if (a.loops && ids > 0)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gc_tail<V>), dim3(gc_blocks(ids, GC_THREADS)), dim3(GC_THREADS), 0, st, a, g.eptr, g.src, g.dst, val);
-    GC_HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gc_tail<V>), dim3(grid_blocks(ids, GC_THREADS)), dim3(GC_THREADS), 0, st, a, g.eptr, g.src, g.dst, val);
+    RLAP_HIPCHK(hipGetLastError());
     return RLAP_OK;
 }
 
@@ -317,7 +288,7 @@ int emit_and_tail(hipStream_t st, const Gcn& a, const SnapshotGcnArgs& g) {
 int gcn_tables_enqueue(hipStream_t st, const int64_t* ptr, int64_t S, int64_t m, const int64_t* node_ptr, int64_t G, int64_t N,
                        int64_t* cptr, int64_t* cnp, int32_t* err) {
     hipLaunchKernelGGL(k_gc_tables, dim3(1), dim3(1024), 0, st, ptr, S, m, node_ptr, G, N, cptr, cnp, err);
-    GC_HIPCHK(hipGetLastError());
+    RLAP_HIPCHK(hipGetLastError());
     return RLAP_OK;
 }
 
@@ -329,8 +300,8 @@ int gcn_degree_enqueue(hipStream_t st, const double* sc, int64_t m, int flags, d
     a.sc = sc; a.m = m; a.weighted = weighted; a.loops = loops; a.normalize = normalize; a.fill = fill;
     a.rb = col.rb; a.blk = col.blk; a.bstart = col.bstart; a.idx = col.idx; a.bcap = col.bcap;
     a.dis = dis; a.lw = lw; a.tot = tot; a.err = col.err;
-    hipLaunchKernelGGL(k_gc_degree, dim3(gc_blocks(col.bcap * GC_GROUP, GC_THREADS)), dim3(GC_THREADS), 0, st, a, weighted && normalize);
-    GC_HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_gc_degree, dim3(grid_blocks(col.bcap * GC_GROUP, GC_THREADS)), dim3(GC_THREADS), 0, st, a, weighted && normalize);
+    RLAP_HIPCHK(hipGetLastError());
     return RLAP_OK;
 }
 
@@ -346,51 +317,50 @@ size_t snapshot_gcn_bytes(int64_t m, int64_t S, int64_t G, int64_t N) {
 
 int snapshot_gcn_run(hipStream_t st, void* ws, size_t ws_bytes, const SnapshotGcnArgs& g, SnapshotGcnReport* rep) {
     *rep = SnapshotGcnReport{};
-    const int64_t m = g.m, S = g.S, G = g.G, N = g.N;
+    const SnapshotSeg& in = g.seg;
+    const int64_t m = in.m, S = in.S, G = in.G, N = in.N;
     Bufs B;
     Carve C{static_cast<char*>(ws), 0};
     if (carve_gcn(C, m, S, G, N, B) > ws_bytes) return RLAP_E_WORKSPACE;
     const int weighted = (g.flags & RLAP_GCN_WEIGHTED) ? 1 : 0, loops = (g.flags & RLAP_GCN_SELF_LOOPS) ? 1 : 0;
     const int normalize = (g.flags & RLAP_GCN_NORMALIZE) ? 1 : 0;
-    Gcn a{g.sc, m, B.cptr, S, g.node_ptr ? B.cnp : nullptr, G, N, weighted, loops, normalize, g.fill,
+    Gcn a{in.sc, m, B.cptr, S, in.node_ptr ? B.cnp : nullptr, G, N, weighted, loops, normalize, g.fill,
           B.col.rb, B.col.blk, B.col.bstart, B.col.idx, B.col.bcap, B.dis, B.lw, B.cnt, B.tbase, B.tiles, B.segl, B.tot, B.col.err};
     // 1. the tables, checked and copied; the column pass on the copies
-    GC_HIPCHK(hipMemsetAsync(B.col.err, 0, sizeof(int32_t) * GERR_WORDS, st));
-    GC_HIPCHK(hipMemsetAsync(B.tot, 0, sizeof(unsigned long long), st));
-    int trc = gcn_tables_enqueue(st, g.ptr, S, m, g.node_ptr, G, N, B.cptr, B.cnp, B.col.err);
+    RLAP_HIPCHK(hipMemsetAsync(B.col.err, 0, sizeof(int32_t) * GERR_WORDS, st));
+    RLAP_HIPCHK(hipMemsetAsync(B.tot, 0, sizeof(unsigned long long), st));
+    int trc = gcn_tables_enqueue(st, in.ptr, S, m, in.node_ptr, G, N, B.cptr, B.cnp, B.col.err);
     if (trc != RLAP_OK) return trc;
     if (m > 0) {
-        const int rc = column_pass_enqueue(st, g.sc, m, a.ptr, S, a.node_ptr, G, N, B.col, B.nodes);
+        const int rc = column_pass_enqueue(st, in.sc, m, a.ptr, S, a.node_ptr, G, N, B.col, B.nodes);
         if (rc != RLAP_OK) return rc;
     }
     // 2. degrees; 3. the loop rows in front of every tile (zeros without a pass over the rows when the input has none)
     if (m > 0 && (normalize || loops)) {
-        trc = gcn_degree_enqueue(st, g.sc, m, g.flags, g.fill, B.col, B.dis, B.lw, B.tot);
+        trc = gcn_degree_enqueue(st, in.sc, m, g.flags, g.fill, B.col, B.dis, B.lw, B.tot);
         if (trc != RLAP_OK) return trc;
     }
     if (loops) {
-        GC_HIPCHK(hipMemsetAsync(B.cnt, 0, sizeof(int32_t) * (size_t)(B.tiles + 1), st));
-        GC_HIPCHK(hipMemsetAsync(B.segl, 0, sizeof(int64_t) * (size_t)(S + 1), st));
+        RLAP_HIPCHK(hipMemsetAsync(B.cnt, 0, sizeof(int32_t) * (size_t)(B.tiles + 1), st));
+        RLAP_HIPCHK(hipMemsetAsync(B.segl, 0, sizeof(int64_t) * (size_t)(S + 1), st));
         if (m > 0) hipLaunchKernelGGL(k_gc_count, dim3((unsigned)B.tiles), dim3(GC_THREADS), 0, st, a);
-        GC_HIPCHK(hipGetLastError());
+        RLAP_HIPCHK(hipGetLastError());
         size_t tb = B.tmp_bytes;
-        GC_HIPCHK(rocprim::exclusive_scan(B.tmp, tb, B.cnt, B.tbase, (int64_t)0, (size_t)(B.tiles + 1), rocprim::plus<int64_t>(), st));
+        RLAP_HIPCHK(rocprim::exclusive_scan(B.tmp, tb, B.cnt, B.tbase, (int64_t)0, (size_t)(B.tiles + 1), rocprim::plus<int64_t>(), st));
     }
-    GC_HIPCHK(hipGetLastError());
+    RLAP_HIPCHK(hipGetLastError());
     // 4. the entries, the offsets, the loops
     const int rc = (g.flags & RLAP_GCN_F32) ? emit_and_tail<float>(st, a, g) : emit_and_tail<double>(st, a, g);
     if (rc != RLAP_OK) return rc;
     // 5. the error words and the loop rows, read back once
     int32_t herr[GERR_WORDS];
     unsigned long long hloops = 0;
-    GC_HIPCHK(hipMemcpyAsync(herr, B.col.err, sizeof(herr), hipMemcpyDeviceToHost, st));
-    GC_HIPCHK(hipMemcpyAsync(&hloops, B.tot, sizeof(hloops), hipMemcpyDeviceToHost, st));
-    GC_HIPCHK(hipStreamSynchronize(st));
+    RLAP_HIPCHK(hipMemcpyAsync(herr, B.col.err, sizeof(herr), hipMemcpyDeviceToHost, st));
+    RLAP_HIPCHK(hipMemcpyAsync(&hloops, B.tot, sizeof(hloops), hipMemcpyDeviceToHost, st));
+    RLAP_HIPCHK(hipStreamSynchronize(st));
     rep->host_syncs = 1;
     if (herr[GERR_ARG]) return RLAP_E_BAD_ARG;
-    if (herr[COL_ERR_RANGE]) return RLAP_E_INDEX_RANGE;
-    if (herr[COL_ERR_GROUP]) return RLAP_E_NOT_GROUPED;
-    if (herr[COL_ERR_NOCOL]) return RLAP_E_NOT_SYMMETRIC;
+    if (const int lrc = layout_status(herr)) return lrc;
     if (herr[GERR_WEIGHT]) return RLAP_E_BAD_ARG;
     rep->loops_removed = loops ? (int64_t)hloops : 0;
     rep->entries = snapshot_gcn_cap(m, S, G, N, g.flags) - rep->loops_removed;

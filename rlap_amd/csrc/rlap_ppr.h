@@ -1,17 +1,12 @@
 // rlap_ppr.h -- PPR diffusion of snapshots (rlap_snapshot_ppr): the interface between rlap_ppr.hip, which holds the
 // kernels and their orchestration, and the C ABI in rlap_api.hip, which owns the handle, its lock and its arena.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stddef.h>
-#include <stdint.h>
+#include "rlap_snapshot.h"
 
 namespace rlap {
 
 struct SnapshotPprArgs {
-    const double* sc; int64_t m;              // (m, 3) rows [row, col, w]
-    const int64_t* ptr; int64_t S;            // [S+1] segment offsets
-    const int64_t* node_ptr; int64_t G;       // [G+1] or nullptr (then G = 1 and every id range is [0, N))
-    int64_t N;                                // num_nodes
+    SnapshotSeg seg;
     double alpha, eps; int32_t K;             // K: Chebyshev steps (rlap_cheb.h)
     int flags;                                // RLAP_PPR_* (include/rlap_hip.h)
     double* out; int64_t out_cap;             // (out_cap, 3) rows [i, j, value]

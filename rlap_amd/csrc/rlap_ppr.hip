@@ -2,7 +2,7 @@
 //     S = alpha (I - (1 - alpha) D^-1/2 A D^-1/2)^-1 on the segment's ids, entries >= eps kept, then (normalize_out) D_S^-1/2 S D_S^-1/2
 // as sparse rows [i, j, value], row-major per segment -- without an n_s x n_s buffer anywhere.
 //
-// The column pass of rlap_stats.hip numbers the segment's blocks (one per column id) and maps every row to the block of its row id.
+// The column pass (rlap_snapshot.hip) numbers the segment's blocks (one per column id) and maps every row to the block of its row id.
 // Columns of S are found 64 at a time: a tile is (segment, 64 source blocks), an n_s x 64 float64 matrix with one row per node and
 // one lane per source, run through the K fixed Chebyshev steps of rlap_cheb.h (two live copies for the three-term recurrence; the
 // new iterate overwrites x_{k-1} in place).  One wave per node computes sum_r a_r X[rb[r], lane] over the rows of its block in row
@@ -27,7 +27,6 @@
 #include "../../include/rlap_hip.h"
 #include "rlap_cheb.h"
 #include "rlap_ppr.h"
-#include "rlap_stats.h"
 
 namespace rlap {
 namespace {
@@ -37,20 +36,6 @@ constexpr int PP_THREADS = 256;         // every other kernel
 constexpr int64_t PP_GROUP_TILES = 65535;   // tiles per group (k_pp_init's grid.y)
 enum { PERR_WEIGHT = COL_ERR_WORDS, PERR_WORDS = 8 };
 enum { T_SEG = 0, T_C0 = 1, T_XOFF = 2, T_ROFF = 3, T_FIELDS = 4 };   // tile table: int64 fields per tile
-
-#define PP_HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { std::fprintf(stderr, "[rlap_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(_e), __FILE__, __LINE__); return RLAP_E_HIP; } } while (0)
-
-inline unsigned pp_blocks(int64_t n, int bs) { return (unsigned)std::max<int64_t>(1, (n + bs - 1) / bs); }
-
-// last s with sb[s] <= b (empty segments share their sb value with the next one and are skipped)
-__device__ inline int64_t seg_of_block(const int64_t* __restrict__ sb, int64_t S, int64_t b) {
-    int64_t lo = 0, hi = S;
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (sb[mid] <= b) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 __global__ void k_pp_weights(const double* __restrict__ sc, int64_t m, int zero_ok, int32_t* __restrict__ err) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -87,7 +72,7 @@ __global__ void k_pp_bkeys(const double* __restrict__ sc, const int32_t* __restr
                            int64_t B, uint64_t* __restrict__ key, int32_t* __restrict__ val) {
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const int64_t s = seg_of_block(sb, S, b);
+    const int64_t s = seg_of(sb, S, b);
     key[b] = ((uint64_t)s << 32) | (uint64_t)(int64_t)sc[3 * (int64_t)bstart[b] + 1];
     val[b] = (int32_t)b;
 }
@@ -258,7 +243,7 @@ __global__ void k_pp_out(const uint64_t* __restrict__ key, const double* __restr
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= P) return;
     const int64_t p = (int64_t)(key[e] >> 32);
-    const int64_t s = seg_of_block(sb, S, p);
+    const int64_t s = seg_of(sb, S, p);
     const int64_t pj = sb[s] + (int64_t)(key[e] & 0xffffffffull);
     const double v = val[e];
     out[3 * e] = sc[3 * (int64_t)bstart[pos_blk[p]] + 1];
@@ -270,16 +255,6 @@ __global__ void k_pp_outptr(const int64_t* __restrict__ sb, int64_t S, const int
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s <= S) out_ptr[s] = rowptr[sb[s]];
 }
-
-struct Carve {
-    char* base; size_t off;
-    template <class T> T* take(int64_t count) {
-        off = (off + 255) & ~(size_t)255;
-        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += sizeof(T) * (size_t)(count > 0 ? count : 0);
-        return p;
-    }
-};
 
 struct Bufs {
     ColumnBufs col;
@@ -350,58 +325,51 @@ size_t snapshot_ppr_bytes(int64_t m, int64_t S, int64_t G, int64_t N, int64_t ou
 
 int snapshot_ppr_run(hipStream_t st, void* ws, size_t ws_bytes, const SnapshotPprArgs& a, SnapshotPprReport* rep) {
     *rep = SnapshotPprReport{};
-    const int64_t m = a.m, S = a.S, G = a.G, N = a.N;
+    const SnapshotSeg& in = a.seg;
+    const int64_t m = in.m, S = in.S, G = in.G, N = in.N;
     const int weighted = (a.flags & RLAP_PPR_WEIGHTED) ? 1 : 0, self_loop = (a.flags & RLAP_PPR_SELF_LOOP) ? 1 : 0;
     const int normalize = (a.flags & RLAP_PPR_NORMALIZE) ? 1 : 0, zero_ok = (a.flags & RLAP_PPR_ZERO_ROWS) ? 1 : 0;
-    // 1. the segment table, read back once (the host groups the tiles)
-    std::vector<int64_t> hptr((size_t)S + 1), hnp((size_t)G + 1, 0);
-    PP_HIPCHK(hipMemcpyAsync(hptr.data(), a.ptr, sizeof(int64_t) * (size_t)(S + 1), hipMemcpyDeviceToHost, st));
-    if (a.node_ptr) PP_HIPCHK(hipMemcpyAsync(hnp.data(), a.node_ptr, sizeof(int64_t) * (size_t)(G + 1), hipMemcpyDeviceToHost, st));
-    PP_HIPCHK(hipStreamSynchronize(st));
+    // 1. the tables, read back and checked
+    std::vector<int64_t> hptr, hnp;
+    int rc = read_tables_checked(st, in.ptr, S, m, in.node_ptr, G, N, &hptr, &hnp);
     rep->host_syncs = 1;
-    if (hptr[0] != 0 || hptr[(size_t)S] != m) return RLAP_E_BAD_ARG;
-    for (int64_t s = 0; s < S; ++s) if (hptr[(size_t)s + 1] < hptr[(size_t)s]) return RLAP_E_BAD_ARG;
-    if (a.node_ptr) {
-        if (hnp[0] != 0 || hnp[(size_t)G] != N) return RLAP_E_BAD_ARG;
-        for (int64_t g = 0; g < G; ++g) if (hnp[(size_t)g + 1] < hnp[(size_t)g]) return RLAP_E_BAD_ARG;
-    }
+    if (rc != RLAP_OK) return rc;
     Bufs B;
     Carve C{static_cast<char*>(ws), 0};
     if (carve_ppr(C, m, S, G, N, a.out_cap, a.K, B) > ws_bytes) return RLAP_E_WORKSPACE;
     if (m == 0) {
-        PP_HIPCHK(hipMemsetAsync(a.out_ptr, 0, sizeof(int64_t) * (size_t)(S + 1), st));
+        RLAP_HIPCHK(hipMemsetAsync(a.out_ptr, 0, sizeof(int64_t) * (size_t)(S + 1), st));
         return RLAP_OK;
     }
     // 2. the column pass, the weights, the degrees, read back once
-    PP_HIPCHK(hipMemsetAsync(B.col.err, 0, sizeof(int32_t) * PERR_WORDS, st));
+    RLAP_HIPCHK(hipMemsetAsync(B.col.err, 0, sizeof(int32_t) * PERR_WORDS, st));
     std::vector<int64_t> hnodes((size_t)S);
     int64_t* d_nodes = B.nodes;
-    int rc = column_pass_enqueue(st, a.sc, m, a.ptr, S, a.node_ptr, G, N, B.col, d_nodes);
+    rc = column_pass_enqueue(st, in.sc, m, in.ptr, S, in.node_ptr, G, N, B.col, d_nodes);
     if (rc != RLAP_OK) return rc;
-    hipLaunchKernelGGL(k_pp_weights, dim3(pp_blocks(m, 256)), dim3(256), 0, st, a.sc, m, zero_ok, B.col.err);
-    PP_HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_pp_weights, dim3(grid_blocks(m, 256)), dim3(256), 0, st, in.sc, m, zero_ok, B.col.err);
+    RLAP_HIPCHK(hipGetLastError());
     int32_t herr[PERR_WORDS];
-    PP_HIPCHK(hipMemcpyAsync(hnodes.data(), d_nodes, sizeof(int64_t) * (size_t)S, hipMemcpyDeviceToHost, st));
-    PP_HIPCHK(hipMemcpyAsync(herr, B.col.err, sizeof(herr), hipMemcpyDeviceToHost, st));
-    PP_HIPCHK(hipStreamSynchronize(st));
+    RLAP_HIPCHK(hipMemcpyAsync(hnodes.data(), d_nodes, sizeof(int64_t) * (size_t)S, hipMemcpyDeviceToHost, st));
+    RLAP_HIPCHK(hipMemcpyAsync(herr, B.col.err, sizeof(herr), hipMemcpyDeviceToHost, st));
+    RLAP_HIPCHK(hipStreamSynchronize(st));
     rep->host_syncs += 1;
-    if (herr[COL_ERR_RANGE]) return RLAP_E_INDEX_RANGE;
-    if (herr[COL_ERR_GROUP]) return RLAP_E_NOT_GROUPED;
-    if (herr[COL_ERR_NOCOL]) return RLAP_E_NOT_SYMMETRIC;
+    rc = layout_status(herr);
+    if (rc != RLAP_OK) return rc;
     if (weighted && herr[PERR_WEIGHT]) return RLAP_E_BAD_ARG;
     int64_t Btot = 0;
     for (int64_t s = 0; s < S; ++s) Btot += hnodes[(size_t)s];
     if (Btot > B.col.bcap) return RLAP_E_INTERNAL;
     // 3. per block and per row: degrees, normalised weights, ranks by id
-    hipLaunchKernelGGL(k_pp_degrees, dim3(pp_blocks(Btot, 256)), dim3(256), 0, st, a.sc, B.col.bstart, Btot, weighted, self_loop, a.alpha,
+    hipLaunchKernelGGL(k_pp_degrees, dim3(grid_blocks(Btot, 256)), dim3(256), 0, st, in.sc, B.col.bstart, Btot, weighted, self_loop, a.alpha,
                        B.dinv, B.cdiag);
-    hipLaunchKernelGGL(k_pp_norm, dim3(pp_blocks(m, 256)), dim3(256), 0, st, a.sc, m, weighted, a.alpha, B.col.blk, B.col.rb, B.dinv, B.a);
-    hipLaunchKernelGGL(k_pp_bkeys, dim3(pp_blocks(Btot, 256)), dim3(256), 0, st, a.sc, B.col.bstart, B.col.sb, S, Btot, B.bkey, B.bval);
-    PP_HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_pp_norm, dim3(grid_blocks(m, 256)), dim3(256), 0, st, in.sc, m, weighted, a.alpha, B.col.blk, B.col.rb, B.dinv, B.a);
+    hipLaunchKernelGGL(k_pp_bkeys, dim3(grid_blocks(Btot, 256)), dim3(256), 0, st, in.sc, B.col.bstart, B.col.sb, S, Btot, B.bkey, B.bval);
+    RLAP_HIPCHK(hipGetLastError());
     size_t tb = B.tmp_bytes;
-    PP_HIPCHK(rocprim::radix_sort_pairs(B.tmp, tb, B.bkey, B.bkey_out, B.bval, B.pos_blk, (size_t)Btot, 0, 32 + bits_for(S), st));
-    hipLaunchKernelGGL(k_pp_ranks, dim3(pp_blocks(Btot, 256)), dim3(256), 0, st, B.bkey_out, B.pos_blk, B.col.sb, Btot, B.rank);
-    PP_HIPCHK(hipGetLastError());
+    RLAP_HIPCHK(rocprim::radix_sort_pairs(B.tmp, tb, B.bkey, B.bkey_out, B.bval, B.pos_blk, (size_t)Btot, 0, 32 + bits_for(S), st));
+    hipLaunchKernelGGL(k_pp_ranks, dim3(grid_blocks(Btot, 256)), dim3(256), 0, st, B.bkey_out, B.pos_blk, B.col.sb, Btot, B.rank);
+    RLAP_HIPCHK(hipGetLastError());
     // 4. tiles and groups (small segments' tiles first), uploaded with the Chebyshev weights
     std::vector<int64_t> tab;
     std::vector<int64_t> gstart;   // first tile of each group
@@ -437,11 +405,11 @@ int snapshot_ppr_run(hipStream_t st, void* ws, size_t ws_bytes, const SnapshotPp
     tab.push_back(ntiles);
     std::vector<double> om((size_t)std::max<int32_t>(a.K, 1));
     cheb::omegas(a.alpha, a.K, om.data());
-    PP_HIPCHK(hipMemcpyAsync(B.tab, tab.data(), sizeof(int64_t) * tab.size(), hipMemcpyHostToDevice, st));
-    PP_HIPCHK(hipMemcpyAsync(B.om, om.data(), sizeof(double) * om.size(), hipMemcpyHostToDevice, st));
-    PP_HIPCHK(hipMemsetAsync(B.top, 0, sizeof(int64_t), st));
+    RLAP_HIPCHK(hipMemcpyAsync(B.tab, tab.data(), sizeof(int64_t) * tab.size(), hipMemcpyHostToDevice, st));
+    RLAP_HIPCHK(hipMemcpyAsync(B.om, om.data(), sizeof(double) * om.size(), hipMemcpyHostToDevice, st));
+    RLAP_HIPCHK(hipMemsetAsync(B.top, 0, sizeof(int64_t), st));
     rep->groups = ngroups;
-    Tiles T{B.tab, B.om, a.sc, B.col.bstart, B.col.rb, B.col.sb, B.a, B.cdiag, B.rank, B.x, a.alpha, a.eps, a.K};
+    Tiles T{B.tab, B.om, in.sc, B.col.bstart, B.col.rb, B.col.sb, B.a, B.cdiag, B.rank, B.x, a.alpha, a.eps, a.K};
     // 5. the sweeps, group by group; after step K each group's kept entries are counted, scanned and staged
     for (int64_t g = 0; g < ngroups; ++g) {
         const int64_t* gt = B.gt + g;
@@ -454,40 +422,40 @@ int snapshot_ppr_run(hipStream_t st, void* ws, size_t ws_bytes, const SnapshotPp
             rep->launches += 1;
         } else {
             for (int32_t k = 1; k < a.K; ++k) {
-                hipLaunchKernelGGL(k_pp_large, dim3(pp_blocks(rows, PP_THREADS / 64)), dim3(PP_THREADS), 0, st, T, gt, nt, rows, k);
+                hipLaunchKernelGGL(k_pp_large, dim3(grid_blocks(rows, PP_THREADS / 64)), dim3(PP_THREADS), 0, st, T, gt, nt, rows, k);
                 rep->launches += 1;
             }
         }
-        hipLaunchKernelGGL(k_pp_keep, dim3(pp_blocks(rows, PP_THREADS / 64)), dim3(PP_THREADS), 0, st, T, gt, nt, rows, 0, B.cnt, B.scan,
+        hipLaunchKernelGGL(k_pp_keep, dim3(grid_blocks(rows, PP_THREADS / 64)), dim3(PP_THREADS), 0, st, T, gt, nt, rows, 0, B.cnt, B.scan,
                            B.top, B.kin, B.vin, a.out_cap);
-        PP_HIPCHK(hipGetLastError());
+        RLAP_HIPCHK(hipGetLastError());
         size_t sbytes = B.tmp_bytes;
-        PP_HIPCHK(rocprim::inclusive_scan(B.tmp, sbytes, B.cnt, B.scan, (size_t)rows, rocprim::plus<int64_t>(), st));
-        hipLaunchKernelGGL(k_pp_keep, dim3(pp_blocks(rows, PP_THREADS / 64)), dim3(PP_THREADS), 0, st, T, gt, nt, rows, 1, B.cnt, B.scan,
+        RLAP_HIPCHK(rocprim::inclusive_scan(B.tmp, sbytes, B.cnt, B.scan, (size_t)rows, rocprim::plus<int64_t>(), st));
+        hipLaunchKernelGGL(k_pp_keep, dim3(grid_blocks(rows, PP_THREADS / 64)), dim3(PP_THREADS), 0, st, T, gt, nt, rows, 1, B.cnt, B.scan,
                            B.top, B.kin, B.vin, a.out_cap);
         hipLaunchKernelGGL(k_pp_top, dim3(1), dim3(64), 0, st, B.top, B.scan, rows);
-        PP_HIPCHK(hipGetLastError());
+        RLAP_HIPCHK(hipGetLastError());
         rep->launches += 4;
     }
     // 6. the kept count, read back once: too many for the caller's buffer -> nothing is written, the count is reported
     int64_t P = 0;
-    PP_HIPCHK(hipMemcpyAsync(&P, B.top, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    PP_HIPCHK(hipStreamSynchronize(st));
+    RLAP_HIPCHK(hipMemcpyAsync(&P, B.top, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    RLAP_HIPCHK(hipStreamSynchronize(st));
     rep->host_syncs += 1;
     rep->kept = P;
     if (P > a.out_cap) return RLAP_E_OUT_CAPACITY;
     // 7. (segment, i, j) order, row sums, the output rows and offsets
     if (P > 0) {
         tb = B.tmp_bytes;
-        PP_HIPCHK(rocprim::radix_sort_pairs(B.tmp, tb, B.kin, B.kout, B.vin, B.vout, (size_t)P, 0, 32 + bits_for(Btot), st));
+        RLAP_HIPCHK(rocprim::radix_sort_pairs(B.tmp, tb, B.kin, B.kout, B.vin, B.vout, (size_t)P, 0, 32 + bits_for(Btot), st));
     }
-    PP_HIPCHK(hipMemsetAsync(B.rowptr, 0, sizeof(int64_t) * (size_t)(Btot + 1), st));
-    hipLaunchKernelGGL(k_pp_rowptr, dim3(pp_blocks(P, 256)), dim3(256), 0, st, B.kout, P, Btot, B.rowptr);
-    hipLaunchKernelGGL(k_pp_rowsum, dim3(pp_blocks(Btot, PP_THREADS / 64)), dim3(PP_THREADS), 0, st, B.vout, B.rowptr, Btot, B.dsinv);
-    hipLaunchKernelGGL(k_pp_out, dim3(pp_blocks(P, 256)), dim3(256), 0, st, B.kout, B.vout, P, B.col.sb, S, B.pos_blk, B.col.bstart, a.sc,
+    RLAP_HIPCHK(hipMemsetAsync(B.rowptr, 0, sizeof(int64_t) * (size_t)(Btot + 1), st));
+    hipLaunchKernelGGL(k_pp_rowptr, dim3(grid_blocks(P, 256)), dim3(256), 0, st, B.kout, P, Btot, B.rowptr);
+    hipLaunchKernelGGL(k_pp_rowsum, dim3(grid_blocks(Btot, PP_THREADS / 64)), dim3(PP_THREADS), 0, st, B.vout, B.rowptr, Btot, B.dsinv);
+    hipLaunchKernelGGL(k_pp_out, dim3(grid_blocks(P, 256)), dim3(256), 0, st, B.kout, B.vout, P, B.col.sb, S, B.pos_blk, B.col.bstart, in.sc,
                        B.dsinv, normalize, a.out);
-    hipLaunchKernelGGL(k_pp_outptr, dim3(pp_blocks(S + 1, 256)), dim3(256), 0, st, B.col.sb, S, B.rowptr, a.out_ptr);
-    PP_HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_pp_outptr, dim3(grid_blocks(S + 1, 256)), dim3(256), 0, st, B.col.sb, S, B.rowptr, a.out_ptr);
+    RLAP_HIPCHK(hipGetLastError());
     return RLAP_OK;
 }
 

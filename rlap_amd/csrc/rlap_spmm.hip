@@ -5,7 +5,7 @@
 // A translation unit of its own: no device function is shared with the elimination kernels.
 //
 //   tables   rlap_gcn.hip's: ptr / node_ptr checked on the device, copies (or well-formed stand-ins) for every later kernel.
-//   columns  the column pass of rlap_stats.hip: blocks, bstart, rb[r] = block of row r's source, idx[slot of an id] = its block.
+//   columns  the column pass (rlap_snapshot.hip): blocks, bstart, rb[r] = block of row r's source, idx[slot of an id] = its block.
 //   degrees  rlap_gcn.hip's k_gc_degree: dis[b], the loop weight lw[b], the loop rows of the call -- the coefficients are the bits
 //            of rlap_snapshot_gcn_norm because they come from the same kernel and the same rlap_gcnmath.h.
 //   sources  (transposed only) rocPRIM's stable radix sort of (rb[r], r): perm, and [tlo[b], thi[b]) = the entries whose source is
@@ -32,7 +32,6 @@
 #include "rlap_gcnmath.h"
 #include "rlap_spmm.h"
 #include "rlap_spmm_api.h"
-#include "rlap_stats.h"
 
 namespace rlap {
 namespace {
@@ -43,8 +42,7 @@ constexpr int64_t SP_PART_BYTES = (int64_t)256 << 20;    // budget of the chunk 
 constexpr int64_t SP_PART_MIN = 4096;                    // chunk sums that always fit
 enum { CNT_LOOPS = 0, CNT_CHUNKED = 1, CNT_BLOCKS = 2, CNT_WORDS = 4 };
 
-#define SP_HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { std::fprintf(stderr, "[rlap_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(_e), __FILE__, __LINE__); return RLAP_E_HIP; } } while (0)
-
+// (its own grid helper: the cap is applied to the 64-bit count, before it is narrowed)
 inline unsigned sp_blocks(int64_t n, int bs) { return (unsigned)std::min<int64_t>(SP_MAX_GRID, std::max<int64_t>(1, (n + bs - 1) / bs)); }
 
 // what the kernels share (ptr is the checked copy)
@@ -66,15 +64,6 @@ struct Sp {
 
 __device__ inline bool sp_failed(const Sp& a) {
     return (a.err[COL_ERR_RANGE] | a.err[COL_ERR_GROUP] | a.err[COL_ERR_NOCOL] | a.err[GCN_ERR_ARG]) != 0;
-}
-
-__device__ inline int64_t sp_seg_of(const int64_t* __restrict__ tab, int64_t S, int64_t r) {
-    int64_t lo = 0, hi = S;
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (tab[mid] <= r) lo = mid; else hi = mid;
-    }
-    return lo;
 }
 
 __device__ inline int64_t sp_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -246,7 +235,7 @@ __global__ void k_sp_lists(Sp a) {
                 atomicAdd(&a.cnt[CNT_CHUNKED], 1ull);
             }
             const int64_t r = sp_clamp(a.bstart[b], 0, a.m - 1);
-            a.blay[b] = (int32_t)(sp_seg_of(a.ptr, a.S, r) / a.G);
+            a.blay[b] = (int32_t)(seg_of(a.ptr, a.S, r) / a.G);
         }
         a.nch[b] = nc;
         if (b == 0) a.cnt[CNT_BLOCKS] = (unsigned long long)nb;
@@ -335,16 +324,6 @@ __global__ __launch_bounds__(SP_THREADS) void k_sp_rows(Sp a, const T* __restric
     }
 }
 
-struct Carve {
-    char* base; size_t off;
-    template <class T> T* take(int64_t count) {
-        off = (off + 255) & ~(size_t)255;
-        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += sizeof(T) * (size_t)(count > 0 ? count : 0);
-        return p;
-    }
-};
-
 struct Bufs {
     ColumnBufs col;
     int64_t *cptr, *cnp, *nodes, *choff;
@@ -418,7 +397,7 @@ int launch_sums(hipStream_t st, Sp a, const SnapshotSpmmArgs& g, int64_t pcap) {
         if (vec) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sp_rows<T, V>), dim3(nb), dim3(SP_THREADS), 0, st, a, x, y);
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sp_rows<T, 1>), dim3(nb), dim3(SP_THREADS), 0, st, a, x, y);
     }
-    SP_HIPCHK(hipGetLastError());
+    RLAP_HIPCHK(hipGetLastError());
     return RLAP_OK;
 }
 
@@ -432,7 +411,8 @@ size_t snapshot_spmm_bytes(int64_t m, int64_t S, int64_t G, int64_t N, int64_t F
 
 int snapshot_spmm_run(hipStream_t st, void* ws, size_t ws_bytes, const SnapshotSpmmArgs& g, SnapshotSpmmReport* rep) {
     *rep = SnapshotSpmmReport{};
-    const int64_t m = g.m, S = g.S, G = g.G, N = g.N, F = g.F;
+    const SnapshotSeg& in = g.seg;
+    const int64_t m = in.m, S = in.S, G = in.G, N = in.N, F = g.F;
     Bufs B;
     Carve C{static_cast<char*>(ws), 0};
     if (carve_spmm(C, m, S, G, N, F, g.flags, g.part_limit, B) > ws_bytes) return RLAP_E_WORKSPACE;
@@ -440,7 +420,7 @@ int snapshot_spmm_run(hipStream_t st, void* ws, size_t ws_bytes, const SnapshotS
     const int loops = (g.flags & RLAP_GCN_SELF_LOOPS) ? 1 : 0, normalize = (g.flags & RLAP_GCN_NORMALIZE) ? 1 : 0;
     const int transpose = (g.flags & RLAP_SPMM_TRANSPOSE) ? 1 : 0;
     Sp a{};
-    a.sc = g.sc; a.m = m; a.ptr = B.cptr; a.S = S; a.G = G; a.N = N; a.layers = S / G; a.F = F;
+    a.sc = in.sc; a.m = m; a.ptr = B.cptr; a.S = S; a.G = G; a.N = N; a.layers = S / G; a.F = F;
     a.weighted = (g.flags & RLAP_GCN_WEIGHTED) ? 1 : 0; a.loops = loops; a.normalize = normalize; a.transpose = transpose;
     a.per_layer = (g.flags & RLAP_SPMM_X_PER_LAYER) ? 1 : 0;
     a.fill = g.fill;
@@ -449,33 +429,33 @@ int snapshot_spmm_run(hipStream_t st, void* ws, size_t ws_bytes, const SnapshotS
     a.keys = B.keys; a.perm = B.perm; a.tlo = B.tlo; a.thi = B.thi;
     a.nch = B.nch; a.blay = B.blay; a.choff = B.choff; a.part = B.part; a.pcap = B.pcap;
     // 1. the tables, checked and copied; the column pass on the copies; the degrees of rlap_snapshot_gcn_norm
-    SP_HIPCHK(hipMemsetAsync(B.col.err, 0, sizeof(int32_t) * GCN_ERR_WORDS, st));
-    SP_HIPCHK(hipMemsetAsync(B.cnt, 0, sizeof(unsigned long long) * CNT_WORDS, st));
-    int rc = gcn_tables_enqueue(st, g.ptr, S, m, g.node_ptr, G, N, B.cptr, B.cnp, B.col.err);
+    RLAP_HIPCHK(hipMemsetAsync(B.col.err, 0, sizeof(int32_t) * GCN_ERR_WORDS, st));
+    RLAP_HIPCHK(hipMemsetAsync(B.cnt, 0, sizeof(unsigned long long) * CNT_WORDS, st));
+    int rc = gcn_tables_enqueue(st, in.ptr, S, m, in.node_ptr, G, N, B.cptr, B.cnp, B.col.err);
     if (rc != RLAP_OK) return rc;
     if (m > 0) {
-        rc = column_pass_enqueue(st, g.sc, m, B.cptr, S, g.node_ptr ? B.cnp : nullptr, G, N, B.col, B.nodes);
+        rc = column_pass_enqueue(st, in.sc, m, B.cptr, S, in.node_ptr ? B.cnp : nullptr, G, N, B.col, B.nodes);
         if (rc != RLAP_OK) return rc;
         if (normalize || loops) {
-            rc = gcn_degree_enqueue(st, g.sc, m, gflags, g.fill, B.col, B.dis, B.lw, &B.cnt[CNT_LOOPS]);
+            rc = gcn_degree_enqueue(st, in.sc, m, gflags, g.fill, B.col, B.dis, B.lw, &B.cnt[CNT_LOOPS]);
             if (rc != RLAP_OK) return rc;
         }
         // 2. transposed: the rows of every source, in input order
         if (transpose) {
             hipLaunchKernelGGL(k_sp_iota, dim3(sp_blocks(m, 256)), dim3(256), 0, st, B.vals, m);
-            SP_HIPCHK(hipGetLastError());
+            RLAP_HIPCHK(hipGetLastError());
             size_t sb = B.sort_bytes;
-            SP_HIPCHK(rocprim::radix_sort_pairs(B.sort_tmp, sb, (const int32_t*)B.col.rb, B.keys, (const int32_t*)B.vals, B.perm, (size_t)m,
+            RLAP_HIPCHK(rocprim::radix_sort_pairs(B.sort_tmp, sb, (const int32_t*)B.col.rb, B.keys, (const int32_t*)B.vals, B.perm, (size_t)m,
                                                 0u, 32u, st));
-            SP_HIPCHK(hipMemsetAsync(B.tlo, 0, sizeof(int32_t) * (size_t)B.col.bcap, st));
-            SP_HIPCHK(hipMemsetAsync(B.thi, 0, sizeof(int32_t) * (size_t)B.col.bcap, st));
+            RLAP_HIPCHK(hipMemsetAsync(B.tlo, 0, sizeof(int32_t) * (size_t)B.col.bcap, st));
+            RLAP_HIPCHK(hipMemsetAsync(B.thi, 0, sizeof(int32_t) * (size_t)B.col.bcap, st));
             hipLaunchKernelGGL(k_sp_bounds, dim3(sp_blocks(m, 256)), dim3(256), 0, st, a);
         }
         // 3. the long lists and their chunks
         hipLaunchKernelGGL(k_sp_lists, dim3(sp_blocks(B.col.bcap + 1, 256)), dim3(256), 0, st, a);
-        SP_HIPCHK(hipGetLastError());
+        RLAP_HIPCHK(hipGetLastError());
         size_t cb = B.scan_bytes;
-        SP_HIPCHK(rocprim::exclusive_scan(B.scan_tmp, cb, B.nch, B.choff, (int64_t)0, (size_t)(B.col.bcap + 1), rocprim::plus<int64_t>(), st));
+        RLAP_HIPCHK(rocprim::exclusive_scan(B.scan_tmp, cb, B.nch, B.choff, (int64_t)0, (size_t)(B.col.bcap + 1), rocprim::plus<int64_t>(), st));
     }
     // 4. the sums
     rc = (g.flags & RLAP_SPMM_X_F32) ? launch_sums<float>(st, a, g, B.pcap) : launch_sums<double>(st, a, g, B.pcap);
@@ -483,14 +463,12 @@ int snapshot_spmm_run(hipStream_t st, void* ws, size_t ws_bytes, const SnapshotS
     // 5. the error words and the counts, read back once
     int32_t herr[GCN_ERR_WORDS];
     unsigned long long hcnt[CNT_WORDS];
-    SP_HIPCHK(hipMemcpyAsync(herr, B.col.err, sizeof(herr), hipMemcpyDeviceToHost, st));
-    SP_HIPCHK(hipMemcpyAsync(hcnt, B.cnt, sizeof(hcnt), hipMemcpyDeviceToHost, st));
-    SP_HIPCHK(hipStreamSynchronize(st));
+    RLAP_HIPCHK(hipMemcpyAsync(herr, B.col.err, sizeof(herr), hipMemcpyDeviceToHost, st));
+    RLAP_HIPCHK(hipMemcpyAsync(hcnt, B.cnt, sizeof(hcnt), hipMemcpyDeviceToHost, st));
+    RLAP_HIPCHK(hipStreamSynchronize(st));
     rep->host_syncs = 1;
     if (herr[GCN_ERR_ARG]) return RLAP_E_BAD_ARG;
-    if (herr[COL_ERR_RANGE]) return RLAP_E_INDEX_RANGE;
-    if (herr[COL_ERR_GROUP]) return RLAP_E_NOT_GROUPED;
-    if (herr[COL_ERR_NOCOL]) return RLAP_E_NOT_SYMMETRIC;
+    if (const int lrc = layout_status(herr)) return lrc;
     if (herr[GCN_ERR_WEIGHT]) return RLAP_E_BAD_ARG;
     rep->entries = m + (loops ? (S / G) * N - (int64_t)hcnt[CNT_LOOPS] : 0);
     rep->blocks = (int64_t)hcnt[CNT_BLOCKS];

@@ -2,17 +2,12 @@
 // holds the kernels and their orchestration, and the C ABI in rlap_api.hip, which owns the handle, its lock and its arena.  The
 // summation order itself is in rlap_spmm.h.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stddef.h>
-#include <stdint.h>
+#include "rlap_snapshot.h"
 
 namespace rlap {
 
 struct SnapshotSpmmArgs {
-    const double* sc; int64_t m;              // (m, 3) rows [row, col, w]
-    const int64_t* ptr; int64_t S;            // [S+1] segment offsets
-    const int64_t* node_ptr; int64_t G;       // [G+1] or nullptr (then G = 1 and every id range is [0, N))
-    int64_t N;                                // num_nodes
+    SnapshotSeg seg;
     int flags;                                // RLAP_GCN_WEIGHTED / SELF_LOOPS / NORMALIZE, RLAP_SPMM_* (include/rlap_hip.h)
     double fill;                              // weight of an added self loop
     const void* x; int64_t F;                 // (N, F), or with RLAP_SPMM_X_PER_LAYER (S / G, N, F); float32 with RLAP_SPMM_X_F32

@@ -2,13 +2,8 @@
 // node count and the largest eigenvalue of its adjacency matrix by Lanczos in float64.  A translation unit of its own: it shares
 // no device function with the elimination kernels (their register and LDS budgets are read back by tests/test_cabi_symbols.py).
 //
-// Layout the kernels rely on (checked, never assumed): the output pass writes survivor i's column as one contiguous block of rows
-// (row, i, w) (k_sc_compact: row r belongs to the owner with row_off[i] <= r < row_off[i+1]), so within a segment every column id
-// starts exactly one block.  A column id that starts two blocks of one segment is reported (RLAP_E_NOT_GROUPED), as is a row id
-// without a column of its own (RLAP_E_NOT_SYMMETRIC) or an id outside the segment's range (RLAP_E_INDEX_RANGE).
-//
-// Blocks are numbered over the whole call (an inclusive scan of the block-start flags), so segment s owns blocks [sb[s], sb[s+1])
-// and its Lanczos vectors are the entries [sb[s], sb[s+1]) of vectors of B (= blocks of all segments) doubles.  y = A x is then
+// The column pass (rlap_snapshot.hip) checks the layout and numbers the blocks over the whole call, so segment s owns blocks
+// [sb[s], sb[s+1]) and its Lanczos vectors are the entries [sb[s], sb[s+1]) of vectors of B (= blocks of all segments) doubles.  y = A x is then
 // y[b] = sum over the rows r of block b of w_r * x[rb[r]], with rb[r] the block of row r's id: a segmented reduction in a fixed
 // order, no atomics.  Every floating-point reduction below runs in a fixed order (lane strides, xor butterflies, four wave
 // partials added in one order), so a call gives the same bits every time.
@@ -32,93 +27,7 @@ constexpr int ST_THREADS = 256;       // every kernel of this file but the per-s
 constexpr int ST_TILE = 256;          // large regime: columns per workgroup (16 groups of 16 lanes, 16 columns each)
 constexpr int ST_CHECK_EVERY = 4;     // Ritz value of T_j every this many steps (and on a breakdown, and at max_iter)
 constexpr int ST_CHUNK = 32;          // large regime: steps enqueued between two reads of the done count
-enum { ERR_RANGE = 0, ERR_GROUP = 1, ERR_NOCOL = 2, ERR_DONE = 3, ERR_MAX_ITERS = 4, ERR_NOT_CONV = 5, ERR_WORDS = 8 };
-
-#define ST_HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { std::fprintf(stderr, "[rlap_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(_e), __FILE__, __LINE__); return RLAP_E_HIP; } } while (0)
-
-inline unsigned st_blocks(int64_t n, int bs) { return (unsigned)std::max<int64_t>(1, (n + bs - 1) / bs); }
-
-// segment of row r: the last s with ptr[s] <= r (empty segments share their ptr value with the next one and are skipped)
-__device__ inline int64_t seg_of(const int64_t* __restrict__ ptr, int64_t S, int64_t r) {
-    int64_t lo = 0, hi = S;   // ptr[lo] <= r < ptr[hi]
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (ptr[mid] <= r) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// the index slot of id x in segment s (ids of segment s lie in [node_ptr[g], node_ptr[g+1]), g = s % G; segments s and s' with
-// s / G == s' / G cover disjoint ranges, so region s / G of N slots holds all of them); -1 when x is not an id of that range
-__device__ inline int64_t id_slot(double x, int64_t s, const int64_t* __restrict__ node_ptr, int64_t G, int64_t N) {
-    const int64_t g = s % G;
-    const int64_t lo = node_ptr ? node_ptr[g] : 0, hi = node_ptr ? node_ptr[g + 1] : N;
-    if (!(x >= (double)lo && x < (double)hi) || x != floor(x)) return -1;
-    return (s / G) * N + (int64_t)x;
-}
-
-__global__ void k_st_flags(const double* __restrict__ sc, int64_t m, int32_t* __restrict__ f) {
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= m) return;
-    f[r] = (r == 0 || sc[3 * r + 1] != sc[3 * (r - 1) + 1]) ? 1 : 0;
-}
-
-__global__ void k_st_segmark(const int64_t* __restrict__ ptr, int64_t S, int32_t* __restrict__ f) {
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= S) return;
-    if (ptr[s] < ptr[s + 1]) f[ptr[s]] = 1;   // (a segment's first row starts a block whatever the row before it holds)
-}
-
-__global__ void k_st_index_fill(int32_t* __restrict__ idx, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) idx[i] = -1;
-}
-
-// block starts: bstart[b] = first row of block b, idx[slot of its column id] = b (a second block of the same id: ERR_GROUP)
-__global__ void k_st_blocks(const double* __restrict__ sc, int64_t m, const int32_t* __restrict__ f, const int32_t* __restrict__ blk,
-                            const int64_t* __restrict__ ptr, int64_t S, const int64_t* __restrict__ node_ptr, int64_t G, int64_t N,
-                            int32_t* __restrict__ idx, int32_t* __restrict__ bstart, int64_t bcap, int32_t* __restrict__ err) {
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= m) return;
-    // (more blocks than ids can be told apart: some id starts two blocks or lies out of range -- reported, nothing written past bcap)
-    if (r == 0) { if (blk[m - 1] <= bcap) bstart[blk[m - 1]] = (int32_t)m; else atomicOr(&err[ERR_GROUP], 1); }
-    if (!f[r]) return;
-    const int32_t b = blk[r] - 1;
-    if (b < bcap) bstart[b] = (int32_t)r;
-    const int64_t slot = id_slot(sc[3 * r + 1], seg_of(ptr, S, r), node_ptr, G, N);
-    if (slot < 0) { atomicOr(&err[ERR_RANGE], 1); return; }
-    if (atomicCAS(&idx[slot], -1, b) != -1) atomicOr(&err[ERR_GROUP], 1);
-}
-
-// sb[s] = blocks before segment s; nodes[s] = its blocks
-__global__ void k_st_segblocks(const int64_t* __restrict__ ptr, int64_t S, const int32_t* __restrict__ blk, int64_t* __restrict__ sb,
-                               int64_t* __restrict__ nodes) {
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s > S) return;
-    const int64_t p0 = ptr[s];
-    const int64_t b0 = p0 == 0 ? 0 : blk[p0 - 1];
-    sb[s] = b0;
-    if (s < S) {
-        const int64_t p1 = ptr[s + 1];
-        nodes[s] = (p1 == 0 ? 0 : blk[p1 - 1]) - b0;
-    }
-}
-
-// rb[r] = block of row r's id in r's segment
-__global__ void k_st_rows(const double* __restrict__ sc, int64_t m, const int64_t* __restrict__ ptr, int64_t S,
-                          const int64_t* __restrict__ node_ptr, int64_t G, int64_t N, const int32_t* __restrict__ idx,
-                          const int64_t* __restrict__ sb, int32_t* __restrict__ rb, int32_t* __restrict__ err) {
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= m) return;
-    const int64_t s = seg_of(ptr, S, r);
-    const int64_t slot = id_slot(sc[3 * r], s, node_ptr, G, N);
-    int32_t b = -1;
-    if (slot < 0) atomicOr(&err[ERR_RANGE], 1);
-    else {
-        b = idx[slot];
-        if (b < sb[s] || b >= sb[s + 1]) { atomicOr(&err[ERR_NOCOL], 1); b = -1; }
-    }
-    rb[r] = b;
-}
+enum { ERR_DONE = COL_ERR_WORDS, ERR_MAX_ITERS = 4, ERR_NOT_CONV = 5, ERR_WORDS = 8 };   // error words behind the column pass's
 
 // empty segments: 0 / 0 / 0 steps, converged (lambda_max = 0 is exact)
 __global__ void k_st_empty(const int64_t* __restrict__ sb, int64_t S, double* __restrict__ lam, int32_t* __restrict__ iters,
@@ -344,20 +253,9 @@ __global__ __launch_bounds__(64) void k_st_lz_check(LargeTables L, int32_t j, do
     if (d != 1) atomicAdd(&err[ERR_NOT_CONV], 1);
 }
 
-struct Carve {
-    char* base; size_t off;
-    template <class T> T* take(int64_t count) {
-        off = (off + 255) & ~(size_t)255;
-        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += sizeof(T) * (size_t)(count > 0 ? count : 0);
-        return p;
-    }
-};
-
 struct Bufs {
-    int32_t *f, *blk, *bstart, *idx, *err, *stage;
-    int64_t* sb;
-    void* scan_tmp; size_t scan_bytes;
+    ColumnBufs col;
+    int32_t* stage;
     double *v0, *v1, *part, *al, *be, *scr, *tn;
     int32_t* done;
 };
@@ -378,10 +276,7 @@ Dims dims_of(int64_t m, int64_t S, int64_t G, int64_t N) {
 
 size_t carve_stats(Carve& C, int64_t m, int64_t S, int64_t G, int64_t N, int32_t max_iter, Bufs& B) {
     const Dims d = dims_of(m, S, G, N);
-    ColumnBufs cb;
-    C.off = column_pass_carve(C.base, C.off, m, S, G, N, ERR_WORDS, &cb);
-    B.f = cb.rb; B.blk = cb.blk; B.bstart = cb.bstart; B.sb = cb.sb; B.idx = cb.idx; B.err = cb.err;
-    B.scan_tmp = cb.scan_tmp; B.scan_bytes = cb.scan_bytes;
+    C.off = column_pass_carve(C.base, C.off, m, S, G, N, ERR_WORDS, &B.col);
     B.stage = C.take<int32_t>(d.stage_n);
     const int64_t vb = d.lcap > 0 ? d.bcap : 0;   // (vectors of the large regime only)
     B.v0 = C.take<double>(vb);
@@ -409,42 +304,6 @@ __global__ void k_st_fill_large(const int32_t* __restrict__ lseg, int32_t nlarge
 
 }  // namespace
 
-static_assert(COL_ERR_RANGE == ERR_RANGE && COL_ERR_GROUP == ERR_GROUP && COL_ERR_NOCOL == ERR_NOCOL && COL_ERR_WORDS <= ERR_WORDS, "");
-
-size_t column_pass_carve(char* base, size_t off, int64_t m, int64_t S, int64_t G, int64_t N, int err_words, ColumnBufs* B) {
-    Carve C{base, off};
-    B->idx_n = (S / G) * N;
-    B->bcap = std::min<int64_t>(m, B->idx_n);
-    B->rb = C.take<int32_t>(m);   // (the block-start flags first, then rb)
-    B->blk = C.take<int32_t>(m);
-    B->bstart = C.take<int32_t>(B->bcap + 1);
-    B->sb = C.take<int64_t>(S + 1);
-    B->idx = C.take<int32_t>(B->idx_n);
-    B->err = C.take<int32_t>(std::max<int>(err_words, COL_ERR_WORDS));
-    B->scan_bytes = 0;
-    (void)rocprim::inclusive_scan(nullptr, B->scan_bytes, (const int32_t*)nullptr, (int32_t*)nullptr, (size_t)std::max<int64_t>(m, 1),
-                                  rocprim::plus<int32_t>(), (hipStream_t)0);
-    B->scan_tmp = C.take<char>((int64_t)B->scan_bytes);
-    return C.off;
-}
-
-int column_pass_enqueue(hipStream_t st, const double* sc, int64_t m, const int64_t* ptr, int64_t S, const int64_t* node_ptr, int64_t G,
-                        int64_t N, const ColumnBufs& B, int64_t* nodes) {
-    int32_t* f = B.rb;   // block-start flags, then (k_st_rows) the row -> block map
-    hipLaunchKernelGGL(k_st_flags, dim3(st_blocks(m, 256)), dim3(256), 0, st, sc, m, f);
-    hipLaunchKernelGGL(k_st_segmark, dim3(st_blocks(S, 256)), dim3(256), 0, st, ptr, S, f);
-    hipLaunchKernelGGL(k_st_index_fill, dim3((unsigned)std::min<int64_t>(4096, st_blocks(B.idx_n, 256))), dim3(256), 0, st, B.idx, B.idx_n);
-    ST_HIPCHK(hipGetLastError());
-    size_t sb_bytes = B.scan_bytes;
-    ST_HIPCHK(rocprim::inclusive_scan(B.scan_tmp, sb_bytes, f, B.blk, (size_t)m, rocprim::plus<int32_t>(), st));
-    hipLaunchKernelGGL(k_st_blocks, dim3(st_blocks(m, 256)), dim3(256), 0, st, sc, m, f, B.blk, ptr, S, node_ptr, G, N,
-                       B.idx, B.bstart, B.bcap, B.err);
-    hipLaunchKernelGGL(k_st_segblocks, dim3(st_blocks(S + 1, 256)), dim3(256), 0, st, ptr, S, B.blk, B.sb, nodes);
-    hipLaunchKernelGGL(k_st_rows, dim3(st_blocks(m, 256)), dim3(256), 0, st, sc, m, ptr, S, node_ptr, G, N, B.idx, B.sb, f, B.err);
-    ST_HIPCHK(hipGetLastError());
-    return RLAP_OK;
-}
-
 size_t snapshot_stats_bytes(int64_t m, int64_t S, int64_t G, int64_t N, int32_t max_iter) {
     Carve C{nullptr, 0};
     Bufs B;
@@ -453,49 +312,40 @@ size_t snapshot_stats_bytes(int64_t m, int64_t S, int64_t G, int64_t N, int32_t 
 
 int snapshot_stats_run(hipStream_t st, void* ws, size_t ws_bytes, const SnapshotStatsArgs& a, SnapshotStatsReport* rep) {
     *rep = SnapshotStatsReport{};
-    const int64_t m = a.m, S = a.S, G = a.G, N = a.N;
-    // 1. the segment table, read back once (the host picks a regime per segment)
-    std::vector<int64_t> hptr((size_t)S + 1), hnp((size_t)G + 1, 0);
-    ST_HIPCHK(hipMemcpyAsync(hptr.data(), a.ptr, sizeof(int64_t) * (size_t)(S + 1), hipMemcpyDeviceToHost, st));
-    if (a.node_ptr) ST_HIPCHK(hipMemcpyAsync(hnp.data(), a.node_ptr, sizeof(int64_t) * (size_t)(G + 1), hipMemcpyDeviceToHost, st));
-    ST_HIPCHK(hipStreamSynchronize(st));
+    const SnapshotSeg& in = a.seg;
+    const int64_t m = in.m, S = in.S, G = in.G, N = in.N;
+    // 1. the tables, read back and checked
+    std::vector<int64_t> hptr, hnp;
+    int rc = read_tables_checked(st, in.ptr, S, m, in.node_ptr, G, N, &hptr, &hnp);
     rep->host_syncs = 1;
-    if (hptr[0] != 0 || hptr[(size_t)S] != m) return RLAP_E_BAD_ARG;
-    for (int64_t s = 0; s < S; ++s) if (hptr[(size_t)s + 1] < hptr[(size_t)s]) return RLAP_E_BAD_ARG;
-    if (a.node_ptr) {
-        if (hnp[0] != 0 || hnp[(size_t)G] != N) return RLAP_E_BAD_ARG;
-        for (int64_t g = 0; g < G; ++g) if (hnp[(size_t)g + 1] < hnp[(size_t)g]) return RLAP_E_BAD_ARG;
-    }
+    if (rc != RLAP_OK) return rc;
     Bufs B;
     Carve C{static_cast<char*>(ws), 0};
     if (carve_stats(C, m, S, G, N, a.max_iter, B) > ws_bytes) return RLAP_E_WORKSPACE;
     const Dims d = dims_of(m, S, G, N);
     if (m == 0) {
-        ST_HIPCHK(hipMemsetAsync(a.nodes, 0, sizeof(int64_t) * (size_t)S, st));
-        ST_HIPCHK(hipMemsetAsync(a.lambda_max, 0, sizeof(double) * (size_t)S, st));
-        ST_HIPCHK(hipMemsetAsync(a.iters, 0, sizeof(int32_t) * (size_t)S, st));
+        RLAP_HIPCHK(hipMemsetAsync(a.nodes, 0, sizeof(int64_t) * (size_t)S, st));
+        RLAP_HIPCHK(hipMemsetAsync(a.lambda_max, 0, sizeof(double) * (size_t)S, st));
+        RLAP_HIPCHK(hipMemsetAsync(a.iters, 0, sizeof(int32_t) * (size_t)S, st));
         std::vector<int32_t> ones((size_t)S, 1);
-        ST_HIPCHK(hipMemcpyAsync(a.converged, ones.data(), sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, st));
-        ST_HIPCHK(hipStreamSynchronize(st));
+        RLAP_HIPCHK(hipMemcpyAsync(a.converged, ones.data(), sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, st));
+        RLAP_HIPCHK(hipStreamSynchronize(st));
         rep->host_syncs += 1;
         return RLAP_OK;
     }
     // 2. the column pass
-    ST_HIPCHK(hipMemsetAsync(B.err, 0, sizeof(int32_t) * ERR_WORDS, st));
-    const ColumnBufs cb{B.f, B.blk, B.bstart, B.sb, B.idx, B.err, B.scan_tmp, B.scan_bytes, d.bcap, d.idx_n};
-    const int crc = column_pass_enqueue(st, a.sc, m, a.ptr, S, a.node_ptr, G, N, cb, a.nodes);
-    if (crc != RLAP_OK) return crc;
-    int32_t* rb = B.f;   // (the flags are read by k_st_blocks only)
+    RLAP_HIPCHK(hipMemsetAsync(B.col.err, 0, sizeof(int32_t) * ERR_WORDS, st));
+    rc = column_pass_enqueue(st, in.sc, m, in.ptr, S, in.node_ptr, G, N, B.col, a.nodes);
+    if (rc != RLAP_OK) return rc;
     // 3. node counts and the layout checks, read back once
     std::vector<int64_t> hnodes((size_t)S);
     int32_t herr[ERR_WORDS];
-    ST_HIPCHK(hipMemcpyAsync(hnodes.data(), a.nodes, sizeof(int64_t) * (size_t)S, hipMemcpyDeviceToHost, st));
-    ST_HIPCHK(hipMemcpyAsync(herr, B.err, sizeof(herr), hipMemcpyDeviceToHost, st));
-    ST_HIPCHK(hipStreamSynchronize(st));
+    RLAP_HIPCHK(hipMemcpyAsync(hnodes.data(), a.nodes, sizeof(int64_t) * (size_t)S, hipMemcpyDeviceToHost, st));
+    RLAP_HIPCHK(hipMemcpyAsync(herr, B.col.err, sizeof(herr), hipMemcpyDeviceToHost, st));
+    RLAP_HIPCHK(hipStreamSynchronize(st));
     rep->host_syncs += 1;
-    if (herr[ERR_RANGE]) return RLAP_E_INDEX_RANGE;
-    if (herr[ERR_GROUP]) return RLAP_E_NOT_GROUPED;
-    if (herr[ERR_NOCOL]) return RLAP_E_NOT_SYMMETRIC;
+    rc = layout_status(herr);
+    if (rc != RLAP_OK) return rc;
     // 4. the regimes
     std::vector<int32_t> stage((size_t)d.stage_n, 0);
     int32_t nsmall = 0, nlarge = 0, ntiles = 0, nmax = 1;
@@ -521,15 +371,15 @@ int snapshot_stats_run(hipStream_t st, void* ws, size_t ws_bytes, const Snapshot
     }
     tp[nlarge] = ntiles;
     rep->small_segments = nsmall; rep->large_segments = nlarge;
-    ST_HIPCHK(hipMemcpyAsync(B.stage, stage.data(), sizeof(int32_t) * (size_t)d.stage_n, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_st_empty, dim3(st_blocks(S, 256)), dim3(256), 0, st, B.sb, S, a.lambda_max, a.iters, a.converged);
-    ST_HIPCHK(hipGetLastError());
+    RLAP_HIPCHK(hipMemcpyAsync(B.stage, stage.data(), sizeof(int32_t) * (size_t)d.stage_n, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_st_empty, dim3(grid_blocks(S, 256)), dim3(256), 0, st, B.col.sb, S, a.lambda_max, a.iters, a.converged);
+    RLAP_HIPCHK(hipGetLastError());
     if (nsmall > 0) {
         const size_t lds = sizeof(double) * (2 * (size_t)nmax + 4 * (size_t)a.max_iter);
-        ST_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_st_lanczos_small), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_st_lanczos_small, dim3((unsigned)nsmall), dim3(ST_THREADS), lds, st, B.stage, a.sc, a.weighted, B.bstart, rb,
-                           B.sb, nmax, a.tol, a.max_iter, a.lambda_max, a.iters, a.converged, B.err);
-        ST_HIPCHK(hipGetLastError());
+        RLAP_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_st_lanczos_small), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(k_st_lanczos_small, dim3((unsigned)nsmall), dim3(ST_THREADS), lds, st, B.stage, in.sc, a.weighted, B.col.bstart, B.col.rb,
+                           B.col.sb, nmax, a.tol, a.max_iter, a.lambda_max, a.iters, a.converged, B.col.err);
+        RLAP_HIPCHK(hipGetLastError());
     }
     int64_t steps = 0;
     if (nlarge > 0) {
@@ -537,31 +387,31 @@ int snapshot_stats_run(hipStream_t st, void* ws, size_t ws_bytes, const Snapshot
         L.lseg = B.stage + S; L.tp = L.lseg + d.lcap; L.tseg = L.tp + d.lcap + 1; L.tc0 = L.tseg + d.tcap;
         L.nlarge = nlarge; L.ntiles = ntiles; L.max_iter = a.max_iter;
         L.al = B.al; L.be = B.be; L.scr = B.scr; L.tn = B.tn; L.done = B.done; L.part = B.part;
-        hipLaunchKernelGGL(k_st_fill_large, dim3(64, (unsigned)nlarge), dim3(256), 0, st, L.lseg, nlarge, B.sb, B.v0, B.v1, B.tn, B.done);
-        ST_HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_st_fill_large, dim3(64, (unsigned)nlarge), dim3(256), 0, st, L.lseg, nlarge, B.col.sb, B.v0, B.v1, B.tn, B.done);
+        RLAP_HIPCHK(hipGetLastError());
         for (int32_t j0 = 1; j0 <= a.max_iter; j0 += ST_CHUNK) {
             const int32_t j1 = std::min<int32_t>(j0 + ST_CHUNK - 1, a.max_iter);
             for (int32_t j = j0; j <= j1; ++j) {
                 double* v = (j & 1) ? B.v0 : B.v1;   // v_j; the other vector holds v_{j-1} and receives v_{j+1}
                 double* w = (j & 1) ? B.v1 : B.v0;
-                hipLaunchKernelGGL(k_st_lz_spmv, dim3((unsigned)ntiles), dim3(ST_THREADS), 0, st, L, j, a.sc, a.weighted, B.bstart, rb, B.sb, v, w);
-                hipLaunchKernelGGL(k_st_lz_axpy, dim3((unsigned)ntiles), dim3(ST_THREADS), 0, st, L, j, B.sb, v, w);
-                hipLaunchKernelGGL(k_st_lz_scale, dim3((unsigned)ntiles), dim3(ST_THREADS), 0, st, L, j, B.sb, w);
-                hipLaunchKernelGGL(k_st_lz_check, dim3((unsigned)nlarge), dim3(64), 0, st, L, j, a.tol, a.lambda_max, a.iters, a.converged, B.err);
+                hipLaunchKernelGGL(k_st_lz_spmv, dim3((unsigned)ntiles), dim3(ST_THREADS), 0, st, L, j, in.sc, a.weighted, B.col.bstart, B.col.rb, B.col.sb, v, w);
+                hipLaunchKernelGGL(k_st_lz_axpy, dim3((unsigned)ntiles), dim3(ST_THREADS), 0, st, L, j, B.col.sb, v, w);
+                hipLaunchKernelGGL(k_st_lz_scale, dim3((unsigned)ntiles), dim3(ST_THREADS), 0, st, L, j, B.col.sb, w);
+                hipLaunchKernelGGL(k_st_lz_check, dim3((unsigned)nlarge), dim3(64), 0, st, L, j, a.tol, a.lambda_max, a.iters, a.converged, B.col.err);
                 rep->large_launches += 4;
             }
-            ST_HIPCHK(hipGetLastError());
+            RLAP_HIPCHK(hipGetLastError());
             int32_t ndone = 0;
-            ST_HIPCHK(hipMemcpyAsync(&ndone, B.err + ERR_DONE, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            ST_HIPCHK(hipStreamSynchronize(st));
+            RLAP_HIPCHK(hipMemcpyAsync(&ndone, B.col.err + ERR_DONE, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            RLAP_HIPCHK(hipStreamSynchronize(st));
             rep->host_syncs += 1;
             steps = j1;
             if (ndone >= nlarge) break;
         }
     }
     // 5. what the call reports
-    ST_HIPCHK(hipMemcpyAsync(herr, B.err, sizeof(herr), hipMemcpyDeviceToHost, st));
-    ST_HIPCHK(hipStreamSynchronize(st));
+    RLAP_HIPCHK(hipMemcpyAsync(herr, B.col.err, sizeof(herr), hipMemcpyDeviceToHost, st));
+    RLAP_HIPCHK(hipStreamSynchronize(st));
     rep->host_syncs += 1;
     rep->lanczos_steps = herr[ERR_MAX_ITERS];
     rep->large_steps = steps;

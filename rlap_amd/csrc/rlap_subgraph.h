@@ -2,17 +2,12 @@
 // rlap_subgraph.hip, which holds the kernels and their orchestration, and the C ABI in rlap_api.hip, which owns the handle, its lock
 // and its arena.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stddef.h>
-#include <stdint.h>
+#include "rlap_snapshot.h"
 
 namespace rlap {
 
 struct SnapshotSubArgs {
-    const double* sc; int64_t m;              // (m, 3) rows [row, col, w]
-    const int64_t* ptr; int64_t S;            // [S+1] segment offsets
-    const int64_t* node_ptr; int64_t G;       // [G+1] or nullptr (then G = 1 and every id range is [0, N))
-    int64_t N;                                // num_nodes
+    SnapshotSeg seg;
     const int64_t* nodes;                     // node lists, or nullptr (the set of a segment is the ids of its rows)
     const int64_t* nodes_ptr;                 // [S+1] list offsets, or nullptr (one list for all segments)
     int64_t nodes_len;

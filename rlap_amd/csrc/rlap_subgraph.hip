@@ -15,7 +15,7 @@
 //           one count per tile; scan of the tile counts; (b) the flags again, positions from the ballots, kept rows compacted in LDS
 //           and written with coalesced stores at the tile's base.  The lane of the first row of a segment writes out_ptr.
 // Every kernel is safe on malformed tables and ids (they only raise the error words, read back with the totals in the call's one
-// host synchronisation).  No device function is shared with another translation unit.
+// host synchronisation).  The segment search is that of rlap_snapshot.h; no device function is shared with the elimination kernels.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -36,10 +36,6 @@ constexpr int SG_RPT = SUB_TILE / SG_THREADS;   // rows per thread of a filter t
 enum { SERR_ARG = 0, SERR_RANGE = 1, SERR_WORDS = 4 };
 enum { TOT_KEPT = 0, TOT_IDS = 1, TOT_WORDS = 2 };
 
-#define SG_HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { std::fprintf(stderr, "[rlap_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(_e), __FILE__, __LINE__); return RLAP_E_HIP; } } while (0)
-
-inline unsigned sg_blocks(int64_t n, int bs) { return (unsigned)std::max<int64_t>(1, (n + bs - 1) / bs); }
-
 // what the kernels share: the segment description, the lists and the bitmap
 struct Sub {
     const double* sc; int64_t m;
@@ -54,21 +50,6 @@ struct Sub {
     bitrank::Rank* rank;          // [W+1] (word, scan) side by side: what every kernel behind the scan reads
     int32_t* err;
 };
-
-// last s in [0, S) with tab[s] <= r (S >= 1): the segment of row r; equal offsets (empty segments) are skipped
-__device__ inline int64_t seg_of(const int64_t* __restrict__ tab, int64_t S, int64_t r) {
-    int64_t lo = 0, hi = S;
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (tab[mid] <= r) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// the segment of row r given that of an earlier row of the same workgroup (rows of a workgroup mostly share one)
-__device__ inline int64_t seg_near(const int64_t* __restrict__ tab, int64_t S, int64_t r, int64_t s0) {
-    return r < tab[s0 + 1] ? s0 : seg_of(tab, S, r);
-}
 
 // id range of segment s, clipped to [0, N] (a malformed node_ptr is reported by k_sg_check; nothing may index outside the bitmap)
 __device__ inline void seg_range(const Sub& a, int64_t s, int64_t* lo, int64_t* hi) {
@@ -289,16 +270,6 @@ __global__ void k_sg_tail(Sub a, const int64_t* __restrict__ tbase, int64_t tile
     if (s == 0) { tot[TOT_KEPT] = tbase[tiles]; tot[TOT_IDS] = a.rank[a.W].scan; }
 }
 
-struct Carve {
-    char* base; size_t off;
-    template <class T> T* take(int64_t count) {
-        off = (off + 255) & ~(size_t)255;
-        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += sizeof(T) * (size_t)(count > 0 ? count : 0);
-        return p;
-    }
-};
-
 struct Bufs {
     uint8_t* flags; uint64_t* words; int32_t* pc; int64_t* scan; bitrank::Rank* rank; int32_t* cnt; int64_t* tbase; int32_t* err; int64_t* tot;
     void* tmp; size_t tmp_bytes;
@@ -345,53 +316,53 @@ size_t snapshot_subgraph_bytes(int64_t m, int64_t S, int64_t G, int64_t N) {
 
 int snapshot_subgraph_run(hipStream_t st, void* ws, size_t ws_bytes, const SnapshotSubArgs& g, SnapshotSubReport* rep) {
     *rep = SnapshotSubReport{};
-    const int64_t m = g.m, S = g.S, G = g.G, N = g.N;
+    const int64_t m = g.seg.m, S = g.seg.S, G = g.seg.G, N = g.seg.N;
     Bufs B;
     Carve C{static_cast<char*>(ws), 0};
     if (carve_sub(C, m, S, G, N, B) > ws_bytes) return RLAP_E_WORKSPACE;
     const int64_t layers = S / G;
-    Sub a{g.sc, m, g.ptr, S, g.node_ptr, G, N, g.nodes, g.nodes_ptr, g.nodes_len, (g.flags & RLAP_SUB_RELABEL) ? 1 : 0,
+    Sub a{g.seg.sc, m, g.seg.ptr, S, g.seg.node_ptr, G, N, g.nodes, g.nodes_ptr, g.nodes_len, (g.flags & RLAP_SUB_RELABEL) ? 1 : 0,
           (g.flags & RLAP_SUB_NO_SELF_LOOPS) ? 1 : 0, B.flags, B.words, B.W, B.scan, B.rank, B.err};
     // 1. tables checked, flags zeroed and marked
-    SG_HIPCHK(hipMemsetAsync(B.flags, 0, 64 * (size_t)(B.W + 1), st));
-    SG_HIPCHK(hipMemsetAsync(B.err, 0, sizeof(int32_t) * SERR_WORDS, st));
-    SG_HIPCHK(hipMemsetAsync(B.cnt, 0, sizeof(int32_t) * (size_t)(B.tiles + 1), st));
-    hipLaunchKernelGGL(k_sg_check, dim3(sg_blocks(std::max(S, G) + 1, 256)), dim3(256), 0, st, a);
+    RLAP_HIPCHK(hipMemsetAsync(B.flags, 0, 64 * (size_t)(B.W + 1), st));
+    RLAP_HIPCHK(hipMemsetAsync(B.err, 0, sizeof(int32_t) * SERR_WORDS, st));
+    RLAP_HIPCHK(hipMemsetAsync(B.cnt, 0, sizeof(int32_t) * (size_t)(B.tiles + 1), st));
+    hipLaunchKernelGGL(k_sg_check, dim3(grid_blocks(std::max(S, G) + 1, 256)), dim3(256), 0, st, a);
     if (!g.nodes) {
-        if (m > 0) hipLaunchKernelGGL(k_sg_mark_rows, dim3(sg_blocks(m, SG_THREADS)), dim3(SG_THREADS), 0, st, a);
+        if (m > 0) hipLaunchKernelGGL(k_sg_mark_rows, dim3(grid_blocks(m, SG_THREADS)), dim3(SG_THREADS), 0, st, a);
     } else if (g.nodes_ptr) {
-        if (g.nodes_len > 0 && S > 0) hipLaunchKernelGGL(k_sg_mark_lists, dim3(sg_blocks(g.nodes_len, SG_THREADS)), dim3(SG_THREADS), 0, st, a);
+        if (g.nodes_len > 0 && S > 0) hipLaunchKernelGGL(k_sg_mark_lists, dim3(grid_blocks(g.nodes_len, SG_THREADS)), dim3(SG_THREADS), 0, st, a);
     } else if (g.nodes_len > 0 && layers > 0) {
-        hipLaunchKernelGGL(k_sg_mark_shared, dim3(sg_blocks(layers * g.nodes_len, SG_THREADS)), dim3(SG_THREADS), 0, st, a, layers);
+        hipLaunchKernelGGL(k_sg_mark_shared, dim3(grid_blocks(layers * g.nodes_len, SG_THREADS)), dim3(SG_THREADS), 0, st, a, layers);
     }
-    SG_HIPCHK(hipGetLastError());
+    RLAP_HIPCHK(hipGetLastError());
     // 2. ranks: the bitmap and its popcounts, their scan, the ids and their offsets
-    hipLaunchKernelGGL(k_sg_pack, dim3(sg_blocks(B.W + 1, 256)), dim3(256), 0, st, B.flags, B.W, B.words, B.pc);
-    SG_HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_sg_pack, dim3(grid_blocks(B.W + 1, 256)), dim3(256), 0, st, B.flags, B.W, B.words, B.pc);
+    RLAP_HIPCHK(hipGetLastError());
     size_t tb = B.tmp_bytes;
-    SG_HIPCHK(rocprim::exclusive_scan(B.tmp, tb, B.pc, B.scan, (int64_t)0, (size_t)(B.W + 1), rocprim::plus<int64_t>(), st));
-    hipLaunchKernelGGL(k_sg_ids, dim3(sg_blocks(B.W + 1, 256)), dim3(256), 0, st, a, g.ids, g.ids_cap);
-    hipLaunchKernelGGL(k_sg_idsptr, dim3(sg_blocks(S + 1, 256)), dim3(256), 0, st, a, g.ids_ptr);
-    SG_HIPCHK(hipGetLastError());
+    RLAP_HIPCHK(rocprim::exclusive_scan(B.tmp, tb, B.pc, B.scan, (int64_t)0, (size_t)(B.W + 1), rocprim::plus<int64_t>(), st));
+    hipLaunchKernelGGL(k_sg_ids, dim3(grid_blocks(B.W + 1, 256)), dim3(256), 0, st, a, g.ids, g.ids_cap);
+    hipLaunchKernelGGL(k_sg_idsptr, dim3(grid_blocks(S + 1, 256)), dim3(256), 0, st, a, g.ids_ptr);
+    RLAP_HIPCHK(hipGetLastError());
     // 3. the filter: count per tile, scan, write
-    const int vec = (reinterpret_cast<uintptr_t>(g.sc) & 15) == 0 ? 1 : 0;
+    const int vec = (reinterpret_cast<uintptr_t>(g.seg.sc) & 15) == 0 ? 1 : 0;
     if (B.tiles > 0)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sg_filter<0>), dim3((unsigned)B.tiles), dim3(SG_THREADS), 0, st, a, vec, B.cnt, B.tbase, g.ids_ptr,
                            g.out, g.out_ptr);
-    SG_HIPCHK(hipGetLastError());
+    RLAP_HIPCHK(hipGetLastError());
     tb = B.tmp_bytes;
-    SG_HIPCHK(rocprim::exclusive_scan(B.tmp, tb, B.cnt, B.tbase, (int64_t)0, (size_t)(B.tiles + 1), rocprim::plus<int64_t>(), st));
+    RLAP_HIPCHK(rocprim::exclusive_scan(B.tmp, tb, B.cnt, B.tbase, (int64_t)0, (size_t)(B.tiles + 1), rocprim::plus<int64_t>(), st));
     if (B.tiles > 0)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sg_filter<1>), dim3((unsigned)B.tiles), dim3(SG_THREADS), 0, st, a, vec, B.cnt, B.tbase, g.ids_ptr,
                            g.out, g.out_ptr);
-    hipLaunchKernelGGL(k_sg_tail, dim3(sg_blocks(S + 1, 256)), dim3(256), 0, st, a, B.tbase, B.tiles, g.out_ptr, B.tot);
-    SG_HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_sg_tail, dim3(grid_blocks(S + 1, 256)), dim3(256), 0, st, a, B.tbase, B.tiles, g.out_ptr, B.tot);
+    RLAP_HIPCHK(hipGetLastError());
     // 4. the totals and the error words, read back once
     int64_t htot[TOT_WORDS];
     int32_t herr[SERR_WORDS];
-    SG_HIPCHK(hipMemcpyAsync(htot, B.tot, sizeof(htot), hipMemcpyDeviceToHost, st));
-    SG_HIPCHK(hipMemcpyAsync(herr, B.err, sizeof(herr), hipMemcpyDeviceToHost, st));
-    SG_HIPCHK(hipStreamSynchronize(st));
+    RLAP_HIPCHK(hipMemcpyAsync(htot, B.tot, sizeof(htot), hipMemcpyDeviceToHost, st));
+    RLAP_HIPCHK(hipMemcpyAsync(herr, B.err, sizeof(herr), hipMemcpyDeviceToHost, st));
+    RLAP_HIPCHK(hipStreamSynchronize(st));
     rep->host_syncs = 1;
     if (herr[SERR_ARG]) return RLAP_E_BAD_ARG;
     if (herr[SERR_RANGE]) return RLAP_E_INDEX_RANGE;

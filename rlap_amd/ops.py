@@ -556,13 +556,17 @@ def _ptr_table(x, what: str, first: int, last: Optional[int]) -> Tensor:
     return t.contiguous()
 
 
-def _snapshot_args(sc: Tensor, ptr, num_nodes: int, node_ptr, tol: float, max_iter: int) -> Tuple[Tensor, Optional[Tensor]]:
-    """Host-side checks of snapshot_stats, made before anything is launched: (ptr, node_ptr) as int64 CPU tensors."""
-    if not isinstance(sc, Tensor) or sc.dim() != 2 or sc.shape[1] != 3:
-        raise ValueError("sc: an (m, 3) tensor of rows [row, col, w]")
+def _num_nodes(num_nodes) -> int:
     if isinstance(num_nodes, bool) or not hasattr(num_nodes, "__index__") or num_nodes.__index__() < 0:
         raise ValueError(f"num_nodes: a non-negative integer, got {num_nodes!r}")
-    n = num_nodes.__index__()
+    return num_nodes.__index__()
+
+
+def _snapshot_tables(sc: Tensor, ptr, num_nodes: int, node_ptr) -> Tuple[Tensor, Optional[Tensor]]:
+    """Host-side checks every snapshot entry point makes before anything is launched: (ptr, node_ptr) as int64 CPU tensors."""
+    if not isinstance(sc, Tensor) or sc.dim() != 2 or sc.shape[1] != 3:
+        raise ValueError("sc: an (m, 3) tensor of rows [row, col, w]")
+    n = _num_nodes(num_nodes)
     p = _ptr_table(ptr, "ptr", 0, int(sc.shape[0]))
     S = p.numel() - 1
     np_ = None
@@ -571,11 +575,39 @@ def _snapshot_args(sc: Tensor, ptr, num_nodes: int, node_ptr, tol: float, max_it
         G = np_.numel() - 1
         if S % G != 0:
             raise ValueError(f"node_ptr has {G} graphs, which does not divide the {S} segments of ptr")
-    if isinstance(tol, bool) or not isinstance(tol, (int, float)) or not (0.0 < float(tol) < float("inf")):
-        raise ValueError(f"tol: a positive number, got {tol!r}")
-    if isinstance(max_iter, bool) or not hasattr(max_iter, "__index__") or not 1 <= max_iter.__index__() <= SNAPSHOT_MAX_ITER:
-        raise ValueError(f"max_iter: an integer in [1, {SNAPSHOT_MAX_ITER}], got {max_iter!r}")
     return p, np_
+
+
+def _graphs(np_: Optional[Tensor]) -> int:
+    return np_.numel() - 1 if np_ is not None else 1
+
+
+def _snapshot_call(export: str, info_cls, x: Tensor, p: Tensor, np_: Optional[Tensor], n: int, tail: tuple, extra_msg: Optional[str] = None,
+                   grouped: bool = True, accept: tuple = ()):
+    """The call every snapshot entry point makes: the C export `export` on the rows `x` (float64, on the device), the tables p /
+    np_ moved there, G and S derived from them, then the export's own arguments `tail` and an `info_cls` for its report.  Statuses
+    1, 2, 3 (with `extra_msg` appended to 3) and, where the layout is checked (`grouped`), RLAP_E_NOT_GROUPED raise ValueError, the
+    others RuntimeError; a status in `accept` is the caller's to handle.  Sets `last_stats` and returns the info struct."""
+    global last_stats
+    dev = x.device
+    lib, hobj = _handle_obj(dev)
+    fn = getattr(lib, export)
+    S, G, m = p.numel() - 1, _graphs(np_), int(x.shape[0])
+    d_ptr = p.to(dev)
+    d_np = np_.to(dev) if np_ is not None else None
+    info = info_cls()
+    st = _lib.Stats()
+    rc = _run(hobj, dev, m, None, G, False, lambda: fn(
+        hobj.ptr, x.data_ptr() if m else None, m, d_ptr.data_ptr(), S, d_np.data_ptr() if d_np is not None else None, G, n,
+        *tail, ctypes.byref(info)), st)
+    if rc in accept:
+        return info
+    if rc in (1, 2, 3) or (grouped and rc == _lib.E_NOT_GROUPED):
+        raise ValueError(f"rlap: {_lib.status_string(rc)}" + (extra_msg if rc == 3 and extra_msg else ""))
+    if rc != 0:
+        _raise(rc)
+    last_stats = info.as_dict()
+    return info
 
 
 def snapshot_stats(
@@ -609,35 +641,22 @@ def snapshot_stats(
     change later results of any other.  A column whose rows are not contiguous within its segment, a row id without a column, or
     an id outside its segment's range raise ValueError.  `last_stats` then holds what the call did (rlap_snapshot_info).
     """
-    p, np_ = _snapshot_args(sc, ptr, num_nodes, node_ptr, tol, max_iter)
-    global last_stats
+    p, np_ = _snapshot_tables(sc, ptr, num_nodes, node_ptr)
+    if isinstance(tol, bool) or not isinstance(tol, (int, float)) or not (0.0 < float(tol) < float("inf")):
+        raise ValueError(f"tol: a positive number, got {tol!r}")
+    if isinstance(max_iter, bool) or not hasattr(max_iter, "__index__") or not 1 <= max_iter.__index__() <= SNAPSHOT_MAX_ITER:
+        raise ValueError(f"max_iter: an integer in [1, {SNAPSHOT_MAX_ITER}], got {max_iter!r}")
     S = p.numel() - 1
-    n = int(num_nodes)
     dev = _device_for(sc)
-    lib, hobj = _handle_obj(dev)
-    h = hobj.ptr
     with torch.cuda.device(dev):
         x = sc.to(device=dev, dtype=torch.float64).contiguous()
-        d_ptr = p.to(dev)
-        d_np = np_.to(dev) if np_ is not None else None
-        G = np_.numel() - 1 if np_ is not None else 1
         nodes = torch.empty(S, dtype=torch.int64, device=dev)
         lam = torch.empty(S, dtype=torch.float64, device=dev)
         iters = torch.empty(S, dtype=torch.int32, device=dev)
         conv = torch.empty(S, dtype=torch.int32, device=dev)
-        info = _lib.SnapshotInfo()
-        st = _lib.Stats()
-        m = int(x.shape[0])
-        rc = _run(hobj, dev, m, None, G, False, lambda: lib.rlap_snapshot_stats(
-            h, x.data_ptr() if m else None, m, d_ptr.data_ptr(), S, d_np.data_ptr() if d_np is not None else None, G, n,
-            1 if weighted else 0, float(tol), int(max_iter), nodes.data_ptr(), lam.data_ptr(), iters.data_ptr(), conv.data_ptr(),
-            ctypes.byref(info)), st)
-        if rc == _lib.E_NOT_GROUPED:
-            raise ValueError(f"rlap: {_lib.status_string(rc)}")
-        if rc != 0:
-            _raise(rc)
-        last_stats = info.as_dict()
-        rows = d_ptr[1:] - d_ptr[:-1]
+        _snapshot_call("rlap_snapshot_stats", _lib.SnapshotInfo, x, p, np_, int(num_nodes),
+                       (1 if weighted else 0, float(tol), int(max_iter), nodes.data_ptr(), lam.data_ptr(), iters.data_ptr(), conv.data_ptr()))
+        rows = (p[1:] - p[:-1]).to(dev)
     return {"nodes": nodes, "rows": rows, "lambda_max": lam, "iters": iters, "converged": conv.bool()}
 
 
@@ -680,39 +699,23 @@ def _ppr_params(alpha, eps, tol) -> Tuple[float, float, float, int]:
     return a, e, t, K
 
 
-def _ppr_call(x: Tensor, p: Tensor, np_: Optional[Tensor], n: int, alpha: float, eps: float, tol: float, flags: int,
-              dev: torch.device) -> Tuple[Tensor, Tensor]:
+def _ppr_call(x: Tensor, p: Tensor, np_: Optional[Tensor], n: int, alpha: float, eps: float, tol: float, flags: int) -> Tuple[Tensor, Tensor]:
     """One rlap_snapshot_ppr call inside torch-owned memory: the first output capacity is max(16 m + 64, 2^22) rows, at most
     S min(n, m)^2; when the kept entries exceed it the call writes nothing and reports the count, and is made once more with
     exactly that many."""
     global last_stats
-    lib, hobj = _handle_obj(dev)
-    h = hobj.ptr
-    S = p.numel() - 1
-    m = int(x.shape[0])
-    d_ptr = p.to(dev)
-    d_np = np_.to(dev) if np_ is not None else None
-    G = np_.numel() - 1 if np_ is not None else 1
+    S, m, dev = p.numel() - 1, int(x.shape[0]), x.device
     cap = first_cap = min(S * min(n, m) ** 2, max(PPR_FIRST_CAP_PER_ROW * m + 64, PPR_FIRST_CAP_MIN))
-    retries = 0
-    while True:
+    for retries in (0, 1):
         out = torch.empty((cap, 3), dtype=torch.float64, device=dev)
         pptr = torch.empty(S + 1, dtype=torch.int64, device=dev)
-        info = _lib.PprInfo()
-        st = _lib.Stats()
-        rc = _run(hobj, dev, m, None, G, False, lambda: lib.rlap_snapshot_ppr(
-            h, x.data_ptr() if m else None, m, d_ptr.data_ptr(), S, d_np.data_ptr() if d_np is not None else None, G, n,
-            alpha, eps, tol, flags, out.data_ptr() if cap else None, cap, pptr.data_ptr(), ctypes.byref(info)), st)
-        if rc == _lib.E_OUT_CAPACITY and retries == 0:
-            cap = int(info.rows_needed)
-            retries += 1
-            continue
-        break
-    if rc in (_lib.E_NOT_GROUPED, 1, 2, 3):
-        raise ValueError(f"rlap: {_lib.status_string(rc)}" + (" (or a weight is <= 0)" if rc == 3 else ""))
-    if rc != 0:
-        _raise(rc)
-    P = int(info.rows_needed)
+        info = _snapshot_call("rlap_snapshot_ppr", _lib.PprInfo, x, p, np_, n,
+                              (alpha, eps, tol, flags, out.data_ptr() if cap else None, cap, pptr.data_ptr()),
+                              extra_msg=" (or a weight is <= 0)", accept=(_lib.E_OUT_CAPACITY,) if retries == 0 else ())
+        P = int(info.rows_needed)
+        if P <= cap:   # (more than the capacity: RLAP_E_OUT_CAPACITY, accepted on the first attempt only)
+            break
+        cap = P
     last_stats = dict(info.as_dict(), output_retries=retries, first_cap=first_cap)
     return _trim(out, P), pptr
 
@@ -748,7 +751,7 @@ def snapshot_ppr(
     what the call did (rlap_ppr_info: steps, small / large tiles, groups, launches, rows_needed, arena_bytes, host_syncs) and
     `output_retries` (1 when the first capacity guess was short).
     """
-    p, np_ = _snapshot_args(sc, ptr, num_nodes, node_ptr, 1.0, 1)
+    p, np_ = _snapshot_tables(sc, ptr, num_nodes, node_ptr)
     alpha, eps, tol, _ = _ppr_params(alpha, eps, tol)
     if weighted and not sc.is_cuda and sc.shape[0] and not bool((sc[:, 2] > 0).all() and torch.isfinite(sc[:, 2]).all()):
         raise ValueError("sc: every weight must be > 0 (the spectral bound of the iteration needs A >= 0)")
@@ -757,7 +760,7 @@ def snapshot_ppr(
              | (_lib.PPR_NORMALIZE if normalize_out else 0))
     with torch.cuda.device(dev):
         x = sc.to(device=dev, dtype=torch.float64).contiguous()
-        return _ppr_call(x, p, np_, int(num_nodes), alpha, eps, tol, flags, dev)
+        return _ppr_call(x, p, np_, int(num_nodes), alpha, eps, tol, flags)
 
 
 def ppr_diffusion(
@@ -779,9 +782,7 @@ def ppr_diffusion(
     normalisation.  Returns (edge_index (2, P) int64, edge_weights (P,) float64) in row-major order, on the input's device.
     """
     alpha, eps, tol, _ = _ppr_params(alpha, eps, tol)
-    if isinstance(num_nodes, bool) or not hasattr(num_nodes, "__index__") or num_nodes.__index__() < 0:
-        raise ValueError(f"num_nodes: a non-negative integer, got {num_nodes!r}")
-    n = num_nodes.__index__()
+    n = _num_nodes(num_nodes)
     if not isinstance(edge_index, Tensor) or edge_index.dim() != 2 or edge_index.shape[0] != 2:
         raise ValueError("edge_index: a (2, E) tensor")
     E = int(edge_index.shape[1])
@@ -825,7 +826,7 @@ def ppr_diffusion(
         flags = (_lib.PPR_WEIGHTED | _lib.PPR_ZERO_ROWS | (_lib.PPR_SELF_LOOP if add_self_loop else 0)
                  | (_lib.PPR_NORMALIZE if normalize_out else 0))
         p = torch.tensor([0, sc.shape[0]], dtype=torch.int64)
-        out, _ = _ppr_call(sc, p, None, n, alpha, eps, tol, flags, dev)
+        out, _ = _ppr_call(sc, p, None, n, alpha, eps, tol, flags)
         return out[:, :2].long().t().contiguous(), out[:, 2].contiguous()
 
 
@@ -839,13 +840,13 @@ def _subgraph_args(sc: Tensor, ptr, num_nodes: int, nodes, nodes_ptr, node_ptr):
     if single:
         # S = 0: no segment at all (ptr == [0], no rows); sc, num_nodes and node_ptr keep their rules
         rows = int(sc.shape[0]) if isinstance(sc, Tensor) and sc.dim() == 2 else 0
-        _snapshot_args(sc, [0, rows], num_nodes, None, 1.0, 1)
+        _snapshot_tables(sc, [0, rows], num_nodes, None)
         p = _int_tensor(ptr, "ptr").reshape(-1).contiguous()
         if p.numel() != 1 or int(p[0]) != 0 or rows != 0:
             raise ValueError("ptr: a single offset describes no segment and needs ptr == [0] and no rows")
         np_ = _ptr_table(node_ptr, "node_ptr", 0, num_nodes.__index__()) if node_ptr is not None else None
     else:
-        p, np_ = _snapshot_args(sc, ptr, num_nodes, node_ptr, 1.0, 1)
+        p, np_ = _snapshot_tables(sc, ptr, num_nodes, node_ptr)
     S = p.numel() - 1
     if nodes is None:
         if nodes_ptr is not None:
@@ -898,19 +899,12 @@ def snapshot_subgraph(
     call did (rlap_subgraph_info: rows_kept, ids_written, arena_bytes, host_syncs).
     """
     p, np_, nd, q = _subgraph_args(sc, ptr, num_nodes, nodes, nodes_ptr, node_ptr)
-    global last_stats
-    S = p.numel() - 1
-    n = int(num_nodes)
+    S, G, n = p.numel() - 1, _graphs(np_), int(num_nodes)
     dev = _device_for(sc)
-    lib, hobj = _handle_obj(dev)
-    h = hobj.ptr
     flags = (_lib.SUB_RELABEL if relabel else 0) | (_lib.SUB_NO_SELF_LOOPS if remove_self_loops else 0)
     with torch.cuda.device(dev):
         x = sc.to(device=dev, dtype=torch.float64).contiguous()
         m = int(x.shape[0])
-        d_ptr = p.to(dev)
-        d_np = np_.to(dev) if np_ is not None else None
-        G = np_.numel() - 1 if np_ is not None else 1
         d_nd = nd.to(device=dev, dtype=torch.int64).contiguous() if nd is not None else None
         d_q = q.to(dev) if q is not None else None
         L = len(d_nd) if d_nd is not None else 0
@@ -919,17 +913,10 @@ def snapshot_subgraph(
         optr = torch.empty(S + 1, dtype=torch.int64, device=dev)
         ids = torch.empty(cap, dtype=torch.int64, device=dev)
         iptr = torch.empty(S + 1, dtype=torch.int64, device=dev)
-        info = _lib.SubgraphInfo()
-        st = _lib.Stats()
-        rc = _run(hobj, dev, m, None, G, False, lambda: lib.rlap_snapshot_subgraph(
-            h, x.data_ptr() if m else None, m, d_ptr.data_ptr(), S, d_np.data_ptr() if d_np is not None else None, G, n,
+        info = _snapshot_call("rlap_snapshot_subgraph", _lib.SubgraphInfo, x, p, np_, n, (
             (d_nd.data_ptr() or iptr.data_ptr()) if d_nd is not None else None,   # (an empty list is still a list: not NULL)
             d_q.data_ptr() if d_q is not None else None, L,
-            flags, out.data_ptr() if m else None, optr.data_ptr(), ids.data_ptr() if cap else None, cap, iptr.data_ptr(),
-            ctypes.byref(info)), st)
-        if rc != 0:
-            _raise(rc)
-        last_stats = info.as_dict()
+            flags, out.data_ptr() if m else None, optr.data_ptr(), ids.data_ptr() if cap else None, cap, iptr.data_ptr()), grouped=False)
         return _trim(out, int(info.rows_kept)), optr, _trim(ids, int(info.ids_written)), iptr
 
 
@@ -968,39 +955,23 @@ def snapshot_gcn_norm(
     error, or (weighted and normalize) a weight that is not finite or <= 0 raise ValueError.  `last_stats` then holds what the call did
     (rlap_gcn_info: entries, loops_removed, arena_bytes, host_syncs).
     """
-    p, np_ = _snapshot_args(sc, ptr, num_nodes, node_ptr, 1.0, 1)
+    p, np_ = _snapshot_tables(sc, ptr, num_nodes, node_ptr)
     if dtype not in (torch.float32, torch.float64):
         raise ValueError(f"dtype: torch.float32 or torch.float64, got {dtype!r}")
     fill = _real(fill_value, "fill_value", 0.0, float("inf"))
-    global last_stats
-    S = p.numel() - 1
-    n = int(num_nodes)
+    S, G, n = p.numel() - 1, _graphs(np_), int(num_nodes)
     dev = _device_for(sc)
-    lib, hobj = _handle_obj(dev)
-    h = hobj.ptr
     flags = ((_lib.GCN_WEIGHTED if weighted else 0) | (_lib.GCN_SELF_LOOPS if add_self_loops else 0)
              | (_lib.GCN_NORMALIZE if normalize else 0) | (_lib.GCN_F32 if dtype == torch.float32 else 0))
     with torch.cuda.device(dev):
         x = sc.to(device=dev, dtype=torch.float64).contiguous()
-        m = int(x.shape[0])
-        d_ptr = p.to(dev)
-        d_np = np_.to(dev) if np_ is not None else None
-        G = np_.numel() - 1 if np_ is not None else 1
-        cap = m + ((S // G) * n if add_self_loops else 0)
+        cap = int(x.shape[0]) + ((S // G) * n if add_self_loops else 0)
         ei = torch.empty((2, cap), dtype=torch.int64, device=dev)
         val = torch.empty(cap, dtype=dtype, device=dev)
         eptr = torch.empty(S + 1, dtype=torch.int64, device=dev)
-        info = _lib.GcnInfo()
-        st = _lib.Stats()
-        rc = _run(hobj, dev, m, None, G, False, lambda: lib.rlap_snapshot_gcn_norm(
-            h, x.data_ptr() if m else None, m, d_ptr.data_ptr(), S, d_np.data_ptr() if d_np is not None else None, G, n, flags, fill,
-            ei[0].data_ptr() if cap else None, ei[1].data_ptr() if cap else None, val.data_ptr() if cap else None, cap,
-            eptr.data_ptr(), ctypes.byref(info)), st)
-        if rc == _lib.E_NOT_GROUPED:
-            raise ValueError(f"rlap: {_lib.status_string(rc)}")
-        if rc != 0:
-            _raise(rc)
-        last_stats = info.as_dict()
+        info = _snapshot_call("rlap_snapshot_gcn_norm", _lib.GcnInfo, x, p, np_, n, (
+            flags, fill, ei[0].data_ptr() if cap else None, ei[1].data_ptr() if cap else None, val.data_ptr() if cap else None, cap,
+            eptr.data_ptr()))
         M = int(info.entries)
         if M != cap:   # (only an input with loop rows: the two rows of edge_index move together)
             ei, val = ei[:, :M].contiguous(), val[:M].clone()
@@ -1009,10 +980,9 @@ def snapshot_gcn_norm(
 
 def _propagate_args(sc, ptr, num_nodes, x, node_ptr, fill_value):
     """Host-side checks of snapshot_propagate, made before the device is touched: (ptr, node_ptr, fill, layers, per_layer)."""
-    p, np_ = _snapshot_args(sc, ptr, num_nodes, node_ptr, 1.0, 1)
+    p, np_ = _snapshot_tables(sc, ptr, num_nodes, node_ptr)
     fill = _real(fill_value, "fill_value", 0.0, float("inf"))
-    S = p.numel() - 1
-    G = np_.numel() - 1 if np_ is not None else 1
+    S, G = p.numel() - 1, _graphs(np_)
     if S < 1 or S % G != 0:
         raise ValueError(f"ptr: {S} segments; at least one, and a multiple of the {G} graphs")
     L, n = S // G, int(num_nodes)
@@ -1031,33 +1001,17 @@ def _propagate_args(sc, ptr, num_nodes, x, node_ptr, fill_value):
 
 def _propagate(sc, p, np_, n, x, L, per_layer, weighted, add_self_loops, fill, normalize, transpose):
     """One rlap_snapshot_propagate call; x is already checked."""
-    global last_stats
-    S = p.numel() - 1
     dev = _device_for(sc)
-    lib, hobj = _handle_obj(dev)
-    h = hobj.ptr
     flags = ((_lib.GCN_WEIGHTED if weighted else 0) | (_lib.GCN_SELF_LOOPS if add_self_loops else 0)
              | (_lib.GCN_NORMALIZE if normalize else 0) | (_lib.SPMM_TRANSPOSE if transpose else 0)
              | (_lib.SPMM_X_F32 if x.dtype == torch.float32 else 0) | (_lib.SPMM_X_PER_LAYER if per_layer else 0))
     with torch.cuda.device(dev):
         rows = sc.to(device=dev, dtype=torch.float64).contiguous()
-        m = int(rows.shape[0])
         d_x = x.detach().to(device=dev).contiguous()
         F = int(d_x.shape[-1])
-        d_ptr = p.to(dev)
-        d_np = np_.to(dev) if np_ is not None else None
-        G = np_.numel() - 1 if np_ is not None else 1
         y = torch.empty((L, n, F), dtype=d_x.dtype, device=dev)
-        info = _lib.SpmmInfo()
-        st = _lib.Stats()
-        rc = _run(hobj, dev, m, None, G, False, lambda: lib.rlap_snapshot_propagate(
-            h, rows.data_ptr() if m else None, m, d_ptr.data_ptr(), S, d_np.data_ptr() if d_np is not None else None, G, n, flags, fill,
-            d_x.data_ptr() if d_x.numel() else None, F, y.data_ptr() if y.numel() else None, ctypes.byref(info)), st)
-        if rc == _lib.E_NOT_GROUPED:
-            raise ValueError(f"rlap: {_lib.status_string(rc)}")
-        if rc != 0:
-            _raise(rc)
-        last_stats = info.as_dict()
+        _snapshot_call("rlap_snapshot_propagate", _lib.SpmmInfo, rows, p, np_, n,
+                       (flags, fill, d_x.data_ptr() if d_x.numel() else None, F, y.data_ptr() if y.numel() else None))
         return y
 
 

@@ -3,6 +3,8 @@ import ctypes
 import os
 import re
 
+import pytest
+
 from rlap_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -124,27 +126,35 @@ def test_size_query_rejects_what_int32_slot_ids_cannot_hold():
     assert lib.rlap_status_string(9).decode() == "problem exceeds int32 slot ids"
 
 
-def test_stats_layout_matches_the_header(tmp_path):
-    """`_lib.Stats` (ctypes) and `rlap_stats` of include/rlap_hip.h describe the same bytes: a C99 program compiled against the
+LAYOUTS = [("rlap_stats", "Stats"), ("rlap_snapshot_info", "SnapshotInfo"), ("rlap_ppr_info", "PprInfo"),
+           ("rlap_subgraph_info", "SubgraphInfo"), ("rlap_gcn_info", "GcnInfo"), ("rlap_spmm_info", "SpmmInfo")]
+
+
+@pytest.mark.parametrize("c_name,py_name", LAYOUTS)
+def test_layout_matches_the_header(tmp_path, c_name, py_name):
+    """A ctypes structure of `_lib` and its struct in include/rlap_hip.h describe the same bytes: a C99 program compiled against the
     header prints sizeof and every offsetof, compared with what ctypes computes for the Python structure."""
     import shutil
     import subprocess
     gcc = shutil.which("gcc")
     assert gcc, "gcc is needed to check the C layout"
-    fields = [f for f, _ in _lib.Stats._fields_]
+    cls = getattr(_lib, py_name)
+    fields = [f for f, _ in cls._fields_]
     hdr = open(os.path.join(ROOT, "include", "rlap_hip.h")).read()
-    body = hdr[hdr.index("typedef struct {", hdr.index("RLAP_E_WORKSPACE")):hdr.index("} rlap_stats;")]
-    declared = re.findall(r"\b(?:int32_t|int64_t|float|double)\s+([a-z_0-9]+)\s*;", body)
-    assert declared == fields, "the header's fields and _lib.Stats differ in name or order"
+    end = hdr.index("} %s;" % c_name)
+    body = hdr[hdr.rindex("typedef struct {", 0, end):end]
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    declared = [name for decl in re.findall(r"\b(?:int32_t|int64_t|float|double)\s+([a-z_0-9, ]+);", body) for name in decl.split(", ")]
+    assert declared == fields, f"the header's fields and _lib.{py_name} differ in name or order"
     src = tmp_path / "layout.c"
     lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "rlap_hip.h"', "int main(void) {",
-             '    printf("sizeof %zu\\n", sizeof(rlap_stats));']
-    lines += [f'    printf("{f} %zu\\n", offsetof(rlap_stats, {f}));' for f in fields]
+             f'    printf("sizeof %zu\\n", sizeof({c_name}));']
+    lines += [f'    printf("{f} %zu\\n", offsetof({c_name}, {f}));' for f in fields]
     lines += ["    return 0;", "}"]
     src.write_text("\n".join(lines) + "\n")
     exe = tmp_path / "layout"
     subprocess.check_call([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
     got = dict(line.split() for line in subprocess.check_output([str(exe)], text=True).splitlines())
-    assert int(got.pop("sizeof")) == ctypes.sizeof(_lib.Stats)
-    assert {f: int(v) for f, v in got.items()} == {f: getattr(_lib.Stats, f).offset for f in fields}
-    assert ctypes.sizeof(_lib.Stats) % 8 == 0
+    assert int(got.pop("sizeof")) == ctypes.sizeof(cls)
+    assert {f: int(v) for f, v in got.items()} == {f: getattr(cls, f).offset for f in fields}
+    assert ctypes.sizeof(cls) % 8 == 0

@@ -1,12 +1,12 @@
 """The Python -> C mapping of every elimination entry point, without a GPU: the device is the CPU and the library a stub that
 records each call with its arguments (host tables read through their addresses) and writes a result of its own."""
-import contextlib
 import ctypes
 
 import pytest
 import torch
 
-from rlap_amd import _lib, ops
+from rlap_amd import ops
+from util import StubLib, i64_at as i64, stub_ops
 
 # positional arguments of the six exports (include/rlap_hip.h)
 SIGS = {
@@ -20,41 +20,8 @@ SIGS = {
 NN = 37   # num_nodes the stub "finds" for rlap_approx_chol_from_edges with n < 0
 
 
-def i64(addr, count):
-    return list(ctypes.cast(addr, ctypes.POINTER(ctypes.c_int64))[:count])
-
-
-class StubLib:
-    def __init__(self, status=0):
-        self.calls = []
-        self.status = status
-
-    def rlap_create(self, out):
-        out._obj.value = 0x1000
-        return 0
-
-    def rlap_destroy(self, h):
-        return 0
-
-    def rlap_set_rng_mode(self, h, mode):
-        self.calls.append(("rlap_set_rng_mode", {"mode": mode}))
-        return 0
-
-    def rlap_workspace_query(self, h, E, n_total, G, symmetrize, ws_bytes, rng_entries):
-        self.calls.append(("rlap_workspace_query", {"args": (E, n_total, G, symmetrize)}))
-        ws_bytes._obj.value = 1 << 12
-        rng_entries._obj.value = 1 << 10
-        return 0
-
-    def rlap_set_workspace(self, h, d_ws, ws_bytes, d_rng, rng_entries):
-        return 0
-
-    def __getattr__(self, name):
-        if name not in SIGS:
-            raise AttributeError(name)
-        return lambda *args: self._export(name, dict(zip(SIGS[name].split(), args)))
-
-    def _export(self, name, a):
+class ElimStub(StubLib):
+    def export(self, name, a):
         rec = {k: a[k] for k in ("E", "o_v", "o_n", "seed", "cap")}
         E = a["E"]
         rec["rows"] = (i64(a["row"], E), i64(a["col"], E))
@@ -98,14 +65,7 @@ class StubLib:
 
 @pytest.fixture
 def lib(monkeypatch):
-    stub = StubLib()
-    monkeypatch.setattr(ops, "_device_for", lambda t: torch.device("cpu"))
-    monkeypatch.setattr(torch.cuda, "device", contextlib.nullcontext)
-    hobj = ops._Handle(stub, 0)
-    monkeypatch.setattr(ops, "_handle_obj", lambda dev: (stub, hobj))
-    monkeypatch.setattr(ops, "last_stats", None)
-    monkeypatch.setattr(_lib, "status_string", lambda rc: f"status {rc}")   # (the message of a failed call, without the library)
-    return stub
+    return stub_ops(monkeypatch, ElimStub(SIGS))
 
 
 def path(n):
@@ -114,7 +74,7 @@ def path(n):
 
 
 def exports(stub):
-    return [c for c in stub.calls if c[0] in SIGS]
+    return stub.exports()
 
 
 def queries(stub):

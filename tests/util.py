@@ -1,4 +1,8 @@
-"""Shared test helpers: seeded synthetic graphs (numpy) and canonical forms."""
+"""Shared test helpers: seeded synthetic graphs (numpy), canonical forms, and a stub of the C library for the tests of the Python ->
+C mapping."""
+import contextlib
+import ctypes
+
 import numpy as np
 
 
@@ -163,3 +167,75 @@ def default_kernel(o_v, G, n_total):
 def kernel_for(kernel, n, t):
     """What elim_kernel reports for a single graph of n vertices with num_remove t run on `kernel`: nothing runs when no vertex goes."""
     return kernel if min(t, n - 1) > 0 else 0
+
+
+def i64_at(addr, count):
+    """`count` int64 values read through an address a stubbed export was given."""
+    return list(ctypes.cast(addr, ctypes.POINTER(ctypes.c_int64))[:count])
+
+
+def f64_at(addr, count):
+    return list(ctypes.cast(addr, ctypes.POINTER(ctypes.c_double))[:count])
+
+
+class StubLib:
+    """The C library without a GPU: `sigs` maps every export under test to the names of its positional arguments
+    (include/rlap_hip.h); a call of one goes to export(name, {argument name: value}), which a test's subclass provides -- it records
+    what it was given in `calls` and writes a result of its own.  The handle and arena calls around it answer as the library does."""
+
+    def __init__(self, sigs, status=0):
+        self.sigs = sigs
+        self.calls = []
+        self.status = status
+        self.ws_needed = 1 << 12
+
+    def rlap_create(self, out):
+        out._obj.value = 0x1000
+        return 0
+
+    def rlap_destroy(self, h):
+        return 0
+
+    def rlap_set_rng_mode(self, h, mode):
+        self.calls.append(("rlap_set_rng_mode", {"mode": mode}))
+        return 0
+
+    def rlap_workspace_query(self, h, E, n_total, G, symmetrize, ws_bytes, rng_entries):
+        self.calls.append(("rlap_workspace_query", {"args": (E, n_total, G, symmetrize)}))
+        ws_bytes._obj.value = 1 << 12
+        rng_entries._obj.value = 1 << 10
+        return 0
+
+    def rlap_set_workspace(self, h, d_ws, ws_bytes, d_rng, rng_entries):
+        self.calls.append(("rlap_set_workspace", {"ws_bytes": ws_bytes, "rng_entries": rng_entries}))
+        return 0
+
+    def rlap_workspace_needed(self, h, ws_bytes, rng_entries):
+        self.calls.append(("rlap_workspace_needed", {}))
+        ws_bytes._obj.value = self.ws_needed
+        rng_entries._obj.value = 1 << 10
+        return 0
+
+    def __getattr__(self, name):
+        if name == "sigs" or name not in self.sigs:
+            raise AttributeError(name)
+        return lambda *args: self.export(name, dict(zip(self.sigs[name].split(), args)))
+
+    def export(self, name, a):
+        raise NotImplementedError
+
+    def exports(self):
+        return [c for c in self.calls if c[0] in self.sigs]
+
+
+def stub_ops(monkeypatch, stub):
+    """rlap_amd.ops on `stub`: the device is the CPU, the handle the stub's, status strings are "status <rc>"."""
+    import torch
+    from rlap_amd import _lib, ops
+    monkeypatch.setattr(ops, "_device_for", lambda t: torch.device("cpu"))
+    monkeypatch.setattr(torch.cuda, "device", contextlib.nullcontext)
+    hobj = ops._Handle(stub, 0)
+    monkeypatch.setattr(ops, "_handle_obj", lambda dev: (stub, hobj))
+    monkeypatch.setattr(ops, "last_stats", None)
+    monkeypatch.setattr(_lib, "status_string", lambda rc: f"status {rc}")   # (the message of a failed call, without the library)
+    return stub
