@@ -406,6 +406,64 @@ int rlap_snapshot_propagate(rlap_handle h, const double* d_sc, int64_t m, const 
                             int64_t G, int64_t num_nodes, int flags, double fill_value, const void* d_x, int64_t F, void* d_y,
                             rlap_spmm_info* h_info);
 
+/* Propagation plans: the x-independent half of rlap_snapshot_propagate, built once per elimination result and used by any number
+ * of planned calls.  A plan is a device buffer that the CALLER owns (the library allocates nothing) plus the host
+ * descriptor below; it holds, per direction, every list of the product as packed 16-byte records {double coefficient, int32 source
+ * id, int32 0} in list order, the int64 record offset of every (layer, id), a directory of the chunks of the lists longer than 256
+ * entries, and one loop coefficient per (layer, id).  The buffer is valid while it is unchanged, and independent of d_sc once the
+ * build has returned.  A planned call returns the bits of rlap_snapshot_propagate on the same input with the same flags, for every
+ * F, both types, both forms of d_x and both directions: the coefficients come from the same functions on the same inputs, the lists
+ * hold the entries that stay in the order of rlap_amd/csrc/rlap_spmm.h, and the sum is that header's rule.
+ *
+ * The size query is host arithmetic (no GPU needed): an upper bound on the plan buffer for the directions `flags` asks for.
+ * A negative count, S < 1, G that does not divide S or a flag that is not the build's: RLAP_E_BAD_ARG; m, S, num_nodes or
+ * (S / G) num_nodes beyond the limits of rlap_snapshot_propagate: RLAP_E_TOO_LARGE.
+ *
+ * The build takes d_sc .. num_nodes, RLAP_GCN_WEIGHTED / SELF_LOOPS / NORMALIZE and fill_value exactly as rlap_snapshot_gcn_norm,
+ * checks and error codes included, and
+ *   RLAP_PLAN_FORWARD, RLAP_PLAN_TRANSPOSED : the directions to build; with neither, both
+ *   d_plan, plan_bytes : the buffer (256-byte aligned) and its size, at least what the size query says (else RLAP_E_BAD_ARG)
+ *   h_desc             : what a planned call needs without looking at the device; zeroed on any error (d_plan is then unspecified)
+ *   h_info             : (nullable) what the build did
+ * Scratch from the arena (RLAP_E_WORKSPACE when a caller-provided one is too small); one host synchronisation.
+ *
+ * The planned call takes RLAP_SPMM_TRANSPOSE, RLAP_SPMM_X_F32 and RLAP_SPMM_X_PER_LAYER; d_x, F, d_y and the limits are those of
+ * rlap_snapshot_propagate.  It does not read d_sc.  A direction the plan does not hold, or a descriptor that is not a successful
+ * build's: RLAP_E_BAD_ARG before anything is launched.  No host synchronisation (every data-dependent error was found by the
+ * build).  Arena: the chunk sums alone, by the budget rule and test hook of rlap_snapshot_propagate.  A buffer altered after the
+ * build is the caller's error; the kernels clamp every id and offset they read from it, so it gives wrong numbers, never an access
+ * out of range. */
+enum { RLAP_PLAN_FORWARD = 256, RLAP_PLAN_TRANSPOSED = 512 };
+typedef struct {
+    int64_t m, segments, graphs, num_nodes;               /* the build's m, S, G (1 without node_ptr), num_nodes  */
+    double fill_value;
+    int64_t entries_forward, entries_transposed;          /* records of a direction (-1: not built)               */
+    int64_t chunks_forward, chunks_transposed;            /* chunks of its lists longer than one chunk            */
+    int64_t loop_offset;                                  /* byte offsets of the parts within the buffer          */
+    int64_t off_forward, dir_forward, rec_forward;
+    int64_t off_transposed, dir_transposed, rec_transposed;
+    int64_t plan_bytes;                                   /* bytes of the buffer in use (the rest may be trimmed) */
+    int32_t flags;                                        /* the build's flags, both direction bits resolved      */
+    int32_t magic;                                        /* marks a successful build                             */
+} rlap_plan_desc;
+typedef struct {
+    int64_t entries;                  /* entries of the list the products run over (rows that stay + loops)  */
+    int64_t blocks;                   /* column blocks of the call: the ids with rows                         */
+    int64_t chunked_lists_forward;    /* lists longer than one chunk (-1: direction not built)                */
+    int64_t chunked_lists_transposed;
+    int64_t loops_removed;            /* loop rows of the input that left the lists                           */
+    int64_t arena_bytes;              /* scratch bytes of the call                                            */
+    int32_t host_syncs;               /* host synchronisations of the call                                    */
+    int32_t pad;
+} rlap_plan_info;
+
+int rlap_snapshot_plan_bytes(int64_t m, int64_t S, int64_t G, int64_t num_nodes, int flags, size_t* bytes);
+int rlap_snapshot_plan_build(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
+                             int64_t G, int64_t num_nodes, int flags, double fill_value, void* d_plan, size_t plan_bytes,
+                             rlap_plan_desc* h_desc, rlap_plan_info* h_info);
+int rlap_snapshot_plan_propagate(rlap_handle h, const void* d_plan, const rlap_plan_desc* h_desc, int flags, const void* d_x, int64_t F,
+                                 void* d_y, rlap_spmm_info* h_info);
+
 /* The op with the step BEFORE the path fused in (scripts/node_shared.py:326-327,
  * scripts/augmentor_benchmarks.py:77-78):
  *   symmetrize != 0 : the input holds every undirected edge in one or both directions; (b,a) is

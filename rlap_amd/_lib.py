@@ -21,6 +21,7 @@ EXPORTS = [
     "rlap_set_rng_mode", "rlap_approx_chol_views", "rlap_approx_chol_depths", "rlap_debug_set_flow_limits",
     "rlap_approx_chol_views_depths", "rlap_snapshot_stats", "rlap_snapshot_ppr", "rlap_snapshot_subgraph",
     "rlap_snapshot_gcn_norm", "rlap_snapshot_propagate",
+    "rlap_snapshot_plan_bytes", "rlap_snapshot_plan_build", "rlap_snapshot_plan_propagate",
 ]
 
 E_WORKSPACE = 11   # RLAP_E_WORKSPACE
@@ -34,6 +35,9 @@ SUB_RELABEL, SUB_NO_SELF_LOOPS = 1, 2
 GCN_WEIGHTED, GCN_SELF_LOOPS, GCN_NORMALIZE, GCN_F32 = 1, 2, 4, 8
 # rlap_snapshot_propagate flags (beside the first three above)
 SPMM_TRANSPOSE, SPMM_X_F32, SPMM_X_PER_LAYER = 16, 32, 64
+# rlap_snapshot_plan_build flags (beside the first three of rlap_snapshot_gcn_norm): the directions to build
+PLAN_FORWARD, PLAN_TRANSPOSED = 256, 512
+PLAN_MAGIC = 0x504C414E   # rlap_plan_desc.magic of a successful build
 
 # rlap_stats.elim_kernel
 KERNEL_NONE, KERNEL_ROUND, KERNEL_FLOW = 0, 1, 2
@@ -104,6 +108,29 @@ class SpmmInfo(_Report):
     ]
 
 
+class PlanDesc(_Report):
+    """rlap_plan_desc (include/rlap_hip.h)."""
+    _fields_ = [
+        ("m", ctypes.c_int64), ("segments", ctypes.c_int64), ("graphs", ctypes.c_int64), ("num_nodes", ctypes.c_int64),
+        ("fill_value", ctypes.c_double),
+        ("entries_forward", ctypes.c_int64), ("entries_transposed", ctypes.c_int64),
+        ("chunks_forward", ctypes.c_int64), ("chunks_transposed", ctypes.c_int64),
+        ("loop_offset", ctypes.c_int64),
+        ("off_forward", ctypes.c_int64), ("dir_forward", ctypes.c_int64), ("rec_forward", ctypes.c_int64),
+        ("off_transposed", ctypes.c_int64), ("dir_transposed", ctypes.c_int64), ("rec_transposed", ctypes.c_int64),
+        ("plan_bytes", ctypes.c_int64), ("flags", ctypes.c_int32), ("magic", ctypes.c_int32),
+    ]
+
+
+class PlanInfo(_Report):
+    """rlap_plan_info (include/rlap_hip.h)."""
+    _fields_ = [
+        ("entries", ctypes.c_int64), ("blocks", ctypes.c_int64), ("chunked_lists_forward", ctypes.c_int64),
+        ("chunked_lists_transposed", ctypes.c_int64), ("loops_removed", ctypes.c_int64), ("arena_bytes", ctypes.c_int64),
+        ("host_syncs", ctypes.c_int32), ("pad", ctypes.c_int32),
+    ]
+
+
 def load():
     """dlopen the library and declare prototypes. Raises if it is not built."""
     global _lib
@@ -155,6 +182,13 @@ def load():
     lib.rlap_snapshot_propagate.restype = ci
     lib.rlap_snapshot_propagate.argtypes = [vp, vp, i64, vp, i64, vp, i64, i64, ci, ctypes.c_double, vp, i64, vp,
                                             ctypes.POINTER(SpmmInfo)]
+    lib.rlap_snapshot_plan_bytes.restype = ci
+    lib.rlap_snapshot_plan_bytes.argtypes = [i64, i64, i64, i64, ci, ctypes.POINTER(ctypes.c_size_t)]
+    lib.rlap_snapshot_plan_build.restype = ci
+    lib.rlap_snapshot_plan_build.argtypes = [vp, vp, i64, vp, i64, vp, i64, i64, ci, ctypes.c_double, vp, ctypes.c_size_t,
+                                             ctypes.POINTER(PlanDesc), ctypes.POINTER(PlanInfo)]
+    lib.rlap_snapshot_plan_propagate.restype = ci
+    lib.rlap_snapshot_plan_propagate.argtypes = [vp, vp, ctypes.POINTER(PlanDesc), ci, vp, i64, vp, ctypes.POINTER(SpmmInfo)]
     lib.rlap_approx_chol_views.restype = ci
     lib.rlap_approx_chol_views.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, vp, ci, ci, vp, u64, vp, i64, vp,
                                            ctypes.POINTER(Stats)]

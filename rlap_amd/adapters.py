@@ -56,6 +56,36 @@ class Snapshots:
         return ops.snapshot_propagate(self.sc, self.ptr, self.num_nodes, x, node_ptr=self.node_ptr, weighted=self.weighted,
                                       add_self_loops=True, fill_value=self.fill_value, normalize=True, transpose=transpose)
 
+    def plan(self, directions: str = "both") -> "PlannedSnapshots":
+        """The same snapshots served by one propagation plan (ops.snapshot_plan), built on first use: for the six to twelve
+        products a training step makes on them.  SnapshotGCNConv takes the holder as it takes this one."""
+        return PlannedSnapshots(self, directions)
+
+
+class PlannedSnapshots:
+    """`Snapshots` behind a plan: the same `.layers` and `.propagate(x, transpose=False)`, the same bits, the lists built once (on
+    the first product) instead of in every call.  `snapshot_plan` is the ops.SnapshotPlan, None before the first use."""
+
+    def __init__(self, snapshots: Snapshots, directions: str = "both"):
+        if directions not in ops.PLAN_DIRECTIONS:
+            raise ValueError(f"directions: one of {sorted(ops.PLAN_DIRECTIONS)}, got {directions!r}")
+        self.snapshots, self.directions, self.snapshot_plan = snapshots, directions, None
+
+    @property
+    def layers(self) -> int:
+        return self.snapshots.layers
+
+    @property
+    def num_nodes(self) -> int:
+        return self.snapshots.num_nodes
+
+    def propagate(self, x, transpose: bool = False):
+        if self.snapshot_plan is None:
+            s = self.snapshots
+            self.snapshot_plan = ops.snapshot_plan(s.sc, s.ptr, s.num_nodes, node_ptr=s.node_ptr, weighted=s.weighted, add_self_loops=True,
+                                                   fill_value=s.fill_value, normalize=True, directions=self.directions)
+        return self.snapshot_plan.propagate(x, transpose=transpose)
+
 
 def _snapshots_of(x, sc, ptr, num_nodes, keep_weights, fill_value):
     """The holder of one call; like _gcn_graphs the loops cover x.shape[0] nodes when x is given, else the call's num_nodes."""

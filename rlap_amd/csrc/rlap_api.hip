@@ -23,6 +23,7 @@
 #include "rlap_stats.h"
 #include "rlap_subgraph.h"
 #include "rlap_gcn.h"
+#include "rlap_plan.h"
 #include "rlap_spmm_api.h"
 
 using namespace rlap;
@@ -1400,6 +1401,88 @@ int rlap_snapshot_propagate(rlap_handle h, const double* d_sc, int64_t m, const 
         if (h_info) {
             h_info->entries = rep.entries; h_info->blocks = rep.blocks; h_info->chunked_lists = rep.chunked_lists;
             h_info->arena_bytes = (int64_t)need; h_info->host_syncs = rep.host_syncs;
+        }
+        return rc;
+    });
+}
+
+int rlap_snapshot_plan_bytes(int64_t m, int64_t S, int64_t G, int64_t num_nodes, int flags, size_t* bytes) {
+    if (!bytes || m < 0 || S < 1 || G < 1 || num_nodes < 0 || S % G != 0) return RLAP_E_BAD_ARG;
+    if (flags & ~(RLAP_GCN_WEIGHTED | RLAP_GCN_SELF_LOOPS | RLAP_GCN_NORMALIZE | RLAP_PLAN_FORWARD | RLAP_PLAN_TRANSPOSED)) return RLAP_E_BAD_ARG;
+    if (m >= INT32_MAX || S >= (int64_t)1 << 30 || num_nodes >= INT32_MAX || (S / G) * num_nodes >= SPMM_MAX_ELEMS) return RLAP_E_TOO_LARGE;
+    if (!(flags & (RLAP_PLAN_FORWARD | RLAP_PLAN_TRANSPOSED))) flags |= RLAP_PLAN_FORWARD | RLAP_PLAN_TRANSPOSED;
+    *bytes = snapshot_plan_buffer_bytes(m, S, G, num_nodes, flags);
+    return RLAP_OK;
+}
+
+int rlap_snapshot_plan_build(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
+                             int64_t G, int64_t num_nodes, int flags, double fill_value, void* d_plan, size_t plan_bytes,
+                             rlap_plan_desc* h_desc, rlap_plan_info* h_info) {
+    if (h_info) *h_info = rlap_plan_info{};
+    if (!h_desc) return RLAP_E_BAD_ARG;
+    *h_desc = rlap_plan_desc{};
+    if (!d_plan || (reinterpret_cast<uintptr_t>(d_plan) & 15)) return RLAP_E_BAD_ARG;
+    if (flags & ~(RLAP_GCN_WEIGHTED | RLAP_GCN_SELF_LOOPS | RLAP_GCN_NORMALIZE | RLAP_PLAN_FORWARD | RLAP_PLAN_TRANSPOSED)) return RLAP_E_BAD_ARG;
+    if ((flags & RLAP_GCN_SELF_LOOPS) && !(fill_value > 0.0 && std::isfinite(fill_value))) return RLAP_E_BAD_ARG;
+    if (!(flags & (RLAP_PLAN_FORWARD | RLAP_PLAN_TRANSPOSED))) flags |= RLAP_PLAN_FORWARD | RLAP_PLAN_TRANSPOSED;
+    SnapshotSeg g{d_sc, m, d_ptr, S, d_node_ptr, G, num_nodes};
+    if (const int rc = snapshot_check(h, &g, 1)) return rc;
+    if (num_nodes >= INT32_MAX || (g.S / g.G) * num_nodes >= SPMM_MAX_ELEMS) return RLAP_E_TOO_LARGE;
+    if (plan_bytes < snapshot_plan_buffer_bytes(g.m, g.S, g.G, g.N, flags)) return RLAP_E_BAD_ARG;
+    return snapshot_call(h, [&] { return snapshot_plan_build_bytes(g.m, g.S, g.G, g.N, flags); }, [&](void* base, size_t have, size_t need) -> int {
+        if (h->poison >= 0) {   // debug: the plan must not depend on what the arena or the caller's buffer held
+            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_plan, h->poison, plan_bytes, h->stream));
+        }
+        const SnapshotPlanArgs a{g, flags, fill_value, d_plan, plan_bytes};
+        SnapshotPlanReport rep;
+        const int rc = snapshot_plan_build_run(h->stream, base, have, a, h_desc, &rep);
+        if (rc != RLAP_OK) *h_desc = rlap_plan_desc{};
+        if (h_info) {
+            h_info->entries = rep.entries; h_info->blocks = rep.blocks; h_info->chunked_lists_forward = rep.chunked[0];
+            h_info->chunked_lists_transposed = rep.chunked[1]; h_info->loops_removed = rep.loops_removed;
+            h_info->arena_bytes = (int64_t)need; h_info->host_syncs = rep.host_syncs;
+        }
+        return rc;
+    });
+}
+
+int rlap_snapshot_plan_propagate(rlap_handle h, const void* d_plan, const rlap_plan_desc* h_desc, int flags, const void* d_x, int64_t F,
+                                 void* d_y, rlap_spmm_info* h_info) {
+    if (h_info) *h_info = rlap_spmm_info{};
+    if (!h || !d_plan || !h_desc || F < 1) return RLAP_E_BAD_ARG;
+    if (flags & ~(RLAP_SPMM_TRANSPOSE | RLAP_SPMM_X_F32 | RLAP_SPMM_X_PER_LAYER)) return RLAP_E_BAD_ARG;
+    const rlap_plan_desc d = *h_desc;
+    // a descriptor that a successful build wrote: every part it names lies inside the bytes it reports
+    if (d.magic != plan::MAGIC || d.m < 0 || d.m >= INT32_MAX || d.num_nodes < 0 || d.num_nodes >= INT32_MAX || d.graphs < 1 ||
+        d.segments < 1 || d.segments >= (int64_t)1 << 30 || d.segments % d.graphs != 0 || (reinterpret_cast<uintptr_t>(d_plan) & 15))
+        return RLAP_E_BAD_ARG;
+    const int64_t slots = (d.segments / d.graphs) * d.num_nodes;
+    if (slots >= SPMM_MAX_ELEMS) return RLAP_E_BAD_ARG;
+    const bool t = (flags & RLAP_SPMM_TRANSPOSE) != 0;
+    if (!(d.flags & (t ? RLAP_PLAN_TRANSPOSED : RLAP_PLAN_FORWARD))) return RLAP_E_BAD_ARG;
+    {
+        const int64_t ent = t ? d.entries_transposed : d.entries_forward, ch = t ? d.chunks_transposed : d.chunks_forward;
+        const int64_t off = t ? d.off_transposed : d.off_forward, dir = t ? d.dir_transposed : d.dir_forward, rec = t ? d.rec_transposed : d.rec_forward;
+        if (ent < 0 || ent > d.m || ch < 0 || ch > plan::dir_cap(d.m) || off < 0 || dir < 0 || rec < 0 || ((off | dir | rec) & 15) ||
+            off + 8 * (slots + 1) > d.plan_bytes || dir + 16 * ch > d.plan_bytes || rec + 16 * ent > d.plan_bytes)
+            return RLAP_E_BAD_ARG;
+        if ((d.flags & RLAP_GCN_SELF_LOOPS) && (d.loop_offset < 0 || (d.loop_offset & 7) || d.loop_offset + 8 * slots > d.plan_bytes)) return RLAP_E_BAD_ARG;
+    }
+    if (F > SPMM_MAX_F || slots * F >= SPMM_MAX_ELEMS) return RLAP_E_TOO_LARGE;
+    const int64_t elems = slots * F;
+    if (elems > 0 && (!d_x || !d_y)) return RLAP_E_BAD_ARG;
+    return snapshot_call(h, [&] { return snapshot_plan_use_bytes(d, F, flags, h->dbg_scr); }, [&](void* base, size_t have, size_t need) -> int {
+        if (h->poison >= 0) {   // debug: the result must not depend on what the arena or the result buffer held
+            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
+            if (elems > 0) RLAP_HIPCHK(hipMemsetAsync(d_y, h->poison, (size_t)elems * ((flags & RLAP_SPMM_X_F32) ? 4 : 8), h->stream));
+        }
+        const PlanUseArgs a{d_plan, &d, flags, d_x, F, d_y, h->dbg_scr};
+        const int rc = snapshot_plan_use_run(h->stream, base, have, a);
+        if (h_info) {
+            h_info->entries = (t ? d.entries_transposed : d.entries_forward) + ((d.flags & RLAP_GCN_SELF_LOOPS) ? slots : 0);
+            h_info->chunked_lists = 0; h_info->blocks = 0;
+            h_info->arena_bytes = (int64_t)need; h_info->host_syncs = 0;
         }
         return rc;
     });

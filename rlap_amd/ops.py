@@ -978,14 +978,8 @@ def snapshot_gcn_norm(
         return ei, val, eptr
 
 
-def _propagate_args(sc, ptr, num_nodes, x, node_ptr, fill_value):
-    """Host-side checks of snapshot_propagate, made before the device is touched: (ptr, node_ptr, fill, layers, per_layer)."""
-    p, np_ = _snapshot_tables(sc, ptr, num_nodes, node_ptr)
-    fill = _real(fill_value, "fill_value", 0.0, float("inf"))
-    S, G = p.numel() - 1, _graphs(np_)
-    if S < 1 or S % G != 0:
-        raise ValueError(f"ptr: {S} segments; at least one, and a multiple of the {G} graphs")
-    L, n = S // G, int(num_nodes)
+def _features_arg(x, n: int, L: int) -> bool:
+    """The checks of the features of a propagation, (n, F) or (L, n, F): whether there is one matrix per layer."""
     if not isinstance(x, Tensor) or x.dim() not in (2, 3):
         raise ValueError("x: a (num_nodes, F) or (layers, num_nodes, F) tensor")
     if x.dtype not in (torch.float32, torch.float64):
@@ -996,7 +990,18 @@ def _propagate_args(sc, ptr, num_nodes, x, node_ptr, fill_value):
         raise ValueError(f"x: {x.shape[0]} layers, the call has {L} (segments / graphs)")
     if x.shape[-1] < 1:
         raise ValueError("x: at least one feature column")
-    return p, np_, fill, L, x.dim() == 3
+    return x.dim() == 3
+
+
+def _propagate_args(sc, ptr, num_nodes, x, node_ptr, fill_value):
+    """Host-side checks of snapshot_propagate, made before the device is touched: (ptr, node_ptr, fill, layers, per_layer)."""
+    p, np_ = _snapshot_tables(sc, ptr, num_nodes, node_ptr)
+    fill = _real(fill_value, "fill_value", 0.0, float("inf"))
+    S, G = p.numel() - 1, _graphs(np_)
+    if S < 1 or S % G != 0:
+        raise ValueError(f"ptr: {S} segments; at least one, and a multiple of the {G} graphs")
+    L = S // G
+    return p, np_, fill, L, _features_arg(x, int(num_nodes), L)
 
 
 def _propagate(sc, p, np_, n, x, L, per_layer, weighted, add_self_loops, fill, normalize, transpose):
@@ -1070,6 +1075,146 @@ def snapshot_propagate(
     if torch.is_grad_enabled() and x.requires_grad:
         return _Propagate.apply(x, call)
     return _propagate(sc, p, np_, int(num_nodes), x, L, per_layer, *call[6:])
+
+
+PLAN_DIRECTIONS = {"forward": _lib.PLAN_FORWARD, "transposed": _lib.PLAN_TRANSPOSED, "both": _lib.PLAN_FORWARD | _lib.PLAN_TRANSPOSED}
+
+
+def _plan_call(plan, flags: int, d_x: Tensor, F: int, y: Tensor):
+    """One rlap_snapshot_plan_propagate call on the plan's device: the arena is sized by the call itself (RLAP_E_WORKSPACE and one
+    regrow), statuses become exceptions as in _snapshot_call, `last_stats` is set on success."""
+    global last_stats
+    dev = plan.buffer.device
+    lib, hobj = _handle_obj(dev)
+    info = _lib.SpmmInfo()
+    st = _lib.Stats()
+    rc = _run(hobj, dev, 0, None, 1, False, lambda: lib.rlap_snapshot_plan_propagate(
+        hobj.ptr, plan.buffer.data_ptr(), ctypes.byref(plan.desc), flags, d_x.data_ptr() if d_x.numel() else None, F,
+        y.data_ptr() if y.numel() else None, ctypes.byref(info)), st)
+    if rc in (1, 2, 3, _lib.E_NOT_GROUPED):
+        raise ValueError(f"rlap: {_lib.status_string(rc)}")
+    if rc != 0:
+        _raise(rc)
+    last_stats = info.as_dict()
+    return info
+
+
+def _plan_propagate(plan, x: Tensor, per_layer: bool, transpose: bool) -> Tensor:
+    """One planned product; x and the direction are already checked."""
+    dev = plan.buffer.device
+    flags = ((_lib.SPMM_TRANSPOSE if transpose else 0) | (_lib.SPMM_X_F32 if x.dtype == torch.float32 else 0)
+             | (_lib.SPMM_X_PER_LAYER if per_layer else 0))
+    with torch.cuda.device(dev):
+        d_x = x.detach().to(device=dev).contiguous()
+        F = int(d_x.shape[-1])
+        y = torch.empty((plan.layers, plan.num_nodes, F), dtype=d_x.dtype, device=dev)
+        _plan_call(plan, flags, d_x, F, y)
+        return y
+
+
+class _PlanPropagate(torch.autograd.Function):
+    """_Propagate over a plan: the gradient with respect to x is the planned call with `transpose` flipped."""
+
+    @staticmethod
+    def forward(ctx, x, plan, per_layer, transpose):
+        ctx.call = (plan, per_layer, transpose)
+        return _plan_propagate(plan, x, per_layer, transpose)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        plan, per_layer, transpose = ctx.call
+        gx = _plan_propagate(plan, gy.contiguous(), True, not transpose)
+        return (gx if per_layer else gx.sum(0)), None, None, None
+
+
+class SnapshotPlan:
+    """What snapshot_plan returns: the lists of snapshot_propagate for one elimination result, built once.  `buffer` is the plan (a
+    torch.uint8 tensor on the device, owned by this object; valid while it is unchanged, and independent of `sc` after the build),
+    `desc` its host descriptor (rlap_plan_desc), `info` what the build did (rlap_plan_info).
+
+      layers, num_nodes : the shape of a result, (layers, num_nodes, F)
+      entries           : entries of the list the products run over (rows that stay + loops)
+      nbytes            : bytes of the plan buffer
+      directions        : "forward", "transposed" or "both"
+    """
+
+    def __init__(self, buffer: Tensor, desc, info: dict, directions: str):
+        self.buffer, self.desc, self.info, self.directions = buffer, desc, info, directions
+        self.layers = int(desc.segments) // int(desc.graphs)
+        self.num_nodes = int(desc.num_nodes)
+        self.entries = int(info["entries"])
+        self.nbytes = int(buffer.numel())
+
+    def _need(self, transpose: bool):
+        if not PLAN_DIRECTIONS[self.directions] & (_lib.PLAN_TRANSPOSED if transpose else _lib.PLAN_FORWARD):
+            raise ValueError(f"this plan holds the {self.directions} lists only: build it with directions=\"both\" for "
+                             f"transpose={transpose} (the backward pass of a product needs the other direction)")
+
+    def propagate(self, x: Tensor, transpose: bool = False) -> Tensor:
+        """y[l] = A^_l x (transpose: its transposed product) as ops.snapshot_propagate returns it for the plan's input and flags --
+        the same bits -- without the preparation and without a host synchronisation.  x is (num_nodes, F) or (layers, num_nodes, F),
+        float32 or float64.  Differentiable in x; the backward pass is the planned call of the other direction, so a plan of one
+        direction refuses an x that requires a gradient.  Sets `last_stats` (rlap_spmm_info; host_syncs is 0)."""
+        per_layer = _features_arg(x, self.num_nodes, self.layers)
+        transpose = bool(transpose)
+        self._need(transpose)
+        if torch.is_grad_enabled() and x.requires_grad:
+            self._need(not transpose)
+            return _PlanPropagate.apply(x, self, per_layer, transpose)
+        return _plan_propagate(self, x, per_layer, transpose)
+
+
+def snapshot_plan(
+    sc: Tensor,
+    ptr: Union[Tensor, Sequence[int]],
+    num_nodes: int,
+    node_ptr: Optional[Union[Tensor, Sequence[int]]] = None,
+    weighted: bool = False,
+    add_self_loops: bool = True,
+    fill_value: float = 1.0,
+    normalize: bool = True,
+    directions: str = "both",
+) -> SnapshotPlan:
+    """The x-independent half of snapshot_propagate, built once: a `SnapshotPlan` whose `.propagate(x, transpose)` returns what
+    snapshot_propagate(sc, ptr, num_nodes, x, node_ptr, weighted, add_self_loops, fill_value, normalize, transpose) returns -- the
+    same bits, for every F, float32 and float64, shared and per-layer x -- without the table checks, the column pass, the degrees, the
+    sort by source and the host synchronisation that every unplanned call repeats.  One training step makes six to twelve products on
+    the same (sc, ptr): build the plan after the elimination and use it for all of them.  All arguments as for snapshot_propagate;
+
+      directions : "forward", "transposed" or "both" (default) -- the lists to build.  The backward pass of a product is the other
+                   direction, so training needs "both"; a plan of one direction is about half the size.
+
+    The plan lives in a torch.uint8 tensor on sc's device (16 bytes per row and direction, 8 to 24 bytes per (layer, id)); `sc` may be
+    freed or overwritten after the build.  Malformed arguments raise ValueError before the device is touched; layout errors and (with
+    weighted and normalize) a weight that is not finite or <= 0 raise ValueError as for snapshot_gcn_norm.  One host synchronisation.
+    `last_stats` then holds what the build did (rlap_plan_info: entries, blocks, chunked_lists_forward, chunked_lists_transposed,
+    loops_removed, arena_bytes, host_syncs)."""
+    p, np_ = _snapshot_tables(sc, ptr, num_nodes, node_ptr)
+    fill = _real(fill_value, "fill_value", 0.0, float("inf"))
+    if directions not in PLAN_DIRECTIONS:
+        raise ValueError(f"directions: one of {sorted(PLAN_DIRECTIONS)}, got {directions!r}")
+    S, G, n = p.numel() - 1, _graphs(np_), int(num_nodes)
+    if S < 1 or S % G != 0:
+        raise ValueError(f"ptr: {S} segments; at least one, and a multiple of the {G} graphs")
+    dev = _device_for(sc)
+    flags = ((_lib.GCN_WEIGHTED if weighted else 0) | (_lib.GCN_SELF_LOOPS if add_self_loops else 0)
+             | (_lib.GCN_NORMALIZE if normalize else 0) | PLAN_DIRECTIONS[directions])
+    with torch.cuda.device(dev):
+        rows = sc.to(device=dev, dtype=torch.float64).contiguous()
+        lib, _ = _handle_obj(dev)
+        bound = ctypes.c_size_t(0)
+        rc = lib.rlap_snapshot_plan_bytes(int(rows.shape[0]), S, G, n, flags, ctypes.byref(bound))
+        if rc != 0:
+            _raise(rc)
+        buf = torch.empty(int(bound.value), dtype=torch.uint8, device=dev)
+        desc = _lib.PlanDesc()
+        info = _snapshot_call("rlap_snapshot_plan_build", _lib.PlanInfo, rows, p, np_, n,
+                              (flags, fill, buf.data_ptr(), buf.numel(), ctypes.byref(desc)))
+        used = int(desc.plan_bytes)
+        if 0 < used < buf.numel():   # (an input with loop rows, or few long lists: the tail is not in use)
+            buf = buf[:used].clone() if 4 * used < 3 * buf.numel() else buf[:used]
+        return SnapshotPlan(buf, desc, info.as_dict(), directions)
 
 
 def identity(a: Tensor) -> Tensor:

@@ -10,6 +10,11 @@ Medians of 5 after a warm-up, host clock around a synchronise; the five times ar
   c5   : bench config 5, a node_ptr batch of 1024 x BA(4096, 8), depths [n/8, n/4, n/2] (3,072 snapshots, 3 layers)
     python tools/propagate_latency.py --graphs ba1m,c5
     python tools/propagate_latency.py --graphs ba1m --features 256 --no-torch     # the calls alone (for rocprofv3 --kernel-trace --stats)
+    python tools/propagate_latency.py --plan --no-torch                           # and the same products over a propagation plan
+--plan adds, next to the figures above: the time of ops.snapshot_plan (both directions), the planned forward product and
+the planned forward + transposed pair, the plan's bytes, the algorithmic bytes of k_pl_rows and the calls after which the plan has paid
+for itself, build time / (unplanned forward - planned forward).  --plan-only leaves the unplanned calls out (a profile of the planned
+kernels alone; also what runs against a library without the plan exports when it is absent).
 """
 import argparse
 import json
@@ -64,6 +69,10 @@ def run(name, F, args, fh):
     rows = int(sc.shape[0])
     x = torch.randn(N, F, dtype=torch.float32, generator=torch.Generator().manual_seed(F)).cuda()
     rec = {"graph": name, "F": F, "snapshots": S, "layers": L, "rows": rows}
+    if args.plan_only:
+        plan_figures(rec, sc, ptr, N, node_ptr, x, L, F, None, None, args)
+        emit(rec, fh)
+        return
     t, ts, y = timed(lambda: ops.snapshot_propagate(sc, ptr, N, x, node_ptr=node_ptr), args.reps)
     st = dict(ops.last_stats)
     M = st["entries"]
@@ -81,6 +90,8 @@ def run(name, F, args, fh):
         return ops.snapshot_propagate(sc, ptr, N, out, node_ptr=node_ptr, transpose=True)
     t2, ts2, _ = timed(both, args.reps)
     rec.update({"forward_transpose_ms": round(t2, 3), "forward_transpose_runs_ms": ts2})
+    if args.plan:
+        plan_figures(rec, sc, ptr, N, node_ptr, x, L, F, t, y, args)
     if not args.no_torch:
         tl, tsl, (eidx, val, eptr) = timed(lambda: ops.snapshot_gcn_norm(sc, ptr, N, node_ptr=node_ptr), args.reps)
         e = eptr.tolist()
@@ -108,13 +119,44 @@ def run(name, F, args, fh):
         except Exception as exc:   # (not every ROCm build has the CSR product)
             rec["torch_csr_ms"] = f"not available: {type(exc).__name__}"
         del eidx, val
+    emit(rec, fh)
+    del sc, x, y
+    torch.cuda.empty_cache()
+
+
+def emit(rec, fh):
     line = json.dumps(rec)
     print(line, flush=True)
     if fh is not None:
         fh.write(line + "\n")
         fh.flush()
-    del sc, x, y
-    torch.cuda.empty_cache()
+
+
+def plan_figures(rec, sc, ptr, N, node_ptr, x, L, F, unplanned_ms, y, args):
+    """The planned products of the same input: build, forward, forward + transposed, bytes."""
+    tb, tsb, plan = timed(lambda: ops.snapshot_plan(sc, ptr, N, node_ptr=node_ptr), args.reps)
+    info = dict(plan.info)
+    tp, tsp, yp = timed(lambda: plan.propagate(x), args.reps)
+    syncs = ops.last_stats["host_syncs"]
+
+    def both():
+        return plan.propagate(plan.propagate(x), transpose=True)
+    tp2, tsp2, _ = timed(both, args.reps)
+    M = info["entries"]
+    records = int(plan.desc.entries_forward)
+    # algorithmic bytes of k_pl_rows: per record its 16 bytes and the gathered row of x; per (layer, id) two offsets (one new), the
+    # loop coefficient and the loop's row of x (inside M); y written once
+    rows_bytes = records * 16 + M * 4 * F + L * N * (8 + 8) + 4 * L * N * F
+    rec.update({"plan_build_ms": round(tb, 3), "plan_build_runs_ms": tsb, "plan_bytes": plan.nbytes, "plan_entries": M,
+                "plan_chunked_lists": [info["chunked_lists_forward"], info["chunked_lists_transposed"]],
+                "planned_forward_ms": round(tp, 3), "planned_forward_runs_ms": tsp, "planned_forward_transpose_ms": round(tp2, 3),
+                "planned_forward_transpose_runs_ms": tsp2, "planned_host_syncs": syncs, "plan_rows_kernel_bytes": rows_bytes,
+                "planned_whole_call_bytes_per_s": round(rows_bytes / (tp * 1e-3), 1)})
+    if unplanned_ms is not None:
+        rec["planned_equals_unplanned"] = bool(torch.equal(yp, y))
+        gain = unplanned_ms - tp
+        rec["plan_pays_after_calls"] = round(tb / gain, 2) if gain > 0 else None
+    del plan, yp
 
 
 def main():
@@ -123,6 +165,8 @@ def main():
     ap.add_argument("--features", default="64,256")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-torch", action="store_true", help="time the calls alone")
+    ap.add_argument("--plan", action="store_true", help="also build a propagation plan and time the planned products")
+    ap.add_argument("--plan-only", action="store_true", help="the planned products alone")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file")
     args = ap.parse_args()
     fh = open(args.out, "a") if args.out else None
