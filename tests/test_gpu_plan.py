@@ -376,3 +376,34 @@ def test_errors_leave_the_handle_intact(ops):
             ops.snapshot_plan(bad, ptr, n, **kw)
         check_plan(ops, sc, ptr, n, f"after {match}", Fs=(16,), dtypes=(torch.float64,), weighted=True)
     ops.snapshot_plan(weight, ptr, n)                                        # unweighted: the weights are not looked at
+
+
+# ------------------------------------------------------------------------------------------------ 10. streams
+def test_planned_call_on_a_side_stream(ops):
+    """The planned call never synchronises: what orders it behind the kernels that produce x, and in front of those that consume y,
+    is the stream the handle is bound to at the call.  The plan is built on the default stream; on a side stream that has waited for
+    it, x comes out of a chain of torch kernels long enough for the device to lag behind the host, the planned call follows at
+    once, and y is consumed there.  The bits of the same calls on the default stream, made after everything has finished."""
+    n, F = 3000, 16
+    sc, ptr = depths_views(ops, n, 5, 2, "random", [n // 8, n // 4, n // 2])
+    plan = ops.snapshot_plan(sc, ptr, n, weighted=True)
+    base = features(n, F, 6, seed=9, dtype=torch.float32)
+    w = torch.randn(2048, 2048, generator=torch.Generator().manual_seed(1)).cuda() / 32.0
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(40):
+            w = torch.sin(w @ w)
+        x = base + w[:1, :F]                                                  # the last kernel of the chain writes x
+        got = []
+        for t in (False, True):
+            y = plan.propagate(x, transpose=t)
+            assert ops.last_stats["host_syncs"] == 0
+            got.append(y * 2.0)                                                # consumed on the same stream
+    side.synchronize()
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(x).all()) and not torch.equal(x, base)
+    for t in (False, True):
+        ref = plan.propagate(x, transpose=t) * 2.0
+        assert same(got[t], ref), f"transpose={t}: the side stream's result differs from the default stream's"
+        assert same(plan.propagate(x, transpose=t), ops.snapshot_propagate(sc, ptr, n, x, weighted=True, transpose=t))

@@ -345,6 +345,52 @@ def test_chunk_sums_past_their_budget(ops, mirror, limit):
         ops.debug_set_limits()
 
 
+# F_PATHS: the feature widths at which launch_sums takes a lane path that ALL_F leaves out (V = 4 float32 / 2 float64 a lane).
+#   65          : the one-column kernels with two tiles of 64 lanes, the second holding one lane (both types)
+#   66, 130     : float32 -- no multiple of 4: the one-column kernels with two and three tiles; float64 -- vector lanes: 33 in one
+#                 tile, and 65 in two tiles of which the second holds one lane
+#   2, 6, 12    : groups of 1, 2, 4, 8 lanes of which some idle (6: 3 of 4 float64 lanes; 12: 3 of 4 float32, 6 of 8 float64), and
+#                 the one-column kernels with two and six lanes (float32, 2 and 6)
+#   256         : float32 -- exactly one full tile of 64 vector lanes; float64 -- two full tiles
+F_PATHS = (2, 6, 12, 65, 66, 130, 256)
+
+
+@pytest.fixture
+def poisoned(ops):
+    """y holds NaN patterns before every call: an element that is never written cannot pass by finding an earlier call's result
+    in reused memory."""
+    ops.debug_set_poison(0xFF)
+    yield
+    ops.debug_set_poison(-1)
+
+
+@pytest.mark.parametrize("F", F_PATHS)
+def test_lane_paths_depths_views(ops, mirror, poisoned, F):
+    n = 300
+    sc, ptr = depths_views(ops, n, 3, 2, "random", [75, 150], views=2)
+    assert ptr.numel() == 5
+    check_call(ops, mirror, sc, ptr, n, f"lane paths F={F}", Fs=(F,), weighted=True)
+
+
+@pytest.mark.parametrize("limit", [None, 0])
+@pytest.mark.parametrize("F", F_PATHS)
+def test_lane_paths_long_lists(ops, mirror, poisoned, F, limit):
+    """Two stars of three chunks each: the chunk kernel on the same lane paths, and (limit 0: no chunk sum kept) the rows kernel
+    summing a long list chunk by chunk itself."""
+    C = mirror.spmm_chunk()
+    leaves = 2 * C + 40
+    a, b = star(leaves, 1), star(leaves, 2)
+    sc = torch.from_numpy(np.concatenate([a, b])).cuda()
+    ptr, n = [0, len(a), len(a) + len(b)], leaves + 1
+    try:
+        if limit is not None:
+            ops.debug_set_limits(scratch_entries=limit)
+        check_call(ops, mirror, sc, ptr, n, f"stars, lane paths F={F} limit={limit}", Fs=(F,), weighted=True)
+        assert ops.last_stats["chunked_lists"] == 2
+    finally:
+        ops.debug_set_limits()
+
+
 @pytest.mark.parametrize("weighted", [False, True])
 def test_star_with_loop_rows(ops, mirror, weighted):
     """Loop rows inside a long block: an entry's place in its list is no longer its place in its block."""

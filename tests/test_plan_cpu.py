@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import plan_buffer
 import spmm_mirror
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -75,15 +76,8 @@ def build(lib, rows, ptr, N, c, drop, transpose):
 
 
 def python_lists(rows, ptr, N, c, drop, transpose):
-    """{slot: [(coefficient, id taken)]}: every list by appending in input order."""
-    lists = {}
-    for s in range(len(ptr) - 1):
-        for r in range(ptr[s], ptr[s + 1]):
-            vi, vj = int(rows[r, 0]), int(rows[r, 1])
-            if drop and vi == vj:
-                continue
-            lists.setdefault(s * N + (vi if transpose else vj), []).append((c[r], vj if transpose else vi))
-    return lists
+    """{slot: [(coefficient, id taken)]}: every list by appending in input order (tests/plan_buffer.py, one graph a layer)."""
+    return {slot: [(c[r], i) for r, i in l] for slot, l in plan_buffer.expected_lists(rows, ptr, N, 1, drop, transpose).items()}
 
 
 @pytest.mark.parametrize("which", ["hand", "star"])
