@@ -464,6 +464,27 @@ int rlap_snapshot_plan_build(rlap_handle h, const double* d_sc, int64_t m, const
 int rlap_snapshot_plan_propagate(rlap_handle h, const void* d_plan, const rlap_plan_desc* h_desc, int flags, const void* d_x, int64_t F,
                                  void* d_y, rlap_spmm_info* h_info);
 
+/* Propagation plans for rows in ANY order: the arguments, the flags, the descriptor and the info of
+ * rlap_snapshot_plan_build, for an input that need not be an elimination result -- a plain COO edge list, the (out, pptr) of
+ * rlap_snapshot_ppr, a subgraph result.  The rows of a segment may come in any order; duplicate rows, directed structure, loop rows
+ * and ids without rows are legal.  Row id is the source, column id the target.  The plan has the layout of the build above, so the
+ * size query above is its bound and every planned call runs on it unchanged.  What the lists hold depends on a row's place in the
+ * input alone (rlap_amd/csrc/rlap_edgeplan.h): the forward list of (layer, j) is the rows with target j in input order, the
+ * transposed list of (layer, i) the rows with source i in input order; the degree of (layer, j) is summed over the forward list in
+ * the fixed order of rlap_snapshot_gcn_norm, the loop's weight (that of the list's last loop row, or fill_value) last; an id
+ * without incoming rows has the loop's weight alone, or degree 0.  For an input in the elimination layout the buffer equals
+ * rlap_snapshot_plan_build's bit for bit, both directions.
+ *   h_info->blocks : the non-empty forward lists
+ *   h_desc         : zeroed on every refusal
+ * An id that is not an integer of its graph's range [node_ptr[g], node_ptr[g+1]) (or [0, num_nodes)): RLAP_E_INDEX_RANGE; with
+ * RLAP_GCN_WEIGHTED and RLAP_GCN_NORMALIZE a weight that is not finite or <= 0, a bad ptr / node_ptr, a buffer below the size query:
+ * RLAP_E_BAD_ARG.  Limits: m < 2^31 - 1 and (S / G) num_nodes < 2^31 (RLAP_E_TOO_LARGE, never truncated).  Scratch from the arena
+ * (two stable sorts of (slot, row) by rocPRIM; RLAP_E_WORKSPACE when a caller-provided one is too small); one host synchronisation;
+ * no atomic on a floating-point value: the same input gives the same bits. */
+int rlap_edge_plan_build(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
+                         int64_t G, int64_t num_nodes, int flags, double fill_value, void* d_plan, size_t plan_bytes,
+                         rlap_plan_desc* h_desc, rlap_plan_info* h_info);
+
 /* The op with the step BEFORE the path fused in (scripts/node_shared.py:326-327,
  * scripts/augmentor_benchmarks.py:77-78):
  *   symmetrize != 0 : the input holds every undirected edge in one or both directions; (b,a) is

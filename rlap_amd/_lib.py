@@ -21,9 +21,10 @@ EXPORTS = [
     "rlap_set_rng_mode", "rlap_approx_chol_views", "rlap_approx_chol_depths", "rlap_debug_set_flow_limits",
     "rlap_approx_chol_views_depths", "rlap_snapshot_stats", "rlap_snapshot_ppr", "rlap_snapshot_subgraph",
     "rlap_snapshot_gcn_norm", "rlap_snapshot_propagate",
-    "rlap_snapshot_plan_bytes", "rlap_snapshot_plan_build", "rlap_snapshot_plan_propagate",
+    "rlap_snapshot_plan_bytes", "rlap_snapshot_plan_build", "rlap_snapshot_plan_propagate", "rlap_edge_plan_build",
 ]
 
+E_INDEX_RANGE = 2   # RLAP_E_INDEX_RANGE
 E_WORKSPACE = 11   # RLAP_E_WORKSPACE
 E_NOT_GROUPED = 12   # RLAP_E_NOT_GROUPED
 E_OUT_CAPACITY = 13   # RLAP_E_OUT_CAPACITY
@@ -187,6 +188,8 @@ def load():
     lib.rlap_snapshot_plan_build.restype = ci
     lib.rlap_snapshot_plan_build.argtypes = [vp, vp, i64, vp, i64, vp, i64, i64, ci, ctypes.c_double, vp, ctypes.c_size_t,
                                              ctypes.POINTER(PlanDesc), ctypes.POINTER(PlanInfo)]
+    lib.rlap_edge_plan_build.restype = ci
+    lib.rlap_edge_plan_build.argtypes = lib.rlap_snapshot_plan_build.argtypes
     lib.rlap_snapshot_plan_propagate.restype = ci
     lib.rlap_snapshot_plan_propagate.argtypes = [vp, vp, ctypes.POINTER(PlanDesc), ci, vp, i64, vp, ctypes.POINTER(SpmmInfo)]
     lib.rlap_approx_chol_views.restype = ci

@@ -96,7 +96,9 @@ class SnapshotGCNConv(torch.nn.Module):
     """GCNConv for all views of a call at once: forward(x, snapshots) = snapshots.propagate(x @ W) + b, an (L, n, out_channels)
     tensor for the L layers of `snapshots` (a `Snapshots`).  x is (n, in_channels), shared by the layers (the first GCN layer of
     every view), or (L, n, in_channels) (the later ones).  The dense product is torch's, the sparse one ops.snapshot_propagate;
-    gradients reach W, b and x.  Glorot-uniform W and zero b, as PyG's GCNConv initialises them.  (Unpinned: PyG is not installed
+    gradients reach W, b and x.  `snapshots` is taken by duck typing: anything with `.propagate(x, transpose=False)` and the
+    (L, n, F) result serves, so forward(x, plan) with an ops.SnapshotPlan -- graph_plan(g) for the input graph itself,
+    rLapDepths.diffuse_plan(g) for its PPR diffusions -- works as it does with a holder.  Glorot-uniform W and zero b, as PyG's GCNConv initialises them.  (Unpinned: PyG is not installed
     here; this restates its published semantics -- linear without bias, propagate with gcn_norm's coefficients, then the bias --
     not a run of it: DESIGN 4.10 and section 7.)"""
 
@@ -115,6 +117,16 @@ class SnapshotGCNConv(torch.nn.Module):
     def forward(self, x, snapshots: Snapshots):
         y = snapshots.propagate(x @ self.weight)
         return y if self.bias is None else y + self.bias
+
+
+def graph_plan(g, fill_value: float = 1.0, directions: str = "both"):
+    """The propagation plan of the input graph itself (ops.edge_plan): `g` is an (x, edge_index, edge_weights) triple or a Graph
+    (anything with `.unfold()`); weighted iff edge_weights is given; the loops cover x.shape[0] ids (what GCNConv uses), or
+    edge_index.max() + 1 without x.  SnapshotGCNConv.forward(x, graph_plan(g)) is then the encoder's z of the un-augmented graph,
+    with the normalisation, the summation order and the bits of the views' plans."""
+    x, edge_index, edge_weights = g.unfold() if hasattr(g, "unfold") else g
+    return ops.edge_plan(edge_index, edge_weights, int(x.shape[0]) if x is not None else None, add_self_loops=True, fill_value=fill_value,
+                         normalize=True, directions=directions)
 
 
 class rLap:
@@ -310,6 +322,16 @@ class rLapDepths:
             return [graph(k) for k in range(K)]
         R = int(self.views)
         return [[graph(k * R + r) for k in range(K)] for r in range(R)]
+
+    def diffuse_plan(self, g, alpha: float = 0.2, eps: float = 1e-4, tol: float = 1e-10, directions: str = "both"):
+        """One propagation plan over all diffused snapshots of `diffuse`: straight from the (out, pptr) of the one ops.snapshot_ppr
+        call to ops.edge_list_plan(weighted=True) -- no slicing, no edge_index.  Layer i is snapshot i in pptr order (depth-major,
+        then view, as the rows are); the loops cover x.shape[0] ids when x is given, with this augmentor's fill_value."""
+        x, sc, ptr, num_nodes = self._snapshots(g)
+        out, pptr = ops.snapshot_ppr(sc, ptr, num_nodes, alpha=alpha, eps=eps, tol=tol)
+        n = int(x.shape[0]) if x is not None else int(num_nodes)
+        return ops.edge_list_plan(out, pptr, n, weighted=True, add_self_loops=True, fill_value=self.fill_value, normalize=True,
+                                  directions=directions)
 
     def relabelled(self, g):
         """The compact graph of every run and depth and its id map -- torch.unique + subgraph(relabel_nodes=True) of every snapshot

@@ -24,6 +24,7 @@
 #include "rlap_subgraph.h"
 #include "rlap_gcn.h"
 #include "rlap_plan.h"
+#include "rlap_edgeplan.h"
 #include "rlap_spmm_api.h"
 
 using namespace rlap;
@@ -1437,6 +1438,38 @@ int rlap_snapshot_plan_build(rlap_handle h, const double* d_sc, int64_t m, const
         const SnapshotPlanArgs a{g, flags, fill_value, d_plan, plan_bytes};
         SnapshotPlanReport rep;
         const int rc = snapshot_plan_build_run(h->stream, base, have, a, h_desc, &rep);
+        if (rc != RLAP_OK) *h_desc = rlap_plan_desc{};
+        if (h_info) {
+            h_info->entries = rep.entries; h_info->blocks = rep.blocks; h_info->chunked_lists_forward = rep.chunked[0];
+            h_info->chunked_lists_transposed = rep.chunked[1]; h_info->loops_removed = rep.loops_removed;
+            h_info->arena_bytes = (int64_t)need; h_info->host_syncs = rep.host_syncs;
+        }
+        return rc;
+    });
+}
+
+int rlap_edge_plan_build(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
+                         int64_t G, int64_t num_nodes, int flags, double fill_value, void* d_plan, size_t plan_bytes,
+                         rlap_plan_desc* h_desc, rlap_plan_info* h_info) {
+    if (h_info) *h_info = rlap_plan_info{};
+    if (!h_desc) return RLAP_E_BAD_ARG;
+    *h_desc = rlap_plan_desc{};
+    if (!d_plan || (reinterpret_cast<uintptr_t>(d_plan) & 15)) return RLAP_E_BAD_ARG;
+    if (flags & ~(RLAP_GCN_WEIGHTED | RLAP_GCN_SELF_LOOPS | RLAP_GCN_NORMALIZE | RLAP_PLAN_FORWARD | RLAP_PLAN_TRANSPOSED)) return RLAP_E_BAD_ARG;
+    if ((flags & RLAP_GCN_SELF_LOOPS) && !(fill_value > 0.0 && std::isfinite(fill_value))) return RLAP_E_BAD_ARG;
+    if (!(flags & (RLAP_PLAN_FORWARD | RLAP_PLAN_TRANSPOSED))) flags |= RLAP_PLAN_FORWARD | RLAP_PLAN_TRANSPOSED;
+    SnapshotSeg g{d_sc, m, d_ptr, S, d_node_ptr, G, num_nodes};
+    if (const int rc = snapshot_check(h, &g, 1)) return rc;
+    if (num_nodes >= INT32_MAX || (g.S / g.G) * num_nodes >= edgeplan::MAX_SLOTS) return RLAP_E_TOO_LARGE;   // (rlap_edgeplan.h: uint32 slot keys)
+    if (plan_bytes < snapshot_plan_buffer_bytes(g.m, g.S, g.G, g.N, flags)) return RLAP_E_BAD_ARG;
+    return snapshot_call(h, [&] { return edge_plan_build_bytes(g.m, g.S, g.G, g.N, flags); }, [&](void* base, size_t have, size_t need) -> int {
+        if (h->poison >= 0) {   // debug: the plan must not depend on what the arena or the caller's buffer held
+            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_plan, h->poison, plan_bytes, h->stream));
+        }
+        const SnapshotPlanArgs a{g, flags, fill_value, d_plan, plan_bytes};
+        SnapshotPlanReport rep;
+        const int rc = edge_plan_build_run(h->stream, base, have, a, h_desc, &rep);
         if (rc != RLAP_OK) *h_desc = rlap_plan_desc{};
         if (h_info) {
             h_info->entries = rep.entries; h_info->blocks = rep.blocks; h_info->chunked_lists_forward = rep.chunked[0];

@@ -1190,6 +1190,12 @@ def snapshot_plan(
     weighted and normalize) a weight that is not finite or <= 0 raise ValueError as for snapshot_gcn_norm.  One host synchronisation.
     `last_stats` then holds what the build did (rlap_plan_info: entries, blocks, chunked_lists_forward, chunked_lists_transposed,
     loops_removed, arena_bytes, host_syncs)."""
+    return _plan_build("rlap_snapshot_plan_build", sc, ptr, num_nodes, node_ptr, weighted, add_self_loops, fill_value, normalize, directions)
+
+
+def _plan_build(export: str, sc, ptr, num_nodes, node_ptr, weighted, add_self_loops, fill_value, normalize, directions,
+                extra_msg: Optional[str] = None, range_msg: Optional[str] = None) -> SnapshotPlan:
+    """What snapshot_plan and edge_list_plan share: the host checks, the size query, the buffer, the build `export`, the trimming."""
     p, np_ = _snapshot_tables(sc, ptr, num_nodes, node_ptr)
     fill = _real(fill_value, "fill_value", 0.0, float("inf"))
     if directions not in PLAN_DIRECTIONS:
@@ -1209,12 +1215,87 @@ def snapshot_plan(
             _raise(rc)
         buf = torch.empty(int(bound.value), dtype=torch.uint8, device=dev)
         desc = _lib.PlanDesc()
-        info = _snapshot_call("rlap_snapshot_plan_build", _lib.PlanInfo, rows, p, np_, n,
-                              (flags, fill, buf.data_ptr(), buf.numel(), ctypes.byref(desc)))
+        try:
+            info = _snapshot_call(export, _lib.PlanInfo, rows, p, np_, n, (flags, fill, buf.data_ptr(), buf.numel(), ctypes.byref(desc)),
+                                  extra_msg=extra_msg)
+        except ValueError as e:
+            if range_msg and str(e) == f"rlap: {_lib.status_string(_lib.E_INDEX_RANGE)}":
+                raise ValueError(str(e) + range_msg) from None
+            raise
         used = int(desc.plan_bytes)
         if 0 < used < buf.numel():   # (an input with loop rows, or few long lists: the tail is not in use)
             buf = buf[:used].clone() if 4 * used < 3 * buf.numel() else buf[:used]
         return SnapshotPlan(buf, desc, info.as_dict(), directions)
+
+
+def edge_list_plan(
+    rows: Tensor,
+    ptr: Union[Tensor, Sequence[int]],
+    num_nodes: int,
+    node_ptr: Optional[Union[Tensor, Sequence[int]]] = None,
+    weighted: bool = False,
+    add_self_loops: bool = True,
+    fill_value: float = 1.0,
+    normalize: bool = True,
+    directions: str = "both",
+) -> SnapshotPlan:
+    """snapshot_plan for a row table in ANY order: the (out, pptr) of snapshot_ppr, a snapshot_subgraph result, any (m, 3) table
+    [source, target, w] whose S segments (segment = layer * G + graph) hold their rows in whatever order.  Duplicate rows, directed
+    structure, loop rows and ids without rows are legal; nothing is coalesced.  The arguments are snapshot_plan's and so is the
+    result: a `SnapshotPlan` whose `.propagate`, autograd and SnapshotGCNConv work unchanged.
+
+    What the plan holds depends on a row's place in the input alone (rlap_amd/csrc/rlap_edgeplan.h): the list of target j is the
+    rows with target j in input order, the transposed list of source i the rows with source i in input order; deg[j] is summed over
+    j's list in the fixed order of snapshot_gcn_norm, the loop's weight (that of j's last loop row, or fill_value) last; an id
+    without incoming rows has the loop's weight alone, or degree 0 (coefficient 0) without loops.  For an input in the elimination
+    layout the buffer equals snapshot_plan's bit for bit.  The same input gives the same bits.
+
+    Malformed arguments raise ValueError before the device is touched; an id that is not an integer of its graph's range and (with
+    weighted and normalize) a weight that is not finite or <= 0 raise ValueError and say which.  One host synchronisation; `last_stats`
+    holds rlap_plan_info (`blocks`: the non-empty forward lists)."""
+    return _plan_build("rlap_edge_plan_build", rows, ptr, num_nodes, node_ptr, weighted, add_self_loops, fill_value, normalize, directions,
+                       extra_msg=" (with weighted and normalize: a weight is not finite or <= 0)",
+                       range_msg=" (an id of the rows is not an integer of its graph's range)")
+
+
+def edge_plan(
+    edge_index: Tensor,
+    edge_weight: Optional[Tensor] = None,
+    num_nodes: Optional[int] = None,
+    add_self_loops: bool = True,
+    fill_value: float = 1.0,
+    normalize: bool = True,
+    directions: str = "both",
+) -> SnapshotPlan:
+    """The plan of a plain graph: `edge_index` (2, E) integer, source row 0 and target row 1 (flow="source_to_target"), in any
+    order; one segment, one layer; weighted iff `edge_weight` (E,) is given; `num_nodes=None` means edge_index.max() + 1.  A PyG
+    batch is one block-diagonal graph.  plan.propagate(x)[0] is then GCNConv's A^ x of the graph itself, with the normalisation,
+    the summation order and the bits of the snapshots' plans -- see edge_list_plan.  The rows are formed in torch: a plan is built
+    once per graph."""
+    if not isinstance(edge_index, Tensor) or edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise ValueError("edge_index: a (2, E) integer tensor")
+    if edge_index.dtype.is_floating_point or edge_index.dtype.is_complex or edge_index.dtype == torch.bool:
+        raise ValueError(f"edge_index: an integer tensor, got {edge_index.dtype}")
+    E = int(edge_index.shape[1])
+    if edge_weight is not None:
+        if not isinstance(edge_weight, Tensor) or edge_weight.dim() != 1 or edge_weight.shape[0] != E:
+            raise ValueError(f"edge_weight: a ({E},) tensor, one weight per column of edge_index")
+        if not edge_weight.dtype.is_floating_point:
+            raise ValueError(f"edge_weight: a floating-point tensor, got {edge_weight.dtype}")
+    if num_nodes is not None:
+        n = _num_nodes(num_nodes)
+    fill = _real(fill_value, "fill_value", 0.0, float("inf"))
+    if directions not in PLAN_DIRECTIONS:
+        raise ValueError(f"directions: one of {sorted(PLAN_DIRECTIONS)}, got {directions!r}")
+    dev = _device_for(edge_index)
+    with torch.cuda.device(dev):
+        ei = edge_index.to(dev)
+        if num_nodes is None:
+            n = int(ei.max().item()) + 1 if E else 0
+        rows = torch.empty((E, 3), dtype=torch.float64, device=dev)
+        rows[:, 0], rows[:, 1] = ei[0], ei[1]
+        rows[:, 2] = edge_weight.detach().to(dev) if edge_weight is not None else 1.0
+    return edge_list_plan(rows, [0, E], n, None, edge_weight is not None, add_self_loops, fill, normalize, directions)
 
 
 def identity(a: Tensor) -> Tensor:

@@ -15,6 +15,11 @@ Medians of 5 after a warm-up, host clock around a synchronise; the five times ar
 the planned forward + transposed pair, the plan's bytes, the algorithmic bytes of k_pl_rows and the calls after which the plan has paid
 for itself, build time / (unplanned forward - planned forward).  --plan-only leaves the unplanned calls out (a profile of the planned
 kernels alone; also what runs against a library without the plan exports when it is absent).
+--edges times the plans of rows in any order instead: ops.edge_plan of the BA(1M, 10) input graph itself (20 M directed
+rows) against the torch pipeline for the same structure on the same tensors -- the gcn_norm formulation of 4.10 plus a stable sort by
+target into CSR arrays -- and ops.edge_list_plan of the six-snapshot elimination result against ops.snapshot_plan of the same rows
+(rlap_plan.hip is the parent's, unchanged), with the plan bytes and the planned products of both.
+    python tools/propagate_latency.py --edges --features 64
 """
 import argparse
 import json
@@ -159,6 +164,67 @@ def plan_figures(rec, sc, ptr, N, node_ptr, x, L, F, unplanned_ms, y, args):
     del plan, yp
 
 
+def torch_gcn_csr(ei, N):
+    """The torch pipeline an edge plan replaces, forward direction: add_remaining_self_loops + gcn_norm (DESIGN 4.10's formulation,
+    unit weights), then a stable sort by target into CSR arrays (crow, col, val)."""
+    ar = torch.arange(N, device=ei.device)
+    keep = ei[0] != ei[1]
+    src, dst = torch.cat([ei[0][keep], ar]), torch.cat([ei[1][keep], ar])
+    w = torch.ones(src.numel(), dtype=torch.float64, device=ei.device)
+    deg = torch.zeros(N, dtype=torch.float64, device=ei.device).index_add_(0, dst, w)
+    dis = deg.pow(-0.5)
+    dis[dis == float("inf")] = 0.0
+    val = dis[src] * w * dis[dst]
+    order = torch.argsort(dst, stable=True)
+    crow = torch.zeros(N + 1, dtype=torch.int64, device=ei.device)
+    crow[1:] = torch.cumsum(torch.bincount(dst, minlength=N), 0)
+    return crow, src[order], val[order]
+
+
+def run_edges(F, args, fh):
+    n, m, _, K = GRAPHS["ba1m"]
+    ei = graphs.barabasi_albert(n, m, 1).cuda()
+    x = torch.randn(n, F, dtype=torch.float32, generator=torch.Generator().manual_seed(F)).cuda()
+    rec = {"graph": "ba1m input graph", "F": F, "rows": int(ei.shape[1])}
+    tb, tsb, plan = timed(lambda: ops.edge_plan(ei, None, n), args.reps)
+    rows = torch.empty((ei.shape[1], 3), dtype=torch.float64, device="cuda")
+    rows[:, 0], rows[:, 1], rows[:, 2] = ei[0], ei[1], 1.0
+    tl, tsl, _ = timed(lambda: ops.edge_list_plan(rows, [0, int(rows.shape[0])], n), args.reps)
+    del rows
+    tp, tsp, y = timed(lambda: plan.propagate(x), args.reps)
+    tp2, tsp2, _ = timed(lambda: plan.propagate(plan.propagate(x), transpose=True), args.reps)
+    rec.update({"edge_plan_ms": round(tb, 3), "edge_plan_runs_ms": tsb, "edge_list_plan_ms": round(tl, 3), "edge_list_plan_runs_ms": tsl,
+                "plan_bytes": plan.nbytes, "planned_forward_ms": round(tp, 3), "planned_forward_runs_ms": tsp,
+                "planned_forward_transpose_ms": round(tp2, 3), "planned_forward_transpose_runs_ms": tsp2})
+    if not args.no_torch:
+        tt, tst, (crow, col, val) = timed(lambda: torch_gcn_csr(ei, n), args.reps)
+        want = torch.zeros(n, F, dtype=torch.float64, device="cuda").index_add_(
+            0, torch.repeat_interleave(torch.arange(n, device="cuda"), crow[1:] - crow[:-1]), val[:, None] * x[col].double())
+        rec.update({"torch_gcn_norm_csr_ms": round(tt, 3), "torch_gcn_norm_csr_runs_ms": tst, "torch_over_edge_plan": round(tt / tb, 3),
+                    "max_abs_diff_to_torch": float((y[0].double() - want).abs().max())})
+        del crow, col, val, want
+    emit(rec, fh)
+    del plan, y, ei
+    torch.cuda.empty_cache()
+    # the elimination result propagate_latency already uses: the same rows through both builds
+    ei = graphs.barabasi_albert(n, m, 1).cuda()
+    sc, ptr = ops.approximate_cholesky_depths(ei, None, n, [n // 8, n // 4, n // 2], "random", "asc", views=K, seed=1, return_device="same")
+    del ei
+    rec = {"graph": "ba1m elimination result", "F": F, "snapshots": ptr.numel() - 1, "rows": int(sc.shape[0])}
+    ts_, tss, splan = timed(lambda: ops.snapshot_plan(sc, ptr, n), args.reps)
+    te, tse, eplan = timed(lambda: ops.edge_list_plan(sc, ptr, n), args.reps)
+    rec.update({"snapshot_plan_ms": round(ts_, 3), "snapshot_plan_runs_ms": tss, "edge_list_plan_ms": round(te, 3), "edge_list_plan_runs_ms": tse,
+                "edge_over_snapshot_build": round(te / ts_, 3), "snapshot_plan_bytes": splan.nbytes, "edge_plan_bytes": eplan.nbytes})
+    for name, pl in (("snapshot", splan), ("edge", eplan)):
+        tp, tsp, y = timed(lambda: pl.propagate(x), args.reps)
+        tp2, tsp2, _ = timed(lambda: pl.propagate(pl.propagate(x), transpose=True), args.reps)
+        rec.update({f"{name}_planned_forward_ms": round(tp, 3), f"{name}_planned_forward_runs_ms": tsp,
+                    f"{name}_planned_forward_transpose_ms": round(tp2, 3), f"{name}_planned_forward_transpose_runs_ms": tsp2})
+    rec["products_equal"] = bool(torch.equal(splan.propagate(x), eplan.propagate(x))
+                                 and torch.equal(splan.propagate(x, transpose=True), eplan.propagate(x, transpose=True)))
+    emit(rec, fh)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", default="ba1m,c5")
@@ -167,9 +233,14 @@ def main():
     ap.add_argument("--no-torch", action="store_true", help="time the calls alone")
     ap.add_argument("--plan", action="store_true", help="also build a propagation plan and time the planned products")
     ap.add_argument("--plan-only", action="store_true", help="the planned products alone")
+    ap.add_argument("--edges", action="store_true", help="the plans of rows in any order (ops.edge_plan / edge_list_plan) instead")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file")
     args = ap.parse_args()
     fh = open(args.out, "a") if args.out else None
+    if args.edges:
+        for F in args.features.split(","):
+            run_edges(int(F), args, fh)
+        return
     for g in args.graphs.split(","):
         for F in args.features.split(","):
             run(g, int(F), args, fh)
