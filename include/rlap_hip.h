@@ -485,6 +485,46 @@ int rlap_edge_plan_build(rlap_handle h, const double* d_sc, int64_t m, const int
                          int64_t G, int64_t num_nodes, int flags, double fill_value, void* d_plan, size_t plan_bytes,
                          rlap_plan_desc* h_desc, rlap_plan_info* h_info);
 
+/* Per-graph readout of batched node embeddings: y[l, g, :] = the sum (or mean) of x[l, i, :] over the ids i of graph g,
+ * [node_ptr[g], node_ptr[g+1]) -- what global_add_pool(z, batch) does after every GIN layer of a graph-level step, without float
+ * atomics and in a fixed order.
+ *   d_x, L, num_nodes, F : the embeddings (L, num_nodes, F), row-major, float64 or (RLAP_READOUT_X_F32) float32; L >= 0, F >= 1
+ *   d_node_ptr, G        : [G+1] offsets on the device, G >= 1: non-decreasing from 0 to num_nodes (the caller's to check)
+ *   flags                : RLAP_READOUT_MEAN divides the sum by the graph's number of ids; RLAP_READOUT_X_F32
+ *   d_y                  : (L, G, F) of d_x's type; every element is written
+ *   h_info               : (nullable) what the call did
+ * One element is the rule of rlap_amd/csrc/rlap_spmm.h on the list of the graph's ids in increasing order, every coefficient 1.0, no
+ * loop term: float64 terms, chunks of 256 ids summed from 0 in id order, the chunk sums added to 0 in chunk order; the mean is that
+ * sum divided once, in float64, by the count; an empty graph gives exactly 0 for both; a float32 result is the float64 value rounded
+ * once; values that are not finite pass through as the arithmetic gives them.  So the same input gives the same bits, and a graph's
+ * result does not depend on L, on F's tiling, on the other graphs of the call or on what d_y or the arena held.
+ * The backward call is the gradient with respect to d_x: d_gx[l, i, :] = d_gy[l, g(i), :], for the mean divided by the count of g(i)
+ * (one float64 division, rounded once for float32); d_gy is (L, G, F), d_gx (L, num_nodes, F), every element of it is written.
+ * Neither call synchronises with the host.  The work of the forward call is mapped to (graph, chunk) on the device; its grid is sized
+ * from the bound ceil(num_nodes / 256) + G chunks.  h_info->chunks and ->chunked_graphs (graphs of more than 256 ids, whose chunk
+ * sums go through the arena) are EXACT when G == 1, where the host knows them from num_nodes; otherwise they are the host's BOUNDS,
+ * ceil(num_nodes / 256) + G and min(G, num_nodes / 257): the table is never read back.  As for the plans, the table is the caller's
+ * to get right: the kernels clamp what they read from it before it becomes an address, so a table that is not well formed gives wrong
+ * numbers, never an access out of range.
+ * A negative count, F < 1, G < 1, a null pointer or a flag that is not this call's: RLAP_E_BAD_ARG.  F, L * num_nodes, L * G or the
+ * elements of d_x or d_y beyond the limits of rlap_snapshot_propagate: RLAP_E_TOO_LARGE.  Scratch of the forward call from the arena
+ * (RLAP_E_WORKSPACE when a caller-provided one is too small, rlap_workspace_needed() saying how much). */
+enum { RLAP_READOUT_MEAN = 1, RLAP_READOUT_X_F32 = 32 };
+typedef struct {
+    int64_t rows;             /* num_nodes                                                            */
+    int64_t graphs;           /* G                                                                    */
+    int64_t chunks;           /* chunks of the call: exact when G == 1, else the bound                */
+    int64_t chunked_graphs;   /* graphs of more than one chunk: exact when G == 1, else the bound     */
+    int64_t arena_bytes;      /* scratch bytes of the call                                            */
+    int32_t host_syncs;       /* host synchronisations of the call: 0                                 */
+    int32_t pad;
+} rlap_readout_info;
+
+int rlap_graph_readout(rlap_handle h, const void* d_x, int64_t L, int64_t num_nodes, int64_t F, const int64_t* d_node_ptr, int64_t G,
+                       int flags, void* d_y, rlap_readout_info* h_info);
+int rlap_graph_readout_backward(rlap_handle h, const void* d_gy, int64_t L, int64_t num_nodes, int64_t F, const int64_t* d_node_ptr,
+                                int64_t G, int flags, void* d_gx, rlap_readout_info* h_info);
+
 /* The op with the step BEFORE the path fused in (scripts/node_shared.py:326-327,
  * scripts/augmentor_benchmarks.py:77-78):
  *   symmetrize != 0 : the input holds every undirected edge in one or both directions; (b,a) is

@@ -22,6 +22,7 @@ EXPORTS = [
     "rlap_approx_chol_views_depths", "rlap_snapshot_stats", "rlap_snapshot_ppr", "rlap_snapshot_subgraph",
     "rlap_snapshot_gcn_norm", "rlap_snapshot_propagate",
     "rlap_snapshot_plan_bytes", "rlap_snapshot_plan_build", "rlap_snapshot_plan_propagate", "rlap_edge_plan_build",
+    "rlap_graph_readout", "rlap_graph_readout_backward",
 ]
 
 E_INDEX_RANGE = 2   # RLAP_E_INDEX_RANGE
@@ -39,6 +40,8 @@ SPMM_TRANSPOSE, SPMM_X_F32, SPMM_X_PER_LAYER = 16, 32, 64
 # rlap_snapshot_plan_build flags (beside the first three of rlap_snapshot_gcn_norm): the directions to build
 PLAN_FORWARD, PLAN_TRANSPOSED = 256, 512
 PLAN_MAGIC = 0x504C414E   # rlap_plan_desc.magic of a successful build
+# rlap_graph_readout flags
+READOUT_MEAN, READOUT_X_F32 = 1, 32
 
 # rlap_stats.elim_kernel
 KERNEL_NONE, KERNEL_ROUND, KERNEL_FLOW = 0, 1, 2
@@ -132,6 +135,14 @@ class PlanInfo(_Report):
     ]
 
 
+class ReadoutInfo(_Report):
+    """rlap_readout_info (include/rlap_hip.h)."""
+    _fields_ = [
+        ("rows", ctypes.c_int64), ("graphs", ctypes.c_int64), ("chunks", ctypes.c_int64), ("chunked_graphs", ctypes.c_int64),
+        ("arena_bytes", ctypes.c_int64), ("host_syncs", ctypes.c_int32), ("pad", ctypes.c_int32),
+    ]
+
+
 def load():
     """dlopen the library and declare prototypes. Raises if it is not built."""
     global _lib
@@ -192,6 +203,10 @@ def load():
     lib.rlap_edge_plan_build.argtypes = lib.rlap_snapshot_plan_build.argtypes
     lib.rlap_snapshot_plan_propagate.restype = ci
     lib.rlap_snapshot_plan_propagate.argtypes = [vp, vp, ctypes.POINTER(PlanDesc), ci, vp, i64, vp, ctypes.POINTER(SpmmInfo)]
+    lib.rlap_graph_readout.restype = ci
+    lib.rlap_graph_readout.argtypes = [vp, vp, i64, i64, i64, vp, i64, ci, vp, ctypes.POINTER(ReadoutInfo)]
+    lib.rlap_graph_readout_backward.restype = ci
+    lib.rlap_graph_readout_backward.argtypes = lib.rlap_graph_readout.argtypes
     lib.rlap_approx_chol_views.restype = ci
     lib.rlap_approx_chol_views.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, vp, ci, ci, vp, u64, vp, i64, vp,
                                            ctypes.POINTER(Stats)]

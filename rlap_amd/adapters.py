@@ -14,6 +14,10 @@ Mirrors of the reference's L2 adapters that keep everything on the GPU:
   * `.snapshots(g)` on rLap / rLapViews / rLapDepths: the same one elimination call as a `Snapshots` holder, whose `.propagate(x)`
                   is the sparse product of a GCN layer for all views at once (ops.snapshot_propagate); `SnapshotGCNConv` is the
                   layer built on it
+  * graph-level steps (scripts/graph_shared.py): `node_ptr_of(batch)` turns a PyG `batch` vector into the `node_ptr` of a batch;
+                  `.snapshots(g, node_ptr=)` on rLapViews / rLapDepths eliminates every graph of the batch in the one call;
+                  `Snapshots.aggregate(x)` is GIN's plain neighbour sum, `SnapshotGINConv` the layer on it, and
+                  `Snapshots.readout(z)` the per-graph sum of global_add_pool (ops.graph_readout)
   * `rLapChain` -- the chain of scripts/rlap_vc_spectral.py: eliminate, relabel the survivors 0..k-1, eliminate again
 PyGCL / DGL are optional: with them installed the classes return their graph types,
 without them a small named tuple with the same fields.
@@ -46,6 +50,7 @@ class Snapshots:
     def __init__(self, sc, ptr, num_nodes: int, node_ptr=None, weighted: bool = False, fill_value: float = 1.0):
         self.sc, self.ptr, self.num_nodes, self.node_ptr = sc, ptr, int(num_nodes), node_ptr
         self.weighted, self.fill_value = bool(weighted), fill_value
+        self._table = None   # (the readout's ops.GraphTable, made on first use)
 
     @property
     def layers(self) -> int:
@@ -55,6 +60,20 @@ class Snapshots:
     def propagate(self, x, transpose: bool = False):
         return ops.snapshot_propagate(self.sc, self.ptr, self.num_nodes, x, node_ptr=self.node_ptr, weighted=self.weighted,
                                       add_self_loops=True, fill_value=self.fill_value, normalize=True, transpose=transpose)
+
+    def aggregate(self, x, transpose: bool = False):
+        """GIN's aggregation for every layer at once: y[l, i] = the sum of x[j] over the neighbours j of i in snapshot l -- the
+        product without self loops and without the normalisation (weights kept iff the holder's `weighted`)."""
+        return ops.snapshot_propagate(self.sc, self.ptr, self.num_nodes, x, node_ptr=self.node_ptr, weighted=self.weighted,
+                                      add_self_loops=False, fill_value=self.fill_value, normalize=False, transpose=transpose)
+
+    def readout(self, z, reduce: str = "sum"):
+        """global_add_pool (reduce="mean": global_mean_pool) of node embeddings z, (n, F) or (L, n, F), over the holder's batch:
+        ops.graph_readout with its `node_ptr`, (G, F) or (L, G, F).  Without a `node_ptr` the whole id range is one graph.  The
+        table is checked and copied to the device once and kept on the holder."""
+        if self._table is None:
+            self._table = ops.GraphTable([0, self.num_nodes] if self.node_ptr is None else self.node_ptr, self.num_nodes)
+        return ops.graph_readout(z, self._table, reduce=reduce)
 
     def plan(self, directions: str = "both") -> "PlannedSnapshots":
         """The same snapshots served by one propagation plan (ops.snapshot_plan), built on first use: for the six to twelve
@@ -70,6 +89,7 @@ class PlannedSnapshots:
         if directions not in ops.PLAN_DIRECTIONS:
             raise ValueError(f"directions: one of {sorted(ops.PLAN_DIRECTIONS)}, got {directions!r}")
         self.snapshots, self.directions, self.snapshot_plan = snapshots, directions, None
+        self.aggregate_plan = None   # (the second plan, of `aggregate`: no loops, no normalisation; None before its first use)
 
     @property
     def layers(self) -> int:
@@ -85,6 +105,49 @@ class PlannedSnapshots:
             self.snapshot_plan = ops.snapshot_plan(s.sc, s.ptr, s.num_nodes, node_ptr=s.node_ptr, weighted=s.weighted, add_self_loops=True,
                                                    fill_value=s.fill_value, normalize=True, directions=self.directions)
         return self.snapshot_plan.propagate(x, transpose=transpose)
+
+    def aggregate(self, x, transpose: bool = False):
+        """`Snapshots.aggregate` over a second plan with its flags (no self loops, no normalisation), built on first use."""
+        if self.aggregate_plan is None:
+            s = self.snapshots
+            self.aggregate_plan = ops.snapshot_plan(s.sc, s.ptr, s.num_nodes, node_ptr=s.node_ptr, weighted=s.weighted, add_self_loops=False,
+                                                    fill_value=s.fill_value, normalize=False, directions=self.directions)
+        return self.aggregate_plan.propagate(x, transpose=transpose)
+
+    def readout(self, z, reduce: str = "sum"):
+        return self.snapshots.readout(z, reduce=reduce)
+
+
+def node_ptr_of(batch, num_graphs: Optional[int] = None) -> torch.Tensor:
+    """The `node_ptr` of a PyG `batch` vector (batch[i] = the graph of node i, sorted, as DataLoader collates it): an int64 CPU
+    table [G+1] with node_ptr[g] the first node of graph g.  G is `num_graphs`, or batch.max() + 1.  bincount and cumsum on
+    batch's device, then ONE read by the host.  A vector that is not sorted, holds a negative entry or an entry >= num_graphs
+    raises ValueError."""
+    b = torch.as_tensor(batch)
+    if b.dim() != 1 or b.dtype.is_floating_point or b.dtype.is_complex or b.dtype == torch.bool:
+        raise ValueError("batch: a 1-D vector of graph numbers")
+    if num_graphs is not None and (isinstance(num_graphs, bool) or not hasattr(num_graphs, "__index__") or num_graphs.__index__() < 0):
+        raise ValueError(f"num_graphs: a non-negative integer, got {num_graphs!r}")
+    G = None if num_graphs is None else num_graphs.__index__()
+    b = b.to(torch.int64)
+    bad = (b[1:] < b[:-1]).any() | (b[:1] < 0).any()
+    counts = torch.bincount(b.clamp_min(0), minlength=G or 0)
+    table = torch.cat([bad.reshape(1).to(torch.int64), torch.zeros(1, dtype=torch.int64, device=b.device), counts.cumsum(0)]).cpu()
+    if int(table[0]):
+        raise ValueError("batch: not sorted (node_ptr needs the nodes of a graph side by side), or a negative entry")
+    if G is not None and table.numel() - 2 > G:
+        raise ValueError(f"batch: an entry >= num_graphs ({G})")
+    return table[1:].contiguous()
+
+
+def _batch_tables(node_ptr, x, fracs):
+    """`node_ptr` checked (ops._ptr_table), the batch's num_nodes and, per fraction, int(frac * n_g) for every graph g."""
+    np_ = ops._ptr_table(node_ptr, "node_ptr", 0, None)
+    n = int(np_[-1])
+    if x is not None and int(x.shape[0]) != n:
+        raise ValueError(f"x: {int(x.shape[0])} rows, node_ptr[-1] is {n}")
+    sizes = (np_[1:] - np_[:-1]).tolist()
+    return np_, n, [[int(f * n_g) for n_g in sizes] for f in fracs]
 
 
 def _snapshots_of(x, sc, ptr, num_nodes, keep_weights, fill_value):
@@ -117,6 +180,37 @@ class SnapshotGCNConv(torch.nn.Module):
     def forward(self, x, snapshots: Snapshots):
         y = snapshots.propagate(x @ self.weight)
         return y if self.bias is None else y + self.bias
+
+
+class SnapshotGINConv(torch.nn.Module):
+    """GINConv for all views of a call at once: forward(x, snapshots) = nn((1 + eps) * x + snapshots.aggregate(x)), an
+    (L, n, out) tensor for the L layers of `snapshots`.  x is (n, F), shared by the layers (the first GIN layer of every view), or
+    (L, n, F) (the later ones); `nn` is any module mapping (..., F) to (..., out), the MLP of scripts/graph_shared.py.  `eps` is a
+    parameter when `train_eps` is set, else a buffer.  The neighbour sum is ops.snapshot_propagate without loops and without the
+    normalisation, in its fixed order; gradients reach nn, eps and x.  `snapshots` is taken by duck typing: anything with
+    `.aggregate(x)` and the (L, n, F) result serves -- a `Snapshots`, or its `.plan()`.  (Unpinned: PyG is not installed here; this
+    restates its published semantics -- x_i' = nn((1 + eps) x_i + sum_j x_j) -- not a run of it.)"""
+
+    def __init__(self, nn: torch.nn.Module, eps: float = 0.0, train_eps: bool = False):
+        super().__init__()
+        self.nn, self.initial_eps = nn, float(eps)
+        if train_eps:
+            self.eps = torch.nn.Parameter(torch.empty(()))
+        else:
+            self.register_buffer("eps", torch.empty(()))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        with torch.no_grad():
+            self.eps.fill_(self.initial_eps)
+        for m in self.nn.modules():
+            if m is not self.nn and hasattr(m, "reset_parameters"):
+                m.reset_parameters()
+        if hasattr(self.nn, "reset_parameters"):
+            self.nn.reset_parameters()
+
+    def forward(self, x, snapshots):
+        return self.nn((1 + self.eps).to(x.dtype) * x + snapshots.aggregate(x))
 
 
 def graph_plan(g, fill_value: float = 1.0, directions: str = "both"):
@@ -216,10 +310,23 @@ class rLapViews:
                                                  seed=self.seed, return_device="same", mode=self.mode)
         return x, sc, ptr, num_nodes
 
-    def snapshots(self, g) -> Snapshots:
-        """The one elimination call of `augment` as a `Snapshots` holder: layer k is view k."""
-        x, sc, ptr, num_nodes = self._call(g)
-        return _snapshots_of(x, sc, ptr, num_nodes, self.keep_weights, self.fill_value)
+    def snapshots(self, g, node_ptr=None) -> Snapshots:
+        """The one elimination call of `augment` as a `Snapshots` holder: layer k is view k.
+
+        `node_ptr` ([G+1] offsets, node_ptr_of(batch)): g is a batch of G graphs, graph j owning the ids [node_ptr[j],
+        node_ptr[j+1]).  The one call then eliminates every graph on its own (ops.approximate_cholesky_views(node_ptr=)): view k
+        removes int(fracs[k] * n_j) vertices of graph j, n_j its node count -- a (K, G) table, kept as `num_remove` -- and the holder
+        keeps `node_ptr`, so `.readout(z)` pools per graph.  This DIFFERS from scripts/graph_shared.py, which hands the disjoint
+        union of the batch to the augmentor as ONE graph with one global count int(frac * num_nodes): there a graph of the batch
+        may lose any share of its vertices, here each loses its own fraction."""
+        if node_ptr is None:
+            x, sc, ptr, num_nodes = self._call(g)
+            return _snapshots_of(x, sc, ptr, num_nodes, self.keep_weights, self.fill_value)
+        x, edge_index, edge_weights = g.unfold() if hasattr(g, "unfold") else g
+        np_, n, self.num_remove = _batch_tables(node_ptr, x, self.fracs)
+        sc, ptr = ops.approximate_cholesky_views(edge_index, edge_weights, n, self.num_remove, self.o_v, self.o_n, node_ptr=np_,
+                                                 seed=self.seed, return_device="same", mode=self.mode)
+        return Snapshots(sc, ptr, n, np_, self.keep_weights, self.fill_value)
 
     def augment(self, g):
         x, sc, ptr, num_nodes = self._call(g)
@@ -284,11 +391,25 @@ class rLapDepths:
                                                   seed=self.seed, return_device="same", mode=self.mode, **extra)
         return x, sc, ptr, num_nodes
 
-    def snapshots(self, g) -> Snapshots:
+    def snapshots(self, g, node_ptr=None) -> Snapshots:
         """The one elimination call of `augment` as a `Snapshots` holder: layer k * R + r is depth k of run r (depth-major, then
-        view, as the rows are)."""
-        x, sc, ptr, num_nodes = self._snapshots(g)
-        return _snapshots_of(x, sc, ptr, num_nodes, self.keep_weights, self.fill_value)
+        view, as the rows are).
+
+        `node_ptr` ([G+1] offsets, node_ptr_of(batch)): g is a batch of G graphs and the one call eliminates every graph on its
+        own (ops.approximate_cholesky_depths(node_ptr=)): depth k removes int(fracs[k] * n_j) vertices of graph j, n_j its node
+        count -- a (D, R, G) table, kept as `num_remove` -- and the holder keeps `node_ptr`.  This DIFFERS from
+        scripts/graph_shared.py, which eliminates the disjoint union of the batch as ONE graph with one global count
+        int(frac * num_nodes)."""
+        if node_ptr is None:
+            x, sc, ptr, num_nodes = self._snapshots(g)
+            return _snapshots_of(x, sc, ptr, num_nodes, self.keep_weights, self.fill_value)
+        x, edge_index, edge_weights = g.unfold() if hasattr(g, "unfold") else g
+        np_, n, table = _batch_tables(node_ptr, x, self.fracs)
+        R = 1 if self.views is None else int(self.views)
+        self.num_remove = [[row] * R for row in table]
+        sc, ptr = ops.approximate_cholesky_depths(edge_index, edge_weights, n, self.num_remove, self.o_v, self.o_n, node_ptr=np_, views=R,
+                                                  seed=self.seed, return_device="same", mode=self.mode)
+        return Snapshots(sc, ptr, n, np_, self.keep_weights, self.fill_value)
 
     def stats(self, g, weighted: bool = False, tol: float = 1e-10, max_iter: int = 1000):
         """The three lists scripts/rlap_vc_spectral.py records per snapshot (get_rlap_sc_stats: max_sv, num_unique_nodes, num_edges)

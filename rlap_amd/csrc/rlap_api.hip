@@ -26,6 +26,9 @@
 #include "rlap_plan.h"
 #include "rlap_edgeplan.h"
 #include "rlap_spmm_api.h"
+#include "rlap_spmm.h"
+#include "rlap_readout.h"
+#include "rlap_readout_api.h"
 
 using namespace rlap;
 
@@ -1518,6 +1521,52 @@ int rlap_snapshot_plan_propagate(rlap_handle h, const void* d_plan, const rlap_p
             h_info->arena_bytes = (int64_t)need; h_info->host_syncs = 0;
         }
         return rc;
+    });
+}
+
+namespace {
+
+// what both readout exports check, and what the host knows of the call without reading the table
+int readout_check(rlap_handle h, const void* d_in, int64_t L, int64_t N, int64_t F, const int64_t* d_node_ptr, int64_t G, int flags,
+                  void* d_out, rlap_readout_info* h_info) {
+    if (h_info) *h_info = rlap_readout_info{};
+    if (!h || !d_node_ptr || L < 0 || N < 0 || F < 1 || G < 1) return RLAP_E_BAD_ARG;
+    if (flags & ~(RLAP_READOUT_MEAN | RLAP_READOUT_X_F32)) return RLAP_E_BAD_ARG;
+    if (F > SPMM_MAX_F || G >= SPMM_MAX_ELEMS || N >= SPMM_MAX_ELEMS || L >= SPMM_MAX_ELEMS) return RLAP_E_TOO_LARGE;
+    if (L * N >= SPMM_MAX_ELEMS || L * N * F >= SPMM_MAX_ELEMS || L * G >= SPMM_MAX_ELEMS || L * G * F >= SPMM_MAX_ELEMS) return RLAP_E_TOO_LARGE;
+    if ((L * N * F > 0 && !d_in) || (L * G * F > 0 && !d_out)) return RLAP_E_BAD_ARG;   // (either of them is x or y)
+    if (h_info) {
+        h_info->rows = N; h_info->graphs = G;
+        h_info->chunks = G == 1 ? spmm::num_chunks(N) : readout::chunk_bound(N, G);
+        h_info->chunked_graphs = G == 1 ? (N > spmm::CHUNK ? 1 : 0) : readout::chunked_bound(N, G);
+    }
+    return RLAP_OK;
+}
+
+}  // namespace
+
+int rlap_graph_readout(rlap_handle h, const void* d_x, int64_t L, int64_t num_nodes, int64_t F, const int64_t* d_node_ptr, int64_t G,
+                       int flags, void* d_y, rlap_readout_info* h_info) {
+    if (const int rc = readout_check(h, d_x, L, num_nodes, F, d_node_ptr, G, flags, d_y, h_info)) return rc;
+    const ReadoutArgs a{d_x, L, num_nodes, F, d_node_ptr, G, flags, d_y};
+    return snapshot_call(h, [&] { return readout_bytes(L, num_nodes, F, G); }, [&](void* base, size_t have, size_t need) -> int {
+        if (h->poison >= 0) {   // debug: the result must not depend on what the arena or the result buffer held
+            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
+            if (L * G * F > 0) RLAP_HIPCHK(hipMemsetAsync(d_y, h->poison, (size_t)(L * G * F) * ((flags & RLAP_READOUT_X_F32) ? 4 : 8), h->stream));
+        }
+        if (h_info) h_info->arena_bytes = (int64_t)need;
+        return readout_run(h->stream, base, have, a);
+    });
+}
+
+int rlap_graph_readout_backward(rlap_handle h, const void* d_gy, int64_t L, int64_t num_nodes, int64_t F, const int64_t* d_node_ptr,
+                                int64_t G, int flags, void* d_gx, rlap_readout_info* h_info) {
+    if (const int rc = readout_check(h, d_gx, L, num_nodes, F, d_node_ptr, G, flags, const_cast<void*>(d_gy), h_info)) return rc;
+    const ReadoutArgs a{d_gy, L, num_nodes, F, d_node_ptr, G, flags, d_gx};
+    return snapshot_call(h, [&] { return (size_t)0; }, [&](void*, size_t, size_t) -> int {   // (no scratch: the gather reads the table itself)
+        if (h->poison >= 0 && L * num_nodes * F > 0)
+            RLAP_HIPCHK(hipMemsetAsync(d_gx, h->poison, (size_t)(L * num_nodes * F) * ((flags & RLAP_READOUT_X_F32) ? 4 : 8), h->stream));
+        return readout_backward_run(h->stream, a);
     });
 }
 

@@ -1077,6 +1077,120 @@ def snapshot_propagate(
     return _propagate(sc, p, np_, int(num_nodes), x, L, per_layer, *call[6:])
 
 
+READOUT_REDUCE = {"sum": 0, "mean": _lib.READOUT_MEAN}
+
+
+class GraphTable:
+    """The `node_ptr` of a batch as graph_readout takes it, checked once: `host` the int64 CPU table (non-decreasing from 0 to
+    `num_nodes`), `graphs` its G, `chunks` and `chunked_graphs` what rlap_readout_info reports as bounds, counted exactly here
+    (rlap_amd/csrc/rlap_readout.h: chunks of 256 ids, graphs of more than one chunk).  `on(device)` is the device copy, made once
+    per device and kept.  A holder that reads out after every layer (adapters.Snapshots.readout) keeps one of these."""
+
+    def __init__(self, node_ptr, num_nodes: int):
+        self.num_nodes = _num_nodes(num_nodes)
+        self.host = _ptr_table(node_ptr, "node_ptr", 0, self.num_nodes)
+        self.graphs = self.host.numel() - 1
+        counts = self.host[1:] - self.host[:-1]
+        self.chunks = int(((counts + 255) // 256).sum())
+        self.chunked_graphs = int((counts > 256).sum())
+        self._dev = {}
+
+    def on(self, device) -> Tensor:
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = self.host.to(device)
+        return self._dev[key]
+
+
+def _readout_args(x, node_ptr, reduce):
+    """Host-side checks of graph_readout, made before the device is touched: (table, flags without the type)."""
+    if not isinstance(x, Tensor) or x.dim() not in (2, 3):
+        raise ValueError("x: a (num_nodes, F) or (layers, num_nodes, F) tensor")
+    if x.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"x: torch.float32 or torch.float64, got {x.dtype}")
+    if x.shape[-1] < 1:
+        raise ValueError("x: at least one feature column")
+    if not isinstance(reduce, str) or reduce not in READOUT_REDUCE:
+        raise ValueError(f"reduce: one of {sorted(READOUT_REDUCE)}, got {reduce!r}")
+    n = int(x.shape[-2])
+    if isinstance(node_ptr, GraphTable):
+        if node_ptr.num_nodes != n:
+            raise ValueError(f"node_ptr[-1] ({node_ptr.num_nodes}) must equal {n}")
+        table = node_ptr
+    else:
+        table = GraphTable(node_ptr, n)
+    return table, READOUT_REDUCE[reduce]
+
+
+def _readout(export: str, x: Tensor, table: GraphTable, flags: int, rows_out: int) -> Tensor:
+    """One rlap_graph_readout / _backward call: x is (L, rows, F) and checked, the result (L, rows_out, F) on the library's device."""
+    global last_stats
+    dev = _device_for(x)
+    flags |= _lib.READOUT_X_F32 if x.dtype == torch.float32 else 0
+    with torch.cuda.device(dev):
+        d_x = x.detach().to(device=dev).contiguous()
+        L, F, N, G = int(d_x.shape[0]), int(d_x.shape[2]), table.num_nodes, table.graphs
+        out = torch.empty((L, rows_out, F), dtype=d_x.dtype, device=dev)
+        d_np = table.on(dev)
+        lib, hobj = _handle_obj(dev)
+        fn = getattr(lib, export)
+        info = _lib.ReadoutInfo()
+        st = _lib.Stats()
+        rc = _run(hobj, dev, 0, None, G, False, lambda: fn(
+            hobj.ptr, d_x.data_ptr() if d_x.numel() else None, L, N, F, d_np.data_ptr(), G, flags,
+            out.data_ptr() if out.numel() else None, ctypes.byref(info)), st)
+    if rc in (1, 2, 3):
+        raise ValueError(f"rlap: {_lib.status_string(rc)}")
+    if rc != 0:
+        _raise(rc)
+    last_stats = info.as_dict()
+    last_stats.update(chunks=table.chunks, chunked_graphs=table.chunked_graphs)   # (exact: this host has read the table)
+    return out
+
+
+class _Readout(torch.autograd.Function):
+    """y = the per-graph sum (mean) of x; the gradient with respect to x is the gather of the backward export."""
+
+    @staticmethod
+    def forward(ctx, x, table, flags):
+        ctx.call = (table, flags)
+        return _readout("rlap_graph_readout", x, table, flags, table.graphs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        table, flags = ctx.call
+        return _readout("rlap_graph_readout_backward", gy.contiguous(), table, flags, table.num_nodes), None, None
+
+
+def graph_readout(x: Tensor, node_ptr: Union[Tensor, Sequence[int], GraphTable], reduce: str = "sum") -> Tensor:
+    """The readout of a batch of graphs: y[g] = the sum (reduce="mean": the mean) of the rows x[i] of graph g's nodes,
+    node_ptr[g] <= i < node_ptr[g+1] -- global_add_pool(z, batch) of the graph-level training step (scripts/graph_shared.py: after
+    every GIN layer), without float atomics and in a fixed order.
+
+      x        : (num_nodes, F), returning (G, F), or (L, num_nodes, F) -- the embeddings of L views at once -- returning (L, G, F);
+                 float32 or float64, on any device (moved to the library's)
+      node_ptr : [G+1] offsets, non-decreasing from 0 to num_nodes (adapters.node_ptr_of turns a PyG `batch` vector into one),
+                 checked on the host; or a GraphTable, which keeps the check and the device copy for the next call
+      reduce   : "sum" or "mean"
+    One element is the rule of rlap_amd/csrc/rlap_spmm.h on the graph's rows in id order: float64 terms, chunks of 256 rows summed
+    from 0, the chunk sums added in chunk order; the mean divides that sum once, in float64, by the number of nodes; an empty graph
+    gives exactly 0; a float32 result is the float64 value rounded once.  The same input gives the same bits, and a graph's result
+    does not depend on the other graphs, on L or on F.
+
+    Differentiable in x (the backward is one gather, rlap_graph_readout_backward); double backward is not supported.  Malformed
+    arguments raise ValueError before the device is touched.  No host synchronisation.  `last_stats` then holds what the call did
+    (rlap_readout_info: rows, graphs, chunks, chunked_graphs -- counted exactly from the host's table --, arena_bytes, host_syncs).
+    """
+    table, flags = _readout_args(x, node_ptr, reduce)
+    x3 = x if x.dim() == 3 else x.unsqueeze(0)
+    if torch.is_grad_enabled() and x.requires_grad:
+        y = _Readout.apply(x3, table, flags)
+    else:
+        y = _readout("rlap_graph_readout", x3, table, flags, table.graphs)
+    return y if x.dim() == 3 else y[0]
+
+
 PLAN_DIRECTIONS = {"forward": _lib.PLAN_FORWARD, "transposed": _lib.PLAN_TRANSPOSED, "both": _lib.PLAN_FORWARD | _lib.PLAN_TRANSPOSED}
 
 
