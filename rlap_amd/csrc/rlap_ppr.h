@@ -1,6 +1,7 @@
 // rlap_ppr.h -- PPR diffusion of snapshots (rlap_snapshot_ppr): the interface between rlap_ppr.hip, which holds the
 // kernels and their orchestration, and the C ABI in rlap_api.hip, which owns the handle, its lock and its arena.
 #pragma once
+#include "rlap_ppr_tiles.h"
 #include "rlap_snapshot.h"
 
 namespace rlap {
@@ -19,9 +20,7 @@ struct SnapshotPprReport {
     int32_t host_syncs;
 };
 
-constexpr int PPR_TILE = 64;                  // sources per tile: one lane each
-constexpr int PPR_SMALL_MAX = 4096;           // segments of up to this many nodes run each tile's K steps in one workgroup
-constexpr size_t PPR_TILE_BUDGET = (size_t)1 << 30;   // bytes of live tiles (two n_s x 64 float64 copies each) per group
+// (PPR_TILE, PPR_SMALL_MAX, PPR_TILE_BUDGET and the tile and group table: rlap_ppr_tiles.h)
 
 // arena bytes of a call (an upper bound from the host-known sizes)
 size_t snapshot_ppr_bytes(int64_t m, int64_t S, int64_t G, int64_t N, int64_t out_cap, int32_t K);

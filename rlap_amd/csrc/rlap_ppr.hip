@@ -33,9 +33,8 @@ namespace {
 
 constexpr int PP_SMALL_THREADS = 512;   // small regime: 8 waves per tile
 constexpr int PP_THREADS = 256;         // every other kernel
-constexpr int64_t PP_GROUP_TILES = 65535;   // tiles per group (k_pp_init's grid.y)
 enum { PERR_WEIGHT = COL_ERR_WORDS, PERR_WORDS = 8 };
-enum { T_SEG = 0, T_C0 = 1, T_XOFF = 2, T_ROFF = 3, T_FIELDS = 4 };   // tile table: int64 fields per tile
+using pprtiles::T_SEG; using pprtiles::T_C0; using pprtiles::T_XOFF; using pprtiles::T_ROFF; using pprtiles::T_FIELDS;   // the tile table
 
 __global__ void k_pp_weights(const double* __restrict__ sc, int64_t m, int zero_ok, int32_t* __restrict__ err) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -266,19 +265,13 @@ struct Bufs {
     int64_t tcap, area, area_rows;
 };
 
-// the tile area: one tile of the largest possible segment, or the budget when the tiles of all segments could exceed it
-int64_t area_elems(int64_t bcap) {
-    const int64_t one = 2 * PPR_TILE * bcap;
-    const int64_t all = one * ((bcap + PPR_TILE - 1) / PPR_TILE);
-    return std::max<int64_t>(one, std::min<int64_t>((int64_t)(PPR_TILE_BUDGET / sizeof(double)), all));
-}
-
 size_t carve_ppr(Carve& C, int64_t m, int64_t S, int64_t G, int64_t N, int64_t cap, int32_t K, Bufs& B) {
     C.off = column_pass_carve(C.base, C.off, m, S, G, N, PERR_WORDS, &B.col);
     const int64_t bc = B.col.bcap;
-    B.tcap = bc / PPR_TILE + std::min<int64_t>(S, bc) + 1;
-    B.area = area_elems(bc);
-    B.area_rows = B.area / (2 * PPR_TILE) + 1;
+    const pprtiles::Sizes z = pprtiles::sizes(bc, S);   // (rlap_ppr_tiles.h)
+    B.tcap = z.tcap;
+    B.area = z.area;
+    B.area_rows = z.area_rows;
     B.dinv = C.take<double>(bc);
     B.cdiag = C.take<double>(bc);
     B.a = C.take<double>(m);
@@ -370,36 +363,18 @@ int snapshot_ppr_run(hipStream_t st, void* ws, size_t ws_bytes, const SnapshotPp
     RLAP_HIPCHK(rocprim::radix_sort_pairs(B.tmp, tb, B.bkey, B.bkey_out, B.bval, B.pos_blk, (size_t)Btot, 0, 32 + bits_for(S), st));
     hipLaunchKernelGGL(k_pp_ranks, dim3(grid_blocks(Btot, 256)), dim3(256), 0, st, B.bkey_out, B.pos_blk, B.col.sb, Btot, B.rank);
     RLAP_HIPCHK(hipGetLastError());
-    // 4. tiles and groups (small segments' tiles first), uploaded with the Chebyshev weights
-    std::vector<int64_t> tab;
-    std::vector<int64_t> gstart;   // first tile of each group
-    std::vector<int> gsmall;
-    std::vector<int64_t> grows;
-    for (int pass = 0; pass < 2; ++pass) {
-        int64_t gbytes = 0, groff = 0, ntile_g = 0;
-        bool open = false;
-        for (int64_t s = 0; s < S; ++s) {
-            const int64_t n = hnodes[(size_t)s];
-            if (n == 0 || (pass == 0) != (n <= PPR_SMALL_MAX)) continue;
-            const int64_t tbytes = 2 * PPR_TILE * n * (int64_t)sizeof(double);
-            for (int64_t c0 = 0; c0 < n; c0 += PPR_TILE) {
-                if (!open || gbytes + tbytes > (int64_t)PPR_TILE_BUDGET || ntile_g >= PP_GROUP_TILES) {
-                    if (open) grows.push_back(groff);
-                    gstart.push_back((int64_t)tab.size() / T_FIELDS);
-                    gsmall.push_back(pass == 0);
-                    gbytes = 0; groff = 0; ntile_g = 0; open = true;
-                }
-                tab.push_back(s); tab.push_back(c0); tab.push_back(gbytes / (int64_t)sizeof(double)); tab.push_back(groff);
-                gbytes += tbytes; groff += n; ++ntile_g;
-                if (pass == 0) rep->small_tiles += 1; else rep->large_tiles += 1;
-            }
-        }
-        if (open) grows.push_back(groff);
-    }
-    const int64_t ntiles = (int64_t)tab.size() / T_FIELDS;
-    const int64_t ngroups = (int64_t)gstart.size();
-    if (ntiles > B.tcap) return RLAP_E_INTERNAL;
-    for (int64_t g = 0; g < ngroups; ++g) if (grows[(size_t)g] > B.area_rows) return RLAP_E_INTERNAL;
+    // 4. tiles and groups (rlap_ppr_tiles.h: small segments' tiles first), uploaded with the Chebyshev weights
+    pprtiles::Table tt;
+    pprtiles::build(hnodes.data(), S, &tt);
+    if (!pprtiles::fits(tt, pprtiles::Sizes{B.tcap, B.area, B.area_rows}, hnodes.data())) return RLAP_E_INTERNAL;
+    rep->small_tiles = tt.small_tiles;
+    rep->large_tiles = tt.large_tiles;
+    std::vector<int64_t>& tab = tt.tab;
+    const std::vector<int64_t>& gstart = tt.gstart;
+    const std::vector<int>& gsmall = tt.gsmall;
+    const std::vector<int64_t>& grows = tt.grows;
+    const int64_t ntiles = tt.ntiles();
+    const int64_t ngroups = tt.ngroups();
     tab.resize((size_t)(T_FIELDS * B.tcap), 0);
     for (int64_t g = 0; g < ngroups; ++g) tab.push_back(gstart[(size_t)g]);
     tab.push_back(ntiles);

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from ppr_dense import dense_ppr, to_dense
 from util import ba_graph, grid2d, path
 
 pytestmark = pytest.mark.gpu
@@ -15,40 +16,6 @@ def ops():
     assert torch.cuda.is_available(), "gpu tests need a HIP device"
     from rlap_amd import ops as _ops
     return _ops
-
-
-def dense_ppr(part, alpha=0.2, eps=1e-4, weighted=True, self_loop=False, normalize=True):
-    """(nodes, S before threshold, S kept (and normalised)) of one segment in float64 numpy (the formula of test_ppr_diffusion_adapter)."""
-    part = part.cpu().numpy()
-    nodes = np.unique(part[:, :2].astype(np.int64))
-    rel = {int(v): i for i, v in enumerate(nodes)}
-    k = len(nodes)
-    A = np.zeros((k, k))
-    r = np.array([rel[int(v)] for v in part[:, 0]], dtype=np.int64)
-    c = np.array([rel[int(v)] for v in part[:, 1]], dtype=np.int64)
-    np.add.at(A, (r, c), part[:, 2] if weighted else 1.0)
-    if self_loop:
-        A += np.eye(k)
-    d = A.sum(1)
-    dinv = np.where(d > 0, d ** -0.5, 0)
-    S0 = alpha * np.linalg.inv(np.eye(k) - (1 - alpha) * (dinv[:, None] * A * dinv[None, :]))
-    S = np.where(S0 >= eps, S0, 0.0)
-    if normalize:
-        d2 = S.sum(1)
-        d2inv = np.where(d2 > 0, d2 ** -0.5, 0)
-        S = d2inv[:, None] * S * d2inv[None, :]
-    return nodes, S0, S
-
-
-def to_dense(out, nodes):
-    o = out.cpu().numpy()
-    pos = {int(v): i for i, v in enumerate(nodes)}
-    D = np.zeros((len(nodes), len(nodes)))
-    keep = np.zeros_like(D, dtype=bool)
-    for i, j, v in o:
-        D[pos[int(i)], pos[int(j)]] = v
-        keep[pos[int(i)], pos[int(j)]] = True
-    return D, keep
 
 
 def check_segment(ops, part, out, tol, eps=1e-4, **kw):

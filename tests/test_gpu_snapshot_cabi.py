@@ -154,3 +154,30 @@ def test_statuses_of_the_argument_checks(env, handle):
     rc, info, outs = call(env, handle, "subgraph", S=0, m=0, ptr=torch.zeros(1, dtype=torch.int64, device=dev))
     assert rc == 0 and (info.rows_kept, info.ids_written) == (0, 0)
     assert outs[0].numel() == 0 and outs[2].numel() == 0 and int(outs[1][0]) == 0 and int(outs[3][0]) == 0
+
+
+E_OUT_CAPACITY = 13
+POISON = 0x7FF8DEADBEEF1234   # a quiet NaN no call computes
+
+
+def test_ppr_output_capacity_one_short_then_exact(env, handle):
+    """rlap_snapshot_ppr with room for one row less than it keeps: status 13, the exact count reported, d_out and d_out_ptr left as
+    they were; with exactly that many rows: the expected bits."""
+    lib, _lib, sc, dev = env["lib"], env["_lib"], env["sc"], env["sc"].device
+    want, want_ptr = env["expected"]["ppr"]
+    rows = want.shape[0]
+    assert rows > 1 and rows < PPR_CAP
+    assert _lib.E_OUT_CAPACITY == E_OUT_CAPACITY
+    for cap, status in [(rows - 1, E_OUT_CAPACITY), (0, E_OUT_CAPACITY), (rows, 0)]:
+        out = torch.full((rows, 3), POISON, dtype=torch.int64, device=dev)
+        out_ptr = torch.full((S + 1,), POISON, dtype=torch.int64, device=dev)
+        info = _lib.PprInfo()
+        rc = lib.rlap_snapshot_ppr(handle, addr(sc), sc.shape[0], env["ptr"].data_ptr(), S, None, 1, N, 0.2, 1e-4, 1e-10,
+                                   _lib.PPR_WEIGHTED | _lib.PPR_NORMALIZE, addr(out), cap, addr(out_ptr), ctypes.byref(info))
+        torch.cuda.synchronize()
+        assert rc == status, (cap, rc)
+        assert info.rows_needed == rows and info.steps == 35
+        if status:
+            assert bool((out == POISON).all()) and bool((out_ptr == POISON).all()), "a refused call wrote to its outputs"
+        else:
+            same_bits([out.view(torch.float64), out_ptr], [want, want_ptr])
