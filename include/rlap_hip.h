@@ -78,6 +78,9 @@ typedef struct {
                              3 appended count over 2^22, 4 column longer than its buffer */
     int32_t n_rounds_narrow; /* degree order: the part of n_rounds that the 16-slot round kernel ran before it handed over to the
                              32-slot one (0: it was not used, or the first column was already longer than 16 slots) */
+    int32_t n_squeezes;   /* degree order on large graphs: squeeze passes (dead entries removed from all columns between two launches
+                             of the 16-slot kernel) behind which that kernel committed at least one more round, summed over graphs */
+    int32_t pad;
 } rlap_stats;
 
 /* Lifetime.  A handle binds to the HIP device current at creation.  It owns a few KB of tables (allocated in

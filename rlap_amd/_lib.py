@@ -67,6 +67,7 @@ class Stats(_Report):
         ("n_retries", ctypes.c_int32), ("reserved", ctypes.c_int32),
         ("n_rounds", ctypes.c_int64), ("n_singles", ctypes.c_int64),
         ("elim_kernel", ctypes.c_int32), ("retry_causes", ctypes.c_int32), ("flow_abort", ctypes.c_int32), ("n_rounds_narrow", ctypes.c_int32),
+        ("n_squeezes", ctypes.c_int32), ("pad", ctypes.c_int32),
     ]
 
 

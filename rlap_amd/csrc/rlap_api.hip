@@ -313,11 +313,13 @@ struct Sizes {
     bool flow;                    // dataflow elimination (o_v = random): its arrays are part of the arena
     int64_t flow_Q, flow_scr;     // look-back words (positions + one sentinel per graph); entries of long-column working storage
     int64_t D;                    // depths call: snapshots (0 otherwise)
+    int squeeze;                  // squeeze passes of the degree order (0: none): a second entry arena and the pass's arrays are part of the arena
 };
 struct WBuf { void* p = nullptr; template <class T> T* as() const { return reinterpret_cast<T*>(p); } };
 struct WS {
     WBuf node_ptr_d, depth_t, depth_sb, vgraph, scal, keys0, keys1, idx0, idx1, head, pos, sorttmp, colptr, slot_col, permchk, genperm, ent, vrec, ocur, oend, origpos, orig_order, gd_d, pool_top, bs_cnt, bs_alloc, bs_dir, bs_v, bs_id, bs_pool_top, batch_pos, skey0, skey1, sval0, sval1, scr_rec, scr_i32, scr_f64, surv_base_d, ext, tmp_off, tmp_nbr, tmp_val, cnt, row_off, sc_rec, sc_i32, sc_f64, biglist, hugelists, results,
-         f_cdir, f_atag, f_lb, f_qv, f_qg, f_ctrl, f_scr, f_rocnt, f_rooff;
+         f_cdir, f_atag, f_lb, f_qv, f_qg, f_ctrl, f_scr, f_rocnt, f_rooff,
+         sq_ent, sq_colptr, sq_rank, sq_cnt, sq_list, sq_nlong, sq_marks;
 };
 // depths call (D > 0): the depth table t[D][G] and every snapshot's survivor bases sb[D][G + 1] follow
 inline size_t host_block_bytes(int64_t G, int64_t D) {
@@ -372,6 +374,13 @@ size_t carve(Carve& C, const Sizes& z, WS& W) {
         W.f_scr.p = C.take<char>(z.flow_scr * FLOW_SCR_BYTES);
         W.f_rocnt.p = C.take<int32_t>(S + 1); W.f_rooff.p = C.take<int32_t>(S + 1);
     }
+    if (z.squeeze > 0) {   // 20 bytes per slot and 12 per vertex on top (rlap_squeeze.h)
+        W.sq_ent.p = C.take<Slot>(z.slot_cap);
+        W.sq_rank.p = C.take<int32_t>(z.slot_cap);
+        W.sq_colptr.p = C.take<int32_t>(N + 1); W.sq_cnt.p = C.take<int32_t>(N + 1); W.sq_list.p = C.take<int32_t>(N);
+        W.sq_nlong.p = C.take<int32_t>(1);
+        W.sq_marks.p = C.take<int32_t>((int64_t)z.squeeze * G);
+    }
     return (C.off + 255) & ~(size_t)255;
 }
 
@@ -380,7 +389,7 @@ size_t carve(Carve& C, const Sizes& z, WS& W) {
 // host block carries the depth table and the snapshots' survivor bases, and the read-back block holds segs * G + 1 row pointers, the
 // scratch maximum and the stop word
 int call_sizes(const rlap_handle h, int64_t Eeff, int64_t N, int64_t G, int64_t bucket_total, int64_t S, bool want_genperm, bool flow, int64_t nelim_total, Sizes* z,
-               int64_t segs = 0) {
+               int64_t segs = 0, int squeeze = 0) {
     const double pool_factor = h->dbg_pool >= 0 ? h->dbg_pool : h->pool_factor;
     const double log_factor = h->dbg_log >= 0 ? h->dbg_log : h->log_factor;
     const int64_t nnz_ub = Eeff;
@@ -396,11 +405,18 @@ int call_sizes(const rlap_handle h, int64_t Eeff, int64_t N, int64_t G, int64_t 
     z->D = segs;
     z->want_genperm = want_genperm;
     z->flow = flow;
+    z->squeeze = squeeze;
     z->flow_Q = nelim_total + G;
     z->flow_scr = flow ? (int64_t)(h->flow_scr_factor * (double)std::max<int64_t>(Eeff / 16, 1 << 17)) : 0;
     if (flow && h->dbg_scr >= 0) z->flow_scr = std::max<int64_t>(h->dbg_scr, 16);   // (test hook: a tiny first size, so that the retry runs)
     if (z->flow_scr >= ((int64_t)1 << 31) - 64) z->flow_scr = ((int64_t)1 << 31) - 64;
-    return sort_tmp_bytes(Eeff, N, G, S, flow, &z->sort_tmp);
+    { int rc = sort_tmp_bytes(Eeff, N, G, S, flow, &z->sort_tmp); if (rc) return rc; }
+    if (squeeze > 0) {   // the pass's prefix sum over the N + 1 live counts shares the temporary storage
+        size_t b = 0;
+        RLAP_HIPCHK((hipError_t)squeeze_scan_tmp_bytes(N, &b));
+        z->sort_tmp = std::max(z->sort_tmp, b);
+    }
+    return RLAP_OK;
 }
 
 // uniforms a call may draw: a graph rarely draws more than its own directed entry count; an overflow doubles the table
@@ -488,7 +504,9 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
     Sizes z;
     const bool flow = flow_wanted(h, c.o_v, G, N);
     st.elim_kernel = nelim_total > 0 ? (flow ? 2 : 1) : 0;
-    { int rc = call_sizes(h, Eeff, N, G, bucket_total, S0, c.o_v == OV_RANDOM && !c.d_perm, flow, nelim_total, &z, depths ? nseg : 0); if (rc) return rc; }
+    // degree order on a large graph: squeeze passes between launches of the 16-slot kernel (rlap_squeeze.h; 0: none)
+    const int squeeze = flow ? 0 : squeeze_passes(c.o_v, (unsigned)G, h->n_cu, depths, c.K > 1, Eeff);
+    { int rc = call_sizes(h, Eeff, N, G, bucket_total, S0, c.o_v == OV_RANDOM && !c.d_perm, flow, nelim_total, &z, depths ? nseg : 0, squeeze); if (rc) return rc; }
     const int64_t slot_cap = z.slot_cap, log_total = z.log_total, scr_total = z.scr_total, scr_budget = z.scr_budget;
     const size_t res_bytes = z.res_bytes;
 
@@ -764,7 +782,16 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
                 launch_flow_eliminate(shape, grid, s, A, FA, FP);
                 launch_flow_finish(s, A, FA, gd_d, (int32_t)N, (int32_t)G);
             } else {
-                launch_eliminate_batch(c.o_v, c.o_n, (unsigned)G, h->n_cu, s, A, gd_d, ES, W.batch_pos.as<int32_t>(), flags, acc, wide);
+                // (squeeze passes: the elimination ends in whichever arena its last pass wrote -- A names that one from here on)
+                SqueezeBufs SQ;
+                SQ.passes = squeeze; SQ.e2 = W.sq_ent.as<Slot>(); SQ.colptr2 = W.sq_colptr.as<int32_t>(); SQ.rank = W.sq_rank.as<int32_t>();
+                SQ.cnt = W.sq_cnt.as<int32_t>(); SQ.longlist = W.sq_list.as<int32_t>(); SQ.nlong = W.sq_nlong.as<int32_t>();
+                SQ.marks = W.sq_marks.as<int32_t>(); SQ.vgraph = W.vgraph.as<int32_t>(); SQ.scan_tmp = W.sorttmp.p; SQ.scan_tmp_bytes = z.sort_tmp;
+                SQ.N = (int32_t)N;
+                Arrays A_end;
+                RLAP_HIPCHK((hipError_t)launch_eliminate_batch(c.o_v, c.o_n, (unsigned)G, h->n_cu, s, A, gd_d, ES, W.batch_pos.as<int32_t>(), flags, acc, wide,
+                                                               squeeze > 0 ? &SQ : nullptr, &A_end));
+                A = A_end;
             }
             RLAP_HIPCHK(hipGetLastError());
             if (depths) hipLaunchKernelGGL(k_depth_stop, dim3(1), dim3(256), 0, s, gd_d, (int32_t)G, stop_d);
@@ -800,7 +827,7 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
             order = W.sval1.as<uint32_t>();
         }
         if (Sk > 0)
-            hipLaunchKernelGGL(k_sc_ext, dim3(nblk(Sk, 256)), dim3(256), 0, s, order, W.colptr.as<int32_t>(), W.vrec.as<VRec>(), (int32_t)Sk, flags, acc, W.ext.as<int32_t>(), stop_d);
+            hipLaunchKernelGGL(k_sc_ext, dim3(nblk(Sk, 256)), dim3(256), 0, s, order, A.colptr, W.vrec.as<VRec>(), (int32_t)Sk, flags, acc, W.ext.as<int32_t>(), stop_d);
         { int rc = excl_scan(h, ST, W.ext.as<int32_t>(), W.tmp_off.as<int64_t>(), Sk + 1); if (rc) return rc; }
         if (h->timing) RLAP_HIPCHK(hipEventRecord(h->ev[3], s));
         if (Sk > 0) {
@@ -849,7 +876,8 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
     if (!depths)
         hipLaunchKernelGGL(k_graph_rows, dim3(nblk(G + 1, 256)), dim3(256), 0, s, W.surv_base_d.as<int64_t>(), W.row_off.as<int64_t>(), (int32_t)G, out_ptr_d);
     hipLaunchKernelGGL(k_collect, dim3(1), dim3(256), 0, s, flags, acc, nnz_p, counters, live, W.tmp_off.as<int64_t>(), W.row_off.as<int64_t>(), (int32_t)S,
-                       W.gd_d.as<GraphDesc>(), (int32_t)G, W.pool_top.as<int32_t>(), W.bs_pool_top.as<int32_t>(), flow ? W.f_ctrl.as<int32_t>() + FC_REASON : nullptr, res_d);
+                       W.gd_d.as<GraphDesc>(), (int32_t)G, W.pool_top.as<int32_t>(), W.bs_pool_top.as<int32_t>(), flow ? W.f_ctrl.as<int32_t>() + FC_REASON : nullptr,
+                       W.sq_marks.as<int32_t>(), (int32_t)squeeze, res_d);
     RLAP_HIPCHK(hipMemcpyAsync(h->h_results, W.results.p, res_bytes, hipMemcpyDeviceToHost, s));
     if (h->timing) RLAP_HIPCHK(hipEventRecord(h->ev[7], s));
     RLAP_HIPCHK(hipStreamSynchronize(s));
@@ -892,6 +920,7 @@ int run_once(rlap_handle h, const Call& c, int* retry_kind, int64_t* retry_need,
     st.nnz = R.nnz;
     st.n_draws = R.n_draws;
     st.n_rounds = R.rounds; st.n_singles = R.singles; st.n_rounds_narrow = R.rounds_narrow;
+    st.n_squeezes = R.n_squeezes;
     const int64_t m_total = depths ? out_ptr_h[nseg * G] : R.m_total;   // (depths: the rows of all snapshots)
     st.out_rows = m_total;
     st.live_entries = R.live_total;
@@ -1061,7 +1090,9 @@ static int ws_query(const rlap_handle h, int64_t E, int64_t n_total, int64_t G, 
     const rlap_handle hh = h ? h : &defaults;
     Sizes z;
     // bounds that hold for every split of n_total over G graphs and every num_remove: 2n+1 buckets per graph, S <= n_total
-    int rc = call_sizes(hh, Eeff, n_total, G, 2 * n_total + G, n_total, true, flow_wanted(hh, OV_RANDOM, G, n_total), n_total, &z);
+    // (the degree order's squeeze passes are part of the bound wherever a call of these sizes could run them)
+    int rc = call_sizes(hh, Eeff, n_total, G, 2 * n_total + G, n_total, true, flow_wanted(hh, OV_RANDOM, G, n_total), n_total, &z, 0,
+                        squeeze_passes(OV_DEGREE, (unsigned)G, hh->n_cu, false, false, Eeff));
     if (rc) return rc;
     WS W; Carve dry{nullptr, 0};
     *ws_bytes = carve(dry, z, W);

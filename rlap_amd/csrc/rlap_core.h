@@ -432,6 +432,55 @@ RLAP_HD int32_t serial_gather(const Arrays& A, int32_t v, const ColBuf& B, int32
     return len;
 }
 
+// ---------------------------------------------------------------------------
+// Squeeze (rlap_squeeze.hip): every surviving column is rewritten into a second entry arena as a plain CSR segment of its
+// live entries, so that a column's extent is its live count again.  The order in which a traversal meets the live entries
+// of a column is all that gather, std::sort under ties, merge and sampling see of the layout; it is kept: the r-th live
+// entry of the old traversal (appended entries newest first, then the CSR segment backwards) is the r-th slot from the end
+// of the new segment, which is read backwards.
+// ---------------------------------------------------------------------------
+constexpr int SQUEEZE_PASSES = 2;   // squeezes of a degree-order call: on BA(1M,10) a third would be due about 100 pops after it
+
+// f(slot) for every slot of column v, dead ones included, in traversal order (serial_gather's)
+template <class F>
+RLAP_HD void col_for_each_slot(const Arrays& A, int32_t v, F f) {
+    const int32_t a = A.vr[v].app_cnt;
+    if (a > 0) {
+        int32_t base = A.vr[v].app_chunk;
+        int c = chunk_of(a - 1);
+        int32_t idx = a - 1;
+        while (idx >= 0 && base >= 0) {
+            const int32_t cs = chunk_start(c);
+            for (int32_t t = idx; t >= cs; --t) f(base + 1 + (t - cs));
+            idx = cs - 1;
+            base = A.e[base].nbr;
+            --c;
+        }
+    }
+    for (int32_t s = A.colptr[v + 1] - 1; s >= A.colptr[v]; --s) f(s);
+}
+// rank[s] = r for the r-th live entry of column v's traversal; returns the live count
+RLAP_HD int32_t squeeze_rank_col(const Arrays& A, int32_t v, int32_t* rank) {
+    int32_t r = 0;
+    col_for_each_slot(A, v, [&](int32_t s) { if (A.e[s].val > 0) rank[s] = r++; });
+    return r;
+}
+// THE RULE: where the live entry of rank r of column `col` lies once the new column pointers are known
+RLAP_HD int32_t squeeze_slot(const int32_t* colptr2, int32_t col, int32_t r) { return colptr2[col + 1] - 1 - r; }
+// ... applied to the live slot s of column v: the entry moves to its new slot, and its twin -- a live entry of column nbr, so it
+// has a rank of its own -- is named by the new slot of that one.  Only ranks of live entries are read.  false: an index out of
+// range (nothing is written; cannot happen on a consistent state).
+RLAP_HD bool squeeze_entry(const Arrays& A, const int32_t* rank, const int32_t* colptr2, Slot* e2, int32_t n_total, int32_t v, int32_t s) {
+    const Slot x = A.e[s];
+    if ((uint32_t)x.nbr >= (uint32_t)n_total || (uint32_t)x.twin >= (uint32_t)A.slot_cap) return false;
+    const int32_t d = squeeze_slot(colptr2, v, rank[s]);
+    if (d < colptr2[v] || d >= colptr2[v + 1]) return false;
+    Slot y;
+    y.val = x.val; y.nbr = x.nbr; y.twin = squeeze_slot(colptr2, x.nbr, rank[x.twin]);
+    e2[d] = y;
+    return true;
+}
+
 // Bucket stacks == the reference's doubly linked bucket lists
 // (preconditioner.cc:125-246): a move re-inserts the vertex at the bucket head,
 // so a bucket pops its moved vertices newest first, then its never-moved

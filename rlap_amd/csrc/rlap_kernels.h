@@ -5,6 +5,7 @@
 
 #include "rlap_core.h"
 #include "rlap_flow.h"
+#include "rlap_squeeze.h"
 
 namespace rlap {
 
@@ -23,6 +24,8 @@ struct CallResults {
     int32_t pool_used, log_used;
     int32_t flow_abort;        // dataflow elimination: why the launch gave up (FA_*, rlap_flow.h), 0 otherwise
     int32_t rounds_narrow;     // degree order: the part of `rounds` the 16-slot round kernel ran
+    int32_t n_squeezes;        // degree order: squeeze passes behind which the 16-slot kernel committed another round, summed over graphs
+    int32_t pad;
 };
 constexpr int ECAP = 384;  // elimination: column extent handled in LDS; longer -> sequential form in global scratch
 constexpr int ECAP_SMALL = 320;   // the same for the 256-thread shape (four workgroups per CU: 40 KB of LDS each)
@@ -103,7 +106,8 @@ __global__ void k_perm_check(const int64_t* perm, const int32_t* vgraph, const G
 __global__ void k_gd_scratch(const int32_t* colptr, const int64_t* node_ptr, int32_t G, GraphDesc* gd);
 __global__ void k_collect(const int32_t* flags, const double* acc, const int32_t* nnz_p, const unsigned long long* counters,
                           const unsigned long long* live, const int64_t* tmp_off, const int64_t* row_off, int32_t S, const GraphDesc* gd, int32_t G,
-                          const int32_t* pool_top, const int32_t* bs_pool_top, const int32_t* flow_reason, CallResults* out);
+                          const int32_t* pool_top, const int32_t* bs_pool_top, const int32_t* flow_reason, const int32_t* sq_marks, int32_t n_sq,
+                          CallResults* out);
 __global__ void k_heads(const uint64_t* keys, int64_t E, int32_t* head);
 __global__ void k_fill_csr(const uint64_t* keys, const uint32_t* idx, const int32_t* head, const int32_t* pos, const double* w,
                            int64_t E, int set_semantics, int kbits, Slot* ent, int32_t* slot_col, int32_t* nbr32);
@@ -116,8 +120,15 @@ __global__ void k_pq_init(const int32_t* colptr, const int32_t* vgraph, int32_t 
 __global__ void k_bucket_bounds(const uint32_t* order, const VRec* vr, const int32_t* vgraph, const GraphDesc* gd, int32_t N,
                                 int32_t* ocur, int32_t* oend, int32_t* origpos);
 void launch_eq_tables(hipStream_t stream, uint8_t* out);
-void launch_eliminate_batch(int o_v, int o_n, unsigned G, int n_cu, hipStream_t stream, const Arrays& A, GraphDesc* gd, const ElimScratch& S,
-                            int32_t* batch_pos, const int32_t* flags, const double* acc, bool wide);
+// `sq` (degree order, may be null): the schedule 16-slot, squeeze, 16-slot, squeeze, 16-slot, 32-slot; *A_cur = the Arrays of the
+// arena the elimination ended in (the output pass reads that one); returns a hipError_t as int
+int launch_eliminate_batch(int o_v, int o_n, unsigned G, int n_cu, hipStream_t stream, const Arrays& A, GraphDesc* gd, const ElimScratch& S,
+                           int32_t* batch_pos, const int32_t* flags, const double* acc, bool wide, const SqueezeBufs* sq, Arrays* A_cur);
+// Squeeze passes a call of these sizes runs (SQUEEZE_PASSES or 0): the degree order in its 1024-thread shape with the 16-slot kernel
+// in use, not a depths or views call, nnz_ub >= SQUEEZE_MIN_NNZ -- below that the passes cost more than they can save.
+// RLAP_SQUEEZE=0|1 (diagnostic, like RLAP_NARROW) overrides the size gate both ways.
+constexpr int64_t SQUEEZE_MIN_NNZ = (int64_t)1 << 21;
+int squeeze_passes(int o_v, unsigned G, int n_cu, bool depths, bool views, int64_t nnz_ub);
 // ---- dataflow elimination for o_v = random (rlap_flow.hip) ----
 constexpr int FLOW_EC = 896;              // column extent a wave handles in its own LDS (two one-wave workgroups per CU)
 constexpr int FLOW_EC_SMALL = 192;        // ... in the shape for batches of small graphs (eight per CU)

@@ -227,14 +227,15 @@ __global__ __launch_bounds__(256) void k_collect(const int32_t* __restrict__ fla
                           const unsigned long long* __restrict__ counters, const unsigned long long* __restrict__ live,
                           const int64_t* __restrict__ tmp_off, const int64_t* __restrict__ row_off,
                           int32_t S, const GraphDesc* __restrict__ gd, int32_t G, const int32_t* __restrict__ pool_top,
-                          const int32_t* __restrict__ bs_pool_top, const int32_t* __restrict__ flow_reason, CallResults* __restrict__ out) {
+                          const int32_t* __restrict__ bs_pool_top, const int32_t* __restrict__ flow_reason,
+                          const int32_t* __restrict__ sq_marks, int32_t n_sq, CallResults* __restrict__ out) {
     __shared__ int32_t s_st;
     __shared__ unsigned long long s_nd, s_rounds, s_singles;
-    __shared__ int32_t s_narrow;
+    __shared__ int32_t s_narrow, s_nsq;
     const int tid = threadIdx.x;
-    if (tid == 0) { s_st = 0; s_nd = 0ull; s_rounds = 0ull; s_singles = 0ull; s_narrow = 0; }
+    if (tid == 0) { s_st = 0; s_nd = 0ull; s_rounds = 0ull; s_singles = 0ull; s_narrow = 0; s_nsq = 0; }
     __syncthreads();
-    int32_t st = 0, narrow = 0; unsigned long long nd = 0, rounds = 0, singles = 0;
+    int32_t st = 0, narrow = 0, nsq = 0; unsigned long long nd = 0, rounds = 0, singles = 0;
     for (int32_t g = tid; g < G; g += blockDim.x) {
         const int32_t sg = gd[g].status;
         if (sg > st) st = sg;
@@ -242,8 +243,13 @@ __global__ __launch_bounds__(256) void k_collect(const int32_t* __restrict__ fla
         nd = d > nd ? d : nd;
         rounds += (unsigned long long)gd[g].pad0; singles += (unsigned long long)gd[g].pad1;
         narrow += gd[g].narrow_rounds;
+        // squeeze pass p counts when the 16-slot kernel ran a round between it and the next pass (or the end): sq_marks[p * G + g] is
+        // the graph's narrow_rounds when pass p ran
+        for (int32_t p = 0; p < n_sq; ++p)
+            if ((p + 1 < n_sq ? sq_marks[(p + 1) * G + g] : gd[g].narrow_rounds) > sq_marks[p * G + g]) ++nsq;
     }
     if (narrow) atomicAdd(&s_narrow, narrow);
+    if (nsq) atomicAdd(&s_nsq, nsq);
     if (st) atomicMax(&s_st, st);
     if (nd) atomicMax(&s_nd, nd);
     if (rounds) atomicAdd(&s_rounds, rounds);
@@ -262,6 +268,7 @@ __global__ __launch_bounds__(256) void k_collect(const int32_t* __restrict__ fla
     R.log_used = *bs_pool_top;
     R.status = s_st; R.n_draws = (int64_t)s_nd; R.rounds = (int64_t)s_rounds; R.singles = (int64_t)s_singles;
     R.flow_abort = flow_reason ? *flow_reason : 0; R.rounds_narrow = s_narrow;
+    R.n_squeezes = s_nsq; R.pad = 0;
     *out = R;
 }
 
@@ -3026,18 +3033,37 @@ void launch_eq_tables(hipStream_t stream, uint8_t* out) {
 }
 
 // the priority-queue instantiations live in the other translation unit (top of this file)
-void launch_eliminate_pq(int o_v, int o_n, unsigned G, bool many, hipStream_t stream, const Arrays& A, GraphDesc* gd, const ElimScratch& S,
-                         int32_t* batch_pos, const int32_t* flags, const double* acc);
+int launch_eliminate_pq(int o_v, int o_n, unsigned G, bool many, bool narrow, hipStream_t stream, const Arrays& A, GraphDesc* gd, const ElimScratch& S,
+                        int32_t* batch_pos, const int32_t* flags, const double* acc, const SqueezeBufs* sq, Arrays* A_cur);
 
-void launch_eliminate_batch(int o_v, int o_n, unsigned G, int n_cu, hipStream_t stream, const Arrays& A, GraphDesc* gd, const ElimScratch& S,
-                            int32_t* batch_pos, const int32_t* flags, const double* acc, bool wide) {
+// more graphs than CUs: the 256-thread shape (launch_eliminate_batch)
+static bool elim_shape_many(unsigned G, int n_cu) {
+    if (n_cu <= 0) n_cu = 256;
+    bool many = G > (unsigned)n_cu;
+    if (const char* e = std::getenv("RLAP_BATCH_SHAPE")) { if (e[0] == '2') many = true; else if (e[0] == '1') many = false; }   // diagnostic override: 256 / 1024
+    return many;
+}
+// degree order, 1024-thread shape: the 16-slot kernel runs first (launch_eliminate_pq)
+static bool elim_narrow(int o_v, bool many) {
+    bool narrow = o_v == OV_DEGREE && !many;
+    if (const char* e = std::getenv("RLAP_NARROW")) { if (e[0] == '0') narrow = false; }   // diagnostic override: the 32-slot kernel alone
+    return narrow;
+}
+int squeeze_passes(int o_v, unsigned G, int n_cu, bool depths, bool views, int64_t nnz_ub) {
+    if (!elim_narrow(o_v, elim_shape_many(G, n_cu)) || depths || views) return 0;
+    bool on = nnz_ub >= SQUEEZE_MIN_NNZ;
+    if (const char* e = std::getenv("RLAP_SQUEEZE")) { if (e[0] == '0') on = false; else if (e[0] == '1') on = true; }   // diagnostic override of the size gate
+    return on ? SQUEEZE_PASSES : 0;
+}
+
+int launch_eliminate_batch(int o_v, int o_n, unsigned G, int n_cu, hipStream_t stream, const Arrays& A, GraphDesc* gd, const ElimScratch& S,
+                           int32_t* batch_pos, const int32_t* flags, const double* acc, bool wide, const SqueezeBufs* sq, Arrays* A_cur) {
+    *A_cur = A;
     // o_v = random meets long columns all the time (19 % of BA(1M,10) have more than 32 live entries when their
     // turn comes): it runs with 64 slots per candidate (64 candidates per round); the min-degree orders with 32.
     // more graphs than CUs: the 256-thread shape, four workgroups per CU (128 VGPRs, 39 KB of LDS; measured on 4096-node graphs: the same
     // time per graph as the 1024-thread shape, which is only ahead when one graph offers more than 32 independent vertices a round)
-    if (n_cu <= 0) n_cu = 256;
-    bool many = G > (unsigned)n_cu;
-    if (const char* e = std::getenv("RLAP_BATCH_SHAPE")) { if (e[0] == '2') many = true; else if (e[0] == '1') many = false; }   // diagnostic override: 256 / 1024
+    const bool many = elim_shape_many(G, n_cu);
     // o_v = random on graphs with long columns (`wide`, chosen by the caller from the entries per vertex): 128 slots per
     // candidate, 32 candidates per round -- a column of 65..128 entries no longer ends the round (BA(4096,8): 134 rounds + 13
     // single vertices instead of 148 + 60).  Sparse graphs fill their rounds with 64 slots and keep 64 candidates.
@@ -3046,36 +3072,60 @@ void launch_eliminate_batch(int o_v, int o_n, unsigned G, int n_cu, hipStream_t 
         if (o_n == ON_ASC) hipLaunchKernelGGL((k_eliminate_batch_t<OV_RANDOM, ON_ASC, 128, 1024>), dim3(G), dim3(1024), 0, stream, A, gd, S, batch_pos, flags, acc);
         else if (o_n == ON_DESC) hipLaunchKernelGGL((k_eliminate_batch_t<OV_RANDOM, ON_DESC, 128, 1024>), dim3(G), dim3(1024), 0, stream, A, gd, S, batch_pos, flags, acc);
         else hipLaunchKernelGGL((k_eliminate_batch_t<OV_RANDOM, ON_RANDOM, 128, 1024>), dim3(G), dim3(1024), 0, stream, A, gd, S, batch_pos, flags, acc);
-        return;
+        return 0;
     }
 #define RLAP_CASE(OV, ON, BC) if (o_v == OV && o_n == ON) { \
         if (many) hipLaunchKernelGGL((k_eliminate_batch_t<OV, ON, BC, 256>), dim3(G), dim3(256), 0, stream, A, gd, S, batch_pos, flags, acc); \
         else hipLaunchKernelGGL((k_eliminate_batch_t<OV, ON, BC, 1024>), dim3(G), dim3(1024), 0, stream, A, gd, S, batch_pos, flags, acc); \
-        return; }
+        return 0; }
     RLAP_CASE(OV_RANDOM, ON_ASC, 64) RLAP_CASE(OV_RANDOM, ON_DESC, 64) RLAP_CASE(OV_RANDOM, ON_RANDOM, 64)
 #undef RLAP_CASE
-    launch_eliminate_pq(o_v, o_n, G, many, stream, A, gd, S, batch_pos, flags, acc);
+    return launch_eliminate_pq(o_v, o_n, G, many, elim_narrow(o_v, many), stream, A, gd, S, batch_pos, flags, acc, sq, A_cur);
 }
 #else   // RLAP_ELIM_PQ_TU
-void launch_eliminate_pq(int o_v, int o_n, unsigned G, bool many, hipStream_t stream, const Arrays& A, GraphDesc* gd, const ElimScratch& S,
-                         int32_t* batch_pos, const int32_t* flags, const double* acc) {
-    // degree order, 1024-thread shape: the 16-slot kernel first (256 candidates per round while the columns at the head of the queue
-    // are short: BA(1M,10) has none longer than 16 slots among its first 300,000 pops); it stops in front of the first longer column
-    // and the 32-slot kernel below, launched right behind it, continues from there (GraphDesc::resume) -- or finds nothing left to do
-    bool narrow = o_v == OV_DEGREE && !many;
-    if (const char* e = std::getenv("RLAP_NARROW")) { if (e[0] == '0') narrow = false; }   // diagnostic override: the 32-slot kernel alone
+constexpr int NARROW_BATCH_LATE = 144;   // candidates a round of the 16-slot kernel predicts behind a squeeze pass (NARROW_BATCH = 192 in front of the first); RLAP_NARROW_BATCH_LATE for measurements
+int launch_eliminate_pq(int o_v, int o_n, unsigned G, bool many, bool narrow, hipStream_t stream, const Arrays& A_in, GraphDesc* gd, const ElimScratch& S,
+                        int32_t* batch_pos, const int32_t* flags, const double* acc, const SqueezeBufs* sq, Arrays* A_cur) {
+    // degree order, 1024-thread shape (`narrow`): the 16-slot kernel first (256 candidates per round while the columns at the head of
+    // the queue are short: BA(1M,10) has none longer than 16 slots among its first 270,000 pops); it stops in front of the first longer
+    // column and the 32-slot kernel below, launched right behind it, continues from there (GraphDesc::resume) -- or finds nothing left to do.
+    // With squeeze passes (`sq`): a column's extent counts its dead entries, and for another 110,000 pops of that graph it is one to
+    // four of those that make a column longer than 16 slots.  Each pass (rlap_squeeze.hip, all CUs) rewrites the surviving columns
+    // into the other arena without them and clears GraphDesc::narrow, and the 16-slot kernel is launched again: it ends at once where
+    // nothing is left to do or the first candidate is still too long.  All on the one stream; the host only keeps track of which arena
+    // is current.  The hand-over behind the last pass is final.
+    Arrays A = A_in;
+    auto launch16 = [&](const ElimScratch& S16) {
+        if (o_n == ON_ASC) hipLaunchKernelGGL((k_eliminate_batch_t<OV_DEGREE, ON_ASC, 16, 1024>), dim3(G), dim3(1024), 0, stream, A, gd, S16, batch_pos, flags, acc);
+        else if (o_n == ON_DESC) hipLaunchKernelGGL((k_eliminate_batch_t<OV_DEGREE, ON_DESC, 16, 1024>), dim3(G), dim3(1024), 0, stream, A, gd, S16, batch_pos, flags, acc);
+        else hipLaunchKernelGGL((k_eliminate_batch_t<OV_DEGREE, ON_RANDOM, 16, 1024>), dim3(G), dim3(1024), 0, stream, A, gd, S16, batch_pos, flags, acc);
+    };
+    // behind a squeeze the columns at the head of the queue hold 13 to 16 live entries, and the move list (1,024 moves a round) ends
+    // a round at about 105 committed candidates: what is predicted beyond that is prepared, sampled and replayed for nothing
+    ElimScratch S_late = S;
+    S_late.narrow_batch = S.narrow_batch < NARROW_BATCH_LATE ? S.narrow_batch : NARROW_BATCH_LATE;
+    if (const char* e = std::getenv("RLAP_NARROW_BATCH_LATE")) { const int q = std::atoi(e); S_late.narrow_batch = q < 1 ? 1 : (q > 256 ? 256 : q); }   // diagnostic override
     if (narrow) {
-        if (o_n == ON_ASC) hipLaunchKernelGGL((k_eliminate_batch_t<OV_DEGREE, ON_ASC, 16, 1024>), dim3(G), dim3(1024), 0, stream, A, gd, S, batch_pos, flags, acc);
-        else if (o_n == ON_DESC) hipLaunchKernelGGL((k_eliminate_batch_t<OV_DEGREE, ON_DESC, 16, 1024>), dim3(G), dim3(1024), 0, stream, A, gd, S, batch_pos, flags, acc);
-        else hipLaunchKernelGGL((k_eliminate_batch_t<OV_DEGREE, ON_RANDOM, 16, 1024>), dim3(G), dim3(1024), 0, stream, A, gd, S, batch_pos, flags, acc);
+        launch16(S);
+        for (int p = 0; sq && p < sq->passes; ++p) {
+            // pass p reads the current arena and writes the other one: the call's first arena and sq->e2 take turns
+            Slot* const e_dst = (p & 1) ? A_in.e : sq->e2;
+            int32_t* const colptr_dst = (p & 1) ? const_cast<int32_t*>(A_in.colptr) : sq->colptr2;
+            const int rc = launch_squeeze(stream, A, *sq, p, e_dst, colptr_dst, gd, (int32_t)G, flags, acc);
+            if (rc) return rc;
+            A.e = e_dst; A.colptr = colptr_dst;
+            launch16(S_late);
+        }
     }
+    *A_cur = A;
 #define RLAP_CASE(OV, ON, BC) if (o_v == OV && o_n == ON) { \
         if (many) hipLaunchKernelGGL((k_eliminate_batch_t<OV, ON, BC, 256>), dim3(G), dim3(256), 0, stream, A, gd, S, batch_pos, flags, acc); \
         else hipLaunchKernelGGL((k_eliminate_batch_t<OV, ON, BC, 1024>), dim3(G), dim3(1024), 0, stream, A, gd, S, batch_pos, flags, acc); \
-        return; }
+        return 0; }
     RLAP_CASE(OV_DEGREE, ON_ASC, 32) RLAP_CASE(OV_DEGREE, ON_DESC, 32) RLAP_CASE(OV_DEGREE, ON_RANDOM, 32)
     RLAP_CASE(OV_COARSEN, ON_ASC, 32) RLAP_CASE(OV_COARSEN, ON_DESC, 32) RLAP_CASE(OV_COARSEN, ON_RANDOM, 32)
 #undef RLAP_CASE
+    return 0;
 }
 #endif  // RLAP_ELIM_PQ_TU
 
