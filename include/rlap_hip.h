@@ -528,6 +528,42 @@ int rlap_graph_readout(rlap_handle h, const void* d_x, int64_t L, int64_t num_no
 int rlap_graph_readout_backward(rlap_handle h, const void* d_gy, int64_t L, int64_t num_nodes, int64_t F, const int64_t* d_node_ptr,
                                 int64_t G, int flags, void* d_gx, rlap_readout_info* h_info);
 
+/* The fused InfoNCE contrastive loss of two views' node embeddings, forward and backward: what
+ * DualBranchContrast(InfoNCEBatched(tau), mode="L2L") computes for one direction, without the N x N similarity matrix.
+ *   d_a, d_b, N, F : anchor and sample embeddings, (N, F) float32 row-major; N >= 1, 1 <= F <= 512
+ *   tau            : the temperature, in [1/32, 1024]
+ *   flags          : RLAP_INFONCE_POSITIVE_RAW takes the positive term as s_ii (the reference's InfoNCEBatched, which does not divide
+ *                    it by tau); without it the term is s_ii / tau (GCL's InfoNCE)
+ *   forward        : d_loss one double; d_rows [N] doubles, the row terms c s_ii - 1/tau - log Z_i; d_z [N] doubles, the row sums
+ *                    Z_i = sum_j exp((s_ij - 1) / tau), which the backward call reads
+ *   backward       : d_z as the forward call left it; d_g the upstream gradient, one double ON THE DEVICE (so that no
+ *                    synchronisation is needed); d_ga, d_gb (N, F) float32, the gradients with respect to d_a and d_b
+ *   h_info         : (nullable) what the call did
+ * The positive of row i is column i; every column, the positive included, is in the denominator.  Every value and the order of every
+ * sum are defined in rlap_amd/csrc/rlap_infonce.h: rows normalised in float64 and rounded once; s_ij the float32 fmaf chain over the
+ * columns in increasing order (what the f32 matrix-core instruction computes); a float32 exponential written out there; Z_i summed in
+ * float64 in an order that depends on N alone; the loss summed by the chunk rule of rlap_amd/csrc/rlap_spmm.h.  The backward call
+ * recomputes the similarities with the same chain.  So the same input gives the same bits, whatever the arena held; no atomic
+ * touches a floating-point value; neither call synchronises with the host; memory is O(N F): the similarities are never stored.
+ * Features that are not finite are not looked for (that would cost a synchronisation): they give a NaN loss, as in torch.
+ * tau outside its range (or not a number), N < 1, F < 1, a null pointer or a flag that is not this call's: RLAP_E_BAD_ARG.  F > 512 or
+ * N >= 2^31: RLAP_E_TOO_LARGE.  Scratch from the arena (RLAP_E_WORKSPACE when a caller-provided one is too small, the
+ * workspace-needed query saying how much). */
+enum { RLAP_INFONCE_POSITIVE_RAW = 1 };
+typedef struct {
+    int64_t rows;             /* N                                                                    */
+    int64_t features;         /* F                                                                    */
+    int64_t parts;            /* contiguous parts the column tiles are dealt into: a function of N    */
+    int64_t arena_bytes;      /* scratch bytes of the call                                            */
+    int32_t host_syncs;       /* host synchronisations of the call: 0                                 */
+    int32_t pad;
+} rlap_infonce_info;
+
+int rlap_infonce(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double tau, int flags, double* d_loss,
+                 double* d_rows, double* d_z, rlap_infonce_info* h_info);
+int rlap_infonce_backward(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double tau, int flags,
+                          const double* d_z, const double* d_g, float* d_ga, float* d_gb, rlap_infonce_info* h_info);
+
 /* The op with the step BEFORE the path fused in (scripts/node_shared.py:326-327,
  * scripts/augmentor_benchmarks.py:77-78):
  *   symmetrize != 0 : the input holds every undirected edge in one or both directions; (b,a) is

@@ -22,7 +22,7 @@ EXPORTS = [
     "rlap_approx_chol_views_depths", "rlap_snapshot_stats", "rlap_snapshot_ppr", "rlap_snapshot_subgraph",
     "rlap_snapshot_gcn_norm", "rlap_snapshot_propagate",
     "rlap_snapshot_plan_bytes", "rlap_snapshot_plan_build", "rlap_snapshot_plan_propagate", "rlap_edge_plan_build",
-    "rlap_graph_readout", "rlap_graph_readout_backward",
+    "rlap_graph_readout", "rlap_graph_readout_backward", "rlap_infonce", "rlap_infonce_backward",
 ]
 
 E_INDEX_RANGE = 2   # RLAP_E_INDEX_RANGE
@@ -42,6 +42,8 @@ PLAN_FORWARD, PLAN_TRANSPOSED = 256, 512
 PLAN_MAGIC = 0x504C414E   # rlap_plan_desc.magic of a successful build
 # rlap_graph_readout flags
 READOUT_MEAN, READOUT_X_F32 = 1, 32
+# rlap_infonce flags
+INFONCE_POSITIVE_RAW = 1
 
 # rlap_stats.elim_kernel
 KERNEL_NONE, KERNEL_ROUND, KERNEL_FLOW = 0, 1, 2
@@ -144,6 +146,14 @@ class ReadoutInfo(_Report):
     ]
 
 
+class InfonceInfo(_Report):
+    """rlap_infonce_info (include/rlap_hip.h)."""
+    _fields_ = [
+        ("rows", ctypes.c_int64), ("features", ctypes.c_int64), ("parts", ctypes.c_int64), ("arena_bytes", ctypes.c_int64),
+        ("host_syncs", ctypes.c_int32), ("pad", ctypes.c_int32),
+    ]
+
+
 def load():
     """dlopen the library and declare prototypes. Raises if it is not built."""
     global _lib
@@ -208,6 +218,10 @@ def load():
     lib.rlap_graph_readout.argtypes = [vp, vp, i64, i64, i64, vp, i64, ci, vp, ctypes.POINTER(ReadoutInfo)]
     lib.rlap_graph_readout_backward.restype = ci
     lib.rlap_graph_readout_backward.argtypes = lib.rlap_graph_readout.argtypes
+    lib.rlap_infonce.restype = ci
+    lib.rlap_infonce.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ci, vp, vp, vp, ctypes.POINTER(InfonceInfo)]
+    lib.rlap_infonce_backward.restype = ci
+    lib.rlap_infonce_backward.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ci, vp, vp, vp, vp, ctypes.POINTER(InfonceInfo)]
     lib.rlap_approx_chol_views.restype = ci
     lib.rlap_approx_chol_views.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, vp, ci, ci, vp, u64, vp, i64, vp,
                                            ctypes.POINTER(Stats)]

@@ -18,6 +18,8 @@ Mirrors of the reference's L2 adapters that keep everything on the GPU:
                   `.snapshots(g, node_ptr=)` on rLapViews / rLapDepths eliminates every graph of the batch in the one call;
                   `Snapshots.aggregate(x)` is GIN's plain neighbour sum, `SnapshotGINConv` the layer on it, and
                   `Snapshots.readout(z)` the per-graph sum of global_add_pool (ops.graph_readout)
+  * `NodeContrast` -- the contrastive loss of the node-level step (scripts/node_shared.py: DualBranchContrast(InfoNCEBatched(tau),
+                  mode="L2L")) on the embeddings of two views, fused on the device (ops.info_nce)
   * `rLapChain` -- the chain of scripts/rlap_vc_spectral.py: eliminate, relabel the survivors 0..k-1, eliminate again
 PyGCL / DGL are optional: with them installed the classes return their graph types,
 without them a small named tuple with the same fields.
@@ -211,6 +213,28 @@ class SnapshotGINConv(torch.nn.Module):
 
     def forward(self, x, snapshots):
         return self.nn((1 + self.eps).to(x.dtype) * x + snapshots.aggregate(x))
+
+
+class NodeContrast(torch.nn.Module):
+    """The contrastive loss of the node-level training step: forward(h1, h2) = 0.5 * (info_nce(h1, h2) + info_nce(h2, h1)), what
+    DualBranchContrast(InfoNCEBatched(tau, batch_size), mode="L2L") of scripts/node_shared.py computes, by two ops.info_nce calls
+    (no N x N matrix, fixed summation order, memory O(N F)).  h1, h2 are (N, F) float32 embeddings of two views; given one
+    (L, N, F) tensor of L >= 2 views, as SnapshotGCNConv returns it, forward(h) contrasts view 0 with view 1.  `positive="raw"`
+    (the default) restates the reference's InfoNCEBatched, whose positive term s_ii is not divided by tau; "scaled" is GCL's
+    InfoNCE.  The loss is a 0-dim float64 tensor; gradients reach both views."""
+
+    def __init__(self, tau: float = 0.4, positive: str = "raw"):
+        super().__init__()
+        self.tau, self.positive = tau, positive
+
+    def forward(self, h1, h2=None):
+        if h2 is None:
+            if not isinstance(h1, torch.Tensor) or h1.dim() != 3 or h1.shape[0] < 2:
+                raise ValueError("NodeContrast: two (N, F) embeddings, or one (L, N, F) tensor of L >= 2 views")
+            h1, h2 = h1[0], h1[1]
+        l1 = ops.info_nce(h1, h2, tau=self.tau, positive=self.positive)
+        l2 = ops.info_nce(h2, h1, tau=self.tau, positive=self.positive)
+        return 0.5 * (l1 + l2)
 
 
 def graph_plan(g, fill_value: float = 1.0, directions: str = "both"):

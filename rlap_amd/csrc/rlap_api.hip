@@ -29,6 +29,8 @@
 #include "rlap_spmm.h"
 #include "rlap_readout.h"
 #include "rlap_readout_api.h"
+#include "rlap_infonce.h"
+#include "rlap_infonce_api.h"
 
 using namespace rlap;
 
@@ -1598,6 +1600,55 @@ int rlap_graph_readout_backward(rlap_handle h, const void* d_gy, int64_t L, int6
         if (h->poison >= 0 && L * num_nodes * F > 0)
             RLAP_HIPCHK(hipMemsetAsync(d_gx, h->poison, (size_t)(L * num_nodes * F) * ((flags & RLAP_READOUT_X_F32) ? 4 : 8), h->stream));
         return readout_backward_run(h->stream, a);
+    });
+}
+
+namespace {
+
+// what both InfoNCE exports check (their pointers come before this)
+int infonce_check(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double tau, int flags, rlap_infonce_info* h_info) {
+    if (h_info) *h_info = rlap_infonce_info{};
+    if (!h || !d_a || !d_b || N < 1 || F < 1 || !infonce::tau_ok(tau)) return RLAP_E_BAD_ARG;
+    if (flags & ~RLAP_INFONCE_POSITIVE_RAW) return RLAP_E_BAD_ARG;
+    if (F > infonce::MAX_F || N >= (int64_t)1 << 31) return RLAP_E_TOO_LARGE;
+    if (h_info) { h_info->rows = N; h_info->features = F; h_info->parts = infonce::num_parts(N); }
+    return RLAP_OK;
+}
+
+}  // namespace
+
+int rlap_infonce(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double tau, int flags, double* d_loss,
+                 double* d_rows, double* d_z, rlap_infonce_info* h_info) {
+    if (const int rc = infonce_check(h, d_a, d_b, N, F, tau, flags, h_info)) return rc;
+    if (!d_loss || !d_rows || !d_z) return RLAP_E_BAD_ARG;
+    InfonceArgs a{};
+    a.a = d_a; a.b = d_b; a.N = N; a.F = F; a.tau = tau; a.flags = flags; a.loss = d_loss; a.rows = d_rows; a.z = d_z;
+    return snapshot_call(h, [&] { return infonce_bytes(N, F); }, [&](void* base, size_t have, size_t need) -> int {
+        if (h->poison >= 0) {   // debug: the result must not depend on what the arena or the result buffers held
+            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_loss, h->poison, 8, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_rows, h->poison, (size_t)N * 8, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_z, h->poison, (size_t)N * 8, h->stream));
+        }
+        if (h_info) h_info->arena_bytes = (int64_t)need;
+        return infonce_run(h->stream, base, have, a);
+    });
+}
+
+int rlap_infonce_backward(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double tau, int flags,
+                          const double* d_z, const double* d_g, float* d_ga, float* d_gb, rlap_infonce_info* h_info) {
+    if (const int rc = infonce_check(h, d_a, d_b, N, F, tau, flags, h_info)) return rc;
+    if (!d_z || !d_g || !d_ga || !d_gb) return RLAP_E_BAD_ARG;
+    InfonceArgs a{};
+    a.a = d_a; a.b = d_b; a.N = N; a.F = F; a.tau = tau; a.flags = flags; a.z_in = d_z; a.g = d_g; a.ga = d_ga; a.gb = d_gb;
+    return snapshot_call(h, [&] { return infonce_backward_bytes(N, F); }, [&](void* base, size_t have, size_t need) -> int {
+        if (h->poison >= 0) {
+            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_ga, h->poison, (size_t)(N * F) * 4, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_gb, h->poison, (size_t)(N * F) * 4, h->stream));
+        }
+        if (h_info) h_info->arena_bytes = (int64_t)need;
+        return infonce_backward_run(h->stream, base, have, a);
     });
 }
 

@@ -1,0 +1,154 @@
+// rlap_infonce.h -- the rule of the fused InfoNCE contrastive loss (rlap_infonce / rlap_infonce_backward, rlap_infonce.hip,
+// DESIGN 4.15): every value of the call and the order of every sum.  Plain __host__ __device__ functions without any HIP dependency,
+// as rlap_spmm.h: tests/csrc/infonce_mirror.cc compiles this file with g++ (contraction off, as the library) and computes the same
+// bits; tests/csrc/infonce_main.cc runs the index arithmetic under the sanitizers; the kernels read the same functions.
+//
+// Inputs: a (anchor) and b (sample), (N, F) float32, and tau in [1/32, 1024].  The positive of row i is column i; every column, the
+// positive included, is in the denominator (the L2L / G2G sampler with intraview_negs=False).
+//
+//   normalisation   n2_i = sum over k = 0 .. F-1, in order, of (double)a_ik * (double)a_ik (product rounded, add rounded);
+//                   nrm_i = max(sqrt(n2_i), 1e-12);  ah_ik = (float)((double)a_ik / nrm_i); the same for bh.  A zero row stays zero.
+//   similarity      s_ij = the float32 fmaf chain over k = 0 .. F-1 in increasing k from +0: acc = fmaf(ah_ik, bh_jk, acc) -- what
+//                   v_mfma_f32_32x32x2_f32 computes.  Zero columns behind F leave the chain's value as it is (fmaf(0, 0, x) = x; a
+//                   -0 may become +0, and the sign of a zero s reaches no result: s enters as s - 1 and as c * s - inv_tau).
+//   exponent        e_ij = expw((s_ij - 1) * (float)(1 / tau)): |s| <= 1 up to rounding, so the shift by 1 bounds the row maximum
+//                   and no rescaling is needed; expw is written out below, its argument stays in [-64, 0] and e stays normal.
+//   row sum         Z_i over the 32-column tiles of the samples, T = ceil(N / 32), dealt into num_parts(N) contiguous parts
+//                   (tiles [part_begin(N, p), part_begin(N, p + 1))).  Inside a part two float64 sums run, one per lane half h:
+//                   half h adds (double)e_ij of the columns j = 32 t + reg_row(r, h), r = 0 .. 15 in order, tile after tile
+//                   (columns >= N are left out).  The part's sum is half 0 + half 1; Z_i = 0 + part 0 + part 1 + ... in order.
+//                   The order depends on N alone.
+//   row term        row_i = c * (double)s_ii - 1 / tau - log(Z_i), c = 1 / tau ("scaled", GCL's InfoNCE) or c = 1 ("raw",
+//                   the reference's InfoNCEBatched, whose first term is not divided by tau).
+//   loss            -(sum of row_i by rlap_spmm.h's chunk rule: chunks of 256 rows in order, chunk sums added in order) / N.
+//   backward        with the upstream gradient g:  p_ij = e_ij * (float)(1 / Z_i);
+//                   D_ik  = sum over j of p_ij bh_jk   (owner: the anchor i, stream: the samples j)
+//                   D'_jk = sum over i of p_ij ah_ik   (owner: the sample j, stream: the anchors i)
+//                   as float32 fmaf chains over the STREAM index, from +0 per part: the parts and their tiles as above; inside tile
+//                   t the stream rows come in the order 32 t + reg_row(r, h), r = 0 .. 15 outside, h = 0, 1 inside (rows
+//                   0 4 1 5 2 6 3 7 8 12 ...: a 32x32 accumulator tile fed to the next 32x32x2 MFMA as its A operand); a row
+//                   >= N takes its turn as fmaf(0, 0, acc).  D = 0 + part 0 + part 1 + ... in float32.  Then in float64
+//                   Gh_ik = gs * (c * bh_ik - (1 / tau) * D_ik), gs = -(g / N);  dot_i = sum over k in order of ah_ik * Gh_ik;
+//                   ga_ik = (float)((Gh_ik - ah_ik * dot_i) / nrm_i), or (float)(Gh_ik / 1e-12) where sqrt(n2_i) < 1e-12 (the
+//                   clamp of F.normalize passes no gradient to the norm).  The same for gb with the roles swapped.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "rlap_spmm.h"
+
+namespace rlap {
+namespace infonce {
+
+constexpr int TILE = 32;                  // rows and columns of a similarity tile (one 32x32 MFMA accumulator)
+constexpr int MAX_F = 512;                // feature columns of a call
+constexpr int BLOCK_TILES = 4;            // owner tiles of a workgroup (one per wave)
+constexpr int64_t TARGET_GROUPS = 256;    // workgroups a call aims at when N is small: what num_parts() is made from
+constexpr double NORM_EPS = 1e-12;        // F.normalize's eps
+
+RLAP_SPMM_HD bool tau_ok(double tau) { return tau >= 1.0 / 32.0 && tau <= 1024.0; }   // (false for a NaN)
+
+// the 32-row tiles of N rows, the workgroups' row blocks, the padded sizes of the arena's copies
+RLAP_SPMM_HD int64_t num_tiles(int64_t N) { return N > 0 ? (N + TILE - 1) / TILE : 0; }
+RLAP_SPMM_HD int64_t row_blocks(int64_t N) { return (num_tiles(N) + BLOCK_TILES - 1) / BLOCK_TILES; }
+RLAP_SPMM_HD int64_t padded_rows(int64_t N) { return num_tiles(N) * TILE; }
+RLAP_SPMM_HD int padded_features(int64_t F) { return (int)((F + TILE - 1) / TILE) * TILE; }
+
+// The parts of the stream tiles: a function of N alone.  As many as bring the row blocks up to TARGET_GROUPS workgroups, at most
+// one per tile.
+RLAP_SPMM_HD int64_t num_parts(int64_t N) {
+    const int64_t T = num_tiles(N), rb = row_blocks(N);
+    if (T < 1) return 1;
+    const int64_t p = (TARGET_GROUPS + rb - 1) / rb;
+    return p < 1 ? 1 : (p > T ? T : p);
+}
+RLAP_SPMM_HD int64_t part_begin(int64_t N, int64_t p) { return p * num_tiles(N) / num_parts(N); }   // (T < 2^26, p <= 256)
+
+// row of a 32x32 accumulator tile that register r of a lane of half h holds (the tile's column is lane & 31)
+RLAP_SPMM_HD int reg_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+// where element (row i, column k) of a normalised copy lies in its FRAGMENT image: tile by tile, eight columns (four k-pairs) by
+// eight columns, 64 lanes x 4 floats -- a lane's 16 bytes are its operands of four consecutive 32x32x2 MFMAs (lane = 32 (k & 1) + row)
+RLAP_SPMM_HD int64_t frag_offset(int64_t i, int k, int Fp) {
+    const int64_t t = i >> 5;
+    const int r = (int)(i & 31), q = k >> 1;
+    return ((t * (Fp >> 3) + (q >> 2)) * 64 + (k & 1) * 32 + r) * 4 + (q & 3);
+}
+
+// ---- the values
+RLAP_SPMM_HD double norm2_step(double acc, float x) {
+    const double t = (double)x * (double)x;
+    return acc + t;
+}
+RLAP_SPMM_HD double norm2(const float* row, int64_t F) {
+    double n2 = 0.0;
+    for (int64_t k = 0; k < F; ++k) n2 = norm2_step(n2, row[k]);
+    return n2;
+}
+RLAP_SPMM_HD double norm_of(double n2) {
+    const double r = sqrt(n2);
+    return r > NORM_EPS ? r : NORM_EPS;   // (a row that holds a NaN keeps it in hat(): the loss is then NaN, as in torch)
+}
+RLAP_SPMM_HD bool norm_clamped(double n2) { return sqrt(n2) < NORM_EPS; }
+RLAP_SPMM_HD float hat(float x, double nrm) { return (float)((double)x / nrm); }
+
+RLAP_SPMM_HD float sim_step(float acc, float x, float y) { return fmaf(x, y, acc); }
+
+RLAP_SPMM_HD double inv_tau(double tau) { return 1.0 / tau; }
+RLAP_SPMM_HD float inv_tau_f(double tau) { return (float)inv_tau(tau); }
+RLAP_SPMM_HD float exp_arg(float s, float itf) { return (s - 1.0f) * itf; }
+
+// exp(x) in float32 for x in [-64, 0] (any x in [-87, 88] in fact): n = x / ln 2 rounded to nearest by the 1.5 * 2^23 shift, r = x - n ln 2
+// in two fmaf steps, the degree-7 Taylor polynomial in Horner form, 2^n added to the exponent bits.  IEEE operations only.
+RLAP_SPMM_HD float expw(float x) {
+    const float shift = 12582912.0f;
+    const float t = x * 1.44269504088896341f + shift;
+    const float n = t - shift;
+    float r = fmaf(n, -0.693359375f, x);
+    r = fmaf(n, 2.12194440e-4f, r);
+    float p = 1.0f / 5040.0f;
+    p = fmaf(p, r, 1.0f / 720.0f);
+    p = fmaf(p, r, 1.0f / 120.0f);
+    p = fmaf(p, r, 1.0f / 24.0f);
+    p = fmaf(p, r, 1.0f / 6.0f);
+    p = fmaf(p, r, 0.5f);
+    p = fmaf(p, r, 1.0f);
+    p = fmaf(p, r, 1.0f);
+    int32_t bits;
+    memcpy(&bits, &p, 4);
+    bits += (int32_t)n * (1 << 23);
+    memcpy(&p, &bits, 4);
+    return p;
+}
+
+RLAP_SPMM_HD double row_term(double c, float sii, double itau, double Z) {
+    const double t = c * (double)sii;
+    const double u = t - itau;
+    return u - log(Z);
+}
+RLAP_SPMM_HD double positive_coef(bool raw, double tau) { return raw ? 1.0 : inv_tau(tau); }
+RLAP_SPMM_HD double loss_of(double total, int64_t N) { return -total / (double)N; }
+
+RLAP_SPMM_HD float recip_z(double Z) { return (float)(1.0 / Z); }
+RLAP_SPMM_HD float prob(float e, float rz) { return e * rz; }
+
+RLAP_SPMM_HD double grad_scale(double g, int64_t N) { return -(g / (double)N); }
+// the gradient with respect to a normalised element: `other` is the element of the other view's row, D the chain's sum
+RLAP_SPMM_HD double grad_hat(double gs, double c, float other, double itau, float D) {
+    const double t = c * (double)other;
+    const double u = itau * (double)D;
+    return gs * (t - u);
+}
+RLAP_SPMM_HD double dot_step(double acc, float h, double G) {
+    const double t = (double)h * G;
+    return acc + t;
+}
+RLAP_SPMM_HD float grad_in(double G, float h, double dot, double nrm, bool clamped) {
+    if (clamped) return (float)(G / NORM_EPS);
+    const double t = (double)h * dot;
+    return (float)((G - t) / nrm);
+}
+
+}  // namespace infonce
+}  // namespace rlap

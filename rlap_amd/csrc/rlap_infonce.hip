@@ -1,0 +1,381 @@
+// rlap_infonce.hip -- the fused InfoNCE contrastive loss, forward and backward (rlap_infonce / rlap_infonce_backward):
+// DualBranchContrast(InfoNCEBatched(tau), mode="L2L") of the node-level training step without the N x N similarity matrix.  The
+// similarities come from v_mfma_f32_32x32x2_f32 -- bit for bit a k-ordered float32 fmaf chain --, live in registers and are never
+// written to memory; every sum has the fixed order of rlap_infonce.h; the backward pass recomputes the similarities with the same
+// chain.  Memory is O(N F).  A translation unit of its own.
+//
+//   pre-pass   the float64 squared norms (one thread per row, sequential as the rule says), then the normalised copies ah, bh in the
+//              arena, zero-padded to 32-row tiles and to a multiple of 32 columns, in two images: row-major, and the FRAGMENT image
+//              (infonce::frag_offset) in which the 16 bytes of a lane are its operands of four consecutive MFMAs, so that a tile is
+//              one contiguous block that waves read 1 KiB an instruction.
+//   main       one template for the three kernels.  A workgroup of four waves OWNS four 32-row tiles (one per wave) of one input
+//              and walks the 32-row tiles of the other input, the STREAM, over its part of them (infonce::num_parts: small N is
+//              split so that the chip fills); a stream tile's fragment image (backward: and its row-major image) is staged through
+//              LDS once for the four waves: 32 KB (64 KB) at F = 256, 64 KB (128 KB) at F = 512.
+//              Per tile a wave computes X[stream row][owner row] = the chain over F -- stream as the A operand, owner as B, so the
+//              owner is on the lane and the stream rows are in the 16 registers (infonce::reg_row).
+//                forward   e = expw((X - 1) / tau) added in register order into the lane's float64 sum; the diagonal is kept.
+//                backward  p = e * (1 / Z_anchor); the accumulator tile is then the A operand of the next MFMAs as it stands
+//                          (register r of the two lane halves holds stream rows reg_row(r, 0), reg_row(r, 1): the k pair of
+//                          step r), the B operand being the stream's row-major image in LDS: D[owner row][32 columns] per feature tile,
+//                          F / 32 accumulator tiles per wave (256 registers at F = 512, the AGPR half included).
+//              anchor-owner and sample-owner backward kernels are the same code with the inputs swapped; 1 / Z belongs to the
+//              anchor, which is the lane in one and the register's row in the other.
+//   finish     forward: Z = the part sums in order, the row terms, the chunk-rule sum of them, the loss.  backward: the part
+//              accumulators added in order, then the float64 push through the normalisation, one wave per row.
+// No float atomics, no host synchronisation, nothing allocated outside the arena.  Every address is formed from the padded sizes:
+// a wave whose owner tile lies behind the last one only takes part in the staging.
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/rlap_hip.h"
+#include "rlap_infonce.h"
+#include "rlap_infonce_api.h"
+#include "rlap_spmm.h"
+
+namespace rlap {
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int IN_THREADS = 256;                 // four waves: infonce::BLOCK_TILES owner tiles
+constexpr int64_t IN_MAX_GRID = 1 << 20;        // workgroups of an elementwise launch (the kernels stride)
+static_assert(IN_THREADS == 64 * infonce::BLOCK_TILES, "one wave per owner tile");
+
+inline unsigned in_blocks(int64_t n, int per_block) {
+    return (unsigned)std::min<int64_t>(IN_MAX_GRID, std::max<int64_t>(1, (n + per_block - 1) / per_block));
+}
+
+// ------------------------------------------------------------------------------------------------ pre-pass
+__global__ __launch_bounds__(256) void k_in_norms(const float* __restrict__ a, const float* __restrict__ b, int64_t N, int64_t F,
+                                                  double* __restrict__ n2a, double* __restrict__ n2b) {
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < 2 * N; t += (int64_t)gridDim.x * blockDim.x) {
+        const bool second = t >= N;
+        const int64_t i = second ? t - N : t;
+        (second ? n2b : n2a)[i] = infonce::norm2((second ? b : a) + i * F, F);
+    }
+}
+
+// the normalised copy of x, padded with zeros: the fragment image and (rows != nullptr) the row-major image
+__global__ __launch_bounds__(256) void k_in_hats(const float* __restrict__ x, const double* __restrict__ n2, int64_t N, int64_t F,
+                                                 int64_t Np, int Fp, float* __restrict__ frag, float* __restrict__ rows) {
+    const int64_t elems = Np * Fp;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < elems; e += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = e / Fp;
+        const int k = (int)(e - i * Fp);
+        float v = 0.0f;
+        if (i < N && k < F) v = infonce::hat(x[i * F + k], infonce::norm_of(n2[i]));
+        frag[infonce::frag_offset(i, k, Fp)] = v;
+        if (rows) rows[e] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_in_recip(const double* __restrict__ z, int64_t N, int64_t Np, float* __restrict__ rz) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < Np; i += (int64_t)gridDim.x * blockDim.x)
+        rz[i] = i < N ? infonce::recip_z(z[i]) : 0.0f;
+}
+
+// ------------------------------------------------------------------------------------------------ main
+struct Main {
+    const float* own_frag; const float* str_frag;   // fragment images, Np x Fp each
+    const float* str_rows;                          // backward: the stream's row-major image
+    const float* rz;                                // backward: [Np] 1 / Z of the anchors, 0 behind N
+    float itf;                                      // (float)(1 / tau)
+    int64_t N, Np, T, RB; int parts; int Fp; int nft;
+    double* zpart; float* sdiag;                    // forward: [parts, Np] part sums of Z; [Np] the diagonal
+    float* partial;                                 // backward: [parts, Np, Fp] part accumulators
+};
+
+enum { IN_FORWARD = 0, IN_BACK_ANCHOR = 1, IN_BACK_SAMPLE = 2 };
+
+// X[stream row][owner row] of one tile pair: the chain over the padded columns, four MFMAs per 16 bytes of either operand
+__device__ inline f32x16 in_sim_tile(const float4* __restrict__ stream_lds, const float4* __restrict__ owner, int nqq, int lane) {
+    f32x16 x;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) x[r] = 0.0f;
+    for (int qq = 0; qq < nqq; ++qq) {
+        const float4 s = stream_lds[qq * 64 + lane];
+        const float4 o = owner[qq * 64 + lane];
+        x = __builtin_amdgcn_mfma_f32_32x32x2f32(s.x, o.x, x, 0, 0, 0);
+        x = __builtin_amdgcn_mfma_f32_32x32x2f32(s.y, o.y, x, 0, 0, 0);
+        x = __builtin_amdgcn_mfma_f32_32x32x2f32(s.z, o.z, x, 0, 0, 0);
+        x = __builtin_amdgcn_mfma_f32_32x32x2f32(s.w, o.w, x, 0, 0, 0);
+    }
+    return x;
+}
+
+template <int NFT, int MODE>
+__global__ __launch_bounds__(IN_THREADS) void k_in_main(Main a) {
+    extern __shared__ __attribute__((aligned(16))) float in_lds[];   // 32 x Fp floats: the stream tile's fragment image; backward: and its row-major image
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int c = lane & 31, h = lane >> 5;
+    const int64_t blk = (int64_t)blockIdx.x % a.RB, part = (int64_t)blockIdx.x / a.RB;
+    const int64_t ot = blk * infonce::BLOCK_TILES + wave;
+    const bool active = ot < a.T;                                    // (wave-uniform)
+    const int64_t tile_floats = (int64_t)infonce::TILE * a.Fp;
+    const int tile_vec = (int)(tile_floats >> 2), nqq = a.Fp >> 3;
+    const float4* __restrict__ owner = reinterpret_cast<const float4*>(a.own_frag + (active ? ot : 0) * tile_floats);
+    const int64_t orow = ot * infonce::TILE + c;                     // the lane's owner row (< Np when active)
+    const int64_t tb = infonce::part_begin(a.N, part), te = infonce::part_begin(a.N, part + 1);
+
+    double zsum = 0.0;
+    float rz_lane = 0.0f;
+    if (MODE == IN_BACK_ANCHOR && active) rz_lane = a.rz[orow];
+    f32x16 acc[NFT];
+    if (MODE != IN_FORWARD) {
+#pragma unroll
+        for (int ft = 0; ft < NFT; ++ft)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[ft][r] = 0.0f;
+    }
+
+#pragma unroll 1
+    for (int64_t t = tb; t < te; ++t) {
+        __syncthreads();   // (the previous tile has been read)
+        {
+            const float4* __restrict__ src = reinterpret_cast<const float4*>(a.str_frag + t * tile_floats);
+            float4* dst = reinterpret_cast<float4*>(in_lds);
+            for (int v = threadIdx.x; v < tile_vec; v += IN_THREADS) dst[v] = src[v];
+            if (MODE != IN_FORWARD) {
+                const float4* __restrict__ src2 = reinterpret_cast<const float4*>(a.str_rows + t * tile_floats);   // (rows 32 t .. 32 t + 31 are contiguous)
+                for (int v = threadIdx.x; v < tile_vec; v += IN_THREADS) dst[tile_vec + v] = src2[v];
+            }
+        }
+        __syncthreads();
+        if (!active) continue;
+        f32x16 x = in_sim_tile(reinterpret_cast<const float4*>(in_lds), owner, nqq, lane);
+        const int64_t srow0 = t * infonce::TILE;
+        if (MODE == IN_FORWARD) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int64_t srow = srow0 + infonce::reg_row(r, h);
+                const float e = infonce::expw(infonce::exp_arg(x[r], a.itf));
+                const double z2 = zsum + (double)e;
+                zsum = srow < a.N ? z2 : zsum;
+                if (srow == orow) a.sdiag[orow] = x[r];   // (once per owner row of the call: the tile t == ot of one part)
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int64_t srow = srow0 + infonce::reg_row(r, h);
+                const float e = infonce::expw(infonce::exp_arg(x[r], a.itf));
+                const float rz = MODE == IN_BACK_ANCHOR ? rz_lane : a.rz[srow];   // (srow < Np; 0 behind N)
+                const float p = infonce::prob(e, rz);
+                x[r] = srow < a.N ? p : 0.0f;
+            }
+            const float* brow = in_lds + (int)tile_floats + 4 * h * a.Fp + c;   // row reg_row(r, h) = reg_row(r, 0) + 4 h of the staged tile
+#pragma unroll
+            for (int ft = 0; ft < NFT; ++ft) {
+                if (ft < a.nft) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float bv = brow[infonce::reg_row(r, 0) * a.Fp + ft * infonce::TILE];
+                        acc[ft] = __builtin_amdgcn_mfma_f32_32x32x2f32(x[r], bv, acc[ft], 0, 0, 0);
+                    }
+                }
+            }
+        }
+    }
+
+    if (!active) return;
+    if (MODE == IN_FORWARD) {
+        const double other = __shfl_xor(zsum, 32);
+        if (h == 0) a.zpart[part * a.Np + orow] = zsum + other;      // half 0 + half 1
+    } else {
+        float* __restrict__ out = a.partial + (part * a.Np + ot * infonce::TILE) * a.Fp + c;
+#pragma unroll
+        for (int ft = 0; ft < NFT; ++ft) {
+            if (ft < a.nft) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) out[(int64_t)infonce::reg_row(r, h) * a.Fp + ft * infonce::TILE] = acc[ft][r];
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ finish, forward
+__global__ __launch_bounds__(256) void k_in_rows(const double* __restrict__ zpart, const float* __restrict__ sdiag, int64_t N, int64_t Np,
+                                                 int parts, double c, double itau, double* __restrict__ z, double* __restrict__ rows) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
+        double Z = 0.0;
+        for (int p = 0; p < parts; ++p) Z = Z + zpart[p * Np + i];
+        z[i] = Z;
+        rows[i] = infonce::row_term(c, sdiag[i], itau, Z);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_in_chunks(const double* __restrict__ rows, int64_t N, double* __restrict__ csum) {
+    const int64_t nc = spmm::num_chunks(N);
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < nc; k += (int64_t)gridDim.x * blockDim.x)
+        csum[k] = spmm::chunk_sum(N, k, [](int64_t) { return 1.0; }, [&](int64_t e) { return rows[e]; });
+}
+
+__global__ void k_in_loss(const double* __restrict__ csum, int64_t N, double* __restrict__ loss) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    double total = 0.0;
+    for (int64_t k = 0; k < spmm::num_chunks(N); ++k) total = total + csum[k];
+    *loss = infonce::loss_of(total, N);
+}
+
+// ------------------------------------------------------------------------------------------------ finish, backward
+// one wave per owner row, lanes along the columns: the part accumulators are added once, in part order, and the gradient of the
+// normalised row is kept in LDS; every lane then takes the dot product over it in column order (the same chain on every lane, the
+// LDS reads broadcast), and the lanes push their columns through the normalisation in float64
+constexpr int IN_GRAD_WAVES = 4;
+__global__ __launch_bounds__(64 * IN_GRAD_WAVES) void k_in_grad(const float* __restrict__ partial, int parts, int64_t N, int64_t F, int64_t Np, int Fp,
+                                                                const float* __restrict__ own_rows, const float* __restrict__ other_rows,
+                                                                const double* __restrict__ n2, const double* __restrict__ g, double c, double itau,
+                                                                float* __restrict__ out) {
+    __shared__ double gh[IN_GRAD_WAVES][infonce::MAX_F];
+    __shared__ float oh[IN_GRAD_WAVES][infonce::MAX_F];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const double gs = infonce::grad_scale(*g, N);
+    for (int64_t base = (int64_t)blockIdx.x * IN_GRAD_WAVES; base < N; base += (int64_t)gridDim.x * IN_GRAD_WAVES) {   // (the same turns for every wave)
+        const int64_t i = base + wave;
+        const bool live = i < N;
+        if (live) {
+            for (int k = lane; k < F; k += 64) {
+                float D = 0.0f;
+                for (int p = 0; p < parts; ++p) D = D + partial[(p * Np + i) * Fp + k];
+                gh[wave][k] = infonce::grad_hat(gs, c, other_rows[i * Fp + k], itau, D);
+                oh[wave][k] = own_rows[i * Fp + k];
+            }
+        }
+        __syncthreads();
+        if (live) {
+            const bool clamped = infonce::norm_clamped(n2[i]);
+            const double nrm = infonce::norm_of(n2[i]);
+            double dot = 0.0;
+            for (int k = 0; k < F; ++k) dot = infonce::dot_step(dot, oh[wave][k], gh[wave][k]);
+            for (int k = lane; k < F; k += 64) out[i * F + k] = infonce::grad_in(gh[wave][k], oh[wave][k], dot, nrm, clamped);
+        }
+        __syncthreads();   // (the row has been read before the next one is written)
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ host
+struct Bufs {
+    double *n2a, *n2b;
+    float *a_frag, *b_frag, *a_rows, *b_rows;
+    double* zpart; float* sdiag; double* csum;
+    float* rz; float *part_a, *part_b;
+};
+
+size_t carve_infonce(Carve& C, int64_t N, int64_t F, bool backward, Bufs& B) {
+    const int64_t Np = infonce::padded_rows(N), Fp = infonce::padded_features(F), parts = infonce::num_parts(N);
+    B = Bufs{};
+    B.n2a = C.take<double>(Np);
+    B.n2b = C.take<double>(Np);
+    B.a_frag = C.take<float>(Np * Fp);
+    B.b_frag = C.take<float>(Np * Fp);
+    if (!backward) {
+        B.zpart = C.take<double>(parts * Np);
+        B.sdiag = C.take<float>(Np);
+        B.csum = C.take<double>(spmm::num_chunks(N));
+    } else {
+        B.a_rows = C.take<float>(Np * Fp);
+        B.b_rows = C.take<float>(Np * Fp);
+        B.rz = C.take<float>(Np);
+        B.part_a = C.take<float>(parts * Np * Fp);
+        B.part_b = C.take<float>(parts * Np * Fp);
+    }
+    return C.off + 256;
+}
+
+Main main_args(const InfonceArgs& g) {
+    Main m{};
+    m.itf = infonce::inv_tau_f(g.tau);
+    m.N = g.N; m.Np = infonce::padded_rows(g.N); m.T = infonce::num_tiles(g.N); m.RB = infonce::row_blocks(g.N);
+    m.parts = (int)infonce::num_parts(g.N);
+    m.Fp = infonce::padded_features(g.F); m.nft = m.Fp / infonce::TILE;
+    return m;
+}
+
+template <int NFT, int MODE>
+int launch_main_t(hipStream_t st, const Main& m) {
+    const size_t lds = (size_t)infonce::TILE * m.Fp * sizeof(float) * (MODE == IN_FORWARD ? 1 : 2);
+    auto* fn = &k_in_main<NFT, MODE>;
+    RLAP_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_in_main<NFT, MODE>), dim3((unsigned)(m.RB * m.parts)), dim3(IN_THREADS), lds, st, m);
+    RLAP_HIPCHK(hipGetLastError());
+    return RLAP_OK;
+}
+
+template <int MODE>
+int launch_backward_main(hipStream_t st, const Main& m) {
+    if (m.nft <= 1) return launch_main_t<1, MODE>(st, m);
+    if (m.nft <= 2) return launch_main_t<2, MODE>(st, m);
+    if (m.nft <= 4) return launch_main_t<4, MODE>(st, m);
+    if (m.nft <= 8) return launch_main_t<8, MODE>(st, m);
+    return launch_main_t<16, MODE>(st, m);
+}
+
+int prepass(hipStream_t st, const InfonceArgs& g, const Bufs& B) {
+    const int64_t Np = infonce::padded_rows(g.N);
+    const int Fp = infonce::padded_features(g.F);
+    hipLaunchKernelGGL(k_in_norms, dim3(in_blocks(2 * g.N, 256)), dim3(256), 0, st, g.a, g.b, g.N, g.F, B.n2a, B.n2b);
+    hipLaunchKernelGGL(k_in_hats, dim3(in_blocks(Np * Fp, 256)), dim3(256), 0, st, g.a, (const double*)B.n2a, g.N, g.F, Np, Fp, B.a_frag, B.a_rows);
+    hipLaunchKernelGGL(k_in_hats, dim3(in_blocks(Np * Fp, 256)), dim3(256), 0, st, g.b, (const double*)B.n2b, g.N, g.F, Np, Fp, B.b_frag, B.b_rows);
+    RLAP_HIPCHK(hipGetLastError());
+    return RLAP_OK;
+}
+
+}  // namespace
+
+size_t infonce_bytes(int64_t N, int64_t F) {
+    Carve C{nullptr, 0};
+    Bufs B;
+    return carve_infonce(C, N, F, false, B);
+}
+
+size_t infonce_backward_bytes(int64_t N, int64_t F) {
+    Carve C{nullptr, 0};
+    Bufs B;
+    return carve_infonce(C, N, F, true, B);
+}
+
+int infonce_run(hipStream_t st, void* ws, size_t ws_bytes, const InfonceArgs& g) {
+    Bufs B;
+    Carve C{static_cast<char*>(ws), 0};
+    if (carve_infonce(C, g.N, g.F, false, B) > ws_bytes) return RLAP_E_WORKSPACE;
+    if (const int rc = prepass(st, g, B)) return rc;
+    Main m = main_args(g);
+    m.own_frag = B.a_frag; m.str_frag = B.b_frag; m.zpart = B.zpart; m.sdiag = B.sdiag;
+    if (const int rc = launch_main_t<1, IN_FORWARD>(st, m)) return rc;
+    const double c = infonce::positive_coef((g.flags & RLAP_INFONCE_POSITIVE_RAW) != 0, g.tau), itau = infonce::inv_tau(g.tau);
+    hipLaunchKernelGGL(k_in_rows, dim3(in_blocks(g.N, 256)), dim3(256), 0, st, (const double*)B.zpart, (const float*)B.sdiag, g.N, m.Np, m.parts,
+                       c, itau, g.z, g.rows);
+    hipLaunchKernelGGL(k_in_chunks, dim3(in_blocks(spmm::num_chunks(g.N), 256)), dim3(256), 0, st, (const double*)g.rows, g.N, B.csum);
+    hipLaunchKernelGGL(k_in_loss, dim3(1), dim3(64), 0, st, (const double*)B.csum, g.N, g.loss);
+    RLAP_HIPCHK(hipGetLastError());
+    return RLAP_OK;
+}
+
+int infonce_backward_run(hipStream_t st, void* ws, size_t ws_bytes, const InfonceArgs& g) {
+    Bufs B;
+    Carve C{static_cast<char*>(ws), 0};
+    if (carve_infonce(C, g.N, g.F, true, B) > ws_bytes) return RLAP_E_WORKSPACE;
+    if (const int rc = prepass(st, g, B)) return rc;
+    Main m = main_args(g);
+    hipLaunchKernelGGL(k_in_recip, dim3(in_blocks(m.Np, 256)), dim3(256), 0, st, g.z_in, g.N, m.Np, B.rz);
+    RLAP_HIPCHK(hipGetLastError());
+    m.rz = B.rz;
+    const double c = infonce::positive_coef((g.flags & RLAP_INFONCE_POSITIVE_RAW) != 0, g.tau), itau = infonce::inv_tau(g.tau);
+    // the anchors own, the samples stream: D = sum_j p_ij bh_j
+    m.own_frag = B.a_frag; m.str_frag = B.b_frag; m.str_rows = B.b_rows; m.partial = B.part_a;
+    if (const int rc = launch_backward_main<IN_BACK_ANCHOR>(st, m)) return rc;
+    // the samples own, the anchors stream: D' = sum_i p_ij ah_i
+    m.own_frag = B.b_frag; m.str_frag = B.a_frag; m.str_rows = B.a_rows; m.partial = B.part_b;
+    if (const int rc = launch_backward_main<IN_BACK_SAMPLE>(st, m)) return rc;
+    hipLaunchKernelGGL(k_in_grad, dim3(in_blocks(g.N, IN_GRAD_WAVES)), dim3(64 * IN_GRAD_WAVES), 0, st, (const float*)B.part_a, m.parts, g.N, g.F, m.Np, m.Fp,
+                       (const float*)B.a_rows, (const float*)B.b_rows, (const double*)B.n2a, g.g, c, itau, g.ga);
+    hipLaunchKernelGGL(k_in_grad, dim3(in_blocks(g.N, IN_GRAD_WAVES)), dim3(64 * IN_GRAD_WAVES), 0, st, (const float*)B.part_b, m.parts, g.N, g.F, m.Np, m.Fp,
+                       (const float*)B.b_rows, (const float*)B.a_rows, (const double*)B.n2b, g.g, c, itau, g.gb);
+    RLAP_HIPCHK(hipGetLastError());
+    return RLAP_OK;
+}
+
+}  // namespace rlap

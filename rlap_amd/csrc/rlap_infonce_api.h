@@ -1,0 +1,25 @@
+// rlap_infonce_api.h -- the fused InfoNCE loss (rlap_infonce / rlap_infonce_backward): the interface between
+// rlap_infonce.hip, which holds the kernels and their orchestration, and the C ABI in rlap_api.hip, which owns the handle, its lock
+// and its arena.  The rule is rlap_infonce.h's.
+#pragma once
+#include "rlap_snapshot.h"
+
+namespace rlap {
+
+struct InfonceArgs {
+    const float* a; const float* b; int64_t N, F;   // anchor and sample, (N, F) float32 on the device
+    double tau; int flags;                          // RLAP_INFONCE_POSITIVE_RAW (include/rlap_hip.h)
+    // forward: results
+    double* loss; double* rows; double* z;          // one double; N; N
+    // backward: the forward's row sums, the upstream scalar on the device; results (N, F) each
+    const double* z_in; const double* g; float* ga; float* gb;
+};
+
+// arena bytes of the two calls
+size_t infonce_bytes(int64_t N, int64_t F);
+size_t infonce_backward_bytes(int64_t N, int64_t F);
+// the calls on `stream`; no host synchronisation; return an RLAP_* status
+int infonce_run(hipStream_t stream, void* ws, size_t ws_bytes, const InfonceArgs& a);
+int infonce_backward_run(hipStream_t stream, void* ws, size_t ws_bytes, const InfonceArgs& a);
+
+}  // namespace rlap

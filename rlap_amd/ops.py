@@ -1191,6 +1191,118 @@ def graph_readout(x: Tensor, node_ptr: Union[Tensor, Sequence[int], GraphTable],
     return y if x.dim() == 3 else y[0]
 
 
+INFONCE_POSITIVE = {"scaled": 0, "raw": _lib.INFONCE_POSITIVE_RAW}
+INFONCE_MAX_F = 512
+INFONCE_TAU = (1.0 / 32.0, 1024.0)
+
+
+def _info_nce_args(anchor, sample, tau, positive):
+    """Host-side checks of info_nce, made before the device is touched: (tau, flags)."""
+    for t, what in ((anchor, "anchor"), (sample, "sample")):
+        if not isinstance(t, Tensor) or t.dim() != 2:
+            raise ValueError(f"{what}: a (num_nodes, F) tensor")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: torch.float32, got {t.dtype}")
+    if anchor.shape != sample.shape:
+        raise ValueError(f"anchor and sample: equal shapes, got {tuple(anchor.shape)} and {tuple(sample.shape)}")
+    n, f = int(anchor.shape[0]), int(anchor.shape[1])
+    if n < 1 or f < 1:
+        raise ValueError("anchor: at least one row and one feature column")
+    if f > INFONCE_MAX_F:
+        raise ValueError(f"anchor: at most {INFONCE_MAX_F} feature columns, got {f}")
+    if n >= 1 << 31:
+        raise ValueError("anchor: fewer than 2^31 rows")
+    if isinstance(tau, bool) or not isinstance(tau, (int, float)):
+        raise ValueError(f"tau: a number, got {tau!r}")
+    tau = float(tau)
+    if not INFONCE_TAU[0] <= tau <= INFONCE_TAU[1]:
+        raise ValueError(f"tau: must lie in [{INFONCE_TAU[0]}, {INFONCE_TAU[1]}], got {tau!r}")
+    if not isinstance(positive, str) or positive not in INFONCE_POSITIVE:
+        raise ValueError(f"positive: one of {sorted(INFONCE_POSITIVE)}, got {positive!r}")
+    return tau, INFONCE_POSITIVE[positive]
+
+
+def _info_nce_call(export: str, dev, tail):
+    """One rlap_infonce / _backward call on the library's device: tail(info) gives the arguments behind the handle."""
+    global last_stats
+    lib, hobj = _handle_obj(dev)
+    fn = getattr(lib, export)
+    info = _lib.InfonceInfo()
+    st = _lib.Stats()
+    rc = _run(hobj, dev, 0, None, 1, False, lambda: fn(hobj.ptr, *tail, ctypes.byref(info)), st)
+    if rc in (1, 2, 3):
+        raise ValueError(f"rlap: {_lib.status_string(rc)}")
+    if rc != 0:
+        _raise(rc)
+    last_stats = info.as_dict()
+
+
+def _info_nce_forward(a: Tensor, b: Tensor, tau: float, flags: int):
+    """The forward export: (loss 0-dim, rows [N], z [N], the device copies of a and b)."""
+    dev = _device_for(a)
+    with torch.cuda.device(dev):
+        d_a = a.detach().to(device=dev).contiguous()
+        d_b = b.detach().to(device=dev).contiguous()
+        n, f = int(d_a.shape[0]), int(d_a.shape[1])
+        out = torch.empty(1 + 2 * n, dtype=torch.float64, device=dev)   # loss | rows | z
+        p = out.data_ptr()
+        _info_nce_call("rlap_infonce", dev, (d_a.data_ptr(), d_b.data_ptr(), n, f, tau, flags, p, p + 8, p + 8 * (1 + n)))
+    return out[0], out[1:1 + n], out[1 + n:], d_a, d_b
+
+
+class _InfoNCE(torch.autograd.Function):
+    """loss = the fused InfoNCE of (anchor, sample); the gradients with respect to both come from the backward export."""
+
+    @staticmethod
+    def forward(ctx, a, b, tau, flags):
+        loss, rows, z, d_a, d_b = _info_nce_forward(a, b, tau, flags)
+        ctx.save_for_backward(d_a, d_b, z)
+        ctx.call = (tau, flags, a.device, b.device)
+        ctx.mark_non_differentiable(rows)
+        return loss, rows
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_rows):
+        d_a, d_b, z = ctx.saved_tensors
+        tau, flags, dev_a, dev_b = ctx.call
+        dev = d_a.device
+        with torch.cuda.device(dev):
+            d_g = g.detach().to(device=dev, dtype=torch.float64).reshape(1).contiguous()
+            n, f = int(d_a.shape[0]), int(d_a.shape[1])
+            ga = torch.empty_like(d_a)
+            gb = torch.empty_like(d_b)
+            _info_nce_call("rlap_infonce_backward", dev, (d_a.data_ptr(), d_b.data_ptr(), n, f, tau, flags, z.data_ptr(), d_g.data_ptr(),
+                                                             ga.data_ptr(), gb.data_ptr()))
+        return ga.to(dev_a), gb.to(dev_b), None, None
+
+
+def info_nce(anchor: Tensor, sample: Tensor, tau: float = 0.4, positive: str = "scaled", return_rows: bool = False):
+    """The InfoNCE contrastive loss of two views' node embeddings, fused on the device (rlap_infonce): with the rows
+    normalised, s = ah bh^T, loss = -mean_i(c s_ii - log sum_j exp(s_ij / tau)) -- one direction of
+    DualBranchContrast(InfoNCEBatched(tau), mode="L2L") (scripts/node_shared.py) without the N x N similarity matrix.
+
+      anchor, sample : (N, F) float32 of equal shape, F <= 512, on any device (moved to the library's)
+      tau            : the temperature, in [1/32, 1024]
+      positive       : "scaled" -- c = 1 / tau, GCL's InfoNCE; "raw" -- c = 1, the reference's InfoNCEBatched, which does not
+                       divide the positive term by tau
+      return_rows    : also return the (N,) float64 row terms c s_ii - 1/tau - log Z_i (not differentiable)
+    Returns the 0-dim float64 loss.  The positive of row i is column i; every column is in the denominator.  Every value and the
+    order of every sum are fixed (rlap_amd/csrc/rlap_infonce.h): the same input gives the same bits.  Memory is O(N F).
+
+    Differentiable in both inputs (the backward recomputes the similarities, rlap_infonce_backward); double backward is not
+    supported.  Malformed arguments raise ValueError before the device is touched; features that are not finite give a NaN loss.
+    No host synchronisation.  `last_stats` then holds what the call did (rlap_infonce_info: rows, features, parts, arena_bytes,
+    host_syncs).
+    """
+    tau, flags = _info_nce_args(anchor, sample, tau, positive)
+    if torch.is_grad_enabled() and (anchor.requires_grad or sample.requires_grad):
+        loss, rows = _InfoNCE.apply(anchor, sample, tau, flags)
+    else:
+        loss, rows = _info_nce_forward(anchor, sample, tau, flags)[:2]
+    return (loss, rows) if return_rows else loss
+
+
 PLAN_DIRECTIONS = {"forward": _lib.PLAN_FORWARD, "transposed": _lib.PLAN_TRANSPOSED, "both": _lib.PLAN_FORWARD | _lib.PLAN_TRANSPOSED}
 
 
