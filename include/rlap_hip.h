@@ -564,6 +564,42 @@ int rlap_infonce(rlap_handle h, const float* d_a, const float* d_b, int64_t N, i
 int rlap_infonce_backward(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double tau, int flags,
                           const double* d_z, const double* d_g, float* d_ga, float* d_gb, rlap_infonce_info* h_info);
 
+/* The fused CCA-SSG loss of two views' node embeddings, forward and backward: the standardisation of
+ * CCA-SSG/model.py and the loss of CCA-SSG/main.py.  With z = (h - mean_0(h)) / std_0(h) (unbiased), c = z1^T z2 / N,
+ * c1 = z1^T z1 / N and c2 = z2^T z2 / N:  loss = -trace(c) + lambd * (||I - c1||_F^2 + ||I - c2||_F^2).
+ *   d_a, d_b, N, F : the two views' embeddings, (N, F) float32 row-major; N >= 2, 1 <= F <= 512
+ *   lambd          : the trade-off, finite and >= 0
+ *   flags          : reserved, 0
+ *   forward        : d_terms four doubles: loss, inv = -trace(c), dec1, dec2; d_colstat [4 F] doubles: the column means of d_a, their
+ *                    deviations, the means of d_b, their deviations; d_gram [2 F F] float32: r1 = I - c1 and r2 = I - c2, rounded
+ *                    from float64, exactly symmetric.  The backward call reads d_colstat and d_gram.
+ *   backward       : d_colstat, d_gram as the forward call left them; d_g the upstream gradient, one double ON THE DEVICE (so that
+ *                    no synchronisation is needed); d_ga, d_gb (N, F) float32, the gradients with respect to d_a and d_b
+ *   h_info         : (nullable) what the call did
+ * Every value and the order of every sum are defined in rlap_amd/csrc/rlap_cca.h: the column statistics in float64 in two passes;
+ * the Gram sums as float32 fmaf chains over the nodes in increasing order (what the f32 matrix-core instruction computes), per part
+ * of the rows, the parts a function of (N, F) alone and added in float64; the terms summed by the chunk rule of
+ * rlap_amd/csrc/rlap_spmm.h.  The backward call standardises again and does not repeat the Gram products.  So the same input gives
+ * the same bits, whatever the arena held; no atomic touches a floating-point value; neither call synchronises with the host.
+ * A column of zero variance divides by zero, as in the reference: the loss and the gradients are then NaN, and the status is
+ * RLAP_OK (looking for it would cost a synchronisation).  A null pointer, N < 2, F < 1, F > 512, a lambd that is negative or not
+ * finite, or flags other than 0: RLAP_E_BAD_ARG.  N >= 2^31: RLAP_E_TOO_LARGE.  Scratch from the arena (RLAP_E_WORKSPACE when a
+ * caller-provided one is too small, the workspace-needed query saying how much). */
+typedef struct {
+    int64_t rows;             /* N                                                                    */
+    int64_t features;         /* F                                                                    */
+    int64_t parts;            /* contiguous parts the rows are dealt into: a function of (N, F)       */
+    int64_t arena_bytes;      /* scratch bytes of the call                                            */
+    int32_t host_syncs;       /* host synchronisations of the call: 0                                 */
+    int32_t pad;
+} rlap_cca_info;
+
+int rlap_cca_loss(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double lambd, int flags, double* d_terms,
+                  double* d_colstat, float* d_gram, rlap_cca_info* h_info);
+int rlap_cca_loss_backward(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double lambd, int flags,
+                           const double* d_colstat, const float* d_gram, const double* d_g, float* d_ga, float* d_gb,
+                           rlap_cca_info* h_info);
+
 /* The op with the step BEFORE the path fused in (scripts/node_shared.py:326-327,
  * scripts/augmentor_benchmarks.py:77-78):
  *   symmetrize != 0 : the input holds every undirected edge in one or both directions; (b,a) is

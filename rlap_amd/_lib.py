@@ -23,6 +23,7 @@ EXPORTS = [
     "rlap_snapshot_gcn_norm", "rlap_snapshot_propagate",
     "rlap_snapshot_plan_bytes", "rlap_snapshot_plan_build", "rlap_snapshot_plan_propagate", "rlap_edge_plan_build",
     "rlap_graph_readout", "rlap_graph_readout_backward", "rlap_infonce", "rlap_infonce_backward",
+    "rlap_cca_loss", "rlap_cca_loss_backward",
 ]
 
 E_INDEX_RANGE = 2   # RLAP_E_INDEX_RANGE
@@ -154,6 +155,14 @@ class InfonceInfo(_Report):
     ]
 
 
+class CcaInfo(_Report):
+    """rlap_cca_info (include/rlap_hip.h)."""
+    _fields_ = [
+        ("rows", ctypes.c_int64), ("features", ctypes.c_int64), ("parts", ctypes.c_int64), ("arena_bytes", ctypes.c_int64),
+        ("host_syncs", ctypes.c_int32), ("pad", ctypes.c_int32),
+    ]
+
+
 def load():
     """dlopen the library and declare prototypes. Raises if it is not built."""
     global _lib
@@ -222,6 +231,10 @@ def load():
     lib.rlap_infonce.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ci, vp, vp, vp, ctypes.POINTER(InfonceInfo)]
     lib.rlap_infonce_backward.restype = ci
     lib.rlap_infonce_backward.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ci, vp, vp, vp, vp, ctypes.POINTER(InfonceInfo)]
+    lib.rlap_cca_loss.restype = ci
+    lib.rlap_cca_loss.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ci, vp, vp, vp, ctypes.POINTER(CcaInfo)]
+    lib.rlap_cca_loss_backward.restype = ci
+    lib.rlap_cca_loss_backward.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ci, vp, vp, vp, vp, vp, ctypes.POINTER(CcaInfo)]
     lib.rlap_approx_chol_views.restype = ci
     lib.rlap_approx_chol_views.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, vp, ci, ci, vp, u64, vp, i64, vp,
                                            ctypes.POINTER(Stats)]

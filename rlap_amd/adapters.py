@@ -20,6 +20,8 @@ Mirrors of the reference's L2 adapters that keep everything on the GPU:
                   `Snapshots.readout(z)` the per-graph sum of global_add_pool (ops.graph_readout)
   * `NodeContrast` -- the contrastive loss of the node-level step (scripts/node_shared.py: DualBranchContrast(InfoNCEBatched(tau),
                   mode="L2L")) on the embeddings of two views, fused on the device (ops.info_nce)
+  * `CCAContrast` -- the loss of CCA-SSG/main.py on the embeddings of two views, fused on the device (ops.cca_loss);
+                  `drop_feature` -- CCA-SSG/aug.py's feature masking (also A.FeatureMasking), one mask per view
   * `rLapChain` -- the chain of scripts/rlap_vc_spectral.py: eliminate, relabel the survivors 0..k-1, eliminate again
 PyGCL / DGL are optional: with them installed the classes return their graph types,
 without them a small named tuple with the same fields.
@@ -235,6 +237,41 @@ class NodeContrast(torch.nn.Module):
         l1 = ops.info_nce(h1, h2, tau=self.tau, positive=self.positive)
         l2 = ops.info_nce(h2, h1, tau=self.tau, positive=self.positive)
         return 0.5 * (l1 + l2)
+
+
+class CCAContrast(torch.nn.Module):
+    """The loss of CCA-SSG/main.py: forward(h1, h2) = ops.cca_loss(h1, h2, lambd), the standardisation of CCA-SSG/model.py included
+    -- h1, h2 are the encoder's outputs, not the standardised z.  h1, h2 are (N, F) float32 embeddings of two views; given one
+    (L, N, F) tensor of L >= 2 views, as SnapshotGCNConv returns it, forward(h) takes view 0 against view 1.  The loss is a 0-dim
+    float64 tensor; gradients reach both views."""
+
+    def __init__(self, lambd: float = 1e-3):
+        super().__init__()
+        self.lambd = lambd
+
+    def forward(self, h1, h2=None):
+        if h2 is None:
+            if not isinstance(h1, torch.Tensor) or h1.dim() != 3 or h1.shape[0] < 2:
+                raise ValueError("CCAContrast: two (N, F) embeddings, or one (L, N, F) tensor of L >= 2 views")
+            h1, h2 = h1[0], h1[1]
+        return ops.cca_loss(h1, h2, lambd=self.lambd)
+
+
+def drop_feature(x, p: float, views: int = 1, generator=None):
+    """CCA-SSG/aug.py's drop_feature (A.FeatureMasking of the PyGCL scripts) for `views` views at once: per view, F uniforms are
+    drawn (from `generator`, on x's device) and the columns with u < p are set to zero.  x is (N, F); returns (views, N, F), which
+    SnapshotGCNConv takes as its per-view x.  Plain torch."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise ValueError("drop_feature: x is a (N, F) tensor")
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= float(p) <= 1.0:
+        raise ValueError(f"drop_feature: p in [0, 1], got {p!r}")
+    if isinstance(views, bool) or not isinstance(views, int) or views < 1:
+        raise ValueError(f"drop_feature: views >= 1, got {views!r}")
+    out = x.unsqueeze(0).repeat(views, 1, 1)
+    for v in range(views):
+        mask = torch.empty((x.size(1),), dtype=torch.float32, device=x.device).uniform_(0, 1, generator=generator) < p
+        out[v][:, mask] = 0
+    return out
 
 
 def graph_plan(g, fill_value: float = 1.0, directions: str = "both"):

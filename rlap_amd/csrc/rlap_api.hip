@@ -31,6 +31,8 @@
 #include "rlap_readout_api.h"
 #include "rlap_infonce.h"
 #include "rlap_infonce_api.h"
+#include "rlap_cca.h"
+#include "rlap_cca_api.h"
 
 using namespace rlap;
 
@@ -1649,6 +1651,55 @@ int rlap_infonce_backward(rlap_handle h, const float* d_a, const float* d_b, int
         }
         if (h_info) h_info->arena_bytes = (int64_t)need;
         return infonce_backward_run(h->stream, base, have, a);
+    });
+}
+
+namespace {
+
+// what both CCA exports check (their pointers come before this)
+int cca_check(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double lambd, int flags, rlap_cca_info* h_info) {
+    if (h_info) *h_info = rlap_cca_info{};
+    if (!h || !d_a || !d_b || N < 2 || F < 1 || F > cca::MAX_F || !cca::lambd_ok(lambd) || flags != 0) return RLAP_E_BAD_ARG;
+    if (N >= (int64_t)1 << 31) return RLAP_E_TOO_LARGE;
+    if (h_info) { h_info->rows = N; h_info->features = F; h_info->parts = cca::num_parts(N, F); }
+    return RLAP_OK;
+}
+
+}  // namespace
+
+int rlap_cca_loss(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double lambd, int flags, double* d_terms,
+                  double* d_colstat, float* d_gram, rlap_cca_info* h_info) {
+    if (const int rc = cca_check(h, d_a, d_b, N, F, lambd, flags, h_info)) return rc;
+    if (!d_terms || !d_colstat || !d_gram) return RLAP_E_BAD_ARG;
+    CcaArgs a{};
+    a.a = d_a; a.b = d_b; a.N = N; a.F = F; a.lambd = lambd; a.terms = d_terms; a.colstat = d_colstat; a.gram = d_gram;
+    return snapshot_call(h, [&] { return cca_bytes(N, F); }, [&](void* base, size_t have, size_t need) -> int {
+        if (h->poison >= 0) {   // debug: the result must not depend on what the arena or the result buffers held
+            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_terms, h->poison, 4 * 8, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_colstat, h->poison, (size_t)(4 * F) * 8, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_gram, h->poison, (size_t)(2 * F * F) * 4, h->stream));
+        }
+        if (h_info) h_info->arena_bytes = (int64_t)need;
+        return cca_run(h->stream, base, have, a);
+    });
+}
+
+int rlap_cca_loss_backward(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double lambd, int flags,
+                           const double* d_colstat, const float* d_gram, const double* d_g, float* d_ga, float* d_gb,
+                           rlap_cca_info* h_info) {
+    if (const int rc = cca_check(h, d_a, d_b, N, F, lambd, flags, h_info)) return rc;
+    if (!d_colstat || !d_gram || !d_g || !d_ga || !d_gb) return RLAP_E_BAD_ARG;
+    CcaArgs a{};
+    a.a = d_a; a.b = d_b; a.N = N; a.F = F; a.lambd = lambd; a.colstat_in = d_colstat; a.gram_in = d_gram; a.g = d_g; a.ga = d_ga; a.gb = d_gb;
+    return snapshot_call(h, [&] { return cca_backward_bytes(N, F); }, [&](void* base, size_t have, size_t need) -> int {
+        if (h->poison >= 0) {
+            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_ga, h->poison, (size_t)(N * F) * 4, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_gb, h->poison, (size_t)(N * F) * 4, h->stream));
+        }
+        if (h_info) h_info->arena_bytes = (int64_t)need;
+        return cca_backward_run(h->stream, base, have, a);
     });
 }
 

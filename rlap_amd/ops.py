@@ -1303,6 +1303,121 @@ def info_nce(anchor: Tensor, sample: Tensor, tau: float = 0.4, positive: str = "
     return (loss, rows) if return_rows else loss
 
 
+CCA_MAX_F = 512
+
+
+def _cca_args(h1, h2, lambd):
+    """Host-side checks of cca_loss, made before the device is touched: lambd as a float."""
+    for t, what in ((h1, "h1"), (h2, "h2")):
+        if not isinstance(t, Tensor) or t.dim() != 2:
+            raise ValueError(f"{what}: a (num_nodes, F) tensor")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: torch.float32, got {t.dtype}")
+    if h1.shape != h2.shape:
+        raise ValueError(f"h1 and h2: equal shapes, got {tuple(h1.shape)} and {tuple(h2.shape)}")
+    if h1.device != h2.device:
+        raise ValueError(f"h1 and h2: one device, got {h1.device} and {h2.device}")
+    n, f = int(h1.shape[0]), int(h1.shape[1])
+    if n < 2:
+        raise ValueError("h1: at least two rows (the unbiased deviation divides by N - 1)")
+    if f < 1:
+        raise ValueError("h1: at least one feature column")
+    if f > CCA_MAX_F:
+        raise ValueError(f"h1: at most {CCA_MAX_F} feature columns, got {f}")
+    if n >= 1 << 31:
+        raise ValueError("h1: fewer than 2^31 rows")
+    if isinstance(lambd, bool) or not isinstance(lambd, (int, float)):
+        raise ValueError(f"lambd: a number, got {lambd!r}")
+    lambd = float(lambd)
+    if not (0.0 <= lambd < float("inf")):
+        raise ValueError(f"lambd: finite and >= 0, got {lambd!r}")
+    return lambd
+
+
+def _cca_call(export: str, dev, tail):
+    """One rlap_cca_loss / _backward call on the library's device: the arguments behind the handle."""
+    global last_stats
+    lib, hobj = _handle_obj(dev)
+    fn = getattr(lib, export)
+    info = _lib.CcaInfo()
+    st = _lib.Stats()
+    rc = _run(hobj, dev, 0, None, 1, False, lambda: fn(hobj.ptr, *tail, ctypes.byref(info)), st)
+    if rc in (1, 2, 3):
+        raise ValueError(f"rlap: {_lib.status_string(rc)}")
+    if rc != 0:
+        _raise(rc)
+    last_stats = info.as_dict()
+
+
+def _cca_forward(a: Tensor, b: Tensor, lambd: float):
+    """The forward export: (terms [4] float64: loss, inv, dec1, dec2; colstat [4 F] float64; gram [2, F, F] float32; the device
+    copies of a and b)."""
+    dev = _device_for(a)
+    with torch.cuda.device(dev):
+        d_a = a.detach().to(device=dev).contiguous()
+        d_b = b.detach().to(device=dev).contiguous()
+        n, f = int(d_a.shape[0]), int(d_a.shape[1])
+        out = torch.empty(4 + 4 * f, dtype=torch.float64, device=dev)   # terms | colstat
+        gram = torch.empty((2, f, f), dtype=torch.float32, device=dev)
+        p = out.data_ptr()
+        _cca_call("rlap_cca_loss", dev, (d_a.data_ptr(), d_b.data_ptr(), n, f, lambd, 0, p, p + 32, gram.data_ptr()))
+    return out[:4], out[4:], gram, d_a, d_b
+
+
+class _CcaLoss(torch.autograd.Function):
+    """terms = the fused CCA-SSG loss of (h1, h2) and its three parts; the gradients of the loss with respect to both inputs come
+    from the backward export, which reads the forward's column statistics and residuals."""
+
+    @staticmethod
+    def forward(ctx, a, b, lambd):
+        terms, colstat, gram, d_a, d_b = _cca_forward(a, b, lambd)
+        ctx.save_for_backward(d_a, d_b, colstat, gram)
+        ctx.call = (lambd, a.device, b.device)
+        parts = terms[1:].clone()
+        ctx.mark_non_differentiable(parts)
+        return terms[0], parts
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_parts):
+        d_a, d_b, colstat, gram = ctx.saved_tensors
+        lambd, dev_a, dev_b = ctx.call
+        dev = d_a.device
+        with torch.cuda.device(dev):
+            d_g = g.detach().to(device=dev, dtype=torch.float64).reshape(1).contiguous()
+            n, f = int(d_a.shape[0]), int(d_a.shape[1])
+            ga = torch.empty_like(d_a)
+            gb = torch.empty_like(d_b)
+            _cca_call("rlap_cca_loss_backward", dev, (d_a.data_ptr(), d_b.data_ptr(), n, f, lambd, 0, colstat.data_ptr(), gram.data_ptr(),
+                                                      d_g.data_ptr(), ga.data_ptr(), gb.data_ptr()))
+        return ga.to(dev_a), gb.to(dev_b), None
+
+
+def cca_loss(h1: Tensor, h2: Tensor, lambd: float = 1e-3, return_terms: bool = False):
+    """The CCA-SSG loss of two views' node embeddings, fused on the device (rlap_cca_loss): with
+    z = (h - h.mean(0)) / h.std(0), c = z1^T z2 / N, c1 = z1^T z1 / N, c2 = z2^T z2 / N,
+    loss = -trace(c) + lambd * (||I - c1||^2 + ||I - c2||^2) -- CCA-SSG/model.py:77-78 and CCA-SSG/main.py:111-124 in one call.
+
+      h1, h2       : (N, F) float32 of equal shape on one device (moved to the library's), N >= 2, F <= 512
+      lambd        : the trade-off between invariance and decorrelation, finite and >= 0
+      return_terms : return (loss, inv, dec1, dec2), 0-dim float64 each: inv = -trace(c), dec = ||I - c_v||^2 (not differentiable)
+    Returns the 0-dim float64 loss.  Every value and the order of every sum are fixed (rlap_amd/csrc/rlap_cca.h): the same input
+    gives the same bits.  A column of zero variance gives a NaN loss, as in the reference; nothing is clamped.
+
+    Differentiable in both inputs (rlap_cca_loss_backward standardises again and reads the forward's column statistics and
+    residual matrices, it does not repeat the Gram products); double backward is not supported.  Malformed arguments raise
+    ValueError before the device is touched.  No host synchronisation.  `last_stats` then holds what the call did
+    (rlap_cca_info: rows, features, parts, arena_bytes, host_syncs).
+    """
+    lambd = _cca_args(h1, h2, lambd)
+    if torch.is_grad_enabled() and (h1.requires_grad or h2.requires_grad):
+        loss, parts = _CcaLoss.apply(h1, h2, lambd)
+    else:
+        terms = _cca_forward(h1, h2, lambd)[0]
+        loss, parts = terms[0], terms[1:]
+    return (loss, parts[0], parts[1], parts[2]) if return_terms else loss
+
+
 PLAN_DIRECTIONS = {"forward": _lib.PLAN_FORWARD, "transposed": _lib.PLAN_TRANSPOSED, "both": _lib.PLAN_FORWARD | _lib.PLAN_TRANSPOSED}
 
 
