@@ -600,6 +600,55 @@ int rlap_cca_loss_backward(rlap_handle h, const float* d_a, const float* d_b, in
                            const double* d_colstat, const float* d_gram, const double* d_g, float* d_ga, float* d_gb,
                            rlap_cca_info* h_info);
 
+/* The fused graph-to-local losses of node embeddings against graph summaries, forward and backward: one direction of
+ * DualBranchContrast(JSD(), mode="G2L") and of BootstrapContrast(BootstrapLatent(), mode="G2L"), without the concatenated copy,
+ * the dense (G, N) masks and the dense similarity matrix.  With s_ij = <h_i, g_j> and g(i) the graph of node i:
+ *   JSD        positives (i, g(i)); negatives every (i, j) with j != g(i) when G >= 2, or s'_i = <neg_i, g_0> when G == 1;
+ *              loss = mean_neg(softplus(s) - ln 2) - mean_pos(ln 2 - softplus(-s))
+ *   bootstrap  loss = (sum_i cos(h_i, g_g(i))) / G, the sign as published: not negated; g is a constant
+ *   d_h, N, F       : node embeddings (N, F) float32 row-major; N >= 1, 1 <= F <= 512
+ *   d_neg           : JSD only: the embeddings of the corrupted input, (N, F); required when G == 1, NULL when G >= 2
+ *   d_g, G          : graph summaries (G, F) float32; G >= 1
+ *   d_node_ptr      : [G+1] offsets on the device, non-decreasing from 0 to N (the caller's to check): node i belongs to the graph
+ *                     whose id range holds it; empty graphs and G > N are legal
+ *   flags           : reserved, 0
+ *   forward         : d_loss one double; d_rows doubles: JSD [2 N], the positive terms pos_i and then the negative sums neg_i;
+ *                     bootstrap [N], the cosines c_i
+ *   backward        : d_gup the upstream gradient, one double ON THE DEVICE (so that no synchronisation is needed); d_gh (N, F),
+ *                     d_gneg (N, F) exactly when d_neg is given, d_gg (G, F): the gradients with respect to d_h, d_neg and d_g.
+ *                     The bootstrap has a gradient for d_h alone.
+ *   h_info          : (nullable) what the call did
+ * Every value and the order of every sum are defined in rlap_amd/csrc/rlap_g2l.h: s_ij the float32 fmaf chain over the columns in
+ * increasing order (what the f32 matrix-core instruction computes); softplus from rlap_infonce.h's float32 exponential and the
+ * float64 log1p; neg_i summed in float64 in an order that depends on G alone, the positive and the padding left out of it; the losses
+ * summed by the chunk rule of rlap_amd/csrc/rlap_spmm.h; dg summed per part of the nodes, the parts a function of (N, G, F) alone.
+ * The bootstrap normalises rows as rlap_infonce does.  So the same input gives the same bits, whatever the arena held; no atomic
+ * touches a floating-point value; no call synchronises with the host; the table is never read back: the kernels clamp what they read
+ * from it before it becomes an address, so a table that is not well formed gives wrong numbers, never an access out of range.
+ * Features that are not finite are not looked for: a score that is not finite gives a NaN loss.
+ * A null pointer, N < 1, F < 1, G < 1, G == 1 without d_neg, G >= 2 with d_neg, or flags other than 0: RLAP_E_BAD_ARG.  F > 512, or
+ * N or G >= 2^31: RLAP_E_TOO_LARGE.  Scratch from the arena (RLAP_E_WORKSPACE when a caller-provided one is too small, the
+ * workspace-needed query saying how much). */
+typedef struct {
+    int64_t rows;             /* N                                                                    */
+    int64_t graphs;           /* G                                                                    */
+    int64_t features;         /* F                                                                    */
+    int64_t parts;            /* contiguous parts of the node tiles in dg: a function of (N, G, F)    */
+    int64_t arena_bytes;      /* scratch bytes of the call                                            */
+    int32_t host_syncs;       /* host synchronisations of the call: 0                                 */
+    int32_t pad;
+} rlap_g2l_info;
+
+int rlap_g2l_jsd(rlap_handle h, const float* d_h, const float* d_neg, const float* d_g, int64_t N, int64_t F, const int64_t* d_node_ptr,
+                 int64_t G, int flags, double* d_loss, double* d_rows, rlap_g2l_info* h_info);
+int rlap_g2l_jsd_backward(rlap_handle h, const float* d_h, const float* d_neg, const float* d_g, int64_t N, int64_t F,
+                          const int64_t* d_node_ptr, int64_t G, int flags, const double* d_gup, float* d_gh, float* d_gneg, float* d_gg,
+                          rlap_g2l_info* h_info);
+int rlap_g2l_bootstrap(rlap_handle h, const float* d_h, const float* d_g, int64_t N, int64_t F, const int64_t* d_node_ptr, int64_t G,
+                       int flags, double* d_loss, double* d_rows, rlap_g2l_info* h_info);
+int rlap_g2l_bootstrap_backward(rlap_handle h, const float* d_h, const float* d_g, int64_t N, int64_t F, const int64_t* d_node_ptr,
+                                int64_t G, int flags, const double* d_gup, float* d_gh, rlap_g2l_info* h_info);
+
 /* The op with the step BEFORE the path fused in (scripts/node_shared.py:326-327,
  * scripts/augmentor_benchmarks.py:77-78):
  *   symmetrize != 0 : the input holds every undirected edge in one or both directions; (b,a) is

@@ -24,6 +24,7 @@ EXPORTS = [
     "rlap_snapshot_plan_bytes", "rlap_snapshot_plan_build", "rlap_snapshot_plan_propagate", "rlap_edge_plan_build",
     "rlap_graph_readout", "rlap_graph_readout_backward", "rlap_infonce", "rlap_infonce_backward",
     "rlap_cca_loss", "rlap_cca_loss_backward",
+    "rlap_g2l_jsd", "rlap_g2l_jsd_backward", "rlap_g2l_bootstrap", "rlap_g2l_bootstrap_backward",
 ]
 
 E_INDEX_RANGE = 2   # RLAP_E_INDEX_RANGE
@@ -163,6 +164,14 @@ class CcaInfo(_Report):
     ]
 
 
+class G2lInfo(_Report):
+    """rlap_g2l_info (include/rlap_hip.h)."""
+    _fields_ = [
+        ("rows", ctypes.c_int64), ("graphs", ctypes.c_int64), ("features", ctypes.c_int64), ("parts", ctypes.c_int64),
+        ("arena_bytes", ctypes.c_int64), ("host_syncs", ctypes.c_int32), ("pad", ctypes.c_int32),
+    ]
+
+
 def load():
     """dlopen the library and declare prototypes. Raises if it is not built."""
     global _lib
@@ -235,6 +244,14 @@ def load():
     lib.rlap_cca_loss.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ci, vp, vp, vp, ctypes.POINTER(CcaInfo)]
     lib.rlap_cca_loss_backward.restype = ci
     lib.rlap_cca_loss_backward.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ci, vp, vp, vp, vp, vp, ctypes.POINTER(CcaInfo)]
+    lib.rlap_g2l_jsd.restype = ci
+    lib.rlap_g2l_jsd.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, ci, vp, vp, ctypes.POINTER(G2lInfo)]
+    lib.rlap_g2l_jsd_backward.restype = ci
+    lib.rlap_g2l_jsd_backward.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, ci, vp, vp, vp, vp, ctypes.POINTER(G2lInfo)]
+    lib.rlap_g2l_bootstrap.restype = ci
+    lib.rlap_g2l_bootstrap.argtypes = [vp, vp, vp, i64, i64, vp, i64, ci, vp, vp, ctypes.POINTER(G2lInfo)]
+    lib.rlap_g2l_bootstrap_backward.restype = ci
+    lib.rlap_g2l_bootstrap_backward.argtypes = [vp, vp, vp, i64, i64, vp, i64, ci, vp, vp, ctypes.POINTER(G2lInfo)]
     lib.rlap_approx_chol_views.restype = ci
     lib.rlap_approx_chol_views.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, vp, ci, ci, vp, u64, vp, i64, vp,
                                            ctypes.POINTER(Stats)]

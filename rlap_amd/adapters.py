@@ -257,6 +257,58 @@ class CCAContrast(torch.nn.Module):
         return ops.cca_loss(h1, h2, lambd=self.lambd)
 
 
+def _view_pair(x, y, what: str, name: str):
+    """(x, y), or the first two views of one (L, rows, F) tensor of L >= 2 views given as x."""
+    if y is None:
+        if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[0] < 2:
+            raise ValueError(f"{name}: two (rows, F) tensors for {what}, or one (L, rows, F) tensor of L >= 2 views")
+        return x[0], x[1]
+    return x, y
+
+
+class G2LContrast(torch.nn.Module):
+    """The graph-to-local contrastive loss of scripts/node_dedicated.py: forward(h1, h2, g1, g2, h3, h4, node_ptr) =
+    0.5 * (g2l_jsd(h2, g1, neg=h4) + g2l_jsd(h1, g2, neg=h3)), the single-graph and the multi-graph branch of the reference's
+    DualBranchContrast(JSD(), mode="G2L") (scripts/node_shared.py: the text of the branches; the sampler restates PyGCL's published
+    CrossScaleSampler, which is not installed here), by two ops.g2l_jsd calls.  h1, h2 are (N, F) float32 node embeddings of two
+    views, g1, g2 (G, F) their graph summaries, h3, h4 the embeddings of the corrupted input (adapters.corrupt), required exactly
+    when there is one graph; node_ptr the batch's table (None: one graph).  Given (L, N, F) / (L, G, F) tensors of L >= 2 views in
+    place of a pair (h2, g2, h4 = None), views 0 and 1 are taken.  The loss is a 0-dim float64 tensor; gradients reach h, g and the
+    corrupted embeddings."""
+
+    def forward(self, h1, h2=None, g1=None, g2=None, h3=None, h4=None, node_ptr=None):
+        h1, h2 = _view_pair(h1, h2, "h1, h2", "G2LContrast")
+        g1, g2 = _view_pair(g1, g2, "g1, g2", "G2LContrast")
+        if h3 is not None or h4 is not None:
+            h3, h4 = _view_pair(h3, h4, "h3, h4", "G2LContrast")
+        l1 = ops.g2l_jsd(h2, g1, node_ptr=node_ptr, neg=h4)
+        l2 = ops.g2l_jsd(h1, g2, node_ptr=node_ptr, neg=h3)
+        return 0.5 * (l1 + l2)
+
+
+class BootstrapG2L(torch.nn.Module):
+    """The graph-to-local bootstrap loss of scripts/graph_shared_g2l.py: forward(h1_pred, h2_pred, g1_target, g2_target, node_ptr) =
+    0.5 * (g2l_bootstrap(h2_pred, g1_target) + g2l_bootstrap(h1_pred, g2_target)), what BootstrapContrast(BootstrapLatent(),
+    mode="G2L") computes (restated from PyGCL as published; it is not installed here), by two ops.g2l_bootstrap calls.  The targets
+    are detached, as the script does.  Given (L, N, F) / (L, G, F) tensors of L >= 2 views in place of a pair, views 0 and 1 are
+    taken.  The loss is a 0-dim float64 tensor; gradients reach the predictions alone."""
+
+    def forward(self, h1_pred, h2_pred=None, g1_target=None, g2_target=None, node_ptr=None):
+        h1_pred, h2_pred = _view_pair(h1_pred, h2_pred, "h1_pred, h2_pred", "BootstrapG2L")
+        g1_target, g2_target = _view_pair(g1_target, g2_target, "g1_target, g2_target", "BootstrapG2L")
+        l1 = ops.g2l_bootstrap(h2_pred, g1_target.detach(), node_ptr=node_ptr)
+        l2 = ops.g2l_bootstrap(h1_pred, g2_target.detach(), node_ptr=node_ptr)
+        return 0.5 * (l1 + l2)
+
+
+def corrupt(x, generator=None):
+    """scripts/node_dedicated.py's `corruption`: the rows of x in a random order, x[randperm(N)] (from `generator`, on x's device).
+    Plain torch."""
+    if not isinstance(x, torch.Tensor) or x.dim() < 1:
+        raise ValueError("corrupt: x is a tensor with rows")
+    return x[torch.randperm(x.size(0), device=x.device, generator=generator)]
+
+
 def drop_feature(x, p: float, views: int = 1, generator=None):
     """CCA-SSG/aug.py's drop_feature (A.FeatureMasking of the PyGCL scripts) for `views` views at once: per view, F uniforms are
     drawn (from `generator`, on x's device) and the columns with u < p are set to zero.  x is (N, F); returns (views, N, F), which

@@ -31,6 +31,8 @@
 #include "rlap_readout_api.h"
 #include "rlap_infonce.h"
 #include "rlap_infonce_api.h"
+#include "rlap_g2l.h"
+#include "rlap_g2l_api.h"
 #include "rlap_cca.h"
 #include "rlap_cca_api.h"
 
@@ -1701,6 +1703,73 @@ int rlap_cca_loss_backward(rlap_handle h, const float* d_a, const float* d_b, in
         if (h_info) h_info->arena_bytes = (int64_t)need;
         return cca_backward_run(h->stream, base, have, a);
     });
+}
+
+namespace {
+
+// what the four graph-to-local exports check (their result pointers come before this)
+int g2l_check(rlap_handle h, const float* d_h, const float* d_g, int64_t N, int64_t F, const int64_t* d_node_ptr, int64_t G, int flags,
+              rlap_g2l_info* h_info) {
+    if (h_info) *h_info = rlap_g2l_info{};
+    if (!h || !d_h || !d_g || !d_node_ptr || N < 1 || F < 1 || G < 1 || flags != 0) return RLAP_E_BAD_ARG;
+    if (F > g2l::MAX_F || N >= (int64_t)1 << 31 || G >= (int64_t)1 << 31) return RLAP_E_TOO_LARGE;
+    if (h_info) { h_info->rows = N; h_info->graphs = G; h_info->features = F; h_info->parts = g2l::num_parts(N, G, F); }
+    return RLAP_OK;
+}
+
+// one of the four calls on the checked path; `outs` are the result buffers (pointer, bytes) a poisoned run fills first
+int g2l_call(rlap_handle h, int call, const G2lArgs& a, rlap_g2l_info* h_info, std::initializer_list<std::pair<void*, size_t>> outs) {
+    return snapshot_call(h, [&] { return g2l_bytes(call, a.N, a.G, a.F); }, [&](void* base, size_t have, size_t need) -> int {
+        if (h->poison >= 0) {   // debug: the result must not depend on what the arena or the result buffers held
+            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
+            for (const auto& o : outs)
+                if (o.first) RLAP_HIPCHK(hipMemsetAsync(o.first, h->poison, o.second, h->stream));
+        }
+        if (h_info) h_info->arena_bytes = (int64_t)need;
+        return g2l_run(call, h->stream, base, have, a);
+    });
+}
+
+}  // namespace
+
+int rlap_g2l_jsd(rlap_handle h, const float* d_h, const float* d_neg, const float* d_g, int64_t N, int64_t F, const int64_t* d_node_ptr,
+                 int64_t G, int flags, double* d_loss, double* d_rows, rlap_g2l_info* h_info) {
+    if (const int rc = g2l_check(h, d_h, d_g, N, F, d_node_ptr, G, flags, h_info)) return rc;
+    if (!d_loss || !d_rows || (G == 1) != (d_neg != nullptr)) { if (h_info) *h_info = rlap_g2l_info{}; return RLAP_E_BAD_ARG; }
+    G2lArgs a{};
+    a.h = d_h; a.neg = d_neg; a.g = d_g; a.N = N; a.F = F; a.node_ptr = d_node_ptr; a.G = G; a.loss = d_loss; a.rows = d_rows;
+    return g2l_call(h, g2l::JSD_FORWARD, a, h_info, {{d_loss, 8}, {d_rows, (size_t)(2 * N) * 8}});
+}
+
+int rlap_g2l_jsd_backward(rlap_handle h, const float* d_h, const float* d_neg, const float* d_g, int64_t N, int64_t F,
+                          const int64_t* d_node_ptr, int64_t G, int flags, const double* d_gup, float* d_gh, float* d_gneg, float* d_gg,
+                          rlap_g2l_info* h_info) {
+    if (const int rc = g2l_check(h, d_h, d_g, N, F, d_node_ptr, G, flags, h_info)) return rc;
+    if (!d_gup || !d_gh || !d_gg || (G == 1) != (d_neg != nullptr) || (G == 1) != (d_gneg != nullptr)) {
+        if (h_info) *h_info = rlap_g2l_info{};
+        return RLAP_E_BAD_ARG;
+    }
+    G2lArgs a{};
+    a.h = d_h; a.neg = d_neg; a.g = d_g; a.N = N; a.F = F; a.node_ptr = d_node_ptr; a.G = G; a.gup = d_gup; a.gh = d_gh; a.gneg = d_gneg; a.gg = d_gg;
+    return g2l_call(h, g2l::JSD_BACKWARD, a, h_info, {{d_gh, (size_t)(N * F) * 4}, {d_gneg, (size_t)(N * F) * 4}, {d_gg, (size_t)(G * F) * 4}});
+}
+
+int rlap_g2l_bootstrap(rlap_handle h, const float* d_h, const float* d_g, int64_t N, int64_t F, const int64_t* d_node_ptr, int64_t G,
+                       int flags, double* d_loss, double* d_rows, rlap_g2l_info* h_info) {
+    if (const int rc = g2l_check(h, d_h, d_g, N, F, d_node_ptr, G, flags, h_info)) return rc;
+    if (!d_loss || !d_rows) { if (h_info) *h_info = rlap_g2l_info{}; return RLAP_E_BAD_ARG; }
+    G2lArgs a{};
+    a.h = d_h; a.g = d_g; a.N = N; a.F = F; a.node_ptr = d_node_ptr; a.G = G; a.loss = d_loss; a.rows = d_rows;
+    return g2l_call(h, g2l::BOOT_FORWARD, a, h_info, {{d_loss, 8}, {d_rows, (size_t)N * 8}});
+}
+
+int rlap_g2l_bootstrap_backward(rlap_handle h, const float* d_h, const float* d_g, int64_t N, int64_t F, const int64_t* d_node_ptr,
+                                int64_t G, int flags, const double* d_gup, float* d_gh, rlap_g2l_info* h_info) {
+    if (const int rc = g2l_check(h, d_h, d_g, N, F, d_node_ptr, G, flags, h_info)) return rc;
+    if (!d_gup || !d_gh) { if (h_info) *h_info = rlap_g2l_info{}; return RLAP_E_BAD_ARG; }
+    G2lArgs a{};
+    a.h = d_h; a.g = d_g; a.N = N; a.F = F; a.node_ptr = d_node_ptr; a.G = G; a.gup = d_gup; a.gh = d_gh;
+    return g2l_call(h, g2l::BOOT_BACKWARD, a, h_info, {{d_gh, (size_t)(N * F) * 4}});
 }
 
 int rlap_debug_set_limits(rlap_handle h, double pool_factor, double log_factor, int64_t rng_len, int64_t scratch_entries) {

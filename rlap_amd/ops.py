@@ -1418,6 +1418,208 @@ def cca_loss(h1: Tensor, h2: Tensor, lambd: float = 1e-3, return_terms: bool = F
     return (loss, parts[0], parts[1], parts[2]) if return_terms else loss
 
 
+G2L_MAX_F = 512
+
+
+def _g2l_args(h, g, node_ptr, neg, what_neg: bool):
+    """Host-side checks of g2l_jsd / g2l_bootstrap, made before the device is touched: the GraphTable of the call."""
+    tensors = [(h, "h"), (g, "g")] + ([(neg, "neg")] if neg is not None else [])
+    for t, what in tensors:
+        if not isinstance(t, Tensor) or t.dim() != 2:
+            raise ValueError(f"{what}: a (rows, F) tensor")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: torch.float32, got {t.dtype}")
+    n, f, G = int(h.shape[0]), int(h.shape[1]), int(g.shape[0])
+    if n < 1 or f < 1:
+        raise ValueError("h: at least one row and one feature column")
+    if G < 1:
+        raise ValueError("g: at least one graph")
+    if int(g.shape[1]) != f:
+        raise ValueError(f"h and g: the same number of feature columns, got {f} and {int(g.shape[1])}")
+    if f > G2L_MAX_F:
+        raise ValueError(f"h: at most {G2L_MAX_F} feature columns, got {f}")
+    if n >= 1 << 31 or G >= 1 << 31:
+        raise ValueError("h, g: fewer than 2^31 rows")
+    if neg is not None and neg.shape != h.shape:
+        raise ValueError(f"h and neg: equal shapes, got {tuple(h.shape)} and {tuple(neg.shape)}")
+    if node_ptr is None:
+        if G != 1:
+            raise ValueError(f"node_ptr: required for g of {G} graphs (the default [0, N] is one graph)")
+        table = GraphTable([0, n], n)
+    elif isinstance(node_ptr, GraphTable):
+        if node_ptr.num_nodes != n:
+            raise ValueError(f"node_ptr[-1] ({node_ptr.num_nodes}) must equal {n}")
+        table = node_ptr
+    else:
+        table = GraphTable(node_ptr, n)
+    if table.graphs != G:
+        raise ValueError(f"node_ptr: {table.graphs} graphs, g has {G} rows")
+    if what_neg:
+        if G == 1 and neg is None:
+            raise ValueError("neg: required for one graph (the embeddings of the corrupted input are its negatives)")
+        if G >= 2 and neg is not None:
+            raise ValueError("neg: only for one graph (with several, the other graphs' summaries are the negatives)")
+    return table
+
+
+def _g2l_call(export: str, dev, G: int, tail):
+    """One rlap_g2l_* call on the library's device: the arguments behind the handle."""
+    global last_stats
+    lib, hobj = _handle_obj(dev)
+    fn = getattr(lib, export)
+    info = _lib.G2lInfo()
+    st = _lib.Stats()
+    rc = _run(hobj, dev, 0, None, G, False, lambda: fn(hobj.ptr, *tail, ctypes.byref(info)), st)
+    if rc in (1, 2, 3):
+        raise ValueError(f"rlap: {_lib.status_string(rc)}")
+    if rc != 0:
+        _raise(rc)
+    last_stats = info.as_dict()
+
+
+def _g2l_jsd_forward(h: Tensor, g: Tensor, neg: Optional[Tensor], table: GraphTable):
+    """The forward export: (loss 0-dim, rows (2, N): pos_i, neg_i; the device copies of h, g, neg)."""
+    dev = _device_for(h)
+    with torch.cuda.device(dev):
+        d_h = h.detach().to(device=dev).contiguous()
+        d_g = g.detach().to(device=dev).contiguous()
+        d_n = neg.detach().to(device=dev).contiguous() if neg is not None else None
+        n, f = int(d_h.shape[0]), int(d_h.shape[1])
+        out = torch.empty(1 + 2 * n, dtype=torch.float64, device=dev)   # loss | pos | neg
+        p = out.data_ptr()
+        _g2l_call("rlap_g2l_jsd", dev, table.graphs, (d_h.data_ptr(), d_n.data_ptr() if d_n is not None else None, d_g.data_ptr(), n, f,
+                                                      table.on(dev).data_ptr(), table.graphs, 0, p, p + 8))
+    return out[0], out[1:].view(2, n), d_h, d_g, d_n
+
+
+class _G2lJsd(torch.autograd.Function):
+    """loss = the fused JSD of (h, g) in the graph-to-local mode; the gradients with respect to h, g and neg come from the backward
+    export, which recomputes the scores."""
+
+    @staticmethod
+    def forward(ctx, h, g, neg, table):
+        loss, rows, d_h, d_g, d_n = _g2l_jsd_forward(h, g, neg, table)
+        ctx.save_for_backward(d_h, d_g, *([d_n] if d_n is not None else []))
+        ctx.call = (table, h.device, g.device, neg.device if neg is not None else None)
+        ctx.mark_non_differentiable(rows)
+        return loss, rows
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gup, _g_rows):
+        d_h, d_g = ctx.saved_tensors[:2]
+        d_n = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else None
+        table, dev_h, dev_g, dev_n = ctx.call
+        dev = d_h.device
+        with torch.cuda.device(dev):
+            d_up = gup.detach().to(device=dev, dtype=torch.float64).reshape(1).contiguous()
+            n, f = int(d_h.shape[0]), int(d_h.shape[1])
+            gh, gg = torch.empty_like(d_h), torch.empty_like(d_g)
+            gn = torch.empty_like(d_n) if d_n is not None else None
+            _g2l_call("rlap_g2l_jsd_backward", dev, table.graphs, (
+                d_h.data_ptr(), d_n.data_ptr() if d_n is not None else None, d_g.data_ptr(), n, f, table.on(dev).data_ptr(), table.graphs, 0,
+                d_up.data_ptr(), gh.data_ptr(), gn.data_ptr() if gn is not None else None, gg.data_ptr()))
+        return gh.to(dev_h), gg.to(dev_g), gn.to(dev_n) if gn is not None else None, None
+
+
+def g2l_jsd(h: Tensor, g: Tensor, node_ptr: Union[Tensor, Sequence[int], GraphTable, None] = None, neg: Optional[Tensor] = None,
+            return_rows: bool = False):
+    """The Jensen-Shannon contrastive loss between node embeddings and graph summaries, fused on the device (rlap_g2l_jsd, DESIGN
+    4.17): one direction of DualBranchContrast(JSD(), mode="G2L") of scripts/node_dedicated.py.  The JSD loss and the mode's branches
+    are the reference's text (scripts/node_dedicated.py: JSD.compute; scripts/node_shared.py: DualBranchContrast.forward); the masks
+    restate PyGCL's published CrossScaleSampler, which is not installed here.  With s_ij = <h_i, g_j> and g(i) the graph of node i:
+    the positives are the pairs (i, g(i)); with several graphs the negatives are every (i, j), j != g(i); with one graph they are
+    s'_i = <neg_i, g_0>;  loss = mean_neg(softplus(s) - ln 2) - mean_pos(ln 2 - softplus(-s)).
+
+      h           : (N, F) float32 node embeddings, F <= 512, on any device (moved to the library's)
+      g           : (G, F) float32 graph summaries
+      node_ptr    : [G+1] offsets, non-decreasing from 0 to N, checked on the host, or an ops.GraphTable; None is [0, N], one graph.
+                    Empty graphs and G > N are legal.
+      neg         : (N, F) float32, the embeddings of the corrupted input: required for one graph, refused for several
+      return_rows : also return the (2, N) float64 row terms: pos_i, and neg_i, the sum of node i's negative terms (not
+                    differentiable)
+    Returns the 0-dim float64 loss.  Every value and the order of every sum are fixed (rlap_amd/csrc/rlap_g2l.h): the same input
+    gives the same bits.  No (2N, F) copy, no (G, N) mask or similarity matrix is formed.
+
+    Differentiable in h, g and neg (rlap_g2l_jsd_backward); double backward is not supported.  Malformed arguments raise ValueError
+    before the device is touched; a score that is not finite gives a NaN loss.  No host synchronisation.  `last_stats` then holds what
+    the call did (rlap_g2l_info: rows, graphs, features, parts, arena_bytes, host_syncs).
+    """
+    table = _g2l_args(h, g, node_ptr, neg, True)
+    if torch.is_grad_enabled() and (h.requires_grad or g.requires_grad or (neg is not None and neg.requires_grad)):
+        loss, rows = _G2lJsd.apply(h, g, neg, table)
+    else:
+        loss, rows = _g2l_jsd_forward(h, g, neg, table)[:2]
+    return (loss, rows) if return_rows else loss
+
+
+def _g2l_bootstrap_forward(h: Tensor, g: Tensor, table: GraphTable):
+    """The forward export: (loss 0-dim, rows [N]: c_i; the device copies of h and g)."""
+    dev = _device_for(h)
+    with torch.cuda.device(dev):
+        d_h = h.detach().to(device=dev).contiguous()
+        d_g = g.detach().to(device=dev).contiguous()
+        n, f = int(d_h.shape[0]), int(d_h.shape[1])
+        out = torch.empty(1 + n, dtype=torch.float64, device=dev)   # loss | c
+        p = out.data_ptr()
+        _g2l_call("rlap_g2l_bootstrap", dev, table.graphs, (d_h.data_ptr(), d_g.data_ptr(), n, f, table.on(dev).data_ptr(), table.graphs, 0, p, p + 8))
+    return out[0], out[1:], d_h, d_g
+
+
+class _G2lBootstrap(torch.autograd.Function):
+    """loss = the fused bootstrap loss of (h, g) in the graph-to-local mode; the gradient with respect to h comes from the backward
+    export.  g is a constant."""
+
+    @staticmethod
+    def forward(ctx, h, g, table):
+        loss, rows, d_h, d_g = _g2l_bootstrap_forward(h, g, table)
+        ctx.save_for_backward(d_h, d_g)
+        ctx.call = (table, h.device)
+        ctx.mark_non_differentiable(rows)
+        return loss, rows
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gup, _g_rows):
+        d_h, d_g = ctx.saved_tensors
+        table, dev_h = ctx.call
+        dev = d_h.device
+        with torch.cuda.device(dev):
+            d_up = gup.detach().to(device=dev, dtype=torch.float64).reshape(1).contiguous()
+            n, f = int(d_h.shape[0]), int(d_h.shape[1])
+            gh = torch.empty_like(d_h)
+            _g2l_call("rlap_g2l_bootstrap_backward", dev, table.graphs, (d_h.data_ptr(), d_g.data_ptr(), n, f, table.on(dev).data_ptr(), table.graphs, 0,
+                                                                         d_up.data_ptr(), gh.data_ptr()))
+        return gh.to(dev_h), None, None
+
+
+def g2l_bootstrap(h: Tensor, g: Tensor, node_ptr: Union[Tensor, Sequence[int], GraphTable, None] = None, return_rows: bool = False):
+    """The bootstrap loss between node predictions and graph targets, fused on the device (rlap_g2l_bootstrap): one
+    direction of BootstrapContrast(BootstrapLatent(), mode="G2L") of scripts/graph_shared_g2l.py.  PyGCL is not installed here: this
+    restates its published BootstrapLatent and BootstrapContrast.  With the rows of h and g normalised as F.normalize does and g(i)
+    the graph of node i:  loss = (sum_i cos(h_i, g_{g(i)})) / G, the mean over graphs of the per-graph sums of cosines.  The sign is
+    PyGCL's as published: the sum is not negated.
+
+      h           : (N, F) float32 node predictions, F <= 512, on any device (moved to the library's)
+      g           : (G, F) float32 graph targets; a constant (the script detaches them): a g that requires grad raises ValueError
+      node_ptr    : [G+1] offsets, non-decreasing from 0 to N, checked on the host, or an ops.GraphTable; None is [0, N], one graph
+      return_rows : also return the (N,) float64 cosines c_i (not differentiable)
+    Returns the 0-dim float64 loss.  Every value and the order of every sum are fixed (rlap_amd/csrc/rlap_g2l.h): the same input
+    gives the same bits.
+
+    Differentiable in h (rlap_g2l_bootstrap_backward); double backward is not supported.  Malformed arguments raise ValueError before
+    the device is touched.  No host synchronisation.  `last_stats` then holds what the call did (rlap_g2l_info).
+    """
+    table = _g2l_args(h, g, node_ptr, None, False)
+    if g.requires_grad:
+        raise ValueError("g: the bootstrap targets are constants; detach them (there is no gradient for g)")
+    if torch.is_grad_enabled() and h.requires_grad:
+        loss, rows = _G2lBootstrap.apply(h, g, table)
+    else:
+        loss, rows = _g2l_bootstrap_forward(h, g, table)[:2]
+    return (loss, rows) if return_rows else loss
+
+
 PLAN_DIRECTIONS = {"forward": _lib.PLAN_FORWARD, "transposed": _lib.PLAN_TRANSPOSED, "both": _lib.PLAN_FORWARD | _lib.PLAN_TRANSPOSED}
 
 

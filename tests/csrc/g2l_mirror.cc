@@ -1,0 +1,172 @@
+// Host mirror of the fused graph-to-local losses (tests/test_g2l_cpu.py, tests/test_gpu_g2l.py): every value comes from
+// rlap_amd/csrc/rlap_g2l.h, compiled with g++ and contraction off, so that it computes the bits the kernels compute.  The loops below
+// restate only the ORDER the header fixes: graph tiles, parts, registers, lane halves.  `block_rows` groups the owner rows the way a
+// different tiling of them would (and deals them to threads); no result may depend on it.
+#include <algorithm>
+#include <cstdint>
+#include <thread>
+#include <vector>
+
+#include "rlap_g2l.h"
+
+using namespace rlap;
+
+namespace {
+
+// run body(i0, i1) over [0, N) in blocks of `block` rows, on up to `threads` threads
+template <class Body>
+void over_blocks(int64_t N, int64_t block, int threads, Body body) {
+    const int64_t nb = (N + block - 1) / block;
+    const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(threads, nb));
+    std::vector<std::thread> pool;
+    for (int w = 0; w < nt; ++w)
+        pool.emplace_back([=] {
+            for (int64_t b = w; b < nb; b += nt) body(b * block, std::min(N, (b + 1) * block));
+        });
+    for (auto& t : pool) t.join();
+}
+
+// the chain with the graph's row first, as the kernels' operands
+float score(const float* grow, const float* hrow, int64_t F) {
+    float acc = 0.0f;
+    for (int64_t k = 0; k < F; ++k) acc = g2l::score_step(acc, grow[k], hrow[k]);
+    return acc;
+}
+
+}  // namespace
+
+extern "C" {
+
+double g2l_pos_term(float s) { return g2l::pos_term(s); }
+double g2l_neg_term(float s) { return g2l::neg_term(s); }
+float g2l_sigma(float s) { return g2l::sigma(s); }
+int64_t g2l_parts(int64_t N, int64_t G, int64_t F) { return g2l::num_parts(N, G, F); }
+int64_t g2l_part_begin(int64_t N, int64_t G, int64_t F, int64_t p) { return g2l::part_begin(N, G, F, p); }
+int64_t g2l_arena_bytes(int call, int64_t N, int64_t G, int64_t F) { return g2l::arena(call, N, G, F).bytes; }
+int64_t g2l_graph_of(const int64_t* node_ptr, int64_t G, int64_t N, int64_t i) { return g2l::graph_of(node_ptr, G, N, i); }
+int64_t g2l_num_neg(int64_t N, int64_t G) { return g2l::num_neg(N, G); }
+
+// rows [2 N] (pos_i, then neg_i), loss [1]; with grad != 0 and the upstream gradient gup: gh (N, F), gneg (N, F) when neg is given,
+// gg (G, F).  Returns 0, or 1 for arguments the library refuses.
+int g2l_jsd_mirror(const float* h, const float* neg, const float* g, int64_t N, int64_t F, const int64_t* node_ptr, int64_t G,
+                   int64_t block_rows, int threads, double gup, int grad, double* rows, double* loss, float* gh, float* gneg, float* gg) {
+    if (N < 1 || F < 1 || F > g2l::MAX_F || G < 1 || block_rows < 1 || (G == 1) != (neg != nullptr)) return 1;
+    const double cp = g2l::pos_coef(gup, N), cn = g2l::neg_coef(gup, N, G);
+    const int64_t TG = g2l::num_tiles(G);
+    std::vector<int64_t> map((size_t)N);
+    for (int64_t i = 0; i < N; ++i) map[(size_t)i] = g2l::graph_of(node_ptr, G, N, i);
+    std::vector<float> W(grad ? (size_t)(G == 1 ? 2 * N : N * G) : 0);   // G == 1: w_i, then w'_i; else node-major
+    over_blocks(N, block_rows, threads, [&](int64_t i0, int64_t i1) {
+        std::vector<float> s((size_t)G);
+        for (int64_t i = i0; i < i1; ++i) {
+            const int64_t gi = map[(size_t)i];
+            if (G == 1) {
+                const float sp = score(g, h + i * F, F), sn = score(g, neg + i * F, F);
+                rows[i] = g2l::pos_term(sp);
+                rows[N + i] = g2l::neg_term(sn);
+                if (grad) {
+                    W[(size_t)i] = g2l::weight(cp, cn, sp, true);
+                    W[(size_t)(N + i)] = g2l::weight(cp, cn, sn, false);
+                    for (int64_t k = 0; k < F; ++k) {
+                        gh[i * F + k] = fmaf(W[(size_t)i], g[k], 0.0f);
+                        gneg[i * F + k] = fmaf(W[(size_t)(N + i)], g[k], 0.0f);
+                    }
+                }
+                continue;
+            }
+            for (int64_t j = 0; j < G; ++j) s[(size_t)j] = score(g + j * F, h + i * F, F);
+            rows[i] = g2l::pos_term(s[(size_t)gi]);
+            double half[2] = {0.0, 0.0};
+            for (int64_t t = 0; t < TG; ++t)
+                for (int hf = 0; hf < 2; ++hf)
+                    for (int r = 0; r < 16; ++r) {
+                        const int64_t j = t * g2l::TILE + g2l::reg_row(r, hf);
+                        if (j < G && j != gi) half[hf] = half[hf] + g2l::neg_term(s[(size_t)j]);
+                    }
+            rows[N + i] = half[0] + half[1];
+            if (!grad) continue;
+            std::vector<float> acc((size_t)F, 0.0f);
+            for (int64_t t = 0; t < TG; ++t)
+                for (int r = 0; r < 16; ++r)
+                    for (int hf = 0; hf < 2; ++hf) {
+                        const int64_t j = t * g2l::TILE + g2l::reg_row(r, hf);
+                        if (j < G) {
+                            const float w = g2l::weight(cp, cn, s[(size_t)j], j == gi);
+                            W[(size_t)(i * G + j)] = w;
+                            for (int64_t k = 0; k < F; ++k) acc[(size_t)k] = fmaf(w, g[j * F + k], acc[(size_t)k]);
+                        } else {
+                            for (int64_t k = 0; k < F; ++k) acc[(size_t)k] = fmaf(0.0f, 0.0f, acc[(size_t)k]);
+                        }
+                    }
+            for (int64_t k = 0; k < F; ++k) gh[i * F + k] = acc[(size_t)k];
+        }
+    });
+    const double tp = spmm::list_sum(N, [](int64_t) { return 1.0; }, [&](int64_t e) { return rows[e]; }, false, 0.0, 0.0);
+    const double tn = spmm::list_sum(N, [](int64_t) { return 1.0; }, [&](int64_t e) { return rows[N + e]; }, false, 0.0, 0.0);
+    *loss = g2l::jsd_loss(tp, tn, N, G);
+    if (!grad) return 0;
+    const int64_t P = g2l::num_parts(N, G, F);
+    over_blocks(G, block_rows, threads, [&](int64_t j0, int64_t j1) {
+        std::vector<float> acc((size_t)F), D((size_t)F);
+        for (int64_t j = j0; j < j1; ++j) {
+            std::fill(D.begin(), D.end(), 0.0f);
+            for (int64_t p = 0; p < P; ++p) {
+                std::fill(acc.begin(), acc.end(), 0.0f);
+                const int64_t tb = g2l::part_begin(N, G, F, p), te = g2l::part_begin(N, G, F, p + 1);
+                if (G == 1) {
+                    for (int64_t i = tb * g2l::TILE; i < std::min(N, te * g2l::TILE); ++i)
+                        for (int64_t k = 0; k < F; ++k) {
+                            acc[(size_t)k] = fmaf(W[(size_t)i], h[i * F + k], acc[(size_t)k]);
+                            acc[(size_t)k] = fmaf(W[(size_t)(N + i)], neg[i * F + k], acc[(size_t)k]);
+                        }
+                } else {
+                    for (int64_t t = tb; t < te; ++t)
+                        for (int r = 0; r < 16; ++r)
+                            for (int hf = 0; hf < 2; ++hf) {
+                                const int64_t i = t * g2l::TILE + g2l::reg_row(r, hf);
+                                if (i < N) {
+                                    const float w = W[(size_t)(i * G + j)];
+                                    for (int64_t k = 0; k < F; ++k) acc[(size_t)k] = fmaf(w, h[i * F + k], acc[(size_t)k]);
+                                } else {
+                                    for (int64_t k = 0; k < F; ++k) acc[(size_t)k] = fmaf(0.0f, 0.0f, acc[(size_t)k]);
+                                }
+                            }
+                }
+                for (int64_t k = 0; k < F; ++k) D[(size_t)k] = D[(size_t)k] + acc[(size_t)k];
+            }
+            for (int64_t k = 0; k < F; ++k) gg[j * F + k] = D[(size_t)k];
+        }
+    });
+    return 0;
+}
+
+// rows [N] (c_i as doubles), loss [1]; with grad != 0: gh (N, F)
+int g2l_bootstrap_mirror(const float* h, const float* g, int64_t N, int64_t F, const int64_t* node_ptr, int64_t G, int64_t block_rows,
+                         int threads, double gup, int grad, double* rows, double* loss, float* gh) {
+    if (N < 1 || F < 1 || F > g2l::MAX_F || G < 1 || block_rows < 1) return 1;
+    std::vector<float> ghat((size_t)(G * F));
+    for (int64_t j = 0; j < G; ++j) {
+        const double nrm = infonce::norm_of(infonce::norm2(g + j * F, F));
+        for (int64_t k = 0; k < F; ++k) ghat[(size_t)(j * F + k)] = infonce::hat(g[j * F + k], nrm);
+    }
+    const double scale = g2l::boot_scale(gup, G);
+    over_blocks(N, block_rows, threads, [&](int64_t i0, int64_t i1) {
+        std::vector<float> hh((size_t)F);
+        for (int64_t i = i0; i < i1; ++i) {
+            const int64_t gi = g2l::graph_of(node_ptr, G, N, i);
+            const double n2 = infonce::norm2(h + i * F, F);
+            const double nrm = infonce::norm_of(n2);
+            for (int64_t k = 0; k < F; ++k) hh[(size_t)k] = infonce::hat(h[i * F + k], nrm);
+            rows[i] = (double)score(ghat.data() + gi * F, hh.data(), F);
+            if (!grad) continue;
+            double dot = 0.0;
+            for (int64_t k = 0; k < F; ++k) dot = infonce::dot_step(dot, hh[(size_t)k], g2l::boot_grad_hat(scale, ghat[(size_t)(gi * F + k)]));
+            for (int64_t k = 0; k < F; ++k)
+                gh[i * F + k] = infonce::grad_in(g2l::boot_grad_hat(scale, ghat[(size_t)(gi * F + k)]), hh[(size_t)k], dot, nrm, infonce::norm_clamped(n2));
+        }
+    });
+    *loss = g2l::boot_loss(spmm::list_sum(N, [](int64_t) { return 1.0; }, [&](int64_t e) { return rows[e]; }, false, 0.0, 0.0), G);
+    return 0;
+}
+
+}  // extern "C"
