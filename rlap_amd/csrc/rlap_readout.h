@@ -1,5 +1,5 @@
 // rlap_readout.h -- the per-graph readout of batched node embeddings (rlap_graph_readout, rlap_readout.hip): what one
-// element is, and the arithmetic that maps the work of a call to (graph, chunk).  Plain __host__ __device__ functions without any
+// element is, the arithmetic that maps the work of a call to (graph, chunk), and the rule that chooses the kernel.  Plain __host__ __device__ functions without any
 // HIP dependency, as rlap_spmm.h: tests/csrc/readout_map_main.cc compiles this file with g++ under the sanitizers and checks the map
 // exhaustively; the kernels read the same functions.
 //
@@ -49,6 +49,22 @@ RLAP_SPMM_HD bool item_of(const int64_t* choff, int64_t G, int64_t q, int64_t* g
     *g = lo;
     *k = q - choff[lo];
     return true;
+}
+
+// Which kernel a call takes (launch_readout / launch_backward of rlap_readout.hip): a row of F elements of `elem_bytes` (4 or 8)
+// takes 16 bytes a lane (`vec`) when F is a multiple of V = 16 / elem_bytes and both pointers lie on the 16-byte grid, else one
+// element a lane.  `lg` is the smallest value with 2^lg >= lanes, capped at 6: below 6 the staged kernel for narrow rows runs with
+// groups of 2^lg lanes, at 6 the kernel of one wave a row with `ftiles` tiles of 64 lanes.  The backward call reads vec and lanes.
+struct Dispatch { bool vec; int64_t lanes; int lg; int64_t ftiles; };
+RLAP_SPMM_HD Dispatch dispatch(int64_t F, int elem_bytes, bool aligned16) {
+    const int64_t V = 16 / elem_bytes;
+    Dispatch d;
+    d.vec = aligned16 && F % V == 0;
+    d.lanes = d.vec ? F / V : F;
+    d.lg = 0;
+    while (d.lg < 6 && ((int64_t)1 << d.lg) < d.lanes) ++d.lg;
+    d.ftiles = (d.lanes + 63) >> 6;
+    return d;
 }
 
 // the definition of one element: feat(e) is the feature of the e-th id of the graph

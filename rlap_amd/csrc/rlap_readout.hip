@@ -292,11 +292,10 @@ size_t carve_readout(Carve& C, int64_t L, int64_t N, int64_t F, int64_t G, Bufs&
     return C.off + 256;
 }
 
-// lanes of a row: 16 bytes a lane when F and the pointers allow
+// lanes of a row: 16 bytes a lane when F and the pointers allow (readout::dispatch, rlap_readout.h)
 template <class T>
-bool vec_ok(int64_t F, const void* p, const void* q) {
-    constexpr int V = 16 / (int)sizeof(T);
-    return F % V == 0 && ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(q)) & 15) == 0;
+readout::Dispatch dispatch_of(int64_t F, const void* p, const void* q) {
+    return readout::dispatch(F, (int)sizeof(T), ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(q)) & 15) == 0);
 }
 
 template <class T>
@@ -304,11 +303,10 @@ int launch_readout(hipStream_t st, Ro a, const ReadoutArgs& g) {
     constexpr int V = 16 / (int)sizeof(T);
     const T* x = static_cast<const T*>(g.x);
     T* y = static_cast<T*>(g.y);
-    const bool vec = vec_ok<T>(a.F, x, y);
-    const int64_t lanes = vec ? a.F / V : a.F;
-    a.lg = 0;
-    while (a.lg < 6 && ((int64_t)1 << a.lg) < lanes) ++a.lg;
-    a.ftiles = (lanes + 63) >> 6;
+    const readout::Dispatch d = dispatch_of<T>(a.F, x, y);
+    const bool vec = d.vec;
+    a.lg = d.lg;
+    a.ftiles = d.ftiles;
     const int64_t bound = readout::chunk_bound(a.N, a.G);
     if (a.N > 0) {
         if (a.lg == 6) {
@@ -332,8 +330,9 @@ int launch_backward(hipStream_t st, Ro a, const ReadoutArgs& g) {
     constexpr int V = 16 / (int)sizeof(T);
     const T* gy = static_cast<const T*>(g.x);
     T* gx = static_cast<T*>(g.y);
-    const bool vec = vec_ok<T>(a.F, gy, gx);
-    const unsigned nb = ro_blocks(a.N * (vec ? a.F / V : a.F), RO_THREADS);
+    const readout::Dispatch d = dispatch_of<T>(a.F, gy, gx);
+    const bool vec = d.vec;
+    const unsigned nb = ro_blocks(a.N * d.lanes, RO_THREADS);
     if (vec) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ro_backward<T, V>), dim3(nb), dim3(RO_THREADS), 0, st, a, gy, gx);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ro_backward<T, 1>), dim3(nb), dim3(RO_THREADS), 0, st, a, gy, gx);
     RLAP_HIPCHK(hipGetLastError());

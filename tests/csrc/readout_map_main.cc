@@ -1,7 +1,8 @@
 // The host-side arithmetic of the readout (rlap_amd/csrc/rlap_readout.h: clamped ranges, chunk counts, bounds, the map from work item
-// to (graph, chunk), the definition of an element) in a stand-alone program, built with g++ -fsanitize=address,undefined by
+// to (graph, chunk), the definition of an element, the dispatch rule of the launchers for every F up to 65,536) in a stand-alone program, built with g++ -fsanitize=address,undefined by
 // tests/test_readout_cpu.py.  Reads tables from standard input, one a line: "<well formed 0/1> <N> <G> <G+1 entries>", and checks
-// each exhaustively; prints "table <chunks> <chunked graphs> <part chunks>" per table and "<n> failures" at the end.
+// each exhaustively; prints "dispatch <cases> <narrow> <16 bytes a lane>", "table <chunks> <chunked graphs> <part chunks>" per table
+// and "<n> failures" at the end.
 #include <stdint.h>
 
 #include <cmath>
@@ -89,8 +90,36 @@ static void check_rule() {
     }
 }
 
+// the dispatch rule of both launchers, for every F the exports accept, both element sizes and both alignments
+static void check_dispatch() {
+    long long cases = 0, narrow = 0, vec = 0;
+    for (int elem = 4; elem <= 8; elem += 4) {
+        const int64_t V = 16 / elem;
+        for (int aligned = 0; aligned < 2; ++aligned) {
+            for (int64_t F = 1; F <= 65536; ++F) {
+                const readout::Dispatch d = readout::dispatch(F, elem, aligned != 0);
+                bool ok = d.lanes >= 1 && d.lanes <= 64 * d.ftiles && d.lanes > 64 * (d.ftiles - 1);
+                ok = ok && d.lg >= 0 && d.lg <= 6;
+                ok = ok && (d.lg == 6 || ((int64_t)1 << d.lg) >= d.lanes);                  // a group holds the row's lanes (6: a wave a row)
+                ok = ok && (d.lg == 0 || ((int64_t)1 << (d.lg - 1)) < d.lanes);             // ... and is the smallest that does
+                if (d.lg < 6) {   // the staged kernel: C = 64 >> lg chunks of upp = 8 x lanes units fit the 64 lanes x 8 turns of a piece
+                    ok = ok && d.lanes <= 32 && d.ftiles == 1 && (int64_t)(64 >> d.lg) * 8 * d.lanes <= 512;
+                } else {
+                    ok = ok && d.lanes > 32;
+                }
+                ok = ok && (!d.vec || (F % V == 0 && aligned)) && (d.vec || !(F % V == 0 && aligned));
+                ok = ok && d.lanes == (d.vec ? F / V : F);
+                if (!ok) { ++failures; std::printf("FAILED dispatch F=%lld elem=%d aligned=%d\n", (long long)F, elem, aligned); }
+                ++cases; narrow += d.lg < 6; vec += d.vec;
+            }
+        }
+    }
+    std::printf("dispatch %lld %lld %lld\n", cases, narrow, vec);
+}
+
 int main() {
     check_rule();
+    check_dispatch();
     int wf;
     int64_t N, G;
     int tables = 0;

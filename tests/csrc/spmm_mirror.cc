@@ -6,9 +6,19 @@
 
 #include <vector>
 
+#include "rlap_readout.h"
 #include "rlap_spmm.h"
 
 extern "C" {
+
+// the readout's dispatch rule (rlap_readout.h), for the regime accounting of tests/test_gpu_readout_regimes.py: out = vec, lanes, lg, ftiles
+void readout_dispatch(int64_t F, int elem_bytes, int aligned16, int64_t* out) {
+    const rlap::readout::Dispatch d = rlap::readout::dispatch(F, elem_bytes, aligned16 != 0);
+    out[0] = d.vec ? 1 : 0;
+    out[1] = d.lanes;
+    out[2] = d.lg;
+    out[3] = d.ftiles;
+}
 
 int spmm_chunk() { return rlap::spmm::CHUNK; }
 

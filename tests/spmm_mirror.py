@@ -24,7 +24,16 @@ def build(directory):
     lib.spmm_list.argtypes = [i64, vp, vp, ci, dbl, dbl]
     lib.spmm_entries.restype = None
     lib.spmm_entries.argtypes = [i64, vp, vp, vp, i64, i64, vp, ci, ci, vp]
+    lib.readout_dispatch.restype = None
+    lib.readout_dispatch.argtypes = [i64, ci, ci, vp]
     return lib
+
+
+def readout_dispatch(lib, F, elem_bytes, aligned16):
+    """{"vec", "lanes", "lg", "ftiles"} of rlap_readout.h's dispatch rule: which kernel a readout of F columns takes."""
+    out = np.zeros(4, dtype=np.int64)
+    lib.readout_dispatch(int(F), int(elem_bytes), 1 if aligned16 else 0, out.ctypes.data)
+    return {"vec": bool(out[0]), "lanes": int(out[1]), "lg": int(out[2]), "ftiles": int(out[3])}
 
 
 def list_sum(lib, c, x, loop=None):

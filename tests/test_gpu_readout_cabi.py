@@ -1,7 +1,7 @@
 """The two readout exports (rlap_graph_readout / rlap_graph_readout_backward) called through the C ABI on raw device pointers and a
 handle of the test's own, after the pattern of tests/test_gpu_plan_cabi.py: the arena the library owns, a caller's arena that is
 too small and one of the size the library then asks for; the statuses of the host checks, which answer before anything is launched
-(y is filled with a pattern first and must come back unchanged); what h_info reports without the table being read back; and a
+(y is filled with a pattern first and must come back unchanged); what h_info reports without the table being read back; pointers off the 16-byte grid, which take the one-element kernels; and a
 table that is not well formed on a tiny input -- decreasing, or ending beyond num_nodes -- which the kernels clamp: the call ends
 cleanly with some numbers.  That case exercises the clamp; it provokes no error."""
 import ctypes
@@ -52,9 +52,10 @@ def forward(env, h, x, node_ptr, flags, y=None, over=None):
     return rc, y, info
 
 
-def backward(env, h, gy, node_ptr, N, flags, over=None):
+def backward(env, h, gy, node_ptr, N, flags, over=None, gx=None):
     L, G, F = gy.shape
-    gx = torch.full((L, N, F), PATTERN, dtype=gy.dtype, device=gy.device)
+    if gx is None:
+        gx = torch.full((L, N, F), PATTERN, dtype=gy.dtype, device=gy.device)
     info = env["_lib"].ReadoutInfo()
     a = {"gy": ptr(gy), "L": L, "N": N, "F": F, "node_ptr": ptr(node_ptr), "G": G, "flags": flags | (X_F32 if gy.dtype == torch.float32 else 0), "gx": ptr(gx)}
     a.update(over or {})
@@ -99,6 +100,59 @@ def test_both_exports_on_raw_pointers(env, handle, dtype):
         if flags == MEAN:
             want = (want.cpu().double() / (p[1:] - p[:-1]).double()[batch.cpu()][None, :, None]).to(dtype).cuda()
         assert torch.equal(gx, want)
+
+
+def off_the_grid(t=None, shape=None, dtype=None):
+    """(view, buffer): a contiguous view one element into a buffer filled with the pattern, holding t's values if given."""
+    shape = tuple(t.shape) if t is not None else shape
+    count = 1
+    for s in shape:
+        count *= s
+    big = torch.full((count + 8,), PATTERN, dtype=t.dtype if t is not None else dtype, device="cuda")
+    if t is not None:
+        big[1:1 + count] = t.reshape(-1)
+    v = big[1:1 + count].view(shape)
+    assert big.data_ptr() % 16 == 0 and v.is_contiguous() and v.data_ptr() % 16 != 0 and v.data_ptr() % v.element_size() == 0
+    return v, big
+
+
+def bits_equal(a, b):
+    it = torch.int64 if a.dtype == torch.float64 else torch.int32
+    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.contiguous().view(it), b.contiguous().view(it))
+
+
+def around_intact(big, count):
+    return float(big[0]) == PATTERN and bool((big[1 + count:] == PATTERN).all())
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+@pytest.mark.parametrize("F", [16, 200])
+def test_misaligned_pointers(env, handle, F, dtype):
+    """F = 16 and F = 200 take the 16-byte-a-lane kernels (the staged and the one-wave-a-row kernel of the forward call, the gather of
+    the backward call); an x, a y, a gy or a gx one element past a 16-byte boundary must take the one-element kernels: RLAP_OK, the
+    bits of the aligned call, nothing written in front of or behind the result."""
+    assert F % (16 // torch.empty(0, dtype=dtype).element_size()) == 0
+    x, node_ptr = small(dtype, F=F)
+    L, N, G = x.shape[0], x.shape[1], node_ptr.numel() - 1
+    for flags in (0, MEAN):
+        rc, y0, _ = forward(env, handle, x, node_ptr, flags)
+        assert rc == OK and x.data_ptr() % 16 == 0 and y0.data_ptr() % 16 == 0
+        assert torch.equal(y0, exact(x, node_ptr, flags == MEAN))
+        rc, gx0, _ = backward(env, handle, y0, node_ptr, N, flags)
+        assert rc == OK and gx0.data_ptr() % 16 == 0 and bool((gx0 != PATTERN).all())
+        for x_off, y_off in ((True, False), (False, True), (True, True)):
+            xv = off_the_grid(x)[0] if x_off else x
+            yv, ybig = off_the_grid(shape=(L, G, F), dtype=dtype) if y_off else (None, None)
+            rc, y, _ = forward(env, handle, xv, node_ptr, flags, y=yv)
+            assert rc == OK, (x_off, y_off)
+            assert bits_equal(y, y0), (x_off, y_off)
+            assert not y_off or around_intact(ybig, L * G * F), (x_off, y_off)
+            gyv = off_the_grid(y0)[0] if x_off else y0
+            gxv, gbig = off_the_grid(shape=(L, N, F), dtype=dtype) if y_off else (None, None)
+            rc, gx, _ = backward(env, handle, gyv, node_ptr, N, flags, gx=gxv)
+            assert rc == OK, (x_off, y_off)
+            assert bits_equal(gx, gx0), (x_off, y_off)
+            assert not y_off or around_intact(gbig, L * N * F), (x_off, y_off)
 
 
 def test_one_graph_reports_exact_counts(env, handle):

@@ -3,8 +3,8 @@
   * the rule -- spmm_mirror.list_sum(lib, ones, column) is the readout's definition (tests/csrc/spmm_mirror.cc around
     rlap_amd/csrc/rlap_spmm.h): against math.fsum within (n - 1) 2^-53 sum |x|, and bit for bit against a Python restatement of
     the chunk rule on both sides of the chunk edges;
-  * the host-side arithmetic of rlap_amd/csrc/rlap_readout.h (clamped ranges, chunk counts, bounds, work item -> (graph, chunk)) in
-    a stand-alone program under -fsanitize=address,undefined, exhaustively for the tables of tests/test_gpu_readout.py and for
+  * the host-side arithmetic of rlap_amd/csrc/rlap_readout.h (clamped ranges, chunk counts, bounds, work item -> (graph, chunk), the
+    dispatch rule of the launchers for every F) in a stand-alone program under -fsanitize=address,undefined, exhaustively for the tables of tests/test_gpu_readout.py and for
     tables that are not well formed;
   * the Python -> C mapping of both exports on a stub library, in the style of tests/test_plan_entry_points_cpu.py;
   * the layout of rlap_readout_info against _lib.ReadoutInfo;
@@ -105,6 +105,9 @@ def test_the_work_map_under_asan_ubsan(tmp_path):
     r = subprocess.run([str(exe)], input="\n".join(lines) + "\n", capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert f"{len(lines)} tables, 0 failures" in r.stdout
+    # readout::dispatch over F = 1..65,536, two element sizes, two alignments: the cases, those of the narrow kernel (F <= 32, or 16
+    # bytes a lane and F <= 32 V), those of 16 bytes a lane (aligned and F a multiple of V = 4, 2)
+    assert f"dispatch {4 * 65536} {32 + 32 + (32 + 24) + (32 + 16)} {65536 // 4 + 65536 // 2}" in r.stdout.splitlines()
     got = [tuple(map(int, ln.split()[1:])) for ln in r.stdout.splitlines() if ln.startswith("table ")]
     for t, (chunks, chunked, part) in zip(WELL_FORMED, got):      # the counts ops.GraphTable reports are the header's
         sizes = np.diff(t)
