@@ -649,6 +649,63 @@ int rlap_g2l_bootstrap(rlap_handle h, const float* d_h, const float* d_g, int64_
 int rlap_g2l_bootstrap_backward(rlap_handle h, const float* d_h, const float* d_g, int64_t N, int64_t F, const int64_t* d_node_ptr,
                                 int64_t G, int flags, const double* d_gup, float* d_gh, rlap_g2l_info* h_info);
 
+/* The linear-probe evaluator on the device: R independent runs of LREvaluator's loop (scripts/node_shared.py:163-230) or
+ * of CCA-SSG/main.py:152-194's in one call -- full-batch Adam on a Linear(F, C) under log-softmax + NLL, scored on a validation and a
+ * test list, the selection rule applied on the device.
+ *   d_x, N, F, ldx  : features (N, F) float32, row i at d_x + i * ldx (ldx >= F); 1 <= F <= 512; only read
+ *   d_y, C          : [N] int64 labels in [0, C), 2 <= C <= 64
+ *   R               : runs, 1 <= R <= 32
+ *   d_train, h_train_ptr (and valid, test) : run r's list is d_*[h_*_ptr[r] .. h_*_ptr[r+1]), row indices in [0, N) ON THE DEVICE in
+ *                     any order, a repeated row counting twice; the [R+1] offsets ON THE HOST, from 0, strictly increasing (no list
+ *                     is empty)
+ *   epochs, lr, weight_decay, beta1, beta2, eps : Adam with L2 weight decay; epochs >= 1, lr finite
+ *   test_interval, select : RLAP_PROBE_SELECT_SCRIPTS scores after every epoch e (from 0) with (e + 1) % test_interval == 0 and records
+ *                     the test scores when the validation count rises above the best so far; RLAP_PROBE_SELECT_CCA scores after every
+ *                     epoch (test_interval is not read): when val >= best_val, best_val = val, and when test > best_test the test
+ *                     scores are recorded.  Both compare integer counts of correct rows: the denominators are fixed, so below 2^24
+ *                     rows this equals the reference's comparison of float32 ratios.
+ *   d_weight0, d_bias0 : (R, C, F), (R, C) float32: the initial parameters, so the call is a pure function of its arguments
+ *   d_weight, d_bias   : the final parameters (may be the initial buffers)
+ *   d_scores        : (R, 4) doubles: micro-F1, macro-F1 and accuracy of the test list at the recorded evaluation, the last epoch's
+ *                     training loss
+ *   d_best          : (R, 2) int64: the recorded epoch and the best validation count
+ *   d_confusion     : (R, 2, C, C) int64: validation and test at the recorded evaluation, rows true, columns predicted
+ *   d_status        : one int32 ON THE DEVICE, valid once the stream has run: RLAP_OK, RLAP_E_INDEX_RANGE (an index outside [0, N): row
+ *                     0 was read in its place) or RLAP_E_BAD_ARG (a label outside [0, C): the row marks no class and is not counted)
+ *   h_info          : (nullable) what the call did; detail says which host-side check refused it (1 shape, 2 a list, 3 a parameter,
+ *                     4 a pointer)
+ * rlap_probe_scores is the scoring pass alone on one list per run: d_pred one int64 per listed row, d_confusion (R, C, C), d_scores
+ * (R, 3): micro-F1, macro-F1, accuracy.
+ * Every value and the order of every sum are defined in rlap_amd/csrc/rlap_probe.h: the logits and the gradient sums are float32 fmaf
+ * chains (what the f32 matrix-core instruction computes), the gradient per part of the training list, the parts a function of (n, F,
+ * C) alone and added in float64; the softmax with rlap_infonce.h's exponential; Adam operation by operation.  The parameter
+ * trajectory holds IEEE operations only, so the same input gives the same bits, whatever the arena held; no atomic touches a
+ * floating-point value; neither call synchronises with the host.  The scores are sklearn's accuracy_score and f1_score (micro, macro)
+ * as the scripts call them, float64 functions of the integer counts.
+ * A null pointer, N < 1, F < 1, C < 2, ldx < F, R < 1, an empty list or offsets that do not start at 0, epochs < 1, test_interval < 1,
+ * an unknown select, an lr that is not finite, weight_decay < 0, a beta outside [0, 1), eps <= 0: RLAP_E_BAD_ARG.  F > 512, C > 64,
+ * R > 32, N >= 2^31: RLAP_E_TOO_LARGE.  Scratch from the arena (RLAP_E_WORKSPACE when a caller-provided one is too small, the
+ * workspace-needed query saying how much). */
+enum { RLAP_PROBE_SELECT_SCRIPTS = 0, RLAP_PROBE_SELECT_CCA = 1 };
+typedef struct {
+    int64_t runs;             /* R                                                                    */
+    int64_t parts;            /* parts of the longest training list: a function of (n, F, C)          */
+    int64_t launches;         /* kernels the call enqueued                                            */
+    int64_t arena_bytes;      /* scratch bytes of the call                                            */
+    int32_t host_syncs;       /* host synchronisations of the call: 0                                 */
+    int32_t detail;           /* the host-side check that refused the call, 0 otherwise               */
+} rlap_probe_info;
+
+int rlap_linear_probe(rlap_handle h, const float* d_x, int64_t N, int64_t F, int64_t ldx, const int64_t* d_y, int64_t C, int64_t R,
+                      const int64_t* d_train, const int64_t* h_train_ptr, const int64_t* d_valid, const int64_t* h_valid_ptr,
+                      const int64_t* d_test, const int64_t* h_test_ptr, int64_t epochs, double lr, double weight_decay,
+                      int64_t test_interval, int select, double beta1, double beta2, double eps, const float* d_weight0,
+                      const float* d_bias0, float* d_weight, float* d_bias, double* d_scores, int64_t* d_best, int64_t* d_confusion,
+                      int32_t* d_status, rlap_probe_info* h_info);
+int rlap_probe_scores(rlap_handle h, const float* d_x, int64_t N, int64_t F, int64_t ldx, const int64_t* d_y, int64_t C, int64_t R,
+                      const int64_t* d_index, const int64_t* h_ptr, const float* d_weight, const float* d_bias, int64_t* d_pred,
+                      int64_t* d_confusion, double* d_scores, int32_t* d_status, rlap_probe_info* h_info);
+
 /* The op with the step BEFORE the path fused in (scripts/node_shared.py:326-327,
  * scripts/augmentor_benchmarks.py:77-78):
  *   symmetrize != 0 : the input holds every undirected edge in one or both directions; (b,a) is

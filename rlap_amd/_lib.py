@@ -25,6 +25,7 @@ EXPORTS = [
     "rlap_graph_readout", "rlap_graph_readout_backward", "rlap_infonce", "rlap_infonce_backward",
     "rlap_cca_loss", "rlap_cca_loss_backward",
     "rlap_g2l_jsd", "rlap_g2l_jsd_backward", "rlap_g2l_bootstrap", "rlap_g2l_bootstrap_backward",
+    "rlap_linear_probe", "rlap_probe_scores",
 ]
 
 E_INDEX_RANGE = 2   # RLAP_E_INDEX_RANGE
@@ -46,6 +47,8 @@ PLAN_MAGIC = 0x504C414E   # rlap_plan_desc.magic of a successful build
 READOUT_MEAN, READOUT_X_F32 = 1, 32
 # rlap_infonce flags
 INFONCE_POSITIVE_RAW = 1
+# rlap_linear_probe select
+PROBE_SELECT_SCRIPTS, PROBE_SELECT_CCA = 0, 1
 
 # rlap_stats.elim_kernel
 KERNEL_NONE, KERNEL_ROUND, KERNEL_FLOW = 0, 1, 2
@@ -172,6 +175,14 @@ class G2lInfo(_Report):
     ]
 
 
+class ProbeInfo(_Report):
+    """rlap_probe_info (include/rlap_hip.h)."""
+    _fields_ = [
+        ("runs", ctypes.c_int64), ("parts", ctypes.c_int64), ("launches", ctypes.c_int64), ("arena_bytes", ctypes.c_int64),
+        ("host_syncs", ctypes.c_int32), ("detail", ctypes.c_int32),
+    ]
+
+
 def load():
     """dlopen the library and declare prototypes. Raises if it is not built."""
     global _lib
@@ -252,6 +263,12 @@ def load():
     lib.rlap_g2l_bootstrap.argtypes = [vp, vp, vp, i64, i64, vp, i64, ci, vp, vp, ctypes.POINTER(G2lInfo)]
     lib.rlap_g2l_bootstrap_backward.restype = ci
     lib.rlap_g2l_bootstrap_backward.argtypes = [vp, vp, vp, i64, i64, vp, i64, ci, vp, vp, ctypes.POINTER(G2lInfo)]
+    dbl = ctypes.c_double
+    lib.rlap_linear_probe.restype = ci
+    lib.rlap_linear_probe.argtypes = [vp, vp, i64, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, i64, dbl, dbl, i64, ci, dbl, dbl, dbl,
+                                      vp, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(ProbeInfo)]
+    lib.rlap_probe_scores.restype = ci
+    lib.rlap_probe_scores.argtypes = [vp, vp, i64, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(ProbeInfo)]
     lib.rlap_approx_chol_views.restype = ci
     lib.rlap_approx_chol_views.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, vp, ci, ci, vp, u64, vp, i64, vp,
                                            ctypes.POINTER(Stats)]

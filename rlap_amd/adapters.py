@@ -809,3 +809,54 @@ class rLapDGL:
         if dgl is not None and hasattr(graph, "edges"):
             return dgl.graph((ei[0], ei[1]), num_nodes=num_nodes)
         return ei, num_nodes
+
+
+def get_split(num_samples: int, train_ratio: float = 0.1, test_ratio: float = 0.8, runs: Optional[int] = None, generator=None):
+    """PyGCL's get_split (GCL/eval/eval.py), restated from the published text -- PyGCL is not a dependency, as SnapshotGCNConv
+    restates PyG's layer: a randperm of the rows is cut at int(n * train_ratio) and int(n * test_ratio); 'train' is the first
+    train_size rows, 'valid' the NEXT test_size rows and 'test' the rest, exactly as published (so with the defaults 'valid' holds
+    80 % of the rows and 'test' 10 %).  runs=R returns a list of R splits drawn one after the other from `generator`."""
+    assert train_ratio + test_ratio < 1
+    train_size = int(num_samples * train_ratio)
+    test_size = int(num_samples * test_ratio)
+
+    def one():
+        indices = torch.randperm(num_samples, generator=generator)
+        return {"train": indices[:train_size], "valid": indices[train_size: test_size + train_size], "test": indices[test_size + train_size:]}
+
+    return one() if runs is None else [one() for _ in range(int(runs))]
+
+
+class LREvaluator:
+    """The reference's LREvaluator (scripts/node_shared.py:163-230) on ops.linear_probe: evaluate(x, y, split) returns its dict of
+    Python floats {"micro_f1", "macro_f1", "accuracy"}; reading them is the one host synchronisation.  evaluate_runs(x, y, splits)
+    takes a list of splits -- the ten of a test() loop, say --, makes ONE call and returns the list of dicts.  select="cca" applies
+    CCA-SSG/main.py:172-186's rule instead.  The initial parameters are drawn as the reference draws them, from `generator`."""
+
+    def __init__(self, num_epochs: int = 2000, learning_rate: float = 0.01, weight_decay: float = 0.0, test_interval: int = 20,
+                 select: str = "scripts", generator=None):
+        self.num_epochs = num_epochs
+        self.learning_rate = learning_rate
+        self.weight_decay = weight_decay
+        self.test_interval = test_interval
+        self.select = select
+        self.generator = generator
+        self.last = None   # the device result of the last call
+
+    def evaluate_runs(self, x: torch.Tensor, y: torch.Tensor, splits) -> list:
+        splits = list(splits)
+        res = ops.linear_probe(x, y, [s["train"] for s in splits], [s["valid"] for s in splits], [s["test"] for s in splits],
+                               epochs=self.num_epochs, lr=self.learning_rate, weight_decay=self.weight_decay,
+                               test_interval=self.test_interval, select=self.select, generator=self.generator)
+        self.last = res
+        status = int(res["status"])   # (the synchronisation)
+        if status != 0:
+            raise ValueError("LREvaluator: " + ("an index outside [0, N)" if status == 2 else "a label outside [0, num_classes)"))
+        micro, macro, acc = res["micro_f1"].tolist(), res["macro_f1"].tolist(), res["accuracy"].tolist()
+        return [{"micro_f1": micro[r], "macro_f1": macro[r], "accuracy": acc[r]} for r in range(len(splits))]
+
+    def evaluate(self, x: torch.Tensor, y: torch.Tensor, split: dict) -> dict:
+        return self.evaluate_runs(x, y, [split])[0]
+
+    def __call__(self, x: torch.Tensor, y: torch.Tensor, split: dict) -> dict:
+        return self.evaluate(x, y, split)

@@ -35,6 +35,8 @@
 #include "rlap_g2l_api.h"
 #include "rlap_cca.h"
 #include "rlap_cca_api.h"
+#include "rlap_probe.h"
+#include "rlap_probe_api.h"
 
 using namespace rlap;
 
@@ -1770,6 +1772,83 @@ int rlap_g2l_bootstrap_backward(rlap_handle h, const float* d_h, const float* d_
     G2lArgs a{};
     a.h = d_h; a.g = d_g; a.N = N; a.F = F; a.node_ptr = d_node_ptr; a.G = G; a.gup = d_gup; a.gh = d_gh;
     return g2l_call(h, g2l::BOOT_BACKWARD, a, h_info, {{d_gh, (size_t)(N * F) * 4}});
+}
+
+namespace {
+
+// what both probe exports check on the host; the lists' contents and the labels are checked by the kernels (the status word)
+int probe_check(rlap_handle h, const ProbeArgs& a, int lists, bool train, rlap_probe_info* h_info) {
+    if (h_info) *h_info = rlap_probe_info{};
+    auto fail = [&](int rc, int detail) { if (h_info) h_info->detail = detail; return rc; };
+    if (!h || !a.x || !a.y || !a.w0 || !a.b0 || !a.scores || !a.confusion || !a.status) return fail(RLAP_E_BAD_ARG, probe::DETAIL_POINTER);
+    if (train ? (!a.w || !a.b || !a.best) : !a.pred) return fail(RLAP_E_BAD_ARG, probe::DETAIL_POINTER);
+    if (a.N < 1 || a.F < 1 || a.C < 2 || a.R < 1 || a.ldx < a.F) return fail(RLAP_E_BAD_ARG, probe::DETAIL_SHAPE);
+    if (a.F > probe::MAX_F || a.C > probe::MAX_C || a.R > probe::MAX_RUNS || a.N >= (int64_t)1 << 31) return fail(RLAP_E_TOO_LARGE, probe::DETAIL_SHAPE);
+    for (int s = 0; s < lists; ++s)
+        if (!a.idx[s] || !probe_lists_ok(a.hptr[s], a.R)) return fail(RLAP_E_BAD_ARG, probe::DETAIL_LIST);
+    if (train) {
+        if (a.epochs < 1 || a.test_interval < 1 || (a.select != probe::SELECT_SCRIPTS && a.select != probe::SELECT_CCA))
+            return fail(RLAP_E_BAD_ARG, probe::DETAIL_PARAM);
+        if (!probe::finite_ok(a.lr) || !probe::finite_ok(a.wd) || a.wd < 0.0 || !(a.beta1 >= 0.0 && a.beta1 < 1.0) ||
+            !(a.beta2 >= 0.0 && a.beta2 < 1.0) || !probe::finite_ok(a.eps) || !(a.eps > 0.0))
+            return fail(RLAP_E_BAD_ARG, probe::DETAIL_PARAM);
+    }
+    if (h_info) h_info->runs = a.R;
+    return RLAP_OK;
+}
+
+}  // namespace
+
+int rlap_linear_probe(rlap_handle h, const float* d_x, int64_t N, int64_t F, int64_t ldx, const int64_t* d_y, int64_t C, int64_t R,
+                      const int64_t* d_train, const int64_t* h_train_ptr, const int64_t* d_valid, const int64_t* h_valid_ptr,
+                      const int64_t* d_test, const int64_t* h_test_ptr, int64_t epochs, double lr, double weight_decay,
+                      int64_t test_interval, int select, double beta1, double beta2, double eps, const float* d_weight0,
+                      const float* d_bias0, float* d_weight, float* d_bias, double* d_scores, int64_t* d_best, int64_t* d_confusion,
+                      int32_t* d_status, rlap_probe_info* h_info) {
+    ProbeArgs a{};
+    a.x = d_x; a.N = N; a.F = F; a.ldx = ldx; a.y = d_y; a.C = C; a.R = R;
+    a.idx[0] = d_train; a.hptr[0] = h_train_ptr; a.idx[1] = d_valid; a.hptr[1] = h_valid_ptr; a.idx[2] = d_test; a.hptr[2] = h_test_ptr;
+    a.epochs = epochs; a.test_interval = test_interval; a.select = select; a.lr = lr; a.wd = weight_decay; a.beta1 = beta1; a.beta2 = beta2;
+    a.eps = eps; a.w0 = d_weight0; a.b0 = d_bias0; a.w = d_weight; a.b = d_bias; a.scores = d_scores; a.best = d_best;
+    a.confusion = d_confusion; a.status = d_status;
+    if (const int rc = probe_check(h, a, 3, true, h_info)) return rc;
+    return snapshot_call(h, [&] { return probe_bytes(a); }, [&](void* base, size_t have, size_t need) -> int {
+        if (h->poison >= 0) {   // debug: the result must not depend on what the arena or the result buffers held
+            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
+            if (d_weight != d_weight0) RLAP_HIPCHK(hipMemsetAsync(d_weight, h->poison, (size_t)(R * C * F) * 4, h->stream));
+            if (d_bias != d_bias0) RLAP_HIPCHK(hipMemsetAsync(d_bias, h->poison, (size_t)(R * C) * 4, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_scores, h->poison, (size_t)(R * 4) * 8, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_best, h->poison, (size_t)(R * 2) * 8, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_confusion, h->poison, (size_t)(R * 2 * C * C) * 8, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_status, h->poison, 4, h->stream));
+        }
+        int64_t parts = 0, launches = 0;
+        const int rc = probe_run(h->stream, base, have, a, &parts, &launches);
+        if (h_info) { h_info->arena_bytes = (int64_t)need; h_info->parts = parts; h_info->launches = launches; }
+        return rc;
+    });
+}
+
+int rlap_probe_scores(rlap_handle h, const float* d_x, int64_t N, int64_t F, int64_t ldx, const int64_t* d_y, int64_t C, int64_t R,
+                      const int64_t* d_index, const int64_t* h_ptr, const float* d_weight, const float* d_bias, int64_t* d_pred,
+                      int64_t* d_confusion, double* d_scores, int32_t* d_status, rlap_probe_info* h_info) {
+    ProbeArgs a{};
+    a.x = d_x; a.N = N; a.F = F; a.ldx = ldx; a.y = d_y; a.C = C; a.R = R; a.idx[0] = d_index; a.hptr[0] = h_ptr;
+    a.w0 = d_weight; a.b0 = d_bias; a.pred = d_pred; a.confusion = d_confusion; a.scores = d_scores; a.status = d_status;
+    if (const int rc = probe_check(h, a, 1, false, h_info)) return rc;
+    return snapshot_call(h, [&] { return scores_bytes(a); }, [&](void* base, size_t have, size_t need) -> int {
+        if (h->poison >= 0) {
+            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_pred, h->poison, (size_t)h_ptr[R] * 8, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_confusion, h->poison, (size_t)(R * C * C) * 8, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_scores, h->poison, (size_t)(R * 3) * 8, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_status, h->poison, 4, h->stream));
+        }
+        int64_t launches = 0;
+        const int rc = scores_run(h->stream, base, have, a, &launches);
+        if (h_info) { h_info->arena_bytes = (int64_t)need; h_info->parts = 1; h_info->launches = launches; }
+        return rc;
+    });
 }
 
 int rlap_debug_set_limits(rlap_handle h, double pool_factor, double log_factor, int64_t rng_len, int64_t scratch_entries) {

@@ -1623,6 +1623,211 @@ def g2l_bootstrap(h: Tensor, g: Tensor, node_ptr: Union[Tensor, Sequence[int], G
 PLAN_DIRECTIONS = {"forward": _lib.PLAN_FORWARD, "transposed": _lib.PLAN_TRANSPOSED, "both": _lib.PLAN_FORWARD | _lib.PLAN_TRANSPOSED}
 
 
+PROBE_MAX_F, PROBE_MAX_C, PROBE_MAX_RUNS = 512, 64, 32
+PROBE_SELECT = {"scripts": _lib.PROBE_SELECT_SCRIPTS, "cca": _lib.PROBE_SELECT_CCA}
+
+
+def _probe_lists(arg, what: str) -> Tuple[Tensor, list]:
+    """The runs' index lists of linear_probe / probe_scores as (concatenated int64 indices, the [R+1] offsets as Python ints), from
+    an index tensor (one run), a list of index tensors (ragged) or a tuple (indices, ptr) whose ptr lives on the host."""
+    if isinstance(arg, tuple):
+        if len(arg) != 2:
+            raise ValueError(f"{what}: an index tensor, a list of index tensors or a tuple (indices, ptr)")
+        flat, ptr = arg
+        if isinstance(ptr, Tensor):
+            if ptr.is_cuda:
+                raise ValueError(f"{what}: ptr on the host (a CPU tensor or a sequence of ints); reading it from the device would synchronise")
+            ptr = ptr.tolist()
+        ptr = [int(p) for p in ptr]
+        if not isinstance(flat, Tensor) or flat.dim() != 1 or flat.dtype != torch.int64:
+            raise ValueError(f"{what}: indices as a 1-D torch.int64 tensor")
+        if len(ptr) < 2 or ptr[0] != 0 or ptr[-1] != flat.numel():
+            raise ValueError(f"{what}: ptr runs from 0 to the number of indices")
+    else:
+        lists = [arg] if isinstance(arg, Tensor) else list(arg) if isinstance(arg, (list,)) else None
+        if not lists:
+            raise ValueError(f"{what}: an index tensor, a list of index tensors or a tuple (indices, ptr)")
+        for t in lists:
+            if not isinstance(t, Tensor) or t.dim() != 1 or t.dtype != torch.int64:
+                raise ValueError(f"{what}: every index list a 1-D torch.int64 tensor")
+        ptr = [0]
+        for t in lists:
+            ptr.append(ptr[-1] + int(t.numel()))
+        flat = lists[0] if len(lists) == 1 else torch.cat([t.to(lists[0].device) for t in lists])
+    if any(b <= a for a, b in zip(ptr[:-1], ptr[1:])):
+        raise ValueError(f"{what}: every set of every run must be non-empty")
+    return flat, ptr
+
+
+def _probe_inputs(x, y, num_classes):
+    """Host-side checks of x, y and the class count; C from y.max() when it is not given (the one host read before the call)."""
+    if not isinstance(x, Tensor) or x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError("x: a (N, F) torch.float32 tensor")
+    if not isinstance(y, Tensor) or y.dim() != 1 or y.dtype != torch.int64 or y.shape[0] != x.shape[0]:
+        raise ValueError("y: a (N,) torch.int64 tensor, one label per row of x")
+    n, f = int(x.shape[0]), int(x.shape[1])
+    if n < 1 or n >= 1 << 31:
+        raise ValueError("x: between 1 and 2^31 - 1 rows")
+    if not 1 <= f <= PROBE_MAX_F:
+        raise ValueError(f"x: between 1 and {PROBE_MAX_F} feature columns, got {f}")
+    c = int(y.max()) + 1 if num_classes is None else int(num_classes)
+    if not 2 <= c <= PROBE_MAX_C:
+        raise ValueError(f"num_classes: between 2 and {PROBE_MAX_C}, got {c}")
+    return n, f, c
+
+
+def _probe_x(x: Tensor, dev) -> Tuple[Tensor, int]:
+    """x on the library's device and its row stride: a view with unit column stride and rows at least F apart is read in place,
+    anything else is copied."""
+    d_x = x.detach().to(device=dev)
+    n, f = int(d_x.shape[0]), int(d_x.shape[1])
+    unit = f == 1 or d_x.stride(1) == 1
+    if not unit or (n > 1 and d_x.stride(0) < f):
+        d_x = d_x.contiguous()
+    return d_x, (int(d_x.stride(0)) if n > 1 else f)
+
+
+def _probe_call(export: str, dev, args):
+    """One rlap_linear_probe / rlap_probe_scores call on the library's device: the arguments behind the handle."""
+    global last_stats
+    lib, hobj = _handle_obj(dev)
+    fn = getattr(lib, export)
+    info = _lib.ProbeInfo()
+    st = _lib.Stats()
+    rc = _run(hobj, dev, 0, None, 1, False, lambda: fn(hobj.ptr, *args, ctypes.byref(info)), st)
+    if rc in (1, 2, 3):
+        raise ValueError(f"rlap: {_lib.status_string(rc)} (detail {info.detail})")
+    if rc != 0:
+        _raise(rc)
+    last_stats = info.as_dict()
+
+
+def probe_init(num_runs: int, num_classes: int, num_features: int, generator=None) -> Tuple[Tensor, Tensor]:
+    """The initial parameters of `num_runs` probes as the reference draws them (scripts/node_shared.py:152-156), on the host:
+    nn.Linear's default draws (a weight that is thrown away, the bias in U(-1/sqrt(F), 1/sqrt(F))) and then xavier_uniform_ for the
+    weight, U(-a, a) with a = sqrt(6 / (F + C)) -- in that order, so a generator seeded as the reference's yields its values.
+    Returns ((R, C, F), (R, C)) float32."""
+    r, c, f = int(num_runs), int(num_classes), int(num_features)
+    w = torch.empty((r, c, f), dtype=torch.float32)
+    b = torch.empty((r, c), dtype=torch.float32)
+    kb = 1.0 / f ** 0.5
+    xa = (6.0 / (f + c)) ** 0.5
+    for k in range(r):
+        w[k].uniform_(-kb, kb, generator=generator)
+        b[k].uniform_(-kb, kb, generator=generator)
+        w[k].uniform_(-xa, xa, generator=generator)
+    return w, b
+
+
+def _i64_array(values):
+    return (ctypes.c_int64 * len(values))(*values)
+
+
+def linear_probe(x: Tensor, y: Tensor, train, valid, test, num_classes: Optional[int] = None, epochs: int = 2000, lr: float = 0.01,
+                 weight_decay: float = 0.0, test_interval: int = 20, select: str = "scripts", weight: Optional[Tensor] = None,
+                 bias: Optional[Tensor] = None, generator=None, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8) -> dict:
+    """R linear probes in one call on the device (rlap_linear_probe): LREvaluator's loop of the reference's scripts
+    (scripts/node_shared.py:163-230; select="scripts") or CCA-SSG/main.py:152-194's (select="cca") -- full-batch Adam on a
+    Linear(F, C) under log-softmax + NLL, scored on a validation and a test set, the selection rule applied on the device.
+
+      x            : (N, F) float32, 1 <= F <= 512; detached, never differentiated.  A view with unit column stride is read in place.
+      y            : (N,) int64 labels in [0, C); C = num_classes, or y.max() + 1 (the one host read before the call); 2 <= C <= 64
+      train, valid, test : the rows of the R runs: an int64 index tensor (R = 1), a list of R index tensors (ragged), or a tuple
+                     (indices, ptr) with ptr on the host.  Any order, a repeated row counts twice, sums run in list order; no set empty.
+      weight, bias : (R, C, F), (R, C) float32 initial parameters; None draws them with `generator` as the reference does (probe_init)
+      select       : "scripts": after every epoch e with (e + 1) % test_interval == 0, when val_micro > best_val_micro record the test
+                     micro-F1, macro-F1, accuracy and e.  "cca": after every epoch, if val_acc >= best_val: best_val = val_acc, and if
+                     test_acc > eval_acc: record.  Both compare integer counts of correct rows.
+    Returns a dict of device tensors: micro_f1, macro_f1, accuracy (R,) float64; best_epoch, best_val_correct (R,) int64; weight, bias
+    (the final parameters); loss (R,) float64, the last epoch's training loss; confusion (R, 2, C, C) int64, validation and test at the
+    recorded evaluation, rows true, columns predicted; status, one int32: 0, or 2 / 3 when a kernel met an index outside [0, N) / a
+    label outside [0, C) (reading it synchronises; adapters.LREvaluator does).  No host synchronisation inside the call.  Every
+    value and the order of every sum are fixed (rlap_amd/csrc/rlap_probe.h): the same arguments give the same bits.
+    """
+    n, f, c = _probe_inputs(x, y, num_classes)
+    lists = [_probe_lists(a, what) for a, what in ((train, "train"), (valid, "valid"), (test, "test"))]
+    r = len(lists[0][1]) - 1
+    if any(len(p) - 1 != r for _, p in lists):
+        raise ValueError("train, valid, test: the same number of runs")
+    if r > PROBE_MAX_RUNS:
+        raise ValueError(f"at most {PROBE_MAX_RUNS} runs a call, got {r}")
+    if select not in PROBE_SELECT:
+        raise ValueError(f"select: one of {sorted(PROBE_SELECT)}, got {select!r}")
+    epochs, test_interval = int(epochs), int(test_interval)
+    if epochs < 1 or test_interval < 1:
+        raise ValueError("epochs and test_interval: at least 1")
+    lr, weight_decay, eps = float(lr), float(weight_decay), float(eps)
+    b1, b2 = float(betas[0]), float(betas[1])
+    if not (abs(lr) < float("inf")):
+        raise ValueError(f"lr: finite, got {lr!r}")
+    if not (0.0 <= weight_decay < float("inf")) or not (0.0 <= b1 < 1.0) or not (0.0 <= b2 < 1.0) or not (0.0 < eps < float("inf")):
+        raise ValueError("weight_decay >= 0, betas in [0, 1), eps > 0")
+    if (weight is None) != (bias is None):
+        raise ValueError("weight and bias: both or neither")
+    if weight is None:
+        weight, bias = probe_init(r, c, f, generator)
+    if not isinstance(weight, Tensor) or weight.dtype != torch.float32 or tuple(weight.shape) != (r, c, f):
+        raise ValueError(f"weight: a ({r}, {c}, {f}) torch.float32 tensor")
+    if not isinstance(bias, Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (r, c):
+        raise ValueError(f"bias: a ({r}, {c}) torch.float32 tensor")
+    dev = _device_for(x)
+    with torch.cuda.device(dev):
+        d_x, ldx = _probe_x(x, dev)
+        d_y = y.to(device=dev).contiguous()
+        d_l = [flat.to(device=dev).contiguous() for flat, _ in lists]
+        h_p = [_i64_array(p) for _, p in lists]
+        w0 = weight.detach().to(device=dev).contiguous()
+        b0 = bias.detach().to(device=dev).contiguous()
+        w, b = torch.empty_like(w0), torch.empty_like(b0)
+        scores = torch.empty((r, 4), dtype=torch.float64, device=dev)
+        best = torch.empty((r, 2), dtype=torch.int64, device=dev)
+        conf = torch.empty((r, 2, c, c), dtype=torch.int64, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        _probe_call("rlap_linear_probe", dev, (
+            d_x.data_ptr(), n, f, ldx, d_y.data_ptr(), c, r, d_l[0].data_ptr(), h_p[0], d_l[1].data_ptr(), h_p[1], d_l[2].data_ptr(), h_p[2],
+            epochs, lr, weight_decay, test_interval, PROBE_SELECT[select], b1, b2, eps, w0.data_ptr(), b0.data_ptr(), w.data_ptr(),
+            b.data_ptr(), scores.data_ptr(), best.data_ptr(), conf.data_ptr(), status.data_ptr()))
+    return {"micro_f1": scores[:, 0], "macro_f1": scores[:, 1], "accuracy": scores[:, 2], "loss": scores[:, 3], "best_epoch": best[:, 0],
+            "best_val_correct": best[:, 1], "weight": w, "bias": b, "confusion": conf, "status": status}
+
+
+def probe_scores(x: Tensor, y: Tensor, index, weight: Tensor, bias: Tensor) -> dict:
+    """The scoring pass of linear_probe alone (rlap_probe_scores): the predictions of R probes on their index lists and sklearn's
+    scores of them.  `index` has the forms of linear_probe's sets; weight (R, C, F) and bias (R, C) float32 (or (C, F), (C,) for one
+    run); C is weight's.  Returns a dict of device tensors: pred (int64, one per listed row, the lowest index among the largest
+    logits), confusion (R, C, C) int64 (rows true, columns predicted), micro_f1, macro_f1, accuracy (R,) float64, status.
+    macro_f1 is the plain mean of 2 tp / (2 tp + fp + fn) over the labels that occur among the true or the predicted labels.
+    No host synchronisation."""
+    if isinstance(weight, Tensor) and weight.dim() == 2 and isinstance(bias, Tensor) and bias.dim() == 1:
+        weight, bias = weight[None], bias[None]
+    if not isinstance(weight, Tensor) or weight.dim() != 3 or weight.dtype != torch.float32:
+        raise ValueError("weight: a (R, C, F) torch.float32 tensor")
+    n, f, c = _probe_inputs(x, y, int(weight.shape[1]))
+    flat, ptr = _probe_lists(index, "index")
+    r = len(ptr) - 1
+    if r > PROBE_MAX_RUNS:
+        raise ValueError(f"at most {PROBE_MAX_RUNS} runs a call, got {r}")
+    if tuple(weight.shape) != (r, c, f):
+        raise ValueError(f"weight: a ({r}, {c}, {f}) torch.float32 tensor")
+    if not isinstance(bias, Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (r, c):
+        raise ValueError(f"bias: a ({r}, {c}) torch.float32 tensor")
+    dev = _device_for(x)
+    with torch.cuda.device(dev):
+        d_x, ldx = _probe_x(x, dev)
+        d_y = y.to(device=dev).contiguous()
+        d_i = flat.to(device=dev).contiguous()
+        h_p = _i64_array(ptr)
+        d_w = weight.detach().to(device=dev).contiguous()
+        d_b = bias.detach().to(device=dev).contiguous()
+        pred = torch.empty(ptr[-1], dtype=torch.int64, device=dev)
+        conf = torch.empty((r, c, c), dtype=torch.int64, device=dev)
+        scores = torch.empty((r, 3), dtype=torch.float64, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        _probe_call("rlap_probe_scores", dev, (d_x.data_ptr(), n, f, ldx, d_y.data_ptr(), c, r, d_i.data_ptr(), h_p, d_w.data_ptr(),
+                                               d_b.data_ptr(), pred.data_ptr(), conf.data_ptr(), scores.data_ptr(), status.data_ptr()))
+    return {"pred": pred, "confusion": conf, "micro_f1": scores[:, 0], "macro_f1": scores[:, 1], "accuracy": scores[:, 2], "status": status}
+
+
 def _plan_call(plan, flags: int, d_x: Tensor, F: int, y: Tensor):
     """One rlap_snapshot_plan_propagate call on the plan's device: the arena is sized by the call itself (RLAP_E_WORKSPACE and one
     regrow), statuses become exceptions as in _snapshot_call, `last_stats` is set on success."""
