@@ -67,7 +67,21 @@ RLAP_SPMM_HD bool tile_stored(int I, int J, int a, int b, int nft) {
     return tk < nft && tl < nft && tk <= tl;
 }
 
-// The parts of the rows: a function of (N, F) alone.  As many as bring a view's pair groups up to TARGET_GROUPS workgroups, at most
+// Which instances the launchers of rlap_cca.hip take for nft = feature_tiles(F); 0 for an nft outside [1, MAX_F / TILE], which no
+// launcher accepts.
+//   k_cca_gram<NV>   a thread stages nft float4s of a 32-row step and guards each with j < nft: the smallest NV of 1, 2, 4, 8, 16
+//                    that holds nft.
+//   k_cca_zr<NCT>    wave w owns the column tiles w, w + 4, ..., guarded with w + 4 j < nft: NCT = ceil(nft / 4), 1 to 4.
+RLAP_SPMM_HD int gram_instance(int nft) {
+    if (nft < 1 || nft > MAX_F / TILE) return 0;
+    return nft <= 1 ? 1 : (nft <= 2 ? 2 : (nft <= 4 ? 4 : (nft <= 8 ? 8 : 16)));
+}
+RLAP_SPMM_HD int zr_instance(int nft) {
+    if (nft < 1 || nft > MAX_F / TILE) return 0;
+    return (nft + 3) / 4;   // (four waves a workgroup)
+}
+
+// The parts of the rows: a function of (N, F) alone. As many as bring a view's pair groups up to TARGET_GROUPS workgroups, at most
 // one per 32-row tile and at most MAX_PARTS.
 RLAP_SPMM_HD int64_t num_parts(int64_t N, int64_t F) {
     const int64_t T = num_tiles(N), G = pair_groups(F);

@@ -425,6 +425,28 @@ int launch_zr(hipStream_t st, const ZR& a) {
     return RLAP_OK;
 }
 
+// the instances by the header's rules; no instance (F outside [1, MAX_F], which the entry point refuses) is an error
+int launch_gram_of(hipStream_t st, const Gram& m) {
+    switch (cca::gram_instance(m.nft)) {
+        case 1: return launch_gram<1>(st, m);
+        case 2: return launch_gram<2>(st, m);
+        case 4: return launch_gram<4>(st, m);
+        case 8: return launch_gram<8>(st, m);
+        case 16: return launch_gram<16>(st, m);
+    }
+    return RLAP_E_INTERNAL;
+}
+
+int launch_zr_of(hipStream_t st, const ZR& a) {
+    switch (cca::zr_instance(a.nft)) {
+        case 1: return launch_zr<1>(st, a);
+        case 2: return launch_zr<2>(st, a);
+        case 3: return launch_zr<3>(st, a);
+        case 4: return launch_zr<4>(st, a);
+    }
+    return RLAP_E_INTERNAL;
+}
+
 }  // namespace
 
 size_t cca_bytes(int64_t N, int64_t F) {
@@ -457,8 +479,7 @@ int cca_run(hipStream_t st, void* ws, size_t ws_bytes, const CcaArgs& g) {
     m.z[0] = B.z0; m.z[1] = B.z1; m.N = g.N; m.F = F; m.Fp = cca::padded_features(g.F); m.nft = cca::feature_tiles(g.F);
     m.nst = cca::super_tiles(g.F); m.npairs = cca::super_pairs(g.F); m.groups = cca::pair_groups(g.F);
     m.parts = (int)cca::num_parts(g.N, g.F); m.partial = B.partial;
-    if (const int rc = m.nft <= 1 ? launch_gram<1>(st, m) : m.nft <= 2 ? launch_gram<2>(st, m) : m.nft <= 4 ? launch_gram<4>(st, m)
-                       : m.nft <= 8 ? launch_gram<8>(st, m) : launch_gram<16>(st, m)) return rc;
+    if (const int rc = launch_gram_of(st, m)) return rc;
     hipLaunchKernelGGL(k_cca_resid, dim3(cc_blocks(2 * (int64_t)F * F, 256)), dim3(256), 0, st, (const float*)B.partial, m.parts, g.N, F, m.Fp, B.R, g.gram);
     hipLaunchKernelGGL(k_cca_decchunks, dim3(cc_blocks(2 * spmm::num_chunks((int64_t)F * F), 256)), dim3(256), 0, st, (const double*)B.R, F, B.dcs);
     hipLaunchKernelGGL(k_cca_terms, dim3(1), dim3(256), 0, st, (const double*)B.dcs, (const double*)B.d, g.N, F, g.lambd, g.terms);
@@ -477,8 +498,7 @@ int cca_backward_run(hipStream_t st, void* ws, size_t ws_bytes, const CcaArgs& g
     a.P[0] = B.P0; a.P[1] = B.P1;
     hipLaunchKernelGGL(k_cca_rpad, dim3(cc_blocks(2 * (int64_t)a.Fp * a.Fp, 256)), dim3(256), 0, st, g.gram_in, F, a.Fp, B.rp);
     RLAP_HIPCHK(hipGetLastError());
-    const int nct = (a.nft + 3) / 4;
-    if (const int rc = nct <= 1 ? launch_zr<1>(st, a) : nct == 2 ? launch_zr<2>(st, a) : nct == 3 ? launch_zr<3>(st, a) : launch_zr<4>(st, a)) return rc;
+    if (const int rc = launch_zr_of(st, a)) return rc;
     Col c = col_args(g, B, g.colstat_in);
     c.out = B.m;
     if (const int rc = col_sums<CS_M>(st, c)) return rc;

@@ -423,11 +423,14 @@ int launch_main_t(hipStream_t st, const Main& m) {
 
 template <int MODE>
 int launch_backward_main(hipStream_t st, const Main& m) {
-    if (m.nft <= 1) return launch_main_t<1, MODE>(st, m);
-    if (m.nft <= 2) return launch_main_t<2, MODE>(st, m);
-    if (m.nft <= 4) return launch_main_t<4, MODE>(st, m);
-    if (m.nft <= 8) return launch_main_t<8, MODE>(st, m);
-    return launch_main_t<16, MODE>(st, m);
+    switch (infonce::main_instance(m.nft)) {   // the rule is rlap_infonce.h's
+        case 1: return launch_main_t<1, MODE>(st, m);
+        case 2: return launch_main_t<2, MODE>(st, m);
+        case 4: return launch_main_t<4, MODE>(st, m);
+        case 8: return launch_main_t<8, MODE>(st, m);
+        case 16: return launch_main_t<16, MODE>(st, m);
+    }
+    return RLAP_E_INTERNAL;   // (no instance: F outside [1, MAX_F], which the entry point refuses)
 }
 
 template <int MODE>

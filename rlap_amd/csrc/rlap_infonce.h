@@ -54,6 +54,16 @@ RLAP_SPMM_HD int64_t num_tiles(int64_t N) { return N > 0 ? (N + TILE - 1) / TILE
 RLAP_SPMM_HD int64_t row_blocks(int64_t N) { return (num_tiles(N) + BLOCK_TILES - 1) / BLOCK_TILES; }
 RLAP_SPMM_HD int64_t padded_rows(int64_t N) { return num_tiles(N) * TILE; }
 RLAP_SPMM_HD int padded_features(int64_t F) { return (int)((F + TILE - 1) / TILE) * TILE; }
+RLAP_SPMM_HD int feature_tiles(int64_t F) { return padded_features(F) / TILE; }
+
+// Which instance of a backward main kernel a call of nft = feature_tiles(F) takes (launch_backward_main of rlap_infonce.hip and of
+// rlap_g2l.hip): k_in_main<NFT, .> and k_g2l_main<NFT, .> hold NFT accumulator tiles a wave and guard each with ft < nft, so the
+// instance is the smallest of 1, 2, 4, 8, 16 that holds nft.  The launchers instantiate exactly these five; 0 for an nft outside
+// [1, MAX_F / TILE], which no launcher accepts.
+RLAP_SPMM_HD int main_instance(int nft) {
+    if (nft < 1 || nft > MAX_F / TILE) return 0;
+    return nft <= 1 ? 1 : (nft <= 2 ? 2 : (nft <= 4 ? 4 : (nft <= 8 ? 8 : 16)));
+}
 
 // The parts of the stream tiles: a function of N alone.  As many as bring the row blocks up to TARGET_GROUPS workgroups, at most
 // one per tile.

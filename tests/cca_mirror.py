@@ -29,6 +29,12 @@ def build(directory):
     lib.cca_pair_groups.argtypes = [i64]
     lib.cca_lambd_ok.restype = ci
     lib.cca_lambd_ok.argtypes = [dbl]
+    for name in ("cca_feature_tiles", "cca_super_pairs"):
+        getattr(lib, name).restype = ci
+        getattr(lib, name).argtypes = [i64]
+    for name in ("cca_gram_instance", "cca_zr_instance"):
+        getattr(lib, name).restype = ci
+        getattr(lib, name).argtypes = [ci]
     lib.cca_mirror.restype = ci
     lib.cca_mirror.argtypes = [vp, vp, i64, i64, dbl, i64, ci, ci, dbl, vp, vp, vp, vp, vp]
     return lib

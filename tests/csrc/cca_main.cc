@@ -3,6 +3,7 @@
 // {1, 31, 32, 33, 100, 512} it walks the parts, the workgroup map of the Gram kernel (block -> view, part, group; wave -> super-tile
 // pair -> tiles), the workgroup map of the backward product, the padded sizes and the finish through arrays of exactly the sizes the
 // library carves, so that an index out of range is an error of the sanitizer and a cell visited twice or never one of the program.
+// For every F from 1 to 512: the super-tile pairs, the tiles their waves store, and the instances the launchers choose.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -42,6 +43,44 @@ static void check_pairs(int64_t F) {
     }
     for (int I = 0; I < nst; ++I)
         for (int J = 0; J < nst; ++J) CHECK(seen[(size_t)(I * nst + J)] == (I <= J ? 1 : 0), "super pair (%d, %d) of %lld", I, J, (long long)F);
+    // the tiles the waves store, over all pairs: inside the image, in the upper triangle, each exactly once -- a clamped tile (odd
+    // nft: the second tile of the last super tile) is computed and not stored; the operands of every tile, stored or not, are inside
+    std::vector<int> tiles((size_t)(nft * nft), 0);
+    for (int q = 0; q < np; ++q) {
+        int I = 0, J = 0;
+        cca::pair_of(q, nst, &I, &J);
+        for (int a = 0; a < 2; ++a)
+            for (int b = 0; b < 2; ++b) {
+                const int tk = cca::tile_of(I, a, nft), tl = cca::tile_of(J, b, nft);
+                CHECK(tk >= 0 && tk < nft && tl >= 0 && tl < nft, "operand tiles (%d, %d) of %lld", tk, tl, (long long)F);
+                if (!cca::tile_stored(I, J, a, b, nft)) continue;
+                CHECK(tk == 2 * I + a && tl == 2 * J + b, "a stored tile of %lld is a clamped one", (long long)F);
+                CHECK(tk <= tl, "stored tile (%d, %d) of %lld is below the diagonal", tk, tl, (long long)F);
+                if (tk >= 0 && tk < nft && tl >= 0 && tl < nft) ++tiles[(size_t)(tk * nft + tl)];
+            }
+    }
+    for (int tk = 0; tk < nft; ++tk)
+        for (int tl = 0; tl < nft; ++tl)
+            CHECK(tiles[(size_t)(tk * nft + tl)] == (tk <= tl ? 1 : 0), "tile (%d, %d) of %lld stored %d times", tk, tl, (long long)F, tiles[(size_t)(tk * nft + tl)]);
+    // the rules of the launchers: instances they have, the smallest that hold nft; what a thread or wave of the instance indexes
+    // (j < NV float4s; wave + 4 j, j < NCT column tiles) covers the live ones and stays inside its array
+    const int nv = cca::gram_instance(nft), nct = cca::zr_instance(nft);
+    const bool nv_known = nv == 1 || nv == 2 || nv == 4 || nv == 8 || nv == 16;
+    CHECK(nv_known && nv >= nft && (nv == 1 || nv / 2 < nft), "Gram instance %d of %lld (%d tiles)", nv, (long long)F, nft);
+    CHECK(nct >= 1 && nct <= 4 && 4 * nct >= nft && 4 * (nct - 1) < nft, "zr instance %d of %lld (%d tiles)", nct, (long long)F, nft);
+    if (nv_known && nv >= nft && nct >= 1 && nct <= 4) {
+        std::vector<int> pre((size_t)nv, 0), pre_zr((size_t)(4 * nct), 0), col((size_t)nft, 0);
+        for (int j = 0; j < nv; ++j)
+            if (j < nft) ++pre[(size_t)j];
+        for (int j = 0; j < 4 * nct; ++j)
+            if (j < nft) ++pre_zr[(size_t)j];
+        for (int wave = 0; wave < 4; ++wave)
+            for (int j = 0; j < nct; ++j)
+                if (wave + 4 * j < nft) ++col[(size_t)(wave + 4 * j)];
+        for (int j = 0; j < nft; ++j)
+            CHECK(pre[(size_t)j] == 1 && pre_zr[(size_t)j] == 1 && col[(size_t)j] == 1, "tile %d of %lld: staged %d and %d times, owned %d times", j,
+                  (long long)F, pre[(size_t)j], pre_zr[(size_t)j], col[(size_t)j]);
+    }
 }
 
 static void check_nf(int64_t N, int64_t F, bool elements) {
@@ -159,6 +198,7 @@ int main(int argc, char** argv) {
             for (int64_t p = 0; p < P; ++p)
                 CHECK(cca::part_begin(N, F, p) < cca::part_begin(N, F, p + 1) && cca::part_begin(N, F, p) % 32 == 0, "part %lld of %lld", (long long)p, (long long)N);
         }
+    CHECK(cca::gram_instance(0) == 0 && cca::gram_instance(17) == 0 && cca::zr_instance(0) == 0 && cca::zr_instance(17) == 0, "no instance outside 1 .. 16 tiles");
     CHECK(cca::lambd_ok(0.0) && cca::lambd_ok(1e-3) && cca::lambd_ok(1e300), "lambd inside");
     CHECK(!cca::lambd_ok(-1e-9) && !cca::lambd_ok((double)NAN) && !cca::lambd_ok((double)INFINITY), "lambd outside");
     std::printf("%lld sizes, %lld failures\n", (long long)bound, (long long)failures);

@@ -68,6 +68,11 @@ int64_t cca_parts(int64_t N, int64_t F) { return cca::num_parts(N, F); }
 int64_t cca_part_begin(int64_t N, int64_t F, int64_t p) { return cca::part_begin(N, F, p); }
 int64_t cca_pair_groups(int64_t F) { return cca::pair_groups(F); }
 int cca_lambd_ok(double l) { return cca::lambd_ok(l) ? 1 : 0; }
+// the rules both launchers call, for the regime accounting of tests/test_gpu_loss_regimes.py
+int cca_feature_tiles(int64_t F) { return cca::feature_tiles(F); }
+int cca_super_pairs(int64_t F) { return cca::super_pairs(F); }
+int cca_gram_instance(int nft) { return cca::gram_instance(nft); }
+int cca_zr_instance(int nft) { return cca::zr_instance(nft); }
 
 // terms [4], colstat [4 F], gram [2 F F]; ga, gb (N, F) when ga != nullptr (with the upstream gradient g).  Returns 0, or 1 for
 // arguments the library refuses.

@@ -2,7 +2,8 @@
 // -fsanitize=address,undefined by tests/test_g2l_cpu.py: for every N up to the bound given on the command line and G in
 // {1, 2, 31, 32, 33, 65, N, N + 3} it walks the node tiles, the graph tiles and the parts, the node -> graph map over tables with
 // empty graphs at the front, in the middle and at the end, the register-to-row map, the workgroup maps of the three main kernels
-// and the row blocks of the vector kernels, and the arena carve-up through arrays of exactly the carved sizes, so that an index out
+// and the row blocks of the vector kernels (for every F from 1 to 512: the instance of the backward kernels that the launchers
+// choose and the rows of a vector block), and the arena carve-up through arrays of exactly the carved sizes, so that an index out
 // of range is an error of the sanitizer and a cell visited twice or never one of the program.
 #include <cstdint>
 #include <cstdio>
@@ -247,9 +248,36 @@ static void check_ng(int64_t N, int64_t G) {
     for (int call = 0; call < 4; ++call) check_arena(call, N, G, F);
 }
 
+// the rule of launch_backward_main (rlap_infonce.h's, which both backward kernels of the JSD take) and the rows of a block of the
+// vector kernels, for every F the exports accept
+static void check_instances() {
+    int rows_prev = g2l::VEC_THREADS;
+    for (int64_t F = 1; F <= g2l::MAX_F; ++F) {
+        const int nft = g2l::padded_features(F) / g2l::TILE, inst = infonce::main_instance(nft);
+        const bool known = inst == 1 || inst == 2 || inst == 4 || inst == 8 || inst == 16;
+        CHECK(known, "instance %d of F = %lld is not one the launchers have", inst, LL(F));
+        CHECK(inst >= nft && (inst == 1 || inst / 2 < nft), "instance %d of F = %lld (%d tiles)", inst, LL(F), nft);
+        if (known && inst >= nft) {
+            std::vector<int> acc((size_t)inst, 0);                       // f32x16 acc[NFT]
+            for (int ft = 0; ft < inst; ++ft)
+                if (ft < nft) ++acc[(size_t)ft];
+            for (int ft = 0; ft < nft; ++ft) CHECK(acc[(size_t)ft] == 1, "tile %d of F = %lld", ft, LL(F));
+        }
+        const int R = g2l::vec_rows(F);
+        CHECK((R == 32 || R == 64 || R == 128 || R == 256) && R <= rows_prev, "rows of a block at F = %lld: %d after %d", LL(F), R, rows_prev);
+        CHECK(R == 32 || (int64_t)R * g2l::vec_stride(F) * 4 <= g2l::VEC_LDS_BYTES, "LDS of a block at F = %lld", LL(F));
+        CHECK(R == g2l::VEC_THREADS || (int64_t)2 * R * g2l::vec_stride(F) * 4 > g2l::VEC_LDS_BYTES, "a block at F = %lld could hold twice its rows", LL(F));
+        rows_prev = R;
+    }
+    CHECK(g2l::vec_rows(65) == 256 && g2l::vec_rows(66) == 128 && g2l::vec_rows(131) == 128 && g2l::vec_rows(132) == 64 &&
+          g2l::vec_rows(263) == 64 && g2l::vec_rows(264) == 32 && g2l::vec_rows(512) == 32, "the edges of vec_rows");
+}
+
 int main(int argc, char** argv) {
     const int64_t bound = argc > 1 ? std::atoll(argv[1]) : 300;
     check_reg_rows();
+    check_instances();
+    for (int64_t F : {65, 66, 131, 132, 263, 264}) check_vec(513, F);   // a last block of one row on either side of every edge
     for (int64_t N = 1; N <= bound; ++N) {
         const int64_t gs[] = {1, 2, 31, 32, 33, 65, N, N + 3};
         for (int64_t G : gs) check_ng(N, G);

@@ -45,6 +45,11 @@ int64_t g2l_part_begin(int64_t N, int64_t G, int64_t F, int64_t p) { return g2l:
 int64_t g2l_arena_bytes(int call, int64_t N, int64_t G, int64_t F) { return g2l::arena(call, N, G, F).bytes; }
 int64_t g2l_graph_of(const int64_t* node_ptr, int64_t G, int64_t N, int64_t i) { return g2l::graph_of(node_ptr, G, N, i); }
 int64_t g2l_num_neg(int64_t N, int64_t G) { return g2l::num_neg(N, G); }
+// the rules the launchers call, for the regime accounting of tests/test_gpu_loss_regimes.py
+int g2l_feature_tiles(int64_t F) { return infonce::feature_tiles(F); }
+int g2l_main_instance(int nft) { return infonce::main_instance(nft); }
+int g2l_vec_rows(int64_t F) { return g2l::vec_rows(F); }
+int64_t g2l_vec_blocks(int64_t N, int64_t F) { return g2l::vec_blocks(N, F); }
 
 // rows [2 N] (pos_i, then neg_i), loss [1]; with grad != 0 and the upstream gradient gup: gh (N, F), gneg (N, F) when neg is given,
 // gg (G, F).  Returns 0, or 1 for arguments the library refuses.

@@ -1,6 +1,7 @@
 // The index arithmetic of the fused InfoNCE loss (rlap_amd/csrc/rlap_infonce.h) as a stand-alone program, built with
 // -fsanitize=address,undefined by tests/test_infonce_cpu.py: for every N up to the bound given on the command line it walks the parts,
-// the tiles, the register-to-row map, the workgroup map of the main kernels, the fragment image and the chunk finish through arrays
+// the tiles, the register-to-row map, the workgroup map of the main kernels, the fragment image and the chunk finish (and, for every
+// F from 1 to 512, the instance of the backward kernels that the launchers choose) through arrays
 // of exactly the sizes the library carves, so that an index out of range is an error of the sanitizer and a cell visited twice or
 // never one of the program.
 #include <cstdint>
@@ -97,9 +98,33 @@ static void check_frag(int64_t N, int64_t F) {
     for (size_t e = 0; e < cell.size(); ++e) CHECK(cell[e] == 1, "fragment cell %zu of (%lld, %lld) written %d times", e, (long long)N, (long long)F, cell[e]);
 }
 
+// the rule of launch_backward_main for every F the exports accept: an instance the launchers have, the smallest that holds nft; the
+// accumulator tiles a wave of that instance indexes (ft < NFT) cover the live ones (ft < nft) and stay inside its array
+static void check_instances() {
+    int used[17];
+    std::memset(used, 0, sizeof used);
+    for (int64_t F = 1; F <= infonce::MAX_F; ++F) {
+        const int nft = infonce::feature_tiles(F), inst = infonce::main_instance(nft);
+        CHECK(nft * infonce::TILE == infonce::padded_features(F) && nft >= 1 && nft <= 16, "feature tiles of %lld", (long long)F);
+        const bool known = inst == 1 || inst == 2 || inst == 4 || inst == 8 || inst == 16;
+        CHECK(known, "instance %d of F = %lld is not one the launchers have", inst, (long long)F);
+        CHECK(inst >= nft, "instance %d of F = %lld holds fewer than %d tiles", inst, (long long)F, nft);
+        CHECK(inst == 1 || inst / 2 < nft, "instance %d of F = %lld is not the smallest for %d tiles", inst, (long long)F, nft);
+        if (!known || inst < nft) continue;
+        std::vector<int> acc((size_t)inst, 0);                           // f32x16 acc[NFT]
+        for (int ft = 0; ft < inst; ++ft)
+            if (ft < nft) ++acc[(size_t)ft];
+        for (int ft = 0; ft < nft; ++ft) CHECK(acc[(size_t)ft] == 1, "tile %d of F = %lld", ft, (long long)F);
+        ++used[inst];
+    }
+    CHECK(used[1] == 32 && used[2] == 32 && used[4] == 64 && used[8] == 128 && used[16] == 256, "the instances' shares of F = 1 .. 512");
+    CHECK(infonce::main_instance(0) == 0 && infonce::main_instance(17) == 0 && infonce::main_instance(-1) == 0, "no instance outside 1 .. 16 tiles");
+}
+
 int main(int argc, char** argv) {
     const int64_t bound = argc > 1 ? std::atoll(argv[1]) : 300;
     check_reg_rows();
+    check_instances();
     for (int64_t N = 1; N <= bound; ++N) check_n(N);
     const int64_t fs[] = {1, 2, 3, 31, 32, 33, 100, 256, 512};
     const int64_t ns[] = {1, 31, 32, 33, 65, 129, 300};

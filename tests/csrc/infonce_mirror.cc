@@ -91,6 +91,9 @@ int64_t infonce_parts(int64_t N) { return infonce::num_parts(N); }
 int64_t infonce_part_begin(int64_t N, int64_t p) { return infonce::part_begin(N, p); }
 int infonce_reg_row(int r, int h) { return infonce::reg_row(r, h); }
 int infonce_tau_ok(double tau) { return infonce::tau_ok(tau) ? 1 : 0; }
+// the rule both launch_backward_main call, for the regime accounting of tests/test_gpu_loss_regimes.py
+int infonce_feature_tiles(int64_t F) { return infonce::feature_tiles(F); }
+int infonce_main_instance(int nft) { return infonce::main_instance(nft); }
 
 // Z [N], rows [N], loss [1], sii [N]; ga, gb (N, F) when ga != nullptr (with the upstream gradient g).  Returns 0, or 1 for arguments
 // the library refuses.

@@ -37,6 +37,14 @@ def build(directory):
     lib.g2l_graph_of.argtypes = [vp, i64, i64, i64]
     lib.g2l_num_neg.restype = i64
     lib.g2l_num_neg.argtypes = [i64, i64]
+    lib.g2l_feature_tiles.restype = ci
+    lib.g2l_feature_tiles.argtypes = [i64]
+    lib.g2l_main_instance.restype = ci
+    lib.g2l_main_instance.argtypes = [ci]
+    lib.g2l_vec_rows.restype = ci
+    lib.g2l_vec_rows.argtypes = [i64]
+    lib.g2l_vec_blocks.restype = i64
+    lib.g2l_vec_blocks.argtypes = [i64, i64]
     lib.g2l_jsd_mirror.restype = ci
     lib.g2l_jsd_mirror.argtypes = [vp, vp, vp, i64, i64, vp, i64, i64, ci, dbl, ci, vp, vp, vp, vp, vp]
     lib.g2l_bootstrap_mirror.restype = ci

@@ -32,6 +32,10 @@ def build(directory):
     lib.infonce_reg_row.argtypes = [ci, ci]
     lib.infonce_tau_ok.restype = ci
     lib.infonce_tau_ok.argtypes = [dbl]
+    lib.infonce_feature_tiles.restype = ci
+    lib.infonce_feature_tiles.argtypes = [i64]
+    lib.infonce_main_instance.restype = ci
+    lib.infonce_main_instance.argtypes = [ci]
     lib.infonce_mirror.restype = ci
     lib.infonce_mirror.argtypes = [vp, vp, i64, i64, dbl, ci, i64, ci, dbl, vp, vp, vp, vp, vp, vp]
     return lib

@@ -2,10 +2,12 @@
 (tests/csrc/cca_mirror.cc around rlap_amd/csrc/rlap_cca.h, the header the kernels include).
 
 Shapes: N at the edges of the MFMA's row pair, of the 32-row tile, of the 256-row chunk and of the part split (2, 3, 31, 32, 33, 64,
-65, 255, 257, 300, and 2708 -- Cora's size: 64 parts), F at the edges of the 32-column tile, of the 64-column super tile and of every
-template instance of the backward product (1, 2, 31, 32, 33, 64, 100, 256, 300, 512 -- one to sixteen tiles, one to nine workgroups
-a (view, part)), in a sparse cross product, lambd cycling over 1e-3, 1, 0.  The mirror runs once per shape (a module-wide cache) and
-serves every test.
+65, 255, 257, 300, and 2708 -- Cora's size: 64 parts), F at the edges of the 32-column tile, of the 64-column super tile and of the
+template instances of both products (1, 2, 31, 32, 33, 64, 100, 256, 300, 512 -- 1, 2, 4, 8, 10 and 16 tiles: every instance, all
+but one completely filled; 1, 3, 4 and 9 workgroups a (view, part)), in a sparse cross product, lambd cycling over 1e-3, 1, 0.  The
+mirror runs once per shape (a module-wide cache) and serves every test.  The other tile counts (odd ones, whose clamped Gram tile
+is computed twice and stored once; instances with dead registers; 2, 6 and 7 workgroups; a last workgroup of one or two live waves)
+and the parts capped by the workgroup target are tests/test_gpu_loss_regimes.py's.
 
   forward    colstat, gram and the four terms equal the mirror's bit for bit (every operation is an IEEE float64 or float32 one,
              division and square root included; no neighbour is allowed).

@@ -4,8 +4,11 @@
 Shapes: N at the edges of the 32-node tiles and of the workgroup's 128-node block (1, 31, 32, 33, 65, 300), G on both paths -- one
 graph with the corrupted embeddings (the vector kernels), and 2, 31, 33, 65 graphs (the matrix-core kernels: one to three graph
 tiles, padding graphs in the last one) --, F at the edges of the MFMA's k pair, of the 8-column fragment group, of the 16-byte loads
-and of the 32-column feature tiles of the backward accumulators (1, 3, 32, 33, 100, 256, 512: every template instance of both
-backward kernels), in a sparse cross product.  Tables: "even" (graph boundaries inside 32-node tiles), "empty" (empty graphs at the
+and of the 32-column feature tiles of the backward accumulators (1, 3, 32, 33, 100, 256, 512 -- 1, 2, 4, 8 and 16 tiles: every
+template instance of both backward kernels, each completely filled; 256, 128 and 32 rows a block of the single-graph vector
+kernels, and 64 as well for the bootstrap's), in a sparse cross product.  The other tile counts, the single-graph kernels at 64 rows
+a block, both sides of each edge of the rows a block, and part counts below the tile count (every case here has one part per node
+tile) are tests/test_gpu_loss_regimes.py's.  Tables: "even" (graph boundaries inside 32-node tiles), "empty" (empty graphs at the
 front, in the middle and at the end), "one" (one graph holds every node, the others are empty).  The mirror runs once per shape (a
 module-wide cache) and serves every test.
 

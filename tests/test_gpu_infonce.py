@@ -3,8 +3,10 @@
 
 Shapes: N at the edges of the 32-wide tiles, of the workgroup's 128-row block and of the part split (1, 31, 32, 33, 64, 65, 127, 129,
 300, and 2708 -- Cora's size: several parts, many workgroups), F at the edges of the MFMA's k pair, of the 8-column fragment group
-and of the 32-column feature tiles of the backward accumulators (1, 2, 3, 31, 32, 33, 100, 256, 512 -- one to sixteen tiles, every
-template instance), in a sparse cross product.  The mirror runs once per shape (a module-wide cache) and serves every test.
+and of the 32-column feature tiles of the backward accumulators (1, 2, 3, 31, 32, 33, 100, 256, 512 -- 1, 2, 4, 8 and 16 tiles:
+every template instance, each completely filled), in a sparse cross product.  The mirror runs once per shape (a module-wide cache)
+and serves every test.  The other tile counts (an instance with dead accumulator tiles), the part counts below the tile count and
+the single part of N >= 32,641 are tests/test_gpu_loss_regimes.py's.
 
   forward    Z equals the mirror's bit for bit.  rows: the device's float64 log may differ from the host's by one unit in the last
              place and nothing else may, so with u = c s_ii - 1/tau from the MIRROR's s_ii, the device's row must be fl(u - L) for L
@@ -82,16 +84,22 @@ def test_forward_against_the_mirror(ops, mirror, n, f, positive, tau):
     st = dict(ops.last_stats)
     assert (st["rows"], st["features"], st["host_syncs"]) == (n, f, 0) and st["parts"] == mirror.lib.infonce_parts(n)
     assert loss.dtype == torch.float64 and loss.dim() == 0 and rows.shape == (n,)
+    err = rows_against_the_mirror(rows, m, positive, tau)
+    print(f"n={n} F={f} {positive} tau={tau}: rows max |diff| {err:.3g}, loss diff {abs(float(loss) - m['loss']):.3g}")
+    assert err <= 1e-13
+    assert abs(float(loss) - m["loss"]) <= 1e-13
+
+
+def rows_against_the_mirror(rows, m, positive, tau):
+    """Asserts the neighbour rule of the module docstring on the device's rows (every row is fl(u - L), u from the mirror's s_ii and L
+    one of log(Z) and its two neighbours); returns the largest |row - the mirror's row|, which the caller holds to 1e-13."""
     rows = rows.cpu().numpy()
     c = 1.0 if positive == "raw" else 1.0 / tau
     u = c * m["sii"].astype(np.float64) - 1.0 / tau
     L = np.log(m["z"])
     allowed = np.stack([u - np.nextafter(L, -np.inf), u - L, u - np.nextafter(L, np.inf)])
-    err = np.abs(rows - m["rows"]).max()
-    print(f"n={n} F={f} {positive} tau={tau}: rows max |diff| {err:.3g}, loss diff {abs(float(loss) - m['loss']):.3g}")
     assert (rows[None, :] == allowed).any(axis=0).all(), "a row is not c s_ii - 1/tau - log Z with the mirror's s_ii and Z"
-    assert err <= 1e-13
-    assert abs(float(loss) - m["loss"]) <= 1e-13
+    return np.abs(rows - m["rows"]).max()
 
 
 @pytest.mark.parametrize("n,f,positive,tau", CASES)
@@ -114,17 +122,23 @@ def forward_z(ops, a, b, tau, positive):
     return ops._info_nce_forward(a, b, float(tau), ops.INFONCE_POSITIVE[positive])[2]
 
 
-@pytest.mark.parametrize("n,f", [(65, 8), (300, 40), (129, 33)])
-def test_operand_maps_with_exact_data(ops, mirror, n, f):
-    """a_i = e_(i mod F); b_j = four entries +-1 (hat: +-0.5) in columns drawn per j: s_ij = bh_j[i mod F], exactly 0 or +-0.5, and
-    s_ij != s_ji in general.  Z_i = (count of +0.5) e+ + (count of 0) e0 + (count of -0.5) e-, exact in float64 in any order."""
-    tau = 2.0
+def exact_views(n, f):
+    """The data of test_operand_maps_with_exact_data: a_i = e_(i mod F), b_j = four entries +-1 in columns drawn per j."""
     rng = np.random.RandomState(n + f)
     a = np.zeros((n, f), dtype=np.float32)
     a[np.arange(n), np.arange(n) % f] = 1.0
     b = np.zeros((n, f), dtype=np.float32)
     for j in range(n):
         b[j, rng.choice(f, 4, replace=False)] = rng.choice([-1.0, 1.0], 4)
+    return a, b
+
+
+@pytest.mark.parametrize("n,f", [(65, 8), (300, 40), (129, 33)])
+def test_operand_maps_with_exact_data(ops, mirror, n, f):
+    """a_i = e_(i mod F); b_j = four entries +-1 (hat: +-0.5) in columns drawn per j: s_ij = bh_j[i mod F], exactly 0 or +-0.5, and
+    s_ij != s_ji in general.  Z_i = (count of +0.5) e+ + (count of 0) e0 + (count of -0.5) e-, exact in float64 in any order."""
+    tau = 2.0
+    a, b = exact_views(n, f)
     s = (b / 2.0)[:, np.arange(n) % f].T                                        # s[i, j] = bh_j[i mod F]
     assert not np.array_equal(s, s.T)
     itf = np.float32(1.0 / tau)
