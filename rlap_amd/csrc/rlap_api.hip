@@ -1321,6 +1321,23 @@ int snapshot_call(rlap_handle h, Bytes bytes, Run run) {
     return run(base, have, need);
 }
 
+// One call of the readout, the fused losses or the probe on that path.  A poisoned handle (debug) first fills the arena and the
+// result buffers `outs` -- (pointer, bytes); a null pointer or zero bytes is skipped -- so that no result can depend on what they
+// held.  *arena_bytes (may be null) gets the arena's size; then run(base, have) -> status.
+using PoisonList = std::initializer_list<std::pair<void*, size_t>>;
+template <class Bytes, class Run>
+int poisoned_call(rlap_handle h, Bytes bytes, PoisonList outs, int64_t* arena_bytes, Run run) {
+    return snapshot_call(h, bytes, [&](void* base, size_t have, size_t need) -> int {
+        if (h->poison >= 0) {
+            if (need) RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
+            for (const auto& o : outs)
+                if (o.first && o.second) RLAP_HIPCHK(hipMemsetAsync(o.first, h->poison, o.second, h->stream));
+        }
+        if (arena_bytes) *arena_bytes = (int64_t)need;
+        return run(base, have);
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1588,25 +1605,17 @@ int rlap_graph_readout(rlap_handle h, const void* d_x, int64_t L, int64_t num_no
                        int flags, void* d_y, rlap_readout_info* h_info) {
     if (const int rc = readout_check(h, d_x, L, num_nodes, F, d_node_ptr, G, flags, d_y, h_info)) return rc;
     const ReadoutArgs a{d_x, L, num_nodes, F, d_node_ptr, G, flags, d_y};
-    return snapshot_call(h, [&] { return readout_bytes(L, num_nodes, F, G); }, [&](void* base, size_t have, size_t need) -> int {
-        if (h->poison >= 0) {   // debug: the result must not depend on what the arena or the result buffer held
-            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
-            if (L * G * F > 0) RLAP_HIPCHK(hipMemsetAsync(d_y, h->poison, (size_t)(L * G * F) * ((flags & RLAP_READOUT_X_F32) ? 4 : 8), h->stream));
-        }
-        if (h_info) h_info->arena_bytes = (int64_t)need;
-        return readout_run(h->stream, base, have, a);
-    });
+    return poisoned_call(h, [&] { return readout_bytes(L, num_nodes, F, G); }, {{d_y, (size_t)(L * G * F) * ((flags & RLAP_READOUT_X_F32) ? 4 : 8)}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) { return readout_run(h->stream, base, have, a); });
 }
 
 int rlap_graph_readout_backward(rlap_handle h, const void* d_gy, int64_t L, int64_t num_nodes, int64_t F, const int64_t* d_node_ptr,
                                 int64_t G, int flags, void* d_gx, rlap_readout_info* h_info) {
     if (const int rc = readout_check(h, d_gx, L, num_nodes, F, d_node_ptr, G, flags, const_cast<void*>(d_gy), h_info)) return rc;
     const ReadoutArgs a{d_gy, L, num_nodes, F, d_node_ptr, G, flags, d_gx};
-    return snapshot_call(h, [&] { return (size_t)0; }, [&](void*, size_t, size_t) -> int {   // (no scratch: the gather reads the table itself)
-        if (h->poison >= 0 && L * num_nodes * F > 0)
-            RLAP_HIPCHK(hipMemsetAsync(d_gx, h->poison, (size_t)(L * num_nodes * F) * ((flags & RLAP_READOUT_X_F32) ? 4 : 8), h->stream));
-        return readout_backward_run(h->stream, a);
-    });
+    // (no scratch: the gather reads the table itself)
+    return poisoned_call(h, [&] { return (size_t)0; }, {{d_gx, (size_t)(L * num_nodes * F) * ((flags & RLAP_READOUT_X_F32) ? 4 : 8)}}, nullptr,
+                         [&](void*, size_t) { return readout_backward_run(h->stream, a); });
 }
 
 namespace {
@@ -1629,16 +1638,8 @@ int rlap_infonce(rlap_handle h, const float* d_a, const float* d_b, int64_t N, i
     if (!d_loss || !d_rows || !d_z) return RLAP_E_BAD_ARG;
     InfonceArgs a{};
     a.a = d_a; a.b = d_b; a.N = N; a.F = F; a.tau = tau; a.flags = flags; a.loss = d_loss; a.rows = d_rows; a.z = d_z;
-    return snapshot_call(h, [&] { return infonce_bytes(N, F); }, [&](void* base, size_t have, size_t need) -> int {
-        if (h->poison >= 0) {   // debug: the result must not depend on what the arena or the result buffers held
-            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
-            RLAP_HIPCHK(hipMemsetAsync(d_loss, h->poison, 8, h->stream));
-            RLAP_HIPCHK(hipMemsetAsync(d_rows, h->poison, (size_t)N * 8, h->stream));
-            RLAP_HIPCHK(hipMemsetAsync(d_z, h->poison, (size_t)N * 8, h->stream));
-        }
-        if (h_info) h_info->arena_bytes = (int64_t)need;
-        return infonce_run(h->stream, base, have, a);
-    });
+    return poisoned_call(h, [&] { return infonce_bytes(N, F); }, {{d_loss, 8}, {d_rows, (size_t)N * 8}, {d_z, (size_t)N * 8}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) { return infonce_run(h->stream, base, have, a); });
 }
 
 int rlap_infonce_backward(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double tau, int flags,
@@ -1647,15 +1648,8 @@ int rlap_infonce_backward(rlap_handle h, const float* d_a, const float* d_b, int
     if (!d_z || !d_g || !d_ga || !d_gb) return RLAP_E_BAD_ARG;
     InfonceArgs a{};
     a.a = d_a; a.b = d_b; a.N = N; a.F = F; a.tau = tau; a.flags = flags; a.z_in = d_z; a.g = d_g; a.ga = d_ga; a.gb = d_gb;
-    return snapshot_call(h, [&] { return infonce_backward_bytes(N, F); }, [&](void* base, size_t have, size_t need) -> int {
-        if (h->poison >= 0) {
-            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
-            RLAP_HIPCHK(hipMemsetAsync(d_ga, h->poison, (size_t)(N * F) * 4, h->stream));
-            RLAP_HIPCHK(hipMemsetAsync(d_gb, h->poison, (size_t)(N * F) * 4, h->stream));
-        }
-        if (h_info) h_info->arena_bytes = (int64_t)need;
-        return infonce_backward_run(h->stream, base, have, a);
-    });
+    return poisoned_call(h, [&] { return infonce_backward_bytes(N, F); }, {{d_ga, (size_t)(N * F) * 4}, {d_gb, (size_t)(N * F) * 4}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) { return infonce_backward_run(h->stream, base, have, a); });
 }
 
 namespace {
@@ -1677,16 +1671,8 @@ int rlap_cca_loss(rlap_handle h, const float* d_a, const float* d_b, int64_t N, 
     if (!d_terms || !d_colstat || !d_gram) return RLAP_E_BAD_ARG;
     CcaArgs a{};
     a.a = d_a; a.b = d_b; a.N = N; a.F = F; a.lambd = lambd; a.terms = d_terms; a.colstat = d_colstat; a.gram = d_gram;
-    return snapshot_call(h, [&] { return cca_bytes(N, F); }, [&](void* base, size_t have, size_t need) -> int {
-        if (h->poison >= 0) {   // debug: the result must not depend on what the arena or the result buffers held
-            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
-            RLAP_HIPCHK(hipMemsetAsync(d_terms, h->poison, 4 * 8, h->stream));
-            RLAP_HIPCHK(hipMemsetAsync(d_colstat, h->poison, (size_t)(4 * F) * 8, h->stream));
-            RLAP_HIPCHK(hipMemsetAsync(d_gram, h->poison, (size_t)(2 * F * F) * 4, h->stream));
-        }
-        if (h_info) h_info->arena_bytes = (int64_t)need;
-        return cca_run(h->stream, base, have, a);
-    });
+    return poisoned_call(h, [&] { return cca_bytes(N, F); }, {{d_terms, 4 * 8}, {d_colstat, (size_t)(4 * F) * 8}, {d_gram, (size_t)(2 * F * F) * 4}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) { return cca_run(h->stream, base, have, a); });
 }
 
 int rlap_cca_loss_backward(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double lambd, int flags,
@@ -1696,15 +1682,8 @@ int rlap_cca_loss_backward(rlap_handle h, const float* d_a, const float* d_b, in
     if (!d_colstat || !d_gram || !d_g || !d_ga || !d_gb) return RLAP_E_BAD_ARG;
     CcaArgs a{};
     a.a = d_a; a.b = d_b; a.N = N; a.F = F; a.lambd = lambd; a.colstat_in = d_colstat; a.gram_in = d_gram; a.g = d_g; a.ga = d_ga; a.gb = d_gb;
-    return snapshot_call(h, [&] { return cca_backward_bytes(N, F); }, [&](void* base, size_t have, size_t need) -> int {
-        if (h->poison >= 0) {
-            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
-            RLAP_HIPCHK(hipMemsetAsync(d_ga, h->poison, (size_t)(N * F) * 4, h->stream));
-            RLAP_HIPCHK(hipMemsetAsync(d_gb, h->poison, (size_t)(N * F) * 4, h->stream));
-        }
-        if (h_info) h_info->arena_bytes = (int64_t)need;
-        return cca_backward_run(h->stream, base, have, a);
-    });
+    return poisoned_call(h, [&] { return cca_backward_bytes(N, F); }, {{d_ga, (size_t)(N * F) * 4}, {d_gb, (size_t)(N * F) * 4}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) { return cca_backward_run(h->stream, base, have, a); });
 }
 
 namespace {
@@ -1719,17 +1698,10 @@ int g2l_check(rlap_handle h, const float* d_h, const float* d_g, int64_t N, int6
     return RLAP_OK;
 }
 
-// one of the four calls on the checked path; `outs` are the result buffers (pointer, bytes) a poisoned run fills first
-int g2l_call(rlap_handle h, int call, const G2lArgs& a, rlap_g2l_info* h_info, std::initializer_list<std::pair<void*, size_t>> outs) {
-    return snapshot_call(h, [&] { return g2l_bytes(call, a.N, a.G, a.F); }, [&](void* base, size_t have, size_t need) -> int {
-        if (h->poison >= 0) {   // debug: the result must not depend on what the arena or the result buffers held
-            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
-            for (const auto& o : outs)
-                if (o.first) RLAP_HIPCHK(hipMemsetAsync(o.first, h->poison, o.second, h->stream));
-        }
-        if (h_info) h_info->arena_bytes = (int64_t)need;
-        return g2l_run(call, h->stream, base, have, a);
-    });
+// one of the four calls on the checked path; `outs` are the result buffers a poisoned run fills first
+int g2l_call(rlap_handle h, int call, const G2lArgs& a, rlap_g2l_info* h_info, PoisonList outs) {
+    return poisoned_call(h, [&] { return g2l_bytes(call, a.N, a.G, a.F); }, outs, h_info ? &h_info->arena_bytes : nullptr,
+                         [&](void* base, size_t have) { return g2l_run(call, h->stream, base, have, a); });
 }
 
 }  // namespace
@@ -1812,19 +1784,14 @@ int rlap_linear_probe(rlap_handle h, const float* d_x, int64_t N, int64_t F, int
     a.eps = eps; a.w0 = d_weight0; a.b0 = d_bias0; a.w = d_weight; a.b = d_bias; a.scores = d_scores; a.best = d_best;
     a.confusion = d_confusion; a.status = d_status;
     if (const int rc = probe_check(h, a, 3, true, h_info)) return rc;
-    return snapshot_call(h, [&] { return probe_bytes(a); }, [&](void* base, size_t have, size_t need) -> int {
-        if (h->poison >= 0) {   // debug: the result must not depend on what the arena or the result buffers held
-            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
-            if (d_weight != d_weight0) RLAP_HIPCHK(hipMemsetAsync(d_weight, h->poison, (size_t)(R * C * F) * 4, h->stream));
-            if (d_bias != d_bias0) RLAP_HIPCHK(hipMemsetAsync(d_bias, h->poison, (size_t)(R * C) * 4, h->stream));
-            RLAP_HIPCHK(hipMemsetAsync(d_scores, h->poison, (size_t)(R * 4) * 8, h->stream));
-            RLAP_HIPCHK(hipMemsetAsync(d_best, h->poison, (size_t)(R * 2) * 8, h->stream));
-            RLAP_HIPCHK(hipMemsetAsync(d_confusion, h->poison, (size_t)(R * 2 * C * C) * 8, h->stream));
-            RLAP_HIPCHK(hipMemsetAsync(d_status, h->poison, 4, h->stream));
-        }
+    // (parameters that are trained in place are inputs: not poisoned)
+    return poisoned_call(h, [&] { return probe_bytes(a); },
+                         {{d_weight != d_weight0 ? d_weight : nullptr, (size_t)(R * C * F) * 4}, {d_bias != d_bias0 ? d_bias : nullptr, (size_t)(R * C) * 4},
+                          {d_scores, (size_t)(R * 4) * 8}, {d_best, (size_t)(R * 2) * 8}, {d_confusion, (size_t)(R * 2 * C * C) * 8}, {d_status, 4}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) {
         int64_t parts = 0, launches = 0;
         const int rc = probe_run(h->stream, base, have, a, &parts, &launches);
-        if (h_info) { h_info->arena_bytes = (int64_t)need; h_info->parts = parts; h_info->launches = launches; }
+        if (h_info) { h_info->parts = parts; h_info->launches = launches; }
         return rc;
     });
 }
@@ -1836,17 +1803,12 @@ int rlap_probe_scores(rlap_handle h, const float* d_x, int64_t N, int64_t F, int
     a.x = d_x; a.N = N; a.F = F; a.ldx = ldx; a.y = d_y; a.C = C; a.R = R; a.idx[0] = d_index; a.hptr[0] = h_ptr;
     a.w0 = d_weight; a.b0 = d_bias; a.pred = d_pred; a.confusion = d_confusion; a.scores = d_scores; a.status = d_status;
     if (const int rc = probe_check(h, a, 1, false, h_info)) return rc;
-    return snapshot_call(h, [&] { return scores_bytes(a); }, [&](void* base, size_t have, size_t need) -> int {
-        if (h->poison >= 0) {
-            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
-            RLAP_HIPCHK(hipMemsetAsync(d_pred, h->poison, (size_t)h_ptr[R] * 8, h->stream));
-            RLAP_HIPCHK(hipMemsetAsync(d_confusion, h->poison, (size_t)(R * C * C) * 8, h->stream));
-            RLAP_HIPCHK(hipMemsetAsync(d_scores, h->poison, (size_t)(R * 3) * 8, h->stream));
-            RLAP_HIPCHK(hipMemsetAsync(d_status, h->poison, 4, h->stream));
-        }
+    return poisoned_call(h, [&] { return scores_bytes(a); },
+                         {{d_pred, (size_t)h_ptr[R] * 8}, {d_confusion, (size_t)(R * C * C) * 8}, {d_scores, (size_t)(R * 3) * 8}, {d_status, 4}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) {
         int64_t launches = 0;
         const int rc = scores_run(h->stream, base, have, a, &launches);
-        if (h_info) { h_info->arena_bytes = (int64_t)need; h_info->parts = 1; h_info->launches = launches; }
+        if (h_info) { h_info->parts = 1; h_info->launches = launches; }
         return rc;
     });
 }

@@ -32,11 +32,19 @@
 #include <stdint.h>
 
 #include "rlap_spmm.h"
+#include "rlap_tile32.h"
 
 namespace rlap {
 namespace cca {
 
-constexpr int TILE = 32;                  // rows and columns of a Gram tile (one 32x32 MFMA accumulator)
+// a Gram tile is rlap_tile32.h's: its sizes and its register layout (reg_row)
+using tile32::TILE;
+using tile32::num_tiles;
+using tile32::padded_rows;
+using tile32::feature_tiles;
+using tile32::padded_features;
+using tile32::reg_row;
+
 constexpr int MAX_F = 512;                // feature columns of a call
 constexpr int SUPER = 2;                  // a wave owns SUPER x SUPER Gram tiles: a 64 x 64 "super tile" pair
 constexpr int GROUP_PAIRS = 4;            // super-tile pairs of a workgroup (one per wave)
@@ -45,11 +53,7 @@ constexpr int64_t MAX_PARTS = 64;         // (bounds the part accumulators of th
 
 RLAP_SPMM_HD bool lambd_ok(double l) { return l >= 0.0 && l <= 1.7976931348623157e308; }   // (false for a NaN and for inf)
 
-// the 32-row tiles of N rows, the padded sizes of the arena's images, the 32- and 64-column tiles of F columns
-RLAP_SPMM_HD int64_t num_tiles(int64_t N) { return N > 0 ? (N + TILE - 1) / TILE : 0; }
-RLAP_SPMM_HD int64_t padded_rows(int64_t N) { return num_tiles(N) * TILE; }
-RLAP_SPMM_HD int feature_tiles(int64_t F) { return (int)((F + TILE - 1) / TILE); }
-RLAP_SPMM_HD int padded_features(int64_t F) { return feature_tiles(F) * TILE; }
+// the 64-column tiles of F columns
 RLAP_SPMM_HD int super_tiles(int64_t F) { return (feature_tiles(F) + SUPER - 1) / SUPER; }
 // the upper triangle of super-tile pairs (I <= J), numbered row by row, and the workgroups of a (view, part) that share them out
 RLAP_SPMM_HD int super_pairs(int64_t F) { return super_tiles(F) * (super_tiles(F) + 1) / 2; }
@@ -69,13 +73,10 @@ RLAP_SPMM_HD bool tile_stored(int I, int J, int a, int b, int nft) {
 
 // Which instances the launchers of rlap_cca.hip take for nft = feature_tiles(F); 0 for an nft outside [1, MAX_F / TILE], which no
 // launcher accepts.
-//   k_cca_gram<NV>   a thread stages nft float4s of a 32-row step and guards each with j < nft: the smallest NV of 1, 2, 4, 8, 16
-//                    that holds nft.
+//   k_cca_gram<NV>   a thread stages nft float4s of a 32-row step and guards each with j < nft: the ladder's instance.
 //   k_cca_zr<NCT>    wave w owns the column tiles w, w + 4, ..., guarded with w + 4 j < nft: NCT = ceil(nft / 4), 1 to 4.
-RLAP_SPMM_HD int gram_instance(int nft) {
-    if (nft < 1 || nft > MAX_F / TILE) return 0;
-    return nft <= 1 ? 1 : (nft <= 2 ? 2 : (nft <= 4 ? 4 : (nft <= 8 ? 8 : 16)));
-}
+static_assert(MAX_F / TILE == tile32::MAX_INSTANCE, "the ladder ends at MAX_F");
+RLAP_SPMM_HD int gram_instance(int nft) { return tile32::ladder_instance(nft); }
 RLAP_SPMM_HD int zr_instance(int nft) {
     if (nft < 1 || nft > MAX_F / TILE) return 0;
     return (nft + 3) / 4;   // (four waves a workgroup)
@@ -91,9 +92,6 @@ RLAP_SPMM_HD int64_t num_parts(int64_t N, int64_t F) {
     return p < 1 ? 1 : (p > T ? T : p);
 }
 RLAP_SPMM_HD int64_t part_begin(int64_t N, int64_t F, int64_t p) { return (p * num_tiles(N) / num_parts(N, F)) * TILE; }   // a ROW; (T < 2^26, p <= 64)
-
-// row of a 32x32 accumulator tile that register r of a lane of half h holds (the tile's column is lane & 31)
-RLAP_SPMM_HD int reg_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // ---- the values
 RLAP_SPMM_HD double col_mean(double total, int64_t N) { return total / (double)N; }

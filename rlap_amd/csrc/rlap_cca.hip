@@ -28,20 +28,19 @@
 #include "rlap_cca.h"
 #include "rlap_cca_api.h"
 #include "rlap_spmm.h"
+#include "rlap_tile32_dev.h"
 
 namespace rlap {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using tile32::f32x16;
 
 constexpr int CC_THREADS = 256;                 // four waves: cca::GROUP_PAIRS super-tile pairs
 constexpr int64_t CC_MAX_GRID = 1 << 20;        // workgroups of a striding launch
 static_assert(CC_THREADS == 64 * cca::GROUP_PAIRS, "one wave per super-tile pair");
 static_assert(cca::SUPER == 2, "the Gram kernel holds 2 x 2 accumulator tiles");
 
-inline unsigned cc_blocks(int64_t n, int per_block) {
-    return (unsigned)std::min<int64_t>(CC_MAX_GRID, std::max<int64_t>(1, (n + per_block - 1) / per_block));
-}
+inline unsigned cc_blocks(int64_t n, int per_block) { return capped_blocks(n, per_block, CC_MAX_GRID); }
 
 // ------------------------------------------------------------------------------------------------ column sums by the chunk rule
 enum { CS_SUM = 0, CS_SS = 1, CS_DOT = 2, CS_M = 3, CS_Q = 4 };
@@ -408,8 +407,7 @@ int launch_z(hipStream_t st, const CcaArgs& g, const Bufs& B, const double* cols
 template <int NV>
 int launch_gram(hipStream_t st, const Gram& m) {
     const size_t lds = (size_t)cca::TILE * m.Fp * sizeof(float);
-    auto* fn = &k_cca_gram<NV>;
-    RLAP_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (const int rc = tile32::allow_lds(&k_cca_gram<NV>, lds)) return rc;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cca_gram<NV>), dim3((unsigned)(2 * m.parts * m.groups)), dim3(CC_THREADS), lds, st, m);
     RLAP_HIPCHK(hipGetLastError());
     return RLAP_OK;
@@ -418,8 +416,7 @@ int launch_gram(hipStream_t st, const Gram& m) {
 template <int NCT>
 int launch_zr(hipStream_t st, const ZR& a) {
     const size_t lds = (size_t)cca::TILE * a.Fp * sizeof(float);
-    auto* fn = &k_cca_zr<NCT>;
-    RLAP_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (const int rc = tile32::allow_lds(&k_cca_zr<NCT>, lds)) return rc;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cca_zr<NCT>), dim3((unsigned)(2 * a.T)), dim3(CC_THREADS), lds, st, a);
     RLAP_HIPCHK(hipGetLastError());
     return RLAP_OK;
@@ -427,14 +424,7 @@ int launch_zr(hipStream_t st, const ZR& a) {
 
 // the instances by the header's rules; no instance (F outside [1, MAX_F], which the entry point refuses) is an error
 int launch_gram_of(hipStream_t st, const Gram& m) {
-    switch (cca::gram_instance(m.nft)) {
-        case 1: return launch_gram<1>(st, m);
-        case 2: return launch_gram<2>(st, m);
-        case 4: return launch_gram<4>(st, m);
-        case 8: return launch_gram<8>(st, m);
-        case 16: return launch_gram<16>(st, m);
-    }
-    return RLAP_E_INTERNAL;
+    return tile32::ladder_launch(m.nft, [&](auto nv) { return launch_gram<decltype(nv)::value>(st, m); });
 }
 
 int launch_zr_of(hipStream_t st, const ZR& a) {

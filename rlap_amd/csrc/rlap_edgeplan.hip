@@ -36,7 +36,7 @@ constexpr int EP_THREADS = 256;
 constexpr int64_t EP_MAX_GRID = 8192;                    // workgroups of a launch (the kernels stride over their tasks)
 enum { CNT_LOOPS = 0, CNT_BLOCKS = 1, CNT_CHUNKED_F = 2, CNT_CHUNKED_T = 3, CNT_WORDS = 4 };
 
-inline unsigned ep_blocks(int64_t n, int bs) { return (unsigned)std::min<int64_t>(EP_MAX_GRID, std::max<int64_t>(1, (n + bs - 1) / bs)); }
+inline unsigned ep_blocks(int64_t n, int bs) { return capped_blocks(n, bs, EP_MAX_GRID); }
 
 __device__ inline int64_t ep_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 

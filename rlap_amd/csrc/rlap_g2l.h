@@ -49,13 +49,21 @@
 
 #include "rlap_infonce.h"
 #include "rlap_spmm.h"
+#include "rlap_tile32.h"
 
 namespace rlap {
 namespace g2l {
 
-constexpr int TILE = infonce::TILE;               // nodes / graphs of a score tile (one 32x32 MFMA accumulator)
+// a score tile (32 nodes x 32 graphs) is rlap_tile32.h's
+using tile32::TILE;
+using tile32::BLOCK_TILES;
+using tile32::num_tiles;
+using tile32::row_blocks;
+using tile32::padded_rows;
+using tile32::padded_features;
+using tile32::reg_row;
+
 constexpr int MAX_F = infonce::MAX_F;             // feature columns of a call
-constexpr int BLOCK_TILES = infonce::BLOCK_TILES; // owner tiles of a workgroup (one per wave)
 constexpr int64_t TARGET_GROUPS = 256;            // workgroups the dg pass aims at when G is small
 constexpr int64_t VEC_PARTS = 1024;               // parts of the dg pass of a single graph, at most
 constexpr int VEC_THREADS = 256;                  // rows of a block of the vector kernels, at most (one thread per row)
@@ -63,13 +71,7 @@ constexpr int64_t VEC_LDS_BYTES = 66 * 1024;      // LDS of a block of the vecto
 
 enum Call { JSD_FORWARD = 0, JSD_BACKWARD = 1, BOOT_FORWARD = 2, BOOT_BACKWARD = 3 };
 
-// ---- tiles, parts, padded sizes
-RLAP_SPMM_HD int64_t num_tiles(int64_t n) { return infonce::num_tiles(n); }
-RLAP_SPMM_HD int64_t row_blocks(int64_t n) { return infonce::row_blocks(n); }
-RLAP_SPMM_HD int64_t padded_rows(int64_t n) { return infonce::padded_rows(n); }
-RLAP_SPMM_HD int padded_features(int64_t F) { return infonce::padded_features(F); }
-RLAP_SPMM_HD int reg_row(int r, int hf) { return infonce::reg_row(r, hf); }
-
+// ---- parts
 // the parts of the node tiles in the dg pass: a function of (N, G, F) alone (F does not enter today)
 RLAP_SPMM_HD int64_t num_parts(int64_t N, int64_t G, int64_t F) {
     (void)F;

@@ -5,7 +5,7 @@
 //
 //   pre-pass   the node -> graph map from node_ptr (every value read from the table is clamped before it is compared: the map lies
 //              in [0, G) whatever the table holds; the table is never read back).  JSD, G >= 2: the zero-padded images of h and g,
-//              the FRAGMENT image of rlap_infonce.h and (backward) the row-major image.  Bootstrap: the hat image of g.
+//              the FRAGMENT image of rlap_tile32.h and (backward) the row-major image.  Bootstrap: the hat image of g.
 //   JSD main   G >= 2: rlap_infonce.hip's structure with a short stream.  A workgroup of four waves OWNS four 32-row tiles of one
 //              input and walks the 32-row tiles of the other, staged through LDS once for the four waves; per tile a wave computes
 //              X[stream row][owner row] with v_mfma_f32_32x32x2_f32.
@@ -28,20 +28,19 @@
 #include "rlap_g2l.h"
 #include "rlap_g2l_api.h"
 #include "rlap_spmm.h"
+#include "rlap_tile32_dev.h"
 
 namespace rlap {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using tile32::f32x16;
 
 constexpr int GL_THREADS = 256;                 // four waves: g2l::BLOCK_TILES owner tiles
 constexpr int64_t GL_MAX_GRID = 1 << 20;        // workgroups of a striding launch
 static_assert(GL_THREADS == 64 * g2l::BLOCK_TILES, "one wave per owner tile");
 static_assert(GL_THREADS == g2l::VEC_THREADS, "one thread per staged row");
 
-inline unsigned gl_blocks(int64_t n, int per_block) {
-    return (unsigned)std::min<int64_t>(GL_MAX_GRID, std::max<int64_t>(1, (n + per_block - 1) / per_block));
-}
+inline unsigned gl_blocks(int64_t n, int per_block) { return capped_blocks(n, per_block, GL_MAX_GRID); }
 
 // ------------------------------------------------------------------------------------------------ pre-pass
 // map[i] = g(i) for i < N, 0 behind (`len` entries)
@@ -58,7 +57,7 @@ __global__ __launch_bounds__(256) void k_g2l_pad(const float* __restrict__ x, in
         const int64_t i = e / Fp;
         const int k = (int)(e - i * Fp);
         const float v = (i < N && k < F) ? x[i * F + k] : 0.0f;
-        frag[infonce::frag_offset(i, k, Fp)] = v;
+        frag[tile32::frag_offset(i, k, Fp)] = v;
         if (rows) rows[e] = v;
     }
 }
@@ -84,22 +83,6 @@ struct Main {
 };
 
 enum { GL_FORWARD = 0, GL_BACK_DH = 1, GL_BACK_DG = 2 };
-
-// X[stream row][owner row] of one tile pair: the chain over the padded columns, four MFMAs per 16 bytes of either operand
-__device__ inline f32x16 gl_score_tile(const float4* __restrict__ stream_lds, const float4* __restrict__ owner, int nqq, int lane) {
-    f32x16 x;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) x[r] = 0.0f;
-    for (int qq = 0; qq < nqq; ++qq) {
-        const float4 s = stream_lds[qq * 64 + lane];
-        const float4 o = owner[qq * 64 + lane];
-        x = __builtin_amdgcn_mfma_f32_32x32x2f32(s.x, o.x, x, 0, 0, 0);
-        x = __builtin_amdgcn_mfma_f32_32x32x2f32(s.y, o.y, x, 0, 0, 0);
-        x = __builtin_amdgcn_mfma_f32_32x32x2f32(s.z, o.z, x, 0, 0, 0);
-        x = __builtin_amdgcn_mfma_f32_32x32x2f32(s.w, o.w, x, 0, 0, 0);
-    }
-    return x;
-}
 
 template <int NFT, int MODE>
 __global__ __launch_bounds__(GL_THREADS) void k_g2l_main(Main a) {
@@ -127,28 +110,15 @@ __global__ __launch_bounds__(GL_THREADS) void k_g2l_main(Main a) {
     double nsum = 0.0, pos = 0.0;
     int have = 0;
     f32x16 acc[NFT];
-    if (MODE != GL_FORWARD) {
-#pragma unroll
-        for (int ft = 0; ft < NFT; ++ft)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[ft][r] = 0.0f;
-    }
+    if (MODE != GL_FORWARD) tile32::zero_tiles(acc);
 
 #pragma unroll 1
     for (int64_t t = tb; t < te; ++t) {
         __syncthreads();   // (the previous tile has been read)
-        {
-            const float4* __restrict__ src = reinterpret_cast<const float4*>(a.str_frag + t * tile_floats);
-            float4* dst = reinterpret_cast<float4*>(gl_lds);
-            for (int v = threadIdx.x; v < tile_vec; v += GL_THREADS) dst[v] = src[v];
-            if (MODE != GL_FORWARD) {
-                const float4* __restrict__ src2 = reinterpret_cast<const float4*>(a.str_rows + t * tile_floats);   // (rows 32 t .. 32 t + 31 are contiguous)
-                for (int v = threadIdx.x; v < tile_vec; v += GL_THREADS) dst[tile_vec + v] = src2[v];
-            }
-        }
+        tile32::stage_tile<GL_THREADS>(gl_lds, a.str_frag + t * tile_floats, MODE != GL_FORWARD ? a.str_rows + t * tile_floats : nullptr, tile_vec);
         __syncthreads();
         if (!active) continue;
-        f32x16 x = gl_score_tile(reinterpret_cast<const float4*>(gl_lds), owner, nqq, lane);
+        f32x16 x = tile32::pair_chain(reinterpret_cast<const float4*>(gl_lds), owner, nqq, lane);
         const int64_t srow0 = t * g2l::TILE;
         if (MODE == GL_FORWARD) {
 #pragma unroll
@@ -172,17 +142,7 @@ __global__ __launch_bounds__(GL_THREADS) void k_g2l_main(Main a) {
                 const float w = g2l::weight(cp, cn, x[r], graph == gi);
                 x[r] = (node < a.N && graph < a.G) ? w : 0.0f;
             }
-            const float* brow = gl_lds + (int)tile_floats + 4 * hf * a.Fp + c;   // row reg_row(r, hf) = reg_row(r, 0) + 4 hf of the staged tile
-#pragma unroll
-            for (int ft = 0; ft < NFT; ++ft) {
-                if (ft < a.nft) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const float bv = brow[g2l::reg_row(r, 0) * a.Fp + ft * g2l::TILE];
-                        acc[ft] = __builtin_amdgcn_mfma_f32_32x32x2f32(x[r], bv, acc[ft], 0, 0, 0);
-                    }
-                }
-            }
+            tile32::accumulate_tiles(acc, a.nft, x, gl_lds + (int)tile_floats, a.Fp, c, hf);
         }
     }
 
@@ -207,14 +167,7 @@ __global__ __launch_bounds__(GL_THREADS) void k_g2l_main(Main a) {
             }
         }
     } else {
-        float* __restrict__ out = a.partial + (part * a.Gp + ot * g2l::TILE) * a.Fp + c;
-#pragma unroll
-        for (int ft = 0; ft < NFT; ++ft) {
-            if (ft < a.nft) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) out[(int64_t)g2l::reg_row(r, hf) * a.Fp + ft * g2l::TILE] = acc[ft][r];
-            }
-        }
+        tile32::store_tiles(acc, a.nft, a.partial + (part * a.Gp + ot * g2l::TILE) * a.Fp, a.Fp, c, hf);
     }
 }
 
@@ -379,12 +332,7 @@ __global__ __launch_bounds__(64 * GL_GRAD_WAVES) void k_g2l_boot_grad(const floa
 // ------------------------------------------------------------------------------------------------ finish
 // chunk sums of `lists` lists of N doubles each, list l at rows + l N, into csum + l num_chunks(N)
 __global__ __launch_bounds__(256) void k_g2l_chunks(const double* __restrict__ rows, int64_t N, int lists, double* __restrict__ csum) {
-    const int64_t nc = spmm::num_chunks(N);
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nc * lists; q += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t l = q / nc, k = q - l * nc;
-        const double* list = rows + l * N;
-        csum[q] = spmm::chunk_sum(N, k, [](int64_t) { return 1.0; }, [&](int64_t e) { return list[e]; });
-    }
+    tile32::chunk_sums(rows, N, lists, csum);
 }
 
 __global__ void k_g2l_loss(const double* __restrict__ csum, int64_t N, int64_t G, int boot, double* __restrict__ loss) {
@@ -403,19 +351,10 @@ T* piece(void* ws, const g2l::Arena& A, int p) {
     return A.off[p] < 0 ? nullptr : reinterpret_cast<T*>(static_cast<char*>(ws) + A.off[p]);
 }
 
-// A launch takes up to 48 KB of dynamic LDS unasked; only a larger one raises the function's limit first.  Stateless: nothing is
-// remembered per process, so it holds for every device.
-template <class K>
-int allow_lds(K* fn, size_t lds) {
-    if (lds <= 48 * 1024) return RLAP_OK;
-    RLAP_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return RLAP_OK;
-}
-
 template <int NFT, int MODE>
 int launch_main_t(hipStream_t st, const Main& m) {
     const size_t lds = (size_t)g2l::TILE * m.Fp * sizeof(float) * (MODE == GL_FORWARD ? 1 : 2);
-    if (const int rc = allow_lds(&k_g2l_main<NFT, MODE>, lds)) return rc;
+    if (const int rc = tile32::allow_lds(&k_g2l_main<NFT, MODE>, lds)) return rc;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_g2l_main<NFT, MODE>), dim3((unsigned)(m.RB * m.parts)), dim3(GL_THREADS), lds, st, m);
     RLAP_HIPCHK(hipGetLastError());
     return RLAP_OK;
@@ -423,20 +362,13 @@ int launch_main_t(hipStream_t st, const Main& m) {
 
 template <int MODE>
 int launch_backward_main(hipStream_t st, const Main& m) {
-    switch (infonce::main_instance(m.nft)) {   // the rule is rlap_infonce.h's
-        case 1: return launch_main_t<1, MODE>(st, m);
-        case 2: return launch_main_t<2, MODE>(st, m);
-        case 4: return launch_main_t<4, MODE>(st, m);
-        case 8: return launch_main_t<8, MODE>(st, m);
-        case 16: return launch_main_t<16, MODE>(st, m);
-    }
-    return RLAP_E_INTERNAL;   // (no instance: F outside [1, MAX_F], which the entry point refuses)
+    return tile32::ladder_launch(m.nft, [&](auto nft) { return launch_main_t<decltype(nft)::value, MODE>(st, m); });
 }
 
 template <int MODE>
 int launch_vec(hipStream_t st, const Vec& v) {
     const size_t lds = (size_t)g2l::vec_rows(v.F) * g2l::vec_stride(v.F) * sizeof(float);
-    if (const int rc = allow_lds(&k_g2l_vec<MODE>, lds)) return rc;
+    if (const int rc = tile32::allow_lds(&k_g2l_vec<MODE>, lds)) return rc;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_g2l_vec<MODE>), dim3(gl_blocks(g2l::vec_blocks(v.N, v.F), 1)), dim3(GL_THREADS), lds, st, v);
     RLAP_HIPCHK(hipGetLastError());
     return RLAP_OK;

@@ -37,33 +37,33 @@
 #include <string.h>
 
 #include "rlap_spmm.h"
+#include "rlap_tile32.h"
 
 namespace rlap {
 namespace infonce {
 
-constexpr int TILE = 32;                  // rows and columns of a similarity tile (one 32x32 MFMA accumulator)
+// a similarity tile is rlap_tile32.h's: its sizes, its register layout (reg_row) and the fragment image (frag_offset)
+using tile32::TILE;
+using tile32::BLOCK_TILES;
+using tile32::num_tiles;
+using tile32::row_blocks;
+using tile32::padded_rows;
+using tile32::padded_features;
+using tile32::feature_tiles;
+using tile32::reg_row;
+using tile32::frag_offset;
+
 constexpr int MAX_F = 512;                // feature columns of a call
-constexpr int BLOCK_TILES = 4;            // owner tiles of a workgroup (one per wave)
 constexpr int64_t TARGET_GROUPS = 256;    // workgroups a call aims at when N is small: what num_parts() is made from
 constexpr double NORM_EPS = 1e-12;        // F.normalize's eps
 
 RLAP_SPMM_HD bool tau_ok(double tau) { return tau >= 1.0 / 32.0 && tau <= 1024.0; }   // (false for a NaN)
 
-// the 32-row tiles of N rows, the workgroups' row blocks, the padded sizes of the arena's copies
-RLAP_SPMM_HD int64_t num_tiles(int64_t N) { return N > 0 ? (N + TILE - 1) / TILE : 0; }
-RLAP_SPMM_HD int64_t row_blocks(int64_t N) { return (num_tiles(N) + BLOCK_TILES - 1) / BLOCK_TILES; }
-RLAP_SPMM_HD int64_t padded_rows(int64_t N) { return num_tiles(N) * TILE; }
-RLAP_SPMM_HD int padded_features(int64_t F) { return (int)((F + TILE - 1) / TILE) * TILE; }
-RLAP_SPMM_HD int feature_tiles(int64_t F) { return padded_features(F) / TILE; }
-
 // Which instance of a backward main kernel a call of nft = feature_tiles(F) takes (launch_backward_main of rlap_infonce.hip and of
 // rlap_g2l.hip): k_in_main<NFT, .> and k_g2l_main<NFT, .> hold NFT accumulator tiles a wave and guard each with ft < nft, so the
-// instance is the smallest of 1, 2, 4, 8, 16 that holds nft.  The launchers instantiate exactly these five; 0 for an nft outside
-// [1, MAX_F / TILE], which no launcher accepts.
-RLAP_SPMM_HD int main_instance(int nft) {
-    if (nft < 1 || nft > MAX_F / TILE) return 0;
-    return nft <= 1 ? 1 : (nft <= 2 ? 2 : (nft <= 4 ? 4 : (nft <= 8 ? 8 : 16)));
-}
+// instance is the ladder's.  The launchers instantiate exactly its five; 0 for an nft outside [1, MAX_F / TILE].
+static_assert(MAX_F / TILE == tile32::MAX_INSTANCE, "the ladder ends at MAX_F");
+RLAP_SPMM_HD int main_instance(int nft) { return tile32::ladder_instance(nft); }
 
 // The parts of the stream tiles: a function of N alone.  As many as bring the row blocks up to TARGET_GROUPS workgroups, at most
 // one per tile.
@@ -74,17 +74,6 @@ RLAP_SPMM_HD int64_t num_parts(int64_t N) {
     return p < 1 ? 1 : (p > T ? T : p);
 }
 RLAP_SPMM_HD int64_t part_begin(int64_t N, int64_t p) { return p * num_tiles(N) / num_parts(N); }   // (T < 2^26, p <= 256)
-
-// row of a 32x32 accumulator tile that register r of a lane of half h holds (the tile's column is lane & 31)
-RLAP_SPMM_HD int reg_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-// where element (row i, column k) of a normalised copy lies in its FRAGMENT image: tile by tile, eight columns (four k-pairs) by
-// eight columns, 64 lanes x 4 floats -- a lane's 16 bytes are its operands of four consecutive 32x32x2 MFMAs (lane = 32 (k & 1) + row)
-RLAP_SPMM_HD int64_t frag_offset(int64_t i, int k, int Fp) {
-    const int64_t t = i >> 5;
-    const int r = (int)(i & 31), q = k >> 1;
-    return ((t * (Fp >> 3) + (q >> 2)) * 64 + (k & 1) * 32 + r) * 4 + (q & 3);
-}
 
 // ---- the values
 RLAP_SPMM_HD double norm2_step(double acc, float x) {

@@ -35,19 +35,18 @@
 #include "rlap_infonce.h"
 #include "rlap_infonce_api.h"
 #include "rlap_spmm.h"
+#include "rlap_tile32_dev.h"
 
 namespace rlap {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using tile32::f32x16;
 
 constexpr int IN_THREADS = 256;                 // four waves: infonce::BLOCK_TILES owner tiles
 constexpr int64_t IN_MAX_GRID = 1 << 20;        // workgroups of an elementwise launch (the kernels stride)
 static_assert(IN_THREADS == 64 * infonce::BLOCK_TILES, "one wave per owner tile");
 
-inline unsigned in_blocks(int64_t n, int per_block) {
-    return (unsigned)std::min<int64_t>(IN_MAX_GRID, std::max<int64_t>(1, (n + per_block - 1) / per_block));
-}
+inline unsigned in_blocks(int64_t n, int per_block) { return capped_blocks(n, per_block, IN_MAX_GRID); }
 
 // ------------------------------------------------------------------------------------------------ pre-pass
 __global__ __launch_bounds__(256) void k_in_norms(const float* __restrict__ a, const float* __restrict__ b, int64_t N, int64_t F,
@@ -91,22 +90,6 @@ struct Main {
 
 enum { IN_FORWARD = 0, IN_BACK_ANCHOR = 1, IN_BACK_SAMPLE = 2 };
 
-// X[stream row][owner row] of one tile pair: the chain over the padded columns, four MFMAs per 16 bytes of either operand
-__device__ inline f32x16 in_sim_tile(const float4* __restrict__ stream_lds, const float4* __restrict__ owner, int nqq, int lane) {
-    f32x16 x;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) x[r] = 0.0f;
-    for (int qq = 0; qq < nqq; ++qq) {
-        const float4 s = stream_lds[qq * 64 + lane];
-        const float4 o = owner[qq * 64 + lane];
-        x = __builtin_amdgcn_mfma_f32_32x32x2f32(s.x, o.x, x, 0, 0, 0);
-        x = __builtin_amdgcn_mfma_f32_32x32x2f32(s.y, o.y, x, 0, 0, 0);
-        x = __builtin_amdgcn_mfma_f32_32x32x2f32(s.z, o.z, x, 0, 0, 0);
-        x = __builtin_amdgcn_mfma_f32_32x32x2f32(s.w, o.w, x, 0, 0, 0);
-    }
-    return x;
-}
-
 template <int NFT, int MODE>
 __global__ __launch_bounds__(IN_THREADS) void k_in_main(Main a) {
     extern __shared__ __attribute__((aligned(16))) float in_lds[];   // 32 x Fp floats: the stream tile's fragment image; backward: and its row-major image
@@ -125,28 +108,15 @@ __global__ __launch_bounds__(IN_THREADS) void k_in_main(Main a) {
     float rz_lane = 0.0f;
     if (MODE == IN_BACK_ANCHOR && active) rz_lane = a.rz[orow];
     f32x16 acc[NFT];
-    if (MODE != IN_FORWARD) {
-#pragma unroll
-        for (int ft = 0; ft < NFT; ++ft)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[ft][r] = 0.0f;
-    }
+    if (MODE != IN_FORWARD) tile32::zero_tiles(acc);
 
 #pragma unroll 1
     for (int64_t t = tb; t < te; ++t) {
         __syncthreads();   // (the previous tile has been read)
-        {
-            const float4* __restrict__ src = reinterpret_cast<const float4*>(a.str_frag + t * tile_floats);
-            float4* dst = reinterpret_cast<float4*>(in_lds);
-            for (int v = threadIdx.x; v < tile_vec; v += IN_THREADS) dst[v] = src[v];
-            if (MODE != IN_FORWARD) {
-                const float4* __restrict__ src2 = reinterpret_cast<const float4*>(a.str_rows + t * tile_floats);   // (rows 32 t .. 32 t + 31 are contiguous)
-                for (int v = threadIdx.x; v < tile_vec; v += IN_THREADS) dst[tile_vec + v] = src2[v];
-            }
-        }
+        tile32::stage_tile<IN_THREADS>(in_lds, a.str_frag + t * tile_floats, MODE != IN_FORWARD ? a.str_rows + t * tile_floats : nullptr, tile_vec);
         __syncthreads();
         if (!active) continue;
-        f32x16 x = in_sim_tile(reinterpret_cast<const float4*>(in_lds), owner, nqq, lane);
+        f32x16 x = tile32::pair_chain(reinterpret_cast<const float4*>(in_lds), owner, nqq, lane);
         const int64_t srow0 = t * infonce::TILE;
         if (MODE == IN_FORWARD) {
 #pragma unroll
@@ -166,17 +136,7 @@ __global__ __launch_bounds__(IN_THREADS) void k_in_main(Main a) {
                 const float p = infonce::prob(e, rz);
                 x[r] = srow < a.N ? p : 0.0f;
             }
-            const float* brow = in_lds + (int)tile_floats + 4 * h * a.Fp + c;   // row reg_row(r, h) = reg_row(r, 0) + 4 h of the staged tile
-#pragma unroll
-            for (int ft = 0; ft < NFT; ++ft) {
-                if (ft < a.nft) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const float bv = brow[infonce::reg_row(r, 0) * a.Fp + ft * infonce::TILE];
-                        acc[ft] = __builtin_amdgcn_mfma_f32_32x32x2f32(x[r], bv, acc[ft], 0, 0, 0);
-                    }
-                }
-            }
+            tile32::accumulate_tiles(acc, a.nft, x, in_lds + (int)tile_floats, a.Fp, c, h);
         }
     }
 
@@ -185,14 +145,7 @@ __global__ __launch_bounds__(IN_THREADS) void k_in_main(Main a) {
         const double other = __shfl_xor(zsum, 32);
         if (h == 0) a.zpart[part * a.Np + orow] = zsum + other;      // half 0 + half 1
     } else {
-        float* __restrict__ out = a.partial + (part * a.Np + ot * infonce::TILE) * a.Fp + c;
-#pragma unroll
-        for (int ft = 0; ft < NFT; ++ft) {
-            if (ft < a.nft) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) out[(int64_t)infonce::reg_row(r, h) * a.Fp + ft * infonce::TILE] = acc[ft][r];
-            }
-        }
+        tile32::store_tiles(acc, a.nft, a.partial + (part * a.Np + ot * infonce::TILE) * a.Fp, a.Fp, c, h);
     }
 }
 
@@ -208,9 +161,7 @@ __global__ __launch_bounds__(256) void k_in_rows(const double* __restrict__ zpar
 }
 
 __global__ __launch_bounds__(256) void k_in_chunks(const double* __restrict__ rows, int64_t N, double* __restrict__ csum) {
-    const int64_t nc = spmm::num_chunks(N);
-    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < nc; k += (int64_t)gridDim.x * blockDim.x)
-        csum[k] = spmm::chunk_sum(N, k, [](int64_t) { return 1.0; }, [&](int64_t e) { return rows[e]; });
+    tile32::chunk_sums(rows, N, 1, csum);
 }
 
 __global__ void k_in_loss(const double* __restrict__ csum, int64_t N, double* __restrict__ loss) {
@@ -297,8 +248,7 @@ Main main_args(const InfonceArgs& g) {
 template <int NFT, int MODE>
 int launch_main_t(hipStream_t st, const Main& m) {
     const size_t lds = (size_t)infonce::TILE * m.Fp * sizeof(float) * (MODE == IN_FORWARD ? 1 : 2);
-    auto* fn = &k_in_main<NFT, MODE>;
-    RLAP_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (const int rc = tile32::allow_lds(&k_in_main<NFT, MODE>, lds)) return rc;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_in_main<NFT, MODE>), dim3((unsigned)(m.RB * m.parts)), dim3(IN_THREADS), lds, st, m);
     RLAP_HIPCHK(hipGetLastError());
     return RLAP_OK;
@@ -306,14 +256,7 @@ int launch_main_t(hipStream_t st, const Main& m) {
 
 template <int MODE>
 int launch_backward_main(hipStream_t st, const Main& m) {
-    switch (infonce::main_instance(m.nft)) {   // the rule is the header's
-        case 1: return launch_main_t<1, MODE>(st, m);
-        case 2: return launch_main_t<2, MODE>(st, m);
-        case 4: return launch_main_t<4, MODE>(st, m);
-        case 8: return launch_main_t<8, MODE>(st, m);
-        case 16: return launch_main_t<16, MODE>(st, m);
-    }
-    return RLAP_E_INTERNAL;   // (no instance: F outside [1, MAX_F], which the entry point refuses)
+    return tile32::ladder_launch(m.nft, [&](auto nft) { return launch_main_t<decltype(nft)::value, MODE>(st, m); });
 }
 
 int prepass(hipStream_t st, const InfonceArgs& g, const Bufs& B) {

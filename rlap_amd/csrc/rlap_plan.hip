@@ -44,7 +44,7 @@ constexpr int64_t PL_PART_MIN = 4096;                    // chunk sums that alwa
 constexpr int PL_TURN = 4;                               // records of a turn
 enum { CNT_LOOPS = 0, CNT_BLOCKS = 1, CNT_CHUNKED_F = 2, CNT_CHUNKED_T = 3, CNT_WORDS = 4 };
 
-inline unsigned pl_blocks(int64_t n, int bs) { return (unsigned)std::min<int64_t>(PL_MAX_GRID, std::max<int64_t>(1, (n + bs - 1) / bs)); }
+inline unsigned pl_blocks(int64_t n, int bs) { return capped_blocks(n, bs, PL_MAX_GRID); }
 
 __device__ inline int64_t pl_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 

@@ -40,11 +40,14 @@
 
 #include "rlap_infonce.h"
 #include "rlap_spmm.h"
+#include "rlap_tile32.h"
 
 namespace rlap {
 namespace probe {
 
-constexpr int TILE = 32;                  // training rows a workgroup holds at a time
+using tile32::TILE;                       // training rows a workgroup holds at a time: rlap_tile32.h's tile
+using tile32::num_tiles;
+using tile32::padded_rows;
 constexpr int MAX_F = 512;                // feature columns of a call
 constexpr int MAX_C = 64;                 // classes of a call
 constexpr int MIN_CP = 8;                 // the class count is padded to 8, 16, 32 or 64 in the kernels' images
@@ -61,8 +64,6 @@ enum { DETAIL_OK = 0, DETAIL_SHAPE = 1, DETAIL_LIST = 2, DETAIL_PARAM = 3, DETAI
 RLAP_SPMM_HD bool finite_ok(double v) { return v >= -1.7976931348623157e308 && v <= 1.7976931348623157e308; }   // (false for a NaN)
 
 RLAP_SPMM_HD int class_pad(int64_t C) { int p = MIN_CP; while (p < C && p < MAX_C) p *= 2; return p; }
-RLAP_SPMM_HD int64_t num_tiles(int64_t n) { return n > 0 ? (n + TILE - 1) / TILE : 0; }
-RLAP_SPMM_HD int64_t padded_rows(int64_t n) { return num_tiles(n) * TILE; }
 // the row stride of a training image and of the step's tile in LDS, in floats: odd, so that rows fall into different banks
 RLAP_SPMM_HD int64_t image_stride(int64_t F) { return F | 1; }
 

@@ -420,7 +420,7 @@ int launch_score_any(hipStream_t st, const Dev& d, const Runs& t, int64_t max_ti
          : d.CP == 32 ? launch_score<32>(st, d, t, max_tiles, first_set, sets, first) : launch_score<64>(st, d, t, max_tiles, first_set, sets, first);
 }
 
-unsigned pb_blocks(int64_t n) { return (unsigned)std::min<int64_t>(PB_MAX_GRID, std::max<int64_t>(1, (n + PB_THREADS - 1) / PB_THREADS)); }
+unsigned pb_blocks(int64_t n) { return capped_blocks(n, PB_THREADS, PB_MAX_GRID); }
 
 }  // namespace
 

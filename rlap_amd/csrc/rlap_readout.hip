@@ -39,9 +39,7 @@ constexpr int RO_DEPTH = 8;                               // rows in flight (wid
 constexpr int RO_TILE_BYTES = 64 * 16 * RO_R + 64 * 16;   // a wave's pieces: 64 lanes x 16 bytes x RO_R rows, one unit of padding a chunk
 constexpr int64_t RO_MAX_GRID = 8192;                     // workgroups of a launch (the kernels stride over their items)
 
-inline unsigned ro_blocks(int64_t n, int per_block) {
-    return (unsigned)std::min<int64_t>(RO_MAX_GRID, std::max<int64_t>(1, (n + per_block - 1) / per_block));
-}
+inline unsigned ro_blocks(int64_t n, int per_block) { return capped_blocks(n, per_block, RO_MAX_GRID); }
 
 // what the kernels share
 struct Ro {

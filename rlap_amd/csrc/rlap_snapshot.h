@@ -36,6 +36,8 @@ struct Carve {
 };
 
 inline unsigned grid_blocks(int64_t n, int bs) { return (unsigned)std::max<int64_t>(1, (n + bs - 1) / bs); }
+// the same, at most max_grid workgroups: for kernels that stride over their items
+inline unsigned capped_blocks(int64_t n, int per_block, int64_t max_grid) { return (unsigned)std::min<int64_t>(max_grid, grid_blocks(n, per_block)); }
 
 // last s in [0, S) with tab[s] <= r (S >= 1): the segment of row r; equal offsets (empty segments) are skipped
 __device__ inline int64_t seg_of(const int64_t* __restrict__ tab, int64_t S, int64_t r) {

@@ -43,7 +43,7 @@ constexpr int64_t SP_PART_MIN = 4096;                    // chunk sums that alwa
 enum { CNT_LOOPS = 0, CNT_CHUNKED = 1, CNT_BLOCKS = 2, CNT_WORDS = 4 };
 
 // (its own grid helper: the cap is applied to the 64-bit count, before it is narrowed)
-inline unsigned sp_blocks(int64_t n, int bs) { return (unsigned)std::min<int64_t>(SP_MAX_GRID, std::max<int64_t>(1, (n + bs - 1) / bs)); }
+inline unsigned sp_blocks(int64_t n, int bs) { return capped_blocks(n, bs, SP_MAX_GRID); }
 
 // what the kernels share (ptr is the checked copy)
 struct Sp {

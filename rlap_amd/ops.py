@@ -610,6 +610,29 @@ def _snapshot_call(export: str, info_cls, x: Tensor, p: Tensor, np_: Optional[Te
     return info
 
 
+def _device_call(export: str, info_cls, dev, G: int, tail: tuple):
+    """The call of the readout, the fused losses and the probe: the C export `export` on the library's device `dev` with the
+    arguments `tail` behind the handle and an `info_cls` for its report.  Statuses 1, 2, 3 raise ValueError (with the report's
+    `detail`, where it has one), the others RuntimeError.  Sets `last_stats` and returns the info struct."""
+    global last_stats
+    lib, hobj = _handle_obj(dev)
+    fn = getattr(lib, export)
+    info = info_cls()
+    st = _lib.Stats()
+    rc = _run(hobj, dev, 0, None, G, False, lambda: fn(hobj.ptr, *tail, ctypes.byref(info)), st)
+    if rc in (1, 2, 3):
+        raise ValueError(f"rlap: {_lib.status_string(rc)}" + (f" (detail {info.detail})" if hasattr(info, "detail") else ""))
+    if rc != 0:
+        _raise(rc)
+    last_stats = info.as_dict()
+    return info
+
+
+def _upstream(g: Tensor, dev) -> Tensor:
+    """The upstream gradient of a scalar loss as the backward exports read it: one float64 on the library's device."""
+    return g.detach().to(device=dev, dtype=torch.float64).reshape(1).contiguous()
+
+
 def snapshot_stats(
     sc: Tensor,
     ptr: Union[Tensor, Sequence[int]],
@@ -1102,6 +1125,15 @@ class GraphTable:
         return self._dev[key]
 
 
+def _graph_table(node_ptr, n: int) -> GraphTable:
+    """The GraphTable of a call on n nodes: the caller's own, checked against n, or one made from its node_ptr."""
+    if not isinstance(node_ptr, GraphTable):
+        return GraphTable(node_ptr, n)
+    if node_ptr.num_nodes != n:
+        raise ValueError(f"node_ptr[-1] ({node_ptr.num_nodes}) must equal {n}")
+    return node_ptr
+
+
 def _readout_args(x, node_ptr, reduce):
     """Host-side checks of graph_readout, made before the device is touched: (table, flags without the type)."""
     if not isinstance(x, Tensor) or x.dim() not in (2, 3):
@@ -1112,38 +1144,19 @@ def _readout_args(x, node_ptr, reduce):
         raise ValueError("x: at least one feature column")
     if not isinstance(reduce, str) or reduce not in READOUT_REDUCE:
         raise ValueError(f"reduce: one of {sorted(READOUT_REDUCE)}, got {reduce!r}")
-    n = int(x.shape[-2])
-    if isinstance(node_ptr, GraphTable):
-        if node_ptr.num_nodes != n:
-            raise ValueError(f"node_ptr[-1] ({node_ptr.num_nodes}) must equal {n}")
-        table = node_ptr
-    else:
-        table = GraphTable(node_ptr, n)
-    return table, READOUT_REDUCE[reduce]
+    return _graph_table(node_ptr, int(x.shape[-2])), READOUT_REDUCE[reduce]
 
 
 def _readout(export: str, x: Tensor, table: GraphTable, flags: int, rows_out: int) -> Tensor:
     """One rlap_graph_readout / _backward call: x is (L, rows, F) and checked, the result (L, rows_out, F) on the library's device."""
-    global last_stats
     dev = _device_for(x)
     flags |= _lib.READOUT_X_F32 if x.dtype == torch.float32 else 0
     with torch.cuda.device(dev):
         d_x = x.detach().to(device=dev).contiguous()
         L, F, N, G = int(d_x.shape[0]), int(d_x.shape[2]), table.num_nodes, table.graphs
         out = torch.empty((L, rows_out, F), dtype=d_x.dtype, device=dev)
-        d_np = table.on(dev)
-        lib, hobj = _handle_obj(dev)
-        fn = getattr(lib, export)
-        info = _lib.ReadoutInfo()
-        st = _lib.Stats()
-        rc = _run(hobj, dev, 0, None, G, False, lambda: fn(
-            hobj.ptr, d_x.data_ptr() if d_x.numel() else None, L, N, F, d_np.data_ptr(), G, flags,
-            out.data_ptr() if out.numel() else None, ctypes.byref(info)), st)
-    if rc in (1, 2, 3):
-        raise ValueError(f"rlap: {_lib.status_string(rc)}")
-    if rc != 0:
-        _raise(rc)
-    last_stats = info.as_dict()
+        _device_call(export, _lib.ReadoutInfo, dev, G, (
+            d_x.data_ptr() if d_x.numel() else None, L, N, F, table.on(dev).data_ptr(), G, flags, out.data_ptr() if out.numel() else None))
     last_stats.update(chunks=table.chunks, chunked_graphs=table.chunked_graphs)   # (exact: this host has read the table)
     return out
 
@@ -1222,21 +1235,6 @@ def _info_nce_args(anchor, sample, tau, positive):
     return tau, INFONCE_POSITIVE[positive]
 
 
-def _info_nce_call(export: str, dev, tail):
-    """One rlap_infonce / _backward call on the library's device: tail(info) gives the arguments behind the handle."""
-    global last_stats
-    lib, hobj = _handle_obj(dev)
-    fn = getattr(lib, export)
-    info = _lib.InfonceInfo()
-    st = _lib.Stats()
-    rc = _run(hobj, dev, 0, None, 1, False, lambda: fn(hobj.ptr, *tail, ctypes.byref(info)), st)
-    if rc in (1, 2, 3):
-        raise ValueError(f"rlap: {_lib.status_string(rc)}")
-    if rc != 0:
-        _raise(rc)
-    last_stats = info.as_dict()
-
-
 def _info_nce_forward(a: Tensor, b: Tensor, tau: float, flags: int):
     """The forward export: (loss 0-dim, rows [N], z [N], the device copies of a and b)."""
     dev = _device_for(a)
@@ -1246,7 +1244,7 @@ def _info_nce_forward(a: Tensor, b: Tensor, tau: float, flags: int):
         n, f = int(d_a.shape[0]), int(d_a.shape[1])
         out = torch.empty(1 + 2 * n, dtype=torch.float64, device=dev)   # loss | rows | z
         p = out.data_ptr()
-        _info_nce_call("rlap_infonce", dev, (d_a.data_ptr(), d_b.data_ptr(), n, f, tau, flags, p, p + 8, p + 8 * (1 + n)))
+        _device_call("rlap_infonce", _lib.InfonceInfo, dev, 1, (d_a.data_ptr(), d_b.data_ptr(), n, f, tau, flags, p, p + 8, p + 8 * (1 + n)))
     return out[0], out[1:1 + n], out[1 + n:], d_a, d_b
 
 
@@ -1268,12 +1266,12 @@ class _InfoNCE(torch.autograd.Function):
         tau, flags, dev_a, dev_b = ctx.call
         dev = d_a.device
         with torch.cuda.device(dev):
-            d_g = g.detach().to(device=dev, dtype=torch.float64).reshape(1).contiguous()
+            d_g = _upstream(g, dev)
             n, f = int(d_a.shape[0]), int(d_a.shape[1])
             ga = torch.empty_like(d_a)
             gb = torch.empty_like(d_b)
-            _info_nce_call("rlap_infonce_backward", dev, (d_a.data_ptr(), d_b.data_ptr(), n, f, tau, flags, z.data_ptr(), d_g.data_ptr(),
-                                                             ga.data_ptr(), gb.data_ptr()))
+            _device_call("rlap_infonce_backward", _lib.InfonceInfo, dev, 1, (
+                d_a.data_ptr(), d_b.data_ptr(), n, f, tau, flags, z.data_ptr(), d_g.data_ptr(), ga.data_ptr(), gb.data_ptr()))
         return ga.to(dev_a), gb.to(dev_b), None, None
 
 
@@ -1334,21 +1332,6 @@ def _cca_args(h1, h2, lambd):
     return lambd
 
 
-def _cca_call(export: str, dev, tail):
-    """One rlap_cca_loss / _backward call on the library's device: the arguments behind the handle."""
-    global last_stats
-    lib, hobj = _handle_obj(dev)
-    fn = getattr(lib, export)
-    info = _lib.CcaInfo()
-    st = _lib.Stats()
-    rc = _run(hobj, dev, 0, None, 1, False, lambda: fn(hobj.ptr, *tail, ctypes.byref(info)), st)
-    if rc in (1, 2, 3):
-        raise ValueError(f"rlap: {_lib.status_string(rc)}")
-    if rc != 0:
-        _raise(rc)
-    last_stats = info.as_dict()
-
-
 def _cca_forward(a: Tensor, b: Tensor, lambd: float):
     """The forward export: (terms [4] float64: loss, inv, dec1, dec2; colstat [4 F] float64; gram [2, F, F] float32; the device
     copies of a and b)."""
@@ -1360,7 +1343,7 @@ def _cca_forward(a: Tensor, b: Tensor, lambd: float):
         out = torch.empty(4 + 4 * f, dtype=torch.float64, device=dev)   # terms | colstat
         gram = torch.empty((2, f, f), dtype=torch.float32, device=dev)
         p = out.data_ptr()
-        _cca_call("rlap_cca_loss", dev, (d_a.data_ptr(), d_b.data_ptr(), n, f, lambd, 0, p, p + 32, gram.data_ptr()))
+        _device_call("rlap_cca_loss", _lib.CcaInfo, dev, 1, (d_a.data_ptr(), d_b.data_ptr(), n, f, lambd, 0, p, p + 32, gram.data_ptr()))
     return out[:4], out[4:], gram, d_a, d_b
 
 
@@ -1384,12 +1367,12 @@ class _CcaLoss(torch.autograd.Function):
         lambd, dev_a, dev_b = ctx.call
         dev = d_a.device
         with torch.cuda.device(dev):
-            d_g = g.detach().to(device=dev, dtype=torch.float64).reshape(1).contiguous()
+            d_g = _upstream(g, dev)
             n, f = int(d_a.shape[0]), int(d_a.shape[1])
             ga = torch.empty_like(d_a)
             gb = torch.empty_like(d_b)
-            _cca_call("rlap_cca_loss_backward", dev, (d_a.data_ptr(), d_b.data_ptr(), n, f, lambd, 0, colstat.data_ptr(), gram.data_ptr(),
-                                                      d_g.data_ptr(), ga.data_ptr(), gb.data_ptr()))
+            _device_call("rlap_cca_loss_backward", _lib.CcaInfo, dev, 1, (
+                d_a.data_ptr(), d_b.data_ptr(), n, f, lambd, 0, colstat.data_ptr(), gram.data_ptr(), d_g.data_ptr(), ga.data_ptr(), gb.data_ptr()))
         return ga.to(dev_a), gb.to(dev_b), None
 
 
@@ -1445,13 +1428,8 @@ def _g2l_args(h, g, node_ptr, neg, what_neg: bool):
     if node_ptr is None:
         if G != 1:
             raise ValueError(f"node_ptr: required for g of {G} graphs (the default [0, N] is one graph)")
-        table = GraphTable([0, n], n)
-    elif isinstance(node_ptr, GraphTable):
-        if node_ptr.num_nodes != n:
-            raise ValueError(f"node_ptr[-1] ({node_ptr.num_nodes}) must equal {n}")
-        table = node_ptr
-    else:
-        table = GraphTable(node_ptr, n)
+        node_ptr = [0, n]
+    table = _graph_table(node_ptr, n)
     if table.graphs != G:
         raise ValueError(f"node_ptr: {table.graphs} graphs, g has {G} rows")
     if what_neg:
@@ -1460,21 +1438,6 @@ def _g2l_args(h, g, node_ptr, neg, what_neg: bool):
         if G >= 2 and neg is not None:
             raise ValueError("neg: only for one graph (with several, the other graphs' summaries are the negatives)")
     return table
-
-
-def _g2l_call(export: str, dev, G: int, tail):
-    """One rlap_g2l_* call on the library's device: the arguments behind the handle."""
-    global last_stats
-    lib, hobj = _handle_obj(dev)
-    fn = getattr(lib, export)
-    info = _lib.G2lInfo()
-    st = _lib.Stats()
-    rc = _run(hobj, dev, 0, None, G, False, lambda: fn(hobj.ptr, *tail, ctypes.byref(info)), st)
-    if rc in (1, 2, 3):
-        raise ValueError(f"rlap: {_lib.status_string(rc)}")
-    if rc != 0:
-        _raise(rc)
-    last_stats = info.as_dict()
 
 
 def _g2l_jsd_forward(h: Tensor, g: Tensor, neg: Optional[Tensor], table: GraphTable):
@@ -1487,8 +1450,8 @@ def _g2l_jsd_forward(h: Tensor, g: Tensor, neg: Optional[Tensor], table: GraphTa
         n, f = int(d_h.shape[0]), int(d_h.shape[1])
         out = torch.empty(1 + 2 * n, dtype=torch.float64, device=dev)   # loss | pos | neg
         p = out.data_ptr()
-        _g2l_call("rlap_g2l_jsd", dev, table.graphs, (d_h.data_ptr(), d_n.data_ptr() if d_n is not None else None, d_g.data_ptr(), n, f,
-                                                      table.on(dev).data_ptr(), table.graphs, 0, p, p + 8))
+        _device_call("rlap_g2l_jsd", _lib.G2lInfo, dev, table.graphs, (
+            d_h.data_ptr(), d_n.data_ptr() if d_n is not None else None, d_g.data_ptr(), n, f, table.on(dev).data_ptr(), table.graphs, 0, p, p + 8))
     return out[0], out[1:].view(2, n), d_h, d_g, d_n
 
 
@@ -1512,11 +1475,11 @@ class _G2lJsd(torch.autograd.Function):
         table, dev_h, dev_g, dev_n = ctx.call
         dev = d_h.device
         with torch.cuda.device(dev):
-            d_up = gup.detach().to(device=dev, dtype=torch.float64).reshape(1).contiguous()
+            d_up = _upstream(gup, dev)
             n, f = int(d_h.shape[0]), int(d_h.shape[1])
             gh, gg = torch.empty_like(d_h), torch.empty_like(d_g)
             gn = torch.empty_like(d_n) if d_n is not None else None
-            _g2l_call("rlap_g2l_jsd_backward", dev, table.graphs, (
+            _device_call("rlap_g2l_jsd_backward", _lib.G2lInfo, dev, table.graphs, (
                 d_h.data_ptr(), d_n.data_ptr() if d_n is not None else None, d_g.data_ptr(), n, f, table.on(dev).data_ptr(), table.graphs, 0,
                 d_up.data_ptr(), gh.data_ptr(), gn.data_ptr() if gn is not None else None, gg.data_ptr()))
         return gh.to(dev_h), gg.to(dev_g), gn.to(dev_n) if gn is not None else None, None
@@ -1562,7 +1525,8 @@ def _g2l_bootstrap_forward(h: Tensor, g: Tensor, table: GraphTable):
         n, f = int(d_h.shape[0]), int(d_h.shape[1])
         out = torch.empty(1 + n, dtype=torch.float64, device=dev)   # loss | c
         p = out.data_ptr()
-        _g2l_call("rlap_g2l_bootstrap", dev, table.graphs, (d_h.data_ptr(), d_g.data_ptr(), n, f, table.on(dev).data_ptr(), table.graphs, 0, p, p + 8))
+        _device_call("rlap_g2l_bootstrap", _lib.G2lInfo, dev, table.graphs, (
+            d_h.data_ptr(), d_g.data_ptr(), n, f, table.on(dev).data_ptr(), table.graphs, 0, p, p + 8))
     return out[0], out[1:], d_h, d_g
 
 
@@ -1585,11 +1549,11 @@ class _G2lBootstrap(torch.autograd.Function):
         table, dev_h = ctx.call
         dev = d_h.device
         with torch.cuda.device(dev):
-            d_up = gup.detach().to(device=dev, dtype=torch.float64).reshape(1).contiguous()
+            d_up = _upstream(gup, dev)
             n, f = int(d_h.shape[0]), int(d_h.shape[1])
             gh = torch.empty_like(d_h)
-            _g2l_call("rlap_g2l_bootstrap_backward", dev, table.graphs, (d_h.data_ptr(), d_g.data_ptr(), n, f, table.on(dev).data_ptr(), table.graphs, 0,
-                                                                         d_up.data_ptr(), gh.data_ptr()))
+            _device_call("rlap_g2l_bootstrap_backward", _lib.G2lInfo, dev, table.graphs, (
+                d_h.data_ptr(), d_g.data_ptr(), n, f, table.on(dev).data_ptr(), table.graphs, 0, d_up.data_ptr(), gh.data_ptr()))
         return gh.to(dev_h), None, None
 
 
@@ -1687,21 +1651,6 @@ def _probe_x(x: Tensor, dev) -> Tuple[Tensor, int]:
     return d_x, (int(d_x.stride(0)) if n > 1 else f)
 
 
-def _probe_call(export: str, dev, args):
-    """One rlap_linear_probe / rlap_probe_scores call on the library's device: the arguments behind the handle."""
-    global last_stats
-    lib, hobj = _handle_obj(dev)
-    fn = getattr(lib, export)
-    info = _lib.ProbeInfo()
-    st = _lib.Stats()
-    rc = _run(hobj, dev, 0, None, 1, False, lambda: fn(hobj.ptr, *args, ctypes.byref(info)), st)
-    if rc in (1, 2, 3):
-        raise ValueError(f"rlap: {_lib.status_string(rc)} (detail {info.detail})")
-    if rc != 0:
-        _raise(rc)
-    last_stats = info.as_dict()
-
-
 def probe_init(num_runs: int, num_classes: int, num_features: int, generator=None) -> Tuple[Tensor, Tensor]:
     """The initial parameters of `num_runs` probes as the reference draws them (scripts/node_shared.py:152-156), on the host:
     nn.Linear's default draws (a weight that is thrown away, the bias in U(-1/sqrt(F), 1/sqrt(F))) and then xavier_uniform_ for the
@@ -1783,7 +1732,7 @@ def linear_probe(x: Tensor, y: Tensor, train, valid, test, num_classes: Optional
         best = torch.empty((r, 2), dtype=torch.int64, device=dev)
         conf = torch.empty((r, 2, c, c), dtype=torch.int64, device=dev)
         status = torch.empty(1, dtype=torch.int32, device=dev)
-        _probe_call("rlap_linear_probe", dev, (
+        _device_call("rlap_linear_probe", _lib.ProbeInfo, dev, 1, (
             d_x.data_ptr(), n, f, ldx, d_y.data_ptr(), c, r, d_l[0].data_ptr(), h_p[0], d_l[1].data_ptr(), h_p[1], d_l[2].data_ptr(), h_p[2],
             epochs, lr, weight_decay, test_interval, PROBE_SELECT[select], b1, b2, eps, w0.data_ptr(), b0.data_ptr(), w.data_ptr(),
             b.data_ptr(), scores.data_ptr(), best.data_ptr(), conf.data_ptr(), status.data_ptr()))
@@ -1823,8 +1772,9 @@ def probe_scores(x: Tensor, y: Tensor, index, weight: Tensor, bias: Tensor) -> d
         conf = torch.empty((r, c, c), dtype=torch.int64, device=dev)
         scores = torch.empty((r, 3), dtype=torch.float64, device=dev)
         status = torch.empty(1, dtype=torch.int32, device=dev)
-        _probe_call("rlap_probe_scores", dev, (d_x.data_ptr(), n, f, ldx, d_y.data_ptr(), c, r, d_i.data_ptr(), h_p, d_w.data_ptr(),
-                                               d_b.data_ptr(), pred.data_ptr(), conf.data_ptr(), scores.data_ptr(), status.data_ptr()))
+        _device_call("rlap_probe_scores", _lib.ProbeInfo, dev, 1, (
+            d_x.data_ptr(), n, f, ldx, d_y.data_ptr(), c, r, d_i.data_ptr(), h_p, d_w.data_ptr(), d_b.data_ptr(), pred.data_ptr(), conf.data_ptr(),
+            scores.data_ptr(), status.data_ptr()))
     return {"pred": pred, "confusion": conf, "micro_f1": scores[:, 0], "macro_f1": scores[:, 1], "accuracy": scores[:, 2], "status": status}
 
 

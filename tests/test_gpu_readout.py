@@ -193,6 +193,8 @@ def test_same_bits_however_it_is_called(ops, features, name, F, dtype):
         ops.debug_set_poison(0xA5)
         try:
             assert same_bits(y, ops.graph_readout(x, node_ptr, reduce=reduce))                              # whatever the arena and y held
+            xg = x.clone().requires_grad_(True)                                                             # the gather, whatever gx held
+            assert same_bits(torch.autograd.grad(ops.graph_readout(xg, node_ptr).sum(), xg)[0], torch.ones_like(x))
         finally:
             ops.debug_set_poison(-1)
 
