@@ -1044,6 +1044,13 @@ RLAP_HD void cand_replay_pre(const Arrays& A, const CT& C, int32_t j, int* cnt, 
     }
     *cnt = c; *last_inc = li;
 }
+// Does a candidate with m neighbours touch its target at position j, given the c pushes cand_replay_pre counted for it?  Where
+// this is false cand_replay_post returns key0 with no move and nothing is pushed into the target's column: the pair needs no key,
+// no place among the round's shared targets and no order against other candidates (its twin slot is rewritten in place at commit).
+RLAP_HD bool cand_touches(int o_v, int32_t m, int32_t j, int32_t koff, int c) {
+    if (o_v == OV_COARSEN) return j == koff;     // :880-896: the chosen neighbour takes every push and the Dec
+    return c > 0 || j == m - 1;                  // :399 Inc per pick; :427 Dec of the last neighbour
+}
 // ... and the key arithmetic on top of it (a target shared by several candidates chains it through their records)
 template <class CT>
 RLAP_HD int32_t cand_replay_post(const Arrays& A, const CT& C, int32_t j, int32_t key0, int32_t n, bool allow_last_dec,

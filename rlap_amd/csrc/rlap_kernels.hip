@@ -1611,6 +1611,10 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
     // order (C3 369 -> 274 ms); with o_v = random (64-slot candidates; wave_patch handles them too) the rounds of config 5 get 6.5 %
     // fewer and no faster, and the coarsening order fills its rounds without it -- so only the degree order uses it.
     constexpr bool PATCH = (OV == OV_DEGREE);
+    // the replay (P4) sees only the (candidate, target) pairs rlap_core.h::cand_touches passes: about half of a degree-order
+    // candidate's pairs name a target nobody picked, which keeps its key and gets nothing appended.  The PQ orders (16 and 32 slots)
+    // take the rule; o_v = random (64 and 128 slots) has no keys to replay and finds its picks with ballots: it keeps every pair.
+    constexpr bool SKIP = (BC <= 32);
     constexpr int GSH = BC >= 64 ? 0 : 64 - BC;                   // lane & GSH = first lane of my group
     constexpr uint64_t GMASK = BC >= 64 ? ~0ull : ((1ull << (BC & 63)) - 1ull);   // a group's part of a 64-bit ballot
     Arrays A = A_in;
@@ -2294,6 +2298,18 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
                 if constexpr (NARROW) tck[k] = -1;
                 if (i >= Pmax) continue;
                 if (j < L.cand[i].m) {
+                    if constexpr (SKIP) {
+                        // the key-independent half of the replay first: it says whether this pair touches its target at all.  Parked in
+                        // the pair's record (not kept in registers across the barrier); an untouched pair is done here -- no key, no
+                        // place in the table -- and its record reads "nothing happens" to the commit
+                        Cand& C = L.cand[i];
+                        int c0, li0;
+                        cand_replay_pre(A, C, j, &c0, &li0);
+                        TRes& R = ent_tres(C.e[j]);
+                        R.key_after = 0; R.flags = 0;
+                        if (!cand_touches(OV, C.m, j, C.koff, c0)) { R.c = 0; R.mv = -1; continue; }
+                        R.c = (uint8_t)c0; R.mv = (int16_t)li0;
+                    }
                     const int32_t x = L.cand[i].e[j].nbr;
                     if (use_pq) key0k[k] = A.vr[x].key;
                     uint32_t hh = ((uint32_t)x * 2654435761u) >> (32 - HBITS);
@@ -2349,8 +2365,12 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
                     pm = group_pick_mask<BC <= 64 ? BC : 64>(L.cand[cok ? i : 0].ksel, cok ? L.cand[i].m : 0, cok, lane);
                 }
                 if (i >= Pmax) continue;
+                if constexpr (NARROW) { if (tck[k] == 0) continue; }   // no such position, or an untouched pair: its count was never taken
                 Cand& C = L.cand[i];
                 if (j >= C.m) continue;
+                TRes& R = ent_tres(C.e[j]);
+                // an untouched pair is not in the table (the look-up below would never end for it): before anything else
+                if constexpr (SKIP && !NARROW) { if (!cand_touches(OV, C.m, j, C.koff, (int)R.c)) continue; }
                 const int32_t x = C.e[j].nbr;
                 int32_t tc;
                 if constexpr (NARROW) tc = tck[k];
@@ -2360,13 +2380,15 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
                     tc = hcnt[hh];
                 }
                 const int32_t key0 = key0k[k];
-                TRes& R = ent_tres(C.e[j]);
                 if (tc > 1) {
-                    // the key-independent half of the replay now, in parallel; the walk below chains the keys
-                    int c0, li0;
-                    if constexpr (GROUPED) { c0 = __popcll(pm); li0 = pm ? 63 - __builtin_clzll(pm) : -1; }
-                    else cand_replay_pre(A, C, j, &c0, &li0);
-                    R.flags = TF_CONTENDED; R.mv = (int16_t)li0; R.c = (uint8_t)c0; R.key_after = 0;
+                    // the key-independent half of the replay is done (P4.1, or here, in parallel); the walk below chains the keys
+                    if constexpr (SKIP) R.flags = TF_CONTENDED;
+                    else {
+                        int c0, li0;
+                        if constexpr (GROUPED) { c0 = __popcll(pm); li0 = pm ? 63 - __builtin_clzll(pm) : -1; }
+                        else cand_replay_pre(A, C, j, &c0, &li0);
+                        R.flags = TF_CONTENDED; R.mv = (int16_t)li0; R.c = (uint8_t)c0; R.key_after = 0;
+                    }
                     int32_t q;
                     if constexpr (NARROW) q = crec++; else q = atomicAdd(&s_ncont, 1);
                     if (q < CCAP) { L.cont[q].x = x; L.cont[q].i = i; L.cont[q].j = j; }
@@ -2379,6 +2401,9 @@ __global__ __launch_bounds__(NTT, (NTT >= 1024 ? 1 : 4)) void k_eliminate_batch_
                 if constexpr (GROUPED) {
                     c = __popcll(pm);
                     k2 = cand_replay_post(A, C, j, key0, use_pq ? n : 0x7FFFFFFF, allow_last, c, pm ? 63 - __builtin_clzll(pm) : -1, &mv, &cx);
+                } else if constexpr (SKIP) {
+                    c = (int)R.c;
+                    k2 = cand_replay_post(A, C, j, key0, use_pq ? n : 0x7FFFFFFF, allow_last, c, (int)R.mv, &mv, &cx);
                 } else k2 = cand_replay(A, C, j, key0, use_pq ? n : 0x7FFFFFFF, allow_last, &mv, &c, &cx);
                 if (!use_pq) { mv = -1; cx = false; }
                 R.key_after = k2; R.mv = (int16_t)mv; R.c = (uint8_t)c; R.flags = 0;
