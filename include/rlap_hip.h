@@ -564,6 +564,34 @@ int rlap_infonce(rlap_handle h, const float* d_a, const float* d_b, int64_t N, i
 int rlap_infonce_backward(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double tau, int flags,
                           const double* d_z, const double* d_g, float* d_ga, float* d_gb, rlap_infonce_info* h_info);
 
+/* The symmetric pair of the above: loss = 0.5 * (l(a, b) + l(b, a)), what DualBranchContrast(...) computes for both
+ * directions, from ONE pass over the similarities: s(b, a) is the transpose of s(a, b) bit for bit, so the row sums Z_i (the
+ * denominators of the first direction) and the column sums Zc_j (of the second) come from the same tiles, and the backward call folds
+ * both directions into one weight e_ij (1 / Z_i + 1 / Zc_j): five N x N x F products a step where two calls of each of the above make ten.
+ *   arguments      : as rlap_infonce / rlap_infonce_backward, except
+ *   d_rows         : [2, N] doubles: c s_ii - 1/tau - log Z_i, then c s_jj - 1/tau - log Zc_j
+ *   d_z            : [2, N] doubles: Z, then Zc; the backward call reads both
+ *   d_ga, d_gb     : the gradients of the pair's loss with respect to d_a and d_b
+ * The rule is rlap_amd/csrc/rlap_infonce.h's: Z_i as in rlap_infonce over a split of the column tiles of its own; Zc_j in float64 in
+ * an order that depends on N alone (groups of row blocks, row blocks, the four 32-row tiles of a block, a stated tree over a tile's 32
+ * rows).  The same input gives the same bits, whatever the arena held; no atomic touches a floating-point value; neither call
+ * synchronises with the host; memory is O(N F).  The loss equals 0.5 * (rlap_infonce(a, b) + rlap_infonce(b, a)) up to the order of
+ * the sums.  The refusals and statuses are rlap_infonce's. */
+typedef struct {
+    int64_t rows;             /* N                                                                    */
+    int64_t features;         /* F                                                                    */
+    int64_t arena_bytes;      /* scratch bytes of the call                                            */
+    int64_t parts;            /* contiguous parts of the column tiles (forward): a function of N      */
+    int64_t groups;           /* contiguous groups of the 128-row blocks (forward): a function of N   */
+    int32_t host_syncs;       /* host synchronisations of the call: 0                                 */
+    int32_t pad;
+} rlap_infonce_pair_info;
+
+int rlap_infonce_pair(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double tau, int flags, double* d_loss,
+                      double* d_rows, double* d_z, rlap_infonce_pair_info* h_info);
+int rlap_infonce_pair_backward(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double tau, int flags,
+                               const double* d_z, const double* d_g, float* d_ga, float* d_gb, rlap_infonce_pair_info* h_info);
+
 /* The fused CCA-SSG loss of two views' node embeddings, forward and backward: the standardisation of
  * CCA-SSG/model.py and the loss of CCA-SSG/main.py.  With z = (h - mean_0(h)) / std_0(h) (unbiased), c = z1^T z2 / N,
  * c1 = z1^T z1 / N and c2 = z2^T z2 / N:  loss = -trace(c) + lambd * (||I - c1||_F^2 + ||I - c2||_F^2).

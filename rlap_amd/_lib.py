@@ -23,6 +23,7 @@ EXPORTS = [
     "rlap_snapshot_gcn_norm", "rlap_snapshot_propagate",
     "rlap_snapshot_plan_bytes", "rlap_snapshot_plan_build", "rlap_snapshot_plan_propagate", "rlap_edge_plan_build",
     "rlap_graph_readout", "rlap_graph_readout_backward", "rlap_infonce", "rlap_infonce_backward",
+    "rlap_infonce_pair", "rlap_infonce_pair_backward",
     "rlap_cca_loss", "rlap_cca_loss_backward",
     "rlap_g2l_jsd", "rlap_g2l_jsd_backward", "rlap_g2l_bootstrap", "rlap_g2l_bootstrap_backward",
     "rlap_linear_probe", "rlap_probe_scores",
@@ -159,6 +160,14 @@ class InfonceInfo(_Report):
     ]
 
 
+class InfoncePairInfo(_Report):
+    """rlap_infonce_pair_info (include/rlap_hip.h)."""
+    _fields_ = [
+        ("rows", ctypes.c_int64), ("features", ctypes.c_int64), ("arena_bytes", ctypes.c_int64), ("parts", ctypes.c_int64),
+        ("groups", ctypes.c_int64), ("host_syncs", ctypes.c_int32), ("pad", ctypes.c_int32),
+    ]
+
+
 class CcaInfo(_Report):
     """rlap_cca_info (include/rlap_hip.h)."""
     _fields_ = [
@@ -251,6 +260,10 @@ def load():
     lib.rlap_infonce.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ci, vp, vp, vp, ctypes.POINTER(InfonceInfo)]
     lib.rlap_infonce_backward.restype = ci
     lib.rlap_infonce_backward.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ci, vp, vp, vp, vp, ctypes.POINTER(InfonceInfo)]
+    lib.rlap_infonce_pair.restype = ci
+    lib.rlap_infonce_pair.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ci, vp, vp, vp, ctypes.POINTER(InfoncePairInfo)]
+    lib.rlap_infonce_pair_backward.restype = ci
+    lib.rlap_infonce_pair_backward.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ci, vp, vp, vp, vp, ctypes.POINTER(InfoncePairInfo)]
     lib.rlap_cca_loss.restype = ci
     lib.rlap_cca_loss.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ci, vp, vp, vp, ctypes.POINTER(CcaInfo)]
     lib.rlap_cca_loss_backward.restype = ci

@@ -223,17 +223,21 @@ class NodeContrast(torch.nn.Module):
     (no N x N matrix, fixed summation order, memory O(N F)).  h1, h2 are (N, F) float32 embeddings of two views; given one
     (L, N, F) tensor of L >= 2 views, as SnapshotGCNConv returns it, forward(h) contrasts view 0 with view 1.  `positive="raw"`
     (the default) restates the reference's InfoNCEBatched, whose positive term s_ii is not divided by tau; "scaled" is GCL's
-    InfoNCE.  The loss is a 0-dim float64 tensor; gradients reach both views."""
+    InfoNCE.  The loss is a 0-dim float64 tensor; gradients reach both views.  `pair=True` computes the same loss by one
+    ops.info_nce_pair call -- both directions from one pass over the similarities, half the products -- whose value differs from the
+    two calls' in the order of the sums alone."""
 
-    def __init__(self, tau: float = 0.4, positive: str = "raw"):
+    def __init__(self, tau: float = 0.4, positive: str = "raw", pair: bool = False):
         super().__init__()
-        self.tau, self.positive = tau, positive
+        self.tau, self.positive, self.pair = tau, positive, bool(pair)
 
     def forward(self, h1, h2=None):
         if h2 is None:
             if not isinstance(h1, torch.Tensor) or h1.dim() != 3 or h1.shape[0] < 2:
                 raise ValueError("NodeContrast: two (N, F) embeddings, or one (L, N, F) tensor of L >= 2 views")
             h1, h2 = h1[0], h1[1]
+        if self.pair:
+            return ops.info_nce_pair(h1, h2, tau=self.tau, positive=self.positive)
         l1 = ops.info_nce(h1, h2, tau=self.tau, positive=self.positive)
         l2 = ops.info_nce(h2, h1, tau=self.tau, positive=self.positive)
         return 0.5 * (l1 + l2)

@@ -1652,6 +1652,31 @@ int rlap_infonce_backward(rlap_handle h, const float* d_a, const float* d_b, int
                          h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) { return infonce_backward_run(h->stream, base, have, a); });
 }
 
+// the symmetric pair: the checks of rlap_infonce, its own info structure
+int rlap_infonce_pair(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double tau, int flags, double* d_loss,
+                      double* d_rows, double* d_z, rlap_infonce_pair_info* h_info) {
+    if (h_info) *h_info = rlap_infonce_pair_info{};
+    if (const int rc = infonce_check(h, d_a, d_b, N, F, tau, flags, nullptr)) return rc;
+    if (h_info) { h_info->rows = N; h_info->features = F; h_info->parts = infonce::pair_parts(N); h_info->groups = infonce::pair_groups(N); }
+    if (!d_loss || !d_rows || !d_z) return RLAP_E_BAD_ARG;
+    InfonceArgs a{};
+    a.a = d_a; a.b = d_b; a.N = N; a.F = F; a.tau = tau; a.flags = flags; a.loss = d_loss; a.rows = d_rows; a.z = d_z;
+    return poisoned_call(h, [&] { return infonce_pair_bytes(N, F); }, {{d_loss, 8}, {d_rows, (size_t)N * 16}, {d_z, (size_t)N * 16}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) { return infonce_pair_run(h->stream, base, have, a); });
+}
+
+int rlap_infonce_pair_backward(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double tau, int flags,
+                               const double* d_z, const double* d_g, float* d_ga, float* d_gb, rlap_infonce_pair_info* h_info) {
+    if (h_info) *h_info = rlap_infonce_pair_info{};
+    if (const int rc = infonce_check(h, d_a, d_b, N, F, tau, flags, nullptr)) return rc;
+    if (h_info) { h_info->rows = N; h_info->features = F; h_info->parts = infonce::pair_parts(N); h_info->groups = infonce::pair_groups(N); }
+    if (!d_z || !d_g || !d_ga || !d_gb) return RLAP_E_BAD_ARG;
+    InfonceArgs a{};
+    a.a = d_a; a.b = d_b; a.N = N; a.F = F; a.tau = tau; a.flags = flags; a.z_in = d_z; a.g = d_g; a.ga = d_ga; a.gb = d_gb;
+    return poisoned_call(h, [&] { return infonce_pair_backward_bytes(N, F); }, {{d_ga, (size_t)(N * F) * 4}, {d_gb, (size_t)(N * F) * 4}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) { return infonce_pair_backward_run(h->stream, base, have, a); });
+}
+
 namespace {
 
 // what both CCA exports check (their pointers come before this)

@@ -149,5 +149,70 @@ RLAP_SPMM_HD float grad_in(double G, float h, double dot, double nrm, bool clamp
     return (float)((G - t) / nrm);
 }
 
+// ---- the symmetric pair (rlap_infonce_pair / rlap_infonce_pair_backward): 0.5 * (l(a, b) + l(b, a)) from one pass
+// over S.  fmaf(x, y, acc) == fmaf(y, x, acc), so the similarity of the second direction is bit for bit the transpose of the first's:
+// s'_ji == s_ij and e'_ji == e_ij.  Normalisation, s_ij, expw, e_ij, row_term and the chunk rule are the ones above.
+//
+//   work split      a function of N alone.  The 128-row owner blocks (row_blocks(N)) are dealt into pair_groups(N) contiguous groups
+//                   (blocks [pair_group_begin(N, g), pair_group_begin(N, g + 1))), the 32-column stream tiles into pair_parts(N)
+//                   contiguous parts (tiles [pair_part_begin(N, p), pair_part_begin(N, p + 1))); one workgroup owns one (group, part).
+//                   A part is walked in spans of at most PAIR_SPAN_TILES tiles (a part has one span below 262,145 rows).
+//                   The partial sums are (pair_parts + pair_groups) x Np doubles: at most (512 + 16) Np.
+//   row sum         Z_i: inside a span two float64 sums, one per lane half, exactly as above (tiles in order, registers in order,
+//                   columns >= N left out); the span's sum is half 0 + half 1; the part's sum is 0 + span 0 + span 1 + ... (one
+//                   span: half 0 + half 1, as above); Z_i = 0 + part 0 + part 1 + ... in order.
+//   column sum      Zc_j = sum over the anchors i of e_ij, in float64:  Zc_j = 0 + group 0 + group 1 + ... in order; a group's sum
+//                   starts from 0 and takes its row blocks in order; inside a row block the four 32-row owner tiles (the four waves)
+//                   in order, each adding its tile's sum; a tile's sum is tree32 of (double)e_ij over its 32 owner rows, an owner
+//                   row >= N entering as +0 (it is left out: a padded row has s = 0 and e = expw(-1/tau) != 0, so it is masked,
+//                   and x + 0 = x for the non-negative x of these sums).  tree32: five rounds m = 1, 2, 4, 8, 16 of
+//                   v[c] = v[c] + v[c ^ m] on all 32 values at once -- the butterfly x = x + shfl_xor(x, m); IEEE addition commutes,
+//                   so after every round v[c] and v[c ^ m] hold the same bits, and the sum is v[0].  An owner tile behind the last
+//                   adds +0.
+//   row terms       rows_a_i = row_term(c, s_ii, 1/tau, Z_i);  rows_b_j = row_term(c, s_jj, 1/tau, Zc_j)
+//   loss            0.5 * (loss_of(chunk-rule sum of rows_a, N) + loss_of(chunk-rule sum of rows_b, N))
+//   backward        rza_i = recip_z(Z_i), rzb_j = recip_z(Zc_j);  w_ij = pair_weight(e_ij, rza_i, rzb_j) = e_ij * (rza_i + rzb_j) in
+//                   float32 -- symmetric in the two reciprocals, so both owner kernels compute the same bits.  D and D' are the
+//                   chains of the one-direction rule over num_parts(N) parts with w for p.  Gh = grad_hat(gs2, 2 c, other, 1/tau, D)
+//                   with gs2 = pair_grad_scale(g, N) = -(g / (2 N)); dot, grad_in and the clamp as above.
+constexpr int64_t PAIR_GROUPS = 16;           // groups of row blocks a call aims at
+constexpr int64_t PAIR_WORKGROUPS = 512;      // (group, part) workgroups a call aims at
+constexpr int64_t PAIR_SPAN_TILES = 256;      // stream tiles whose column sums a workgroup holds at once: 64 KB of doubles
+
+RLAP_SPMM_HD int64_t pair_groups(int64_t N) {
+    const int64_t rb = row_blocks(N);
+    return rb < 1 ? 1 : (rb < PAIR_GROUPS ? rb : PAIR_GROUPS);
+}
+RLAP_SPMM_HD int64_t pair_group_begin(int64_t N, int64_t g) { return g * row_blocks(N) / pair_groups(N); }   // (RB < 2^24, g <= 16)
+RLAP_SPMM_HD int64_t pair_parts(int64_t N) {
+    const int64_t T = num_tiles(N), g = pair_groups(N);
+    if (T < 1) return 1;
+    const int64_t p = (PAIR_WORKGROUPS + g - 1) / g;
+    return p > T ? T : p;
+}
+RLAP_SPMM_HD int64_t pair_part_begin(int64_t N, int64_t p) { return p * num_tiles(N) / pair_parts(N); }      // (T < 2^26, p <= 512)
+// the most stream tiles of a span of any part: what the forward kernel's column array is sized by
+RLAP_SPMM_HD int64_t pair_span_tiles(int64_t N) {
+    const int64_t T = num_tiles(N), P = pair_parts(N);
+    const int64_t longest = (T + P - 1) / P;   // (no part is longer: p T / P is floored at both ends)
+    return longest < PAIR_SPAN_TILES ? (longest < 1 ? 1 : longest) : PAIR_SPAN_TILES;
+}
+
+// tree32 on 32 values held in an array (what the butterfly does on 32 lanes)
+RLAP_SPMM_HD double tree32(const double* x) {
+    double v[TILE], w[TILE];
+    for (int c = 0; c < TILE; ++c) v[c] = x[c];
+    for (int m = 1; m < TILE; m <<= 1) {
+        for (int c = 0; c < TILE; ++c) w[c] = v[c] + v[c ^ m];
+        for (int c = 0; c < TILE; ++c) v[c] = w[c];
+    }
+    return v[0];
+}
+
+RLAP_SPMM_HD double pair_loss_of(double total_a, double total_b, int64_t N) { return 0.5 * (loss_of(total_a, N) + loss_of(total_b, N)); }
+RLAP_SPMM_HD float pair_weight(float e, float rz_own, float rz_str) { return e * (rz_own + rz_str); }
+RLAP_SPMM_HD double pair_grad_scale(double g, int64_t N) { return -(g / (2.0 * (double)N)); }
+RLAP_SPMM_HD double pair_positive_coef(bool raw, double tau) { return 2.0 * positive_coef(raw, tau); }   // 2 c: exact
+
 }  // namespace infonce
 }  // namespace rlap

@@ -25,6 +25,10 @@
 //              accumulators added in order, then the float64 push through the normalisation, one wave per row.
 // No float atomics, no host synchronisation, nothing allocated outside the arena.  Every address is formed from the padded sizes:
 // a wave whose owner tile lies behind the last one only takes part in the staging.
+//
+// The symmetric pair (rlap_infonce_pair / rlap_infonce_pair_backward) computes 0.5 * (l(a, b) + l(b, a)) from one pass:
+// its forward main kernel k_in_pair_main takes the row sums Z and the column sums Zc from the same tiles, its backward is k_in_main
+// with the weight e (1 / Z_i + 1 / Zc_j) (IN_BACK_PAIR), its finish the one above for two lists.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -81,14 +85,16 @@ __global__ __launch_bounds__(256) void k_in_recip(const double* __restrict__ z, 
 struct Main {
     const float* own_frag; const float* str_frag;   // fragment images, Np x Fp each
     const float* str_rows;                          // backward: the stream's row-major image
-    const float* rz;                                // backward: [Np] 1 / Z of the anchors, 0 behind N
+    const float* rz;                                // backward: [Np] 1 / Z of the anchors, 0 behind N (pair: of the owner's rows)
+    const float* rz2;                               // pair backward: [Np] the reciprocals of the stream's rows, 0 behind N
     float itf;                                      // (float)(1 / tau)
     int64_t N, Np, T, RB; int parts; int Fp; int nft;
     double* zpart; float* sdiag;                    // forward: [parts, Np] part sums of Z; [Np] the diagonal
     float* partial;                                 // backward: [parts, Np, Fp] part accumulators
 };
 
-enum { IN_FORWARD = 0, IN_BACK_ANCHOR = 1, IN_BACK_SAMPLE = 2 };
+// IN_BACK_PAIR: the weight of the symmetric pair, w = e * (rz[owner row] + rz2[stream row]), for either owner
+enum { IN_FORWARD = 0, IN_BACK_ANCHOR = 1, IN_BACK_SAMPLE = 2, IN_BACK_PAIR = 3 };
 
 template <int NFT, int MODE>
 __global__ __launch_bounds__(IN_THREADS) void k_in_main(Main a) {
@@ -106,7 +112,7 @@ __global__ __launch_bounds__(IN_THREADS) void k_in_main(Main a) {
 
     double zsum = 0.0;
     float rz_lane = 0.0f;
-    if (MODE == IN_BACK_ANCHOR && active) rz_lane = a.rz[orow];
+    if ((MODE == IN_BACK_ANCHOR || MODE == IN_BACK_PAIR) && active) rz_lane = a.rz[orow];
     f32x16 acc[NFT];
     if (MODE != IN_FORWARD) tile32::zero_tiles(acc);
 
@@ -132,8 +138,13 @@ __global__ __launch_bounds__(IN_THREADS) void k_in_main(Main a) {
             for (int r = 0; r < 16; ++r) {
                 const int64_t srow = srow0 + infonce::reg_row(r, h);
                 const float e = infonce::expw(infonce::exp_arg(x[r], a.itf));
-                const float rz = MODE == IN_BACK_ANCHOR ? rz_lane : a.rz[srow];   // (srow < Np; 0 behind N)
-                const float p = infonce::prob(e, rz);
+                float p;
+                if (MODE == IN_BACK_PAIR) {
+                    p = infonce::pair_weight(e, rz_lane, a.rz2[srow]);
+                } else {
+                    const float rz = MODE == IN_BACK_ANCHOR ? rz_lane : a.rz[srow];   // (srow < Np; 0 behind N)
+                    p = infonce::prob(e, rz);
+                }
                 x[r] = srow < a.N ? p : 0.0f;
             }
             tile32::accumulate_tiles(acc, a.nft, x, in_lds + (int)tile_floats, a.Fp, c, h);
@@ -146,6 +157,95 @@ __global__ __launch_bounds__(IN_THREADS) void k_in_main(Main a) {
         if (h == 0) a.zpart[part * a.Np + orow] = zsum + other;      // half 0 + half 1
     } else {
         tile32::store_tiles(acc, a.nft, a.partial + (part * a.Np + ot * infonce::TILE) * a.Fp, a.Fp, c, h);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ main, the pair's forward
+// Both directions from one pass over S.  A workgroup owns one (group of row blocks, part of the stream tiles): the
+// owner block outside, the stream tiles inside, staged through LDS per step as in k_in_main.  The row sums stay in registers across
+// the inner loop; the column sums of a step are reduced across the 32 owner lanes by the butterfly, handed over by the four waves
+// through LDS and added, waves in order, to an LDS array of one double per column of the span, which is flushed to
+// colpart[group][column] when the group's blocks are through.  Every barrier is reached by all four waves: a wave whose owner tile
+// lies behind the last one stages, hands over zeros and waits with the others.
+struct PairMain {
+    const float* own_frag; const float* str_frag;   // fragment images of a (owner) and b (stream), Np x Fp each
+    float itf;
+    int64_t N, Np, T; int groups; int Fp; int span;  // span: infonce::pair_span_tiles(N), what the column array holds
+    double* zpart; double* colpart; float* sdiag;   // [parts, Np] part sums of Z; [groups, Np] group sums of Zc; [Np] the diagonal
+};
+
+__global__ __launch_bounds__(IN_THREADS) void k_in_pair_main(PairMain a) {
+    extern __shared__ __attribute__((aligned(16))) float in_lds[];   // the stream tile's fragment image | col [32 span] | wave sums [4][32]
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int c = lane & 31, h = lane >> 5;
+    const int64_t group = (int64_t)blockIdx.x % a.groups, part = (int64_t)blockIdx.x / a.groups;
+    const int64_t tile_floats = (int64_t)infonce::TILE * a.Fp;
+    const int tile_vec = (int)(tile_floats >> 2), nqq = a.Fp >> 3;
+    double* col = reinterpret_cast<double*>(in_lds + tile_floats);
+    double* wsum = col + (int64_t)infonce::TILE * a.span;
+    const int64_t bb = infonce::pair_group_begin(a.N, group), be = infonce::pair_group_begin(a.N, group + 1);
+    const int64_t tb = infonce::pair_part_begin(a.N, part), te = infonce::pair_part_begin(a.N, part + 1);
+
+#pragma unroll 1
+    for (int64_t sb = tb; sb < te; sb += infonce::PAIR_SPAN_TILES) {
+        const int64_t se = sb + infonce::PAIR_SPAN_TILES < te ? sb + infonce::PAIR_SPAN_TILES : te;
+        const int span_cols = (int)(se - sb) * infonce::TILE;        // (<= 32 span)
+        for (int v = threadIdx.x; v < span_cols; v += IN_THREADS) col[v] = 0.0;   // (seen behind the first barrier below: bb < be, sb < se)
+#pragma unroll 1
+        for (int64_t blk = bb; blk < be; ++blk) {
+            const int64_t ot = blk * infonce::BLOCK_TILES + wave;
+            const bool active = ot < a.T;                            // (wave-uniform)
+            const float4* __restrict__ owner = reinterpret_cast<const float4*>(a.own_frag + (active ? ot : 0) * tile_floats);
+            const int64_t orow = ot * infonce::TILE + c;             // the lane's owner row (< Np when active)
+            const bool own_live = active && orow < a.N;
+            double zsum = 0.0;
+#pragma unroll 1
+            for (int64_t t = sb; t < se; ++t) {
+                __syncthreads();   // (the previous tile and the previous wave sums have been read)
+                tile32::stage_tile<IN_THREADS>(in_lds, a.str_frag + t * tile_floats, nullptr, tile_vec);
+                __syncthreads();
+                if (active) {
+                    const f32x16 x = tile32::pair_chain(reinterpret_cast<const float4*>(in_lds), owner, nqq, lane);
+                    const int64_t srow0 = t * infonce::TILE;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int64_t srow = srow0 + infonce::reg_row(r, h);
+                        const float e = infonce::expw(infonce::exp_arg(x[r], a.itf));
+                        const double z2 = zsum + (double)e;
+                        zsum = srow < a.N ? z2 : zsum;
+                        if (srow == orow) a.sdiag[orow] = x[r];      // (once per owner row of the call)
+                        double v = own_live ? (double)e : 0.0;       // tree32 over the 32 owner lanes of the half
+                        v = v + __shfl_xor(v, 1);
+                        v = v + __shfl_xor(v, 2);
+                        v = v + __shfl_xor(v, 4);
+                        v = v + __shfl_xor(v, 8);
+                        v = v + __shfl_xor(v, 16);
+                        if (c == 0) wsum[wave * infonce::TILE + infonce::reg_row(r, h)] = v;
+                    }
+                } else if (lane < infonce::TILE) {
+                    wsum[wave * infonce::TILE + lane] = 0.0;
+                }
+                __syncthreads();
+                if (threadIdx.x < infonce::TILE) {                   // the four waves in order
+                    const int j = (int)(t - sb) * infonce::TILE + threadIdx.x;
+                    double s = col[j];
+#pragma unroll
+                    for (int w = 0; w < infonce::BLOCK_TILES; ++w) s = s + wsum[w * infonce::TILE + threadIdx.x];
+                    col[j] = s;
+                }
+            }
+            if (active) {
+                const double other = __shfl_xor(zsum, 32);
+                if (h == 0) {                                        // the slot is this workgroup's alone: no atomic
+                    const int64_t slot = part * a.Np + orow;
+                    const double before = sb > tb ? a.zpart[slot] : 0.0;
+                    a.zpart[slot] = before + (zsum + other);         // 0 + span 0 + span 1 + ...; a span is half 0 + half 1
+                }
+            }
+        }
+        __syncthreads();   // (the last step's column sums are in)
+        for (int v = threadIdx.x; v < span_cols; v += IN_THREADS) a.colpart[group * a.Np + sb * infonce::TILE + v] = col[v];
+        __syncthreads();   // (flushed before the next span clears the array)
     }
 }
 
@@ -164,6 +264,34 @@ __global__ __launch_bounds__(256) void k_in_chunks(const double* __restrict__ ro
     tile32::chunk_sums(rows, N, 1, csum);
 }
 
+// the pair's finish: Z = the parts in order, Zc = the groups in order, the two lists of row terms; z and rows are [2, N]
+__global__ __launch_bounds__(256) void k_in_pair_rows(const double* __restrict__ zpart, const double* __restrict__ colpart, const float* __restrict__ sdiag,
+                                                      int64_t N, int64_t Np, int parts, int groups, double c, double itau, double* __restrict__ z,
+                                                      double* __restrict__ rows) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
+        double Z = 0.0, Zc = 0.0;
+        for (int p = 0; p < parts; ++p) Z = Z + zpart[p * Np + i];
+        for (int q = 0; q < groups; ++q) Zc = Zc + colpart[q * Np + i];
+        z[i] = Z;
+        z[N + i] = Zc;
+        rows[i] = infonce::row_term(c, sdiag[i], itau, Z);
+        rows[N + i] = infonce::row_term(c, sdiag[i], itau, Zc);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_in_pair_chunks(const double* __restrict__ rows, int64_t N, double* __restrict__ csum) {
+    tile32::chunk_sums(rows, N, 2, csum);
+}
+
+__global__ void k_in_pair_loss(const double* __restrict__ csum, int64_t N, double* __restrict__ loss) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const int64_t nc = spmm::num_chunks(N);
+    double ta = 0.0, tb = 0.0;
+    for (int64_t k = 0; k < nc; ++k) ta = ta + csum[k];
+    for (int64_t k = 0; k < nc; ++k) tb = tb + csum[nc + k];
+    *loss = infonce::pair_loss_of(ta, tb, N);
+}
+
 __global__ void k_in_loss(const double* __restrict__ csum, int64_t N, double* __restrict__ loss) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     double total = 0.0;
@@ -179,11 +307,11 @@ constexpr int IN_GRAD_WAVES = 4;
 __global__ __launch_bounds__(64 * IN_GRAD_WAVES) void k_in_grad(const float* __restrict__ partial, int parts, int64_t N, int64_t F, int64_t Np, int Fp,
                                                                 const float* __restrict__ own_rows, const float* __restrict__ other_rows,
                                                                 const double* __restrict__ n2, const double* __restrict__ g, double c, double itau,
-                                                                float* __restrict__ out) {
+                                                                int pair, float* __restrict__ out) {
     __shared__ double gh[IN_GRAD_WAVES][infonce::MAX_F];
     __shared__ float oh[IN_GRAD_WAVES][infonce::MAX_F];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const double gs = infonce::grad_scale(*g, N);
+    const double gs = pair ? infonce::pair_grad_scale(*g, N) : infonce::grad_scale(*g, N);   // (pair: c is 2 c)
     for (int64_t base = (int64_t)blockIdx.x * IN_GRAD_WAVES; base < N; base += (int64_t)gridDim.x * IN_GRAD_WAVES) {   // (the same turns for every wave)
         const int64_t i = base + wave;
         const bool live = i < N;
@@ -213,7 +341,33 @@ struct Bufs {
     float *a_frag, *b_frag, *a_rows, *b_rows;
     double* zpart; float* sdiag; double* csum;
     float* rz; float *part_a, *part_b;
+    double* colpart; float* rz2;                    // the pair's: the group sums of Zc; the second reciprocal vector
 };
+
+// the pair's arena: the one-direction call's with the pair's partial sums (forward) or the second reciprocal vector (backward)
+size_t carve_pair(Carve& C, int64_t N, int64_t F, bool backward, Bufs& B) {
+    const int64_t Np = infonce::padded_rows(N), Fp = infonce::padded_features(F);
+    B = Bufs{};
+    B.n2a = C.take<double>(Np);
+    B.n2b = C.take<double>(Np);
+    B.a_frag = C.take<float>(Np * Fp);
+    B.b_frag = C.take<float>(Np * Fp);
+    if (!backward) {
+        B.zpart = C.take<double>(infonce::pair_parts(N) * Np);
+        B.colpart = C.take<double>(infonce::pair_groups(N) * Np);
+        B.sdiag = C.take<float>(Np);
+        B.csum = C.take<double>(2 * spmm::num_chunks(N));
+    } else {
+        const int64_t parts = infonce::num_parts(N);
+        B.a_rows = C.take<float>(Np * Fp);
+        B.b_rows = C.take<float>(Np * Fp);
+        B.rz = C.take<float>(Np);
+        B.rz2 = C.take<float>(Np);
+        B.part_a = C.take<float>(parts * Np * Fp);
+        B.part_b = C.take<float>(parts * Np * Fp);
+    }
+    return C.off + 256;
+}
 
 size_t carve_infonce(Carve& C, int64_t N, int64_t F, bool backward, Bufs& B) {
     const int64_t Np = infonce::padded_rows(N), Fp = infonce::padded_features(F), parts = infonce::num_parts(N);
@@ -317,9 +471,75 @@ int infonce_backward_run(hipStream_t st, void* ws, size_t ws_bytes, const Infonc
     m.own_frag = B.b_frag; m.str_frag = B.a_frag; m.str_rows = B.a_rows; m.partial = B.part_b;
     if (const int rc = launch_backward_main<IN_BACK_SAMPLE>(st, m)) return rc;
     hipLaunchKernelGGL(k_in_grad, dim3(in_blocks(g.N, IN_GRAD_WAVES)), dim3(64 * IN_GRAD_WAVES), 0, st, (const float*)B.part_a, m.parts, g.N, g.F, m.Np, m.Fp,
-                       (const float*)B.a_rows, (const float*)B.b_rows, (const double*)B.n2a, g.g, c, itau, g.ga);
+                       (const float*)B.a_rows, (const float*)B.b_rows, (const double*)B.n2a, g.g, c, itau, 0, g.ga);
     hipLaunchKernelGGL(k_in_grad, dim3(in_blocks(g.N, IN_GRAD_WAVES)), dim3(64 * IN_GRAD_WAVES), 0, st, (const float*)B.part_b, m.parts, g.N, g.F, m.Np, m.Fp,
-                       (const float*)B.b_rows, (const float*)B.a_rows, (const double*)B.n2b, g.g, c, itau, g.gb);
+                       (const float*)B.b_rows, (const float*)B.a_rows, (const double*)B.n2b, g.g, c, itau, 0, g.gb);
+    RLAP_HIPCHK(hipGetLastError());
+    return RLAP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the symmetric pair
+size_t infonce_pair_bytes(int64_t N, int64_t F) {
+    Carve C{nullptr, 0};
+    Bufs B;
+    return carve_pair(C, N, F, false, B);
+}
+
+size_t infonce_pair_backward_bytes(int64_t N, int64_t F) {
+    Carve C{nullptr, 0};
+    Bufs B;
+    return carve_pair(C, N, F, true, B);
+}
+
+// LDS of k_in_pair_main: the stream tile's fragment image, the span's column sums, the four waves' sums
+size_t infonce_pair_lds_bytes(int64_t N, int64_t F) {
+    return (size_t)infonce::TILE * infonce::padded_features(F) * sizeof(float) +
+           (size_t)infonce::TILE * (infonce::pair_span_tiles(N) + infonce::BLOCK_TILES) * sizeof(double);
+}
+
+int infonce_pair_run(hipStream_t st, void* ws, size_t ws_bytes, const InfonceArgs& g) {
+    Bufs B;
+    Carve C{static_cast<char*>(ws), 0};
+    if (carve_pair(C, g.N, g.F, false, B) > ws_bytes) return RLAP_E_WORKSPACE;
+    if (const int rc = prepass(st, g, B)) return rc;
+    PairMain m{};
+    m.own_frag = B.a_frag; m.str_frag = B.b_frag; m.itf = infonce::inv_tau_f(g.tau);
+    m.N = g.N; m.Np = infonce::padded_rows(g.N); m.T = infonce::num_tiles(g.N);
+    m.groups = (int)infonce::pair_groups(g.N); m.Fp = infonce::padded_features(g.F); m.span = (int)infonce::pair_span_tiles(g.N);
+    m.zpart = B.zpart; m.colpart = B.colpart; m.sdiag = B.sdiag;
+    const int parts = (int)infonce::pair_parts(g.N);
+    const size_t lds = infonce_pair_lds_bytes(g.N, g.F);
+    if (const int rc = tile32::allow_lds(&k_in_pair_main, lds)) return rc;
+    hipLaunchKernelGGL(k_in_pair_main, dim3((unsigned)(m.groups * parts)), dim3(IN_THREADS), lds, st, m);
+    const double c = infonce::positive_coef((g.flags & RLAP_INFONCE_POSITIVE_RAW) != 0, g.tau), itau = infonce::inv_tau(g.tau);
+    hipLaunchKernelGGL(k_in_pair_rows, dim3(in_blocks(g.N, 256)), dim3(256), 0, st, (const double*)B.zpart, (const double*)B.colpart,
+                       (const float*)B.sdiag, g.N, m.Np, parts, m.groups, c, itau, g.z, g.rows);
+    hipLaunchKernelGGL(k_in_pair_chunks, dim3(in_blocks(2 * spmm::num_chunks(g.N), 256)), dim3(256), 0, st, (const double*)g.rows, g.N, B.csum);
+    hipLaunchKernelGGL(k_in_pair_loss, dim3(1), dim3(64), 0, st, (const double*)B.csum, g.N, g.loss);
+    RLAP_HIPCHK(hipGetLastError());
+    return RLAP_OK;
+}
+
+int infonce_pair_backward_run(hipStream_t st, void* ws, size_t ws_bytes, const InfonceArgs& g) {
+    Bufs B;
+    Carve C{static_cast<char*>(ws), 0};
+    if (carve_pair(C, g.N, g.F, true, B) > ws_bytes) return RLAP_E_WORKSPACE;
+    if (const int rc = prepass(st, g, B)) return rc;
+    Main m = main_args(g);
+    hipLaunchKernelGGL(k_in_recip, dim3(in_blocks(m.Np, 256)), dim3(256), 0, st, g.z_in, g.N, m.Np, B.rz);             // 1 / Z of the anchors
+    hipLaunchKernelGGL(k_in_recip, dim3(in_blocks(m.Np, 256)), dim3(256), 0, st, g.z_in + g.N, g.N, m.Np, B.rz2);     // 1 / Zc of the samples
+    RLAP_HIPCHK(hipGetLastError());
+    const double c2 = infonce::pair_positive_coef((g.flags & RLAP_INFONCE_POSITIVE_RAW) != 0, g.tau), itau = infonce::inv_tau(g.tau);
+    // the anchors own, the samples stream: D = sum_j w_ij bh_j
+    m.own_frag = B.a_frag; m.str_frag = B.b_frag; m.str_rows = B.b_rows; m.partial = B.part_a; m.rz = B.rz; m.rz2 = B.rz2;
+    if (const int rc = launch_backward_main<IN_BACK_PAIR>(st, m)) return rc;
+    // the samples own, the anchors stream: D' = sum_i w_ij ah_i
+    m.own_frag = B.b_frag; m.str_frag = B.a_frag; m.str_rows = B.a_rows; m.partial = B.part_b; m.rz = B.rz2; m.rz2 = B.rz;
+    if (const int rc = launch_backward_main<IN_BACK_PAIR>(st, m)) return rc;
+    hipLaunchKernelGGL(k_in_grad, dim3(in_blocks(g.N, IN_GRAD_WAVES)), dim3(64 * IN_GRAD_WAVES), 0, st, (const float*)B.part_a, m.parts, g.N, g.F, m.Np, m.Fp,
+                       (const float*)B.a_rows, (const float*)B.b_rows, (const double*)B.n2a, g.g, c2, itau, 1, g.ga);
+    hipLaunchKernelGGL(k_in_grad, dim3(in_blocks(g.N, IN_GRAD_WAVES)), dim3(64 * IN_GRAD_WAVES), 0, st, (const float*)B.part_b, m.parts, g.N, g.F, m.Np, m.Fp,
+                       (const float*)B.b_rows, (const float*)B.a_rows, (const double*)B.n2b, g.g, c2, itau, 1, g.gb);
     RLAP_HIPCHK(hipGetLastError());
     return RLAP_OK;
 }

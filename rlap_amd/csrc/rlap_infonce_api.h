@@ -22,4 +22,12 @@ size_t infonce_backward_bytes(int64_t N, int64_t F);
 int infonce_run(hipStream_t stream, void* ws, size_t ws_bytes, const InfonceArgs& a);
 int infonce_backward_run(hipStream_t stream, void* ws, size_t ws_bytes, const InfonceArgs& a);
 
+// the symmetric pair (rlap_infonce_pair / rlap_infonce_pair_backward): the same arguments, with rows, z and z_in
+// [2, N] -- the anchors' list, then the samples'
+size_t infonce_pair_bytes(int64_t N, int64_t F);
+size_t infonce_pair_backward_bytes(int64_t N, int64_t F);
+size_t infonce_pair_lds_bytes(int64_t N, int64_t F);   // dynamic LDS of the forward main kernel
+int infonce_pair_run(hipStream_t stream, void* ws, size_t ws_bytes, const InfonceArgs& a);
+int infonce_pair_backward_run(hipStream_t stream, void* ws, size_t ws_bytes, const InfonceArgs& a);
+
 }  // namespace rlap

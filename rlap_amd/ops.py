@@ -1301,6 +1301,70 @@ def info_nce(anchor: Tensor, sample: Tensor, tau: float = 0.4, positive: str = "
     return (loss, rows) if return_rows else loss
 
 
+def _info_nce_pair_forward(a: Tensor, b: Tensor, tau: float, flags: int):
+    """The pair's forward export: (loss 0-dim, rows [2, N], z [2, N], the device copies of a and b)."""
+    dev = _device_for(a)
+    with torch.cuda.device(dev):
+        d_a = a.detach().to(device=dev).contiguous()
+        d_b = b.detach().to(device=dev).contiguous()
+        n, f = int(d_a.shape[0]), int(d_a.shape[1])
+        out = torch.empty(1 + 4 * n, dtype=torch.float64, device=dev)   # loss | rows (2N) | z (2N)
+        p = out.data_ptr()
+        _device_call("rlap_infonce_pair", _lib.InfoncePairInfo, dev, 1, (d_a.data_ptr(), d_b.data_ptr(), n, f, tau, flags, p, p + 8, p + 8 * (1 + 2 * n)))
+    return out[0], out[1:1 + 2 * n].view(2, n), out[1 + 2 * n:].view(2, n), d_a, d_b
+
+
+class _InfoNCEPair(torch.autograd.Function):
+    """loss = the symmetric InfoNCE of two views; the gradients with respect to both come from one call of the backward export."""
+
+    @staticmethod
+    def forward(ctx, a, b, tau, flags):
+        loss, rows, z, d_a, d_b = _info_nce_pair_forward(a, b, tau, flags)
+        ctx.save_for_backward(d_a, d_b, z)
+        ctx.call = (tau, flags, a.device, b.device)
+        ctx.mark_non_differentiable(rows)
+        return loss, rows
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_rows):
+        d_a, d_b, z = ctx.saved_tensors
+        tau, flags, dev_a, dev_b = ctx.call
+        dev = d_a.device
+        with torch.cuda.device(dev):
+            d_g = _upstream(g, dev)
+            n, f = int(d_a.shape[0]), int(d_a.shape[1])
+            ga = torch.empty_like(d_a)
+            gb = torch.empty_like(d_b)
+            _device_call("rlap_infonce_pair_backward", _lib.InfoncePairInfo, dev, 1, (
+                d_a.data_ptr(), d_b.data_ptr(), n, f, tau, flags, z.data_ptr(), d_g.data_ptr(), ga.data_ptr(), gb.data_ptr()))
+        return ga.to(dev_a), gb.to(dev_b), None, None
+
+
+def info_nce_pair(h1: Tensor, h2: Tensor, tau: float = 0.4, positive: str = "scaled", return_rows: bool = False):
+    """The symmetric InfoNCE loss of two views, 0.5 * (info_nce(h1, h2) + info_nce(h2, h1)), from one pass over the similarities
+    (rlap_infonce_pair): what DualBranchContrast(InfoNCEBatched(tau), mode="L2L") computes for both directions.  The
+    similarity of the second direction is the transpose of the first's bit for bit, so the row sums and the column sums of one set
+    of tiles are the two denominators, and the backward folds both directions into one weight: five N x N x F products a step where
+    the two info_nce calls make ten.
+
+      h1, h2, tau, positive : as info_nce
+      return_rows           : also return the (2, N) float64 row terms: those of (h1, h2), then those of (h2, h1) (not differentiable)
+    Returns the 0-dim float64 loss; it equals the two-call value up to the order of the sums, which is fixed here too
+    (rlap_amd/csrc/rlap_infonce.h): the same input gives the same bits.  Memory is O(N F).
+
+    Differentiable in both inputs (one rlap_infonce_pair_backward call); double backward is not supported.  Malformed arguments
+    raise ValueError before the device is touched.  No host synchronisation.  `last_stats` then holds what the call did
+    (rlap_infonce_pair_info: rows, features, arena_bytes, parts, groups, host_syncs).
+    """
+    tau, flags = _info_nce_args(h1, h2, tau, positive)
+    if torch.is_grad_enabled() and (h1.requires_grad or h2.requires_grad):
+        loss, rows = _InfoNCEPair.apply(h1, h2, tau, flags)
+    else:
+        loss, rows = _info_nce_pair_forward(h1, h2, tau, flags)[:2]
+    return (loss, rows) if return_rows else loss
+
+
 CCA_MAX_F = 512
 
 

@@ -21,6 +21,7 @@ nothing outside the repository.
   arxiv   : (169343, 256)   ogbn-arxiv
     python tools/infonce_latency.py
     python tools/infonce_latency.py --shapes physics --no-torch     # the calls alone (for rocprofv3 --kernel-trace --stats)
+    python tools/infonce_latency.py --pair                           # one ops.info_nce_pair call against the two calls
 """
 import argparse
 import json
@@ -133,8 +134,69 @@ def run(name, n, f, args, fh):
     torch.cuda.empty_cache()
 
 
+def run_pair(name, n, f, args, fh):
+    """--pair: the symmetric loss 0.5 * (l(a, b) + l(b, a)) three ways on the same tensors -- one ops.info_nce_pair call (DESIGN
+    4.19), the two ops.info_nce calls of the default NodeContrast, torch's two directions -- forward and forward + backward, with
+    the peak memory of each and the largest difference between the pair's result and the two calls'."""
+    gen = torch.Generator(device="cuda").manual_seed(n)
+    a = torch.randn(n, f, dtype=torch.float32, device="cuda", generator=gen)
+    b = 0.3 * a + torch.randn(n, f, dtype=torch.float32, device="cuda", generator=gen)
+    flops = 2.0 * n * n * f
+    rec = {"mode": "pair", "shape": name, "N": n, "F": f, "tau": TAU, "flops_per_product": flops}
+    pair = lambda x, y: ops.info_nce_pair(x, y, tau=TAU, positive="raw")
+    two = lambda x, y: 0.5 * (ops.info_nce(x, y, tau=TAU, positive="raw") + ops.info_nce(y, x, tau=TAU, positive="raw"))
+    both = lambda x, y: 0.5 * (torch_batched(x, y) + torch_batched(y, x))
+    tp, tsp, lp, memp = peak_of(lambda: pair(a, b), args.reps)
+    st = dict(ops.last_stats)
+    tw, tsw, lw, memw = peak_of(lambda: two(a, b), args.reps)
+    rec.update({"pair_forward_ms": round(tp, 3), "pair_forward_runs_ms": tsp, "pair_forward_of_157TF": round(flops / (tp * 1e-3) / PEAK, 4),
+                "pair_forward_max_memory_allocated": memp, "pair_forward_arena_bytes": st["arena_bytes"], "parts": st["parts"],
+                "groups": st["groups"], "host_syncs": st["host_syncs"],
+                "two_calls_forward_ms": round(tw, 3), "two_calls_forward_runs_ms": tsw, "two_calls_forward_max_memory_allocated": memw,
+                "two_calls_forward_over_pair": round(tw / tp, 3), "loss": float(lp), "loss_diff_pair_to_two_calls": abs(float(lp) - float(lw))})
+    tp2, tsp2, gp, memp2 = peak_of(both_ways(pair, a, b), args.reps)
+    rec["pair_backward_arena_bytes"] = ops.last_stats["arena_bytes"]
+    tw2, tsw2, gw, memw2 = peak_of(both_ways(two, a, b), args.reps)
+    scale = float(max(gw[0].abs().max(), gw[1].abs().max()))
+    rec.update({"pair_forward_backward_ms": round(tp2, 3), "pair_forward_backward_runs_ms": tsp2,
+                "pair_forward_backward_of_157TF": round(5.0 * flops / (tp2 * 1e-3) / PEAK, 4), "pair_forward_backward_max_memory_allocated": memp2,
+                "two_calls_forward_backward_ms": round(tw2, 3), "two_calls_forward_backward_runs_ms": tsw2,
+                "two_calls_forward_backward_max_memory_allocated": memw2, "two_calls_forward_backward_over_pair": round(tw2 / tp2, 3),
+                "gradient_diff_pair_to_two_calls_over_largest": float(max((gp[0] - gw[0]).abs().max(), (gp[1] - gw[1]).abs().max())) / scale})
+    del gw
+    if not args.no_torch:
+        torch.cuda.empty_cache()
+        free, _ = torch.cuda.mem_get_info()
+        block = 3 * 4 * min(BATCH, n) * n
+        kept = 2 * (4 * n * n) + 2 * block                           # autograd keeps the exponentials of both directions
+        rec["torch_bytes_forward_estimate"], rec["torch_bytes_forward_backward_estimate"], rec["free_bytes"] = block, kept, int(free)
+        if block <= free // 2:
+            tt, tts, want, tmem = peak_of(lambda: both(a, b), args.reps)
+            rec.update({"torch_forward_ms": round(tt, 3), "torch_forward_runs_ms": tts, "torch_forward_over_pair": round(tt / tp, 3),
+                        "torch_forward_max_memory_allocated": tmem, "loss_diff_to_torch": abs(float(lp) - float(want))})
+        else:
+            rec["torch_forward_ms"] = "not measured: its estimated working set exceeds half of the free memory"
+        if kept <= free // 2:
+            tt2, tts2, tg, tmem2 = peak_of(both_ways(both, a, b), args.reps)
+            tscale = float(max(tg[0].abs().max(), tg[1].abs().max()))
+            rec.update({"torch_forward_backward_ms": round(tt2, 3), "torch_forward_backward_runs_ms": tts2,
+                        "torch_forward_backward_over_pair": round(tt2 / tp2, 3), "torch_forward_backward_max_memory_allocated": tmem2,
+                        "gradient_diff_to_torch_over_largest": float(max((gp[0] - tg[0]).abs().max(), (gp[1] - tg[1]).abs().max())) / tscale})
+            del tg
+        else:
+            rec["torch_forward_backward_ms"] = "not measured: its estimated working set exceeds half of the free memory"
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if fh is not None:
+        fh.write(line + "\n")
+        fh.flush()
+    del a, b, gp
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--pair", action="store_true", help="the symmetric loss: ops.info_nce_pair against the two ops.info_nce calls and torch's two directions")
     ap.add_argument("--shapes", default="cora,physics,arxiv")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-torch", action="store_true", help="time the calls alone")
@@ -144,7 +206,7 @@ def main():
     fh = open(args.out, "a") if args.out else None
     for name in args.shapes.split(","):
         n, f = SHAPES[name]
-        run(name, n, f, args, fh)
+        (run_pair if args.pair else run)(name, n, f, args, fh)
 
 
 if __name__ == "__main__":
