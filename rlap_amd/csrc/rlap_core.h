@@ -376,6 +376,8 @@ struct Arrays {
 RLAP_HD double arr_uniform(const Arrays& A, int64_t draw, int32_t vertex, int32_t j) {
     return A.rng_mode == RNG_COUNTER ? frontier_uniform(A.shuffle_seed, (int64_t)(vertex - A.vbase), (int64_t)j) : A.rng[draw];
 }
+// neighbours ordered by the keyed hash of their ids (o_n = random, and every coarsen call), not by their weights
+RLAP_HD bool keyed_order(const Arrays& A) { return A.o_n == ON_RANDOM || A.o_v == OV_COARSEN; }
 
 #if defined(__HIP_DEVICE_COMPILE__)
 RLAP_HD int32_t pool_take(int32_t* top, int32_t cnt) { return atomicAdd(top, cnt); }
@@ -459,6 +461,35 @@ RLAP_HD void col_for_each_slot(const Arrays& A, int32_t v, F f) {
     }
     for (int32_t s = A.colptr[v + 1] - 1; s >= A.colptr[v]; --s) f(s);
 }
+#if defined(__HIPCC__)   // (device code, parsed in the host pass too)
+// The same walk by a wave, 64 slots at a time (all 64 lanes call it together): sink(pos, slot, entry) for every live entry, pos its
+// rank among the live entries in traversal order (compacted by ballot); returns the live count.
+template <class Sink>
+__device__ __forceinline__ int32_t wave_col_live(const Arrays& A, int32_t v, int lane, Sink sink) {
+    const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    int32_t len = 0;
+    auto piece = [&](int32_t hi, int32_t lo) {   // slots hi, hi - 1, .., lo
+        for (int32_t s0 = hi; s0 >= lo; s0 -= 64) {
+            const int32_t s = s0 - lane;
+            Slot g = {};
+            if (s >= lo) g = A.e[s];
+            const bool live = s >= lo && g.val > 0;
+            const uint64_t mask = __ballot(live);
+            if (live) sink(len + __popcll(mask & lt), s, g);
+            len += __popcll(mask);
+        }
+    };
+    const int32_t cp0 = A.colptr[v], cp1 = A.colptr[v + 1];
+    int32_t idx = A.vr[v].app_cnt - 1, base = A.vr[v].app_chunk;
+    for (int c = idx >= 0 ? chunk_of(idx) : 0; idx >= 0; --c) {
+        const int32_t cs = chunk_start(c);
+        piece(base + 1 + (idx - cs), base + 1);
+        idx = cs - 1; base = A.e[base].nbr;
+    }
+    piece(cp1 - 1, cp0);
+    return len;
+}
+#endif
 // rank[s] = r for the r-th live entry of column v's traversal; returns the live count
 RLAP_HD int32_t squeeze_rank_col(const Arrays& A, int32_t v, int32_t* rank) {
     int32_t r = 0;

@@ -1,4 +1,4 @@
-// rlap_kernels.h -- kernel declarations shared by rlap_kernels.hip and rlap_api.hip
+// rlap_kernels.h -- kernel declarations shared by rlap_setup.hip, rlap_kernels.hip, rlap_output.hip, rlap_sorthook.hip and rlap_api.hip
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

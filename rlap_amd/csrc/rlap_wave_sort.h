@@ -1,7 +1,7 @@
 // rlap_wave_sort.h -- wave64 helpers and the wave-parallel restatements of libstdc++ 11 std::sort (same permutation under ties as
 // rlap_core.h::gs_std_sort): wave_std_sort (any length, data in LDS or global memory), wave_lvl_sort (level-synchronous, LDS),
 // wave_sort64 (one element per lane, registers), group_sort (two 32-lane groups per wave).  Templates and inline device code only:
-// included by every translation unit that sorts (rlap_kernels.hip, twice; rlap_flow.hip).
+// included by every translation unit that sorts (rlap_kernels.hip, twice; rlap_output.hip; rlap_sorthook.hip; rlap_flow.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -734,7 +734,7 @@ __device__ void wave_std_sort_staged(T* a, int n, Less less, uint16_t* ulist, ui
 }
 
 // ---------------------------------------------------------------------------
-// One array shared by NW waves of a workgroup, level by level (the form of rlap_kernels.hip::block_std_sort), with the
+// One array shared by NW waves of a workgroup, level by level (the form of rlap_output.hip::block_std_sort), with the
 // level-synchronous form for every segment of 64*LREG elements and less: a level's segments are dealt to the waves; a long one is
 // partitioned by its wave (stop lists at the segment's own offsets) and its parts are queued for the next level; a short one is
 // sorted through by its wave alone (wave_lvl_sort with the loop's remaining depth limit) and marked every 16 elements.  Segments

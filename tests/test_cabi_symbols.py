@@ -47,7 +47,8 @@ def test_ops_refuse_to_run_without_gpu():
 def test_elimination_kernels_keep_their_register_and_lds_budget(tmp_path):
     """The elimination kernels are built for 128 VGPRs (16 waves per CU) and, in the 256-thread shape, 40 KB of LDS (four
     workgroups per CU).  Out-of-line device functions are compiled once for all their callers with the loosest budget among
-    them, so an innocent new caller (a test hook, say) can silently halve the occupancy of every kernel that shares the function:
+    them, so an innocent new caller in their translation unit can silently halve the occupancy of every kernel that shares the
+    function (which is why the output pass and the sorts' test hook have units of their own, rlap_output.hip and rlap_sorthook.hip):
     read the numbers back from the code object inside the built library."""
     import pytest
     import shutil
