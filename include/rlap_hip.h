@@ -50,7 +50,7 @@ enum {
     RLAP_E_INTERNAL = 10,
     RLAP_E_WORKSPACE = 11,    /* caller-provided workspace / uniform table too small: rlap_workspace_needed() says how much */
     RLAP_E_NOT_GROUPED = 12,  /* rlap_snapshot_stats: a column id starts two separate blocks of rows in one segment */
-    RLAP_E_OUT_CAPACITY = 13  /* rlap_snapshot_ppr: the kept entries exceed out_cap_rows; nothing written, rows_needed reported */
+    RLAP_E_OUT_CAPACITY = 13  /* rlap_snapshot_ppr, rlap_edge_drop: the kept entries exceed out_cap_rows; nothing written, rows_needed reported */
 };
 
 typedef struct {
@@ -487,6 +487,46 @@ int rlap_snapshot_plan_propagate(rlap_handle h, const void* d_plan, const rlap_p
 int rlap_edge_plan_build(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
                          int64_t G, int64_t num_nodes, int flags, double fill_value, void* d_plan, size_t plan_bytes,
                          rlap_plan_desc* h_desc, rlap_plan_info* h_info);
+
+/* Centrality-adaptive edge dropping, K views a call: the uniform, degree, PageRank and eigenvector edge-dropping
+ * augmentors of GCA as the training scripts use them, on the device.  The centrality is found once and serves every view; row e is
+ * kept in view k iff u(k, e) >= q(k, e), a counter-based coin against the drop probability.  Every rule -- counts, centralities,
+ * scores, probability, coin and the order of every sum -- is defined in rlap_amd/csrc/rlap_edgedrop.h.
+ *   d_src, d_dst, E    : the rows (source, target), int64 on the device, in any order; duplicates, loops and directed rows stay
+ *   d_w                : (nullable) one weight a row, carried to the output and never read for the scores; NULL: 1.0
+ *   num_nodes          : every id lies in [0, num_nodes)
+ *   scheme             : RLAP_DROP_UNIFORM (q = p), _DEGREE, _PAGERANK, _EIGENVECTOR
+ *   flags              : RLAP_DROP_SOURCE: counts and scores by a row's source; default by its target
+ *   h_p, K             : K drop parameters in [0, 1] ON THE HOST, 1 <= K <= 32; view k uses h_p[k] and seed + k
+ *   threshold          : the cap of every drop probability, in [0, 1]
+ *   pr_damp, pr_iters  : PageRank: the damping in [0, 1] and the number of steps
+ *   evc_tol, evc_max_iter : eigenvector: stops after the step with sum |x' - x| <= num_nodes * evc_tol, or after evc_max_iter steps
+ *   d_rows, out_cap_rows  : (out_cap_rows, 3) f64 rows [source, target, weight], view-major, input order inside a view
+ *   d_ptr              : [K+1] row offsets of the views in d_rows
+ *   d_mask             : (nullable) (K, E) bytes: 1 where the row is kept
+ *   d_centrality, d_node_weight : (nullable) [num_nodes] f64 (zeros for RLAP_DROP_UNIFORM or E = 0)
+ *   h_info             : (nullable) what the call did; iters / converged report the eigenvector iteration
+ * View k of a K-view call equals a one-view call with (h_p[k], seed + k); the same input gives the same bits; no atomic touches a
+ * floating-point value.  More kept rows than out_cap_rows: RLAP_E_OUT_CAPACITY, no row written, h_info->rows_needed says how many.
+ * An id outside [0, num_nodes): RLAP_E_INDEX_RANGE.  A null pointer, K < 1, a parameter out of its range, an unknown scheme or flag:
+ * RLAP_E_BAD_ARG.  E >= 2^31 - 1, num_nodes >= 2^31, K > 32 or more than 100,000 steps: RLAP_E_TOO_LARGE, never truncated.  Scratch
+ * from the arena (RLAP_E_WORKSPACE when a caller-provided one is too small); one host synchronisation. */
+enum { RLAP_DROP_UNIFORM = 0, RLAP_DROP_DEGREE = 1, RLAP_DROP_PAGERANK = 2, RLAP_DROP_EIGENVECTOR = 3 };
+enum { RLAP_DROP_SINK = 0, RLAP_DROP_SOURCE = 1 };
+typedef struct {
+    int64_t rows_needed;      /* kept rows of all views: the rows of d_rows (written, or needed)      */
+    int64_t launches;         /* kernels the call enqueued                                            */
+    int64_t arena_bytes;      /* scratch bytes of the call                                            */
+    int32_t iters;            /* steps of the iteration (eigenvector: until it stopped)               */
+    int32_t converged;        /* eigenvector: whether the stopping rule held within evc_max_iter      */
+    int32_t host_syncs;       /* host synchronisations of the call                                    */
+    int32_t pad;
+} rlap_edge_drop_info;
+
+int rlap_edge_drop(rlap_handle h, const int64_t* d_src, const int64_t* d_dst, const double* d_w, int64_t E, int64_t num_nodes, int scheme,
+                   int flags, const double* h_p, int64_t K, double threshold, uint64_t seed, double pr_damp, int64_t pr_iters,
+                   double evc_tol, int64_t evc_max_iter, double* d_rows, int64_t out_cap_rows, int64_t* d_ptr, uint8_t* d_mask,
+                   double* d_centrality, double* d_node_weight, rlap_edge_drop_info* h_info);
 
 /* Per-graph readout of batched node embeddings: y[l, g, :] = the sum (or mean) of x[l, i, :] over the ids i of graph g,
  * [node_ptr[g], node_ptr[g+1]) -- what global_add_pool(z, batch) does after every GIN layer of a graph-level step, without float

@@ -26,7 +26,7 @@ EXPORTS = [
     "rlap_infonce_pair", "rlap_infonce_pair_backward",
     "rlap_cca_loss", "rlap_cca_loss_backward",
     "rlap_g2l_jsd", "rlap_g2l_jsd_backward", "rlap_g2l_bootstrap", "rlap_g2l_bootstrap_backward",
-    "rlap_linear_probe", "rlap_probe_scores",
+    "rlap_linear_probe", "rlap_probe_scores", "rlap_edge_drop",
 ]
 
 E_INDEX_RANGE = 2   # RLAP_E_INDEX_RANGE
@@ -44,6 +44,10 @@ SPMM_TRANSPOSE, SPMM_X_F32, SPMM_X_PER_LAYER = 16, 32, 64
 # rlap_snapshot_plan_build flags (beside the first three of rlap_snapshot_gcn_norm): the directions to build
 PLAN_FORWARD, PLAN_TRANSPOSED = 256, 512
 PLAN_MAGIC = 0x504C414E   # rlap_plan_desc.magic of a successful build
+# rlap_edge_drop schemes and flags
+DROP_SCHEMES = {"uniform": 0, "degree": 1, "pagerank": 2, "eigenvector": 3}
+DROP_SOURCE = 1
+DROP_MAX_VIEWS = 32
 # rlap_graph_readout flags
 READOUT_MEAN, READOUT_X_F32 = 1, 32
 # rlap_infonce flags
@@ -192,6 +196,14 @@ class ProbeInfo(_Report):
     ]
 
 
+class EdgeDropInfo(_Report):
+    """rlap_edge_drop_info (include/rlap_hip.h)."""
+    _fields_ = [
+        ("rows_needed", ctypes.c_int64), ("launches", ctypes.c_int64), ("arena_bytes", ctypes.c_int64), ("iters", ctypes.c_int32),
+        ("converged", ctypes.c_int32), ("host_syncs", ctypes.c_int32), ("pad", ctypes.c_int32),
+    ]
+
+
 def load():
     """dlopen the library and declare prototypes. Raises if it is not built."""
     global _lib
@@ -282,6 +294,9 @@ def load():
                                       vp, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(ProbeInfo)]
     lib.rlap_probe_scores.restype = ci
     lib.rlap_probe_scores.argtypes = [vp, vp, i64, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(ProbeInfo)]
+    lib.rlap_edge_drop.restype = ci
+    lib.rlap_edge_drop.argtypes = [vp, vp, vp, vp, i64, i64, ci, ci, ctypes.POINTER(dbl), i64, dbl, u64, dbl, i64, dbl, i64, vp, i64, vp, vp, vp, vp,
+                                   ctypes.POINTER(EdgeDropInfo)]
     lib.rlap_approx_chol_views.restype = ci
     lib.rlap_approx_chol_views.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, vp, ci, ci, vp, u64, vp, i64, vp,
                                            ctypes.POINTER(Stats)]

@@ -23,6 +23,8 @@ Mirrors of the reference's L2 adapters that keep everything on the GPU:
   * `CCAContrast` -- the loss of CCA-SSG/main.py on the embeddings of two views, fused on the device (ops.cca_loss);
                   `drop_feature` -- CCA-SSG/aug.py's feature masking (also A.FeatureMasking), one mask per view
   * `rLapChain` -- the chain of scripts/rlap_vc_spectral.py: eliminate, relabel the survivors 0..k-1, eliminate again
+  * `EdgeDropping`, `EdgeDroppingDegree`, `EdgeDroppingPR`, `EdgeDroppingEVC` -- the comparison arms of
+                  scripts/augmentor_benchmarks.py:216-363 on the device (ops.drop_edges); `EdgeDroppingViews` -- K of them from one call
 PyGCL / DGL are optional: with them installed the classes return their graph types,
 without them a small named tuple with the same fields.
 """
@@ -705,7 +707,7 @@ class rLapChain:
 class _ViewAugmentor:
     """One sibling of rLapViews.augmentors(): `aug(x, edge_index, edge_weight)` or `aug.augment(g)`."""
 
-    def __init__(self, parent: rLapViews, k: int):
+    def __init__(self, parent, k: int):
         self.parent, self.k = parent, k
 
     def augment(self, g):
@@ -713,6 +715,94 @@ class _ViewAugmentor:
 
     def __call__(self, x, edge_index, edge_weight=None):
         return self.augment(Graph(x, edge_index, edge_weight))
+
+
+class _EdgeDrop:
+    """What the four edge-dropping augmentors share: one ops.drop_edges call, one view.  `seed=None` (the default) draws a fresh
+    seed from torch's RNG at every call, as adapters.rLap does, so two augmentors built with the same arguments -- the reference's
+    `(aug1, aug2)` -- and two calls of one give independent views; an integer seed makes every call return the same view.
+    `last_seed` is the seed of the latest call.  num_nodes is edge_index.max() + 1, as the reference's lines compute it: one
+    reduction and read-back in front of the call."""
+    scheme = "uniform"
+
+    def __init__(self, p: float, threshold: float = 0.7, seed: Optional[int] = None, aggr: str = "sink"):
+        self.p, self.threshold, self.seed, self.aggr = p, threshold, seed, aggr
+        self.last_seed = None
+
+    def augment(self, g):
+        x, edge_index, edge_weights = g.unfold() if hasattr(g, "unfold") else g
+        self.last_seed = ops._seed_from(self.seed)
+        rows, _ = ops.drop_edges(edge_index, edge_weights, None, self.p, self.scheme, self.threshold, self.last_seed, self.aggr)
+        return _as_graph(x, rows[:, :2].long().t().contiguous(), rows[:, 2].contiguous() if edge_weights is not None else None)
+
+    def __call__(self, x, edge_index, edge_weight=None):
+        return self.augment(Graph(x, edge_index, edge_weight))
+
+
+class EdgeDropping(_EdgeDrop):
+    """PyGCL's EdgeDropping(pe=p) on the device: every edge is dropped with probability p (ops.drop_edges, scheme "uniform").
+    `aug(x, edge_index, edge_weight)` or `aug.augment(g)`; the edges keep their input order and their weights."""
+
+    def __init__(self, p: float, seed: Optional[int] = None):
+        super().__init__(p, 1.0, seed)
+
+
+class EdgeDroppingDegree(_EdgeDrop):
+    """scripts/augmentor_benchmarks.py:289-311 on the device (ops.drop_edges, scheme "degree")."""
+    scheme = "degree"
+
+
+class EdgeDroppingPR(_EdgeDrop):
+    """scripts/augmentor_benchmarks.py:314-336 on the device (ops.drop_edges, scheme "pagerank")."""
+    scheme = "pagerank"
+
+
+class EdgeDroppingEVC(_EdgeDrop):
+    """scripts/augmentor_benchmarks.py:339-363 on the device (ops.drop_edges, scheme "eigenvector"): the power iteration runs on the
+    device instead of a round trip through networkx on the host."""
+    scheme = "eigenvector"
+
+
+class EdgeDroppingViews:
+    """K edge-dropping views of a graph from ONE ops.drop_edges call: the centrality is found once, view k uses ps[k] and seed + k.
+    `seed=None` (the default) draws a fresh seed from torch's RNG at every call, as rLapViews does; an integer seed makes every call
+    return the same views; `last_seed` is the seed of the latest call.  `.augment(g)` returns the list of K graphs, `.augmentors()`
+    the PyGCL-style siblings for the `(aug1, aug2)` pair of the training scripts (as rLapViews.augmentors()), `.plan(g)` one
+    propagation plan over all K views for SnapshotGCNConv."""
+
+    def __init__(self, scheme: str = "degree", ps=(0.3, 0.4), threshold: float = 0.7, seed: Optional[int] = None, aggr: str = "sink"):
+        self.scheme, self.ps, self.threshold, self.seed, self.aggr = scheme, tuple(float(p) for p in ps), threshold, seed, aggr
+        if len(self.ps) < 1:
+            raise ValueError("ps: at least one drop parameter")
+        self._pending = None
+        self.last_seed = None
+
+    def _call(self, g, **kw):
+        x, edge_index, edge_weights = g.unfold() if hasattr(g, "unfold") else g
+        n = int(x.shape[0]) if x is not None else None
+        self.last_seed = ops._seed_from(self.seed)
+        return x, edge_weights, n, ops.drop_edges(edge_index, edge_weights, n, list(self.ps), self.scheme, self.threshold, self.last_seed, self.aggr, **kw)
+
+    def augment(self, g):
+        x, edge_weights, _, (rows, ptr) = self._call(g)
+        e = ptr.tolist()
+        ei = rows[:, :2].long().t().contiguous()
+        return [_as_graph(x, ei[:, e[k]:e[k + 1]], rows[e[k]:e[k + 1], 2] if edge_weights is not None else None) for k in range(len(self.ps))]
+
+    def plan(self, g, directions: str = "both", fill_value: float = 1.0):
+        """One plan over all K views (layer k is view k): ops.edge_list_plan on the call's (rows, ptr), the loops covering x.shape[0]
+        ids (edge_index.max() + 1 without x); weighted iff the graph has edge weights."""
+        x, edge_weights, n, (rows, ptr) = self._call(g)
+        if n is None:
+            edge_index = g.unfold()[1] if hasattr(g, "unfold") else g[1]
+            n = int(edge_index.max().item()) + 1 if edge_index.numel() else 0
+        return ops.edge_list_plan(rows, ptr, n, None, edge_weights is not None, True, fill_value, True, directions)
+
+    _key = staticmethod(rLapViews._key)
+    _view = rLapViews._view
+
+    def augmentors(self):
+        return [_ViewAugmentor(self, k) for k in range(len(self.ps))]
 
 
 def compute_ppr(edge_index: torch.Tensor, edge_weight: Optional[torch.Tensor], num_nodes: int, alpha: float = 0.2,

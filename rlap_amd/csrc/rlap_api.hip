@@ -25,6 +25,7 @@
 #include "rlap_gcn.h"
 #include "rlap_plan.h"
 #include "rlap_edgeplan.h"
+#include "rlap_edgedrop.h"
 #include "rlap_spmm_api.h"
 #include "rlap_spmm.h"
 #include "rlap_readout.h"
@@ -1537,6 +1538,43 @@ int rlap_edge_plan_build(rlap_handle h, const double* d_sc, int64_t m, const int
         }
         return rc;
     });
+}
+
+int rlap_edge_drop(rlap_handle h, const int64_t* d_src, const int64_t* d_dst, const double* d_w, int64_t E, int64_t num_nodes, int scheme,
+                   int flags, const double* h_p, int64_t K, double threshold, uint64_t seed, double pr_damp, int64_t pr_iters,
+                   double evc_tol, int64_t evc_max_iter, double* d_rows, int64_t out_cap_rows, int64_t* d_ptr, uint8_t* d_mask,
+                   double* d_centrality, double* d_node_weight, rlap_edge_drop_info* h_info) {
+    if (h_info) *h_info = rlap_edge_drop_info{};
+    if (!h || E < 0 || num_nodes < 0 || (E > 0 && (!d_src || !d_dst)) || !h_p || K < 1 || !d_ptr) return RLAP_E_BAD_ARG;
+    if (out_cap_rows < 0 || (out_cap_rows > 0 && !d_rows)) return RLAP_E_BAD_ARG;
+    if (scheme < 0 || scheme >= edgedrop::SCHEMES || (flags & ~RLAP_DROP_SOURCE)) return RLAP_E_BAD_ARG;
+    if (E >= INT32_MAX || num_nodes >= (int64_t)1 << 31 || K > edgedrop::MAX_VIEWS) return RLAP_E_TOO_LARGE;
+    if (!(threshold >= 0.0 && threshold <= 1.0)) return RLAP_E_BAD_ARG;
+    for (int64_t k = 0; k < K; ++k)
+        if (!(h_p[k] >= 0.0 && h_p[k] <= 1.0)) return RLAP_E_BAD_ARG;
+    if (scheme == RLAP_DROP_PAGERANK && (!(pr_damp >= 0.0 && pr_damp <= 1.0) || pr_iters < 0)) return RLAP_E_BAD_ARG;
+    if (scheme == RLAP_DROP_EIGENVECTOR && (!(evc_tol >= 0.0) || !std::isfinite(evc_tol) || evc_max_iter < 1)) return RLAP_E_BAD_ARG;
+    if ((scheme == RLAP_DROP_PAGERANK && pr_iters > edgedrop::MAX_PR_ITERS) || (scheme == RLAP_DROP_EIGENVECTOR && evc_max_iter > edgedrop::MAX_EVC_ITERS))
+        return RLAP_E_TOO_LARGE;
+    EdgeDropArgs a{};
+    a.src = d_src; a.dst = d_dst; a.w = d_w; a.E = E; a.N = num_nodes; a.scheme = scheme; a.source = (flags & RLAP_DROP_SOURCE) ? 1 : 0;
+    for (int64_t k = 0; k < K; ++k) a.p[k] = h_p[k];
+    a.K = (int)K; a.threshold = threshold; a.seed = seed; a.damp = pr_damp; a.pr_iters = pr_iters; a.evc_tol = evc_tol;
+    a.evc_max_iter = evc_max_iter; a.rows = d_rows; a.cap = out_cap_rows; a.ptr = d_ptr; a.mask = d_mask; a.centrality = d_centrality;
+    a.node_weight = d_node_weight;
+    // (debug poison: no result may depend on what the arena or any of the five result buffers held)
+    const size_t nodes = (size_t)num_nodes, KE = (size_t)K * (size_t)E;
+    int64_t arena_bytes = 0;
+    EdgeDropReport rep{};
+    const int rc = poisoned_call(h, [&] { return edge_drop_bytes(E, num_nodes, (int)K, scheme); },
+                                 {{d_rows, sizeof(double) * 3 * (size_t)out_cap_rows}, {d_ptr, sizeof(int64_t) * (size_t)(K + 1)}, {d_mask, KE},
+                                  {d_centrality, sizeof(double) * nodes}, {d_node_weight, sizeof(double) * nodes}},
+                                 &arena_bytes, [&](void* base, size_t have) { return edge_drop_run(h->stream, base, have, a, &rep); });
+    if (h_info) {
+        h_info->rows_needed = rep.rows_needed; h_info->launches = rep.launches; h_info->arena_bytes = arena_bytes;
+        h_info->iters = rep.iters; h_info->converged = rep.converged; h_info->host_syncs = rep.host_syncs;
+    }
+    return rc;
 }
 
 int rlap_snapshot_plan_propagate(rlap_handle h, const void* d_plan, const rlap_plan_desc* h_desc, int flags, const void* d_x, int64_t F,

@@ -2060,6 +2060,132 @@ def edge_plan(
     return edge_list_plan(rows, [0, E], n, None, edge_weight is not None, add_self_loops, fill, normalize, directions)
 
 
+DROP_AGGR = {"sink": 0, "source": _lib.DROP_SOURCE}
+DROP_MAX_STEPS = 100000   # cap on pr_iters and evc_max_iter (rlap_amd/csrc/rlap_edgedrop.h)
+
+
+def _count(x, what: str, lo: int, hi: int) -> int:
+    if isinstance(x, bool) or not hasattr(x, "__index__") or not lo <= x.__index__() <= hi:
+        raise ValueError(f"{what}: an integer in [{lo}, {hi}], got {x!r}")
+    return x.__index__()
+
+
+def _unit(x, what: str) -> float:
+    """A number in [0, 1]: anything with __float__ that is no bool or string (Python and numpy scalars, 0-d tensors)."""
+    try:
+        v = None if isinstance(x, (bool, str, bytes)) or not hasattr(x, "__float__") else float(x)
+    except (TypeError, ValueError, RuntimeError):
+        v = None
+    if v is None or not 0.0 <= v <= 1.0:
+        raise ValueError(f"{what}: a number in [0, 1], got {x!r}")
+    return v
+
+
+def _drop_ps(p) -> list:
+    """The K values of `p`: one number, or any sequence of them (list, tuple, ndarray, 1-D tensor)."""
+    if isinstance(p, (str, bytes)) or getattr(p, "ndim", 1) == 0 or not hasattr(p, "__iter__"):
+        ps = [p]
+    else:
+        ps = list(p.tolist() if hasattr(p, "tolist") else p)
+    if not 1 <= len(ps) <= _lib.DROP_MAX_VIEWS:
+        raise ValueError(f"p: one number or a sequence of 1 to {_lib.DROP_MAX_VIEWS} numbers, got {len(ps)}")
+    return [_unit(v, "p") for v in ps]
+
+
+def _drop_args(edge_index, edge_weight, num_nodes, p, scheme, threshold, seed, aggr, pr_damp, pr_iters, evc_tol, evc_max_iter):
+    """Host-side checks of drop_edges, made before anything is launched: (E, n or None, the K values of p, the export's scalars)."""
+    if not isinstance(edge_index, Tensor) or edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise ValueError("edge_index: a (2, E) integer tensor")
+    if edge_index.dtype.is_floating_point or edge_index.dtype.is_complex or edge_index.dtype == torch.bool:
+        raise ValueError(f"edge_index: an integer tensor, got {edge_index.dtype}")
+    E = int(edge_index.shape[1])
+    if edge_weight is not None:
+        if not isinstance(edge_weight, Tensor) or edge_weight.dim() != 1 or edge_weight.shape[0] != E:
+            raise ValueError(f"edge_weight: a ({E},) tensor, one weight per column of edge_index")
+        if not edge_weight.dtype.is_floating_point:
+            raise ValueError(f"edge_weight: a floating-point tensor, got {edge_weight.dtype}")
+    n = None if num_nodes is None else _num_nodes(num_nodes)
+    ps = _drop_ps(p)
+    if scheme not in _lib.DROP_SCHEMES:
+        raise ValueError(f"scheme: one of {sorted(_lib.DROP_SCHEMES)}, got {scheme!r}")
+    if aggr not in DROP_AGGR:
+        raise ValueError(f"aggr: one of {sorted(DROP_AGGR)}, got {aggr!r} (aggr='mean' needs a per-edge maximum and is not provided)")
+    if seed is not None and (isinstance(seed, bool) or not hasattr(seed, "__index__")):
+        raise ValueError(f"seed: an integer or None, got {seed!r}")
+    if isinstance(evc_tol, bool) or not isinstance(evc_tol, (int, float)) or not 0.0 <= float(evc_tol) < float("inf"):
+        raise ValueError(f"evc_tol: a finite number >= 0, got {evc_tol!r}")
+    scalars = (_unit(threshold, "threshold"), _seed_from(None if seed is None else seed.__index__()), _unit(pr_damp, "pr_damp"),
+               _count(pr_iters, "pr_iters", 0, DROP_MAX_STEPS), float(evc_tol), _count(evc_max_iter, "evc_max_iter", 1, DROP_MAX_STEPS))
+    return E, n, ps, scalars
+
+
+def drop_edges(
+    edge_index: Tensor,
+    edge_weight: Optional[Tensor] = None,
+    num_nodes: Optional[int] = None,
+    p=0.5,
+    scheme: str = "uniform",
+    threshold: float = 0.7,
+    seed: Optional[int] = 0,
+    aggr: str = "sink",
+    pr_damp: float = 0.85,
+    pr_iters: int = 10,
+    evc_tol: float = 1e-6,
+    evc_max_iter: int = 1000,
+    return_mask: bool = False,
+    return_scores: bool = False,
+):
+    """Centrality-adaptive edge dropping on the device, K views a call: EdgeDropping, EdgeDroppingDegree, EdgeDroppingPR and
+    EdgeDroppingEVC of scripts/augmentor_benchmarks.py:216-363 (GCA's adaptive schemes) -- `scheme` "uniform", "degree", "pagerank",
+    "eigenvector".  `edge_index` is (2, E), source row 0 and target row 1, in any order; duplicates, loops and directed edges stay as
+    they are; a batch of graphs is its disjoint union.  `edge_weight` (E,) is carried to the output and never read for the scores.
+    `num_nodes=None` means edge_index.max() + 1 (one torch reduction and read-back in front of the call).  `p` is one number or a
+    sequence of K <= 32 numbers in [0, 1]: view k uses p[k] and seed + k, and equals a one-view call with those, bit for bit.
+    `seed=None` draws a seed from torch's RNG (the adapters' default); with an integer the call is a pure function of its arguments.  `aggr`: a row's score is that of its target ("sink", the
+    reference's choice) or of its source ("source").
+
+    The centrality c is found once for all views: the degree after to_undirected; compute_pr's `pr_iters` steps with `pr_damp`; the
+    power iteration of networkx's eigenvector_centrality on the multigraph of the rows (duplicates count), stopped after the step
+    with sum |x' - x| <= N evc_tol or after `evc_max_iter` steps, then max(x, 0) + 1e-8.  With s = log c, taken over the rows:
+    node_weight = ((smax - s) / (smax - smean)) / their mean; row e is dropped in view k with probability
+    q = min(node_weight[endpoint] p[k], threshold) -- a NaN gives threshold -- and kept iff u(k, e) >= q, u a counter-based uniform
+    of (seed + k, e).  Every rule and the order of every sum: rlap_amd/csrc/rlap_edgedrop.h.  All float64.
+
+    Returns (rows, ptr): rows (M, 3) float64 [source, target, weight] (weight 1.0 without edge_weight), view-major, input order
+    inside a view; ptr (K+1,) int64; both on the device -- what edge_list_plan takes.  With return_mask a (K, E) bool tensor follows,
+    with return_scores a dict: centrality (N,), node_weight (N,) (zeros for "uniform"), iters, converged.  The same input gives
+    the same bits.  Malformed arguments raise ValueError before the device is touched; an id outside [0, num_nodes) raises
+    ValueError.  One host synchronisation inside the C call (num_nodes=None adds the read-back above); `last_stats` holds
+    rlap_edge_drop_info."""
+    E, n, ps, scalars = _drop_args(edge_index, edge_weight, num_nodes, p, scheme, threshold, seed, aggr, pr_damp, pr_iters, evc_tol, evc_max_iter)
+    K = len(ps)
+    dev = _device_for(edge_index)
+    with torch.cuda.device(dev):
+        ei = edge_index.to(device=dev, dtype=torch.int64)
+        src, dst = ei[0].contiguous(), ei[1].contiguous()
+        w = edge_weight.detach().to(device=dev, dtype=torch.float64).contiguous() if edge_weight is not None else None
+        if n is None:
+            n = int(ei.max().item()) + 1 if E else 0
+        cap = K * E
+        rows = torch.empty((cap, 3), dtype=torch.float64, device=dev)
+        ptr = torch.empty(K + 1, dtype=torch.int64, device=dev)
+        mask = torch.empty((K, E), dtype=torch.bool, device=dev) if return_mask else None
+        cen = torch.empty(n, dtype=torch.float64, device=dev) if return_scores else None
+        nw = torch.empty(n, dtype=torch.float64, device=dev) if return_scores else None
+        threshold, seed, pr_damp, pr_iters, evc_tol, evc_max_iter = scalars
+        info = _device_call("rlap_edge_drop", _lib.EdgeDropInfo, dev, 1, (
+            src.data_ptr() if E else None, dst.data_ptr() if E else None, w.data_ptr() if w is not None and E else None, E, n,
+            _lib.DROP_SCHEMES[scheme], DROP_AGGR[aggr], (ctypes.c_double * K)(*ps), K, threshold, seed, pr_damp, pr_iters, evc_tol, evc_max_iter,
+            rows.data_ptr() if cap else None, cap, ptr.data_ptr(), mask.data_ptr() if mask is not None and E else None,
+            cen.data_ptr() if cen is not None and n else None, nw.data_ptr() if nw is not None and n else None))
+        out = [_trim(rows, int(info.rows_needed)), ptr]
+    if return_mask:
+        out.append(mask)
+    if return_scores:
+        out.append({"centrality": cen, "node_weight": nw, "iters": int(info.iters), "converged": bool(info.converged)})
+    return tuple(out)
+
+
 def identity(a: Tensor) -> Tensor:
     """Boundary self-test (reference: rlap/ops.py:61-63): tensor -> column-major
     staging -> tensor, on the GPU; returns a tensor on `a`'s device."""
