@@ -50,7 +50,7 @@ enum {
     RLAP_E_INTERNAL = 10,
     RLAP_E_WORKSPACE = 11,    /* caller-provided workspace / uniform table too small: rlap_workspace_needed() says how much */
     RLAP_E_NOT_GROUPED = 12,  /* rlap_snapshot_stats: a column id starts two separate blocks of rows in one segment */
-    RLAP_E_OUT_CAPACITY = 13  /* rlap_snapshot_ppr, rlap_edge_drop: the kept entries exceed out_cap_rows; nothing written, rows_needed reported */
+    RLAP_E_OUT_CAPACITY = 13  /* rlap_snapshot_ppr, rlap_edge_drop, rlap_node_sample: the kept entries exceed out_cap_rows; nothing written, rows_needed reported */
 };
 
 typedef struct {
@@ -527,6 +527,43 @@ int rlap_edge_drop(rlap_handle h, const int64_t* d_src, const int64_t* d_dst, co
                    int flags, const double* h_p, int64_t K, double threshold, uint64_t seed, double pr_damp, int64_t pr_iters,
                    double evc_tol, int64_t evc_max_iter, double* d_rows, int64_t out_cap_rows, int64_t* d_ptr, uint8_t* d_mask,
                    double* d_centrality, double* d_node_weight, rlap_edge_drop_info* h_info);
+
+/* Node dropping and random-walk subgraph views, K views a call: PyGCL's NodeDropping and RWSampling as the training
+ * scripts use them, on the device.  A view is a node set -- drop: node v stays iff its coin u_node(k, v) >= p[k]; walk: every node
+ * that num_seeds[k] uniform random walks of walk_length steps visit, starts included -- and row e is in view k iff its source and
+ * its target are both in the set; ids are not relabelled.  Every rule -- both coins, the pick, a step of a walk -- is defined in
+ * rlap_amd/csrc/rlap_nodesample.h.
+ *   d_src, d_dst, E    : the rows (source, target), int64 on the device, in any order; duplicates, loops and directed rows stay
+ *   d_w                : (nullable) one weight a row, carried to the output and never read otherwise; NULL: 1.0
+ *   num_nodes          : every id lies in [0, num_nodes)
+ *   scheme             : RLAP_SAMPLE_DROP or RLAP_SAMPLE_WALK
+ *   h_p                : drop: K drop probabilities in [0, 1] ON THE HOST (walk: not read, may be NULL)
+ *   h_num_seeds        : walk: K walker counts in [0, 2^31) ON THE HOST (drop: not read, may be NULL)
+ *   K                  : 1 <= K <= 32; view k uses h_p[k] or h_num_seeds[k], and seed + k
+ *   walk_length        : walk: steps of a walk, in [0, 1024]; a walker on a node without outgoing rows stays there
+ *   d_rows, out_cap_rows  : (out_cap_rows, 3) f64 rows [source, target, weight], view-major, input order inside a view
+ *   d_ptr              : [K+1] row offsets of the views in d_rows
+ *   d_node_mask        : (nullable) (K, num_nodes) bytes: 1 where the node is in the view's set
+ *   d_walks            : (nullable, walk only) (sum of h_num_seeds, walk_length + 1) int64: the walks, view-major
+ *   h_info             : (nullable) what the call did
+ * View k of a K-view call equals a one-view call with (h_p[k] or h_num_seeds[k], seed + k); the same input gives the same bits; the
+ * only atomics are integer ORs into a bitmap.  More kept rows than out_cap_rows: RLAP_E_OUT_CAPACITY, no row written,
+ * h_info->rows_needed says how many.  An id outside [0, num_nodes): RLAP_E_INDEX_RANGE.  A null pointer, K < 1, a parameter out of
+ * its range, an unknown scheme, d_walks with drop, walkers without nodes: RLAP_E_BAD_ARG.  E >= 2^31 - 1, num_nodes >= 2^31, K > 32
+ * or a walker count >= 2^31: RLAP_E_TOO_LARGE, never truncated.  Scratch from the arena (RLAP_E_WORKSPACE when a caller-provided one
+ * is too small); one host synchronisation. */
+enum { RLAP_SAMPLE_DROP = 0, RLAP_SAMPLE_WALK = 1 };
+typedef struct {
+    int64_t rows_needed;      /* kept rows of all views: the rows of d_rows (written, or needed)      */
+    int64_t launches;         /* kernels the call enqueued                                            */
+    int64_t arena_bytes;      /* scratch bytes of the call                                            */
+    int32_t host_syncs;       /* host synchronisations of the call                                    */
+    int32_t pad;
+} rlap_node_sample_info;
+
+int rlap_node_sample(rlap_handle h, const int64_t* d_src, const int64_t* d_dst, const double* d_w, int64_t E, int64_t num_nodes, int scheme,
+                     const double* h_p, const int64_t* h_num_seeds, int64_t K, int64_t walk_length, uint64_t seed, double* d_rows,
+                     int64_t out_cap_rows, int64_t* d_ptr, uint8_t* d_node_mask, int64_t* d_walks, rlap_node_sample_info* h_info);
 
 /* Per-graph readout of batched node embeddings: y[l, g, :] = the sum (or mean) of x[l, i, :] over the ids i of graph g,
  * [node_ptr[g], node_ptr[g+1]) -- what global_add_pool(z, batch) does after every GIN layer of a graph-level step, without float

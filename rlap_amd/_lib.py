@@ -26,7 +26,7 @@ EXPORTS = [
     "rlap_infonce_pair", "rlap_infonce_pair_backward",
     "rlap_cca_loss", "rlap_cca_loss_backward",
     "rlap_g2l_jsd", "rlap_g2l_jsd_backward", "rlap_g2l_bootstrap", "rlap_g2l_bootstrap_backward",
-    "rlap_linear_probe", "rlap_probe_scores", "rlap_edge_drop",
+    "rlap_linear_probe", "rlap_probe_scores", "rlap_edge_drop", "rlap_node_sample",
 ]
 
 E_INDEX_RANGE = 2   # RLAP_E_INDEX_RANGE
@@ -48,6 +48,10 @@ PLAN_MAGIC = 0x504C414E   # rlap_plan_desc.magic of a successful build
 DROP_SCHEMES = {"uniform": 0, "degree": 1, "pagerank": 2, "eigenvector": 3}
 DROP_SOURCE = 1
 DROP_MAX_VIEWS = 32
+# rlap_node_sample schemes and limits
+SAMPLE_SCHEMES = {"drop": 0, "walk": 1}
+SAMPLE_MAX_WALK_LENGTH = 1024
+SAMPLE_MAX_SEEDS = 2**31 - 1
 # rlap_graph_readout flags
 READOUT_MEAN, READOUT_X_F32 = 1, 32
 # rlap_infonce flags
@@ -204,6 +208,14 @@ class EdgeDropInfo(_Report):
     ]
 
 
+class NodeSampleInfo(_Report):
+    """rlap_node_sample_info (include/rlap_hip.h)."""
+    _fields_ = [
+        ("rows_needed", ctypes.c_int64), ("launches", ctypes.c_int64), ("arena_bytes", ctypes.c_int64), ("host_syncs", ctypes.c_int32),
+        ("pad", ctypes.c_int32),
+    ]
+
+
 def load():
     """dlopen the library and declare prototypes. Raises if it is not built."""
     global _lib
@@ -297,6 +309,9 @@ def load():
     lib.rlap_edge_drop.restype = ci
     lib.rlap_edge_drop.argtypes = [vp, vp, vp, vp, i64, i64, ci, ci, ctypes.POINTER(dbl), i64, dbl, u64, dbl, i64, dbl, i64, vp, i64, vp, vp, vp, vp,
                                    ctypes.POINTER(EdgeDropInfo)]
+    lib.rlap_node_sample.restype = ci
+    lib.rlap_node_sample.argtypes = [vp, vp, vp, vp, i64, i64, ci, ctypes.POINTER(dbl), ctypes.POINTER(i64), i64, i64, u64, vp, i64, vp, vp, vp,
+                                     ctypes.POINTER(NodeSampleInfo)]
     lib.rlap_approx_chol_views.restype = ci
     lib.rlap_approx_chol_views.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, vp, ci, ci, vp, u64, vp, i64, vp,
                                            ctypes.POINTER(Stats)]

@@ -25,6 +25,8 @@ Mirrors of the reference's L2 adapters that keep everything on the GPU:
   * `rLapChain` -- the chain of scripts/rlap_vc_spectral.py: eliminate, relabel the survivors 0..k-1, eliminate again
   * `EdgeDropping`, `EdgeDroppingDegree`, `EdgeDroppingPR`, `EdgeDroppingEVC` -- the comparison arms of
                   scripts/augmentor_benchmarks.py:216-363 on the device (ops.drop_edges); `EdgeDroppingViews` -- K of them from one call
+  * `NodeDropping`, `RWSampling` -- PyGCL's node-sampling arms (scripts/node_shared.py:458-470) on the device
+                  (ops.sample_subgraphs); `NodeSampleViews` -- K of them from one call
 PyGCL / DGL are optional: with them installed the classes return their graph types,
 without them a small named tuple with the same fields.
 """
@@ -782,6 +784,94 @@ class EdgeDroppingViews:
         n = int(x.shape[0]) if x is not None else None
         self.last_seed = ops._seed_from(self.seed)
         return x, edge_weights, n, ops.drop_edges(edge_index, edge_weights, n, list(self.ps), self.scheme, self.threshold, self.last_seed, self.aggr, **kw)
+
+    def augment(self, g):
+        x, edge_weights, _, (rows, ptr) = self._call(g)
+        e = ptr.tolist()
+        ei = rows[:, :2].long().t().contiguous()
+        return [_as_graph(x, ei[:, e[k]:e[k + 1]], rows[e[k]:e[k + 1], 2] if edge_weights is not None else None) for k in range(len(self.ps))]
+
+    def plan(self, g, directions: str = "both", fill_value: float = 1.0):
+        """One plan over all K views (layer k is view k): ops.edge_list_plan on the call's (rows, ptr), the loops covering x.shape[0]
+        ids (edge_index.max() + 1 without x); weighted iff the graph has edge weights."""
+        x, edge_weights, n, (rows, ptr) = self._call(g)
+        if n is None:
+            edge_index = g.unfold()[1] if hasattr(g, "unfold") else g[1]
+            n = int(edge_index.max().item()) + 1 if edge_index.numel() else 0
+        return ops.edge_list_plan(rows, ptr, n, None, edge_weights is not None, True, fill_value, True, directions)
+
+    _key = staticmethod(rLapViews._key)
+    _view = rLapViews._view
+
+    def augmentors(self):
+        return [_ViewAugmentor(self, k) for k in range(len(self.ps))]
+
+
+class _NodeSample:
+    """What the two node-sampling augmentors share: one ops.sample_subgraphs call, one view.  `seed=None` (the default) draws a fresh
+    seed from torch's RNG at every call, as _EdgeDrop does, so the reference's `(aug1, aug2)` and two calls of one give independent
+    views; an integer seed makes every call return the same view.  `last_seed` is the seed of the latest call.  num_nodes is
+    edge_index.max() + 1, as PyGCL computes it: one reduction and read-back in front of the call."""
+    scheme = "drop"
+
+    def _params(self):
+        raise NotImplementedError
+
+    def augment(self, g):
+        x, edge_index, edge_weights = g.unfold() if hasattr(g, "unfold") else g
+        self.last_seed = ops._seed_from(self.seed)
+        rows, _ = ops.sample_subgraphs(edge_index, edge_weights, None, self.scheme, seed=self.last_seed, **self._params())
+        return _as_graph(x, rows[:, :2].long().t().contiguous(), rows[:, 2].contiguous() if edge_weights is not None else None)
+
+    def __call__(self, x, edge_index, edge_weight=None):
+        return self.augment(Graph(x, edge_index, edge_weight))
+
+
+class NodeDropping(_NodeSample):
+    """PyGCL's NodeDropping(pn) on the device: every node is dropped with probability pn, an edge stays iff both its ends do
+    (ops.sample_subgraphs, scheme "drop").  `aug(x, edge_index, edge_weight)` or `aug.augment(g)`; the edges keep their input order,
+    their ids and their weights."""
+
+    def __init__(self, pn: float, seed: Optional[int] = None):
+        self.pn, self.seed, self.last_seed = pn, seed, None
+
+    def _params(self):
+        return {"p": self.pn}
+
+
+class RWSampling(_NodeSample):
+    """PyGCL's RWSampling(num_seeds, walk_length) on the device: the subgraph among the nodes that num_seeds uniform random walks
+    of walk_length steps visit (ops.sample_subgraphs, scheme "walk")."""
+    scheme = "walk"
+
+    def __init__(self, num_seeds: int, walk_length: int = 10, seed: Optional[int] = None):
+        self.num_seeds, self.walk_length, self.seed, self.last_seed = num_seeds, walk_length, seed, None
+
+    def _params(self):
+        return {"num_seeds": self.num_seeds, "walk_length": self.walk_length}
+
+
+class NodeSampleViews:
+    """K node-sampling views of a graph from ONE ops.sample_subgraphs call: view k uses ps_or_seeds[k] -- a drop probability for
+    scheme "drop", a number of walkers for "walk" -- and seed + k.  `seed=None` (the default) draws a fresh seed from torch's RNG at
+    every call, as EdgeDroppingViews does; an integer seed makes every call return the same views; `last_seed` is the seed of the
+    latest call.  `.augment(g)` returns the list of K graphs, `.augmentors()` the PyGCL-style siblings for the `(aug1, aug2)` pair
+    of the training scripts, `.plan(g)` one propagation plan over all K views for SnapshotGCNConv."""
+
+    def __init__(self, scheme: str = "drop", ps_or_seeds=(0.3, 0.4), walk_length: int = 10, seed: Optional[int] = None):
+        self.scheme, self.walk_length, self.seed = scheme, walk_length, seed
+        self.ps = tuple(ps_or_seeds)
+        if len(self.ps) < 1:
+            raise ValueError("ps_or_seeds: at least one view")
+        self._pending = None
+        self.last_seed = None
+
+    def _call(self, g, **kw):
+        x, edge_index, edge_weights = g.unfold() if hasattr(g, "unfold") else g
+        n = int(x.shape[0]) if x is not None else None
+        self.last_seed = ops._seed_from(self.seed)
+        params = {"p": list(self.ps)} if self.scheme == "drop" else {"num_seeds": list(self.ps), "walk_length": self.walk_length}
+        return x, edge_weights, n, ops.sample_subgraphs(edge_index, edge_weights, n, self.scheme, seed=self.last_seed, **params, **kw)
 
     def augment(self, g):
         x, edge_weights, _, (rows, ptr) = self._call(g)

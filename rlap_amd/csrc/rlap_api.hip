@@ -26,6 +26,7 @@
 #include "rlap_plan.h"
 #include "rlap_edgeplan.h"
 #include "rlap_edgedrop.h"
+#include "rlap_nodesample.h"
 #include "rlap_spmm_api.h"
 #include "rlap_spmm.h"
 #include "rlap_readout.h"
@@ -1538,6 +1539,48 @@ int rlap_edge_plan_build(rlap_handle h, const double* d_sc, int64_t m, const int
         }
         return rc;
     });
+}
+
+int rlap_node_sample(rlap_handle h, const int64_t* d_src, const int64_t* d_dst, const double* d_w, int64_t E, int64_t num_nodes, int scheme,
+                     const double* h_p, const int64_t* h_num_seeds, int64_t K, int64_t walk_length, uint64_t seed, double* d_rows,
+                     int64_t out_cap_rows, int64_t* d_ptr, uint8_t* d_node_mask, int64_t* d_walks, rlap_node_sample_info* h_info) {
+    if (h_info) *h_info = rlap_node_sample_info{};
+    if (!h || E < 0 || num_nodes < 0 || (E > 0 && (!d_src || !d_dst)) || K < 1 || !d_ptr) return RLAP_E_BAD_ARG;
+    if (out_cap_rows < 0 || (out_cap_rows > 0 && !d_rows)) return RLAP_E_BAD_ARG;
+    if (scheme < 0 || scheme >= nodesample::SCHEMES) return RLAP_E_BAD_ARG;
+    const bool walk = scheme == RLAP_SAMPLE_WALK;
+    if (walk ? !h_num_seeds : !h_p) return RLAP_E_BAD_ARG;
+    if (!walk && d_walks) return RLAP_E_BAD_ARG;
+    if (E >= INT32_MAX || num_nodes >= (int64_t)1 << 31 || K > nodesample::MAX_VIEWS) return RLAP_E_TOO_LARGE;
+    NodeSampleArgs a{};
+    int64_t walkers = 0;
+    for (int64_t k = 0; k < K; ++k) {
+        if (walk) {
+            if (h_num_seeds[k] < 0) return RLAP_E_BAD_ARG;
+            if (h_num_seeds[k] >= (int64_t)1 << 31) return RLAP_E_TOO_LARGE;
+            a.seeds[k] = h_num_seeds[k];
+            walkers += h_num_seeds[k];
+        } else {
+            if (!(h_p[k] >= 0.0 && h_p[k] <= 1.0)) return RLAP_E_BAD_ARG;
+            a.p[k] = h_p[k];
+        }
+    }
+    if (walk && (walk_length < 0 || walk_length > nodesample::MAX_WALK_LENGTH || (walkers > 0 && num_nodes == 0))) return RLAP_E_BAD_ARG;
+    a.src = d_src; a.dst = d_dst; a.w = d_w; a.E = E; a.N = num_nodes; a.scheme = scheme; a.K = (int)K;
+    a.walk_length = walk ? walk_length : 0; a.seed = seed; a.rows = d_rows; a.cap = out_cap_rows; a.ptr = d_ptr;
+    a.node_mask = d_node_mask; a.walks = d_walks;
+    // (debug poison: no result may depend on what the arena or any of the four result buffers held)
+    int64_t arena_bytes = 0;
+    NodeSampleReport rep{};
+    const int rc = poisoned_call(h, [&] { return node_sample_bytes(E, num_nodes, (int)K, scheme, d_node_mask != nullptr); },
+                                 {{d_rows, sizeof(double) * 3 * (size_t)out_cap_rows}, {d_ptr, sizeof(int64_t) * (size_t)(K + 1)},
+                                  {d_node_mask, (size_t)K * (size_t)num_nodes}, {d_walks, sizeof(int64_t) * (size_t)walkers * (size_t)(walk_length + 1)}},
+                                 &arena_bytes, [&](void* base, size_t have) { return node_sample_run(h->stream, base, have, a, &rep); });
+    if (h_info) {
+        h_info->rows_needed = rep.rows_needed; h_info->launches = rep.launches; h_info->arena_bytes = arena_bytes;
+        h_info->host_syncs = rep.host_syncs;
+    }
+    return rc;
 }
 
 int rlap_edge_drop(rlap_handle h, const int64_t* d_src, const int64_t* d_dst, const double* d_w, int64_t E, int64_t num_nodes, int scheme,

@@ -2186,6 +2186,112 @@ def drop_edges(
     return tuple(out)
 
 
+def _sample_seeds(num_seeds) -> list:
+    """The K values of `num_seeds`: one integer, or any sequence of them (list, tuple, ndarray, 1-D tensor)."""
+    if isinstance(num_seeds, (str, bytes)) or getattr(num_seeds, "ndim", 1) == 0 or not hasattr(num_seeds, "__iter__"):
+        ns = [num_seeds]
+    else:
+        ns = list(num_seeds.tolist() if hasattr(num_seeds, "tolist") else num_seeds)
+    if not 1 <= len(ns) <= _lib.DROP_MAX_VIEWS:
+        raise ValueError(f"num_seeds: one integer or a sequence of 1 to {_lib.DROP_MAX_VIEWS} integers, got {len(ns)}")
+    return [_count(v, "num_seeds", 0, _lib.SAMPLE_MAX_SEEDS) for v in ns]
+
+
+def _sample_args(edge_index, edge_weight, num_nodes, scheme, p, num_seeds, walk_length, seed, return_walks):
+    """Host-side checks of sample_subgraphs, made before anything is launched: (E, n or None, ps, seeds, walk_length, seed)."""
+    if not isinstance(edge_index, Tensor) or edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise ValueError("edge_index: a (2, E) integer tensor")
+    if edge_index.dtype.is_floating_point or edge_index.dtype.is_complex or edge_index.dtype == torch.bool:
+        raise ValueError(f"edge_index: an integer tensor, got {edge_index.dtype}")
+    E = int(edge_index.shape[1])
+    if edge_weight is not None:
+        if not isinstance(edge_weight, Tensor) or edge_weight.dim() != 1 or edge_weight.shape[0] != E:
+            raise ValueError(f"edge_weight: a ({E},) tensor, one weight per column of edge_index")
+        if not edge_weight.dtype.is_floating_point:
+            raise ValueError(f"edge_weight: a floating-point tensor, got {edge_weight.dtype}")
+    n = None if num_nodes is None else _num_nodes(num_nodes)
+    if scheme not in _lib.SAMPLE_SCHEMES:
+        raise ValueError(f"scheme: one of {sorted(_lib.SAMPLE_SCHEMES)}, got {scheme!r}")
+    ps, seeds, length = None, None, 0
+    if scheme == "drop":
+        ps = _drop_ps(p)
+        if return_walks:
+            raise ValueError("return_walks: only scheme='walk' has walks")
+    else:
+        if num_seeds is None:
+            raise ValueError("num_seeds: scheme='walk' needs one integer or a sequence of 1 to 32 integers, got None")
+        seeds = _sample_seeds(num_seeds)
+        length = _count(walk_length, "walk_length", 0, _lib.SAMPLE_MAX_WALK_LENGTH)
+        if any(seeds) and (n == 0 or (n is None and E == 0)):
+            raise ValueError("num_seeds: walkers need a node to start from, and num_nodes is 0")
+    if seed is not None and (isinstance(seed, bool) or not hasattr(seed, "__index__")):
+        raise ValueError(f"seed: an integer or None, got {seed!r}")
+    return E, n, ps, seeds, length, _seed_from(None if seed is None else seed.__index__())
+
+
+def sample_subgraphs(
+    edge_index: Tensor,
+    edge_weight: Optional[Tensor] = None,
+    num_nodes: Optional[int] = None,
+    scheme: str = "drop",
+    p=0.5,
+    num_seeds=None,
+    walk_length: int = 10,
+    seed: Optional[int] = 0,
+    return_nodes: bool = False,
+    return_walks: bool = False,
+):
+    """Node dropping and random-walk subgraph views on the device, K views a call: PyGCL's NodeDropping(pn) (`scheme` "drop") and
+    RWSampling(num_seeds, walk_length) ("walk") as the training scripts use them.  `edge_index` is (2, E), source row 0 and target
+    row 1, in any order; duplicates, loops and directed edges stay as they are; a batch of graphs is its disjoint union.
+    `edge_weight` (E,) is carried to the output and never read otherwise.  `num_nodes=None` means edge_index.max() + 1 (one torch
+    reduction and read-back in front of the call).  "drop" takes `p`, one number or a sequence of K <= 32 numbers in [0, 1] (and
+    ignores num_seeds and walk_length); "walk" takes `num_seeds`, one integer or K <= 32 integers >= 0, and `walk_length` in
+    [0, 1024] (and ignores p).  View k uses p[k] or num_seeds[k], and seed + k, and equals a one-view call with those, bit for
+    bit.  `seed=None` draws a seed from torch's RNG (the adapters' default); with an integer the call is a pure function of its
+    arguments.
+
+    A view is a node set, and a row is kept iff its source and its target are both in it (PyG's subgraph with
+    relabel_nodes=False: the ids stay).  drop: node v is in the set iff its coin u_node(seed + k, v) >= p[k], so p = 0 keeps every
+    node and p = 1 none.  walk: num_seeds[k] walkers start at uniform nodes and take walk_length steps, each to the target of a
+    uniformly chosen outgoing row of the node they stand on (duplicates and loops count; a node without outgoing rows keeps its
+    walker); the set is every node a walker stood on.  Every rule: rlap_amd/csrc/rlap_nodesample.h.
+
+    Returns (rows, ptr) as drop_edges does: rows (M, 3) float64 [source, target, weight] (weight 1.0 without edge_weight),
+    view-major, input order inside a view; ptr (K+1,) int64; both on the device -- what edge_list_plan takes.  With return_nodes a
+    (K, N) bool tensor follows, the node sets; with return_walks (walk only) a (sum of num_seeds, walk_length + 1) int64 tensor, the
+    walks, view-major.  The same input gives the same bits.  Malformed arguments, walkers without a node among them, raise ValueError
+    before the device is touched; an id outside [0, num_nodes) raises ValueError.  One host synchronisation inside the C call
+    (num_nodes=None adds the read-back above); `last_stats` holds rlap_node_sample_info."""
+    E, n, ps, seeds, length, seed = _sample_args(edge_index, edge_weight, num_nodes, scheme, p, num_seeds, walk_length, seed, return_walks)
+    K = len(ps if ps is not None else seeds)
+    dev = _device_for(edge_index)
+    with torch.cuda.device(dev):
+        ei = edge_index.to(device=dev, dtype=torch.int64)
+        src, dst = ei[0].contiguous(), ei[1].contiguous()
+        w = edge_weight.detach().to(device=dev, dtype=torch.float64).contiguous() if edge_weight is not None else None
+        if n is None:
+            n = int(ei.max().item()) + 1 if E else 0
+        cap = K * E
+        rows = torch.empty((cap, 3), dtype=torch.float64, device=dev)
+        ptr = torch.empty(K + 1, dtype=torch.int64, device=dev)
+        nodes = torch.empty((K, n), dtype=torch.bool, device=dev) if return_nodes else None
+        walkers = sum(seeds) if seeds is not None else 0
+        walks = torch.empty((walkers, length + 1), dtype=torch.int64, device=dev) if return_walks else None
+        info = _device_call("rlap_node_sample", _lib.NodeSampleInfo, dev, 1, (
+            src.data_ptr() if E else None, dst.data_ptr() if E else None, w.data_ptr() if w is not None and E else None, E, n,
+            _lib.SAMPLE_SCHEMES[scheme], (ctypes.c_double * K)(*ps) if ps is not None else None,
+            (ctypes.c_int64 * K)(*seeds) if seeds is not None else None, K, length, seed,
+            rows.data_ptr() if cap else None, cap, ptr.data_ptr(), nodes.data_ptr() if nodes is not None and n else None,
+            walks.data_ptr() if walks is not None and walkers else None))
+        out = [_trim(rows, int(info.rows_needed)), ptr]
+    if return_nodes:
+        out.append(nodes)
+    if return_walks:
+        out.append(walks)
+    return tuple(out)
+
+
 def identity(a: Tensor) -> Tensor:
     """Boundary self-test (reference: rlap/ops.py:61-63): tensor -> column-major
     staging -> tensor, on the GPU; returns a tensor on `a`'s device."""
