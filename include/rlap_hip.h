@@ -50,7 +50,7 @@ enum {
     RLAP_E_INTERNAL = 10,
     RLAP_E_WORKSPACE = 11,    /* caller-provided workspace / uniform table too small: rlap_workspace_needed() says how much */
     RLAP_E_NOT_GROUPED = 12,  /* rlap_snapshot_stats: a column id starts two separate blocks of rows in one segment */
-    RLAP_E_OUT_CAPACITY = 13  /* rlap_snapshot_ppr, rlap_edge_drop, rlap_node_sample: the kept entries exceed out_cap_rows; nothing written, rows_needed reported */
+    RLAP_E_OUT_CAPACITY = 13  /* rlap_snapshot_ppr, rlap_edge_drop, rlap_node_sample, rlap_edge_add: the kept entries exceed out_cap_rows; nothing written, rows_needed reported */
 };
 
 typedef struct {
@@ -564,6 +564,53 @@ typedef struct {
 int rlap_node_sample(rlap_handle h, const int64_t* d_src, const int64_t* d_dst, const double* d_w, int64_t E, int64_t num_nodes, int scheme,
                      const double* h_p, const int64_t* h_num_seeds, int64_t K, int64_t walk_length, uint64_t seed, double* d_rows,
                      int64_t out_cap_rows, int64_t* d_ptr, uint8_t* d_node_mask, int64_t* d_walks, rlap_node_sample_info* h_info);
+
+/* Edge adding, K views a call: the EdgeAdding augmentor of the training scripts (scripts/augmentor_benchmarks.py:44-65)
+ * on the device.  View k adds h_num_add[k] rows whose two ends are drawn uniformly from [0, num_nodes - 2] -- the scripts'
+ * torch.randint(0, num_nodes - 1, ...) has an exclusive upper end, so the last node never receives an added row; restated as it
+ * stands -- and, with RLAP_ADD_COALESCE, holds the distinct (source, target) pairs of the input and the added rows, ascending by
+ * (source, target), the order of sort_edge_index and coalesce.  Every rule -- the coin, the draw, the key of a pair, the tie rule of
+ * the merge and the weight -- is defined in rlap_amd/csrc/rlap_edgeadd.h.
+ *   d_src, d_dst, E    : the rows (source, target), int64 on the device, in any order; duplicates, loops and directed rows allowed
+ *   d_w                : (nullable) one weight a row; NULL: 1.0
+ *   num_nodes          : every id lies in [0, num_nodes); at least 2 where a row is added
+ *   h_num_add, K       : K counts >= 0 ON THE HOST, 1 <= K <= 32: the rows view k adds (the caller's int(E * ratio)); view k uses
+ *                        h_num_add[k] and seed + k
+ *   flags              : RLAP_ADD_COALESCE: sort and merge.  A pair's weight is s_in + (double)c_add: s_in the sum of its input
+ *                        rows from 0.0 in input order (0.0 without one), c_add the number of its added rows.  Without the flag view
+ *                        k is the E rows in input order, then its added rows in draw order with weight 1.0 (CCA-SSG's add_edge).
+ *   d_rows, out_cap_rows : (out_cap_rows, 3) f64 rows [source, target, weight], view-major; K * E + sum(h_num_add) always suffices
+ *   d_ptr              : [K+1] row offsets of the views in d_rows
+ *   d_added, d_aptr    : (nullable, both or neither; d_added may be null where nothing is added) (sum of h_num_add, 2) int64: the
+ *                        added pairs in draw order, view-major, and their [K+1] offsets
+ *   h_info             : (nullable) what the call did
+ * View k of a K-view call equals a one-view call with (h_num_add[k], seed + k); the same input gives the same bits; no atomic touches
+ * a floating-point value.  With RLAP_ADD_COALESCE the input is sorted at most once a call, whatever K is (one stable rocPRIM sort of
+ * (key, row)), and not at all when its keys already ascend (h_info->input_sorted); the added rows' keys are sorted once for all views
+ * where the view number fits beside the key in 63 bits, once a view otherwise (h_info->sorts counts every sort).  One host
+ * synchronisation: the call is enqueued for ascending keys and read back once; for an input that is not ascending that read-back
+ * holds the row total all the same (counted through a set of the input's keys), and the sort and the rows follow on the handle's
+ * stream without another read-back: d_rows is complete in stream order, as the results of the calls that do not synchronise are.
+ * More rows than out_cap_rows: RLAP_E_OUT_CAPACITY, no row written, h_info->rows_needed says how many.  An id outside
+ * [0, num_nodes): RLAP_E_INDEX_RANGE.  A null pointer, K < 1, a negative count, an unknown flag, one of d_added / d_aptr without the
+ * other, num_nodes < 2 with a row to add: RLAP_E_BAD_ARG.  E + max(h_num_add) >= 2^31 - 1, num_nodes >= 2^31 or K > 32:
+ * RLAP_E_TOO_LARGE, never truncated.  Scratch from the arena (RLAP_E_WORKSPACE when a caller-provided one is too small). */
+enum { RLAP_ADD_COALESCE = 1 };
+typedef struct {
+    int64_t rows_needed;      /* rows of all views: the rows of d_rows (written, or needed)           */
+    int64_t added;            /* added rows of all views: sum(h_num_add)                              */
+    int64_t input_distinct;   /* distinct (source, target) pairs of the input (coalesce only)         */
+    int64_t launches;         /* kernels the call enqueued                                            */
+    int64_t arena_bytes;      /* scratch bytes of the call                                            */
+    int32_t input_sorted;     /* coalesce: 1 when the input's keys ascended, so no sort of the input  */
+    int32_t sorts;            /* rocPRIM sorts the call enqueued                                      */
+    int32_t host_syncs;       /* host synchronisations of the call                                    */
+    int32_t pad;
+} rlap_edge_add_info;
+
+int rlap_edge_add(rlap_handle h, const int64_t* d_src, const int64_t* d_dst, const double* d_w, int64_t E, int64_t num_nodes,
+                  const int64_t* h_num_add, int64_t K, uint64_t seed, int flags, double* d_rows, int64_t out_cap_rows, int64_t* d_ptr,
+                  int64_t* d_added, int64_t* d_aptr, rlap_edge_add_info* h_info);
 
 /* Per-graph readout of batched node embeddings: y[l, g, :] = the sum (or mean) of x[l, i, :] over the ids i of graph g,
  * [node_ptr[g], node_ptr[g+1]) -- what global_add_pool(z, batch) does after every GIN layer of a graph-level step, without float

@@ -26,7 +26,7 @@ EXPORTS = [
     "rlap_infonce_pair", "rlap_infonce_pair_backward",
     "rlap_cca_loss", "rlap_cca_loss_backward",
     "rlap_g2l_jsd", "rlap_g2l_jsd_backward", "rlap_g2l_bootstrap", "rlap_g2l_bootstrap_backward",
-    "rlap_linear_probe", "rlap_probe_scores", "rlap_edge_drop", "rlap_node_sample",
+    "rlap_linear_probe", "rlap_probe_scores", "rlap_edge_drop", "rlap_node_sample", "rlap_edge_add",
 ]
 
 E_INDEX_RANGE = 2   # RLAP_E_INDEX_RANGE
@@ -52,6 +52,9 @@ DROP_MAX_VIEWS = 32
 SAMPLE_SCHEMES = {"drop": 0, "walk": 1}
 SAMPLE_MAX_WALK_LENGTH = 1024
 SAMPLE_MAX_SEEDS = 2**31 - 1
+# rlap_edge_add flags and limits
+ADD_COALESCE = 1
+ADD_MAX_ROWS = 2**31 - 2   # E + the largest num_add
 # rlap_graph_readout flags
 READOUT_MEAN, READOUT_X_F32 = 1, 32
 # rlap_infonce flags
@@ -216,6 +219,15 @@ class NodeSampleInfo(_Report):
     ]
 
 
+class EdgeAddInfo(_Report):
+    """rlap_edge_add_info (include/rlap_hip.h)."""
+    _fields_ = [
+        ("rows_needed", ctypes.c_int64), ("added", ctypes.c_int64), ("input_distinct", ctypes.c_int64), ("launches", ctypes.c_int64),
+        ("arena_bytes", ctypes.c_int64), ("input_sorted", ctypes.c_int32), ("sorts", ctypes.c_int32), ("host_syncs", ctypes.c_int32),
+        ("pad", ctypes.c_int32),
+    ]
+
+
 def load():
     """dlopen the library and declare prototypes. Raises if it is not built."""
     global _lib
@@ -312,6 +324,8 @@ def load():
     lib.rlap_node_sample.restype = ci
     lib.rlap_node_sample.argtypes = [vp, vp, vp, vp, i64, i64, ci, ctypes.POINTER(dbl), ctypes.POINTER(i64), i64, i64, u64, vp, i64, vp, vp, vp,
                                      ctypes.POINTER(NodeSampleInfo)]
+    lib.rlap_edge_add.restype = ci
+    lib.rlap_edge_add.argtypes = [vp, vp, vp, vp, i64, i64, ctypes.POINTER(i64), i64, u64, ci, vp, i64, vp, vp, vp, ctypes.POINTER(EdgeAddInfo)]
     lib.rlap_approx_chol_views.restype = ci
     lib.rlap_approx_chol_views.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, vp, ci, ci, vp, u64, vp, i64, vp,
                                            ctypes.POINTER(Stats)]

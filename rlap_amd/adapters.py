@@ -27,6 +27,8 @@ Mirrors of the reference's L2 adapters that keep everything on the GPU:
                   scripts/augmentor_benchmarks.py:216-363 on the device (ops.drop_edges); `EdgeDroppingViews` -- K of them from one call
   * `NodeDropping`, `RWSampling` -- PyGCL's node-sampling arms (scripts/node_shared.py:458-470) on the device
                   (ops.sample_subgraphs); `NodeSampleViews` -- K of them from one call
+  * `EdgeAdding` -- the reference's own edge-adding arm (scripts/augmentor_benchmarks.py:44-65) on the device (ops.add_edges);
+                  `EdgeAddingViews` -- K of them from one call, the input sorted once at most
 PyGCL / DGL are optional: with them installed the classes return their graph types,
 without them a small named tuple with the same fields.
 """
@@ -893,6 +895,71 @@ class NodeSampleViews:
 
     def augmentors(self):
         return [_ViewAugmentor(self, k) for k in range(len(self.ps))]
+
+
+class EdgeAdding:
+    """The EdgeAdding(pe) of the training scripts (scripts/augmentor_benchmarks.py:44-65) on the device: int(E * pe) edges with
+    both ends uniform over [0, edge_index.max() - 1] -- the reference's randint has an exclusive upper end, so the last node never
+    receives one -- are added, and the lot is sorted and coalesced (ops.add_edges).  `aug(x, edge_index, edge_weight)` or
+    `aug.augment(g)`.  For an unweighted input the graph has no edge weights, as the reference's; for a weighted one `edge_weights`
+    holds the coalesced sums, one per edge of the result (an added edge counts 1.0) -- the reference hands back the input's weight
+    vector unchanged, whose length no longer matches the new edge_index.  `seed=None` (the default) draws a fresh seed from torch's
+    RNG at every call, as _EdgeDrop does; an integer seed makes every call return the same view; `last_seed` is the seed of the
+    latest call.  num_nodes is edge_index.max() + 1, as the reference computes it: one reduction and read-back in front of the call."""
+
+    def __init__(self, pe: float, seed: Optional[int] = None):
+        self.pe, self.seed, self.last_seed = pe, seed, None
+
+    def augment(self, g):
+        x, edge_index, edge_weights = g.unfold() if hasattr(g, "unfold") else g
+        self.last_seed = ops._seed_from(self.seed)
+        rows, _ = ops.add_edges(edge_index, edge_weights, None, self.pe, self.last_seed)
+        return _as_graph(x, rows[:, :2].long().t().contiguous(), rows[:, 2].contiguous() if edge_weights is not None else None)
+
+    def __call__(self, x, edge_index, edge_weight=None):
+        return self.augment(Graph(x, edge_index, edge_weight))
+
+
+class EdgeAddingViews:
+    """K edge-adding views of a graph from ONE ops.add_edges call: the input is sorted and coalesced once, view k adds
+    int(E * pes[k]) edges and uses seed + k.  `seed=None` (the default) draws a fresh seed from torch's RNG at every call, as
+    EdgeDroppingViews does; an integer seed makes every call return the same views; `last_seed` is the seed of the latest call.
+    `.augment(g)` returns the list of K graphs (edge weights as EdgeAdding's), `.augmentors()` the PyGCL-style siblings for the
+    `(aug1, aug2)` pair of the training scripts, `.plan(g)` one propagation plan over all K views for SnapshotGCNConv."""
+
+    def __init__(self, pes=(0.3, 0.4), seed: Optional[int] = None):
+        self.pes, self.seed = tuple(pes), seed
+        if len(self.pes) < 1:
+            raise ValueError("pes: at least one view")
+        self._pending = None
+        self.last_seed = None
+
+    def _call(self, g, **kw):
+        x, edge_index, edge_weights = g.unfold() if hasattr(g, "unfold") else g
+        n = int(x.shape[0]) if x is not None else None
+        self.last_seed = ops._seed_from(self.seed)
+        return x, edge_weights, n, ops.add_edges(edge_index, edge_weights, n, list(self.pes), self.last_seed, **kw)
+
+    def augment(self, g):
+        x, edge_weights, _, (rows, ptr) = self._call(g)
+        e = ptr.tolist()
+        ei = rows[:, :2].long().t().contiguous()
+        return [_as_graph(x, ei[:, e[k]:e[k + 1]], rows[e[k]:e[k + 1], 2] if edge_weights is not None else None) for k in range(len(self.pes))]
+
+    def plan(self, g, directions: str = "both", fill_value: float = 1.0):
+        """One plan over all K views (layer k is view k): ops.edge_list_plan on the call's (rows, ptr), the loops covering x.shape[0]
+        ids (edge_index.max() + 1 without x); weighted iff the graph has edge weights."""
+        x, edge_weights, n, (rows, ptr) = self._call(g)
+        if n is None:
+            edge_index = g.unfold()[1] if hasattr(g, "unfold") else g[1]
+            n = int(edge_index.max().item()) + 1 if edge_index.numel() else 0
+        return ops.edge_list_plan(rows, ptr, n, None, edge_weights is not None, True, fill_value, True, directions)
+
+    _key = staticmethod(rLapViews._key)
+    _view = rLapViews._view
+
+    def augmentors(self):
+        return [_ViewAugmentor(self, k) for k in range(len(self.pes))]
 
 
 def compute_ppr(edge_index: torch.Tensor, edge_weight: Optional[torch.Tensor], num_nodes: int, alpha: float = 0.2,

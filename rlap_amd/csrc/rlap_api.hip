@@ -27,6 +27,7 @@
 #include "rlap_edgeplan.h"
 #include "rlap_edgedrop.h"
 #include "rlap_nodesample.h"
+#include "rlap_edgeadd.h"
 #include "rlap_spmm_api.h"
 #include "rlap_spmm.h"
 #include "rlap_readout.h"
@@ -1579,6 +1580,39 @@ int rlap_node_sample(rlap_handle h, const int64_t* d_src, const int64_t* d_dst, 
     if (h_info) {
         h_info->rows_needed = rep.rows_needed; h_info->launches = rep.launches; h_info->arena_bytes = arena_bytes;
         h_info->host_syncs = rep.host_syncs;
+    }
+    return rc;
+}
+
+int rlap_edge_add(rlap_handle h, const int64_t* d_src, const int64_t* d_dst, const double* d_w, int64_t E, int64_t num_nodes,
+                  const int64_t* h_num_add, int64_t K, uint64_t seed, int flags, double* d_rows, int64_t out_cap_rows, int64_t* d_ptr,
+                  int64_t* d_added, int64_t* d_aptr, rlap_edge_add_info* h_info) {
+    if (h_info) *h_info = rlap_edge_add_info{};
+    if (!h || E < 0 || num_nodes < 0 || (E > 0 && (!d_src || !d_dst)) || !h_num_add || K < 1 || !d_ptr) return RLAP_E_BAD_ARG;
+    if (out_cap_rows < 0 || (out_cap_rows > 0 && !d_rows) || (flags & ~RLAP_ADD_COALESCE) || (d_added && !d_aptr)) return RLAP_E_BAD_ARG;
+    if (E >= INT32_MAX || num_nodes >= (int64_t)1 << 31 || K > edgeadd::MAX_VIEWS) return RLAP_E_TOO_LARGE;
+    EdgeAddArgs a{};
+    int64_t added = 0;
+    for (int64_t k = 0; k < K; ++k) {
+        if (h_num_add[k] < 0) return RLAP_E_BAD_ARG;
+        if (h_num_add[k] >= INT32_MAX - E) return RLAP_E_TOO_LARGE;
+        a.num_add[k] = h_num_add[k];
+        added += h_num_add[k];
+    }
+    if (added > 0 && (num_nodes < 2 || (d_aptr && !d_added))) return RLAP_E_BAD_ARG;   // (without an added row d_added may be null)
+    a.src = d_src; a.dst = d_dst; a.w = d_w; a.E = E; a.N = num_nodes; a.K = (int)K; a.coalesce = (flags & RLAP_ADD_COALESCE) ? 1 : 0;
+    a.seed = seed; a.rows = d_rows; a.cap = out_cap_rows; a.ptr = d_ptr; a.added = d_added; a.aptr = d_aptr;
+    // (debug poison: no result may depend on what the arena or any of the four result buffers held)
+    int64_t arena_bytes = 0;
+    EdgeAddReport rep{};
+    const int rc = poisoned_call(h, [&] { return edge_add_bytes(E, num_nodes, (int)K, a.num_add, a.coalesce != 0); },
+                                 {{d_rows, sizeof(double) * 3 * (size_t)out_cap_rows}, {d_ptr, sizeof(int64_t) * (size_t)(K + 1)},
+                                  {d_added, sizeof(int64_t) * 2 * (size_t)added}, {d_aptr, sizeof(int64_t) * (size_t)(K + 1)}},
+                                 &arena_bytes, [&](void* base, size_t have) { return edge_add_run(h->stream, base, have, a, &rep); });
+    if (h_info) {
+        h_info->rows_needed = rep.rows_needed; h_info->added = rep.added; h_info->input_distinct = rep.input_distinct;
+        h_info->launches = rep.launches; h_info->arena_bytes = arena_bytes; h_info->input_sorted = rep.input_sorted;
+        h_info->sorts = rep.sorts; h_info->host_syncs = rep.host_syncs;
     }
     return rc;
 }

@@ -2292,6 +2292,109 @@ def sample_subgraphs(
     return tuple(out)
 
 
+def _add_ratios(ratio) -> list:
+    """The K values of `ratio`: one finite number >= 0, or any sequence of them (list, tuple, ndarray, 1-D tensor)."""
+    if isinstance(ratio, (str, bytes)) or getattr(ratio, "ndim", 1) == 0 or not hasattr(ratio, "__iter__"):
+        rs = [ratio]
+    else:
+        rs = list(ratio.tolist() if hasattr(ratio, "tolist") else ratio)
+    if not 1 <= len(rs) <= _lib.DROP_MAX_VIEWS:
+        raise ValueError(f"ratio: one number or a sequence of 1 to {_lib.DROP_MAX_VIEWS} numbers, got {len(rs)}")
+    out = []
+    for x in rs:
+        try:
+            v = None if isinstance(x, (bool, str, bytes)) or not hasattr(x, "__float__") else float(x)
+        except (TypeError, ValueError, RuntimeError):
+            v = None
+        if v is None or not 0.0 <= v < float("inf"):
+            raise ValueError(f"ratio: a finite number >= 0, got {x!r}")
+        out.append(v)
+    return out
+
+
+def _add_args(edge_index, edge_weight, num_nodes, ratio, seed):
+    """Host-side checks of add_edges, made before anything is launched: (E, n or None, the K counts int(E * ratio[k]), seed)."""
+    if not isinstance(edge_index, Tensor) or edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise ValueError("edge_index: a (2, E) integer tensor")
+    if edge_index.dtype.is_floating_point or edge_index.dtype.is_complex or edge_index.dtype == torch.bool:
+        raise ValueError(f"edge_index: an integer tensor, got {edge_index.dtype}")
+    E = int(edge_index.shape[1])
+    if edge_weight is not None:
+        if not isinstance(edge_weight, Tensor) or edge_weight.dim() != 1 or edge_weight.shape[0] != E:
+            raise ValueError(f"edge_weight: a ({E},) tensor, one weight per column of edge_index")
+        if not edge_weight.dtype.is_floating_point:
+            raise ValueError(f"edge_weight: a floating-point tensor, got {edge_weight.dtype}")
+    n = None if num_nodes is None else _num_nodes(num_nodes)
+    counts = [int(E * r) for r in _add_ratios(ratio)]      # the reference's expression, on Python floats
+    if E + max(counts) > _lib.ADD_MAX_ROWS:
+        raise ValueError(f"ratio: E + int(E * ratio) must stay below 2^31 - 1, got {E} + {max(counts)}")
+    if any(counts) and n is not None and n < 2:
+        raise ValueError(f"num_nodes: added edges draw their ends from [0, num_nodes - 2], which needs num_nodes >= 2, got {n}")
+    if seed is not None and (isinstance(seed, bool) or not hasattr(seed, "__index__")):
+        raise ValueError(f"seed: an integer or None, got {seed!r}")
+    return E, n, counts, _seed_from(None if seed is None else seed.__index__())
+
+
+def add_edges(
+    edge_index: Tensor,
+    edge_weight: Optional[Tensor] = None,
+    num_nodes: Optional[int] = None,
+    ratio=0.5,
+    seed: Optional[int] = 0,
+    coalesce: bool = True,
+    return_added: bool = False,
+):
+    """Edge adding on the device, K views a call: the EdgeAdding augmentor of scripts/augmentor_benchmarks.py:44-65 (`coalesce=True`)
+    and the add_edge of CCA-SSG/aug.py:95-104 (`coalesce=False`).  `edge_index` is (2, E), source row 0 and target row 1, in any
+    order; duplicates, loops and directed edges are allowed; a batch of graphs is its disjoint union.  `num_nodes=None` means
+    edge_index.max() + 1 (one torch reduction and read-back in front of the call).  `ratio` is one number or a sequence of K <= 32
+    finite numbers >= 0 (values above 1 are allowed): view k adds int(E * ratio[k]) edges, uses seed + k, and equals a one-view call
+    with those, bit for bit.  `seed=None` draws a seed from torch's RNG (the adapters' default); with an integer the call is a pure
+    function of its arguments.
+
+    Both ends of an added edge are uniform over [0, num_nodes - 2]: the reference draws torch.randint(0, num_nodes - 1, ...), whose
+    upper end is exclusive, so the last node never receives an added edge -- restated as it stands.  Added edges may be loops, may
+    repeat each other and may repeat input edges.  This is the reference's distribution, not torch's random stream.
+
+    coalesce=True: view k holds the distinct (source, target) pairs of the input and the added edges, ascending by (source, target),
+    the order of sort_edge_index and coalesce.  The weight of a pair is s_in + c_add: s_in the float64 sum of its input edges in
+    input order (`edge_weight`, or 1.0 each; 0.0 without one), c_add the number of its added edges -- without edge_weight the
+    multiplicity, which the reference computes and throws away.  The input is sorted at most once a call, whatever K is, and not at
+    all when it is sorted already (a coalesced PyG graph is): `last_stats` reports input_sorted, sorts and launches.
+    coalesce=False: view k is the E input edges in input order, then its added edges in draw order with weight 1.0.
+
+    Returns (rows, ptr): rows (M, 3) float64 [source, target, weight], view-major; ptr (K+1,) int64; both on the device -- what
+    edge_list_plan takes.  With return_added (added, aptr) follow: added (sum of the counts, 2) int64, the added pairs in draw order,
+    view-major; aptr (K+1,) int64.  The same input gives the same bits.  Malformed arguments, num_nodes < 2 with an edge to add
+    among them, raise ValueError before the call; an id outside [0, num_nodes) raises ValueError.  One host synchronisation inside
+    the C call (num_nodes=None adds the read-back above): for an unsorted input it holds the row total all the same, and the sort
+    and the rows follow on the stream; `last_stats` holds rlap_edge_add_info.  Every rule: rlap_amd/csrc/rlap_edgeadd.h."""
+    E, n, counts, seed = _add_args(edge_index, edge_weight, num_nodes, ratio, seed)
+    K, total_add = len(counts), sum(counts)
+    dev = _device_for(edge_index)
+    with torch.cuda.device(dev):
+        ei = edge_index.to(device=dev, dtype=torch.int64)
+        src, dst = ei[0].contiguous(), ei[1].contiguous()
+        w = edge_weight.detach().to(device=dev, dtype=torch.float64).contiguous() if edge_weight is not None else None
+        if n is None:
+            n = int(ei.max().item()) + 1 if E else 0
+            if total_add and n < 2:
+                raise ValueError(f"num_nodes: added edges draw their ends from [0, num_nodes - 2], which needs num_nodes >= 2, got {n}")
+        cap = K * E + total_add
+        rows = torch.empty((cap, 3), dtype=torch.float64, device=dev)
+        ptr = torch.empty(K + 1, dtype=torch.int64, device=dev)
+        added = torch.empty((total_add, 2), dtype=torch.int64, device=dev) if return_added else None
+        aptr = torch.empty(K + 1, dtype=torch.int64, device=dev) if return_added else None
+        info = _device_call("rlap_edge_add", _lib.EdgeAddInfo, dev, 1, (
+            src.data_ptr() if E else None, dst.data_ptr() if E else None, w.data_ptr() if w is not None and E else None, E, n,
+            (ctypes.c_int64 * K)(*counts), K, seed, _lib.ADD_COALESCE if coalesce else 0, rows.data_ptr() if cap else None, cap, ptr.data_ptr(),
+            added.data_ptr() if added is not None else None, aptr.data_ptr() if aptr is not None else None))
+        out = [_trim(rows, int(info.rows_needed)), ptr]
+    if return_added:
+        out += [added, aptr]
+    return tuple(out)
+
+
 def identity(a: Tensor) -> Tensor:
     """Boundary self-test (reference: rlap/ops.py:61-63): tensor -> column-major
     staging -> tensor, on the GPU; returns a tensor on `a`'s device."""
