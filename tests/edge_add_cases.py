@@ -3,8 +3,12 @@ tests/test_edge_add_cpu.py and the tests/test_gpu_edge_add*.py files: the CPU su
 these inputs, the GPU suite compares the device with the mirror bit for bit."""
 import numpy as np
 
+from edge_drop_cases import MAX_GRID_ROWS, STRIDE_E, STRIDE_N, stride_rows  # noqa: F401  (one constant, one large input for the three calls)
 from util import ba_graph
 
+M64 = (1 << 64) - 1
+WRAP_SEEDS = range(400)
+WRAP_RATIOS = (1.5, 0.5)
 ROW_TILE = 2048                     # merged positions a workgroup owns (rlap_edgeadd.h::ROW_TILE; the CPU suite asserts the equality)
 T = ROW_TILE
 SEED = 20
@@ -61,6 +65,75 @@ def distinct_rows(n_a, n=WIDE_N, seed=11, low=0, high=None):
     key = rs.permutation(key)[:n_a]
     assert key.size == n_a
     return (key // span + low).astype(np.int64), (key % span + low).astype(np.int64), n
+
+
+def tiny_unsorted(seed):
+    """2 to 12 rows on 3 to 6 nodes: a key set of 4 to 24 slots, small enough that a probe often reaches the table's end."""
+    r = np.random.RandomState(seed)
+    E = r.randint(2, 13)
+    N = r.randint(3, 7)
+    return r.randint(0, N, E).astype(np.int64), r.randint(0, N, E).astype(np.int64), int(N)
+
+
+# ---- a model of the key set of an input whose keys do not ascend (rlap_edgeadd.hip: 2 E slots, home = mix64(key) % slots, linear
+# probing that wraps at the table's end).  It is used only to choose inputs: what the call returns is compared with the mirror,
+# which finds the same counts by sorting.
+def mix64(z):
+    z = (z + 0x9E3779B97F4A7C15) & M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
+    return z ^ (z >> 31)
+
+
+def id_bits(n):
+    b = 1
+    while b < 31 and (1 << b) < n:
+        b += 1
+    return b
+
+
+def pair_keys(src, dst, n):
+    b = id_bits(n)
+    return [(int(s) << b) | int(t) for s, t in zip(src, dst)]
+
+
+def table_of(keys):
+    """The table after a sequential insertion of `keys`, and whether a key went into a slot below its home: the occupied run then
+    crosses the table's end.  The set of occupied slots does not depend on the order of insertion."""
+    slots = 2 * len(keys)
+    table, wrapped = [None] * slots, False
+    for key in keys:
+        home = h = mix64(key) % slots
+        while table[h] is not None and table[h] != key:
+            h = 0 if h + 1 == slots else h + 1
+        wrapped = wrapped or h < home
+        table[h] = key
+    return table, wrapped
+
+
+def probe(table, key):
+    """(found, crossed): a probe for `key` as the device makes it, and whether it stepped from the last slot to slot 0."""
+    slots = len(table)
+    h, crossed = mix64(key) % slots, False
+    for _ in range(slots):
+        if table[h] == key:
+            return True, crossed
+        if table[h] is None:
+            return False, crossed
+        crossed = crossed or h + 1 == slots
+        h = 0 if h + 1 == slots else h + 1
+    return False, crossed
+
+
+def wrapping_inputs():
+    """The seeds of WRAP_SEEDS whose tiny_unsorted input has keys that do not ascend and a table whose occupied run crosses its end."""
+    out = []
+    for seed in WRAP_SEEDS:
+        src, dst, n = tiny_unsorted(seed)
+        keys = pair_keys(src, dst, n)
+        if any(a > b for a, b in zip(keys, keys[1:])) and table_of(keys)[1]:
+            out.append(seed)
+    return out
 
 
 def coalesced(src, dst, n):

@@ -12,6 +12,15 @@ COMB_DEGREES = (0, 1, 15, 16, 17, 63, 64, 65, 255, 256, 257, 513)
 SCHEMES = ("uniform", "degree", "pagerank", "eigenvector")
 PS, THRESHOLD, SEED = (0.3, 0.45), 0.7, 20
 TILE_EDGE_ROWS = (0, 1, ROW_TILE - 1, ROW_TILE, ROW_TILE + 1, 3 * ROW_TILE + 5)
+NODE_TILE = 256                     # nodes of a tile, and lanes of a workgroup (rlap_edgedrop.h::TILE)
+MAX_GRID_ROWS = 8192 * 256          # rows one round of a strided launch covers: ED_MAX_GRID workgroups of TILE lanes (the CPU suite ties both)
+# 1, 1, 2, 256 and 257 node tiles on both sides of a power of two: the stride of wg_total runs once at 65,536 nodes, twice at 65,537
+NODE_EDGE_NODES = (255, 256, 257, 65536, 65537)
+NODE_EDGE_ITERS = dict(pr_iters=3, evc_max_iter=5)
+RUN_DEGREES = (1, 63, 64, 65, 129, 300)
+MANY_PS = tuple(k / 40 for k in range(32))            # K = 32: every view a flip kernel keeps a count for
+STRIDE_E, STRIDE_N, STRIDE_SEED = 2**21 + 65, 2**21 + 300, 5   # one full round of a strided launch, then one whole wave and one lane
+STRIDE_ITERS = dict(pr_iters=2, evc_max_iter=3)
 
 
 def _shuffled(src, dst, seed):
@@ -52,6 +61,45 @@ def two_ba50():
     """The disjoint union of two BA(50, 2): a batch as the reference hands it to an augmentor."""
     g0, g1 = ba_graph(50, 2, 1), ba_graph(50, 2, 2)
     return np.concatenate([g0[0], g1[0] + 50]), np.concatenate([g0[1], g1[1] + 50]), 100
+
+
+def node_edge_rows(n):
+    """3 n + 7 random rows on n nodes, the top id written in as a source and as a target: N at the edge of a node tile and of a
+    key width."""
+    E = 3 * n + 7
+    rs = np.random.RandomState(11 + n)
+    src, dst = rs.randint(0, n, E).astype(np.int64), rs.randint(0, n, E).astype(np.int64)
+    src[:3] = n - 1
+    dst[1:5] = n - 1
+    return src, dst, n
+
+
+def runs(front=False, by_source=False):
+    """Targets 0..5 with in-degrees RUN_DEGREES, target j from its own sources j + 1, j + 2, ... (so targets 1..5 are sources too and
+    no score is the same at every node), the rows in ascending target order: the runs of equal ids that a sorted row list hands to
+    the wave-run counter.  `front` puts one row (0 -> 5) before them, so that every run moves one lane; `by_source` swaps the two
+    ends, so that the list is sorted by source."""
+    src, dst = ([0], [5]) if front else ([], [])
+    for j, d in enumerate(RUN_DEGREES):
+        src += list(range(j + 1, j + 1 + d))
+        dst += [j] * d
+    s, d = np.array(src, dtype=np.int64), np.array(dst, dtype=np.int64)
+    return (d, s, 6 + max(RUN_DEGREES)) if by_source else (s, d, 6 + max(RUN_DEGREES))
+
+
+RUN_VARIANTS = {"by_target": (False, False), "by_target_front": (True, False), "by_source": (False, True), "by_source_front": (True, True)}
+
+
+def run_spans(ids):
+    """[first, last] positions of every run of equal neighbouring ids."""
+    cut = np.flatnonzero(np.diff(ids)) + 1
+    return list(zip([0] + cut.tolist(), (cut - 1).tolist() + [len(ids) - 1]))
+
+
+def stride_rows():
+    """More rows than one round of a strided launch covers, by one whole wave and one lane; both ends random."""
+    rs = np.random.RandomState(STRIDE_SEED)
+    return rs.randint(0, STRIDE_N, STRIDE_E).astype(np.int64), rs.randint(0, STRIDE_N, STRIDE_E).astype(np.int64), STRIDE_N
 
 
 GRAPHS = {"ba300": ba300, "comb": comb, "directed": directed, "ring64": ring64, "two_ba50": two_ba50}

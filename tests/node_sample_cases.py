@@ -3,6 +3,7 @@ tests/test_node_sample_cpu.py and the tests/test_gpu_node_sample*.py files: the 
 Python on exactly these inputs, the GPU suite compares the device with the mirror bit for bit."""
 import numpy as np
 
+from edge_drop_cases import MAX_GRID_ROWS, STRIDE_E, STRIDE_N, stride_rows  # noqa: F401  (one constant, one large input for the three calls)
 from util import ba_graph
 
 ROW_TILE = 2048                     # rows a workgroup flips (rlap_nodesample.h::ROW_TILE; the CPU suite asserts the equality)
@@ -13,6 +14,29 @@ TILE_EDGE_ROWS = (0, 1, ROW_TILE - 1, ROW_TILE, ROW_TILE + 1, 3 * ROW_TILE + 5)
 WORD_EDGE_NODES = (1, 63, 64, 65, 129, 4097)
 WALKER_COUNTS = (0, 1, 63, 64, 65, 255, 256, 257)
 WALK_LENGTHS = (0, 1, 10)
+
+
+TOP_ID_NODES = (4097, 65537)        # the top id in a bitmap word of its own: bit 0 of word 64, of word 1,024
+TOP_ID_WALKERS = 4                  # walkers a node: enough that the mirror's walks start on the top id, leave it and arrive at it
+
+
+def top_id_rows(n):
+    """random_rows(300, n) with the top id written in as a source (rows 0..2) and as a target (rows 1..4): two loop rows on it, one
+    row that leaves it and two that arrive from other nodes."""
+    src, dst, _ = random_rows(300, n)
+    src[:3] = n - 1
+    dst[1:5] = n - 1
+    return src, dst, n
+
+
+def top_id_walk(n):
+    return dict(scheme="walk", num_seeds=[TOP_ID_WALKERS * n, 3], walk_length=2, seed=1)
+
+
+def passes_through(walks, v):
+    """(a walk starts on v, a walk arrives at v from another node, a walk leaves v for another node)."""
+    at = walks == v
+    return bool(at[:, 0].any()), bool((~at[:, :-1] & at[:, 1:]).any()), bool((at[:, :-1] & ~at[:, 1:]).any())
 
 
 def directed():

@@ -85,6 +85,61 @@ def test_constants(lib):
     assert lib.edgeadd_one_sort(2**29, 32) == 1 and lib.edgeadd_one_sort(2**29 + 1, 32) == 0 and lib.edgeadd_one_sort(5000, 3) == 1
 
 
+def test_the_stride_constant_and_the_large_input(lib):
+    """MAX_GRID_ROWS is what one round of a strided launch of rlap_edgeadd.hip covers, and the large input of
+    tests/test_gpu_augment_strides.py is one round, one whole wave and one lane."""
+    src = open(os.path.join(INC, "rlap_edgeadd.hip")).read()
+    grid = int(re.search(r"constexpr int64_t EA_MAX_GRID = (\d+);", src).group(1))
+    tile = int(re.search(r"constexpr int TILE = (\d+);", open(os.path.join(INC, "rlap_edgedrop.h")).read()).group(1))
+    assert "constexpr int TILE = edgedrop::TILE;" in open(os.path.join(INC, "rlap_edgeadd.h")).read()
+    assert "return capped_blocks(n, TILE, EA_MAX_GRID);" in src and cases.MAX_GRID_ROWS == grid * tile
+    assert cases.STRIDE_E == cases.MAX_GRID_ROWS + 64 + 1 and cases.STRIDE_N > cases.STRIDE_E
+    s, d, n = cases.stride_rows()
+    assert s.size == d.size == cases.STRIDE_E and n == cases.STRIDE_N and max(s.max(), d.max()) < n
+    assert (np.diff(s * n + d) < 0).any()                                              # the keys do not ascend: the key set is built
+    assert edgeadd_mirror.counts_of(cases.STRIDE_E, 0.001) == [2097]                     # the large input's added rows
+    assert edgeadd_mirror.counts_of(5000, (cases.STRIDE_E + 0.5) / 5000) == [cases.STRIDE_E]   # ... and the many added rows of a small one
+
+
+def test_the_key_set_model_and_its_wrapping_inputs(lib):
+    """The model of tests/edge_add_cases.py restates the device's key set (2 E slots, home = mix64(key) % slots, linear probing that
+    wraps).  Among the tiny inputs it picks, the occupied slots cross the table's end, and among the added keys of the calls the GPU
+    suite makes with them, probes cross that end both ways: one finds its key beyond it, one finds an empty slot beyond it."""
+    src = open(os.path.join(INC, "rlap_edgeadd.hip")).read()
+    assert "a.slots = g.coalesce ? 2 * E : 0;" in src and "return (int64_t)(mix64(key) % (uint64_t)a.slots);" in src
+    assert src.count("h = h + 1 == a.slots ? 0 : h + 1;") == 2                           # the insertion and the probe
+    assert cases.mix64(12345) == mix64(12345)
+    for n in (2, 3, 4, 5, 6, 1025):
+        assert cases.id_bits(n) == lib.edgeadd_id_bits(n)
+        assert cases.pair_keys([n - 1, 1], [0, n - 1], n) == [lib.edgeadd_pair_key(n - 1, 0, n), lib.edgeadd_pair_key(1, n - 1, n)]
+    unsorted, found_across, empty_across = 0, 0, 0
+    seeds = cases.wrapping_inputs()
+    for seed in cases.WRAP_SEEDS:
+        s, d, n = cases.tiny_unsorted(seed)
+        assert 2 <= s.size <= 12 and 3 <= n <= 6
+        keys = cases.pair_keys(s, d, n)
+        ascending = all(a <= b for a, b in zip(keys, keys[1:]))
+        unsorted += 0 if ascending else 1
+        if seed not in seeds:
+            continue
+        got = edgeadd_mirror.run(lib, s, d, n, w=cases.weights(s.size), ratio=cases.WRAP_RATIOS, seed=cases.SEED)
+        assert got["input_sorted"] == 0 and not ascending
+        table, wrapped = cases.table_of(keys)
+        assert wrapped and sorted(k for k in table if k is not None) == sorted(set(keys)) and len(table) == 2 * s.size
+        assert cases.table_of(keys[::-1])[1] and [k is None for k in cases.table_of(keys[::-1])[0]] == [k is None for k in table]   # any order: the same slots
+        for key in sorted(set(cases.pair_keys(got["added"][:, 0], got["added"][:, 1], n))):
+            found, crossed = cases.probe(table, key)
+            assert found == (key in keys)
+            found_across += 1 if crossed and found else 0
+            empty_across += 1 if crossed and not found else 0
+        for k in range(len(cases.WRAP_RATIOS)):                                          # the counts the device takes from the set are the mirror's
+            rows, added = view_of(got, k)
+            fresh = sum(1 for key in set(cases.pair_keys(added[:, 0], added[:, 1], n)) if not cases.probe(table, key)[0])
+            assert rows.shape[0] == got["input_distinct"] + fresh
+    print(f"{unsorted} inputs whose keys do not ascend, {len(seeds)} whose table wraps; probes across the end: {found_across} find their key, {empty_across} an empty slot")
+    assert len(seeds) >= 20 and found_across >= 1 and empty_across >= 1
+
+
 def test_draws_bit_for_bit(lib):
     for seed, k, i, c in [(0, 0, 0, 0), (0, 0, 0, 1), (0, 1, 0, 0), (20, 0, 1, 0), (20, 31, 12345, 1), (2**64 - 1, 1, 2**31 - 3, 1), (2**63 + 5, 7, 4097, 0)]:
         assert lib.edgeadd_u_add(seed, k, i, c) == u_add_int(seed, k, i, c) * 2.0 ** -53

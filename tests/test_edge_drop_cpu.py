@@ -234,6 +234,103 @@ def test_edge_cases(lib):
     assert e.value.status == 2
 
 
+def assert_no_coin_in_the_band(got, what):
+    gap = float(np.abs(got["u"] - got["q"]).min())
+    print(f"{what}: the smallest |u - q| is {gap:.2e}")
+    assert gap > cases.BAND, f"{what}: a coin inside the band: choose another seed"
+    return gap
+
+
+def test_the_stride_constant_and_the_large_input(lib):
+    """MAX_GRID_ROWS is what one round of a strided launch of rlap_edgedrop.hip covers; the large input of
+    tests/test_gpu_augment_strides.py is one round, one whole wave and one lane."""
+    src = open(os.path.join(INC, "rlap_edgedrop.hip")).read()
+    grid = int(re.search(r"constexpr int64_t ED_MAX_GRID = (\d+);", src).group(1))
+    assert "return capped_blocks(n, TILE, ED_MAX_GRID);" in src and cases.NODE_TILE == lib.edgedrop_tile()
+    assert cases.MAX_GRID_ROWS == grid * lib.edgedrop_tile()
+    assert cases.STRIDE_E == cases.MAX_GRID_ROWS + 64 + 1 and cases.STRIDE_N > cases.MAX_GRID_ROWS
+    s, d, n = cases.stride_rows()
+    assert s.size == d.size == cases.STRIDE_E and n == cases.STRIDE_N and 0 <= min(s.min(), d.min()) and max(s.max(), d.max()) < n
+
+
+@pytest.mark.parametrize("scheme", cases.SCHEMES)
+def test_no_coin_of_the_large_input_in_the_band(lib, scheme):
+    s, d, n = cases.stride_rows()
+    got = edgedrop_mirror.run(lib, s, d, n, w=cases.weights(s.size), p=cases.PS, scheme=scheme, threshold=cases.THRESHOLD, seed=cases.SEED,
+                              aggr="sink", **cases.STRIDE_ITERS)
+    assert_no_coin_in_the_band(got, f"large input, {scheme}")
+    assert np.array_equal(got["mask"], got["u"] >= got["q"])
+    if scheme != "uniform":
+        on = np.bincount(d, minlength=n) > 0
+        assert np.isfinite(got["node_weight"][on]).all() and on.sum() < n            # ids without incoming rows occur too
+
+
+@pytest.mark.parametrize("n", cases.NODE_EDGE_NODES)
+def test_node_tile_and_key_width_edges(lib, n):
+    """The inputs of tests/test_gpu_edge_drop_regimes.py: the tiles of wg_total's stride, the key widths on both sides of a power of
+    two, the top id at both ends, and no coin of any of the forty cases within BAND of its drop probability."""
+    src, dst, nn = cases.node_edge_rows(n)
+    assert nn == n and src.size == 3 * n + 7 and (src[:3] == n - 1).all() and (dst[1:5] == n - 1).all() and max(src.max(), dst.max()) == n - 1
+    tiles = -(-n // cases.NODE_TILE)
+    assert tiles == {255: 1, 256: 1, 257: 2, 65536: 256, 65537: 257}[n]
+    strides = -(-tiles // cases.NODE_TILE)                                           # the trips of lane 0 through wg_total's loop
+    assert strides == (2 if n == 65537 else 1)
+    assert lib.edgedrop_pair_key_bits(n) == {255: 16, 256: 16, 257: 17, 65536: 32, 65537: 33}[n]
+    w = cases.weights(src.size)
+    for scheme in cases.SCHEMES:
+        for aggr in ("sink", "source"):
+            got = edgedrop_mirror.run(lib, src, dst, n, w=w, p=cases.PS, scheme=scheme, threshold=cases.THRESHOLD, seed=cases.SEED, aggr=aggr,
+                                      **cases.NODE_EDGE_ITERS)
+            assert_no_coin_in_the_band(got, f"n = {n}, {scheme}, {aggr}")
+            assert np.array_equal(got["u"], np_coins(cases.SEED, len(cases.PS), src.size))
+            if scheme == "degree":
+                assert np.array_equal(got["centrality"], np_degree(src, dst, n))
+            if scheme == "eigenvector":
+                assert (got["iters"], got["converged"]) == (cases.NODE_EDGE_ITERS["evc_max_iter"], False)
+
+
+@pytest.mark.parametrize("variant", list(cases.RUN_VARIANTS))
+def test_sorted_rows_and_their_runs(lib, variant):
+    """Where the runs of the sorted row lists fall in the waves (64 lanes) and workgroups (256 rows) of the keys kernel, asserted
+    from the positions; and the bands of the cases the GPU suite runs on them."""
+    front, by_source = cases.RUN_VARIANTS[variant]
+    src, dst, n = cases.runs(front, by_source)
+    ids = src if by_source else dst
+    assert ids.size == sum(cases.RUN_DEGREES) + front and (np.diff(ids[front:]) >= 0).all()
+    spans = cases.run_spans(ids)
+    assert [b - a + 1 for a, b in spans[front:]] == list(cases.RUN_DEGREES)
+    facts = dict(starts_on_lane_0=any(a % 64 == 0 and b > a for a, b in spans), ends_on_lane_63=any(b % 64 == 63 and b > a for a, b in spans),
+                 whole_wave=any(a % 64 == 0 and b - a + 1 == 64 for a, b in spans), covers_waves=any(b // 64 - a // 64 >= 2 for a, b in spans),
+                 crosses_row_256=any(a < 256 <= b for a, b in spans), partial_last_wave=ids.size % 64 != 0)
+    if front:                                                                        # every run one lane on: none starts on lane 0
+        assert facts == dict(starts_on_lane_0=False, ends_on_lane_63=False, whole_wave=False, covers_waves=True, crosses_row_256=True,
+                             partial_last_wave=True)
+        assert any(a % 64 == 1 and b % 64 == 0 for a, b in spans)                    # the run of 64: lane 1 to lane 0 of the next wave
+    else:
+        assert all(facts.values())
+    w = cases.weights(src.size)
+    for scheme in ("pagerank", "degree"):
+        for aggr in ("sink", "source"):
+            got = edgedrop_mirror.run(lib, src, dst, n, w=w, p=cases.PS, scheme=scheme, threshold=cases.THRESHOLD, seed=cases.SEED, aggr=aggr)
+            assert_no_coin_in_the_band(got, f"runs {variant}, {scheme}, {aggr}")
+            cnt = counts(src, dst, n, aggr)
+            assert np.isfinite(got["node_weight"][cnt > 0]).all()                    # smax > smean: the scores are not degenerate
+            if scheme == "degree":
+                assert np.array_equal(got["centrality"], np_degree(src, dst, n))
+
+
+@pytest.mark.parametrize("scheme", ("uniform", "degree"))
+def test_thirty_two_views(lib, scheme):
+    src, dst, n = cases.random_rows(cases.ROW_TILE + 1)
+    got = edgedrop_mirror.run(lib, src, dst, n, p=cases.MANY_PS, scheme=scheme, threshold=cases.THRESHOLD, seed=cases.SEED)
+    assert len(cases.MANY_PS) == lib.edgedrop_max_views() and got["mask"].shape == (32, cases.ROW_TILE + 1)
+    assert_no_coin_in_the_band(got, f"32 views, {scheme}")
+    assert got["mask"][0].all() and 0 < got["mask"][31].sum() < src.size
+    for k in (0, 31):
+        one = edgedrop_mirror.run(lib, src, dst, n, p=cases.MANY_PS[k], scheme=scheme, threshold=cases.THRESHOLD, seed=cases.SEED + k)
+        assert np.array_equal(one["mask"][0], got["mask"][k])
+
+
 # ------------------------------------------------------------------------------------------------ 2. the sanitizer program
 def test_the_mirror_under_asan_and_ubsan(tmp_path):
     """The mirror as a stand-alone program with its own main: a plain executable, nothing preloaded.  Its last inputs are malformed

@@ -192,6 +192,19 @@ def test_the_widest_keys_take_the_per_view_sorts(ops, mirror):
     assert st["sorts"] == 1 + 1                                                        # K = 2: one bit, which fits
 
 
+def test_the_key_set_wraps_at_the_tables_end(ops, mirror):
+    """Tiny inputs in no order whose key set (2 E slots, linear probing) has its occupied slots across the table's end: chosen with
+    the model of tests/edge_add_cases.py, for which tests/test_edge_add_cpu.py shows that insertions wrap in every one of them and
+    that among the added keys of these very calls probes cross the end both to their key and to an empty slot.  ptr and rows_needed
+    come from the set, the rows from the sort that follows: a wrong wrap shows in the first two."""
+    seeds = cases.wrapping_inputs()
+    assert len(seeds) >= 20
+    for seed in seeds:
+        src, dst, n = cases.tiny_unsorted(seed)
+        _, _, st = both(ops, mirror, src, dst, n, w=cases.weights(src.size), ratio=list(cases.WRAP_RATIOS), seed=cases.SEED)
+        assert st["input_sorted"] == 0 and st["sorts"] == 2, seed
+
+
 def test_views(ops, mirror):
     src, dst, n = cases.distinct_rows(T + 1, n=600)
     ei = on_device(src, dst)

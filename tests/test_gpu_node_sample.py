@@ -88,6 +88,19 @@ def test_bitmap_word_edges(ops, mirror, n):
     assert same(ops.sample_subgraphs(ei, None, n, return_nodes=True, return_walks=True, **kw), nodesample_mirror.run(mirror, src, dst, n, **kw))
 
 
+@pytest.mark.parametrize("n", cases.TOP_ID_NODES)
+def test_walks_through_the_top_id(ops, mirror, n):
+    """Id n - 1 -- bit 0 of the bitmap's last word, a word of its own -- as a walk's start, as a row's target and as a row's source:
+    the mirror's walks start on it, arrive at it and leave it (the WORD_EDGE_NODES cases reach it only by chance)."""
+    src, dst, _ = cases.top_id_rows(n)
+    kw = cases.top_id_walk(n)
+    want = nodesample_mirror.run(mirror, src, dst, n, **kw)
+    assert cases.passes_through(want["walks"], n - 1) == (True, True, True) and want["nodes"][0, n - 1]
+    got = ops.sample_subgraphs(on_device(src, dst), None, n, return_nodes=True, return_walks=True, **kw)
+    assert ops.last_stats["host_syncs"] == 1 and same(got, want)
+    assert bool(got[2][0, n - 1]) and (got[0][:, :2] == n - 1).any()               # the top id is in the set and in the rows kept
+
+
 @pytest.mark.parametrize("walkers", cases.WALKER_COUNTS)
 def test_walker_counts_across_wave_and_workgroup_edges(ops, mirror, walkers):
     src, dst, n = cases.graph("directed")

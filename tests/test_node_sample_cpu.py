@@ -120,6 +120,30 @@ def test_constants(lib):
     assert "0x%Xull" % EDGE_SALT in open(os.path.join(INC, "rlap_edgedrop.h")).read()      # COIN_SALT: the edge views' stream
 
 
+def test_the_stride_constant_and_the_large_input(lib):
+    """MAX_GRID_ROWS is what one round of a strided launch of rlap_nodesample.hip covers; the large input of
+    tests/test_gpu_augment_strides.py is one round, one whole wave and one lane, and its node masks and bitmaps need further rounds."""
+    src = open(os.path.join(INC, "rlap_nodesample.hip")).read()
+    grid = int(re.search(r"constexpr int64_t NS_MAX_GRID = (\d+);", src).group(1))
+    tile = int(re.search(r"constexpr int TILE = (\d+);", open(os.path.join(INC, "rlap_edgedrop.h")).read()).group(1))
+    assert "constexpr int TILE = edgedrop::TILE;" in open(os.path.join(INC, "rlap_nodesample.h")).read()
+    assert "return capped_blocks(n, TILE, NS_MAX_GRID);" in src and cases.MAX_GRID_ROWS == grid * tile
+    assert "capped_blocks(W, TILE / WAVE, NS_MAX_GRID)" in src                            # k_ns_drop_bits: a word a wave, 4 words a workgroup
+    assert cases.STRIDE_E == cases.MAX_GRID_ROWS + 64 + 1
+    assert (cases.STRIDE_N + 63) // 64 > grid * (tile // 64) and len(cases.PS) * cases.STRIDE_N > cases.MAX_GRID_ROWS
+
+
+@pytest.mark.parametrize("n", cases.TOP_ID_NODES)
+def test_walks_pass_through_the_top_id(lib, n):
+    """The condition the GPU suite leans on: with these rows and this many walkers, walks start on id n - 1, arrive at it from
+    another node and leave it, so its bit -- bit 0 of a bitmap word of its own -- is set, tested and walked from."""
+    src, dst, _ = cases.top_id_rows(n)
+    assert (n - 1) % 64 == 0 and (src == n - 1).sum() >= 3 and (dst == n - 1).sum() >= 4
+    got = nodesample_mirror.run(lib, src, dst, n, **cases.top_id_walk(n))
+    assert cases.passes_through(got["walks"], n - 1) == (True, True, True)
+    assert got["nodes"][0, n - 1] and got["rows"].shape[0] > 0
+
+
 def test_coins_bit_for_bit(lib):
     for seed, k, v in [(0, 0, 0), (0, 1, 0), (20, 0, 1), (20, 31, 12345), (2**64 - 1, 1, 2**31 - 1), (2**63 + 5, 7, 4097), (7, 3, 63)]:
         assert lib.nodesample_u_node(seed, k, v) == u_node_int(seed, k, v) * 2.0 ** -53
