@@ -1,6 +1,6 @@
 """Loader of the symmetric InfoNCE pair's host mirror (tests/csrc/infonce_pair_mirror.cc around rlap_amd/csrc/rlap_infonce.h) and the
 float64 restatement 0.5 * (l(a, b) + l(b, a)) built from infonce_mirror.restatement, shared by tests/test_infonce_pair_cpu.py and the
-GPU tests."""
+GPU tests; the vectorised exact-data generator of the regime tests (tests/test_gpu_infonce_pair_regimes.py)."""
 import ctypes
 import os
 import subprocess
@@ -47,6 +47,20 @@ def run(lib, a, b, tau, positive="scaled", g=None):
                                  ga.ctypes.data if g is not None else None, gb.ctypes.data if g is not None else None)
     assert rc == 0, "the mirror refused its arguments"
     return {"loss": loss[0], "rows": rows, "z": z, "sii": sii, "ga": ga, "gb": gb}
+
+
+def exact_views_fast(n, f, seed=None):
+    """The construction of the GPU tests' exact_views without its loop over the rows, for N where that loop is too slow: a_i =
+    e_(i mod F); b_j = four entries +-1 in four distinct columns, the columns of every row drawn at once as the first four of a random
+    order of the F (the argsort of F uniform numbers), the signs at once.  Not the same draws as exact_views."""
+    assert f >= 4
+    rng = np.random.RandomState(n + f if seed is None else seed)
+    a = np.zeros((n, f), dtype=np.float32)
+    a[np.arange(n), np.arange(n) % f] = 1.0
+    cols = np.argsort(rng.random_sample((n, f)), axis=1)[:, :4]
+    b = np.zeros((n, f), dtype=np.float32)
+    b[np.arange(n)[:, None], cols] = rng.choice(np.array([-1.0, 1.0], dtype=np.float32), (n, 4))
+    return a, b
 
 
 def restatement(a, b, tau, positive, g=1.0):
