@@ -287,6 +287,37 @@ int rlap_snapshot_ppr(rlap_handle h, const double* d_sc, int64_t m, const int64_
                       int64_t G, int64_t num_nodes, double alpha, double eps, double tol, int flags, double* d_out,
                       int64_t out_cap_rows, int64_t* d_out_ptr, rlap_ppr_info* h_info);
 
+/* Markov diffusion of snapshots: for every segment s (as for rlap_snapshot_ppr), with Â = D^-1/2 A D^-1/2 (0 where
+ * d = 0; A + I with a self loop), beta = 1 - alpha and order D >= 1:
+ *     M = alpha Â + (1/D) sum_{k=0..D} beta^k Â^(k+1),  entries M_ij >= eps kept,  then (normalize) D_M^-1/2 M D_M^-1/2
+ * with D_M the row sums of the kept entries -- a restatement of PyGCL's compute_markov_diffusion (z = Â; t = Â; D times: t = beta Â t,
+ * z += t; z /= D; z += alpha Â; sparsify_dense('threshold')) without a dense matrix; it is not a run of that function.  Every column
+ * is computed in Horner form by D + 1 applications of Â (rlap_amd/csrc/rlap_markov.h holds every scalar step).
+ *   alpha, order, eps : 0 <= alpha <= 1, 1 <= order <= 1024 (markov::MAX_ORDER), eps > 0
+ *   flags             : RLAP_MARKOV_WEIGHTED / _SELF_LOOP / _NORMALIZE / _ZERO_ROWS, as the RLAP_PPR_* flags
+ *   d_out, d_out_ptr, out_cap_rows, RLAP_E_OUT_CAPACITY : as for rlap_snapshot_ppr (h_info->rows_needed says how many rows)
+ * Exactly symmetric (the pair {i, j} takes its value and its keep decision from the column of the smaller id); the same input gives
+ * the same bits, and a segment's rows do not depend on the other segments of the call.  An id without edges keeps no
+ * row without the self loop and the one entry alpha + (1/D) sum_k beta^k with it.  Layout errors as for rlap_snapshot_stats; a
+ * weight <= 0 (< 0 with RLAP_MARKOV_ZERO_ROWS) or not finite with RLAP_MARKOV_WEIGHTED, or alpha / order / eps out of range:
+ * RLAP_E_BAD_ARG.  Scratch from the arena (RLAP_E_WORKSPACE when a caller-provided one is too small).  Three host synchronisations. */
+enum { RLAP_MARKOV_WEIGHTED = 1, RLAP_MARKOV_SELF_LOOP = 2, RLAP_MARKOV_NORMALIZE = 4, RLAP_MARKOV_ZERO_ROWS = 8 };
+typedef struct {
+    int64_t order;            /* D: D + 1 applications of the normalised adjacency                    */
+    int64_t small_tiles;      /* tiles (segment, 64 sources) that ran all sweeps in one workgroup     */
+    int64_t large_tiles;      /* tiles that stepped with device-wide launches                         */
+    int64_t groups;           /* tile groups (one regime each, live tile bytes within the budget)     */
+    int64_t launches;         /* kernel launches of the sweeps                                        */
+    int64_t rows_needed;      /* kept entries: the rows of d_out (written, or needed)                 */
+    int64_t arena_bytes;      /* scratch bytes of the call                                            */
+    int32_t host_syncs;       /* host synchronisations of the call                                    */
+    int32_t pad;
+} rlap_markov_info;
+
+int rlap_snapshot_markov(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
+                         int64_t G, int64_t num_nodes, double alpha, int32_t order, double eps, int flags, double* d_out,
+                         int64_t out_cap_rows, int64_t* d_out_ptr, rlap_markov_info* h_info);
+
 /* Induced subgraphs and relabelling of snapshots: for every segment s (described as for rlap_snapshot_stats: d_sc, m, d_ptr, S,
  * d_node_ptr, G, num_nodes; S = 0 with m = 0 is allowed) the rows whose two ids both lie in the segment's node set, in their input
  * order -- torch.unique + PyG's subgraph() of every snapshot of a call, without a sort.  The call is a filter: it makes no assumption

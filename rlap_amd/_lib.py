@@ -26,7 +26,7 @@ EXPORTS = [
     "rlap_infonce_pair", "rlap_infonce_pair_backward",
     "rlap_cca_loss", "rlap_cca_loss_backward",
     "rlap_g2l_jsd", "rlap_g2l_jsd_backward", "rlap_g2l_bootstrap", "rlap_g2l_bootstrap_backward",
-    "rlap_linear_probe", "rlap_probe_scores", "rlap_edge_drop", "rlap_node_sample", "rlap_edge_add",
+    "rlap_linear_probe", "rlap_probe_scores", "rlap_edge_drop", "rlap_node_sample", "rlap_edge_add", "rlap_snapshot_markov",
 ]
 
 E_INDEX_RANGE = 2   # RLAP_E_INDEX_RANGE
@@ -35,6 +35,9 @@ E_NOT_GROUPED = 12   # RLAP_E_NOT_GROUPED
 E_OUT_CAPACITY = 13   # RLAP_E_OUT_CAPACITY
 # rlap_snapshot_ppr flags
 PPR_WEIGHTED, PPR_SELF_LOOP, PPR_NORMALIZE, PPR_ZERO_ROWS = 1, 2, 4, 8
+# rlap_snapshot_markov flags and limits (rlap_amd/csrc/rlap_markov.h)
+MARKOV_WEIGHTED, MARKOV_SELF_LOOP, MARKOV_NORMALIZE, MARKOV_ZERO_ROWS = 1, 2, 4, 8
+MARKOV_MAX_ORDER = 1024
 # rlap_snapshot_subgraph flags
 SUB_RELABEL, SUB_NO_SELF_LOOPS = 1, 2
 # rlap_snapshot_gcn_norm flags
@@ -105,6 +108,15 @@ class PprInfo(_Report):
         ("steps", ctypes.c_int64), ("small_tiles", ctypes.c_int64), ("large_tiles", ctypes.c_int64), ("groups", ctypes.c_int64),
         ("launches", ctypes.c_int64), ("rows_needed", ctypes.c_int64), ("arena_bytes", ctypes.c_int64), ("host_syncs", ctypes.c_int32),
         ("pad", ctypes.c_int32),
+    ]
+
+
+class MarkovInfo(_Report):
+    """rlap_markov_info (include/rlap_hip.h)."""
+    _fields_ = [
+        ("order", ctypes.c_int64), ("small_tiles", ctypes.c_int64), ("large_tiles", ctypes.c_int64),
+        ("groups", ctypes.c_int64), ("launches", ctypes.c_int64), ("rows_needed", ctypes.c_int64), ("arena_bytes", ctypes.c_int64),
+        ("host_syncs", ctypes.c_int32), ("pad", ctypes.c_int32),
     ]
 
 
@@ -270,6 +282,9 @@ def load():
     lib.rlap_snapshot_ppr.restype = ci
     lib.rlap_snapshot_ppr.argtypes = [vp, vp, i64, vp, i64, vp, i64, i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, ci, vp, i64,
                                       vp, ctypes.POINTER(PprInfo)]
+    lib.rlap_snapshot_markov.restype = ci
+    lib.rlap_snapshot_markov.argtypes = [vp, vp, i64, vp, i64, vp, i64, i64, ctypes.c_double, ctypes.c_int32, ctypes.c_double, ci, vp, i64,
+                                         vp, ctypes.POINTER(MarkovInfo)]
     lib.rlap_snapshot_subgraph.restype = ci
     lib.rlap_snapshot_subgraph.argtypes = [vp, vp, i64, vp, i64, vp, i64, i64, vp, vp, i64, ci, vp, vp, vp, i64, vp,
                                            ctypes.POINTER(SubgraphInfo)]

@@ -549,13 +549,23 @@ class rLapDepths:
         return {"max_sv": grid(st["lambda_max"]), "node_count": grid(st["nodes"]), "edge_count": grid(st["rows"]),
                 "converged": grid(st["converged"])}
 
-    def diffuse(self, g, alpha: float = 0.2, eps: float = 1e-4, tol: float = 1e-10):
+    def _diffused(self, sc, ptr, num_nodes, alpha, eps, tol, kind, order):
+        """(out, pptr) of the one diffusion call over all snapshots: ops.snapshot_ppr, or with kind="markov" ops.snapshot_markov."""
+        if kind == "ppr":
+            return ops.snapshot_ppr(sc, ptr, num_nodes, alpha=alpha, eps=eps, tol=tol)
+        if kind == "markov":
+            return ops.snapshot_markov(sc, ptr, num_nodes, alpha=alpha, order=order, eps=eps)
+        raise ValueError(f'kind: "ppr" or "markov", got {kind!r}')
+
+    def diffuse(self, g, alpha: float = 0.2, eps: float = 1e-4, tol: float = 1e-10, kind: str = "ppr", order: int = 16):
         """rLapPPRDiffusion's graph (Schur-complement weights -> PPR diffusion, normalised) for every run and depth of ONE call: one
         depths call and one ops.snapshot_ppr call -- the fraction sweep of scripts/rlap_ppr_edge_plots.py from one elimination.
+        kind="markov" takes the Markov diffusion of ops.snapshot_markov (its defaults: self loop, not normalised) with `order` in
+        its place; `tol` is then unused.
         Returns the layout of `augment`: K graphs, or R lists of K with views=R; each is Graph(x, edge_index, edge_weights) with
         ids in the input's space, as rLapPPRDiffusion returns."""
         x, sc, ptr, num_nodes = self._snapshots(g)
-        out, pptr = ops.snapshot_ppr(sc, ptr, num_nodes, alpha=alpha, eps=eps, tol=tol)
+        out, pptr = self._diffused(sc, ptr, num_nodes, alpha, eps, tol, kind, order)
         pp = pptr.cpu()
 
         def graph(i):
@@ -567,12 +577,14 @@ class rLapDepths:
         R = int(self.views)
         return [[graph(k * R + r) for k in range(K)] for r in range(R)]
 
-    def diffuse_plan(self, g, alpha: float = 0.2, eps: float = 1e-4, tol: float = 1e-10, directions: str = "both"):
+    def diffuse_plan(self, g, alpha: float = 0.2, eps: float = 1e-4, tol: float = 1e-10, directions: str = "both", kind: str = "ppr",
+                     order: int = 16):
         """One propagation plan over all diffused snapshots of `diffuse`: straight from the (out, pptr) of the one ops.snapshot_ppr
-        call to ops.edge_list_plan(weighted=True) -- no slicing, no edge_index.  Layer i is snapshot i in pptr order (depth-major,
-        then view, as the rows are); the loops cover x.shape[0] ids when x is given, with this augmentor's fill_value."""
+        (kind="markov": ops.snapshot_markov) call to ops.edge_list_plan(weighted=True) -- no slicing, no edge_index.  Layer i is
+        snapshot i in pptr order (depth-major, then view, as the rows are); the loops cover x.shape[0] ids when x is given, with this
+        augmentor's fill_value."""
         x, sc, ptr, num_nodes = self._snapshots(g)
-        out, pptr = ops.snapshot_ppr(sc, ptr, num_nodes, alpha=alpha, eps=eps, tol=tol)
+        out, pptr = self._diffused(sc, ptr, num_nodes, alpha, eps, tol, kind, order)
         n = int(x.shape[0]) if x is not None else int(num_nodes)
         return ops.edge_list_plan(out, pptr, n, weighted=True, add_self_loops=True, fill_value=self.fill_value, normalize=True,
                                   directions=directions)
@@ -993,6 +1005,74 @@ def compute_ppr(edge_index: torch.Tensor, edge_weight: Optional[torch.Tensor], n
         s = d2inv[:, None] * s * d2inv[None, :]
     idx = s.nonzero(as_tuple=False).t().contiguous()
     return idx, s[idx[0], idx[1]]
+
+
+def compute_markov_diffusion(edge_index: torch.Tensor, edge_weight: Optional[torch.Tensor], num_nodes: int, alpha: float = 0.2,
+                             degree: int = 16, sp_eps: float = 1e-4, add_self_loop: bool = True, normalize_out: bool = False):
+    """Dense Markov diffusion, M = alpha Â + (1/degree) sum_{k=0..degree} (1 - alpha)^k Â^(k+1) with Â = D^-1/2 A D^-1/2 (A + I with
+    add_self_loop), entries below `sp_eps` dropped, then (normalize_out) D_M^-1/2 M D_M^-1/2 with D_M the row sums of what was kept.
+
+    This restates PyGCL's `GCL.augmentors.functional.compute_markov_diffusion` in the published loop's order (z = Â; t = Â; `degree`
+    times: t = (1 - alpha) spmm(Â, t), z += t; z /= degree; z += alpha Â; transposed -- M is symmetric -- and thresholded by
+    sparsify_dense('threshold')).  PyGCL and PyG are absent from this container and not installable, so like compute_ppr this row
+    is UNPINNED: it follows the published semantics as recalled, not a run of them (DESIGN.md sections 4.23 and 7).  The published
+    function ends at the threshold; normalize_out=True adds compute_ppr's last step.  It is the yardstick of ops.markov_diffusion
+    and the opponent of tools/markov_latency.py; torch ops on the input's device."""
+    dev = edge_index.device
+    w = torch.ones(edge_index.shape[1], dtype=torch.float64, device=dev) if edge_weight is None else edge_weight.to(torch.float64)
+    adj = torch.zeros((num_nodes, num_nodes), dtype=torch.float64, device=dev)
+    adj.index_put_((edge_index[0], edge_index[1]), w, accumulate=True)
+    if add_self_loop:
+        adj = adj + torch.eye(num_nodes, dtype=torch.float64, device=dev)
+    deg = adj.sum(1)
+    dinv = torch.where(deg > 0, deg.pow(-0.5), torch.zeros_like(deg))
+    a_hat = dinv[:, None] * adj * dinv[None, :]
+    z = a_hat.clone()
+    t = a_hat.clone()
+    for _ in range(int(degree)):
+        t = (1.0 - alpha) * (a_hat @ t)
+        z = z + t
+    z = z / int(degree)
+    z = z + alpha * a_hat
+    z = z.t()
+    z = torch.where(z >= sp_eps, z, torch.zeros_like(z))
+    if normalize_out:
+        d2 = z.sum(1)
+        d2inv = torch.where(d2 > 0, d2.pow(-0.5), torch.zeros_like(d2))
+        z = d2inv[:, None] * z * d2inv[None, :]
+    idx = z.nonzero(as_tuple=False).t().contiguous()
+    return idx, z[idx[0], idx[1]]
+
+
+class MarkovDiffusion:
+    """PyGCL's A.MarkovDiffusion (restated, unpinned as compute_markov_diffusion is) on the device: ops.markov_diffusion of the
+    graph's edge list, cached after the first call when `use_cache` as PyGCL's is (the graph-level scripts pass use_cache=False and
+    diffuse every batch).  `node_ptr` -- node_ptr_of(batch) for a collated batch -- diffuses every graph of the batch on its own in
+    the one call.  num_nodes is x.shape[0] when x is given, else edge_index.max() + 1."""
+
+    def __init__(self, alpha: float = 0.05, order: int = 16, sp_eps: float = 1e-4, use_cache: bool = True, add_self_loop: bool = True):
+        self.alpha, self.order, self.sp_eps = alpha, order, sp_eps
+        self.use_cache, self.add_self_loop = use_cache, add_self_loop
+        self._cache = None
+
+    def augment(self, g, node_ptr=None):
+        if self._cache is not None and self.use_cache:
+            return self._cache
+        x, edge_index, edge_weights = g.unfold() if hasattr(g, "unfold") else g
+        if x is not None:
+            n = int(x.shape[0])
+        elif node_ptr is not None:
+            n = int(torch.as_tensor(node_ptr)[-1])
+        else:
+            n = int(edge_index.max().item()) + 1 if edge_index.numel() else 0
+        ei, w = ops.markov_diffusion(edge_index, edge_weights, n, node_ptr=node_ptr, alpha=self.alpha, order=self.order,
+                                     eps=self.sp_eps, add_self_loop=self.add_self_loop)
+        res = _as_graph(x, ei, w)
+        self._cache = res
+        return res
+
+    def __call__(self, x, edge_index, edge_weight=None, node_ptr=None):
+        return self.augment(Graph(x, edge_index, edge_weight), node_ptr=node_ptr)
 
 
 class rLapPPRDiffusion:

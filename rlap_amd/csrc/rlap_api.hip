@@ -20,6 +20,7 @@
 #include "rlap_cheb.h"
 #include "rlap_snapshot.h"
 #include "rlap_ppr.h"
+#include "rlap_markov_api.h"
 #include "rlap_stats.h"
 #include "rlap_subgraph.h"
 #include "rlap_gcn.h"
@@ -1385,6 +1386,29 @@ int rlap_snapshot_ppr(rlap_handle h, const double* d_sc, int64_t m, const int64_
             h_info->steps = K; h_info->small_tiles = rep.small_tiles; h_info->large_tiles = rep.large_tiles; h_info->groups = rep.groups;
             h_info->launches = rep.launches; h_info->rows_needed = rep.kept; h_info->arena_bytes = (int64_t)need;
             h_info->host_syncs = rep.host_syncs;
+        }
+        return rc;
+    });
+}
+
+int rlap_snapshot_markov(rlap_handle h, const double* d_sc, int64_t m, const int64_t* d_ptr, int64_t S, const int64_t* d_node_ptr,
+                         int64_t G, int64_t num_nodes, double alpha, int32_t order, double eps, int flags, double* d_out,
+                         int64_t out_cap_rows, int64_t* d_out_ptr, rlap_markov_info* h_info) {
+    if (h_info) *h_info = rlap_markov_info{};
+    if (!d_out_ptr || out_cap_rows < 0 || (out_cap_rows > 0 && !d_out)) return RLAP_E_BAD_ARG;
+    if (flags & ~(RLAP_MARKOV_WEIGHTED | RLAP_MARKOV_SELF_LOOP | RLAP_MARKOV_NORMALIZE | RLAP_MARKOV_ZERO_ROWS)) return RLAP_E_BAD_ARG;
+    if (!markov::valid(alpha, order, eps)) return RLAP_E_BAD_ARG;
+    SnapshotSeg g{d_sc, m, d_ptr, S, d_node_ptr, G, num_nodes};
+    if (const int rc = snapshot_check(h, &g, 1)) return rc;
+    if (num_nodes >= INT32_MAX) return RLAP_E_TOO_LARGE;
+    const SnapshotMarkovArgs a{g, alpha, eps, order, flags, d_out, out_cap_rows, d_out_ptr};
+    return snapshot_call(h, [&] { return snapshot_markov_bytes(g.m, g.S, g.G, g.N, out_cap_rows); }, [&](void* base, size_t have, size_t need) {
+        SnapshotMarkovReport rep;
+        const int rc = snapshot_markov_run(h->stream, base, have, a, &rep);
+        if (h_info) {
+            h_info->order = order; h_info->small_tiles = rep.small_tiles;
+            h_info->large_tiles = rep.large_tiles; h_info->groups = rep.groups; h_info->launches = rep.launches;
+            h_info->rows_needed = rep.kept; h_info->arena_bytes = (int64_t)need; h_info->host_syncs = rep.host_syncs;
         }
         return rc;
     });

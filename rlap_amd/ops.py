@@ -786,25 +786,12 @@ def snapshot_ppr(
         return _ppr_call(x, p, np_, int(num_nodes), alpha, eps, tol, flags)
 
 
-def ppr_diffusion(
-    edge_index: Tensor,
-    edge_weights: Optional[Tensor],
-    num_nodes: int,
-    *,
-    alpha: float = 0.2,
-    eps: float = 1e-4,
-    tol: float = 1e-10,
-    add_self_loop: bool = False,
-    normalize_out: bool = True,
-) -> Tuple[Tensor, Tensor]:
-    """The diffusion of snapshot_ppr on a plain undirected edge list (both directions present), node set [0, num_nodes) -- what
-    adapters.compute_ppr(edge_index, edge_weights, num_nodes, ...) computes densely; PyGCL's A.PPRDiffusion uses add_self_loop=True.
-    Rows of weight 0 are dropped (as the op's reader does); a negative weight raises ValueError.  The rows are grouped by column with
-    a stable device sort and duplicates summed (in input order); a pattern or weights that are not exactly symmetric raise
-    ValueError("adjacency not symmetric").  An id without edges keeps its diagonal entry: alpha (1 with a self loop) before
-    normalisation.  Returns (edge_index (2, P) int64, edge_weights (P,) float64) in row-major order, on the input's device.
-    """
-    alpha, eps, tol, _ = _ppr_params(alpha, eps, tol)
+def _diffusion_input(edge_index: Tensor, edge_weights: Optional[Tensor], num_nodes: int, node_ptr) -> Tuple[Tensor, Tensor, Optional[Tensor], int]:
+    """What ppr_diffusion and markov_diffusion make of a plain undirected edge list before their call: (sc, ptr, node_ptr, n) with
+    sc the (m, 3) float64 rows on the device, grouped by column with a stable sort by (col, row), rows of weight 0 dropped, duplicates
+    summed in input order, symmetry checked, and a row (i, i, 0) for every id without edges.  With `node_ptr` (a batch's contiguous
+    id ranges) every graph is a segment of its own -- ptr holds its rows, found by searchsorted of the column ids -- and a row whose
+    two ends lie in different graphs raises ValueError; without it the list is one segment."""
     n = _num_nodes(num_nodes)
     if not isinstance(edge_index, Tensor) or edge_index.dim() != 2 or edge_index.shape[0] != 2:
         raise ValueError("edge_index: a (2, E) tensor")
@@ -816,14 +803,19 @@ def ppr_diffusion(
             raise ValueError("edge_weights must have one entry per edge")
         if E and not bool((w >= 0).all()):
             raise ValueError("edge_weights: a weight is negative (or not a number)")
+    np_ = _ptr_table(node_ptr, "node_ptr", 0, n) if node_ptr is not None else None
     if E and not edge_index.is_cuda and (int(edge_index.min()) < 0 or int(edge_index.max()) >= n):
         raise ValueError(f"edge_index: ids must lie in [0, {n})")
     dev = _device_for(edge_index)
     with torch.cuda.device(dev):
-        ei = edge_index.to(device=dev, dtype=torch.int64)
+        ei = edge_index.to(device=dev, dtype=torch.int64).contiguous()
         w = torch.ones(E, dtype=torch.float64, device=dev) if w is None else w.to(device=dev, dtype=torch.float64)
         if E and (int(ei.min()) < 0 or int(ei.max()) >= n):
             raise ValueError(f"edge_index: ids must lie in [0, {n})")
+        if np_ is not None and E:
+            bounds = np_[1:].to(dev)
+            if not torch.equal(torch.searchsorted(bounds, ei[0], right=True), torch.searchsorted(bounds, ei[1], right=True)):
+                raise ValueError("edge_index: a row joins two graphs of node_ptr")
         keep = w != 0
         ei, w = ei[:, keep], w[keep]
         key, order = torch.sort(ei[1] * n + ei[0], stable=True)            # (col, row), input order among duplicates
@@ -846,10 +838,150 @@ def ppr_diffusion(
             row, col = torch.cat([row, iso])[o2], torch.cat([col, iso])[o2]
             ws = torch.cat([ws, torch.zeros(iso.numel(), dtype=torch.float64, device=dev)])[o2]
         sc = torch.stack([row.to(torch.float64), col.to(torch.float64), ws], 1).contiguous()
+        if np_ is None:
+            p = torch.tensor([0, sc.shape[0]], dtype=torch.int64)
+        else:   # the rows are in column order, the graphs contiguous id ranges: graph g is the rows with node_ptr[g] <= col < node_ptr[g+1]
+            p = torch.searchsorted(col.contiguous(), np_.to(dev)).to(device="cpu", dtype=torch.int64)
+    return sc, p, np_, n
+
+
+def ppr_diffusion(
+    edge_index: Tensor,
+    edge_weights: Optional[Tensor],
+    num_nodes: int,
+    *,
+    node_ptr: Optional[Union[Tensor, Sequence[int]]] = None,
+    alpha: float = 0.2,
+    eps: float = 1e-4,
+    tol: float = 1e-10,
+    add_self_loop: bool = False,
+    normalize_out: bool = True,
+) -> Tuple[Tensor, Tensor]:
+    """The diffusion of snapshot_ppr on a plain undirected edge list (both directions present), node set [0, num_nodes) -- what
+    adapters.compute_ppr(edge_index, edge_weights, num_nodes, ...) computes densely; PyGCL's A.PPRDiffusion uses add_self_loop=True.
+    Rows of weight 0 are dropped (as the op's reader does); a negative weight raises ValueError.  The rows are grouped by column with
+    a stable device sort and duplicates summed (in input order); a pattern or weights that are not exactly symmetric raise
+    ValueError("adjacency not symmetric").  An id without edges keeps its diagonal entry: alpha (1 with a self loop) before
+    normalisation.  With `node_ptr` (G+1 offsets of a batch's contiguous id ranges) every graph is diffused on its own, as one call
+    per graph would, in the one device call: the cost is the sum of n_g^2, not (sum n_g)^2; a row between two graphs raises
+    ValueError.  Returns (edge_index (2, P) int64, edge_weights (P,) float64) in row-major order, on the input's device.
+    """
+    alpha, eps, tol, _ = _ppr_params(alpha, eps, tol)
+    _num_nodes(num_nodes)
+    sc, p, np_, n = _diffusion_input(edge_index, edge_weights, num_nodes, node_ptr)
+    with torch.cuda.device(sc.device):
         flags = (_lib.PPR_WEIGHTED | _lib.PPR_ZERO_ROWS | (_lib.PPR_SELF_LOOP if add_self_loop else 0)
                  | (_lib.PPR_NORMALIZE if normalize_out else 0))
-        p = torch.tensor([0, sc.shape[0]], dtype=torch.int64)
-        out, _ = _ppr_call(sc, p, None, n, alpha, eps, tol, flags)
+        out, _ = _ppr_call(sc, p, np_, n, alpha, eps, tol, flags)
+        return out[:, :2].long().t().contiguous(), out[:, 2].contiguous()
+
+
+MARKOV_MAX_ORDER = _lib.MARKOV_MAX_ORDER   # cap on the order D (rlap_amd/csrc/rlap_markov.h::MAX_ORDER)
+
+
+def _markov_params(alpha, order, eps) -> Tuple[float, int, float]:
+    """Host-side checks of the Markov diffusion's parameters, made before anything is launched."""
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError(f"alpha: a number in [0, 1], got {alpha!r}")
+    if isinstance(order, bool) or not hasattr(order, "__index__") or not 1 <= order.__index__() <= MARKOV_MAX_ORDER:
+        raise ValueError(f"order: an integer in [1, {MARKOV_MAX_ORDER}], got {order!r}")
+    e = _real(eps, "eps", 0.0, float("inf"))
+    return float(alpha), order.__index__(), e
+
+
+def _markov_call(x: Tensor, p: Tensor, np_: Optional[Tensor], n: int, alpha: float, order: int, eps: float, flags: int) -> Tuple[Tensor, Tensor]:
+    """One rlap_snapshot_markov call inside torch-owned memory, with _ppr_call's first output capacity and single retry."""
+    global last_stats
+    S, m, dev = p.numel() - 1, int(x.shape[0]), x.device
+    cap = first_cap = min(S * min(n, m) ** 2, max(PPR_FIRST_CAP_PER_ROW * m + 64, PPR_FIRST_CAP_MIN))
+    for retries in (0, 1):
+        out = torch.empty((cap, 3), dtype=torch.float64, device=dev)
+        mptr = torch.empty(S + 1, dtype=torch.int64, device=dev)
+        info = _snapshot_call("rlap_snapshot_markov", _lib.MarkovInfo, x, p, np_, n,
+                              (alpha, order, eps, flags, out.data_ptr() if cap else None, cap, mptr.data_ptr()),
+                              extra_msg=" (or a weight is <= 0)", accept=(_lib.E_OUT_CAPACITY,) if retries == 0 else ())
+        P = int(info.rows_needed)
+        if P <= cap:   # (more than the capacity: RLAP_E_OUT_CAPACITY, accepted on the first attempt only)
+            break
+        cap = P
+    last_stats = dict(info.as_dict(), output_retries=retries, first_cap=first_cap)
+    return _trim(out, P), mptr
+
+
+def _markov_flags(weighted: bool, add_self_loop: bool, normalize_out: bool) -> int:
+    return ((_lib.MARKOV_WEIGHTED if weighted else 0) | (_lib.MARKOV_SELF_LOOP if add_self_loop else 0)
+            | (_lib.MARKOV_NORMALIZE if normalize_out else 0))
+
+
+def snapshot_markov(
+    sc: Tensor,
+    ptr: Union[Tensor, Sequence[int]],
+    num_nodes: int,
+    *,
+    node_ptr: Optional[Union[Tensor, Sequence[int]]] = None,
+    alpha: float = 0.2,
+    order: int = 16,
+    eps: float = 1e-4,
+    weighted: bool = True,
+    add_self_loop: bool = True,
+    normalize_out: bool = False,
+) -> Tuple[Tensor, Tensor]:
+    """Markov diffusion of every snapshot of a result of the calls above, on the device and without a dense matrix.  `sc`, `ptr`,
+    `num_nodes` and `node_ptr` as for snapshot_stats.  This restates the published `GCL.augmentors.functional.
+    compute_markov_diffusion` (PyGCL is not installed here: the definition is unpinned, not a run of that function; it calls
+    `order` `degree`).
+
+    For snapshot s with distinct ids V_s and symmetric adjacency A (the rows' weights, or unit entries with weighted=False; duplicate
+    rows summed; A + I with add_self_loop), d = A 1, Â = D^-1/2 A D^-1/2 (0 where d = 0), beta = 1 - alpha, D = order:
+        z = Â; t = Â; D times: t = beta Â t, z += t; z /= D; z += alpha Â
+        M = alpha Â + (1/D) sum_{k=0..D} beta^k Â^(k+1),  entries M_ij >= eps kept,  normalize_out: D_M^-1/2 M D_M^-1/2 (row sums)
+    Returns (out (P, 3) float64 rows [i, j, value] in the input's id space, mptr (S+1,) int64), both on sc's device: segment s is rows
+    [mptr[s], mptr[s+1]) in row-major order (ascending i, then j), the layout of snapshot_ppr.  Every column is computed in Horner
+    form by D + 1 applications of Â (rlap_amd/csrc/rlap_markov.h holds every scalar step, so a g++ build of that header computes
+    the same bits).  The result is exactly symmetric, the same input gives the same bits, and segment s equals the same call on that
+    segment alone, bit for bit.  An id without edges keeps no row without the self loop and the one entry alpha + (1/D) sum_k beta^k
+    with it.
+
+    alpha outside [0, 1], order outside [1, MARKOV_MAX_ORDER], eps <= 0, malformed tables, a column not contiguous within its
+    segment, a row id without a column, an id out of range, or (weighted) a weight <= 0 raise ValueError.  `last_stats` then holds
+    what the call did (rlap_markov_info: order, small / large tiles, groups, launches, rows_needed, arena_bytes, host_syncs)
+    and `output_retries` (1 when the first capacity guess was short).
+    """
+    p, np_ = _snapshot_tables(sc, ptr, num_nodes, node_ptr)
+    alpha, order, eps = _markov_params(alpha, order, eps)
+    if weighted and not sc.is_cuda and sc.shape[0] and not bool((sc[:, 2] > 0).all() and torch.isfinite(sc[:, 2]).all()):
+        raise ValueError("sc: every weight must be > 0")
+    dev = _device_for(sc)
+    flags = _markov_flags(weighted, add_self_loop, normalize_out)
+    with torch.cuda.device(dev):
+        x = sc.to(device=dev, dtype=torch.float64).contiguous()
+        return _markov_call(x, p, np_, int(num_nodes), alpha, order, eps, flags)
+
+
+def markov_diffusion(
+    edge_index: Tensor,
+    edge_weights: Optional[Tensor],
+    num_nodes: int,
+    *,
+    node_ptr: Optional[Union[Tensor, Sequence[int]]] = None,
+    alpha: float = 0.2,
+    order: int = 16,
+    eps: float = 1e-4,
+    add_self_loop: bool = True,
+    normalize_out: bool = False,
+) -> Tuple[Tensor, Tensor]:
+    """The diffusion of snapshot_markov on a plain undirected edge list (both directions present), node set [0, num_nodes) -- what
+    adapters.compute_markov_diffusion(edge_index, edge_weights, num_nodes, ...) computes densely.  The list is prepared as for
+    ppr_diffusion (rows of weight 0 dropped, grouped by column, duplicates summed in input order, symmetry checked, ids without
+    edges kept as (i, i, 0)).  With `node_ptr` (G+1 offsets of a batch's contiguous id ranges) every graph is a segment of its own:
+    a batch costs the sum of n_g^2, not (sum n_g)^2; a row between two graphs raises
+    ValueError.  Returns (edge_index (2, P) int64, edge_weights (P,) float64) in row-major order, on the input's device.
+    """
+    alpha, order, eps = _markov_params(alpha, order, eps)
+    _num_nodes(num_nodes)
+    sc, p, np_, n = _diffusion_input(edge_index, edge_weights, num_nodes, node_ptr)
+    with torch.cuda.device(sc.device):
+        out, _ = _markov_call(sc, p, np_, n, alpha, order, eps, _markov_flags(True, add_self_loop, normalize_out) | _lib.MARKOV_ZERO_ROWS)
         return out[:, :2].long().t().contiguous(), out[:, 2].contiguous()
 
 
