@@ -747,6 +747,32 @@ int rlap_infonce_pair(rlap_handle h, const float* d_a, const float* d_b, int64_t
 int rlap_infonce_pair_backward(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double tau, int flags,
                                const double* d_z, const double* d_g, float* d_ga, float* d_gb, rlap_infonce_pair_info* h_info);
 
+/* The four calls above with intraview negatives: DualBranchContrast(..., intraview_negs=True), the loss GRACE was
+ * published with.  Row i of a view is contrasted with the rows of the other view and with rows of its own view:
+ *   Z_i = sum_j exp((s(a_i, b_j) - 1) / tau) + sum over j in I(i) of exp((s(a_i, a_j) - 1) / tau)
+ * (the pair: Zc_j likewise with the rows of b), the positive staying s(a_i, b_i).
+ *   intraview      : RLAP_INFONCE_INTRA_MASKED -- I(i) is every j != i: GCL's InfoNCE under the sampler's masks;
+ *                    RLAP_INFONCE_INTRA_ALL    -- I(i) is every j: the reference's InfoNCEBatched under the same sampler, which never
+ *                    reads the masks and so counts the row's similarity with itself.
+ *                    Any other value, 0 included: RLAP_E_BAD_ARG (the calls above are the ones without intraview negatives).
+ *   other arguments: as the call of the same name without _intra; d_z holds the totals Z ([N]; the pair: [2, N], Z then Zc), so the
+ *                    backward call needs nothing else from the forward one.  It takes the same flags and intraview.
+ * The rule is rlap_amd/csrc/rlap_infonce.h's: the intraview sums run over the same parts and tiles as the row sum and follow it in
+ * the float64 chain; the backward call folds the two directions of a view's own similarities (symmetric bit for bit) into one
+ * weight and adds them to the same float32 chains, a part's tiles of the other view first, then the same tiles of the own view.  The
+ * same input gives the same bits, whatever the arena held; no atomic touches a floating-point value; no call synchronises with
+ * the host; memory is O(N F).  The refusals and statuses are rlap_infonce's. */
+enum { RLAP_INFONCE_INTRA_MASKED = 1, RLAP_INFONCE_INTRA_ALL = 2 };
+
+int rlap_infonce_intra(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double tau, int flags, int intraview,
+                       double* d_loss, double* d_rows, double* d_z, rlap_infonce_info* h_info);
+int rlap_infonce_intra_backward(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double tau, int flags, int intraview,
+                                const double* d_z, const double* d_g, float* d_ga, float* d_gb, rlap_infonce_info* h_info);
+int rlap_infonce_pair_intra(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double tau, int flags, int intraview,
+                            double* d_loss, double* d_rows, double* d_z, rlap_infonce_pair_info* h_info);
+int rlap_infonce_pair_intra_backward(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double tau, int flags, int intraview,
+                                     const double* d_z, const double* d_g, float* d_ga, float* d_gb, rlap_infonce_pair_info* h_info);
+
 /* The fused CCA-SSG loss of two views' node embeddings, forward and backward: the standardisation of
  * CCA-SSG/model.py and the loss of CCA-SSG/main.py.  With z = (h - mean_0(h)) / std_0(h) (unbiased), c = z1^T z2 / N,
  * c1 = z1^T z1 / N and c2 = z2^T z2 / N:  loss = -trace(c) + lambd * (||I - c1||_F^2 + ||I - c2||_F^2).

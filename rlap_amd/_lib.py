@@ -24,6 +24,7 @@ EXPORTS = [
     "rlap_snapshot_plan_bytes", "rlap_snapshot_plan_build", "rlap_snapshot_plan_propagate", "rlap_edge_plan_build",
     "rlap_graph_readout", "rlap_graph_readout_backward", "rlap_infonce", "rlap_infonce_backward",
     "rlap_infonce_pair", "rlap_infonce_pair_backward",
+    "rlap_infonce_intra", "rlap_infonce_intra_backward", "rlap_infonce_pair_intra", "rlap_infonce_pair_intra_backward",
     "rlap_cca_loss", "rlap_cca_loss_backward",
     "rlap_g2l_jsd", "rlap_g2l_jsd_backward", "rlap_g2l_bootstrap", "rlap_g2l_bootstrap_backward",
     "rlap_linear_probe", "rlap_probe_scores", "rlap_edge_drop", "rlap_node_sample", "rlap_edge_add", "rlap_snapshot_markov",
@@ -62,6 +63,8 @@ ADD_MAX_ROWS = 2**31 - 2   # E + the largest num_add
 READOUT_MEAN, READOUT_X_F32 = 1, 32
 # rlap_infonce flags
 INFONCE_POSITIVE_RAW = 1
+# the intraview argument of rlap_infonce_intra and its kin
+INFONCE_INTRA_MASKED, INFONCE_INTRA_ALL = 1, 2
 # rlap_linear_probe select
 PROBE_SELECT_SCRIPTS, PROBE_SELECT_CCA = 0, 1
 
@@ -315,6 +318,11 @@ def load():
     lib.rlap_infonce_pair.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ci, vp, vp, vp, ctypes.POINTER(InfoncePairInfo)]
     lib.rlap_infonce_pair_backward.restype = ci
     lib.rlap_infonce_pair_backward.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ci, vp, vp, vp, vp, ctypes.POINTER(InfoncePairInfo)]
+    for name, info in (("rlap_infonce_intra", InfonceInfo), ("rlap_infonce_pair_intra", InfoncePairInfo)):   # `intraview` behind `flags`
+        getattr(lib, name).restype = ci
+        getattr(lib, name).argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ci, ci, vp, vp, vp, ctypes.POINTER(info)]
+        getattr(lib, name + "_backward").restype = ci
+        getattr(lib, name + "_backward").argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ci, ci, vp, vp, vp, vp, ctypes.POINTER(info)]
     lib.rlap_cca_loss.restype = ci
     lib.rlap_cca_loss.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ci, vp, vp, vp, ctypes.POINTER(CcaInfo)]
     lib.rlap_cca_loss_backward.restype = ci

@@ -231,11 +231,19 @@ class NodeContrast(torch.nn.Module):
     (the default) restates the reference's InfoNCEBatched, whose positive term s_ii is not divided by tau; "scaled" is GCL's
     InfoNCE.  The loss is a 0-dim float64 tensor; gradients reach both views.  `pair=True` computes the same loss by one
     ops.info_nce_pair call -- both directions from one pass over the similarities, half the products -- whose value differs from the
-    two calls' in the order of the sums alone."""
+    two calls' in the order of the sums alone.  `intraview_negs` is DualBranchContrast's switch: True adds every other row of the
+    anchor's own view to each denominator ("masked": what the sampler gives GCL's InfoNCE, the loss of GRACE); "all" also counts
+    the row itself, which is what InfoNCEBatched computes under that sampler, since it never reads the masks; False (the default)
+    leaves the loss as it was.  It works with either setting of `pair`."""
 
-    def __init__(self, tau: float = 0.4, positive: str = "raw", pair: bool = False):
+    INTRAVIEW = {False: "none", True: "masked", "none": "none", "masked": "masked", "all": "all"}
+
+    def __init__(self, tau: float = 0.4, positive: str = "raw", pair: bool = False, intraview_negs=False):
         super().__init__()
+        if not isinstance(intraview_negs, (bool, str)) or intraview_negs not in self.INTRAVIEW:
+            raise ValueError(f'intraview_negs: False, True ("masked") or "all", got {intraview_negs!r}')
         self.tau, self.positive, self.pair = tau, positive, bool(pair)
+        self.intraview = self.INTRAVIEW[intraview_negs]
 
     def forward(self, h1, h2=None):
         if h2 is None:
@@ -243,9 +251,9 @@ class NodeContrast(torch.nn.Module):
                 raise ValueError("NodeContrast: two (N, F) embeddings, or one (L, N, F) tensor of L >= 2 views")
             h1, h2 = h1[0], h1[1]
         if self.pair:
-            return ops.info_nce_pair(h1, h2, tau=self.tau, positive=self.positive)
-        l1 = ops.info_nce(h1, h2, tau=self.tau, positive=self.positive)
-        l2 = ops.info_nce(h2, h1, tau=self.tau, positive=self.positive)
+            return ops.info_nce_pair(h1, h2, tau=self.tau, positive=self.positive, intraview=self.intraview)
+        l1 = ops.info_nce(h1, h2, tau=self.tau, positive=self.positive, intraview=self.intraview)
+        l2 = ops.info_nce(h2, h1, tau=self.tau, positive=self.positive, intraview=self.intraview)
         return 0.5 * (l1 + l2)
 
 

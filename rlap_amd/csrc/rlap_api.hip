@@ -1816,6 +1816,53 @@ int rlap_infonce_pair_backward(rlap_handle h, const float* d_a, const float* d_b
                          h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) { return infonce_pair_backward_run(h->stream, base, have, a); });
 }
 
+// intraview negatives: the four calls above with the variant behind `flags`; their checks first, then the variant's
+static_assert(RLAP_INFONCE_INTRA_MASKED == infonce::INTRA_MASKED && RLAP_INFONCE_INTRA_ALL == infonce::INTRA_ALL, "the header's variants are the rule's");
+
+int rlap_infonce_intra(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double tau, int flags, int intraview,
+                       double* d_loss, double* d_rows, double* d_z, rlap_infonce_info* h_info) {
+    if (const int rc = infonce_check(h, d_a, d_b, N, F, tau, flags, h_info)) return rc;
+    if (!d_loss || !d_rows || !d_z || !infonce::intra_ok(intraview)) return RLAP_E_BAD_ARG;
+    InfonceArgs a{};
+    a.a = d_a; a.b = d_b; a.N = N; a.F = F; a.tau = tau; a.flags = flags; a.loss = d_loss; a.rows = d_rows; a.z = d_z; a.intraview = intraview;
+    return poisoned_call(h, [&] { return infonce_bytes(N, F, intraview); }, {{d_loss, 8}, {d_rows, (size_t)N * 8}, {d_z, (size_t)N * 8}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) { return infonce_run(h->stream, base, have, a); });
+}
+
+int rlap_infonce_intra_backward(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double tau, int flags, int intraview,
+                                const double* d_z, const double* d_g, float* d_ga, float* d_gb, rlap_infonce_info* h_info) {
+    if (const int rc = infonce_check(h, d_a, d_b, N, F, tau, flags, h_info)) return rc;
+    if (!d_z || !d_g || !d_ga || !d_gb || !infonce::intra_ok(intraview)) return RLAP_E_BAD_ARG;
+    InfonceArgs a{};
+    a.a = d_a; a.b = d_b; a.N = N; a.F = F; a.tau = tau; a.flags = flags; a.z_in = d_z; a.g = d_g; a.ga = d_ga; a.gb = d_gb; a.intraview = intraview;
+    return poisoned_call(h, [&] { return infonce_backward_bytes(N, F, intraview); }, {{d_ga, (size_t)(N * F) * 4}, {d_gb, (size_t)(N * F) * 4}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) { return infonce_backward_run(h->stream, base, have, a); });
+}
+
+int rlap_infonce_pair_intra(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double tau, int flags, int intraview,
+                            double* d_loss, double* d_rows, double* d_z, rlap_infonce_pair_info* h_info) {
+    if (h_info) *h_info = rlap_infonce_pair_info{};
+    if (const int rc = infonce_check(h, d_a, d_b, N, F, tau, flags, nullptr)) return rc;
+    if (h_info) { h_info->rows = N; h_info->features = F; h_info->parts = infonce::pair_parts(N); h_info->groups = infonce::pair_groups(N); }
+    if (!d_loss || !d_rows || !d_z || !infonce::intra_ok(intraview)) return RLAP_E_BAD_ARG;
+    InfonceArgs a{};
+    a.a = d_a; a.b = d_b; a.N = N; a.F = F; a.tau = tau; a.flags = flags; a.loss = d_loss; a.rows = d_rows; a.z = d_z; a.intraview = intraview;
+    return poisoned_call(h, [&] { return infonce_pair_bytes(N, F, intraview); }, {{d_loss, 8}, {d_rows, (size_t)N * 16}, {d_z, (size_t)N * 16}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) { return infonce_pair_run(h->stream, base, have, a); });
+}
+
+int rlap_infonce_pair_intra_backward(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double tau, int flags, int intraview,
+                                     const double* d_z, const double* d_g, float* d_ga, float* d_gb, rlap_infonce_pair_info* h_info) {
+    if (h_info) *h_info = rlap_infonce_pair_info{};
+    if (const int rc = infonce_check(h, d_a, d_b, N, F, tau, flags, nullptr)) return rc;
+    if (h_info) { h_info->rows = N; h_info->features = F; h_info->parts = infonce::pair_parts(N); h_info->groups = infonce::pair_groups(N); }
+    if (!d_z || !d_g || !d_ga || !d_gb || !infonce::intra_ok(intraview)) return RLAP_E_BAD_ARG;
+    InfonceArgs a{};
+    a.a = d_a; a.b = d_b; a.N = N; a.F = F; a.tau = tau; a.flags = flags; a.z_in = d_z; a.g = d_g; a.ga = d_ga; a.gb = d_gb; a.intraview = intraview;
+    return poisoned_call(h, [&] { return infonce_pair_backward_bytes(N, F, intraview); }, {{d_ga, (size_t)(N * F) * 4}, {d_gb, (size_t)(N * F) * 4}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) { return infonce_pair_backward_run(h->stream, base, have, a); });
+}
+
 namespace {
 
 // what both CCA exports check (their pointers come before this)

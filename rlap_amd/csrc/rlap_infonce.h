@@ -4,7 +4,7 @@
 // bits; tests/csrc/infonce_main.cc runs the index arithmetic under the sanitizers; the kernels read the same functions.
 //
 // Inputs: a (anchor) and b (sample), (N, F) float32, and tau in [1/32, 1024].  The positive of row i is column i; every column, the
-// positive included, is in the denominator (the L2L / G2G sampler with intraview_negs=False).
+// positive included, is in the denominator (the L2L / G2G sampler with intraview_negs=False; with it on, the last section below).
 //
 //   normalisation   n2_i = sum over k = 0 .. F-1, in order, of (double)a_ik * (double)a_ik (product rounded, add rounded);
 //                   nrm_i = max(sqrt(n2_i), 1e-12);  ah_ik = (float)((double)a_ik / nrm_i); the same for bh.  A zero row stays zero.
@@ -213,6 +213,40 @@ RLAP_SPMM_HD double pair_loss_of(double total_a, double total_b, int64_t N) { re
 RLAP_SPMM_HD float pair_weight(float e, float rz_own, float rz_str) { return e * (rz_own + rz_str); }
 RLAP_SPMM_HD double pair_grad_scale(double g, int64_t N) { return -(g / (2.0 * (double)N)); }
 RLAP_SPMM_HD double pair_positive_coef(bool raw, double tau) { return 2.0 * positive_coef(raw, tau); }   // 2 c: exact
+
+// ---- intraview negatives (rlap_infonce_intra / rlap_infonce_pair_intra and their backward calls): the sampler with
+// intraview_negs=True.  Row i of a view is contrasted with the rows of the other view AND with rows of its own view, the set I(i):
+// every j != i (INTRA_MASKED: GCL's InfoNCE under the sampler's masks) or every j (INTRA_ALL: the reference's InfoNCEBatched, which
+// never reads the masks and so counts the row's similarity with itself).  Normalisation, the chain s, exp_arg, expw, row_term, the
+// chunk rule, grad_hat, dot, grad_in and the clamp are the ones above; the positive stays s^ab_ii.
+//
+//   intraview s, e  s^aa_ij = the chain over k of fmaf(ah_jk, ah_ik, acc) (the stream row first, as above; the order of the two does
+//                   not reach the bits), e^aa_ij = expw(exp_arg(s^aa_ij, itf)), so e^aa_ij == e^aa_ji bit for bit.  s^aa_ii is a
+//                   float32 chain of squares near 1 and may exceed it by a few roundings: exp_arg is then a few ulps above 0 times
+//                   1 / tau <= 32, far inside the range expw is valid on ([-87, 88]), and e^aa_ii is 1 up to those roundings.
+//   intraview sum   intra_a_i over the SAME parts and tiles as the row sum above (num_parts(N), part_begin) with both rows taken from
+//                   ah: inside a part two float64 sums, one per lane half, registers in order, tile after tile; columns >= N are
+//                   left out, and so is column i under INTRA_MASKED; the part's sum is half 0 + half 1.
+//   one-way Z       Z_i = 0 + ab part 0 + ab part 1 + ... + aa part 0 + aa part 1 + ...: the parts of the row sum above in order,
+//                   then the parts of the intraview sum in order, one float64 chain.
+//   pair Z, Zc      Z_i  = 0 + the pair's parts of the row sum in order (pair_parts(N)) + the parts of intra_a in order;
+//                   Zc_j = 0 + the pair's groups of the column sum in order (pair_groups(N)) + the parts of intra_b in order.
+//   backward        one-way, the anchor owns:  D_ik = sum_j prob(e^ab_ij, rz_i) bh_jk + sum over j in I(i) of
+//                   pair_weight(e^aa_ij, rz_i, rz_j) ah_jk -- row j's intraview sum reaches ah_i with the same e, so both fold into one
+//                   weight; j = i under INTRA_ALL is pair_weight(e_ii, rz_i, rz_i), which the same expression yields.  ONE float32
+//                   accumulator a part: inside part p the chain runs from +0 over the part's tiles of bh (the order above), then
+//                   over the SAME tiles of ah in the same order; D = 0 + part 0 + part 1 + ... as above.  A stream row >= N takes
+//                   its turn as fmaf(0, 0, acc); the masked row j = i takes its turn as fmaf(0, ah_ik, acc), which leaves acc as it
+//                   is.  gb is the sample-owner chain above with rz from the new Z.
+//                   pair: D^a_ik = sum_j pair_weight(e^ab_ij, rza_i, rzb_j) bh_jk + sum over j in I(i) of
+//                   pair_weight(e^aa_ij, rza_i, rza_j) ah_jk in the same one-accumulator order; D^b with the roles swapped (e^bb, rzb).
+// Every order is a function of N alone.
+enum { INTRA_NONE = 0, INTRA_MASKED = 1, INTRA_ALL = 2 };
+RLAP_SPMM_HD bool intra_ok(int intraview) { return intraview == INTRA_MASKED || intraview == INTRA_ALL; }
+// whether column j is in I(i)
+RLAP_SPMM_HD bool intra_member(int intraview, int64_t i, int64_t j) { return intraview == INTRA_ALL || i != j; }
+// the parts a forward call keeps: the row sum's, then the intraview sum's (one-way); the pair adds 2 num_parts to its own
+RLAP_SPMM_HD int64_t intra_z_parts(int64_t N) { return 2 * num_parts(N); }
 
 }  // namespace infonce
 }  // namespace rlap

@@ -29,6 +29,11 @@
 // The symmetric pair (rlap_infonce_pair / rlap_infonce_pair_backward) computes 0.5 * (l(a, b) + l(b, a)) from one pass:
 // its forward main kernel k_in_pair_main takes the row sums Z and the column sums Zc from the same tiles, its backward is k_in_main
 // with the weight e (1 / Z_i + 1 / Zc_j) (IN_BACK_PAIR), its finish the one above for two lists.
+//
+// Intraview negatives (rlap_infonce_intra and its three kin) are further instances of k_in_main: IN_FWD_INTRA, a forward
+// pass whose owner and stream are the same view, with the diagonal left out or kept, whose part sums follow the row sum's in the
+// float64 chain of Z; IN_BACK_ANCHOR_INTRA and IN_BACK_PAIR_INTRA, which walk a part's tiles of the other view and then the same tiles
+// of the owner's own view into ONE accumulator, the second with the weight e (1 / Z_i + 1 / Z_j).  The instances above are unchanged.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -91,10 +96,19 @@ struct Main {
     int64_t N, Np, T, RB; int parts; int Fp; int nft;
     double* zpart; float* sdiag;                    // forward: [parts, Np] part sums of Z; [Np] the diagonal
     float* partial;                                 // backward: [parts, Np, Fp] part accumulators
+    const float* own_rows;                          // intraview backward: the owner's row-major image, the second stream's
+    int mask_diag;                                  // intraview: 1 leaves the owner's own row out of the intraview stream (INTRA_MASKED)
 };
 
-// IN_BACK_PAIR: the weight of the symmetric pair, w = e * (rz[owner row] + rz2[stream row]), for either owner
-enum { IN_FORWARD = 0, IN_BACK_ANCHOR = 1, IN_BACK_SAMPLE = 2, IN_BACK_PAIR = 3 };
+// IN_BACK_PAIR: the weight of the symmetric pair, w = e * (rz[owner row] + rz2[stream row]), for either owner.
+// The intraview instances: IN_FWD_INTRA is the forward pass whose stream is the owner's own view -- it leaves the
+// diagonal of S alone and, masked, leaves e_ii out; IN_BACK_ANCHOR_INTRA and IN_BACK_PAIR_INTRA walk the part's tiles twice into the
+// one accumulator: the other view with the weight of IN_BACK_ANCHOR / IN_BACK_PAIR, then the owner's own view with
+// w = e * (rz[owner row] + rz[stream row]), the masked diagonal entering as a zero weight.
+enum { IN_FORWARD = 0, IN_BACK_ANCHOR = 1, IN_BACK_SAMPLE = 2, IN_BACK_PAIR = 3, IN_FWD_INTRA = 4, IN_BACK_ANCHOR_INTRA = 5, IN_BACK_PAIR_INTRA = 6 };
+constexpr bool in_forward(int mode) { return mode == IN_FORWARD || mode == IN_FWD_INTRA; }
+constexpr bool in_intra(int mode) { return mode >= IN_FWD_INTRA; }
+constexpr bool in_lane_rz(int mode) { return mode != IN_BACK_SAMPLE && !in_forward(mode); }
 
 template <int NFT, int MODE>
 __global__ __launch_bounds__(IN_THREADS) void k_in_main(Main a) {
@@ -112,47 +126,89 @@ __global__ __launch_bounds__(IN_THREADS) void k_in_main(Main a) {
 
     double zsum = 0.0;
     float rz_lane = 0.0f;
-    if ((MODE == IN_BACK_ANCHOR || MODE == IN_BACK_PAIR) && active) rz_lane = a.rz[orow];
+    if (in_lane_rz(MODE) && active) rz_lane = a.rz[orow];
     f32x16 acc[NFT];
-    if (MODE != IN_FORWARD) tile32::zero_tiles(acc);
+    if (!in_forward(MODE)) tile32::zero_tiles(acc);
 
+    if (!in_intra(MODE)) {
 #pragma unroll 1
-    for (int64_t t = tb; t < te; ++t) {
-        __syncthreads();   // (the previous tile has been read)
-        tile32::stage_tile<IN_THREADS>(in_lds, a.str_frag + t * tile_floats, MODE != IN_FORWARD ? a.str_rows + t * tile_floats : nullptr, tile_vec);
-        __syncthreads();
-        if (!active) continue;
-        f32x16 x = tile32::pair_chain(reinterpret_cast<const float4*>(in_lds), owner, nqq, lane);
-        const int64_t srow0 = t * infonce::TILE;
-        if (MODE == IN_FORWARD) {
+        for (int64_t t = tb; t < te; ++t) {
+            __syncthreads();   // (the previous tile has been read)
+            tile32::stage_tile<IN_THREADS>(in_lds, a.str_frag + t * tile_floats, MODE != IN_FORWARD ? a.str_rows + t * tile_floats : nullptr, tile_vec);
+            __syncthreads();
+            if (!active) continue;
+            f32x16 x = tile32::pair_chain(reinterpret_cast<const float4*>(in_lds), owner, nqq, lane);
+            const int64_t srow0 = t * infonce::TILE;
+            if (MODE == IN_FORWARD) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int64_t srow = srow0 + infonce::reg_row(r, h);
-                const float e = infonce::expw(infonce::exp_arg(x[r], a.itf));
-                const double z2 = zsum + (double)e;
-                zsum = srow < a.N ? z2 : zsum;
-                if (srow == orow) a.sdiag[orow] = x[r];   // (once per owner row of the call: the tile t == ot of one part)
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int64_t srow = srow0 + infonce::reg_row(r, h);
-                const float e = infonce::expw(infonce::exp_arg(x[r], a.itf));
-                float p;
-                if (MODE == IN_BACK_PAIR) {
-                    p = infonce::pair_weight(e, rz_lane, a.rz2[srow]);
-                } else {
-                    const float rz = MODE == IN_BACK_ANCHOR ? rz_lane : a.rz[srow];   // (srow < Np; 0 behind N)
-                    p = infonce::prob(e, rz);
+                for (int r = 0; r < 16; ++r) {
+                    const int64_t srow = srow0 + infonce::reg_row(r, h);
+                    const float e = infonce::expw(infonce::exp_arg(x[r], a.itf));
+                    const double z2 = zsum + (double)e;
+                    zsum = srow < a.N ? z2 : zsum;
+                    if (srow == orow) a.sdiag[orow] = x[r];   // (once per owner row of the call: the tile t == ot of one part)
                 }
-                x[r] = srow < a.N ? p : 0.0f;
+            } else {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int64_t srow = srow0 + infonce::reg_row(r, h);
+                    const float e = infonce::expw(infonce::exp_arg(x[r], a.itf));
+                    float p;
+                    if (MODE == IN_BACK_PAIR) {
+                        p = infonce::pair_weight(e, rz_lane, a.rz2[srow]);
+                    } else {
+                        const float rz = MODE == IN_BACK_ANCHOR ? rz_lane : a.rz[srow];   // (srow < Np; 0 behind N)
+                        p = infonce::prob(e, rz);
+                    }
+                    x[r] = srow < a.N ? p : 0.0f;
+                }
+                tile32::accumulate_tiles(acc, a.nft, x, in_lds + (int)tile_floats, a.Fp, c, h);
             }
-            tile32::accumulate_tiles(acc, a.nft, x, in_lds + (int)tile_floats, a.Fp, c, h);
+        }
+    } else {
+        // the intraview instances: the same steps; the backward ones walk the part's tiles of the other view, then the same tiles of
+        // the owner's own view (`intra`), into the one accumulator
+#pragma unroll 1
+        for (int pass = 0; pass < (in_forward(MODE) ? 1 : 2); ++pass) {
+            const bool intra = in_forward(MODE) || pass == 1;            // (uniform) the stream is the owner's own view
+            const float* __restrict__ sfrag = intra ? a.own_frag : a.str_frag;
+            const float* __restrict__ srows = intra ? a.own_rows : a.str_rows;
+            const float* __restrict__ rzs = intra ? a.rz : a.rz2;        // the reciprocals of the stream's rows (the owner's list in its own view)
+            const int64_t skip = intra && a.mask_diag ? orow : -1;       // the stream row that is left out
+#pragma unroll 1
+            for (int64_t t = tb; t < te; ++t) {
+                __syncthreads();   // (the previous tile has been read)
+                tile32::stage_tile<IN_THREADS>(in_lds, sfrag + t * tile_floats, !in_forward(MODE) ? srows + t * tile_floats : nullptr, tile_vec);
+                __syncthreads();
+                if (!active) continue;
+                f32x16 x = tile32::pair_chain(reinterpret_cast<const float4*>(in_lds), owner, nqq, lane);
+                const int64_t srow0 = t * infonce::TILE;
+                if (in_forward(MODE)) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int64_t srow = srow0 + infonce::reg_row(r, h);
+                        const float e = infonce::expw(infonce::exp_arg(x[r], a.itf));
+                        const double z2 = zsum + (double)e;
+                        zsum = srow < a.N && srow != skip ? z2 : zsum;   // (the diagonal of S^ab is the other pass's to keep)
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int64_t srow = srow0 + infonce::reg_row(r, h);
+                        const float e = infonce::expw(infonce::exp_arg(x[r], a.itf));
+                        float p;
+                        if (MODE == IN_BACK_PAIR_INTRA || intra) p = infonce::pair_weight(e, rz_lane, rzs[srow]);   // (srow < Np; 0 behind N)
+                        else p = infonce::prob(e, rz_lane);
+                        x[r] = srow < a.N && srow != skip ? p : 0.0f;
+                    }
+                    tile32::accumulate_tiles(acc, a.nft, x, in_lds + (int)tile_floats, a.Fp, c, h);
+                }
+            }
         }
     }
 
     if (!active) return;
-    if (MODE == IN_FORWARD) {
+    if (in_forward(MODE)) {
         const double other = __shfl_xor(zsum, 32);
         if (h == 0) a.zpart[part * a.Np + orow] = zsum + other;      // half 0 + half 1
     } else {
@@ -279,6 +335,25 @@ __global__ __launch_bounds__(256) void k_in_pair_rows(const double* __restrict__
     }
 }
 
+// the same with intraview negatives: the parts of the two intraview sums (zintra: [2, iparts, Np], view a then view b) follow the
+// pair's parts and groups in the two float64 chains
+__global__ __launch_bounds__(256) void k_in_pair_rows_intra(const double* __restrict__ zpart, const double* __restrict__ colpart,
+                                                            const double* __restrict__ zintra, const float* __restrict__ sdiag, int64_t N, int64_t Np,
+                                                            int parts, int groups, int iparts, double c, double itau, double* __restrict__ z,
+                                                            double* __restrict__ rows) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
+        double Z = 0.0, Zc = 0.0;
+        for (int p = 0; p < parts; ++p) Z = Z + zpart[p * Np + i];
+        for (int p = 0; p < iparts; ++p) Z = Z + zintra[p * Np + i];
+        for (int q = 0; q < groups; ++q) Zc = Zc + colpart[q * Np + i];
+        for (int p = 0; p < iparts; ++p) Zc = Zc + zintra[(iparts + p) * Np + i];
+        z[i] = Z;
+        z[N + i] = Zc;
+        rows[i] = infonce::row_term(c, sdiag[i], itau, Z);
+        rows[N + i] = infonce::row_term(c, sdiag[i], itau, Zc);
+    }
+}
+
 __global__ __launch_bounds__(256) void k_in_pair_chunks(const double* __restrict__ rows, int64_t N, double* __restrict__ csum) {
     tile32::chunk_sums(rows, N, 2, csum);
 }
@@ -342,10 +417,12 @@ struct Bufs {
     double* zpart; float* sdiag; double* csum;
     float* rz; float *part_a, *part_b;
     double* colpart; float* rz2;                    // the pair's: the group sums of Zc; the second reciprocal vector
+    double* zintra;                                 // the pair's with intraview negatives: [2, num_parts, Np] part sums of the intraview sums
 };
 
 // the pair's arena: the one-direction call's with the pair's partial sums (forward) or the second reciprocal vector (backward)
-size_t carve_pair(Carve& C, int64_t N, int64_t F, bool backward, Bufs& B) {
+// (intraview negatives: the forward call keeps the part sums of the two intraview sums; the backward call needs nothing more)
+size_t carve_pair(Carve& C, int64_t N, int64_t F, bool backward, int intraview, Bufs& B) {
     const int64_t Np = infonce::padded_rows(N), Fp = infonce::padded_features(F);
     B = Bufs{};
     B.n2a = C.take<double>(Np);
@@ -357,6 +434,7 @@ size_t carve_pair(Carve& C, int64_t N, int64_t F, bool backward, Bufs& B) {
         B.colpart = C.take<double>(infonce::pair_groups(N) * Np);
         B.sdiag = C.take<float>(Np);
         B.csum = C.take<double>(2 * spmm::num_chunks(N));
+        if (intraview != infonce::INTRA_NONE) B.zintra = C.take<double>(2 * infonce::num_parts(N) * Np);
     } else {
         const int64_t parts = infonce::num_parts(N);
         B.a_rows = C.take<float>(Np * Fp);
@@ -369,7 +447,8 @@ size_t carve_pair(Carve& C, int64_t N, int64_t F, bool backward, Bufs& B) {
     return C.off + 256;
 }
 
-size_t carve_infonce(Carve& C, int64_t N, int64_t F, bool backward, Bufs& B) {
+// (intraview negatives: the forward call's part sums are the row sum's, then the intraview sum's; the backward call's arena is unchanged)
+size_t carve_infonce(Carve& C, int64_t N, int64_t F, bool backward, int intraview, Bufs& B) {
     const int64_t Np = infonce::padded_rows(N), Fp = infonce::padded_features(F), parts = infonce::num_parts(N);
     B = Bufs{};
     B.n2a = C.take<double>(Np);
@@ -377,7 +456,7 @@ size_t carve_infonce(Carve& C, int64_t N, int64_t F, bool backward, Bufs& B) {
     B.a_frag = C.take<float>(Np * Fp);
     B.b_frag = C.take<float>(Np * Fp);
     if (!backward) {
-        B.zpart = C.take<double>(parts * Np);
+        B.zpart = C.take<double>((intraview != infonce::INTRA_NONE ? infonce::intra_z_parts(N) : parts) * Np);
         B.sdiag = C.take<float>(Np);
         B.csum = C.take<double>(spmm::num_chunks(N));
     } else {
@@ -401,7 +480,7 @@ Main main_args(const InfonceArgs& g) {
 
 template <int NFT, int MODE>
 int launch_main_t(hipStream_t st, const Main& m) {
-    const size_t lds = (size_t)infonce::TILE * m.Fp * sizeof(float) * (MODE == IN_FORWARD ? 1 : 2);
+    const size_t lds = (size_t)infonce::TILE * m.Fp * sizeof(float) * (in_forward(MODE) ? 1 : 2);
     if (const int rc = tile32::allow_lds(&k_in_main<NFT, MODE>, lds)) return rc;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_in_main<NFT, MODE>), dim3((unsigned)(m.RB * m.parts)), dim3(IN_THREADS), lds, st, m);
     RLAP_HIPCHK(hipGetLastError());
@@ -411,6 +490,13 @@ int launch_main_t(hipStream_t st, const Main& m) {
 template <int MODE>
 int launch_backward_main(hipStream_t st, const Main& m) {
     return tile32::ladder_launch(m.nft, [&](auto nft) { return launch_main_t<decltype(nft)::value, MODE>(st, m); });
+}
+
+// the forward pass of one view against itself: the part sums of its intraview sum into zpart [num_parts, Np]
+int launch_forward_intra(hipStream_t st, Main m, int intraview, const float* frag, double* zpart) {
+    m.own_frag = frag; m.str_frag = frag; m.zpart = zpart; m.sdiag = nullptr;
+    m.mask_diag = intraview == infonce::INTRA_MASKED;
+    return launch_main_t<1, IN_FWD_INTRA>(st, m);
 }
 
 int prepass(hipStream_t st, const InfonceArgs& g, const Bufs& B) {
@@ -425,28 +511,33 @@ int prepass(hipStream_t st, const InfonceArgs& g, const Bufs& B) {
 
 }  // namespace
 
-size_t infonce_bytes(int64_t N, int64_t F) {
+size_t infonce_bytes(int64_t N, int64_t F, int intraview) {
     Carve C{nullptr, 0};
     Bufs B;
-    return carve_infonce(C, N, F, false, B);
+    return carve_infonce(C, N, F, false, intraview, B);
 }
 
-size_t infonce_backward_bytes(int64_t N, int64_t F) {
+size_t infonce_backward_bytes(int64_t N, int64_t F, int intraview) {
     Carve C{nullptr, 0};
     Bufs B;
-    return carve_infonce(C, N, F, true, B);
+    return carve_infonce(C, N, F, true, intraview, B);
 }
 
 int infonce_run(hipStream_t st, void* ws, size_t ws_bytes, const InfonceArgs& g) {
     Bufs B;
     Carve C{static_cast<char*>(ws), 0};
-    if (carve_infonce(C, g.N, g.F, false, B) > ws_bytes) return RLAP_E_WORKSPACE;
+    if (carve_infonce(C, g.N, g.F, false, g.intraview, B) > ws_bytes) return RLAP_E_WORKSPACE;
     if (const int rc = prepass(st, g, B)) return rc;
     Main m = main_args(g);
     m.own_frag = B.a_frag; m.str_frag = B.b_frag; m.zpart = B.zpart; m.sdiag = B.sdiag;
     if (const int rc = launch_main_t<1, IN_FORWARD>(st, m)) return rc;
+    int zparts = m.parts;
+    if (g.intraview != infonce::INTRA_NONE) {   // the anchors against themselves: the part sums behind the row sum's
+        if (const int rc = launch_forward_intra(st, m, g.intraview, B.a_frag, B.zpart + (int64_t)m.parts * m.Np)) return rc;
+        zparts = (int)infonce::intra_z_parts(g.N);
+    }
     const double c = infonce::positive_coef((g.flags & RLAP_INFONCE_POSITIVE_RAW) != 0, g.tau), itau = infonce::inv_tau(g.tau);
-    hipLaunchKernelGGL(k_in_rows, dim3(in_blocks(g.N, 256)), dim3(256), 0, st, (const double*)B.zpart, (const float*)B.sdiag, g.N, m.Np, m.parts,
+    hipLaunchKernelGGL(k_in_rows, dim3(in_blocks(g.N, 256)), dim3(256), 0, st, (const double*)B.zpart, (const float*)B.sdiag, g.N, m.Np, zparts,
                        c, itau, g.z, g.rows);
     hipLaunchKernelGGL(k_in_chunks, dim3(in_blocks(spmm::num_chunks(g.N), 256)), dim3(256), 0, st, (const double*)g.rows, g.N, B.csum);
     hipLaunchKernelGGL(k_in_loss, dim3(1), dim3(64), 0, st, (const double*)B.csum, g.N, g.loss);
@@ -457,7 +548,7 @@ int infonce_run(hipStream_t st, void* ws, size_t ws_bytes, const InfonceArgs& g)
 int infonce_backward_run(hipStream_t st, void* ws, size_t ws_bytes, const InfonceArgs& g) {
     Bufs B;
     Carve C{static_cast<char*>(ws), 0};
-    if (carve_infonce(C, g.N, g.F, true, B) > ws_bytes) return RLAP_E_WORKSPACE;
+    if (carve_infonce(C, g.N, g.F, true, g.intraview, B) > ws_bytes) return RLAP_E_WORKSPACE;
     if (const int rc = prepass(st, g, B)) return rc;
     Main m = main_args(g);
     hipLaunchKernelGGL(k_in_recip, dim3(in_blocks(m.Np, 256)), dim3(256), 0, st, g.z_in, g.N, m.Np, B.rz);
@@ -466,7 +557,12 @@ int infonce_backward_run(hipStream_t st, void* ws, size_t ws_bytes, const Infonc
     const double c = infonce::positive_coef((g.flags & RLAP_INFONCE_POSITIVE_RAW) != 0, g.tau), itau = infonce::inv_tau(g.tau);
     // the anchors own, the samples stream: D = sum_j p_ij bh_j
     m.own_frag = B.a_frag; m.str_frag = B.b_frag; m.str_rows = B.b_rows; m.partial = B.part_a;
-    if (const int rc = launch_backward_main<IN_BACK_ANCHOR>(st, m)) return rc;
+    if (g.intraview != infonce::INTRA_NONE) {   // then the anchors themselves, into the same accumulator
+        m.own_rows = B.a_rows; m.mask_diag = g.intraview == infonce::INTRA_MASKED;
+        if (const int rc = launch_backward_main<IN_BACK_ANCHOR_INTRA>(st, m)) return rc;
+    } else if (const int rc = launch_backward_main<IN_BACK_ANCHOR>(st, m)) {
+        return rc;
+    }
     // the samples own, the anchors stream: D' = sum_i p_ij ah_i
     m.own_frag = B.b_frag; m.str_frag = B.a_frag; m.str_rows = B.a_rows; m.partial = B.part_b;
     if (const int rc = launch_backward_main<IN_BACK_SAMPLE>(st, m)) return rc;
@@ -479,16 +575,16 @@ int infonce_backward_run(hipStream_t st, void* ws, size_t ws_bytes, const Infonc
 }
 
 // ------------------------------------------------------------------------------------------------ the symmetric pair
-size_t infonce_pair_bytes(int64_t N, int64_t F) {
+size_t infonce_pair_bytes(int64_t N, int64_t F, int intraview) {
     Carve C{nullptr, 0};
     Bufs B;
-    return carve_pair(C, N, F, false, B);
+    return carve_pair(C, N, F, false, intraview, B);
 }
 
-size_t infonce_pair_backward_bytes(int64_t N, int64_t F) {
+size_t infonce_pair_backward_bytes(int64_t N, int64_t F, int intraview) {
     Carve C{nullptr, 0};
     Bufs B;
-    return carve_pair(C, N, F, true, B);
+    return carve_pair(C, N, F, true, intraview, B);
 }
 
 // LDS of k_in_pair_main: the stream tile's fragment image, the span's column sums, the four waves' sums
@@ -500,7 +596,7 @@ size_t infonce_pair_lds_bytes(int64_t N, int64_t F) {
 int infonce_pair_run(hipStream_t st, void* ws, size_t ws_bytes, const InfonceArgs& g) {
     Bufs B;
     Carve C{static_cast<char*>(ws), 0};
-    if (carve_pair(C, g.N, g.F, false, B) > ws_bytes) return RLAP_E_WORKSPACE;
+    if (carve_pair(C, g.N, g.F, false, g.intraview, B) > ws_bytes) return RLAP_E_WORKSPACE;
     if (const int rc = prepass(st, g, B)) return rc;
     PairMain m{};
     m.own_frag = B.a_frag; m.str_frag = B.b_frag; m.itf = infonce::inv_tau_f(g.tau);
@@ -512,8 +608,16 @@ int infonce_pair_run(hipStream_t st, void* ws, size_t ws_bytes, const InfonceArg
     if (const int rc = tile32::allow_lds(&k_in_pair_main, lds)) return rc;
     hipLaunchKernelGGL(k_in_pair_main, dim3((unsigned)(m.groups * parts)), dim3(IN_THREADS), lds, st, m);
     const double c = infonce::positive_coef((g.flags & RLAP_INFONCE_POSITIVE_RAW) != 0, g.tau), itau = infonce::inv_tau(g.tau);
-    hipLaunchKernelGGL(k_in_pair_rows, dim3(in_blocks(g.N, 256)), dim3(256), 0, st, (const double*)B.zpart, (const double*)B.colpart,
-                       (const float*)B.sdiag, g.N, m.Np, parts, m.groups, c, itau, g.z, g.rows);
+    if (g.intraview != infonce::INTRA_NONE) {   // each view against itself, over the one-direction parts
+        const Main im = main_args(g);
+        if (const int rc = launch_forward_intra(st, im, g.intraview, B.a_frag, B.zintra)) return rc;
+        if (const int rc = launch_forward_intra(st, im, g.intraview, B.b_frag, B.zintra + (int64_t)im.parts * im.Np)) return rc;
+        hipLaunchKernelGGL(k_in_pair_rows_intra, dim3(in_blocks(g.N, 256)), dim3(256), 0, st, (const double*)B.zpart, (const double*)B.colpart,
+                           (const double*)B.zintra, (const float*)B.sdiag, g.N, m.Np, parts, m.groups, im.parts, c, itau, g.z, g.rows);
+    } else {
+        hipLaunchKernelGGL(k_in_pair_rows, dim3(in_blocks(g.N, 256)), dim3(256), 0, st, (const double*)B.zpart, (const double*)B.colpart,
+                           (const float*)B.sdiag, g.N, m.Np, parts, m.groups, c, itau, g.z, g.rows);
+    }
     hipLaunchKernelGGL(k_in_pair_chunks, dim3(in_blocks(2 * spmm::num_chunks(g.N), 256)), dim3(256), 0, st, (const double*)g.rows, g.N, B.csum);
     hipLaunchKernelGGL(k_in_pair_loss, dim3(1), dim3(64), 0, st, (const double*)B.csum, g.N, g.loss);
     RLAP_HIPCHK(hipGetLastError());
@@ -523,7 +627,7 @@ int infonce_pair_run(hipStream_t st, void* ws, size_t ws_bytes, const InfonceArg
 int infonce_pair_backward_run(hipStream_t st, void* ws, size_t ws_bytes, const InfonceArgs& g) {
     Bufs B;
     Carve C{static_cast<char*>(ws), 0};
-    if (carve_pair(C, g.N, g.F, true, B) > ws_bytes) return RLAP_E_WORKSPACE;
+    if (carve_pair(C, g.N, g.F, true, g.intraview, B) > ws_bytes) return RLAP_E_WORKSPACE;
     if (const int rc = prepass(st, g, B)) return rc;
     Main m = main_args(g);
     hipLaunchKernelGGL(k_in_recip, dim3(in_blocks(m.Np, 256)), dim3(256), 0, st, g.z_in, g.N, m.Np, B.rz);             // 1 / Z of the anchors
@@ -531,11 +635,13 @@ int infonce_pair_backward_run(hipStream_t st, void* ws, size_t ws_bytes, const I
     RLAP_HIPCHK(hipGetLastError());
     const double c2 = infonce::pair_positive_coef((g.flags & RLAP_INFONCE_POSITIVE_RAW) != 0, g.tau), itau = infonce::inv_tau(g.tau);
     // the anchors own, the samples stream: D = sum_j w_ij bh_j
-    m.own_frag = B.a_frag; m.str_frag = B.b_frag; m.str_rows = B.b_rows; m.partial = B.part_a; m.rz = B.rz; m.rz2 = B.rz2;
-    if (const int rc = launch_backward_main<IN_BACK_PAIR>(st, m)) return rc;
+    const bool intra = g.intraview != infonce::INTRA_NONE;   // then the owner's own view, into the same accumulator
+    m.mask_diag = g.intraview == infonce::INTRA_MASKED;
+    m.own_frag = B.a_frag; m.str_frag = B.b_frag; m.str_rows = B.b_rows; m.partial = B.part_a; m.rz = B.rz; m.rz2 = B.rz2; m.own_rows = B.a_rows;
+    if (const int rc = intra ? launch_backward_main<IN_BACK_PAIR_INTRA>(st, m) : launch_backward_main<IN_BACK_PAIR>(st, m)) return rc;
     // the samples own, the anchors stream: D' = sum_i w_ij ah_i
-    m.own_frag = B.b_frag; m.str_frag = B.a_frag; m.str_rows = B.a_rows; m.partial = B.part_b; m.rz = B.rz2; m.rz2 = B.rz;
-    if (const int rc = launch_backward_main<IN_BACK_PAIR>(st, m)) return rc;
+    m.own_frag = B.b_frag; m.str_frag = B.a_frag; m.str_rows = B.a_rows; m.partial = B.part_b; m.rz = B.rz2; m.rz2 = B.rz; m.own_rows = B.b_rows;
+    if (const int rc = intra ? launch_backward_main<IN_BACK_PAIR_INTRA>(st, m) : launch_backward_main<IN_BACK_PAIR>(st, m)) return rc;
     hipLaunchKernelGGL(k_in_grad, dim3(in_blocks(g.N, IN_GRAD_WAVES)), dim3(64 * IN_GRAD_WAVES), 0, st, (const float*)B.part_a, m.parts, g.N, g.F, m.Np, m.Fp,
                        (const float*)B.a_rows, (const float*)B.b_rows, (const double*)B.n2a, g.g, c2, itau, 1, g.ga);
     hipLaunchKernelGGL(k_in_grad, dim3(in_blocks(g.N, IN_GRAD_WAVES)), dim3(64 * IN_GRAD_WAVES), 0, st, (const float*)B.part_b, m.parts, g.N, g.F, m.Np, m.Fp,

@@ -1339,6 +1339,7 @@ def graph_readout(x: Tensor, node_ptr: Union[Tensor, Sequence[int], GraphTable],
 INFONCE_POSITIVE = {"scaled": 0, "raw": _lib.INFONCE_POSITIVE_RAW}
 INFONCE_MAX_F = 512
 INFONCE_TAU = (1.0 / 32.0, 1024.0)
+INFONCE_INTRAVIEW = {"none": 0, "masked": _lib.INFONCE_INTRA_MASKED, "all": _lib.INFONCE_INTRA_ALL}
 
 
 def _info_nce_args(anchor, sample, tau, positive):
@@ -1367,7 +1368,23 @@ def _info_nce_args(anchor, sample, tau, positive):
     return tau, INFONCE_POSITIVE[positive]
 
 
-def _info_nce_forward(a: Tensor, b: Tensor, tau: float, flags: int):
+def _info_nce_intraview(intraview):
+    """The `intraview` keyword of info_nce and info_nce_pair as the C ABI's value; 0 is "none", which takes the plain exports."""
+    if not isinstance(intraview, str) or intraview not in INFONCE_INTRAVIEW:
+        raise ValueError(f"intraview: one of {sorted(INFONCE_INTRAVIEW)}, got {intraview!r}")
+    return INFONCE_INTRAVIEW[intraview]
+
+
+def _intra_call(name, intra, args):
+    """(export, arguments) of an InfoNCE call: the plain export with today's arguments, or its _intra twin with the variant behind
+    `flags` (the sixth argument after the handle)."""
+    if not intra:
+        return name, args
+    stem, back = (name[:-len("_backward")], "_backward") if name.endswith("_backward") else (name, "")
+    return stem + "_intra" + back, args[:6] + (intra,) + args[6:]
+
+
+def _info_nce_forward(a: Tensor, b: Tensor, tau: float, flags: int, intra: int = 0):
     """The forward export: (loss 0-dim, rows [N], z [N], the device copies of a and b)."""
     dev = _device_for(a)
     with torch.cuda.device(dev):
@@ -1376,7 +1393,8 @@ def _info_nce_forward(a: Tensor, b: Tensor, tau: float, flags: int):
         n, f = int(d_a.shape[0]), int(d_a.shape[1])
         out = torch.empty(1 + 2 * n, dtype=torch.float64, device=dev)   # loss | rows | z
         p = out.data_ptr()
-        _device_call("rlap_infonce", _lib.InfonceInfo, dev, 1, (d_a.data_ptr(), d_b.data_ptr(), n, f, tau, flags, p, p + 8, p + 8 * (1 + n)))
+        export, args = _intra_call("rlap_infonce", intra, (d_a.data_ptr(), d_b.data_ptr(), n, f, tau, flags, p, p + 8, p + 8 * (1 + n)))
+        _device_call(export, _lib.InfonceInfo, dev, 1, args)
     return out[0], out[1:1 + n], out[1 + n:], d_a, d_b
 
 
@@ -1384,10 +1402,10 @@ class _InfoNCE(torch.autograd.Function):
     """loss = the fused InfoNCE of (anchor, sample); the gradients with respect to both come from the backward export."""
 
     @staticmethod
-    def forward(ctx, a, b, tau, flags):
-        loss, rows, z, d_a, d_b = _info_nce_forward(a, b, tau, flags)
+    def forward(ctx, a, b, tau, flags, intra):
+        loss, rows, z, d_a, d_b = _info_nce_forward(a, b, tau, flags, intra)
         ctx.save_for_backward(d_a, d_b, z)
-        ctx.call = (tau, flags, a.device, b.device)
+        ctx.call = (tau, flags, intra, a.device, b.device)
         ctx.mark_non_differentiable(rows)
         return loss, rows
 
@@ -1395,19 +1413,20 @@ class _InfoNCE(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, g, _g_rows):
         d_a, d_b, z = ctx.saved_tensors
-        tau, flags, dev_a, dev_b = ctx.call
+        tau, flags, intra, dev_a, dev_b = ctx.call
         dev = d_a.device
         with torch.cuda.device(dev):
             d_g = _upstream(g, dev)
             n, f = int(d_a.shape[0]), int(d_a.shape[1])
             ga = torch.empty_like(d_a)
             gb = torch.empty_like(d_b)
-            _device_call("rlap_infonce_backward", _lib.InfonceInfo, dev, 1, (
+            export, args = _intra_call("rlap_infonce_backward", intra, (
                 d_a.data_ptr(), d_b.data_ptr(), n, f, tau, flags, z.data_ptr(), d_g.data_ptr(), ga.data_ptr(), gb.data_ptr()))
-        return ga.to(dev_a), gb.to(dev_b), None, None
+            _device_call(export, _lib.InfonceInfo, dev, 1, args)
+        return ga.to(dev_a), gb.to(dev_b), None, None, None
 
 
-def info_nce(anchor: Tensor, sample: Tensor, tau: float = 0.4, positive: str = "scaled", return_rows: bool = False):
+def info_nce(anchor: Tensor, sample: Tensor, tau: float = 0.4, positive: str = "scaled", return_rows: bool = False, intraview: str = "none"):
     """The InfoNCE contrastive loss of two views' node embeddings, fused on the device (rlap_infonce): with the rows
     normalised, s = ah bh^T, loss = -mean_i(c s_ii - log sum_j exp(s_ij / tau)) -- one direction of
     DualBranchContrast(InfoNCEBatched(tau), mode="L2L") (scripts/node_shared.py) without the N x N similarity matrix.
@@ -1417,6 +1436,10 @@ def info_nce(anchor: Tensor, sample: Tensor, tau: float = 0.4, positive: str = "
       positive       : "scaled" -- c = 1 / tau, GCL's InfoNCE; "raw" -- c = 1, the reference's InfoNCEBatched, which does not
                        divide the positive term by tau
       return_rows    : also return the (N,) float64 row terms c s_ii - 1/tau - log Z_i (not differentiable)
+      intraview      : intraview negatives, the sampler's intraview_negs=True (rlap_infonce_intra): "none" -- the
+                       denominator holds the sample's rows alone; "masked" -- and the anchor's other rows j != i (GCL's InfoNCE
+                       under the sampler's masks: the loss GRACE was published with); "all" -- and every anchor row, row i itself
+                       included (the reference's InfoNCEBatched under the same sampler, which never reads the masks)
     Returns the 0-dim float64 loss.  The positive of row i is column i; every column is in the denominator.  Every value and the
     order of every sum are fixed (rlap_amd/csrc/rlap_infonce.h): the same input gives the same bits.  Memory is O(N F).
 
@@ -1426,14 +1449,15 @@ def info_nce(anchor: Tensor, sample: Tensor, tau: float = 0.4, positive: str = "
     host_syncs).
     """
     tau, flags = _info_nce_args(anchor, sample, tau, positive)
+    intra = _info_nce_intraview(intraview)
     if torch.is_grad_enabled() and (anchor.requires_grad or sample.requires_grad):
-        loss, rows = _InfoNCE.apply(anchor, sample, tau, flags)
+        loss, rows = _InfoNCE.apply(anchor, sample, tau, flags, intra)
     else:
-        loss, rows = _info_nce_forward(anchor, sample, tau, flags)[:2]
+        loss, rows = _info_nce_forward(anchor, sample, tau, flags, intra)[:2]
     return (loss, rows) if return_rows else loss
 
 
-def _info_nce_pair_forward(a: Tensor, b: Tensor, tau: float, flags: int):
+def _info_nce_pair_forward(a: Tensor, b: Tensor, tau: float, flags: int, intra: int = 0):
     """The pair's forward export: (loss 0-dim, rows [2, N], z [2, N], the device copies of a and b)."""
     dev = _device_for(a)
     with torch.cuda.device(dev):
@@ -1442,7 +1466,8 @@ def _info_nce_pair_forward(a: Tensor, b: Tensor, tau: float, flags: int):
         n, f = int(d_a.shape[0]), int(d_a.shape[1])
         out = torch.empty(1 + 4 * n, dtype=torch.float64, device=dev)   # loss | rows (2N) | z (2N)
         p = out.data_ptr()
-        _device_call("rlap_infonce_pair", _lib.InfoncePairInfo, dev, 1, (d_a.data_ptr(), d_b.data_ptr(), n, f, tau, flags, p, p + 8, p + 8 * (1 + 2 * n)))
+        export, args = _intra_call("rlap_infonce_pair", intra, (d_a.data_ptr(), d_b.data_ptr(), n, f, tau, flags, p, p + 8, p + 8 * (1 + 2 * n)))
+        _device_call(export, _lib.InfoncePairInfo, dev, 1, args)
     return out[0], out[1:1 + 2 * n].view(2, n), out[1 + 2 * n:].view(2, n), d_a, d_b
 
 
@@ -1450,10 +1475,10 @@ class _InfoNCEPair(torch.autograd.Function):
     """loss = the symmetric InfoNCE of two views; the gradients with respect to both come from one call of the backward export."""
 
     @staticmethod
-    def forward(ctx, a, b, tau, flags):
-        loss, rows, z, d_a, d_b = _info_nce_pair_forward(a, b, tau, flags)
+    def forward(ctx, a, b, tau, flags, intra):
+        loss, rows, z, d_a, d_b = _info_nce_pair_forward(a, b, tau, flags, intra)
         ctx.save_for_backward(d_a, d_b, z)
-        ctx.call = (tau, flags, a.device, b.device)
+        ctx.call = (tau, flags, intra, a.device, b.device)
         ctx.mark_non_differentiable(rows)
         return loss, rows
 
@@ -1461,19 +1486,20 @@ class _InfoNCEPair(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, g, _g_rows):
         d_a, d_b, z = ctx.saved_tensors
-        tau, flags, dev_a, dev_b = ctx.call
+        tau, flags, intra, dev_a, dev_b = ctx.call
         dev = d_a.device
         with torch.cuda.device(dev):
             d_g = _upstream(g, dev)
             n, f = int(d_a.shape[0]), int(d_a.shape[1])
             ga = torch.empty_like(d_a)
             gb = torch.empty_like(d_b)
-            _device_call("rlap_infonce_pair_backward", _lib.InfoncePairInfo, dev, 1, (
+            export, args = _intra_call("rlap_infonce_pair_backward", intra, (
                 d_a.data_ptr(), d_b.data_ptr(), n, f, tau, flags, z.data_ptr(), d_g.data_ptr(), ga.data_ptr(), gb.data_ptr()))
-        return ga.to(dev_a), gb.to(dev_b), None, None
+            _device_call(export, _lib.InfoncePairInfo, dev, 1, args)
+        return ga.to(dev_a), gb.to(dev_b), None, None, None
 
 
-def info_nce_pair(h1: Tensor, h2: Tensor, tau: float = 0.4, positive: str = "scaled", return_rows: bool = False):
+def info_nce_pair(h1: Tensor, h2: Tensor, tau: float = 0.4, positive: str = "scaled", return_rows: bool = False, intraview: str = "none"):
     """The symmetric InfoNCE loss of two views, 0.5 * (info_nce(h1, h2) + info_nce(h2, h1)), from one pass over the similarities
     (rlap_infonce_pair): what DualBranchContrast(InfoNCEBatched(tau), mode="L2L") computes for both directions.  The
     similarity of the second direction is the transpose of the first's bit for bit, so the row sums and the column sums of one set
@@ -1482,6 +1508,8 @@ def info_nce_pair(h1: Tensor, h2: Tensor, tau: float = 0.4, positive: str = "sca
 
       h1, h2, tau, positive : as info_nce
       return_rows           : also return the (2, N) float64 row terms: those of (h1, h2), then those of (h2, h1) (not differentiable)
+      intraview             : as info_nce: each direction's denominator also holds its anchor view's own rows
+                              (rlap_infonce_pair_intra)
     Returns the 0-dim float64 loss; it equals the two-call value up to the order of the sums, which is fixed here too
     (rlap_amd/csrc/rlap_infonce.h): the same input gives the same bits.  Memory is O(N F).
 
@@ -1490,10 +1518,11 @@ def info_nce_pair(h1: Tensor, h2: Tensor, tau: float = 0.4, positive: str = "sca
     (rlap_infonce_pair_info: rows, features, arena_bytes, parts, groups, host_syncs).
     """
     tau, flags = _info_nce_args(h1, h2, tau, positive)
+    intra = _info_nce_intraview(intraview)
     if torch.is_grad_enabled() and (h1.requires_grad or h2.requires_grad):
-        loss, rows = _InfoNCEPair.apply(h1, h2, tau, flags)
+        loss, rows = _InfoNCEPair.apply(h1, h2, tau, flags, intra)
     else:
-        loss, rows = _info_nce_pair_forward(h1, h2, tau, flags)[:2]
+        loss, rows = _info_nce_pair_forward(h1, h2, tau, flags, intra)[:2]
     return (loss, rows) if return_rows else loss
 
 

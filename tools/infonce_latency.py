@@ -22,6 +22,7 @@ nothing outside the repository.
     python tools/infonce_latency.py
     python tools/infonce_latency.py --shapes physics --no-torch     # the calls alone (for rocprofv3 --kernel-trace --stats)
     python tools/infonce_latency.py --pair                           # one ops.info_nce_pair call against the two calls
+    python tools/infonce_latency.py --intraview                      # the plain and the intraview calls, one-way and pair
 """
 import argparse
 import json
@@ -194,9 +195,93 @@ def run_pair(name, n, f, args, fh):
     torch.cuda.empty_cache()
 
 
+def torch_batched_intra(anchor, sample, variant, tau=TAU, batch_size=BATCH):
+    """torch_batched under the sampler with intraview_negs=True: the sample is the (2N, F) concatenation of the sample and the
+    anchor; "all" sums every column, as InfoNCEBatched does (it never reads the masks), "masked" takes the anchor's own column out."""
+    both = torch.nn.functional.normalize(torch.cat([sample, anchor], dim=0))
+    n = anchor.shape[0]
+    losses = []
+    for s in range(0, n, batch_size):
+        sim = torch.nn.functional.normalize(anchor[s:s + batch_size]) @ both.t()
+        e = torch.exp(sim / tau)
+        total = e.sum(dim=1)
+        if variant == "masked":
+            total = total - e.diagonal(offset=n + s)
+        losses.append(sim.diagonal(offset=s) - torch.log(total))
+    return -torch.cat(losses).mean()
+
+
+def run_intraview(name, n, f, args, fh):
+    """--intraview: in one run the plain call and the intraview call, one-way and pair, forward and forward + backward,
+    with the peak memory of each, the ratios intraview / plain (8/5 one-way and 11/5 pair by product count, forward + backward) and,
+    where its working set fits, torch with the concatenated sample."""
+    variant = args.intraview
+    gen = torch.Generator(device="cuda").manual_seed(n)
+    a = torch.randn(n, f, dtype=torch.float32, device="cuda", generator=gen)
+    b = 0.3 * a + torch.randn(n, f, dtype=torch.float32, device="cuda", generator=gen)
+    rec = {"mode": "intraview", "variant": variant, "shape": name, "N": n, "F": f, "tau": TAU, "flops_per_product": 2.0 * n * n * f}
+    calls = {
+        "plain": lambda x, y: ops.info_nce(x, y, tau=TAU, positive="raw"),
+        "intra": lambda x, y: ops.info_nce(x, y, tau=TAU, positive="raw", intraview=variant),
+        "pair_plain": lambda x, y: ops.info_nce_pair(x, y, tau=TAU, positive="raw"),
+        "pair_intra": lambda x, y: ops.info_nce_pair(x, y, tau=TAU, positive="raw", intraview=variant),
+    }
+    grads = {}
+    for key, fn in calls.items():
+        t, ts, loss, mem = peak_of(lambda: fn(a, b), args.reps)
+        st = dict(ops.last_stats)
+        rec.update({f"{key}_forward_ms": round(t, 3), f"{key}_forward_runs_ms": ts, f"{key}_forward_max_memory_allocated": mem,
+                    f"{key}_forward_arena_bytes": st["arena_bytes"], f"{key}_loss": float(loss), f"{key}_host_syncs": st["host_syncs"]})
+        t2, ts2, g, mem2 = peak_of(both_ways(fn, a, b), args.reps)
+        rec.update({f"{key}_forward_backward_ms": round(t2, 3), f"{key}_forward_backward_runs_ms": ts2,
+                    f"{key}_forward_backward_max_memory_allocated": mem2, f"{key}_backward_arena_bytes": ops.last_stats["arena_bytes"]})
+        again = both_ways(fn, a, b)()
+        rec[f"{key}_gradients_repeat_bit_for_bit"] = bool(torch.equal(g[0], again[0]) and torch.equal(g[1], again[1]))
+        if key in ("intra", "pair_intra"):
+            grads[key] = g
+        del again, g
+    for one, base in (("intra", "plain"), ("pair_intra", "pair_plain")):
+        rec[f"{one}_over_{base}_forward"] = round(rec[f"{one}_forward_ms"] / rec[f"{base}_forward_ms"], 3)
+        rec[f"{one}_over_{base}_forward_backward"] = round(rec[f"{one}_forward_backward_ms"] / rec[f"{base}_forward_backward_ms"], 3)
+    if not args.no_torch:
+        torch.cuda.empty_cache()
+        free, _ = torch.cuda.mem_get_info()
+        block = 3 * 4 * min(BATCH, n) * 2 * n                        # the blocks are 1,024 x 2N
+        kept = 4 * n * 2 * n + 2 * block                             # autograd keeps the N x 2N exponentials of a direction
+        one_way = lambda x, y: torch_batched_intra(x, y, variant)
+        both = lambda x, y: 0.5 * (torch_batched_intra(x, y, variant) + torch_batched_intra(y, x, variant))
+        rec["torch_bytes_forward_estimate"], rec["torch_bytes_forward_backward_estimate"], rec["free_bytes"] = block, kept, int(free)
+        rec["torch_pair_bytes_forward_backward_estimate"] = 2 * kept
+        for key, fn, need, ours in (("torch", one_way, kept, "intra"), ("torch_pair", both, 2 * kept, "pair_intra")):
+            if need > free // 2:
+                rec[f"{key}_forward_backward_ms"] = "not measured: its estimated working set exceeds half of the free memory"
+                continue
+            tt, tts, want, tmem = peak_of(lambda: fn(a, b), args.reps)
+            rec.update({f"{key}_forward_ms": round(tt, 3), f"{key}_forward_runs_ms": tts, f"{key}_forward_max_memory_allocated": tmem,
+                        f"{key}_loss_diff": abs(rec[f"{ours}_loss"] - float(want))})
+            tt2, tts2, tg, tmem2 = peak_of(both_ways(fn, a, b), args.reps)
+            scale = float(max(tg[0].abs().max(), tg[1].abs().max()))
+            g = grads[ours]
+            rec.update({f"{key}_forward_backward_ms": round(tt2, 3), f"{key}_forward_backward_runs_ms": tts2,
+                        f"{key}_forward_backward_max_memory_allocated": tmem2,
+                        f"{key}_forward_backward_over_call": round(tt2 / rec[f"{ours}_forward_backward_ms"], 3),
+                        f"{key}_gradient_diff_over_largest": float(max((g[0] - tg[0]).abs().max(), (g[1] - tg[1]).abs().max())) / scale})
+            del tg
+            torch.cuda.empty_cache()
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if fh is not None:
+        fh.write(line + "\n")
+        fh.flush()
+    del a, b, grads
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pair", action="store_true", help="the symmetric loss: ops.info_nce_pair against the two ops.info_nce calls and torch's two directions")
+    ap.add_argument("--intraview", nargs="?", const="masked", default=None, choices=["masked", "all"],
+                    help="the plain and the intraview calls, one-way and pair, in one run (the variant: masked by default)")
     ap.add_argument("--shapes", default="cora,physics,arxiv")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-torch", action="store_true", help="time the calls alone")
@@ -206,7 +291,7 @@ def main():
     fh = open(args.out, "a") if args.out else None
     for name in args.shapes.split(","):
         n, f = SHAPES[name]
-        (run_pair if args.pair else run)(name, n, f, args, fh)
+        (run_intraview if args.intraview else run_pair if args.pair else run)(name, n, f, args, fh)
 
 
 if __name__ == "__main__":
