@@ -915,6 +915,52 @@ int rlap_probe_scores(rlap_handle h, const float* d_x, int64_t N, int64_t F, int
                       const int64_t* d_index, const int64_t* h_ptr, const float* d_weight, const float* d_bias, int64_t* d_pred,
                       int64_t* d_confusion, double* d_scores, int32_t* d_status, rlap_probe_info* h_info);
 
+/* Per-view batch norm with fused activations, forward and backward: every layer l of d_x (L, N, F) is normalised over
+ * its N rows with its own column statistics -- one BatchNorm1d call a view, as the reference's encoders make it -- with an optional
+ * ReLU in front and a ReLU or PReLU behind in the same pass, and the running buffers updated once a layer, the layers in order.
+ *   d_x, L, N, F   : (L, N, F) float32 row-major; L >= 1, 1 <= F <= 4096, N >= 2 in training mode (N >= 1 with RLAP_NORM_EVAL)
+ *   d_weight, d_bias : (nullable) (F) float32; a null pointer means 1 and 0
+ *   d_slope        : the PReLU slope, one float32 or (RLAP_NORM_SLOPE_PER_CHANNEL) (F); required with RLAP_NORM_POST_PRELU
+ *   d_running_mean, d_running_var : (F) float32.  Training: nullable, updated on the device, rm = (float)((1 - momentum) rm +
+ *                    momentum mean), rv the same with the unbiased variance, layer 0 first.  RLAP_NORM_EVAL: required, only read.
+ *   momentum, eps  : momentum in [0, 1]; eps > 0 and finite
+ *   flags          : RLAP_NORM_PRE_RELU; one of RLAP_NORM_POST_RELU / RLAP_NORM_POST_PRELU; RLAP_NORM_SLOPE_PER_CHANNEL; RLAP_NORM_EVAL
+ *   d_y            : (L, N, F) float32; every element is written
+ *   d_stat         : (L, 3, F) float64: the shift c (the layer's first row behind the front activation), m (mean = c + m) and
+ *                    1 / sqrt(var + eps).  Written by a training call, read by its backward call; unused with RLAP_NORM_EVAL (nullable)
+ *   h_info         : (nullable) what the call did
+ * Every value and the order of every sum are defined in rlap_amd/csrc/rlap_norm.h: float64 throughout, the column sums by the
+ * chunk rule of rlap_spmm.h over the rows in order, every output rounded once to float32.  So the same input gives the same bits,
+ * and a layer's result does not depend on L, on the other layers or on what d_y or the arena held.  A column of zero variance
+ * gives 1 / sqrt(eps), no NaN.  No atomic touches a floating-point value; neither call synchronises with the host.
+ * The backward call reads d_x, the upstream d_gy (L, N, F) and the forward call's d_stat (training), and writes d_gx (L, N, F),
+ * d_gweight (F), d_gbias (F) and d_gslope (1, or F per channel): the parameter gradients are summed over the layers in layer
+ * order (the single slope then over the columns in order).  A null gradient output is skipped.
+ * Both post flags, PReLU without a slope, RLAP_NORM_EVAL without both running buffers, N < 2 in training mode, F outside [1, 4096],
+ * L < 1, eps or momentum out of range or not a number, a null d_x, d_y, d_gy or (training) d_stat, an unknown flag: RLAP_E_BAD_ARG
+ * before anything is launched.  L * N * F >= 2^40: RLAP_E_TOO_LARGE.  Scratch from the arena (RLAP_E_WORKSPACE when a
+ * caller-provided one is too small, the workspace-needed query saying how much). */
+enum { RLAP_NORM_PRE_RELU = 1, RLAP_NORM_POST_RELU = 2, RLAP_NORM_POST_PRELU = 4, RLAP_NORM_SLOPE_PER_CHANNEL = 8, RLAP_NORM_EVAL = 16 };
+typedef struct {
+    int64_t rows;             /* N                                                                    */
+    int64_t features;         /* F                                                                    */
+    int64_t layers;           /* L                                                                    */
+    int64_t chunks;           /* chunks of 256 rows a layer has                                       */
+    int64_t arena_bytes;      /* scratch bytes of the call                                            */
+    int32_t vec;              /* 1: 16 bytes a lane (F % 4 == 0, pointers on the 16-byte grid); 0: one element a lane */
+    int32_t launches;         /* kernels the call enqueued                                            */
+    int32_t host_syncs;       /* host synchronisations of the call: 0                                 */
+    int32_t pad;
+} rlap_norm_info;
+
+int rlap_batch_norm(rlap_handle h, const float* d_x, int64_t L, int64_t N, int64_t F, const float* d_weight, const float* d_bias,
+                    const float* d_slope, float* d_running_mean, float* d_running_var, double momentum, double eps, int flags,
+                    float* d_y, double* d_stat, rlap_norm_info* h_info);
+int rlap_batch_norm_backward(rlap_handle h, const float* d_x, const float* d_gy, int64_t L, int64_t N, int64_t F, const float* d_weight,
+                    const float* d_bias, const float* d_slope, const float* d_running_mean, const float* d_running_var, double eps,
+                    int flags, const double* d_stat, float* d_gx, float* d_gweight, float* d_gbias, float* d_gslope,
+                    rlap_norm_info* h_info);
+
 /* The op with the step BEFORE the path fused in (scripts/node_shared.py:326-327,
  * scripts/augmentor_benchmarks.py:77-78):
  *   symmetrize != 0 : the input holds every undirected edge in one or both directions; (b,a) is

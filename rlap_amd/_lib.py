@@ -25,7 +25,7 @@ EXPORTS = [
     "rlap_graph_readout", "rlap_graph_readout_backward", "rlap_infonce", "rlap_infonce_backward",
     "rlap_infonce_pair", "rlap_infonce_pair_backward",
     "rlap_infonce_intra", "rlap_infonce_intra_backward", "rlap_infonce_pair_intra", "rlap_infonce_pair_intra_backward",
-    "rlap_cca_loss", "rlap_cca_loss_backward",
+    "rlap_cca_loss", "rlap_cca_loss_backward", "rlap_batch_norm", "rlap_batch_norm_backward",
     "rlap_g2l_jsd", "rlap_g2l_jsd_backward", "rlap_g2l_bootstrap", "rlap_g2l_bootstrap_backward",
     "rlap_linear_probe", "rlap_probe_scores", "rlap_edge_drop", "rlap_node_sample", "rlap_edge_add", "rlap_snapshot_markov",
 ]
@@ -65,6 +65,9 @@ READOUT_MEAN, READOUT_X_F32 = 1, 32
 INFONCE_POSITIVE_RAW = 1
 # the intraview argument of rlap_infonce_intra and its kin
 INFONCE_INTRA_MASKED, INFONCE_INTRA_ALL = 1, 2
+# rlap_batch_norm flags and limits (rlap_amd/csrc/rlap_norm.h)
+NORM_PRE_RELU, NORM_POST_RELU, NORM_POST_PRELU, NORM_SLOPE_PER_CHANNEL, NORM_EVAL = 1, 2, 4, 8, 16
+NORM_MAX_F = 4096
 # rlap_linear_probe select
 PROBE_SELECT_SCRIPTS, PROBE_SELECT_CCA = 0, 1
 
@@ -202,6 +205,15 @@ class CcaInfo(_Report):
     ]
 
 
+class NormInfo(_Report):
+    """rlap_norm_info (include/rlap_hip.h)."""
+    _fields_ = [
+        ("rows", ctypes.c_int64), ("features", ctypes.c_int64), ("layers", ctypes.c_int64), ("chunks", ctypes.c_int64),
+        ("arena_bytes", ctypes.c_int64), ("vec", ctypes.c_int32), ("launches", ctypes.c_int32), ("host_syncs", ctypes.c_int32),
+        ("pad", ctypes.c_int32),
+    ]
+
+
 class G2lInfo(_Report):
     """rlap_g2l_info (include/rlap_hip.h)."""
     _fields_ = [
@@ -327,6 +339,12 @@ def load():
     lib.rlap_cca_loss.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ci, vp, vp, vp, ctypes.POINTER(CcaInfo)]
     lib.rlap_cca_loss_backward.restype = ci
     lib.rlap_cca_loss_backward.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ci, vp, vp, vp, vp, vp, ctypes.POINTER(CcaInfo)]
+    lib.rlap_batch_norm.restype = ci
+    lib.rlap_batch_norm.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, ctypes.c_double, ctypes.c_double, ci, vp, vp,
+                                    ctypes.POINTER(NormInfo)]
+    lib.rlap_batch_norm_backward.restype = ci
+    lib.rlap_batch_norm_backward.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, ctypes.c_double, ci, vp, vp, vp, vp, vp,
+                                             ctypes.POINTER(NormInfo)]
     lib.rlap_g2l_jsd.restype = ci
     lib.rlap_g2l_jsd.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, ci, vp, vp, ctypes.POINTER(G2lInfo)]
     lib.rlap_g2l_jsd_backward.restype = ci

@@ -22,6 +22,9 @@ Mirrors of the reference's L2 adapters that keep everything on the GPU:
                   mode="L2L")) on the embeddings of two views, fused on the device (ops.info_nce)
   * `CCAContrast` -- the loss of CCA-SSG/main.py on the embeddings of two views, fused on the device (ops.cca_loss);
                   `drop_feature` -- CCA-SSG/aug.py's feature masking (also A.FeatureMasking), one mask per view
+  * `SnapshotBatchNorm` -- BatchNorm1d for all views of a call at once, each view with its own statistics, the activations around
+                  it fused in (ops.batch_norm); `SnapshotGINEncoder` -- scripts/graph_shared.py's GConv on a `Snapshots`: GIN layer,
+                  relu + norm, readout, per layer
   * `rLapChain` -- the chain of scripts/rlap_vc_spectral.py: eliminate, relabel the survivors 0..k-1, eliminate again
   * `EdgeDropping`, `EdgeDroppingDegree`, `EdgeDroppingPR`, `EdgeDroppingEVC` -- the comparison arms of
                   scripts/augmentor_benchmarks.py:216-363 on the device (ops.drop_edges); `EdgeDroppingViews` -- K of them from one call
@@ -221,6 +224,107 @@ class SnapshotGINConv(torch.nn.Module):
 
     def forward(self, x, snapshots):
         return self.nn((1 + self.eps).to(x.dtype) * x + snapshots.aggregate(x))
+
+
+class SnapshotBatchNorm(torch.nn.Module):
+    """BatchNorm1d for all views of a call at once: forward(x) = ops.batch_norm on an (L, N, F) tensor (or one (N, F) view), every
+    layer normalised with its own batch statistics and the running buffers updated once a layer, the layers in order.  That one
+    view per layer and view-ordered buffer updates is the reference's behaviour: scripts/graph_shared.py and
+    scripts/graph_shared_g2l.py run their encoders once per view, so torch.nn.BatchNorm1d sees one view a call; on an (L, N, F)
+    tensor it would take dim 1 for the channels, and on the (L * N, F) reshape it would mix the views' statistics.  `pre="relu"`
+    fuses the F.relu in front (GConv: conv -> relu -> bn), `post="relu"` / `"prelu"` the activation behind (the projection head and
+    the predictor: Linear -> BatchNorm1d -> PReLU); with `"prelu"` the module carries the slope as the parameter `slope`
+    (`slope_init`, one value or `slope_per_channel`).  It restates torch.nn.BatchNorm1d's published semantics -- parameter and
+    buffer names `weight`, `bias`, `running_mean`, `running_var`, `num_batches_tracked`, so a state dict moves across; ones and
+    zeros at reset; `.train()` / `.eval()`; without `track_running_stats` batch statistics in both modes -- except
+    `momentum=None`, the cumulative average, which is refused.  `num_batches_tracked` grows by L a call (host arithmetic)."""
+
+    def __init__(self, num_features: int, eps: float = 1e-5, momentum: float = 0.1, affine: bool = True, track_running_stats: bool = True,
+                 pre: str = "none", post: str = "none", slope_init: float = 0.25, slope_per_channel: bool = False):
+        super().__init__()
+        if momentum is None:
+            raise ValueError("momentum: a number in [0, 1]; the cumulative average (momentum=None) is not provided")
+        if pre not in ops.NORM_PRE or post not in ops.NORM_POST:
+            raise ValueError(f"pre: one of {sorted(ops.NORM_PRE)}; post: one of {sorted(ops.NORM_POST)}")
+        self.num_features, self.eps, self.momentum = int(num_features), eps, momentum
+        self.affine, self.track_running_stats, self.pre, self.post = bool(affine), bool(track_running_stats), pre, post
+        self.slope_init = float(slope_init)
+        if self.affine:
+            self.weight = torch.nn.Parameter(torch.empty(self.num_features))
+            self.bias = torch.nn.Parameter(torch.empty(self.num_features))
+        else:
+            self.register_parameter("weight", None)
+            self.register_parameter("bias", None)
+        if self.track_running_stats:
+            self.register_buffer("running_mean", torch.zeros(self.num_features))
+            self.register_buffer("running_var", torch.ones(self.num_features))
+            self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
+        else:
+            self.register_buffer("running_mean", None)
+            self.register_buffer("running_var", None)
+            self.register_buffer("num_batches_tracked", None)
+        if post == "prelu":
+            self.slope = torch.nn.Parameter(torch.empty(self.num_features if slope_per_channel else 1))
+        else:
+            self.register_parameter("slope", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        with torch.no_grad():
+            if self.track_running_stats:
+                self.running_mean.zero_()
+                self.running_var.fill_(1.0)
+                self.num_batches_tracked.zero_()
+            if self.affine:
+                self.weight.fill_(1.0)
+                self.bias.zero_()
+            if self.slope is not None:
+                self.slope.fill_(self.slope_init)
+
+    def forward(self, x):
+        if not isinstance(x, torch.Tensor) or x.dim() not in (2, 3) or int(x.shape[-1]) != self.num_features:
+            raise ValueError(f"SnapshotBatchNorm: an (N, {self.num_features}) or (L, N, {self.num_features}) tensor")
+        batch_stats = self.training or not self.track_running_stats
+        update = self.training and self.track_running_stats
+        y = ops.batch_norm(x, self.weight, self.bias, self.running_mean if (update or not batch_stats) else None,
+                           self.running_var if (update or not batch_stats) else None, training=batch_stats, momentum=self.momentum,
+                           eps=self.eps, pre=self.pre, post=self.post, slope=self.slope)
+        if update:
+            self.num_batches_tracked += 1 if x.dim() == 2 else int(x.shape[0])
+        return y
+
+    def extra_repr(self):
+        return (f"{self.num_features}, eps={self.eps}, momentum={self.momentum}, affine={self.affine}, "
+                f"track_running_stats={self.track_running_stats}, pre={self.pre!r}, post={self.post!r}")
+
+
+class SnapshotGINEncoder(torch.nn.Module):
+    """scripts/graph_shared.py's GConv for all views of a call at once: per layer SnapshotGINConv(Linear-ReLU-Linear), then the
+    fused SnapshotBatchNorm(hidden_dim, pre="relu") -- conv -> F.relu -> BatchNorm1d, every view with its own statistics --, then
+    the readout of the layer's output.  forward(x, snapshots) takes x (n, input_dim), shared by the views, or (L, n, input_dim), and
+    a `Snapshots` or its `.plan()` (anything with `.aggregate(x)` and `.readout(z)`); it returns the node embeddings
+    (L, n, hidden_dim * num_layers) and the graph embeddings (L, G, hidden_dim * num_layers), the layers' outputs side by side as
+    GConv concatenates them.  So the graph-level step is one (L, n, F) pipeline from the features to both embeddings, without a
+    Python loop over the views.  (GConv's `project` head belongs to the contrast model around it and is not part of this.)"""
+
+    def __init__(self, input_dim: int, hidden_dim: int, num_layers: int):
+        super().__init__()
+        if num_layers < 1:
+            raise ValueError("num_layers: at least one")
+        self.layers = torch.nn.ModuleList()
+        self.batch_norms = torch.nn.ModuleList()
+        for i in range(num_layers):
+            d = input_dim if i == 0 else hidden_dim
+            self.layers.append(SnapshotGINConv(torch.nn.Sequential(torch.nn.Linear(d, hidden_dim), torch.nn.ReLU(), torch.nn.Linear(hidden_dim, hidden_dim))))
+            self.batch_norms.append(SnapshotBatchNorm(hidden_dim, pre="relu"))
+
+    def forward(self, x, snapshots):
+        z, zs = x, []
+        for conv, bn in zip(self.layers, self.batch_norms):
+            z = bn(conv(z, snapshots))
+            zs.append(z)
+        gs = [snapshots.readout(z) for z in zs]
+        return torch.cat(zs, dim=-1), torch.cat(gs, dim=-1)
 
 
 class NodeContrast(torch.nn.Module):

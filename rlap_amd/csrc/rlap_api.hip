@@ -39,6 +39,8 @@
 #include "rlap_g2l_api.h"
 #include "rlap_cca.h"
 #include "rlap_cca_api.h"
+#include "rlap_norm.h"
+#include "rlap_norm_api.h"
 #include "rlap_probe.h"
 #include "rlap_probe_api.h"
 
@@ -2020,6 +2022,68 @@ int rlap_probe_scores(rlap_handle h, const float* d_x, int64_t N, int64_t F, int
         int64_t launches = 0;
         const int rc = scores_run(h->stream, base, have, a, &launches);
         if (h_info) { h_info->parts = 1; h_info->launches = launches; }
+        return rc;
+    });
+}
+
+namespace {
+
+// what both norm exports check (their own pointers come behind this), and what the host knows of the call
+int norm_check(rlap_handle h, const float* d_x, int64_t L, int64_t N, int64_t F, const float* d_slope, const float* d_rm, const float* d_rv,
+               double momentum, double eps, int flags, const double* d_stat, rlap_norm_info* h_info) {
+    if (h_info) *h_info = rlap_norm_info{};
+    if (!h || !d_x || !norm::args_ok(L, N, F, flags, d_slope != nullptr, d_rm && d_rv, eps, momentum)) return RLAP_E_BAD_ARG;
+    if (!(flags & RLAP_NORM_EVAL) && !d_stat) return RLAP_E_BAD_ARG;
+    if (L >= SPMM_MAX_ELEMS || N >= SPMM_MAX_ELEMS || L * N >= SPMM_MAX_ELEMS || L * N * F >= SPMM_MAX_ELEMS) return RLAP_E_TOO_LARGE;
+    if (h_info) { h_info->rows = N; h_info->features = F; h_info->layers = L; h_info->chunks = spmm::num_chunks(N); }
+    return RLAP_OK;
+}
+
+void norm_report(rlap_norm_info* h_info, const NormReport& rep) {
+    if (h_info) { h_info->vec = rep.vec; h_info->launches = rep.launches; h_info->chunks = rep.chunks; }
+}
+
+}  // namespace
+
+int rlap_batch_norm(rlap_handle h, const float* d_x, int64_t L, int64_t N, int64_t F, const float* d_weight, const float* d_bias,
+                    const float* d_slope, float* d_running_mean, float* d_running_var, double momentum, double eps, int flags,
+                    float* d_y, double* d_stat, rlap_norm_info* h_info) {
+    if (const int rc = norm_check(h, d_x, L, N, F, d_slope, d_running_mean, d_running_var, momentum, eps, flags, d_stat, h_info)) return rc;
+    if (!d_y) return RLAP_E_BAD_ARG;
+    const bool eval = (flags & RLAP_NORM_EVAL) != 0;
+    NormArgs a{};
+    a.x = d_x; a.L = L; a.N = N; a.F = F; a.weight = d_weight; a.bias = d_bias; a.slope = d_slope;
+    a.running_mean = d_running_mean; a.running_var = d_running_var;
+    a.upd_mean = eval ? nullptr : d_running_mean; a.upd_var = eval ? nullptr : d_running_var;
+    a.momentum = momentum; a.eps = eps; a.flags = flags; a.out = d_y; a.stat = d_stat;
+    // (the running buffers of a training call are inputs as well: not poisoned)
+    return poisoned_call(h, [&] { return norm_bytes(a, false); }, {{d_y, (size_t)(L * N * F) * 4}, {eval ? nullptr : d_stat, (size_t)(L * 3 * F) * 8}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) {
+        NormReport rep{};
+        const int rc = norm_run(h->stream, base, have, a, &rep);
+        if (rc == RLAP_OK) norm_report(h_info, rep);
+        return rc;
+    });
+}
+
+int rlap_batch_norm_backward(rlap_handle h, const float* d_x, const float* d_gy, int64_t L, int64_t N, int64_t F, const float* d_weight,
+                    const float* d_bias, const float* d_slope, const float* d_running_mean, const float* d_running_var, double eps,
+                    int flags, const double* d_stat, float* d_gx, float* d_gweight, float* d_gbias, float* d_gslope,
+                    rlap_norm_info* h_info) {
+    if (const int rc = norm_check(h, d_x, L, N, F, d_slope, d_running_mean, d_running_var, 0.0, eps, flags, d_stat, h_info)) return rc;
+    if (!d_gy) return RLAP_E_BAD_ARG;
+    NormArgs a{};
+    a.x = d_x; a.gy = d_gy; a.L = L; a.N = N; a.F = F; a.weight = d_weight; a.bias = d_bias; a.slope = d_slope;
+    a.running_mean = d_running_mean; a.running_var = d_running_var; a.eps = eps; a.flags = flags; a.out = d_gx;
+    a.stat = const_cast<double*>(d_stat);
+    a.gweight = d_gweight; a.gbias = d_gbias; a.gslope = (flags & RLAP_NORM_POST_PRELU) ? d_gslope : nullptr;
+    const size_t slope_bytes = (size_t)((flags & RLAP_NORM_SLOPE_PER_CHANNEL) ? F : 1) * 4;
+    return poisoned_call(h, [&] { return norm_bytes(a, true); },
+                         {{d_gx, (size_t)(L * N * F) * 4}, {d_gweight, (size_t)F * 4}, {d_gbias, (size_t)F * 4}, {a.gslope, slope_bytes}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) {
+        NormReport rep{};
+        const int rc = norm_backward_run(h->stream, base, have, a, &rep);
+        if (rc == RLAP_OK) norm_report(h_info, rep);
         return rc;
     });
 }

@@ -1626,6 +1626,174 @@ def cca_loss(h1: Tensor, h2: Tensor, lambd: float = 1e-3, return_terms: bool = F
     return (loss, parts[0], parts[1], parts[2]) if return_terms else loss
 
 
+NORM_MAX_F = _lib.NORM_MAX_F
+NORM_PRE = {"none": 0, "relu": _lib.NORM_PRE_RELU}
+NORM_POST = {"none": 0, "relu": _lib.NORM_POST_RELU, "prelu": _lib.NORM_POST_PRELU}
+
+
+def _norm_vector(t, f: int, what: str, x: Tensor):
+    if t is None:
+        return
+    if not isinstance(t, Tensor) or t.dtype != torch.float32 or t.dim() != 1 or int(t.shape[0]) != f:
+        raise ValueError(f"{what}: a ({f},) torch.float32 tensor or None")
+    if t.device != x.device:
+        raise ValueError(f"{what}: on x's device {x.device}, got {t.device}")
+
+
+def _norm_args(x, weight, bias, running_mean, running_var, training, momentum, eps, pre, post, slope):
+    """Host-side checks of batch_norm, made before the device is touched: (flags, momentum, eps)."""
+    if not isinstance(x, Tensor) or x.dim() not in (2, 3):
+        raise ValueError("x: a (N, F) or (L, N, F) tensor")
+    if x.dtype != torch.float32:
+        raise ValueError(f"x: torch.float32, got {x.dtype}")
+    L, n, f = (1 if x.dim() == 2 else int(x.shape[0])), int(x.shape[-2]), int(x.shape[-1])
+    if not isinstance(training, bool):
+        raise ValueError(f"training: a bool, got {training!r}")
+    if L < 1:
+        raise ValueError("x: at least one layer")
+    if f < 1 or f > NORM_MAX_F:
+        raise ValueError(f"x: between 1 and {NORM_MAX_F} feature columns, got {f}")
+    if n < (2 if training else 1):
+        raise ValueError("x: at least two rows in training mode (one value per channel has no variance), one in evaluation mode")
+    if L * n * f >= 1 << 40:
+        raise ValueError("x: fewer than 2^40 elements")
+    for t, what in ((weight, "weight"), (bias, "bias"), (running_mean, "running_mean"), (running_var, "running_var")):
+        _norm_vector(t, f, what, x)
+    if not training and (running_mean is None or running_var is None):
+        raise ValueError("running_mean and running_var: both are needed in evaluation mode")
+    if momentum is None:
+        raise ValueError("momentum: a number in [0, 1]; the cumulative average (momentum=None) is not provided")
+    for v, what in ((momentum, "momentum"), (eps, "eps")):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"{what}: a number, got {v!r}")
+    momentum, eps = float(momentum), float(eps)
+    if not (0.0 <= momentum <= 1.0):
+        raise ValueError(f"momentum: in [0, 1], got {momentum!r}")
+    if not (0.0 < eps < float("inf")):
+        raise ValueError(f"eps: finite and > 0, got {eps!r}")
+    if not isinstance(pre, str) or pre not in NORM_PRE:
+        raise ValueError(f"pre: one of {sorted(NORM_PRE)}, got {pre!r}")
+    if not isinstance(post, str) or post not in NORM_POST:
+        raise ValueError(f"post: one of {sorted(NORM_POST)}, got {post!r}")
+    flags = NORM_PRE[pre] | NORM_POST[post] | (0 if training else _lib.NORM_EVAL)
+    if post == "prelu":
+        if not isinstance(slope, Tensor) or slope.dtype != torch.float32 or slope.dim() > 1 or slope.numel() not in (1, f):
+            raise ValueError(f'slope: with post="prelu" a torch.float32 tensor of one value or of ({f},)')
+        if slope.device != x.device:
+            raise ValueError(f"slope: on x's device {x.device}, got {slope.device}")
+        if slope.numel() == f and f > 1:
+            flags |= _lib.NORM_SLOPE_PER_CHANNEL
+    elif slope is not None:
+        raise ValueError('slope: only with post="prelu"')
+    return flags, momentum, eps
+
+
+def _norm_ptr(t: Optional[Tensor]):
+    return t.data_ptr() if t is not None else None
+
+
+def _norm_forward(x3: Tensor, weight, bias, slope, running_mean, running_var, momentum: float, eps: float, flags: int):
+    """The forward export on x3 (L, N, F): (y, stat (L, 3, F) float64 or None in evaluation mode, the device copies of x3, weight,
+    bias, slope, running_mean, running_var).  A training call updates the running buffers in place."""
+    dev = _device_for(x3)
+    with torch.cuda.device(dev):
+        put = lambda t: None if t is None else t.detach().to(device=dev).contiguous()
+        d_x, d_w, d_b, d_s, d_rm, d_rv = (put(t) for t in (x3, weight, bias, slope, running_mean, running_var))
+        L, n, f = (int(v) for v in d_x.shape)
+        y = torch.empty_like(d_x)
+        stat = None if flags & _lib.NORM_EVAL else torch.empty((L, 3, f), dtype=torch.float64, device=dev)
+        _device_call("rlap_batch_norm", _lib.NormInfo, dev, 1, (
+            d_x.data_ptr(), L, n, f, _norm_ptr(d_w), _norm_ptr(d_b), _norm_ptr(d_s), _norm_ptr(d_rm), _norm_ptr(d_rv), momentum, eps, flags,
+            y.data_ptr(), _norm_ptr(stat)))
+        if not flags & _lib.NORM_EVAL:
+            with torch.no_grad():
+                for buf, d_buf in ((running_mean, d_rm), (running_var, d_rv)):
+                    if buf is not None and d_buf.data_ptr() != buf.data_ptr():   # (a copy was updated: a strided or remote buffer)
+                        buf.copy_(d_buf)
+    return y, stat, (d_x, d_w, d_b, d_s, d_rm, d_rv)
+
+
+class _BatchNorm(torch.autograd.Function):
+    """y = the fused per-view batch norm of x3; the gradients with respect to x, weight, bias and slope come from the backward
+    export, which reads x and the forward's column constants `stat` and forms everything else again."""
+
+    @staticmethod
+    def forward(ctx, x3, weight, bias, slope, running_mean, running_var, momentum, eps, flags):
+        y, stat, (d_x, d_w, d_b, d_s, d_rm, d_rv) = _norm_forward(x3, weight, bias, slope, running_mean, running_var, momentum, eps, flags)
+        ev = bool(flags & _lib.NORM_EVAL)
+        ctx.save_for_backward(d_x, d_w, d_b, d_s, stat)
+        ctx.running = (d_rm, d_rv) if ev else (None, None)
+        ctx.call = (eps, flags, [None if t is None else (t.device, t.shape) for t in (x3, weight, bias, slope)])
+        if stat is None:
+            stat = torch.empty(0, dtype=torch.float64, device=y.device)
+        ctx.mark_non_differentiable(stat)
+        return y, stat
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy, _g_stat):
+        d_x, d_w, d_b, d_s, stat = ctx.saved_tensors
+        d_rm, d_rv = ctx.running
+        eps, flags, origin = ctx.call
+        dev = d_x.device
+        need = ctx.needs_input_grad
+        with torch.cuda.device(dev):
+            d_gy = gy.detach().to(device=dev, dtype=torch.float32).contiguous()
+            L, n, f = (int(v) for v in d_x.shape)
+            gx = torch.empty_like(d_x) if need[0] else None
+            gw = torch.empty(f, dtype=torch.float32, device=dev) if need[1] and d_w is not None else None
+            gb = torch.empty(f, dtype=torch.float32, device=dev) if need[2] and d_b is not None else None
+            gs = torch.empty(d_s.numel(), dtype=torch.float32, device=dev) if need[3] and d_s is not None else None
+            _device_call("rlap_batch_norm_backward", _lib.NormInfo, dev, 1, (
+                d_x.data_ptr(), d_gy.data_ptr(), L, n, f, _norm_ptr(d_w), _norm_ptr(d_b), _norm_ptr(d_s), _norm_ptr(d_rm), _norm_ptr(d_rv),
+                eps, flags, _norm_ptr(stat), _norm_ptr(gx), _norm_ptr(gw), _norm_ptr(gb), _norm_ptr(gs)))
+        back = lambda g, o: None if g is None else g.reshape(o[1]).to(o[0])
+        return (back(gx, origin[0]), back(gw, origin[1]), back(gb, origin[2]), back(gs, origin[3]), None, None, None, None, None)
+
+
+def batch_norm(x: Tensor, weight: Optional[Tensor] = None, bias: Optional[Tensor] = None, running_mean: Optional[Tensor] = None,
+               running_var: Optional[Tensor] = None, training: bool = True, momentum: float = 0.1, eps: float = 1e-5, pre: str = "none",
+               post: str = "none", slope: Optional[Tensor] = None, return_stats: bool = False):
+    """Batch norm of every view on its own, with the activations around it fused in (rlap_batch_norm):
+    y[l] = post(F.batch_norm(pre(x[l]), running_mean, running_var, weight, bias, training, momentum, eps)) for every layer l of an
+    (L, N, F) tensor in one call -- what the reference's encoders compute by running once per view: each view is normalised with
+    its own batch statistics, and the running buffers are updated once per view, in view order.
+
+      x            : (N, F) or (L, N, F) float32; 1 <= F <= 4096; N >= 2 in training mode
+      weight, bias : (F,) float32 or None (1 and 0)
+      running_mean, running_var : (F,) float32 or None; updated in place in training mode (rm = (1 - momentum) rm + momentum mean,
+                     rv the same with the unbiased variance, layer 0 first), read in evaluation mode, where both are needed
+      momentum     : in [0, 1]; None (torch's cumulative average) is not provided
+      pre          : "none" or "relu", applied to x in front of the norm
+      post         : "none", "relu" or "prelu", applied behind it; "prelu" takes `slope`, one float32 value or (F,) per channel
+      return_stats : also return (mean, var), float64 (L, F): every layer's batch mean and biased variance (var is recovered from
+                     the stored 1 / sqrt(var + eps)); in evaluation mode the running buffers
+    Returns y of x's shape.  Every value and the order of every sum are fixed (rlap_amd/csrc/rlap_norm.h: float64, the column sums
+    by the chunk rule, one rounding to float32): the same input gives the same bits, forward and backward, and layer l of a call
+    equals the (N, F) call on x[l] alone.  A column of zero variance gives 1 / sqrt(eps), no NaN.
+
+    Differentiable in x, weight, bias and slope (rlap_batch_norm_backward; nothing of x's size but x itself is kept for it); double
+    backward is not supported.  Malformed arguments raise ValueError before the device is touched.  No host synchronisation.
+    `last_stats` then holds what the call did (rlap_norm_info: rows, features, layers, chunks, arena_bytes, vec -- 1 when the rows
+    were read 16 bytes a lane --, launches, host_syncs).
+    """
+    flags, momentum, eps = _norm_args(x, weight, bias, running_mean, running_var, training, momentum, eps, pre, post, slope)
+    x3 = x if x.dim() == 3 else x.unsqueeze(0)
+    params = (x, weight, bias, slope)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in params):
+        y, stat = _BatchNorm.apply(x3, weight, bias, slope, running_mean, running_var, momentum, eps, flags)
+    else:
+        y, stat, _ = _norm_forward(x3, weight, bias, slope, running_mean, running_var, momentum, eps, flags)
+    y = y if x.dim() == 3 else y.squeeze(0)
+    if not return_stats:
+        return y
+    if training:
+        s = stat.detach()
+        return y, s[:, 0] + s[:, 1], (s[:, 2].reciprocal().square() - eps).clamp_min(0.0)
+    L = int(x3.shape[0])
+    return y, running_mean.detach().double().expand(L, -1).to(y.device), running_var.detach().double().expand(L, -1).to(y.device)
+
+
 G2L_MAX_F = 512
 
 
