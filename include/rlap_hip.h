@@ -519,6 +519,66 @@ int rlap_edge_plan_build(rlap_handle h, const double* d_sc, int64_t m, const int
                          int64_t G, int64_t num_nodes, int flags, double fill_value, void* d_plan, size_t plan_bytes,
                          rlap_plan_desc* h_desc, rlap_plan_info* h_info);
 
+/* The sparse first layer: feature plans with per-view column masks.  A dense row-major (N, Fin) feature matrix x --
+ * bag-of-words rows, the same in every step of a run -- is turned once into lists, and every step's (x * keep[k]) @ W for K views
+ * and dW = sum_k keep[k] * (x^T G[k]) run over them; the masked copies of x never exist.  The rules are
+ * rlap_amd/csrc/rlap_featlin.h's: an entry is kept iff (double)x[i][j] != 0.0 (-0.0 is dropped, NaN and infinities stay), its
+ * coefficient is that double; the forward list of row i holds its entries by ascending j, the transposed list of column j by
+ * ascending i; a forward value sums the list's chunks of 256 (cut by position in the full list) from 0.0 in list order, an entry
+ * whose column the view drops adding nothing, then the chunk sums in chunk order; a transposed value adds, for the views that keep
+ * the column in view order, the list's sum by rlap_spmm.h's rule; float64 sums, rounded once, no atomic on a float: the same bits
+ * on every run.  The plan is a device buffer that the CALLER owns plus the host descriptor below; per direction it holds an int64
+ * offset table, a directory of the chunks of the lists longer than 256 entries and 16-byte records {double coefficient, int32 id,
+ * int32 0}, every part 256-byte aligned.  It does not depend on d_x after the build.
+ *
+ *   rlap_feature_count      : the kept entries of d_x ((N, Fin) row-major; float32 with RLAP_FEAT_X_F32, else float64) to *h_nnz.
+ *                             One host synchronisation.
+ *   rlap_feature_plan_bytes : host arithmetic (no GPU needed): the bytes of a plan buffer for the directions `flags` asks for
+ *                             (RLAP_PLAN_FORWARD / RLAP_PLAN_TRANSPOSED; with neither, both).  A negative count, N < 1 or Fin < 1:
+ *                             RLAP_E_BAD_ARG; N or Fin >= 2^31 or nnz >= 2^31 - 1: RLAP_E_TOO_LARGE.
+ *   rlap_feature_plan_build : builds the directions asked for into d_plan (256-byte aligned, at least the size query's bytes).
+ *                             Forward by a count per row, a scan and a ranked fill, transposed by counts per (column, block of
+ *                             rows), a scan and a fill in row order: deterministic, no atomic on the lists.  Scratch from the arena
+ *                             (RLAP_E_WORKSPACE when a caller-provided one is too small).  One host synchronisation, which reads
+ *                             back the recount: a count that differs from nnz gives RLAP_E_BAD_ARG.  h_desc is zeroed on every
+ *                             refusal.  h_info (nullable): nnz, the longest list, the long lists and their chunks per direction
+ *                             (-1: not built).
+ *   rlap_feature_plan_apply : forward: d_w is W (Fin, Fout), d_out is y (K, N, Fout).  With RLAP_SPMM_TRANSPOSE: d_w is G
+ *                             (K, N, Fout), d_out is dW (Fin, Fout).  RLAP_SPMM_X_F32: float32 operands and result, else float64.
+ *                             d_keep is uint8 (K, Fin), non-zero = kept, or NULL (K must be 1; everything is kept).  K in 1..32,
+ *                             Fout >= 1.  No host synchronisation.  A direction the plan lacks, a descriptor that is not a
+ *                             successful build's, a bad K or flag: RLAP_E_BAD_ARG before any launch; Fout or the elements of an
+ *                             operand beyond the limits of rlap_snapshot_propagate: RLAP_E_TOO_LARGE.  Arena: the columns' keep
+ *                             words and (transposed) the chunk sums, by the budget rule and test hook of
+ *                             rlap_snapshot_propagate.  The kernels clamp every id and offset they read from the buffer: an
+ *                             altered buffer gives wrong numbers, never an access out of range. */
+enum { RLAP_FEAT_X_F32 = 1 };
+typedef struct {
+    int64_t num_nodes, in_features, nnz;                  /* the build's N, Fin and kept entries                  */
+    int64_t chunks_forward, chunks_transposed;            /* chunks of the lists longer than one chunk (-1: not built) */
+    int64_t off_forward, dir_forward, rec_forward;        /* byte offsets of the parts within the buffer (-1)     */
+    int64_t off_transposed, dir_transposed, rec_transposed;
+    int64_t plan_bytes;                                   /* bytes of the buffer                                  */
+    int32_t flags;                                        /* RLAP_FEAT_X_F32 and both direction bits, resolved    */
+    int32_t magic;                                        /* marks a successful build                             */
+} rlap_feature_desc;
+typedef struct {
+    int64_t nnz;                                          /* kept entries                                         */
+    int64_t longest_forward, longest_transposed;          /* entries of the longest list (-1: not built)          */
+    int64_t long_lists_forward, long_lists_transposed;    /* lists longer than one chunk                          */
+    int64_t chunks_forward, chunks_transposed;            /* their chunks                                         */
+    int64_t arena_bytes;                                  /* scratch bytes of the call                            */
+    int32_t host_syncs;                                   /* host synchronisations of the call                    */
+    int32_t pad;
+} rlap_feature_info;
+
+int rlap_feature_count(rlap_handle h, const void* d_x, int64_t N, int64_t Fin, int flags, int64_t* h_nnz);
+int rlap_feature_plan_bytes(int64_t N, int64_t Fin, int64_t nnz, int flags, size_t* bytes);
+int rlap_feature_plan_build(rlap_handle h, const void* d_x, int64_t N, int64_t Fin, int64_t nnz, int flags, void* d_plan, size_t plan_bytes,
+                            rlap_feature_desc* h_desc, rlap_feature_info* h_info);
+int rlap_feature_plan_apply(rlap_handle h, const void* d_plan, const rlap_feature_desc* h_desc, int flags, const void* d_w,
+                            const uint8_t* d_keep, int64_t K, int64_t Fout, void* d_out, rlap_feature_info* h_info);
+
 /* Centrality-adaptive edge dropping, K views a call: the uniform, degree, PageRank and eigenvector edge-dropping
  * augmentors of GCA as the training scripts use them, on the device.  The centrality is found once and serves every view; row e is
  * kept in view k iff u(k, e) >= q(k, e), a counter-based coin against the drop probability.  Every rule -- counts, centralities,

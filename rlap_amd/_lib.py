@@ -28,6 +28,7 @@ EXPORTS = [
     "rlap_cca_loss", "rlap_cca_loss_backward", "rlap_batch_norm", "rlap_batch_norm_backward",
     "rlap_g2l_jsd", "rlap_g2l_jsd_backward", "rlap_g2l_bootstrap", "rlap_g2l_bootstrap_backward",
     "rlap_linear_probe", "rlap_probe_scores", "rlap_edge_drop", "rlap_node_sample", "rlap_edge_add", "rlap_snapshot_markov",
+    "rlap_feature_count", "rlap_feature_plan_bytes", "rlap_feature_plan_build", "rlap_feature_plan_apply",
 ]
 
 E_INDEX_RANGE = 2   # RLAP_E_INDEX_RANGE
@@ -48,6 +49,10 @@ SPMM_TRANSPOSE, SPMM_X_F32, SPMM_X_PER_LAYER = 16, 32, 64
 # rlap_snapshot_plan_build flags (beside the first three of rlap_snapshot_gcn_norm): the directions to build
 PLAN_FORWARD, PLAN_TRANSPOSED = 256, 512
 PLAN_MAGIC = 0x504C414E   # rlap_plan_desc.magic of a successful build
+# rlap_feature_plan_build flags (beside the two directions above) and limits (rlap_amd/csrc/rlap_featlin.h)
+FEAT_X_F32 = 1
+FEAT_MAGIC = 0x46454154   # rlap_feature_desc.magic of a successful build
+FEAT_MAX_VIEWS = 32
 # rlap_edge_drop schemes and flags
 DROP_SCHEMES = {"uniform": 0, "degree": 1, "pagerank": 2, "eigenvector": 3}
 DROP_SOURCE = 1
@@ -169,6 +174,27 @@ class PlanInfo(_Report):
     _fields_ = [
         ("entries", ctypes.c_int64), ("blocks", ctypes.c_int64), ("chunked_lists_forward", ctypes.c_int64),
         ("chunked_lists_transposed", ctypes.c_int64), ("loops_removed", ctypes.c_int64), ("arena_bytes", ctypes.c_int64),
+        ("host_syncs", ctypes.c_int32), ("pad", ctypes.c_int32),
+    ]
+
+
+class FeatureDesc(_Report):
+    """rlap_feature_desc (include/rlap_hip.h)."""
+    _fields_ = [
+        ("num_nodes", ctypes.c_int64), ("in_features", ctypes.c_int64), ("nnz", ctypes.c_int64),
+        ("chunks_forward", ctypes.c_int64), ("chunks_transposed", ctypes.c_int64),
+        ("off_forward", ctypes.c_int64), ("dir_forward", ctypes.c_int64), ("rec_forward", ctypes.c_int64),
+        ("off_transposed", ctypes.c_int64), ("dir_transposed", ctypes.c_int64), ("rec_transposed", ctypes.c_int64),
+        ("plan_bytes", ctypes.c_int64), ("flags", ctypes.c_int32), ("magic", ctypes.c_int32),
+    ]
+
+
+class FeatureInfo(_Report):
+    """rlap_feature_info (include/rlap_hip.h)."""
+    _fields_ = [
+        ("nnz", ctypes.c_int64), ("longest_forward", ctypes.c_int64), ("longest_transposed", ctypes.c_int64),
+        ("long_lists_forward", ctypes.c_int64), ("long_lists_transposed", ctypes.c_int64),
+        ("chunks_forward", ctypes.c_int64), ("chunks_transposed", ctypes.c_int64), ("arena_bytes", ctypes.c_int64),
         ("host_syncs", ctypes.c_int32), ("pad", ctypes.c_int32),
     ]
 
@@ -318,6 +344,15 @@ def load():
     lib.rlap_edge_plan_build.argtypes = lib.rlap_snapshot_plan_build.argtypes
     lib.rlap_snapshot_plan_propagate.restype = ci
     lib.rlap_snapshot_plan_propagate.argtypes = [vp, vp, ctypes.POINTER(PlanDesc), ci, vp, i64, vp, ctypes.POINTER(SpmmInfo)]
+    lib.rlap_feature_count.restype = ci
+    lib.rlap_feature_count.argtypes = [vp, vp, i64, i64, ci, ctypes.POINTER(i64)]
+    lib.rlap_feature_plan_bytes.restype = ci
+    lib.rlap_feature_plan_bytes.argtypes = [i64, i64, i64, ci, ctypes.POINTER(ctypes.c_size_t)]
+    lib.rlap_feature_plan_build.restype = ci
+    lib.rlap_feature_plan_build.argtypes = [vp, vp, i64, i64, i64, ci, vp, ctypes.c_size_t, ctypes.POINTER(FeatureDesc),
+                                            ctypes.POINTER(FeatureInfo)]
+    lib.rlap_feature_plan_apply.restype = ci
+    lib.rlap_feature_plan_apply.argtypes = [vp, vp, ctypes.POINTER(FeatureDesc), ci, vp, vp, i64, i64, vp, ctypes.POINTER(FeatureInfo)]
     lib.rlap_graph_readout.restype = ci
     lib.rlap_graph_readout.argtypes = [vp, vp, i64, i64, i64, vp, i64, ci, vp, ctypes.POINTER(ReadoutInfo)]
     lib.rlap_graph_readout_backward.restype = ci

@@ -176,7 +176,11 @@ class SnapshotGCNConv(torch.nn.Module):
     (L, n, F) result serves, so forward(x, plan) with an ops.SnapshotPlan -- graph_plan(g) for the input graph itself,
     rLapDepths.diffuse_plan(g) for its PPR diffusions -- works as it does with a holder.  Glorot-uniform W and zero b, as PyG's GCNConv initialises them.  (Unpinned: PyG is not installed
     here; this restates its published semantics -- linear without bias, propagate with gcn_norm's coefficients, then the bias --
-    not a run of it: DESIGN 4.10 and section 7.)"""
+    not a run of it: DESIGN 4.10 and section 7.)
+
+    The first layer also takes an ops.FeaturePlan as x: forward(fp, snapshots, keep) = snapshots.propagate(fp.linear(W, keep)) + b,
+    with `keep` None (every layer reads x @ W) or the (K, in_channels) masks of ops.feature_masks, one view per layer
+    (DESIGN 4.26); gradients then reach W and b."""
 
     def __init__(self, in_channels: int, out_channels: int, bias: bool = True):
         super().__init__()
@@ -190,8 +194,13 @@ class SnapshotGCNConv(torch.nn.Module):
         if self.bias is not None:
             torch.nn.init.zeros_(self.bias)
 
-    def forward(self, x, snapshots: Snapshots):
-        y = snapshots.propagate(x @ self.weight)
+    def forward(self, x, snapshots: Snapshots, keep=None):
+        if isinstance(x, ops.FeaturePlan):   # the sparse first layer: every view's (x * keep[k]) @ W from the plan's lists
+            y = snapshots.propagate(x.linear(self.weight, keep))
+        elif keep is not None:
+            raise ValueError("SnapshotGCNConv: keep goes with an ops.FeaturePlan as x (mask a tensor x with drop_feature)")
+        else:
+            y = snapshots.propagate(x @ self.weight)
         return y if self.bias is None else y + self.bias
 
 
@@ -434,7 +443,8 @@ def corrupt(x, generator=None):
 def drop_feature(x, p: float, views: int = 1, generator=None):
     """CCA-SSG/aug.py's drop_feature (A.FeatureMasking of the PyGCL scripts) for `views` views at once: per view, F uniforms are
     drawn (from `generator`, on x's device) and the columns with u < p are set to zero.  x is (N, F); returns (views, N, F), which
-    SnapshotGCNConv takes as its per-view x.  Plain torch."""
+    SnapshotGCNConv takes as its per-view x.  Plain torch.  For features that stay the same over a run, ops.feature_plan(x) with the
+    masks of ops.feature_masks gives the same products without the `views` dense copies."""
     if not isinstance(x, torch.Tensor) or x.dim() != 2:
         raise ValueError("drop_feature: x is a (N, F) tensor")
     if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= float(p) <= 1.0:

@@ -26,6 +26,7 @@
 #include "rlap_gcn.h"
 #include "rlap_plan.h"
 #include "rlap_edgeplan.h"
+#include "rlap_featlin_api.h"
 #include "rlap_edgedrop.h"
 #include "rlap_nodesample.h"
 #include "rlap_edgeadd.h"
@@ -1715,6 +1716,89 @@ int rlap_snapshot_plan_propagate(rlap_handle h, const void* d_plan, const rlap_p
         if (h_info) {
             h_info->entries = (t ? d.entries_transposed : d.entries_forward) + ((d.flags & RLAP_GCN_SELF_LOOPS) ? slots : 0);
             h_info->chunked_lists = 0; h_info->blocks = 0;
+            h_info->arena_bytes = (int64_t)need; h_info->host_syncs = 0;
+        }
+        return rc;
+    });
+}
+
+int rlap_feature_count(rlap_handle h, const void* d_x, int64_t N, int64_t Fin, int flags, int64_t* h_nnz) {
+    if (!h || !d_x || !h_nnz || N < 1 || Fin < 1 || (flags & ~RLAP_FEAT_X_F32)) return RLAP_E_BAD_ARG;
+    *h_nnz = 0;
+    if (N >= featlin::MAX_DIM || Fin >= featlin::MAX_DIM) return RLAP_E_TOO_LARGE;
+    return snapshot_call(h, [&] { return feature_count_bytes(N, Fin); }, [&](void* base, size_t have, size_t) -> int {
+        return feature_count_run(h->stream, base, have, d_x, N, Fin, flags, h_nnz);
+    });
+}
+
+int rlap_feature_plan_bytes(int64_t N, int64_t Fin, int64_t nnz, int flags, size_t* bytes) {
+    if (!bytes || N < 1 || Fin < 1 || nnz < 0) return RLAP_E_BAD_ARG;
+    if (flags & ~(RLAP_FEAT_X_F32 | RLAP_PLAN_FORWARD | RLAP_PLAN_TRANSPOSED)) return RLAP_E_BAD_ARG;
+    if (N >= featlin::MAX_DIM || Fin >= featlin::MAX_DIM || nnz >= featlin::MAX_NNZ) return RLAP_E_TOO_LARGE;
+    if (!(flags & (RLAP_PLAN_FORWARD | RLAP_PLAN_TRANSPOSED))) flags |= RLAP_PLAN_FORWARD | RLAP_PLAN_TRANSPOSED;
+    *bytes = (size_t)featlin::layout(N, Fin, nnz, (flags & RLAP_PLAN_FORWARD) != 0, (flags & RLAP_PLAN_TRANSPOSED) != 0).bytes;
+    return RLAP_OK;
+}
+
+int rlap_feature_plan_build(rlap_handle h, const void* d_x, int64_t N, int64_t Fin, int64_t nnz, int flags, void* d_plan, size_t plan_bytes,
+                            rlap_feature_desc* h_desc, rlap_feature_info* h_info) {
+    if (h_info) *h_info = rlap_feature_info{};
+    if (!h_desc) return RLAP_E_BAD_ARG;
+    *h_desc = rlap_feature_desc{};
+    if (!h || !d_x || !d_plan || (reinterpret_cast<uintptr_t>(d_plan) & 15)) return RLAP_E_BAD_ARG;
+    size_t bound = 0;
+    if (const int rc = rlap_feature_plan_bytes(N, Fin, nnz, flags, &bound)) return rc;
+    if (plan_bytes < bound) return RLAP_E_BAD_ARG;
+    if (!(flags & (RLAP_PLAN_FORWARD | RLAP_PLAN_TRANSPOSED))) flags |= RLAP_PLAN_FORWARD | RLAP_PLAN_TRANSPOSED;
+    return snapshot_call(h, [&] { return feature_build_bytes(N, Fin, flags); }, [&](void* base, size_t have, size_t need) -> int {
+        if (h->poison >= 0) {   // debug: the plan must not depend on what the arena or the caller's buffer held
+            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_plan, h->poison, plan_bytes, h->stream));
+        }
+        const FeatureBuildArgs a{d_x, N, Fin, nnz, flags, d_plan, plan_bytes};
+        FeatureReport rep;
+        const int rc = feature_build_run(h->stream, base, have, a, h_desc, &rep);
+        if (rc != RLAP_OK) *h_desc = rlap_feature_desc{};
+        if (h_info) {
+            h_info->nnz = rep.nnz;
+            h_info->longest_forward = rep.longest[0]; h_info->longest_transposed = rep.longest[1];
+            h_info->long_lists_forward = rep.long_lists[0]; h_info->long_lists_transposed = rep.long_lists[1];
+            h_info->chunks_forward = rep.chunks[0]; h_info->chunks_transposed = rep.chunks[1];
+            h_info->arena_bytes = (int64_t)need; h_info->host_syncs = rep.host_syncs;
+        }
+        return rc;
+    });
+}
+
+int rlap_feature_plan_apply(rlap_handle h, const void* d_plan, const rlap_feature_desc* h_desc, int flags, const void* d_w,
+                            const uint8_t* d_keep, int64_t K, int64_t Fout, void* d_out, rlap_feature_info* h_info) {
+    if (h_info) *h_info = rlap_feature_info{};
+    if (!h || !d_plan || !h_desc || !d_w || !d_out || Fout < 1) return RLAP_E_BAD_ARG;
+    if (flags & ~(RLAP_SPMM_TRANSPOSE | RLAP_SPMM_X_F32)) return RLAP_E_BAD_ARG;
+    if (K < 1 || K > featlin::MAX_VIEWS || (!d_keep && K != 1)) return RLAP_E_BAD_ARG;
+    const rlap_feature_desc d = *h_desc;
+    // a descriptor that a successful build wrote: every part it names lies inside the bytes it reports
+    if (d.magic != featlin::MAGIC || d.num_nodes < 1 || d.num_nodes >= featlin::MAX_DIM || d.in_features < 1 || d.in_features >= featlin::MAX_DIM ||
+        d.nnz < 0 || d.nnz >= featlin::MAX_NNZ || (reinterpret_cast<uintptr_t>(d_plan) & 15))
+        return RLAP_E_BAD_ARG;
+    const bool t = (flags & RLAP_SPMM_TRANSPOSE) != 0;
+    if (!(d.flags & (t ? RLAP_PLAN_TRANSPOSED : RLAP_PLAN_FORWARD))) return RLAP_E_BAD_ARG;
+    if (!featlin::parts_inside(t ? d.in_features : d.num_nodes, d.nnz, t ? d.chunks_transposed : d.chunks_forward,
+                               t ? d.off_transposed : d.off_forward, t ? d.dir_transposed : d.dir_forward,
+                               t ? d.rec_transposed : d.rec_forward, d.nnz, d.plan_bytes))
+        return RLAP_E_BAD_ARG;
+    if (Fout > SPMM_MAX_F || K * d.num_nodes * Fout >= SPMM_MAX_ELEMS || d.in_features * Fout >= SPMM_MAX_ELEMS) return RLAP_E_TOO_LARGE;
+    const int64_t out_elems = t ? d.in_features * Fout : K * d.num_nodes * Fout;
+    return snapshot_call(h, [&] { return feature_apply_bytes(d, K, Fout, flags, h->dbg_scr); }, [&](void* base, size_t have, size_t need) -> int {
+        if (h->poison >= 0) {   // debug: the result must not depend on what the arena or the result buffer held
+            RLAP_HIPCHK(hipMemsetAsync(base, h->poison, need, h->stream));
+            RLAP_HIPCHK(hipMemsetAsync(d_out, h->poison, (size_t)out_elems * ((flags & RLAP_SPMM_X_F32) ? 4 : 8), h->stream));
+        }
+        const FeatureApplyArgs a{d_plan, &d, flags, d_w, d_keep, K, Fout, d_out, h->dbg_scr};
+        const int rc = feature_apply_run(h->stream, base, have, a);
+        if (h_info) {
+            h_info->nnz = d.nnz; h_info->chunks_forward = d.chunks_forward; h_info->chunks_transposed = d.chunks_transposed;
+            h_info->longest_forward = h_info->longest_transposed = h_info->long_lists_forward = h_info->long_lists_transposed = -1;
             h_info->arena_bytes = (int64_t)need; h_info->host_syncs = 0;
         }
         return rc;

@@ -2389,6 +2389,146 @@ def edge_plan(
     return edge_list_plan(rows, [0, E], n, None, edge_weight is not None, add_self_loops, fill, normalize, directions)
 
 
+def _feature_apply(plan, w: Tensor, keep: Optional[Tensor], views: int, transpose: bool) -> Tensor:
+    """One rlap_feature_plan_apply call; the operands are already checked, on the plan's device and contiguous.  Forward: w is
+    (Fin, Fout) and the result (views, N, Fout); transposed: w is G (views, N, Fout) and the result (Fin, Fout)."""
+    dev = plan.buffer.device
+    flags = (_lib.SPMM_TRANSPOSE if transpose else 0) | (_lib.SPMM_X_F32 if w.dtype == torch.float32 else 0)
+    with torch.cuda.device(dev):
+        fout = int(w.shape[-1])
+        shape = (plan.in_features, fout) if transpose else (views, plan.num_nodes, fout)
+        out = torch.empty(shape, dtype=w.dtype, device=dev)
+        _device_call("rlap_feature_plan_apply", _lib.FeatureInfo, dev, 1, (
+            plan.buffer.data_ptr(), ctypes.byref(plan.desc), flags, w.data_ptr(), keep.data_ptr() if keep is not None else None,
+            views, fout, out.data_ptr()))
+        return out
+
+
+class _FeatureLinear(torch.autograd.Function):
+    """(x * keep[k]) @ W over a feature plan; the gradient with respect to W is the plan's transposed call on the upstream gradient."""
+
+    @staticmethod
+    def forward(ctx, weight, plan, keep, views):
+        ctx.call = (plan, keep, views)
+        return _feature_apply(plan, weight.detach().contiguous(), keep, views, False)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        plan, keep, views = ctx.call
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        if not PLAN_DIRECTIONS[plan.directions] & _lib.PLAN_TRANSPOSED:
+            raise RuntimeError(f"this feature plan holds the {plan.directions} lists only: the gradient with respect to weight is the "
+                               "transposed call; build the plan with directions=\"both\"")
+        return _feature_apply(plan, gy.contiguous(), keep, views, True), None, None, None
+
+
+class FeaturePlan:
+    """What feature_plan returns: the non-zeros of a dense (N, Fin) feature matrix as lists, built once.  `buffer` is the plan (a
+    torch.uint8 tensor on the device, owned by this object and independent of x after the build), `desc` its host descriptor
+    (rlap_feature_desc), `info` what the build did (rlap_feature_info: nnz, longest_forward / _transposed, long_lists_*, chunks_*,
+    arena_bytes, host_syncs).
+
+      num_nodes, in_features : N and Fin
+      nnz                    : kept entries
+      directions             : "forward", "transposed" or "both"
+      nbytes                 : bytes of the plan buffer
+    """
+
+    def __init__(self, buffer: Tensor, desc, info: dict, directions: str):
+        self.buffer, self.desc, self.info, self.directions = buffer, desc, info, directions
+        self.num_nodes, self.in_features, self.nnz = int(desc.num_nodes), int(desc.in_features), int(desc.nnz)
+        self.nbytes = int(buffer.numel())
+
+    def linear(self, weight: Tensor, keep: Optional[Tensor] = None) -> Tensor:
+        """(x * keep[k]) @ weight for every view k, without the masked copies of x: (K, N, Fout) for a (K, Fin) bool / uint8 `keep`
+        (non-zero = the view keeps the column; K <= 32), or x @ weight as (N, Fout) for keep=None.  `weight` is (Fin, Fout), float32
+        or float64, on the plan's device.  float64 sums in the fixed order of rlap_amd/csrc/rlap_featlin.h, rounded once: the same
+        bits on every run.  Differentiable in `weight` alone; the backward pass is the plan's transposed call
+        dW = sum_k keep[k][:, None] * (x^T G[k]), so a plan without the transposed direction raises there.  No host
+        synchronisation.  Sets `last_stats` (rlap_feature_info)."""
+        if not isinstance(weight, Tensor) or weight.dim() != 2 or weight.shape[0] != self.in_features or weight.shape[1] < 1:
+            raise ValueError(f"weight: an ({self.in_features}, Fout) tensor, Fout >= 1")
+        if weight.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"weight: float32 or float64, got {weight.dtype}")
+        if weight.device != self.buffer.device:
+            raise ValueError(f"weight: on the plan's device {self.buffer.device}, got {weight.device}")
+        views = 1
+        if keep is not None:
+            if not isinstance(keep, Tensor) or keep.dim() != 2 or keep.shape[1] != self.in_features or keep.dtype not in (torch.bool, torch.uint8):
+                raise ValueError(f"keep: None or a (K, {self.in_features}) bool or uint8 tensor")
+            views = int(keep.shape[0])
+            if not 1 <= views <= _lib.FEAT_MAX_VIEWS:
+                raise ValueError(f"keep: 1 to {_lib.FEAT_MAX_VIEWS} views, got {views}")
+        if not PLAN_DIRECTIONS[self.directions] & _lib.PLAN_FORWARD:
+            raise ValueError("this feature plan holds the transposed lists only: build it with directions=\"forward\" or \"both\"")
+        d_keep = keep.detach().to(device=self.buffer.device, dtype=torch.uint8).contiguous() if keep is not None else None
+        if torch.is_grad_enabled() and weight.requires_grad:
+            y = _FeatureLinear.apply(weight, self, d_keep, views)
+        else:
+            y = _feature_apply(self, weight.detach().contiguous(), d_keep, views, False)
+        return y if keep is not None else y[0]
+
+
+def feature_plan(x: Tensor, directions: str = "both") -> FeaturePlan:
+    """The sparse first layer's plan: the entries of the dense (N, Fin) float32 or float64 matrix `x` with (double)x != 0.0 (-0.0 is
+    dropped, NaN and infinities stay) as lists by row and by column, built once per run -- bag-of-words features are the same in
+    every step.  `.linear(weight, keep)` then gives every view's (x * keep[k]) @ weight from one pass over a row's list, and its
+    backward pass dW; the dense masked copies of adapters.drop_feature never exist.  `x` must not require a gradient (the call is
+    differentiable in the weight alone).
+
+      directions : "forward", "transposed" or "both" (default) -- the lists to build; training needs "both".
+
+    The plan lives in a torch.uint8 tensor on x's device (16 bytes per non-zero and direction); x may be freed after the build.
+    Malformed arguments raise ValueError before the device is touched.  Two host synchronisations (the count, then the build).
+    `last_stats` then holds rlap_feature_info."""
+    if not isinstance(x, Tensor) or x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError("x: a dense (N, Fin) tensor, N >= 1 and Fin >= 1")
+    if x.layout != torch.strided or x.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"x: a dense float32 or float64 tensor, got {x.dtype} ({x.layout})")
+    if x.requires_grad:
+        raise ValueError("x: must not require a gradient (FeaturePlan.linear is differentiable in the weight alone)")
+    if directions not in PLAN_DIRECTIONS:
+        raise ValueError(f"directions: one of {sorted(PLAN_DIRECTIONS)}, got {directions!r}")
+    N, Fin = int(x.shape[0]), int(x.shape[1])
+    dev = _device_for(x)
+    flags = (_lib.FEAT_X_F32 if x.dtype == torch.float32 else 0) | PLAN_DIRECTIONS[directions]
+    with torch.cuda.device(dev):
+        d_x = x.detach().to(device=dev).contiguous()
+        lib, hobj = _handle_obj(dev)
+        nnz = ctypes.c_int64(0)
+        rc = _run(hobj, dev, 0, None, 1, False, lambda: lib.rlap_feature_count(
+            hobj.ptr, d_x.data_ptr(), N, Fin, flags & _lib.FEAT_X_F32, ctypes.byref(nnz)), _lib.Stats())
+        if rc != 0:
+            _raise(rc)
+        bound = ctypes.c_size_t(0)
+        rc = lib.rlap_feature_plan_bytes(N, Fin, int(nnz.value), flags, ctypes.byref(bound))
+        if rc != 0:
+            _raise(rc)
+        buf = torch.empty(int(bound.value), dtype=torch.uint8, device=dev)
+        desc = _lib.FeatureDesc()
+        info = _device_call("rlap_feature_plan_build", _lib.FeatureInfo, dev, 1, (
+            d_x.data_ptr(), N, Fin, int(nnz.value), flags, buf.data_ptr(), buf.numel(), ctypes.byref(desc)))
+        return FeaturePlan(buf, desc, info.as_dict(), directions)
+
+
+def feature_masks(in_features: int, p: float, views: int = 1, generator=None, device=None) -> Tensor:
+    """The keep masks of FeaturePlan.linear, (views, in_features) bool, drawn as adapters.drop_feature draws its drop masks: per view
+    `torch.empty(in_features).uniform_(0, 1, generator=generator) < p` is dropped.  Under equally seeded generators on the same
+    device, x * keep[k] equals drop_feature(x, p, views, generator)[k].  `device` defaults to the generator's, else the CPU."""
+    fin = _count(in_features, "in_features", 1, 2**31 - 1)
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= float(p) <= 1.0:
+        raise ValueError(f"p: in [0, 1], got {p!r}")
+    k = _count(views, "views", 1, _lib.FEAT_MAX_VIEWS)
+    if device is None:
+        device = generator.device if generator is not None else torch.device("cpu")
+    keep = torch.empty((k, fin), dtype=torch.bool, device=device)
+    for v in range(k):
+        keep[v] = ~(torch.empty((fin,), dtype=torch.float32, device=device).uniform_(0, 1, generator=generator) < p)
+    return keep
+
+
 DROP_AGGR = {"sink": 0, "source": _lib.DROP_SOURCE}
 DROP_MAX_STEPS = 100000   # cap on pr_iters and evc_max_iter (rlap_amd/csrc/rlap_edgedrop.h)
 
