@@ -34,12 +34,16 @@
 
 #include "../../include/rlap_hip.h"
 #include "rlap_edgeadd.h"
+#include "rlap_rowcompact_dev.h"
 #include "rlap_snapshot.h"
 
 namespace rlap {
 namespace {
 
 using namespace edgeadd;
+using rowcompact::clamp;
+using rowcompact::scan_tmp_bytes;
+using rowcompact::store_row;
 
 constexpr int64_t EA_MAX_GRID = 8192;                            // workgroups of a strided launch
 enum { W_ERR = 0, W_UNSORTED = 1 };                              // int32 words
@@ -48,8 +52,6 @@ enum { W_VIEW64 = W_HOST64, W_WORDS64 = W_HOST64 + MAX_VIEWS };  // ... and a co
 constexpr uint64_t EMPTY_SLOT = ~(uint64_t)0;                    // (no key: bit 63 of every key is clear)
 
 inline unsigned ea_blocks(int64_t n) { return capped_blocks(n, TILE, EA_MAX_GRID); }
-
-__device__ inline int64_t ea_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 struct Ea {
     const int64_t* src; const int64_t* dst; const double* w; int64_t E, N;
@@ -104,11 +106,11 @@ __global__ __launch_bounds__(TILE) void k_ea_draw(Ea a, int as_rows) {
         const int k = ea_view_of(a, g);
         const int64_t i = g - a.first[k];
         const uint64_t view = add_view(a.seed, k);
-        const int64_t s = ea_clamp(draw(view, i, 0, a.N), 0, a.N - 1), t = ea_clamp(draw(view, i, 1, a.N), 0, a.N - 1);
+        const int64_t s = clamp(draw(view, i, 0, a.N), 0, a.N - 1), t = clamp(draw(view, i, 1, a.N), 0, a.N - 1);
         if (a.added) { a.added[2 * g] = s; a.added[2 * g + 1] = t; }
         if (as_rows) {
             const int64_t pos = (int64_t)(k + 1) * a.E + g;
-            if (pos < a.cap) { double* __restrict__ o = a.rows + 3 * pos; o[0] = (double)s; o[1] = (double)t; o[2] = 1.0; }
+            if (pos < a.cap) store_row(a.rows, pos, (double)s, (double)t, 1.0);
         } else {
             a.bin[g] = pair_key(s, t, a.b) | (a.one ? (uint64_t)k << (2 * a.b) : (uint64_t)0);
         }
@@ -122,8 +124,7 @@ __global__ __launch_bounds__(TILE) void k_ea_copy(Ea a) {
     for (int64_t j = (int64_t)blockIdx.x * TILE + threadIdx.x; j < total; j += (int64_t)gridDim.x * TILE) {
         const int64_t k = j / a.E, e = j - k * a.E, pos = j + a.first[k];
         if (pos >= a.cap) continue;
-        double* __restrict__ o = a.rows + 3 * pos;
-        o[0] = (double)a.src[e]; o[1] = (double)a.dst[e]; o[2] = a.w ? a.w[e] : 1.0;
+        store_row(a.rows, pos, (double)a.src[e], (double)a.dst[e], a.w ? a.w[e] : 1.0);
     }
 }
 __global__ __launch_bounds__(WAVE) void k_ea_plain_ptr(Ea a) {
@@ -146,7 +147,7 @@ __global__ __launch_bounds__(TILE) void k_ea_runs_b(Ea a) {
     const uint64_t mask = ((uint64_t)1 << (2 * a.b)) - 1;
     for (int64_t g = (int64_t)blockIdx.x * TILE + threadIdx.x; g < total; g += (int64_t)gridDim.x * TILE) {
         if (!a.flag_b[g]) continue;
-        const int64_t end = a.first[ea_view_of(a, g) + 1], p = ea_clamp(a.pos_b[g], 0, total - 1);
+        const int64_t end = a.first[ea_view_of(a, g) + 1], p = clamp(a.pos_b[g], 0, total - 1);
         const uint64_t key = a.bs[g];
         int64_t j = g + 1;
         while (j < end && a.bs[j] == key) ++j;
@@ -262,10 +263,10 @@ __global__ __launch_bounds__(TILE) void k_ea_runs_a(Tail t) {
     for (int64_t e = (int64_t)blockIdx.x * TILE + threadIdx.x; e < t.E; e += (int64_t)gridDim.x * TILE) {
         if (!t.flag_a[e]) continue;
         const uint64_t key = t.key[e];
-        const int64_t p = ea_clamp(t.pos_a[e], 0, t.E - 1);
+        const int64_t p = clamp(t.pos_a[e], 0, t.E - 1);
         double s = 0.0;
         for (int64_t j = e; j < t.E && t.key[j] == key; ++j) {
-            const int64_t row = t.perm ? ea_clamp(t.perm[j], 0, t.E - 1) : j;
+            const int64_t row = t.perm ? clamp(t.perm[j], 0, t.E - 1) : j;
             s = run_add(s, t.w ? t.w[row] : 1.0);
         }
         t.akey[p] = key;
@@ -300,9 +301,9 @@ __global__ __launch_bounds__(TILE) void k_ea_merge(Tail t) {
     const int64_t slot = (int64_t)k * t.nT + blockIdx.x;
     if (WRITE && t.offs[(int64_t)t.K * t.nT] > t.cap) return;   // (too little room: nothing is written)
     const int64_t addk = t.first[k + 1] - t.first[k];
-    const int64_t na = ea_clamp(reinterpret_cast<const int64_t*>(t.words)[W_NA64], 0, t.E);
-    const int64_t bfirst = ea_clamp(t.pos_b[t.first[k]], 0, t.first[t.K]);
-    const int64_t nb = ea_clamp(t.pos_b[t.first[k + 1]] - bfirst, 0, addk);
+    const int64_t na = clamp(reinterpret_cast<const int64_t*>(t.words)[W_NA64], 0, t.E);
+    const int64_t bfirst = clamp(t.pos_b[t.first[k]], 0, t.first[t.K]);
+    const int64_t nb = clamp(t.pos_b[t.first[k + 1]] - bfirst, 0, addk);
     const uint64_t* __restrict__ A = t.akey;
     const uint64_t* __restrict__ B = t.bkey + bfirst;
     const int64_t L = na + nb;
@@ -312,7 +313,7 @@ __global__ __launch_bounds__(TILE) void k_ea_merge(Tail t) {
         ends[threadIdx.x] = merge_split(threadIdx.x ? d1 : d0, na, nb, [&](int64_t i) { return A[i]; }, [&](int64_t i) { return B[i]; });
     __syncthreads();
     const int64_t a0 = ends[0], a1 = ends[1], b0 = d0 - a0, b1 = d1 - a1;
-    const int la = (int)ea_clamp(a1 - a0, 0, ROW_TILE), lb = (int)ea_clamp(b1 - b0, 0, ROW_TILE - la), n = la + lb;
+    const int la = (int)clamp(a1 - a0, 0, ROW_TILE), lb = (int)clamp(b1 - b0, 0, ROW_TILE - la), n = la + lb;
     for (int i = threadIdx.x; i < n; i += TILE) keys[i] = i < la ? A[a0 + i] : B[b0 + (i - la)];
     __syncthreads();
     const uint64_t* sA = keys;
@@ -376,7 +377,7 @@ __global__ __launch_bounds__(TILE) void k_ea_merge(Tail t) {
     __syncthreads();
     const int tile_heads = std::min<int>((wsum[0] + wsum[1]) + (wsum[2] + wsum[3]), ROW_TILE);
     const int64_t room = std::min<int64_t>(end, t.cap) - off;
-    const int rows_out = (int)ea_clamp(room, 0, tile_heads);
+    const int rows_out = (int)clamp(room, 0, tile_heads);
     double* __restrict__ o = t.rows + 3 * off;
     for (int i = threadIdx.x; i < 3 * rows_out; i += TILE) {
         const int row = i / 3, c = i - 3 * row;
@@ -412,12 +413,6 @@ Shape shape_of(int64_t E, int K, const int64_t* num_add) {
     for (int k = 0; k < K; ++k) { s.added += num_add[k]; s.max_add = std::max(s.max_add, num_add[k]); }
     s.nT = std::max<int64_t>(1, (E + s.max_add + ROW_TILE - 1) / ROW_TILE);
     return s;
-}
-
-size_t scan_tmp_bytes(int64_t items) {
-    size_t bytes = 0;
-    (void)rocprim::exclusive_scan(nullptr, bytes, (const int32_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)items, rocprim::plus<int64_t>(), (hipStream_t)0);
-    return bytes;
 }
 
 size_t carve(Carve& C, int64_t E, int64_t N, int K, const int64_t* num_add, bool coalesce, Bufs& B) {
@@ -468,12 +463,6 @@ int edge_add_run(hipStream_t st, void* ws, size_t ws_bytes, const EdgeAddArgs& g
     if (carve(C, E, N, K, g.num_add, g.coalesce != 0, B) > ws_bytes) return RLAP_E_WORKSPACE;
     int64_t launches = 0;
     int32_t sorts = 0;
-#define EA_LAUNCH(kernel, grid, block, ...)                                            \
-    do {                                                                               \
-        hipLaunchKernelGGL(kernel, grid, dim3(block), 0, st, __VA_ARGS__);             \
-        RLAP_HIPCHK(hipGetLastError());                                                \
-        ++launches;                                                                    \
-    } while (0)
     Ea a{};
     a.src = g.src; a.dst = g.dst; a.w = g.w; a.E = E; a.N = N; a.K = K; a.b = id_bits(N); a.one = one_sort(N, K) ? 1 : 0;
     a.words = B.words; a.kin = B.kin; a.vin = B.vin; a.bin = B.bin; a.bs = B.bs; a.flag_b = B.flag_b; a.pos_b = B.pos_b;
@@ -489,11 +478,11 @@ int edge_add_run(hipStream_t st, void* ws, size_t ws_bytes, const EdgeAddArgs& g
         // the range check, the K copies of the rows and the draws behind them; the total is the host's to know
         const int64_t total = (int64_t)K * E + sh.added;
         rep->rows_needed = total;
-        if (E > 0) EA_LAUNCH(k_ea_keys, dim3(ea_blocks(E)), TILE, a, 0);
+        if (E > 0) RLAP_LAUNCH_COUNTED(k_ea_keys, dim3(ea_blocks(E)), TILE, a, 0);
         if (total <= g.cap) {
-            if (E > 0) EA_LAUNCH(k_ea_copy, dim3(ea_blocks((int64_t)K * E)), TILE, a);
-            if (sh.added > 0) EA_LAUNCH(k_ea_draw, dim3(ea_blocks(sh.added)), TILE, a, 1);
-            EA_LAUNCH(k_ea_plain_ptr, dim3(1), WAVE, a);
+            if (E > 0) RLAP_LAUNCH_COUNTED(k_ea_copy, dim3(ea_blocks((int64_t)K * E)), TILE, a);
+            if (sh.added > 0) RLAP_LAUNCH_COUNTED(k_ea_draw, dim3(ea_blocks(sh.added)), TILE, a, 1);
+            RLAP_LAUNCH_COUNTED(k_ea_plain_ptr, dim3(1), WAVE, a);
         }
         RLAP_HIPCHK(hipMemcpyAsync(hw, B.words, sizeof(hw), hipMemcpyDeviceToHost, st));
         RLAP_HIPCHK(hipStreamSynchronize(st));
@@ -503,9 +492,9 @@ int edge_add_run(hipStream_t st, void* ws, size_t ws_bytes, const EdgeAddArgs& g
         return total > g.cap ? RLAP_E_OUT_CAPACITY : RLAP_OK;
     }
     // 1. the input's keys; 2. the draws, their sort and list B of every view
-    if (E > 0) EA_LAUNCH(k_ea_keys, dim3(ea_blocks(E)), TILE, a, 1);
+    if (E > 0) RLAP_LAUNCH_COUNTED(k_ea_keys, dim3(ea_blocks(E)), TILE, a, 1);
     if (sh.added > 0) {
-        EA_LAUNCH(k_ea_draw, dim3(ea_blocks(sh.added)), TILE, a, 0);
+        RLAP_LAUNCH_COUNTED(k_ea_draw, dim3(ea_blocks(sh.added)), TILE, a, 0);
         if (a.one) {
             size_t sb = B.sort_bytes;
             RLAP_HIPCHK(rocprim::radix_sort_keys(B.sort_tmp, sb, (const uint64_t*)B.bin, B.bs, (size_t)sh.added, 0u, key_width(N) + view_bits(K), st));
@@ -520,12 +509,12 @@ int edge_add_run(hipStream_t st, void* ws, size_t ws_bytes, const EdgeAddArgs& g
             }
         }
     }
-    EA_LAUNCH(k_ea_heads_b, dim3(ea_blocks(sh.added + 1)), TILE, a);
+    RLAP_LAUNCH_COUNTED(k_ea_heads_b, dim3(ea_blocks(sh.added + 1)), TILE, a);
     {
         size_t cb = B.scan_bytes;
         RLAP_HIPCHK(rocprim::exclusive_scan(B.scan_tmp, cb, B.flag_b, B.pos_b, (int64_t)0, (size_t)(sh.added + 1), rocprim::plus<int64_t>(), st));
     }
-    if (sh.added > 0) EA_LAUNCH(k_ea_runs_b, dim3(ea_blocks(sh.added)), TILE, a);
+    if (sh.added > 0) RLAP_LAUNCH_COUNTED(k_ea_runs_b, dim3(ea_blocks(sh.added)), TILE, a);
     // 3. list A and the merge
     Tail t{};
     t.w = g.w; t.E = E; t.words = B.words; t.flag_a = B.flag_a; t.pos_a = B.pos_a; t.akey = B.akey; t.asum = B.asum;
@@ -535,26 +524,26 @@ int edge_add_run(hipStream_t st, void* ws, size_t ws_bytes, const EdgeAddArgs& g
     const int64_t slots = (int64_t)K * sh.nT + 1;
     auto tail = [&](const uint64_t* key, const int32_t* perm, int gate) -> int {
         t.key = key; t.perm = perm; t.gate = gate;
-        EA_LAUNCH(k_ea_heads_a, dim3(ea_blocks(E + 1)), TILE, t);
+        RLAP_LAUNCH_COUNTED(k_ea_heads_a, dim3(ea_blocks(E + 1)), TILE, t);
         size_t cb = B.scan_bytes;
         RLAP_HIPCHK(rocprim::exclusive_scan(B.scan_tmp, cb, B.flag_a, B.pos_a, (int64_t)0, (size_t)(E + 1), rocprim::plus<int64_t>(), st));
-        EA_LAUNCH(k_ea_runs_a, dim3(ea_blocks(std::max<int64_t>(E, 1))), TILE, t);
+        RLAP_LAUNCH_COUNTED(k_ea_runs_a, dim3(ea_blocks(std::max<int64_t>(E, 1))), TILE, t);
         RLAP_HIPCHK(hipMemsetAsync(B.counts, 0, sizeof(int32_t) * (size_t)slots, st));
-        EA_LAUNCH(k_ea_merge<false>, dim3((unsigned)sh.nT, (unsigned)K), TILE, t);
+        RLAP_LAUNCH_COUNTED(k_ea_merge<false>, dim3((unsigned)sh.nT, (unsigned)K), TILE, t);
         cb = B.scan_bytes;
         RLAP_HIPCHK(rocprim::exclusive_scan(B.scan_tmp, cb, B.counts, B.offs, (int64_t)0, (size_t)slots, rocprim::plus<int64_t>(), st));
-        EA_LAUNCH(k_ea_ptr, dim3(1), WAVE, t);
-        EA_LAUNCH(k_ea_merge<true>, dim3((unsigned)sh.nT, (unsigned)K), TILE, t);
+        RLAP_LAUNCH_COUNTED(k_ea_ptr, dim3(1), WAVE, t);
+        RLAP_LAUNCH_COUNTED(k_ea_merge<true>, dim3((unsigned)sh.nT, (unsigned)K), TILE, t);
         return RLAP_OK;
     };
     // for keys that ascend: the whole call; every kernel of it returns on the raised word
     if (const int rc = tail(B.kin, nullptr, 1)) return rc;
     // for keys that do not: the row total and ptr from a set of the input's keys; every kernel of it returns unless the word is raised
     if (E > 0) {
-        EA_LAUNCH(k_ea_hash_clear, dim3(ea_blocks(a.slots)), TILE, a);
-        EA_LAUNCH(k_ea_hash_insert, dim3(ea_blocks(E)), TILE, a);
-        if (sh.added > 0) EA_LAUNCH(k_ea_hash_probe, dim3(ea_blocks(sh.max_add)), TILE, a);
-        EA_LAUNCH(k_ea_hash_ptr, dim3(1), WAVE, a);
+        RLAP_LAUNCH_COUNTED(k_ea_hash_clear, dim3(ea_blocks(a.slots)), TILE, a);
+        RLAP_LAUNCH_COUNTED(k_ea_hash_insert, dim3(ea_blocks(E)), TILE, a);
+        if (sh.added > 0) RLAP_LAUNCH_COUNTED(k_ea_hash_probe, dim3(ea_blocks(sh.max_add)), TILE, a);
+        RLAP_LAUNCH_COUNTED(k_ea_hash_ptr, dim3(1), WAVE, a);
     }
     // the one read-back: the error word, whether the keys ascended, the distinct input keys and the row total
     RLAP_HIPCHK(hipMemcpyAsync(hw, B.words, sizeof(hw), hipMemcpyDeviceToHost, st));
@@ -571,7 +560,6 @@ int edge_add_run(hipStream_t st, void* ws, size_t ws_bytes, const EdgeAddArgs& g
         ++sorts;
         if (const int rc = tail(B.ks, g.w ? B.perm : nullptr, 0)) return rc;
     }
-#undef EA_LAUNCH
     rep->launches = launches;
     rep->sorts = sorts;
     rep->input_sorted = h32[W_UNSORTED] ? 0 : 1;

@@ -9,9 +9,9 @@
 //   steps    one launch a step of an iteration; kernel boundaries carry the data between workgroups.  Every kernel of an eigenvector
 //            step returns at once when the `done` word is set: the host enqueues max_iter steps and reads nothing back.
 //   scores   three node-level kernels over tiles of 256 nodes with partials.
-//   flip     the only per-edge kernels: pass A counts the kept rows per (view, tile of 2,048 rows), one scan gives the offsets and
-//            ptr, pass B recomputes the coins and writes [source, target, weight] at offset + rank (ballot and population count
-//            within the wave, wave counts in LDS), rows in input order, and the optional mask.
+//   flip     the only per-edge kernels, rlap_rowcompact_dev.h's two passes (k_rc_count, k_rc_ptr, k_rc_write) with the predicate
+//            DropCoin: the coin of (view, row) against the drop probability, recomputed in pass B, which also writes the optional
+//            mask.
 //   One read-back: the error word, the iteration report and the row total.  No atomic on a float; LDS holds reduction words only.
 #include <algorithm>
 #include <cstdio>
@@ -22,27 +22,26 @@
 
 #include "../../include/rlap_hip.h"
 #include "rlap_edgedrop.h"
+#include "rlap_rowcompact_dev.h"
 #include "rlap_snapshot.h"
 
 namespace rlap {
 namespace {
 
 using namespace edgedrop;
+using rowcompact::clamp;
 
 constexpr int64_t ED_MAX_GRID = 8192;                    // workgroups of a strided launch
-constexpr int ROUNDS = ROW_TILE / TILE;                  // rows a lane flips
 enum { W_ERR = 0, W_DONE = 1, W_ITERS = 2, W_CONV = 3, W_TOTAL64 = 2, W_WORDS64 = 4 };   // int32 words; the total is int64 word 2
 
 inline unsigned ed_blocks(int64_t n) { return capped_blocks(n, TILE, ED_MAX_GRID); }
-
-__device__ inline int64_t ed_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 struct Ed {
     const int64_t* src; const int64_t* dst; int64_t E, N, nt;   // nt: node tiles
     int scheme, source;
     int32_t* words;
     int32_t* in; int32_t* out;
-    uint32_t* key; int32_t* val; uint32_t* skey; int32_t* perm; int32_t* lo; int32_t* hi; int32_t* srcs;
+    uint32_t* key; int32_t* val; int32_t* lo; int32_t* hi; int32_t* srcs;
     uint64_t* key2; uint64_t* skey2; int32_t* dcount;
     double* c; double* s; double* wv; double* nw; double* x; double* y; double* part;   // part: [3][nt]
 };
@@ -71,15 +70,15 @@ __device__ inline double wg_total(Op op, const double* __restrict__ part, int64_
 __device__ inline double ed_list_sum(const Ed& a, int64_t v, int sub, const double* __restrict__ x) {
     int64_t s = 0, n = 0;
     if (v < a.N) {
-        s = ed_clamp(a.lo[v], 0, a.E);
-        n = ed_clamp(a.hi[v], s, a.E) - s;
+        s = clamp(a.lo[v], 0, a.E);
+        n = clamp(a.hi[v], s, a.E) - s;
     }
     double acc[edgeplan::ACCS] = {0.0, 0.0, 0.0, 0.0};
     for (int64_t turn = 0; edgeplan::place_of(turn, 0, sub) < n; ++turn) {
 #pragma unroll
         for (int u = 0; u < edgeplan::ACCS; ++u) {
             const int64_t k = edgeplan::place_of(turn, u, sub);
-            if (k < n) acc[u] += x[ed_clamp(a.srcs[s + k], 0, a.N - 1)];
+            if (k < n) acc[u] += x[clamp(a.srcs[s + k], 0, a.N - 1)];
         }
     }
     double d = edgeplan::combine(acc);
@@ -120,18 +119,6 @@ __global__ __launch_bounds__(TILE) void k_ed_keys(Ed a, int counts, int csr, int
             a.key2[2 * e] = ok ? (uint64_t)d * (uint64_t)a.N + (uint64_t)s : 0ull;
             a.key2[2 * e + 1] = ok ? (uint64_t)s * (uint64_t)a.N + (uint64_t)d : 0ull;
         }
-    }
-}
-
-// [lo[v], hi[v]) = the positions of target v among the sorted rows (both zeroed before); the sources in list order
-__global__ __launch_bounds__(TILE) void k_ed_bounds(Ed a) {
-    if (ed_failed(a)) return;
-    for (int64_t p = (int64_t)blockIdx.x * TILE + threadIdx.x; p < a.E; p += (int64_t)gridDim.x * TILE) {
-        const int64_t key = a.skey[p];
-        a.srcs[p] = (int32_t)ed_clamp(a.src[ed_clamp(a.perm[p], 0, a.E - 1)], 0, a.N - 1);
-        if (key >= a.N) continue;
-        if (p == 0 || a.skey[p - 1] != key) a.lo[key] = (int32_t)p;
-        if (p == a.E - 1 || a.skey[p + 1] != key) a.hi[key] = (int32_t)(p + 1);
     }
 }
 
@@ -273,117 +260,30 @@ __global__ __launch_bounds__(TILE) void k_ed_score_nw(Ed a) {
     if (v < a.N) a.nw[v] = a.wv[v] / wmean;
 }
 
-// ---------------------------------------------------------------- flip and compact
-struct Flip {
-    const int64_t* src; const int64_t* dst; const double* w; int64_t E, N, nT;   // nT: row tiles
-    int uniform, source, K;
+// ---------------------------------------------------------------- flip and compact: rlap_rowcompact_dev.h's passes with this predicate
+struct DropCoin {
+    static constexpr bool MASK = true;
+    struct Row { uint64_t he; double nw; };   // the hash of the row number and the node weight of the endpoint
+    int uniform, source; int64_t N;
     const double* nw; double p[MAX_VIEWS]; double threshold; uint64_t seed;
-    const int32_t* words; int32_t* counts; const int64_t* offs;                  // [K * nT + 1], view-major
-    double* rows; int64_t cap; int64_t* ptr; uint8_t* mask;
+    __device__ Row row(const rowcompact::Rows& c, int64_t e) const {
+        Row r{coin_row(e), 0.0};
+        if (!uniform && e < c.E) r.nw = nw[clamp(source ? c.src[e] : c.dst[e], 0, N - 1)];
+        return r;
+    }
+    __device__ uint64_t view(int k) const { return coin_view(seed, k); }
+    __device__ bool keep(int k, uint64_t view, const Row& r) const {
+        return keeps(coin_of(view, r.he), drop_prob(uniform != 0, r.nw, p[k], threshold));
+    }
 };
-
-// what a lane knows of its ROUNDS rows: the hash of the row number and the node weight of the endpoint
-__device__ inline void flip_load(const Flip& f, int64_t base, uint64_t (&he)[ROUNDS], double (&nw)[ROUNDS]) {
-#pragma unroll
-    for (int r = 0; r < ROUNDS; ++r) {
-        const int64_t e = base + r * TILE + threadIdx.x;
-        he[r] = coin_row(e);
-        nw[r] = 0.0;
-        if (!f.uniform && e < f.E) nw[r] = f.nw[ed_clamp(f.source ? f.src[e] : f.dst[e], 0, f.N - 1)];
-    }
-}
-
-__device__ inline bool flip_keep(const Flip& f, int k, uint64_t view, uint64_t he, double nw) {
-    return keeps(coin_of(view, he), drop_prob(f.uniform != 0, nw, f.p[k], f.threshold));
-}
-
-// pass A: the kept rows of every (view, tile)
-__global__ __launch_bounds__(TILE) void k_ed_count(Flip f) {
-    __shared__ int wc[MAX_VIEWS][TILE / WAVE];
-    if (f.words[W_ERR]) return;
-    const int64_t base = (int64_t)blockIdx.x * ROW_TILE;
-    uint64_t he[ROUNDS];
-    double nw[ROUNDS];
-    flip_load(f, base, he, nw);
-    for (int k = 0; k < f.K; ++k) {
-        const uint64_t view = coin_view(f.seed, k);
-        int c = 0;
-#pragma unroll
-        for (int r = 0; r < ROUNDS; ++r) {
-            const bool keep = base + r * TILE + threadIdx.x < f.E && flip_keep(f, k, view, he[r], nw[r]);
-            c += __popcll(__ballot(keep));
-        }
-        if ((threadIdx.x & (WAVE - 1)) == 0) wc[k][threadIdx.x / WAVE] = c;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < f.K) {
-        const int k = threadIdx.x;
-        f.counts[(int64_t)k * f.nT + blockIdx.x] = (wc[k][0] + wc[k][1]) + (wc[k][2] + wc[k][3]);
-    }
-}
-
-// ptr[k] = the first row of view k; the total for the host
-__global__ __launch_bounds__(WAVE) void k_ed_ptr(Flip f, int32_t* words) {
-    const int k = threadIdx.x;
-    if (k <= f.K) f.ptr[k] = f.offs[(int64_t)k * f.nT];
-    if (k == 0) reinterpret_cast<int64_t*>(words)[W_TOTAL64] = f.offs[(int64_t)f.K * f.nT];
-}
-
-// pass B: the coins again, the rows at offset + rank, the mask
-__global__ __launch_bounds__(TILE) void k_ed_write(Flip f) {
-    __shared__ int wc[ROUNDS][TILE / WAVE];
-    if (f.words[W_ERR]) return;
-    const bool fits = f.offs[(int64_t)f.K * f.nT] <= f.cap;   // (too little room: nothing is written but the mask)
-    const int64_t base = (int64_t)blockIdx.x * ROW_TILE;
-    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-    uint64_t he[ROUNDS];
-    double nw[ROUNDS];
-    flip_load(f, base, he, nw);
-    for (int k = 0; k < f.K; ++k) {
-        const uint64_t view = coin_view(f.seed, k);
-        const int64_t off = f.offs[(int64_t)k * f.nT + blockIdx.x], end = f.offs[(int64_t)k * f.nT + blockIdx.x + 1];
-        unsigned kept = 0;
-        int rank[ROUNDS];
-#pragma unroll
-        for (int r = 0; r < ROUNDS; ++r) {
-            const int64_t e = base + r * TILE + threadIdx.x;
-            const bool keep = e < f.E && flip_keep(f, k, view, he[r], nw[r]);
-            const unsigned long long b = __ballot(keep);
-            rank[r] = __popcll(b & ((1ull << lane) - 1ull));
-            kept |= keep ? 1u << r : 0u;
-            if (lane == 0) wc[r][wave] = __popcll(b);
-            if (f.mask && e < f.E) f.mask[(int64_t)k * f.E + e] = keep ? 1 : 0;
-        }
-        __syncthreads();
-        int pre = 0;
-#pragma unroll
-        for (int r = 0; r < ROUNDS; ++r) {
-#pragma unroll
-            for (int w = 0; w < TILE / WAVE; ++w) {
-                if (w == wave) rank[r] += pre;
-                pre += wc[r][w];
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < ROUNDS; ++r) {
-            const int64_t e = base + r * TILE + threadIdx.x;
-            const int64_t pos = off + rank[r];
-            if (!fits || !(kept >> r & 1u) || pos >= end || pos >= f.cap) continue;
-            double* __restrict__ o = f.rows + 3 * pos;
-            o[0] = (double)f.src[e]; o[1] = (double)f.dst[e]; o[2] = f.w ? f.w[e] : 1.0;
-        }
-        __syncthreads();   // (wc is rewritten by the next view)
-    }
-}
 
 struct Bufs {
     int32_t* words;
-    int32_t *in, *out, *val, *perm, *lo, *hi, *srcs, *dcount, *counts;
+    int32_t *in, *out, *val, *perm, *lo, *hi, *srcs, *dcount;
     uint32_t *key, *skey;
     uint64_t *key2, *skey2;
-    int64_t* offs;
     double *c, *s, *wv, *nw, *x, *y, *part;
-    void* scan_tmp; size_t scan_bytes;
+    rowcompact::Scratch compact;
     void* sort_tmp; size_t sort_bytes;
 };
 
@@ -410,16 +310,8 @@ size_t carve(Carve& C, int64_t E, int64_t N, int K, int scheme, Bufs& B) {
     B.x = C.take<double>(csr ? N : 0);
     B.y = C.take<double>(csr ? N : 0);
     B.part = C.take<double>(scored ? 3 * nt : 0);
-    B.counts = C.take<int32_t>((int64_t)K * nT + 1);
-    B.offs = C.take<int64_t>((int64_t)K * nT + 1);
-    B.scan_bytes = 0;
-    (void)rocprim::exclusive_scan(nullptr, B.scan_bytes, (const int32_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)((int64_t)K * nT + 1),
-                                  rocprim::plus<int64_t>(), (hipStream_t)0);
-    B.scan_tmp = C.take<char>((int64_t)B.scan_bytes);
-    B.sort_bytes = 0;
-    if (csr)
-        (void)rocprim::radix_sort_pairs(nullptr, B.sort_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const int32_t*)nullptr,
-                                        (int32_t*)nullptr, (size_t)std::max<int64_t>(E, 1), 0u, edgeplan::key_bits(N), (hipStream_t)0);
+    rowcompact::carve(C, K, nT, B.compact);
+    B.sort_bytes = csr ? rowcompact::list_sort_bytes(E, N) : 0;
     if (pairs)
         (void)rocprim::radix_sort_keys(nullptr, B.sort_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)std::max<int64_t>(2 * E, 1), 0u,
                                        pair_key_bits(N), (hipStream_t)0);
@@ -444,16 +336,10 @@ int edge_drop_run(hipStream_t st, void* ws, size_t ws_bytes, const EdgeDropArgs&
     Carve C{static_cast<char*>(ws), 0};
     if (carve(C, E, N, K, scheme, B) > ws_bytes) return RLAP_E_WORKSPACE;
     int64_t launches = 0;
-#define ED_LAUNCH(kernel, grid, block, ...)                                            \
-    do {                                                                               \
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, __VA_ARGS__);       \
-        RLAP_HIPCHK(hipGetLastError());                                                \
-        ++launches;                                                                    \
-    } while (0)
     Ed a{};
     a.src = g.src; a.dst = g.dst; a.E = E; a.N = N; a.nt = nt; a.scheme = scheme; a.source = g.source;
     a.words = B.words; a.in = B.in; a.out = B.out;
-    a.key = B.key; a.val = B.val; a.skey = B.skey; a.perm = B.perm; a.lo = B.lo; a.hi = B.hi; a.srcs = B.srcs;
+    a.key = B.key; a.val = B.val; a.lo = B.lo; a.hi = B.hi; a.srcs = B.srcs;
     a.key2 = B.key2; a.skey2 = B.skey2; a.dcount = B.dcount;
     a.c = g.centrality ? g.centrality : B.c; a.s = B.s; a.wv = B.wv; a.nw = g.node_weight ? g.node_weight : B.nw;
     a.x = B.x; a.y = B.y; a.part = B.part;
@@ -467,62 +353,51 @@ int edge_drop_run(hipStream_t st, void* ws, size_t ws_bytes, const EdgeDropArgs&
         RLAP_HIPCHK(hipMemsetAsync(B.in, 0, sizeof(int32_t) * (size_t)N, st));
         RLAP_HIPCHK(hipMemsetAsync(B.out, 0, sizeof(int32_t) * (size_t)N, st));
     }
-    if (E > 0) ED_LAUNCH(k_ed_keys, ed_blocks(E), TILE, a, scored ? 1 : 0, csr ? 1 : 0, pairs ? 1 : 0);
+    if (E > 0) RLAP_LAUNCH_COUNTED(k_ed_keys, ed_blocks(E), TILE, a, scored ? 1 : 0, csr ? 1 : 0, pairs ? 1 : 0);
     if (csr) {
-        RLAP_HIPCHK(hipMemsetAsync(B.lo, 0, sizeof(int32_t) * (size_t)N, st));
-        RLAP_HIPCHK(hipMemsetAsync(B.hi, 0, sizeof(int32_t) * (size_t)N, st));
-        size_t sb = B.sort_bytes;
-        RLAP_HIPCHK(rocprim::radix_sort_pairs(B.sort_tmp, sb, (const uint32_t*)B.key, B.skey, (const int32_t*)B.val, B.perm, (size_t)E, 0u,
-                                            edgeplan::key_bits(N), st));
-        ED_LAUNCH(k_ed_bounds, ed_blocks(E), TILE, a);
+        // every node's incoming rows in input order, their sources in list order
+        const rowcompact::Lists l{E, N, B.words + W_ERR, B.key, B.val, B.skey, B.perm, B.lo, B.hi, g.src, B.srcs, B.sort_tmp, B.sort_bytes};
+        if (const int rc = rowcompact::build_lists(st, l, ed_blocks(E), launches)) return rc;
     }
     // 2. the centrality
     if (pairs) {
         RLAP_HIPCHK(hipMemsetAsync(B.dcount, 0, sizeof(int32_t) * (size_t)N, st));
         size_t sb = B.sort_bytes;
         RLAP_HIPCHK(rocprim::radix_sort_keys(B.sort_tmp, sb, (const uint64_t*)B.key2, B.skey2, (size_t)(2 * E), 0u, pair_key_bits(N), st));
-        ED_LAUNCH(k_ed_heads, ed_blocks(2 * E), TILE, a);
-        ED_LAUNCH(k_ed_degree, ed_blocks(N), TILE, a);
+        RLAP_LAUNCH_COUNTED(k_ed_heads, ed_blocks(2 * E), TILE, a);
+        RLAP_LAUNCH_COUNTED(k_ed_degree, ed_blocks(N), TILE, a);
     }
     if (csr && scheme == PAGERANK) {
         double* x = a.c;   // (the iterate is the centrality)
-        ED_LAUNCH(k_ed_fill, ed_blocks(N), TILE, x, N, 1.0);
+        RLAP_LAUNCH_COUNTED(k_ed_fill, ed_blocks(N), TILE, x, N, 1.0);
         for (int64_t it = 0; it < g.pr_iters; ++it) {
-            ED_LAUNCH(k_ed_pr_share, ed_blocks(N), TILE, a, (const double*)x, B.y);
-            ED_LAUNCH(k_ed_pr_gather, ed_blocks(N * edgeplan::LANES), TILE, a, x, (const double*)B.y, g.damp);
+            RLAP_LAUNCH_COUNTED(k_ed_pr_share, ed_blocks(N), TILE, a, (const double*)x, B.y);
+            RLAP_LAUNCH_COUNTED(k_ed_pr_gather, ed_blocks(N * edgeplan::LANES), TILE, a, x, (const double*)B.y, g.damp);
         }
     }
     if (csr && scheme == EIGENVECTOR) {
-        ED_LAUNCH(k_ed_fill, ed_blocks(N), TILE, B.x, N, evc_start(N));
+        RLAP_LAUNCH_COUNTED(k_ed_fill, ed_blocks(N), TILE, B.x, N, evc_start(N));
         for (int64_t it = 0; it < g.evc_max_iter; ++it) {
-            ED_LAUNCH(k_ed_evc_gather, (unsigned)nt, TILE, a);
-            ED_LAUNCH(k_ed_evc_norm, (unsigned)nt, TILE, a);
-            ED_LAUNCH(k_ed_evc_check, 1, TILE, a, g.evc_tol);
+            RLAP_LAUNCH_COUNTED(k_ed_evc_gather, (unsigned)nt, TILE, a);
+            RLAP_LAUNCH_COUNTED(k_ed_evc_norm, (unsigned)nt, TILE, a);
+            RLAP_LAUNCH_COUNTED(k_ed_evc_check, 1, TILE, a, g.evc_tol);
         }
-        ED_LAUNCH(k_ed_evc_finish, ed_blocks(N), TILE, a);
+        RLAP_LAUNCH_COUNTED(k_ed_evc_finish, ed_blocks(N), TILE, a);
     }
     // 3. the scores
     if (scored) {
-        ED_LAUNCH(k_ed_score_s, (unsigned)nt, TILE, a);
-        ED_LAUNCH(k_ed_score_w, (unsigned)nt, TILE, a);
-        ED_LAUNCH(k_ed_score_nw, (unsigned)nt, TILE, a);
+        RLAP_LAUNCH_COUNTED(k_ed_score_s, (unsigned)nt, TILE, a);
+        RLAP_LAUNCH_COUNTED(k_ed_score_w, (unsigned)nt, TILE, a);
+        RLAP_LAUNCH_COUNTED(k_ed_score_nw, (unsigned)nt, TILE, a);
     }
     // 4. flip and compact
-    Flip f{};
-    f.src = g.src; f.dst = g.dst; f.w = g.w; f.E = E; f.N = N; f.nT = nT;
-    f.uniform = scheme == UNIFORM ? 1 : 0; f.source = g.source; f.K = K;
-    f.nw = a.nw;
-    for (int k = 0; k < K; ++k) f.p[k] = g.p[k];
-    f.threshold = g.threshold; f.seed = g.seed;
-    f.words = B.words; f.counts = B.counts; f.offs = B.offs;
-    f.rows = g.rows; f.cap = g.cap; f.ptr = g.ptr; f.mask = g.mask;
-    RLAP_HIPCHK(hipMemsetAsync(B.counts, 0, sizeof(int32_t) * (size_t)((int64_t)K * nT + 1), st));
-    if (nT > 0) ED_LAUNCH(k_ed_count, (unsigned)nT, TILE, f);
-    size_t cb = B.scan_bytes;
-    RLAP_HIPCHK(rocprim::exclusive_scan(B.scan_tmp, cb, B.counts, B.offs, (int64_t)0, (size_t)((int64_t)K * nT + 1), rocprim::plus<int64_t>(), st));
-    ED_LAUNCH(k_ed_ptr, 1, WAVE, f, B.words);
-    if (nT > 0) ED_LAUNCH(k_ed_write, (unsigned)nT, TILE, f);
-#undef ED_LAUNCH
+    DropCoin p{};
+    p.uniform = scheme == UNIFORM ? 1 : 0; p.source = g.source; p.N = N; p.nw = a.nw;
+    for (int k = 0; k < K; ++k) p.p[k] = g.p[k];
+    p.threshold = g.threshold; p.seed = g.seed;
+    const rowcompact::Rows c{g.src, g.dst, g.w, E, nT, K, B.words + W_ERR, B.compact.counts, B.compact.offs, g.rows, g.cap, g.ptr, g.mask,
+                             reinterpret_cast<int64_t*>(B.words) + W_TOTAL64};
+    if (const int rc = rowcompact::run(st, c, p, B.compact, nT > 0, launches)) return rc;
     // 5. the error word, the iteration report and the total, read back once
     int64_t hw[W_WORDS64];
     RLAP_HIPCHK(hipMemcpyAsync(hw, B.words, sizeof(hw), hipMemcpyDeviceToHost, st));

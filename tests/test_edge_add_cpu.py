@@ -490,6 +490,7 @@ def test_export_in_header_exports_makefile_and_the_checked_call_path():
     assert "hipMalloc" not in src and "asm" not in src and not re.search(r"atomic\w*\([^;]*(double|float)", src)
     assert src.count("hipStreamSynchronize(") == 2                                      # one in the coalesced path, one in the plain one
     assert '#include "rlap_edgeadd.h"' in src and '#include "rlap_edgeadd.h"' in open(edgeadd_mirror.SRC).read()   # one set of rules
+    assert '#include "rlap_rowcompact_dev.h"' in src and "#define" not in src           # the launch macro, clamp, store_row, scan_tmp_bytes: the shared ones
     mk = open(os.path.join(INC, "Makefile")).read()
     assert "rlap_edgeadd.o" in mk and "rlap_edgeadd.h" in mk and "-ffp-contract=off" in mk and "fast-math" not in mk
     import inspect

@@ -571,8 +571,13 @@ def test_export_in_header_exports_makefile_and_the_checked_call_path():
     src = open(os.path.join(INC, "rlap_edgedrop.hip")).read()
     assert "hipMalloc" not in src and src.count("hipStreamSynchronize(") == 1 and "asm" not in src   # scratch from the arena; one synchronisation
     assert not re.search(r"atomic\w*\([^;]*(double|float)", src)
+    shared = open(os.path.join(INC, "rlap_rowcompact_dev.h")).read()                    # the compaction and the list builder: the same of them
+    assert "hipMalloc" not in shared and "hipStreamSynchronize(" not in shared and "asm" not in shared
+    assert not re.search(r"atomic\w*\([^;]*(double|float)", shared)
+    assert '#include "rlap_rowcompact_dev.h"' in src and "struct Flip" not in src and not re.search(r"void k_\w+_(count|write)\b", src)
     mk = open(os.path.join(INC, "Makefile")).read()
     assert "rlap_edgedrop.o" in mk and "rlap_edgedrop.h" in mk and "-ffp-contract=off" in mk and "fast-math" not in mk
+    assert "rlap_rowcompact_dev.h" in mk
     import inspect
     from rlap_amd import ops
     assert '_device_call("rlap_edge_drop"' in inspect.getsource(ops.drop_edges)

@@ -65,7 +65,7 @@ def bits(a):
 
 @pytest.mark.parametrize("scheme", cases.SCHEMES)
 def test_edge_drop(ops, drop_mirror, large, scheme):
-    """k_ed_keys over E rows; degree: k_ed_heads over 2 E keys, k_ed_degree over N; pagerank and eigenvector: k_ed_bounds over E,
+    """k_ed_keys over E rows; degree: k_ed_heads over 2 E keys, k_ed_degree over N; pagerank and eigenvector: k_rc_bounds over E,
     k_ed_fill, k_ed_pr_share, k_ed_evc_finish over N, k_ed_pr_gather over 16 N lanes; wg_total over 8,194 partials: 33 trips."""
     src, dst, n, _ = large
     E = src.size
@@ -95,7 +95,7 @@ def test_node_sample_drop(ops, sample_mirror, large):
 
 
 def test_node_sample_walk(ops, sample_mirror, large):
-    """k_ns_keys and k_ns_bounds over E rows; k_ns_walk over E + 3 walkers; k_ns_mask over K N bytes."""
+    """k_ns_keys and k_rc_bounds over E rows; k_ns_walk over E + 3 walkers; k_ns_mask over K N bytes."""
     src, dst, n, ei = large
     E = src.size
     kw = dict(scheme="walk", num_seeds=[E, 3], walk_length=1, seed=sample_cases.SEED)

@@ -80,11 +80,13 @@ def test_result_equals_the_mirror(env, handle, scheme, name):
 
 def test_refusals(env, handle):
     E, n = env["src"].size, env["n"]
-    full = call(env, handle)[1].rows_needed
-    assert 0 < full < 2 * E
-    # too little room: nothing written, the needed rows reported
+    _, fit_info, fit = call(env, handle)
+    full = fit_info.rows_needed
+    assert 0 < full < 2 * E and int(fit["mask"].max()) <= 1
+    # too little room: no row written, the needed rows reported; the edge mask is written all the same (the same seed, the same coins)
     rc, info, b = call(env, handle, cap=full - 1)
     assert rc == OUT_CAPACITY and info.rows_needed == full and info.host_syncs == 1 and bool((b["rows"] == -7.0).all())
+    assert torch.equal(b["mask"], fit["mask"])
     rc, info, b = call(env, handle, cap=0)
     assert rc == OUT_CAPACITY and info.rows_needed == full
     rc, info, b = call(env, handle, cap=full)

@@ -542,6 +542,11 @@ def test_export_in_header_exports_makefile_and_the_checked_call_path():
     assert "hipMalloc" not in src and src.count("hipStreamSynchronize(") == 1 and "asm" not in src   # scratch from the arena; one synchronisation
     assert not re.search(r"atomic\w*\([^;]*(double|float)", src)
     assert '#include "rlap_nodesample.h"' in src and '#include "rlap_nodesample.h"' in open(nodesample_mirror.SRC).read()   # one set of rules
+    shared = open(os.path.join(INC, "rlap_rowcompact_dev.h")).read()                    # the compaction and the list builder: the same of them
+    assert "hipMalloc" not in shared and "hipStreamSynchronize(" not in shared and "asm" not in shared
+    assert not re.search(r"atomic\w*\([^;]*(double|float)", shared)
+    assert '#include "rlap_rowcompact_dev.h"' in src and "struct Flip" not in src and not re.search(r"void k_\w+_(count|write)\b", src)
+    assert "rowcompact" not in open(nodesample_mirror.SRC).read() and "rowcompact" not in open(os.path.join(INC, "rlap_nodesample.h")).read()
     mk = open(os.path.join(INC, "Makefile")).read()
     assert "rlap_nodesample.o" in mk and "rlap_nodesample.h" in mk and "-ffp-contract=off" in mk and "fast-math" not in mk
     import inspect

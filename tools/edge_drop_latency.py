@@ -6,7 +6,7 @@ eigenvector scheme it runs the same power iteration in torch (one .item() a step
 with --float64-too in float64 beside it), since networkx is not assumed.  Medians of 5 after a warm-up, host clock around a
 synchronise; the five times are printed too.  Prints one JSON line per (graph, scheme) (and appends it to --out).  `flip_bytes` is what the flip-and-compact kernels must move at least: the ids (and
 weights) of every row read once, 24 bytes written per kept row; their own times come from a kernel trace of a --no-torch run
-(k_ed_count + k_ed_write) and are set against 8 TB/s in DESIGN 4.20.  Needs an MI355X; reads nothing outside the repository.
+(k_rc_count<DropCoin> + k_rc_write<DropCoin>) and are set against 8 TB/s in DESIGN 4.20.  Needs an MI355X; reads nothing outside the repository.
 
     python tools/edge_drop_latency.py
     python tools/edge_drop_latency.py --graphs ba --schemes uniform,degree --no-torch   # the calls alone (for a kernel trace)

@@ -6,8 +6,8 @@ gather; RWSampling builds a CSR with sort, takes walk_length steps `col[rowptr[c
 without outgoing rows stays), marks the visited nodes and filters as subgraph does -- torch_sparse and torch_cluster are not
 assumed.  Medians of 5 after a warm-up, host clock around a synchronise; the five times are printed too.  Prints one JSON line per
 (graph, scheme) (and appends it to --out).  `flip_bytes` is what the flip-and-compact kernels must move at least: the two ids of
-every row read once, 24 bytes written per kept row; their own times come from a kernel trace of a --no-torch run (k_ns_count +
-k_ns_write) and are set against 8 TB/s in DESIGN 4.21; `walker_steps` over k_ns_walk's time is the walk kernel's rate.  Needs an
+every row read once, 24 bytes written per kept row; their own times come from a kernel trace of a --no-torch run (k_rc_count +
+k_rc_write, of the predicate NodeCoins for drop and InWalk for walk) and are set against 8 TB/s in DESIGN 4.21; `walker_steps` over k_ns_walk's time is the walk kernel's rate.  Needs an
 MI355X; reads nothing outside the repository.
 
     python tools/node_sample_latency.py
