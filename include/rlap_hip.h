@@ -869,6 +869,46 @@ int rlap_cca_loss_backward(rlap_handle h, const float* d_a, const float* d_b, in
                            const double* d_colstat, const float* d_gram, const double* d_g, float* d_ga, float* d_gb,
                            rlap_cca_info* h_info);
 
+/* The fused Barlow Twins loss of two views' node embeddings, forward and backward: the published bt_loss of PyGCL's
+ * L.BarlowTwins, restated (the package is not pinned).  With z = (h - mean_0(h)) / (std_0(h) + eps) (unbiased) and
+ * c = z1^T z2 / N:  loss = sum_k (1 - c_kk)^2 + lambd * sum_{k != l} c_kl^2.
+ *   d_a, d_b, N, F : the two views' embeddings, (N, F) float32 row-major; N >= 2, 1 <= F <= 512
+ *   lambd          : the weight of the off-diagonal term, finite and >= 0
+ *   eps            : added to the deviations, finite and >= 0
+ *   flags          : RLAP_BT_NO_STANDARDIZE: z = h; no statistics are taken, d_colstat is neither written nor read (NULL is legal)
+ *   forward        : d_terms three doubles: loss, on = sum_k (1 - c_kk)^2, off = sum_{k != l} c_kl^2; d_colstat [4 F] doubles: the
+ *                    column means of d_a, their deviations, the means of d_b, their deviations; d_cross [F F] float32: c, row-major
+ *                    (rows: the columns of d_a), rounded from float64.  The backward call reads d_colstat and d_cross.
+ *   backward       : d_colstat, d_cross as the forward call left them; d_g the upstream gradient, one double ON THE DEVICE (so that
+ *                    no synchronisation is needed); d_ga, d_gb (N, F) float32, the gradients with respect to d_a and d_b
+ *   h_info         : (nullable) what the call did
+ * Every value and the order of every sum are defined in rlap_amd/csrc/rlap_bt.h: the column statistics as in rlap_cca_loss; the
+ * full, non-symmetric cross sums as float32 fmaf chains over the nodes in increasing order (what the f32 matrix-core instruction
+ * computes), per part of the rows, the parts a function of (N, F) alone and added in float64; the terms summed by the chunk rule of
+ * rlap_amd/csrc/rlap_spmm.h.  The backward call standardises again and does not repeat the cross product.  So the same input gives
+ * the same bits, whatever the arena held; no atomic touches a floating-point value; neither call synchronises with the host.
+ * Nothing is clamped: a column of zero variance has z = +0 when eps > 0 -- the loss is finite and that column of its gradient is
+ * NaN -- and with eps = 0 its z is NaN, as in rlap_cca_loss: the terms, that column and the other view's whole gradient are NaN; the
+ * status is RLAP_OK either way.  A null pointer, N < 2, F < 1,
+ * F > 512, a lambd or an eps that is negative or not finite, or an unknown flag: RLAP_E_BAD_ARG.  N >= 2^31: RLAP_E_TOO_LARGE.
+ * Scratch from the arena (RLAP_E_WORKSPACE when a caller-provided one is too small, the workspace-needed query saying how much). */
+enum { RLAP_BT_NO_STANDARDIZE = 1 };
+
+typedef struct {
+    int64_t rows;             /* N                                                                    */
+    int64_t features;         /* F                                                                    */
+    int64_t parts;            /* contiguous parts the rows are dealt into: a function of (N, F)       */
+    int64_t arena_bytes;      /* scratch bytes of the call                                            */
+    int32_t host_syncs;       /* host synchronisations of the call: 0                                 */
+    int32_t pad;
+} rlap_bt_info;
+
+int rlap_bt_loss(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double lambd, double eps, int flags,
+                 double* d_terms, double* d_colstat, float* d_cross, rlap_bt_info* h_info);
+int rlap_bt_loss_backward(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double lambd, double eps, int flags,
+                          const double* d_colstat, const float* d_cross, const double* d_g, float* d_ga, float* d_gb,
+                          rlap_bt_info* h_info);
+
 /* The fused graph-to-local losses of node embeddings against graph summaries, forward and backward: one direction of
  * DualBranchContrast(JSD(), mode="G2L") and of BootstrapContrast(BootstrapLatent(), mode="G2L"), without the concatenated copy,
  * the dense (G, N) masks and the dense similarity matrix.  With s_ij = <h_i, g_j> and g(i) the graph of node i:

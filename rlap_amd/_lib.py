@@ -25,7 +25,7 @@ EXPORTS = [
     "rlap_graph_readout", "rlap_graph_readout_backward", "rlap_infonce", "rlap_infonce_backward",
     "rlap_infonce_pair", "rlap_infonce_pair_backward",
     "rlap_infonce_intra", "rlap_infonce_intra_backward", "rlap_infonce_pair_intra", "rlap_infonce_pair_intra_backward",
-    "rlap_cca_loss", "rlap_cca_loss_backward", "rlap_batch_norm", "rlap_batch_norm_backward",
+    "rlap_cca_loss", "rlap_cca_loss_backward", "rlap_bt_loss", "rlap_bt_loss_backward", "rlap_batch_norm", "rlap_batch_norm_backward",
     "rlap_g2l_jsd", "rlap_g2l_jsd_backward", "rlap_g2l_bootstrap", "rlap_g2l_bootstrap_backward",
     "rlap_linear_probe", "rlap_probe_scores", "rlap_edge_drop", "rlap_node_sample", "rlap_edge_add", "rlap_snapshot_markov",
     "rlap_feature_count", "rlap_feature_plan_bytes", "rlap_feature_plan_build", "rlap_feature_plan_apply",
@@ -231,6 +231,14 @@ class CcaInfo(_Report):
     ]
 
 
+class BtInfo(_Report):
+    """rlap_bt_info (include/rlap_hip.h)."""
+    _fields_ = [
+        ("rows", ctypes.c_int64), ("features", ctypes.c_int64), ("parts", ctypes.c_int64), ("arena_bytes", ctypes.c_int64),
+        ("host_syncs", ctypes.c_int32), ("pad", ctypes.c_int32),
+    ]
+
+
 class NormInfo(_Report):
     """rlap_norm_info (include/rlap_hip.h)."""
     _fields_ = [
@@ -374,6 +382,10 @@ def load():
     lib.rlap_cca_loss.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ci, vp, vp, vp, ctypes.POINTER(CcaInfo)]
     lib.rlap_cca_loss_backward.restype = ci
     lib.rlap_cca_loss_backward.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ci, vp, vp, vp, vp, vp, ctypes.POINTER(CcaInfo)]
+    lib.rlap_bt_loss.restype = ci
+    lib.rlap_bt_loss.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ctypes.c_double, ci, vp, vp, vp, ctypes.POINTER(BtInfo)]
+    lib.rlap_bt_loss_backward.restype = ci
+    lib.rlap_bt_loss_backward.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ctypes.c_double, ci, vp, vp, vp, vp, vp, ctypes.POINTER(BtInfo)]
     lib.rlap_batch_norm.restype = ci
     lib.rlap_batch_norm.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, ctypes.c_double, ctypes.c_double, ci, vp, vp,
                                     ctypes.POINTER(NormInfo)]

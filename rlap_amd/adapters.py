@@ -22,6 +22,8 @@ Mirrors of the reference's L2 adapters that keep everything on the GPU:
                   mode="L2L")) on the embeddings of two views, fused on the device (ops.info_nce)
   * `CCAContrast` -- the loss of CCA-SSG/main.py on the embeddings of two views, fused on the device (ops.cca_loss);
                   `drop_feature` -- CCA-SSG/aug.py's feature masking (also A.FeatureMasking), one mask per view
+  * `BarlowTwinsContrast` -- PyGCL's WithinEmbedContrast(L.BarlowTwins()) on the embeddings of two views, fused on the device
+                  (ops.barlow_twins_loss)
   * `SnapshotBatchNorm` -- BatchNorm1d for all views of a call at once, each view with its own statistics, the activations around
                   it fused in (ops.batch_norm); `SnapshotGINEncoder` -- scripts/graph_shared.py's GConv on a `Snapshots`: GIN layer,
                   relu + norm, readout, per layer
@@ -386,6 +388,27 @@ class CCAContrast(torch.nn.Module):
                 raise ValueError("CCAContrast: two (N, F) embeddings, or one (L, N, F) tensor of L >= 2 views")
             h1, h2 = h1[0], h1[1]
         return ops.cca_loss(h1, h2, lambd=self.lambd)
+
+
+class BarlowTwinsContrast(torch.nn.Module):
+    """PyGCL's WithinEmbedContrast(L.BarlowTwins()), the G-BT baseline: forward(h1, h2) = ops.barlow_twins_loss(h1, h2, lambd, eps),
+    the standardisation included.  h1, h2 are (N, F) float32 embeddings of two views; given one (L, N, F) tensor of L >= 2 views, as
+    SnapshotGCNConv returns it, forward(h) takes view 0 against view 1.  lambd=None means 1 / F.  WithinEmbedContrast averages
+    loss(h1, h2) and loss(h2, h1); the cross-correlation of the swapped call is the transpose of the first's, and the loss sums the
+    same diagonal and the same off-diagonal squares, so the two are one value and this module makes ONE call.  The loss is a 0-dim
+    float64 tensor; gradients reach both views."""
+
+    def __init__(self, lambd: Optional[float] = None, eps: float = 1e-15):
+        super().__init__()
+        self.lambd = lambd
+        self.eps = eps
+
+    def forward(self, h1, h2=None):
+        if h2 is None:
+            if not isinstance(h1, torch.Tensor) or h1.dim() != 3 or h1.shape[0] < 2:
+                raise ValueError("BarlowTwinsContrast: two (N, F) embeddings, or one (L, N, F) tensor of L >= 2 views")
+            h1, h2 = h1[0], h1[1]
+        return ops.barlow_twins_loss(h1, h2, lambd=self.lambd, eps=self.eps)
 
 
 def _view_pair(x, y, what: str, name: str):

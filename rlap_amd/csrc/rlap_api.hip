@@ -40,6 +40,8 @@
 #include "rlap_g2l_api.h"
 #include "rlap_cca.h"
 #include "rlap_cca_api.h"
+#include "rlap_bt.h"
+#include "rlap_bt_api.h"
 #include "rlap_norm.h"
 #include "rlap_norm_api.h"
 #include "rlap_probe.h"
@@ -1981,6 +1983,44 @@ int rlap_cca_loss_backward(rlap_handle h, const float* d_a, const float* d_b, in
     a.a = d_a; a.b = d_b; a.N = N; a.F = F; a.lambd = lambd; a.colstat_in = d_colstat; a.gram_in = d_gram; a.g = d_g; a.ga = d_ga; a.gb = d_gb;
     return poisoned_call(h, [&] { return cca_backward_bytes(N, F); }, {{d_ga, (size_t)(N * F) * 4}, {d_gb, (size_t)(N * F) * 4}},
                          h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) { return cca_backward_run(h->stream, base, have, a); });
+}
+
+static_assert(RLAP_BT_NO_STANDARDIZE == bt::NO_STANDARDIZE, "the header's flag is the rule's");
+
+namespace {
+
+// what both Barlow Twins exports check (their pointers come before this)
+int bt_check(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double lambd, double eps, int flags, rlap_bt_info* h_info) {
+    if (h_info) *h_info = rlap_bt_info{};
+    if (!h || !d_a || !d_b || N < 2 || F < 1 || F > bt::MAX_F || !bt::lambd_ok(lambd) || !bt::eps_ok(eps) || !bt::flags_ok(flags)) return RLAP_E_BAD_ARG;
+    if (N >= (int64_t)1 << 31) return RLAP_E_TOO_LARGE;
+    if (h_info) { h_info->rows = N; h_info->features = F; h_info->parts = bt::num_parts(N, F); }
+    return RLAP_OK;
+}
+
+}  // namespace
+
+int rlap_bt_loss(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double lambd, double eps, int flags,
+                 double* d_terms, double* d_colstat, float* d_cross, rlap_bt_info* h_info) {
+    if (const int rc = bt_check(h, d_a, d_b, N, F, lambd, eps, flags, h_info)) return rc;
+    const bool plain = (flags & bt::NO_STANDARDIZE) != 0;
+    if (!d_terms || (!d_colstat && !plain) || !d_cross) return RLAP_E_BAD_ARG;
+    BtArgs a{};
+    a.a = d_a; a.b = d_b; a.N = N; a.F = F; a.lambd = lambd; a.eps = eps; a.flags = flags; a.terms = d_terms; a.colstat = d_colstat; a.cross = d_cross;
+    return poisoned_call(h, [&] { return bt_bytes(N, F); }, {{d_terms, 3 * 8}, {plain ? nullptr : d_colstat, (size_t)(4 * F) * 8}, {d_cross, (size_t)(F * F) * 4}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) { return bt_run(h->stream, base, have, a); });
+}
+
+int rlap_bt_loss_backward(rlap_handle h, const float* d_a, const float* d_b, int64_t N, int64_t F, double lambd, double eps, int flags,
+                          const double* d_colstat, const float* d_cross, const double* d_g, float* d_ga, float* d_gb,
+                          rlap_bt_info* h_info) {
+    if (const int rc = bt_check(h, d_a, d_b, N, F, lambd, eps, flags, h_info)) return rc;
+    if ((!d_colstat && !(flags & bt::NO_STANDARDIZE)) || !d_cross || !d_g || !d_ga || !d_gb) return RLAP_E_BAD_ARG;
+    BtArgs a{};
+    a.a = d_a; a.b = d_b; a.N = N; a.F = F; a.lambd = lambd; a.eps = eps; a.flags = flags; a.colstat_in = d_colstat; a.cross_in = d_cross;
+    a.g = d_g; a.ga = d_ga; a.gb = d_gb;
+    return poisoned_call(h, [&] { return bt_backward_bytes(N, F); }, {{d_ga, (size_t)(N * F) * 4}, {d_gb, (size_t)(N * F) * 4}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) { return bt_backward_run(h->stream, base, have, a); });
 }
 
 namespace {

@@ -1626,6 +1626,120 @@ def cca_loss(h1: Tensor, h2: Tensor, lambd: float = 1e-3, return_terms: bool = F
     return (loss, parts[0], parts[1], parts[2]) if return_terms else loss
 
 
+BT_MAX_F = 512
+BT_NO_STANDARDIZE = 1   # RLAP_BT_NO_STANDARDIZE
+
+
+def _bt_number(x, what: str) -> float:
+    if isinstance(x, bool) or not isinstance(x, (int, float)):
+        raise ValueError(f"{what}: a number, got {x!r}")
+    x = float(x)
+    if not (0.0 <= x < float("inf")):
+        raise ValueError(f"{what}: finite and >= 0, got {x!r}")
+    return x
+
+
+def _bt_args(h1, h2, lambd, eps, standardize):
+    """Host-side checks of barlow_twins_loss, made before the device is touched: (lambd, eps) as floats and the flags."""
+    for t, what in ((h1, "h1"), (h2, "h2")):
+        if not isinstance(t, Tensor) or t.dim() != 2:
+            raise ValueError(f"{what}: a (num_nodes, F) tensor")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: torch.float32, got {t.dtype}")
+    if h1.shape != h2.shape:
+        raise ValueError(f"h1 and h2: equal shapes, got {tuple(h1.shape)} and {tuple(h2.shape)}")
+    if h1.device != h2.device:
+        raise ValueError(f"h1 and h2: one device, got {h1.device} and {h2.device}")
+    n, f = int(h1.shape[0]), int(h1.shape[1])
+    if n < 2:
+        raise ValueError("h1: at least two rows (the unbiased deviation divides by N - 1)")
+    if f < 1:
+        raise ValueError("h1: at least one feature column")
+    if f > BT_MAX_F:
+        raise ValueError(f"h1: at most {BT_MAX_F} feature columns, got {f}")
+    if n >= 1 << 31:
+        raise ValueError("h1: fewer than 2^31 rows")
+    if not isinstance(standardize, bool):
+        raise ValueError(f"standardize: a bool, got {standardize!r}")
+    lambd = 1.0 / f if lambd is None else _bt_number(lambd, "lambd")
+    return lambd, _bt_number(eps, "eps"), 0 if standardize else BT_NO_STANDARDIZE
+
+
+def _bt_forward(a: Tensor, b: Tensor, lambd: float, eps: float, flags: int):
+    """The forward export: (terms [3] float64: loss, on, off; colstat [4 F] float64, left as allocated without the standardisation;
+    cross (F, F) float32; the device copies of a and b)."""
+    dev = _device_for(a)
+    with torch.cuda.device(dev):
+        d_a = a.detach().to(device=dev).contiguous()
+        d_b = b.detach().to(device=dev).contiguous()
+        n, f = int(d_a.shape[0]), int(d_a.shape[1])
+        out = torch.empty(4 + 4 * f, dtype=torch.float64, device=dev)   # terms (three of four slots) | colstat
+        cross = torch.empty((f, f), dtype=torch.float32, device=dev)
+        p = out.data_ptr()
+        _device_call("rlap_bt_loss", _lib.BtInfo, dev, 1, (d_a.data_ptr(), d_b.data_ptr(), n, f, lambd, eps, flags, p, p + 32, cross.data_ptr()))
+    return out[:3], out[4:], cross, d_a, d_b
+
+
+class _BtLoss(torch.autograd.Function):
+    """terms = the fused Barlow Twins loss of (h1, h2) and its two parts; the gradients of the loss with respect to both inputs come
+    from the backward export, which reads the forward's column statistics and cross-correlation matrix."""
+
+    @staticmethod
+    def forward(ctx, a, b, lambd, eps, flags):
+        terms, colstat, cross, d_a, d_b = _bt_forward(a, b, lambd, eps, flags)
+        ctx.save_for_backward(d_a, d_b, colstat, cross)
+        ctx.call = (lambd, eps, flags, a.device, b.device)
+        parts = terms[1:].clone()
+        ctx.mark_non_differentiable(parts)
+        return terms[0], parts
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_parts):
+        d_a, d_b, colstat, cross = ctx.saved_tensors
+        lambd, eps, flags, dev_a, dev_b = ctx.call
+        dev = d_a.device
+        with torch.cuda.device(dev):
+            d_g = _upstream(g, dev)
+            n, f = int(d_a.shape[0]), int(d_a.shape[1])
+            ga = torch.empty_like(d_a)
+            gb = torch.empty_like(d_b)
+            _device_call("rlap_bt_loss_backward", _lib.BtInfo, dev, 1, (
+                d_a.data_ptr(), d_b.data_ptr(), n, f, lambd, eps, flags, colstat.data_ptr(), cross.data_ptr(), d_g.data_ptr(), ga.data_ptr(),
+                gb.data_ptr()))
+        return ga.to(dev_a), gb.to(dev_b), None, None, None
+
+
+def barlow_twins_loss(h1: Tensor, h2: Tensor, lambd: Optional[float] = None, eps: float = 1e-15, standardize: bool = True,
+                      return_terms: bool = False):
+    """The Barlow Twins loss of two views' node embeddings, fused on the device (rlap_bt_loss): with
+    z = (h - h.mean(0)) / (h.std(0) + eps) and c = z1^T z2 / N,
+    loss = sum_k (1 - c_kk)^2 + lambd * sum_{k != l} c_kl^2 -- the published bt_loss of PyGCL's L.BarlowTwins (the G-BT baseline),
+    restated: the package is not pinned here.
+
+      h1, h2       : (N, F) float32 of equal shape on one device (moved to the library's), N >= 2, F <= 512
+      lambd        : the weight of the off-diagonal term, finite and >= 0; None means 1 / F
+      eps          : added to the deviations, finite and >= 0
+      standardize  : False takes h1 and h2 as they are (z = h)
+      return_terms : return (loss, on, off), 0-dim float64 each: on = sum_k (1 - c_kk)^2, off = sum_{k != l} c_kl^2 (not differentiable)
+    Returns the 0-dim float64 loss.  Every value and the order of every sum are fixed (rlap_amd/csrc/rlap_bt.h): the same input
+    gives the same bits.  Nothing is clamped: a column of zero variance gives z = 0 and NaN in that column of the gradient (with
+    eps = 0 a NaN loss and NaN throughout the other view's gradient too).
+
+    Differentiable in both inputs (rlap_bt_loss_backward standardises again and reads the forward's column statistics and
+    cross-correlation matrix, it does not repeat the cross product); double backward is not supported.  Malformed arguments raise
+    ValueError before the device is touched.  No host synchronisation.  `last_stats` then holds what the call did
+    (rlap_bt_info: rows, features, parts, arena_bytes, host_syncs).
+    """
+    lambd, eps, flags = _bt_args(h1, h2, lambd, eps, standardize)
+    if torch.is_grad_enabled() and (h1.requires_grad or h2.requires_grad):
+        loss, parts = _BtLoss.apply(h1, h2, lambd, eps, flags)
+    else:
+        terms = _bt_forward(h1, h2, lambd, eps, flags)[0]
+        loss, parts = terms[0], terms[1:]
+    return (loss, parts[0], parts[1]) if return_terms else loss
+
+
 NORM_MAX_F = _lib.NORM_MAX_F
 NORM_PRE = {"none": 0, "relu": _lib.NORM_PRE_RELU}
 NORM_POST = {"none": 0, "relu": _lib.NORM_POST_RELU, "prelu": _lib.NORM_POST_PRELU}
