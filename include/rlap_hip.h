@@ -1061,6 +1061,66 @@ int rlap_batch_norm_backward(rlap_handle h, const float* d_x, const float* d_gy,
                     int flags, const double* d_stat, float* d_gx, float* d_gweight, float* d_gbias, float* d_gslope,
                     rlap_norm_info* h_info);
 
+/* Fused bias, activation and dropout, forward and backward: y = dropout(act(x + bias), p) on every element of d_x
+ * (L, N, F) in one pass -- what the reference's encoders run behind every GCN and GIN layer as three torch passes.  No mask is
+ * stored: the dropout coin is a function of (seed, layer, row, column, F, p) alone and the backward call draws it again.
+ *   d_x, L, N, F   : (L, N, F) float32 row-major; L >= 1, N >= 1, 1 <= F <= 4096
+ *   d_bias         : (nullable) (F) float32; a null pointer means 0
+ *   d_slope        : the PReLU slope, one float32 or (RLAP_ROW_SLOPE_PER_CHANNEL) (F); required with RLAP_ROW_ACT_PRELU
+ *   p, seed        : the drop probability, 0 <= p < 1, used as T / 65536 with T = llrint(p * 65536) (at most 65535); what is kept is
+ *                    scaled by 1 / (1 - T / 65536).  Layer l of a call draws the coins of layer 0 of the call with seed + l.
+ *   flags          : at most one of RLAP_ROW_ACT_RELU / RLAP_ROW_ACT_PRELU; RLAP_ROW_SLOPE_PER_CHANNEL (with PReLU only);
+ *                    RLAP_ROW_TRAINING -- without it, or with T = 0, nothing is dropped and the call gives the bits of the call
+ *                    without dropout
+ *   d_y            : (L, N, F) float32; every element is written
+ *   h_info         : (nullable) what the call did
+ * Every value, the coin and the order of every sum are defined in rlap_amd/csrc/rlap_rowops.h: float64 throughout, every output
+ * rounded once to float32.  So the same input gives the same bits, and a layer's result does not depend on L, on the lane path or on
+ * what d_y or the arena held.  No atomic touches a floating-point value; neither call synchronises with the host.
+ * The backward call reads d_x and the upstream d_gy (L, N, F) with the forward call's p, seed and flags, and writes d_gx (L, N, F),
+ * d_gbias (F) and d_gslope (1, or F per channel; ignored without PReLU): the column sums by the chunk rule of rlap_spmm.h over the
+ * rows in order, the layers added in layer order (the single slope then over the columns in order).  A null gradient output is
+ * skipped; without d_gbias and d_gslope the call is one pass and takes no scratch.
+ * Both activation flags, PReLU without a slope, the per-channel flag without PReLU, p outside [0, 1) or not a number, F outside
+ * [1, 4096], L < 1, N < 1, a null d_x, d_y or d_gy, an unknown flag: RLAP_E_BAD_ARG before anything is launched.
+ * L * N * F >= 2^40: RLAP_E_TOO_LARGE.  Scratch from the arena (RLAP_E_WORKSPACE when a caller-provided one is too small, the
+ * workspace-needed query saying how much). */
+enum { RLAP_ROW_ACT_RELU = 1, RLAP_ROW_ACT_PRELU = 2, RLAP_ROW_SLOPE_PER_CHANNEL = 4, RLAP_ROW_TRAINING = 8 };
+typedef struct {
+    int64_t rows;             /* N                                                                    */
+    int64_t features;         /* F                                                                    */
+    int64_t layers;           /* L                                                                    */
+    int64_t chunks;           /* chunks of 256 rows a layer has                                       */
+    int64_t arena_bytes;      /* scratch bytes of the call                                            */
+    int32_t vec;              /* 1: 16 bytes a lane (F % 4 == 0, pointers on the 16-byte grid); 0: one element a lane */
+    int32_t launches;         /* kernels the call enqueued                                            */
+    int32_t instance;         /* layer norm: 16-byte steps a lane holds in registers (1, 2, 4, 8, 16); else 0 */
+    int32_t host_syncs;       /* host synchronisations of the call: 0                                 */
+} rlap_rowops_info;
+
+int rlap_bias_act_dropout(rlap_handle h, const float* d_x, int64_t L, int64_t N, int64_t F, const float* d_bias, const float* d_slope,
+                    double p, uint64_t seed, int flags, float* d_y, rlap_rowops_info* h_info);
+int rlap_bias_act_dropout_backward(rlap_handle h, const float* d_x, const float* d_gy, int64_t L, int64_t N, int64_t F,
+                    const float* d_bias, const float* d_slope, double p, uint64_t seed, int flags, float* d_gx, float* d_gbias,
+                    float* d_gslope, rlap_rowops_info* h_info);
+
+/* Per-row layer norm with a fused activation and dropout, forward and backward: every row of d_x (L, N, F) is
+ * normalised over its F columns (biased variance, as torch.nn.LayerNorm), then y = dropout(act(xh * weight + bias), p) in the same
+ * pass -- the other branch of the reference's Normalize, with the PReLU and the dropout that follow it.  A wave holds a row in
+ * registers; the row is read once and d_y written once.
+ *   d_weight, d_bias : (nullable) (F) float32; a null pointer means 1 and 0
+ *   eps            : > 0 and finite; a constant row gives 1 / sqrt(eps), no NaN
+ *   the other arguments, the flags, the coin and the refusals are rlap_bias_act_dropout's
+ * The row sums run in an order that depends on F alone (rlap_amd/csrc/rlap_rowops.h: row_sum), on either lane path.  Nothing but d_x
+ * is kept for the backward call, which forms mean and 1 / sqrt(var + eps) again from the row, writes d_gx and, where one of
+ * d_gweight (F), d_gbias (F), d_gslope is asked for, a second pass over d_x and d_gy for their column sums by the chunk rule (the
+ * rows' statistics go through the arena). */
+int rlap_layer_norm(rlap_handle h, const float* d_x, int64_t L, int64_t N, int64_t F, const float* d_weight, const float* d_bias,
+                    const float* d_slope, double eps, double p, uint64_t seed, int flags, float* d_y, rlap_rowops_info* h_info);
+int rlap_layer_norm_backward(rlap_handle h, const float* d_x, const float* d_gy, int64_t L, int64_t N, int64_t F, const float* d_weight,
+                    const float* d_bias, const float* d_slope, double eps, double p, uint64_t seed, int flags, float* d_gx,
+                    float* d_gweight, float* d_gbias, float* d_gslope, rlap_rowops_info* h_info);
+
 /* The op with the step BEFORE the path fused in (scripts/node_shared.py:326-327,
  * scripts/augmentor_benchmarks.py:77-78):
  *   symmetrize != 0 : the input holds every undirected edge in one or both directions; (b,a) is

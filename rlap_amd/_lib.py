@@ -29,6 +29,7 @@ EXPORTS = [
     "rlap_g2l_jsd", "rlap_g2l_jsd_backward", "rlap_g2l_bootstrap", "rlap_g2l_bootstrap_backward",
     "rlap_linear_probe", "rlap_probe_scores", "rlap_edge_drop", "rlap_node_sample", "rlap_edge_add", "rlap_snapshot_markov",
     "rlap_feature_count", "rlap_feature_plan_bytes", "rlap_feature_plan_build", "rlap_feature_plan_apply",
+    "rlap_bias_act_dropout", "rlap_bias_act_dropout_backward", "rlap_layer_norm", "rlap_layer_norm_backward",
 ]
 
 E_INDEX_RANGE = 2   # RLAP_E_INDEX_RANGE
@@ -73,6 +74,9 @@ INFONCE_INTRA_MASKED, INFONCE_INTRA_ALL = 1, 2
 # rlap_batch_norm flags and limits (rlap_amd/csrc/rlap_norm.h)
 NORM_PRE_RELU, NORM_POST_RELU, NORM_POST_PRELU, NORM_SLOPE_PER_CHANNEL, NORM_EVAL = 1, 2, 4, 8, 16
 NORM_MAX_F = 4096
+# rlap_bias_act_dropout flags and limits (rlap_amd/csrc/rlap_rowops.h)
+ROW_ACT_RELU, ROW_ACT_PRELU, ROW_SLOPE_PER_CHANNEL, ROW_TRAINING = 1, 2, 4, 8
+ROW_MAX_F = 4096
 # rlap_linear_probe select
 PROBE_SELECT_SCRIPTS, PROBE_SELECT_CCA = 0, 1
 
@@ -248,6 +252,15 @@ class NormInfo(_Report):
     ]
 
 
+class RowopsInfo(_Report):
+    """rlap_rowops_info (include/rlap_hip.h)."""
+    _fields_ = [
+        ("rows", ctypes.c_int64), ("features", ctypes.c_int64), ("layers", ctypes.c_int64), ("chunks", ctypes.c_int64),
+        ("arena_bytes", ctypes.c_int64), ("vec", ctypes.c_int32), ("launches", ctypes.c_int32), ("instance", ctypes.c_int32),
+        ("host_syncs", ctypes.c_int32),
+    ]
+
+
 class G2lInfo(_Report):
     """rlap_g2l_info (include/rlap_hip.h)."""
     _fields_ = [
@@ -392,6 +405,16 @@ def load():
     lib.rlap_batch_norm_backward.restype = ci
     lib.rlap_batch_norm_backward.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, ctypes.c_double, ci, vp, vp, vp, vp, vp,
                                              ctypes.POINTER(NormInfo)]
+    lib.rlap_bias_act_dropout.restype = ci
+    lib.rlap_bias_act_dropout.argtypes = [vp, vp, i64, i64, i64, vp, vp, ctypes.c_double, u64, ci, vp, ctypes.POINTER(RowopsInfo)]
+    lib.rlap_bias_act_dropout_backward.restype = ci
+    lib.rlap_bias_act_dropout_backward.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, ctypes.c_double, u64, ci, vp, vp, vp,
+                                                   ctypes.POINTER(RowopsInfo)]
+    lib.rlap_layer_norm.restype = ci
+    lib.rlap_layer_norm.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, ctypes.c_double, ctypes.c_double, u64, ci, vp, ctypes.POINTER(RowopsInfo)]
+    lib.rlap_layer_norm_backward.restype = ci
+    lib.rlap_layer_norm_backward.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, vp, ctypes.c_double, ctypes.c_double, u64, ci, vp, vp, vp, vp,
+                                             ctypes.POINTER(RowopsInfo)]
     lib.rlap_g2l_jsd.restype = ci
     lib.rlap_g2l_jsd.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, ci, vp, vp, ctypes.POINTER(G2lInfo)]
     lib.rlap_g2l_jsd_backward.restype = ci

@@ -182,13 +182,19 @@ class SnapshotGCNConv(torch.nn.Module):
 
     The first layer also takes an ops.FeaturePlan as x: forward(fp, snapshots, keep) = snapshots.propagate(fp.linear(W, keep)) + b,
     with `keep` None (every layer reads x @ W) or the (K, in_channels) masks of ops.feature_masks, one view per layer
-    (DESIGN 4.26); gradients then reach W and b."""
+    (DESIGN 4.26); gradients then reach W and b.
 
-    def __init__(self, in_channels: int, out_channels: int, bias: bool = True):
+    `epilogue`, a SnapshotActDropout, makes the layer return epilogue(propagate(x @ W), b): the bias add, the activation and the
+    dropout of scripts/node_shared.py's `GCNConv -> PReLU` in one fused pass.  Without it the layer is what it was."""
+
+    def __init__(self, in_channels: int, out_channels: int, bias: bool = True, epilogue=None):
         super().__init__()
         self.in_channels, self.out_channels = int(in_channels), int(out_channels)
         self.weight = torch.nn.Parameter(torch.empty(self.in_channels, self.out_channels))
         self.bias = torch.nn.Parameter(torch.empty(self.out_channels)) if bias else None
+        if epilogue is not None and not isinstance(epilogue, SnapshotActDropout):
+            raise ValueError("SnapshotGCNConv: epilogue is a SnapshotActDropout or None")
+        self.epilogue = epilogue
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -203,6 +209,8 @@ class SnapshotGCNConv(torch.nn.Module):
             raise ValueError("SnapshotGCNConv: keep goes with an ops.FeaturePlan as x (mask a tensor x with drop_feature)")
         else:
             y = snapshots.propagate(x @ self.weight)
+        if self.epilogue is not None:
+            return self.epilogue(y, self.bias)
         return y if self.bias is None else y + self.bias
 
 
@@ -336,6 +344,149 @@ class SnapshotGINEncoder(torch.nn.Module):
             zs.append(z)
         gs = [snapshots.readout(z) for z in zs]
         return torch.cat(zs, dim=-1), torch.cat(gs, dim=-1)
+
+
+class SnapshotActDropout(torch.nn.Module):
+    """activation -> dropout behind a layer, for all views of a call at once: forward(x, bias=None) = ops.bias_act_dropout on an
+    (L, N, F) tensor (or one (N, F) view) -- `conv -> PReLU -> F.dropout(p)` of scripts/graph_shared_g2l.py's GConv and
+    `GCNConv -> PReLU` of scripts/node_shared.py in one pass, the layer's bias added on the way where it is handed over.  `act` is
+    "none", "relu" or "prelu"; with "prelu" the slope is the parameter `weight` (`num_parameters` values, 0.25 at reset), as
+    torch.nn.PReLU names it, so a state dict moves across.  `.eval()` switches the dropout off.  Every training forward draws a
+    fresh seed from torch's generator unless an integer `seed` is given, which fixes the mask."""
+
+    def __init__(self, act: str = "prelu", p: float = 0.0, num_parameters: int = 1, seed: Optional[int] = None):
+        super().__init__()
+        if act not in ops.ROW_ACT:
+            raise ValueError(f"act: one of {sorted(ops.ROW_ACT)}")
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not (0.0 <= p < 1.0):
+            raise ValueError(f"p: a number in [0, 1), got {p!r}")
+        self.act, self.p, self.num_parameters, self.seed = act, float(p), int(num_parameters), seed
+        if act == "prelu":
+            self.weight = torch.nn.Parameter(torch.empty(self.num_parameters))
+        else:
+            self.register_parameter("weight", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        if self.weight is not None:
+            with torch.no_grad():
+                self.weight.fill_(0.25)
+
+    def forward(self, x, bias=None):
+        return ops.bias_act_dropout(x, bias, act=self.act, slope=self.weight, p=self.p, training=self.training, seed=self.seed)
+
+    def extra_repr(self):
+        return f"act={self.act!r}, p={self.p}, num_parameters={self.num_parameters}, seed={self.seed}"
+
+
+class SnapshotLayerNorm(torch.nn.Module):
+    """LayerNorm over the last dimension for all views of a call at once, with the activation and the dropout behind it fused in:
+    forward(x) = ops.layer_norm on an (L, N, F) tensor (or one (N, F) view) -- the "layer" branch of the reference's Normalize, and
+    with post="prelu" and p the `Normalize -> PReLU -> Dropout` of its projection head and predictor in one pass.  It restates
+    torch.nn.LayerNorm's published semantics for one normalised dimension -- parameter names `weight` and `bias`, ones and zeros at
+    reset, biased variance --, so a state dict moves across; with post="prelu" the module also carries the slope as the parameter
+    `slope` (one value, 0.25 at reset).  `.eval()` switches the dropout off; an integer `seed` fixes the mask."""
+
+    def __init__(self, num_features: int, eps: float = 1e-5, elementwise_affine: bool = True, post: str = "none", p: float = 0.0,
+                 seed: Optional[int] = None):
+        super().__init__()
+        if post not in ops.ROW_ACT:
+            raise ValueError(f"post: one of {sorted(ops.ROW_ACT)}")
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not (0.0 <= p < 1.0):
+            raise ValueError(f"p: a number in [0, 1), got {p!r}")
+        self.num_features, self.eps, self.elementwise_affine = int(num_features), eps, bool(elementwise_affine)
+        self.post, self.p, self.seed = post, float(p), seed
+        if self.elementwise_affine:
+            self.weight = torch.nn.Parameter(torch.empty(self.num_features))
+            self.bias = torch.nn.Parameter(torch.empty(self.num_features))
+        else:
+            self.register_parameter("weight", None)
+            self.register_parameter("bias", None)
+        if post == "prelu":
+            self.slope = torch.nn.Parameter(torch.empty(1))
+        else:
+            self.register_parameter("slope", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        with torch.no_grad():
+            if self.elementwise_affine:
+                self.weight.fill_(1.0)
+                self.bias.zero_()
+            if self.slope is not None:
+                self.slope.fill_(0.25)
+
+    def forward(self, x):
+        if not isinstance(x, torch.Tensor) or x.dim() not in (2, 3) or int(x.shape[-1]) != self.num_features:
+            raise ValueError(f"SnapshotLayerNorm: an (N, {self.num_features}) or (L, N, {self.num_features}) tensor")
+        return ops.layer_norm(x, self.weight, self.bias, eps=self.eps, post=self.post, slope=self.slope, p=self.p, training=self.training,
+                              seed=self.seed)
+
+    def extra_repr(self):
+        return f"{self.num_features}, eps={self.eps}, elementwise_affine={self.elementwise_affine}, post={self.post!r}, p={self.p}"
+
+
+class SnapshotG2LEncoder(torch.nn.Module):
+    """scripts/graph_shared_g2l.py's GConv for all views of a call at once: per layer SnapshotGINConv(Linear-ReLU-Linear) and the
+    shared epilogue `activation` (one PReLU slope for all layers, as GConv's, with the dropout fused in); behind the stack
+    `batch_norm`, a SnapshotBatchNorm or SnapshotLayerNorm as `encoder_norm` says ("batch", "layer" or "none"); then the projection
+    head Linear -> norm(post="prelu") -> dropout.  With "layer" the head's PReLU and dropout are part of the layer-norm call; behind
+    a batch norm, whose call is as it was, the dropout is an epilogue call of its own (`head_dropout`).  forward(x, snapshots) takes
+    x (n, input_dim), shared by the views, or (L, n, input_dim), and a `Snapshots` or its `.plan()`; it returns (z, projection),
+    both (L, n, hidden_dim).  An integer `seed` fixes every dropout mask (call c of a forward uses seed + 1000 c)."""
+
+    def __init__(self, input_dim: int, hidden_dim: int, num_layers: int, dropout: float = 0.2, encoder_norm: str = "batch",
+                 projector_norm: str = "batch", seed: Optional[int] = None):
+        super().__init__()
+        if num_layers < 1:
+            raise ValueError("num_layers: at least one")
+        for norm in (encoder_norm, projector_norm):
+            if norm not in ("batch", "layer", "none"):
+                raise ValueError('encoder_norm, projector_norm: "batch", "layer" or "none"')
+        sub = (lambda c: None) if seed is None else (lambda c: int(seed) + 1000 * c)
+        self.layers = torch.nn.ModuleList()
+        for i in range(num_layers):
+            d = input_dim if i == 0 else hidden_dim
+            self.layers.append(SnapshotGINConv(torch.nn.Sequential(torch.nn.Linear(d, hidden_dim), torch.nn.ReLU(), torch.nn.Linear(hidden_dim, hidden_dim))))
+        self.activation = SnapshotActDropout("prelu", dropout, seed=sub(0))
+        self.layer_seeds = None if seed is None else [int(seed) + 1000 * (2 + i) for i in range(num_layers)]
+        if encoder_norm == "batch":
+            self.batch_norm = SnapshotBatchNorm(hidden_dim)
+        elif encoder_norm == "layer":
+            self.batch_norm = SnapshotLayerNorm(hidden_dim)
+        else:
+            self.batch_norm = torch.nn.Identity()
+        self.head_linear = torch.nn.Linear(hidden_dim, hidden_dim)
+        if projector_norm == "batch":
+            self.head_norm = SnapshotBatchNorm(hidden_dim, post="prelu")
+            self.head_dropout = SnapshotActDropout("none", dropout, seed=sub(1))
+        elif projector_norm == "layer":
+            self.head_norm = SnapshotLayerNorm(hidden_dim, post="prelu", p=dropout, seed=sub(1))
+            self.head_dropout = torch.nn.Identity()
+        else:
+            self.head_norm = SnapshotActDropout("prelu", dropout, seed=sub(1))
+            self.head_dropout = torch.nn.Identity()
+
+    def forward(self, x, snapshots):
+        z = x
+        for i, conv in enumerate(self.layers):
+            z = conv(z, snapshots)
+            act = self.activation
+            z = ops.bias_act_dropout(z, None, act=act.act, slope=act.weight, p=act.p, training=self.training,
+                                     seed=None if self.layer_seeds is None else self.layer_seeds[i])
+        z = self.batch_norm(z)
+        return z, self.head_dropout(self.head_norm(self.head_linear(z)))
+
+
+def update_target(target: torch.nn.Module, online: torch.nn.Module, momentum: float) -> None:
+    """The bootstrap's moving average, p_target = momentum * p_target + (1 - momentum) * p_online over the parameters in order
+    (scripts/graph_shared_g2l.py: Encoder.update_target_encoder), in two torch._foreach calls.  A convenience, not a kernel."""
+    tp, op = [p.data for p in target.parameters()], [p.data for p in online.parameters()]
+    if len(tp) != len(op):
+        raise ValueError("update_target: the two modules differ in their parameters")
+    with torch.no_grad():
+        torch._foreach_mul_(tp, float(momentum))
+        torch._foreach_add_(tp, op, alpha=1.0 - float(momentum))
 
 
 class NodeContrast(torch.nn.Module):

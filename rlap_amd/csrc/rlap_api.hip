@@ -44,6 +44,8 @@
 #include "rlap_bt_api.h"
 #include "rlap_norm.h"
 #include "rlap_norm_api.h"
+#include "rlap_rowops.h"
+#include "rlap_rowops_api.h"
 #include "rlap_probe.h"
 #include "rlap_probe_api.h"
 
@@ -2208,6 +2210,94 @@ int rlap_batch_norm_backward(rlap_handle h, const float* d_x, const float* d_gy,
         NormReport rep{};
         const int rc = norm_backward_run(h->stream, base, have, a, &rep);
         if (rc == RLAP_OK) norm_report(h_info, rep);
+        return rc;
+    });
+}
+
+namespace {
+
+// what both row-pass exports check (their own pointers come behind this), and what the host knows of the call
+int rowops_check(rlap_handle h, const float* d_x, int64_t L, int64_t N, int64_t F, const float* d_slope, double p, int flags,
+                 rlap_rowops_info* h_info) {
+    if (h_info) *h_info = rlap_rowops_info{};
+    if (!h || !d_x || !rowops::args_ok(L, N, F, flags, d_slope != nullptr, p)) return RLAP_E_BAD_ARG;
+    if (L >= SPMM_MAX_ELEMS || N >= SPMM_MAX_ELEMS || L * N >= SPMM_MAX_ELEMS || L * N * F >= SPMM_MAX_ELEMS) return RLAP_E_TOO_LARGE;
+    if (h_info) { h_info->rows = N; h_info->features = F; h_info->layers = L; h_info->chunks = spmm::num_chunks(N); }
+    return RLAP_OK;
+}
+
+void rowops_report(rlap_rowops_info* h_info, const RowopsReport& rep) {
+    if (h_info) { h_info->vec = rep.vec; h_info->launches = rep.launches; h_info->chunks = rep.chunks; h_info->instance = rep.instance; }
+}
+
+}  // namespace
+
+int rlap_bias_act_dropout(rlap_handle h, const float* d_x, int64_t L, int64_t N, int64_t F, const float* d_bias, const float* d_slope,
+                    double p, uint64_t seed, int flags, float* d_y, rlap_rowops_info* h_info) {
+    if (const int rc = rowops_check(h, d_x, L, N, F, d_slope, p, flags, h_info)) return rc;
+    if (!d_y) return RLAP_E_BAD_ARG;
+    RowopsArgs a{};
+    a.x = d_x; a.L = L; a.N = N; a.F = F; a.bias = d_bias; a.slope = d_slope; a.p = p; a.seed = seed; a.flags = flags; a.out = d_y;
+    return poisoned_call(h, [&] { return rowops_bytes(a, false); }, {{d_y, (size_t)(L * N * F) * 4}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) {
+        RowopsReport rep{};
+        const int rc = rowops_run(h->stream, base, have, a, &rep);
+        if (rc == RLAP_OK) rowops_report(h_info, rep);
+        return rc;
+    });
+}
+
+int rlap_bias_act_dropout_backward(rlap_handle h, const float* d_x, const float* d_gy, int64_t L, int64_t N, int64_t F,
+                    const float* d_bias, const float* d_slope, double p, uint64_t seed, int flags, float* d_gx, float* d_gbias,
+                    float* d_gslope, rlap_rowops_info* h_info) {
+    if (const int rc = rowops_check(h, d_x, L, N, F, d_slope, p, flags, h_info)) return rc;
+    if (!d_gy) return RLAP_E_BAD_ARG;
+    RowopsArgs a{};
+    a.x = d_x; a.gy = d_gy; a.L = L; a.N = N; a.F = F; a.bias = d_bias; a.slope = d_slope; a.p = p; a.seed = seed; a.flags = flags;
+    a.out = d_gx; a.gbias = d_gbias; a.gslope = (flags & RLAP_ROW_ACT_PRELU) ? d_gslope : nullptr;
+    const size_t slope_bytes = (size_t)((flags & RLAP_ROW_SLOPE_PER_CHANNEL) ? F : 1) * 4;
+    return poisoned_call(h, [&] { return rowops_bytes(a, true); },
+                         {{d_gx, (size_t)(L * N * F) * 4}, {d_gbias, (size_t)F * 4}, {a.gslope, slope_bytes}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) {
+        RowopsReport rep{};
+        const int rc = rowops_backward_run(h->stream, base, have, a, &rep);
+        if (rc == RLAP_OK) rowops_report(h_info, rep);
+        return rc;
+    });
+}
+
+int rlap_layer_norm(rlap_handle h, const float* d_x, int64_t L, int64_t N, int64_t F, const float* d_weight, const float* d_bias,
+                    const float* d_slope, double eps, double p, uint64_t seed, int flags, float* d_y, rlap_rowops_info* h_info) {
+    if (const int rc = rowops_check(h, d_x, L, N, F, d_slope, p, flags, h_info)) return rc;
+    if (!d_y || !norm::eps_ok(eps)) return RLAP_E_BAD_ARG;
+    RowopsArgs a{};
+    a.x = d_x; a.L = L; a.N = N; a.F = F; a.weight = d_weight; a.bias = d_bias; a.slope = d_slope; a.eps = eps; a.p = p; a.seed = seed;
+    a.flags = flags; a.out = d_y;
+    return poisoned_call(h, [&] { return ln_bytes(a, false); }, {{d_y, (size_t)(L * N * F) * 4}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) {
+        RowopsReport rep{};
+        const int rc = ln_run(h->stream, base, have, a, &rep);
+        if (rc == RLAP_OK) rowops_report(h_info, rep);
+        return rc;
+    });
+}
+
+int rlap_layer_norm_backward(rlap_handle h, const float* d_x, const float* d_gy, int64_t L, int64_t N, int64_t F, const float* d_weight,
+                    const float* d_bias, const float* d_slope, double eps, double p, uint64_t seed, int flags, float* d_gx,
+                    float* d_gweight, float* d_gbias, float* d_gslope, rlap_rowops_info* h_info) {
+    if (const int rc = rowops_check(h, d_x, L, N, F, d_slope, p, flags, h_info)) return rc;
+    if (!d_gy || !norm::eps_ok(eps)) return RLAP_E_BAD_ARG;
+    RowopsArgs a{};
+    a.x = d_x; a.gy = d_gy; a.L = L; a.N = N; a.F = F; a.weight = d_weight; a.bias = d_bias; a.slope = d_slope; a.eps = eps; a.p = p;
+    a.seed = seed; a.flags = flags; a.out = d_gx; a.gweight = d_gweight; a.gbias = d_gbias;
+    a.gslope = (flags & RLAP_ROW_ACT_PRELU) ? d_gslope : nullptr;
+    const size_t slope_bytes = (size_t)((flags & RLAP_ROW_SLOPE_PER_CHANNEL) ? F : 1) * 4;
+    return poisoned_call(h, [&] { return ln_bytes(a, true); },
+                         {{d_gx, (size_t)(L * N * F) * 4}, {d_gweight, (size_t)F * 4}, {d_gbias, (size_t)F * 4}, {a.gslope, slope_bytes}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) {
+        RowopsReport rep{};
+        const int rc = ln_backward_run(h->stream, base, have, a, &rep);
+        if (rc == RLAP_OK) rowops_report(h_info, rep);
         return rc;
     });
 }

@@ -1908,6 +1908,152 @@ def batch_norm(x: Tensor, weight: Optional[Tensor] = None, bias: Optional[Tensor
     return y, running_mean.detach().double().expand(L, -1).to(y.device), running_var.detach().double().expand(L, -1).to(y.device)
 
 
+ROW_MAX_F = _lib.ROW_MAX_F
+ROW_ACT = {"none": 0, "relu": _lib.ROW_ACT_RELU, "prelu": _lib.ROW_ACT_PRELU}
+
+
+def _row_args(x, vectors, act, slope, p, training, seed, what_act: str):
+    """Host-side checks of bias_act_dropout and layer_norm, made before the device is touched: (flags, p, seed)."""
+    if not isinstance(x, Tensor) or x.dim() not in (2, 3):
+        raise ValueError("x: a (N, F) or (L, N, F) tensor")
+    if x.dtype != torch.float32:
+        raise ValueError(f"x: torch.float32, got {x.dtype}")
+    L, n, f = (1 if x.dim() == 2 else int(x.shape[0])), int(x.shape[-2]), int(x.shape[-1])
+    if not isinstance(training, bool):
+        raise ValueError(f"training: a bool, got {training!r}")
+    if L < 1 or n < 1:
+        raise ValueError("x: at least one layer and one row")
+    if f < 1 or f > ROW_MAX_F:
+        raise ValueError(f"x: between 1 and {ROW_MAX_F} feature columns, got {f}")
+    if L * n * f >= 1 << 40:
+        raise ValueError("x: fewer than 2^40 elements")
+    for t, what in vectors:
+        _norm_vector(t, f, what, x)
+    if isinstance(p, bool) or not isinstance(p, (int, float)):
+        raise ValueError(f"p: a number, got {p!r}")
+    p = float(p)
+    if not (0.0 <= p < 1.0):
+        raise ValueError(f"p: in [0, 1), got {p!r}")
+    if not isinstance(act, str) or act not in ROW_ACT:
+        raise ValueError(f"{what_act}: one of {sorted(ROW_ACT)}, got {act!r}")
+    flags = ROW_ACT[act] | (_lib.ROW_TRAINING if training else 0)
+    if act == "prelu":
+        if not isinstance(slope, Tensor) or slope.dtype != torch.float32 or slope.dim() > 1 or slope.numel() not in (1, f):
+            raise ValueError(f'slope: with {what_act}="prelu" a torch.float32 tensor of one value or of ({f},)')
+        if slope.device != x.device:
+            raise ValueError(f"slope: on x's device {x.device}, got {slope.device}")
+        if slope.numel() == f and f > 1:
+            flags |= _lib.ROW_SLOPE_PER_CHANNEL
+    elif slope is not None:
+        raise ValueError(f'slope: only with {what_act}="prelu"')
+    if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int)):
+        raise ValueError(f"seed: an int or None, got {seed!r}")
+    dropping = training and p > 0.0
+    return flags, p, (_seed_from(seed) if dropping or seed is not None else 0)
+
+
+def _row_forward(export: str, x3: Tensor, params: tuple, head: tuple, p: float, seed: int, flags: int):
+    """The forward export `export` on x3 (L, N, F): (y, the device copies of x3 and of `params`).  `head` holds the scalar
+    arguments between the parameters and p."""
+    dev = _device_for(x3)
+    with torch.cuda.device(dev):
+        put = lambda t: None if t is None else t.detach().to(device=dev).contiguous()
+        d_x = put(x3)
+        d_params = tuple(put(t) for t in params)
+        L, n, f = (int(v) for v in d_x.shape)
+        y = torch.empty_like(d_x)
+        _device_call(export, _lib.RowopsInfo, dev, 1, (d_x.data_ptr(), L, n, f, *(_norm_ptr(t) for t in d_params), *head, p, seed, flags, y.data_ptr()))
+    return y, d_x, d_params
+
+
+class _RowPass(torch.autograd.Function):
+    """y = the fused row pass `export` of x3; the gradients with respect to x and the parameters come from the backward export,
+    which reads x and draws the forward's dropout coins again from (p, seed): nothing but x is kept."""
+
+    @staticmethod
+    def forward(ctx, export, head, p, seed, flags, x3, *params):
+        y, d_x, d_params = _row_forward(export, x3, params, head, p, seed, flags)
+        ctx.save_for_backward(d_x, *[t for t in d_params if t is not None])
+        ctx.present = [t is not None for t in d_params]
+        ctx.call = (export, head, p, seed, flags, [None if t is None else (t.device, t.shape) for t in (x3, *params)])
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        saved = list(ctx.saved_tensors)
+        d_x = saved.pop(0)
+        d_params = [saved.pop(0) if here else None for here in ctx.present]
+        export, head, p, seed, flags, origin = ctx.call
+        dev = d_x.device
+        need = ctx.needs_input_grad[5:]
+        with torch.cuda.device(dev):
+            d_gy = gy.detach().to(device=dev, dtype=torch.float32).contiguous()
+            L, n, f = (int(v) for v in d_x.shape)
+            gx = torch.empty_like(d_x) if need[0] else None
+            grads = [torch.empty(t.numel(), dtype=torch.float32, device=dev) if t is not None and need[1 + k] else None
+                     for k, t in enumerate(d_params)]
+            _device_call(export + "_backward", _lib.RowopsInfo, dev, 1, (
+                d_x.data_ptr(), d_gy.data_ptr(), L, n, f, *(_norm_ptr(t) for t in d_params), *head, p, seed, flags,
+                _norm_ptr(gx), *(_norm_ptr(g) for g in grads)))
+        back = lambda g, o: None if g is None else g.reshape(o[1]).to(o[0])
+        return (None, None, None, None, None, back(gx, origin[0])) + tuple(back(g, o) for g, o in zip(grads, origin[1:]))
+
+
+def _row_call(export: str, x: Tensor, params: tuple, head: tuple, p: float, seed: int, flags: int) -> Tensor:
+    x3 = x if x.dim() == 3 else x.unsqueeze(0)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, *params)):
+        y = _RowPass.apply(export, head, p, seed, flags, x3, *params)
+    else:
+        y = _row_forward(export, x3, params, head, p, seed, flags)[0]
+    return y if x.dim() == 3 else y.squeeze(0)
+
+
+def bias_act_dropout(x: Tensor, bias: Optional[Tensor] = None, act: str = "none", slope: Optional[Tensor] = None, p: float = 0.0,
+                     training: bool = True, seed: Optional[int] = 0) -> Tensor:
+    """y = F.dropout(act(x + bias), p, training) in one pass over x (rlap_bias_act_dropout) -- the bias add, the PReLU
+    and the dropout that the reference's encoders run behind every GCN and GIN layer, 8 bytes an element instead of three passes,
+    and no mask kept: the dropout coin is a function of (seed, layer, row, column, F, p) alone and is drawn again in the backward pass.
+
+      x        : (N, F) or (L, N, F) float32; 1 <= F <= 4096
+      bias     : (F,) float32 or None (0)
+      act      : "none", "relu" or "prelu"; "prelu" takes `slope`, one float32 value or (F,) per channel
+      p        : the drop probability, 0 <= p < 1; used as T / 65536 with T = round(p * 65536), and what is kept is scaled by
+                 1 / (1 - T / 65536)
+      training : False switches the dropout off, as p = 0 does: the call then gives the bits of the call without dropout
+      seed     : an int fixes the mask; None draws one seed from torch's generator, as drop_edges does.  Layer l of an (L, N, F)
+                 call draws the coins of the (N, F) call with seed + l.
+    Returns y of x's shape.  Every value is fixed (rlap_amd/csrc/rlap_rowops.h: float64, one rounding to float32): the same input
+    and seed give the same bits, forward and backward, on either lane path.
+
+    Differentiable in x, bias and slope (rlap_bias_act_dropout_backward, with the saved seed); double backward is not supported.
+    Malformed arguments raise ValueError before the device is touched.  No host synchronisation.  `last_stats` then holds what
+    the call did (rlap_rowops_info: rows, features, layers, chunks, arena_bytes, vec, launches, instance, host_syncs).
+    """
+    flags, p, seed = _row_args(x, ((bias, "bias"),), act, slope, p, training, seed, "act")
+    return _row_call("rlap_bias_act_dropout", x, (bias, slope), (), p, seed, flags)
+
+
+def layer_norm(x: Tensor, weight: Optional[Tensor] = None, bias: Optional[Tensor] = None, eps: float = 1e-5, post: str = "none",
+               slope: Optional[Tensor] = None, p: float = 0.0, training: bool = True, seed: Optional[int] = 0) -> Tensor:
+    """y = F.dropout(post(F.layer_norm(x, (F,), weight, bias, eps)), p, training) in one pass (rlap_layer_norm): every
+    row of an (N, F) or (L, N, F) float32 tensor is normalised over its F columns -- the LayerNorm branch of the reference's
+    Normalize with the PReLU and the dropout behind it.  A wave holds the row; x is read once and y written once.
+
+      weight, bias : (F,) float32 or None (1 and 0)
+      eps          : finite and > 0; a constant row gives 1 / sqrt(eps), no NaN
+      post, slope, p, training, seed : as bias_act_dropout's act, slope, p, training and seed
+    The row sums run in an order that depends on F alone (rlap_amd/csrc/rlap_rowops.h), so the same input gives the same bits on
+    either lane path.  Differentiable in x, weight, bias and slope (rlap_layer_norm_backward; nothing but x is kept for it).
+    Malformed arguments raise ValueError before the device is touched.  No host synchronisation.  `last_stats` as
+    bias_act_dropout; `instance` is the number of 16-byte steps a lane takes over a row (1, 2, 4: in registers; 8, 16: through LDS).
+    """
+    flags, p, seed = _row_args(x, ((weight, "weight"), (bias, "bias")), post, slope, p, training, seed, "post")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not (0.0 < float(eps) < float("inf")):
+        raise ValueError(f"eps: finite and > 0, got {eps!r}")
+    return _row_call("rlap_layer_norm", x, (weight, bias, slope), (float(eps),), p, seed, flags)
+
+
 G2L_MAX_F = 512
 
 
