@@ -909,6 +909,46 @@ int rlap_bt_loss_backward(rlap_handle h, const float* d_a, const float* d_b, int
                           const double* d_colstat, const float* d_cross, const double* d_g, float* d_ga, float* d_gb,
                           rlap_bt_info* h_info);
 
+/* The fused dense layer, forward and backward: y = act(x W + b) in one pass over x -- the torch.nn.Linear and the
+ * elementwise launches behind it of the encoders, the GIN layers' MLP and the projection heads -- and the gradients from (x, W, y, gy).
+ *   d_x, M, Fin    : (M, Fin) float32 row-major; 1 <= M < 2^31, 1 <= Fin <= 512.  An (L, N, Fin) tensor is its M = L N rows.
+ *   d_w, Fout      : the weight, (Fin, Fout) float32 row-major, or with RLAP_LINEAR_WEIGHT_OUT_IN (Fout, Fin) -- torch.nn.Linear's
+ *                    layout, no transposed copy is needed on the host; 1 <= Fout <= 512
+ *   d_b            : (nullable) the bias, (Fout,) float32
+ *   act, alpha     : RLAP_LINEAR_ACT_NONE, _RELU or _ELU; alpha is ELU's, finite and > 0 (checked whatever act is)
+ *   forward        : d_y (M, Fout) float32
+ *   backward       : d_y as the forward call left it, d_gy the upstream gradient (M, Fout); results, each nullable (a null pointer
+ *                    skips its kernels): d_gx (M, Fin), d_gw of d_w's layout, d_gb (Fout,)
+ *   h_info         : (nullable) what the call did
+ * Every value and the order of every sum are defined in rlap_amd/csrc/rlap_linear.h: x W and gy' W^T as float32 fmaf chains over
+ * the inner index in increasing order (what the f32 matrix-core instruction computes), the bias, the activation and one rounding
+ * applied to the accumulator in float64; the weight gradient as such chains over the rows per part, the parts a function of
+ * (M, Fin, Fout) alone and added in float64; the bias gradient by the chunk rule of rlap_amd/csrc/rlap_spmm.h.  gy' = gy act'(y)
+ * is formed wherever it is read and never stored.  So the same input gives the same bits, whatever the arena held and however the
+ * pointers are aligned; no atomic touches a floating-point value; neither call synchronises with the host; x, y, gy and gx are
+ * read and written in place -- only the weight is copied (padded) into the arena.
+ * A null d_x, d_w, d_y (or d_gy), M < 1, a width outside [1, 512], an unknown act or flag, an alpha that is not finite and > 0:
+ * RLAP_E_BAD_ARG.  M >= 2^31: RLAP_E_TOO_LARGE.  Scratch from the arena (RLAP_E_WORKSPACE when a caller-provided one is too small,
+ * the workspace-needed query saying how much). */
+enum { RLAP_LINEAR_WEIGHT_OUT_IN = 1 };
+enum { RLAP_LINEAR_ACT_NONE = 0, RLAP_LINEAR_ACT_RELU = 1, RLAP_LINEAR_ACT_ELU = 2 };
+
+typedef struct {
+    int64_t rows;             /* M                                                                    */
+    int64_t fin;              /* Fin                                                                  */
+    int64_t fout;             /* Fout                                                                 */
+    int64_t parts;            /* parts the rows are dealt into for the weight gradient: a function of (M, Fin, Fout) */
+    int64_t arena_bytes;      /* scratch bytes of the call                                            */
+    int32_t host_syncs;       /* host synchronisations of the call: 0                                 */
+    int32_t pad;
+} rlap_linear_info;
+
+int rlap_linear_act(rlap_handle h, const float* d_x, int64_t M, int64_t Fin, int64_t Fout, const float* d_w, const float* d_b, int act,
+                    double alpha, int flags, float* d_y, rlap_linear_info* h_info);
+int rlap_linear_act_backward(rlap_handle h, const float* d_x, const float* d_w, const float* d_y, const float* d_gy, int64_t M, int64_t Fin,
+                             int64_t Fout, int act, double alpha, int flags, float* d_gx, float* d_gw, float* d_gb,
+                             rlap_linear_info* h_info);
+
 /* The fused graph-to-local losses of node embeddings against graph summaries, forward and backward: one direction of
  * DualBranchContrast(JSD(), mode="G2L") and of BootstrapContrast(BootstrapLatent(), mode="G2L"), without the concatenated copy,
  * the dense (G, N) masks and the dense similarity matrix.  With s_ij = <h_i, g_j> and g(i) the graph of node i:

@@ -30,6 +30,7 @@ EXPORTS = [
     "rlap_linear_probe", "rlap_probe_scores", "rlap_edge_drop", "rlap_node_sample", "rlap_edge_add", "rlap_snapshot_markov",
     "rlap_feature_count", "rlap_feature_plan_bytes", "rlap_feature_plan_build", "rlap_feature_plan_apply",
     "rlap_bias_act_dropout", "rlap_bias_act_dropout_backward", "rlap_layer_norm", "rlap_layer_norm_backward",
+    "rlap_linear_act", "rlap_linear_act_backward",
 ]
 
 E_INDEX_RANGE = 2   # RLAP_E_INDEX_RANGE
@@ -77,6 +78,10 @@ NORM_MAX_F = 4096
 # rlap_bias_act_dropout flags and limits (rlap_amd/csrc/rlap_rowops.h)
 ROW_ACT_RELU, ROW_ACT_PRELU, ROW_SLOPE_PER_CHANNEL, ROW_TRAINING = 1, 2, 4, 8
 ROW_MAX_F = 4096
+# rlap_linear_act flags, activations and limits (rlap_amd/csrc/rlap_linear.h)
+LINEAR_WEIGHT_OUT_IN = 1
+LINEAR_ACT_NONE, LINEAR_ACT_RELU, LINEAR_ACT_ELU = 0, 1, 2
+LINEAR_MAX_F = 512
 # rlap_linear_probe select
 PROBE_SELECT_SCRIPTS, PROBE_SELECT_CCA = 0, 1
 
@@ -243,6 +248,14 @@ class BtInfo(_Report):
     ]
 
 
+class LinearInfo(_Report):
+    """rlap_linear_info (include/rlap_hip.h)."""
+    _fields_ = [
+        ("rows", ctypes.c_int64), ("fin", ctypes.c_int64), ("fout", ctypes.c_int64), ("parts", ctypes.c_int64),
+        ("arena_bytes", ctypes.c_int64), ("host_syncs", ctypes.c_int32), ("pad", ctypes.c_int32),
+    ]
+
+
 class NormInfo(_Report):
     """rlap_norm_info (include/rlap_hip.h)."""
     _fields_ = [
@@ -399,6 +412,10 @@ def load():
     lib.rlap_bt_loss.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ctypes.c_double, ci, vp, vp, vp, ctypes.POINTER(BtInfo)]
     lib.rlap_bt_loss_backward.restype = ci
     lib.rlap_bt_loss_backward.argtypes = [vp, vp, vp, i64, i64, ctypes.c_double, ctypes.c_double, ci, vp, vp, vp, vp, vp, ctypes.POINTER(BtInfo)]
+    lib.rlap_linear_act.restype = ci
+    lib.rlap_linear_act.argtypes = [vp, vp, i64, i64, i64, vp, vp, ci, ctypes.c_double, ci, vp, ctypes.POINTER(LinearInfo)]
+    lib.rlap_linear_act_backward.restype = ci
+    lib.rlap_linear_act_backward.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, ci, ctypes.c_double, ci, vp, vp, vp, ctypes.POINTER(LinearInfo)]
     lib.rlap_batch_norm.restype = ci
     lib.rlap_batch_norm.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, ctypes.c_double, ctypes.c_double, ci, vp, vp,
                                     ctypes.POINTER(NormInfo)]

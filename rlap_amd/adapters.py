@@ -170,6 +170,70 @@ def _snapshots_of(x, sc, ptr, num_nodes, keep_weights, fill_value):
     return Snapshots(sc, ptr, int(x.shape[0]) if x is not None else int(num_nodes), None, keep_weights, fill_value)
 
 
+def _dense_arg(dense) -> str:
+    if dense not in ("torch", "device"):
+        raise ValueError(f'dense: "torch" or "device", got {dense!r}')
+    return dense
+
+
+class SnapshotLinear(torch.nn.Module):
+    """torch.nn.Linear with a fused activation, on the device: forward(x) = ops.linear_act(x, weight, bias, act, alpha,
+    weight_layout="out_in") for x (N, in_features) or (L, N, in_features) -- one pass over x instead of the matmul, the bias add and
+    the activation.  Parameter names, shapes and initialisation are torch.nn.Linear's (`weight` is
+    (out_features, in_features), read in place in that layout; `bias` (out_features,) or None), so a Linear's state dict loads.
+    `act` is "none", "relu" or "elu" (`alpha` is ELU's)."""
+
+    def __init__(self, in_features: int, out_features: int, bias: bool = True, act: str = "none", alpha: float = 1.0):
+        super().__init__()
+        if act not in ops.LINEAR_ACT:
+            raise ValueError(f"act: one of {sorted(ops.LINEAR_ACT)}, got {act!r}")
+        self.in_features, self.out_features, self.act, self.alpha = int(in_features), int(out_features), act, float(alpha)
+        self.weight = torch.nn.Parameter(torch.empty(self.out_features, self.in_features))
+        if bias:
+            self.bias = torch.nn.Parameter(torch.empty(self.out_features))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        torch.nn.Linear.reset_parameters(self)   # (reads weight, bias and weight's shape alone)
+
+    def forward(self, x):
+        return ops.linear_act(x, self.weight, self.bias, act=self.act, alpha=self.alpha, weight_layout="out_in")
+
+    def extra_repr(self):
+        return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, act={self.act!r}"
+
+
+class SnapshotMLP(torch.nn.Module):
+    """Linear -> act -> Linear in two device calls, the first with the activation fused: the `nn` of scripts/graph_shared.py's GIN
+    layers, nn.Sequential(Linear(in, hidden), ReLU(), Linear(hidden, hidden)), and CCA-SSG/model.py's MLP without its batch norm
+    (use_bn=False).  The two layers are `fc1` and `fc2`, SnapshotLinears; forward(x) takes (N, in_dim) or (L, N, in_dim)."""
+
+    def __init__(self, in_dim: int, hidden_dim: int, out_dim: int, act: str = "relu"):
+        super().__init__()
+        self.fc1 = SnapshotLinear(in_dim, hidden_dim, act=act)
+        self.fc2 = SnapshotLinear(hidden_dim, out_dim)
+
+    def forward(self, x):
+        return self.fc2(self.fc1(x))
+
+
+class ProjectionHead(SnapshotMLP):
+    """scripts/node_shared.py's `project`: fc2(F.elu(fc1(z))) with fc1 = Linear(hidden_dim, proj_dim) and
+    fc2 = Linear(proj_dim, hidden_dim), the ELU fused into the first call."""
+
+    def __init__(self, hidden_dim: int, proj_dim: int, act: str = "elu"):
+        super().__init__(hidden_dim, proj_dim, hidden_dim, act=act)
+
+
+def _gin_mlp(d: int, hidden_dim: int, dense: str) -> torch.nn.Module:
+    """The MLP of a GIN layer: torch's modules, or with dense="device" the fused SnapshotMLP."""
+    if dense == "device":
+        return SnapshotMLP(d, hidden_dim, hidden_dim)
+    return torch.nn.Sequential(torch.nn.Linear(d, hidden_dim), torch.nn.ReLU(), torch.nn.Linear(hidden_dim, hidden_dim))
+
+
 class SnapshotGCNConv(torch.nn.Module):
     """GCNConv for all views of a call at once: forward(x, snapshots) = snapshots.propagate(x @ W) + b, an (L, n, out_channels)
     tensor for the L layers of `snapshots` (a `Snapshots`).  x is (n, in_channels), shared by the layers (the first GCN layer of
@@ -185,10 +249,14 @@ class SnapshotGCNConv(torch.nn.Module):
     (DESIGN 4.26); gradients then reach W and b.
 
     `epilogue`, a SnapshotActDropout, makes the layer return epilogue(propagate(x @ W), b): the bias add, the activation and the
-    dropout of scripts/node_shared.py's `GCNConv -> PReLU` in one fused pass.  Without it the layer is what it was."""
+    dropout of scripts/node_shared.py's `GCNConv -> PReLU` in one fused pass.  Without it the layer is what it was.
 
-    def __init__(self, in_channels: int, out_channels: int, bias: bool = True, epilogue=None):
+    `dense="device"` computes x @ W by ops.linear_act, so that every value of the layer has a stated order; the
+    default "torch" leaves the product to torch, as before."""
+
+    def __init__(self, in_channels: int, out_channels: int, bias: bool = True, epilogue=None, dense: str = "torch"):
         super().__init__()
+        self.dense = _dense_arg(dense)
         self.in_channels, self.out_channels = int(in_channels), int(out_channels)
         self.weight = torch.nn.Parameter(torch.empty(self.in_channels, self.out_channels))
         self.bias = torch.nn.Parameter(torch.empty(self.out_channels)) if bias else None
@@ -207,6 +275,8 @@ class SnapshotGCNConv(torch.nn.Module):
             y = snapshots.propagate(x.linear(self.weight, keep))
         elif keep is not None:
             raise ValueError("SnapshotGCNConv: keep goes with an ops.FeaturePlan as x (mask a tensor x with drop_feature)")
+        elif self.dense == "device":
+            y = snapshots.propagate(ops.linear_act(x, self.weight))
         else:
             y = snapshots.propagate(x @ self.weight)
         if self.epilogue is not None:
@@ -324,17 +394,19 @@ class SnapshotGINEncoder(torch.nn.Module):
     a `Snapshots` or its `.plan()` (anything with `.aggregate(x)` and `.readout(z)`); it returns the node embeddings
     (L, n, hidden_dim * num_layers) and the graph embeddings (L, G, hidden_dim * num_layers), the layers' outputs side by side as
     GConv concatenates them.  So the graph-level step is one (L, n, F) pipeline from the features to both embeddings, without a
-    Python loop over the views.  (GConv's `project` head belongs to the contrast model around it and is not part of this.)"""
+    Python loop over the views.  (GConv's `project` head belongs to the contrast model around it and is not part of this.)
+    `dense="device"` makes every layer's MLP a SnapshotMLP (ops.linear_act); the default leaves the Linears to torch."""
 
-    def __init__(self, input_dim: int, hidden_dim: int, num_layers: int):
+    def __init__(self, input_dim: int, hidden_dim: int, num_layers: int, dense: str = "torch"):
         super().__init__()
+        dense = _dense_arg(dense)
         if num_layers < 1:
             raise ValueError("num_layers: at least one")
         self.layers = torch.nn.ModuleList()
         self.batch_norms = torch.nn.ModuleList()
         for i in range(num_layers):
             d = input_dim if i == 0 else hidden_dim
-            self.layers.append(SnapshotGINConv(torch.nn.Sequential(torch.nn.Linear(d, hidden_dim), torch.nn.ReLU(), torch.nn.Linear(hidden_dim, hidden_dim))))
+            self.layers.append(SnapshotGINConv(_gin_mlp(d, hidden_dim, dense)))
             self.batch_norms.append(SnapshotBatchNorm(hidden_dim, pre="relu"))
 
     def forward(self, x, snapshots):
@@ -433,11 +505,14 @@ class SnapshotG2LEncoder(torch.nn.Module):
     head Linear -> norm(post="prelu") -> dropout.  With "layer" the head's PReLU and dropout are part of the layer-norm call; behind
     a batch norm, whose call is as it was, the dropout is an epilogue call of its own (`head_dropout`).  forward(x, snapshots) takes
     x (n, input_dim), shared by the views, or (L, n, input_dim), and a `Snapshots` or its `.plan()`; it returns (z, projection),
-    both (L, n, hidden_dim).  An integer `seed` fixes every dropout mask (call c of a forward uses seed + 1000 c)."""
+    both (L, n, hidden_dim).  An integer `seed` fixes every dropout mask (call c of a forward uses seed + 1000 c).
+    `dense="device"` makes every layer's MLP a SnapshotMLP and the head's Linear a SnapshotLinear (ops.linear_act); the
+    default leaves them to torch."""
 
     def __init__(self, input_dim: int, hidden_dim: int, num_layers: int, dropout: float = 0.2, encoder_norm: str = "batch",
-                 projector_norm: str = "batch", seed: Optional[int] = None):
+                 projector_norm: str = "batch", seed: Optional[int] = None, dense: str = "torch"):
         super().__init__()
+        dense = _dense_arg(dense)
         if num_layers < 1:
             raise ValueError("num_layers: at least one")
         for norm in (encoder_norm, projector_norm):
@@ -447,7 +522,7 @@ class SnapshotG2LEncoder(torch.nn.Module):
         self.layers = torch.nn.ModuleList()
         for i in range(num_layers):
             d = input_dim if i == 0 else hidden_dim
-            self.layers.append(SnapshotGINConv(torch.nn.Sequential(torch.nn.Linear(d, hidden_dim), torch.nn.ReLU(), torch.nn.Linear(hidden_dim, hidden_dim))))
+            self.layers.append(SnapshotGINConv(_gin_mlp(d, hidden_dim, dense)))
         self.activation = SnapshotActDropout("prelu", dropout, seed=sub(0))
         self.layer_seeds = None if seed is None else [int(seed) + 1000 * (2 + i) for i in range(num_layers)]
         if encoder_norm == "batch":
@@ -456,7 +531,7 @@ class SnapshotG2LEncoder(torch.nn.Module):
             self.batch_norm = SnapshotLayerNorm(hidden_dim)
         else:
             self.batch_norm = torch.nn.Identity()
-        self.head_linear = torch.nn.Linear(hidden_dim, hidden_dim)
+        self.head_linear = SnapshotLinear(hidden_dim, hidden_dim) if dense == "device" else torch.nn.Linear(hidden_dim, hidden_dim)
         if projector_norm == "batch":
             self.head_norm = SnapshotBatchNorm(hidden_dim, post="prelu")
             self.head_dropout = SnapshotActDropout("none", dropout, seed=sub(1))

@@ -42,6 +42,8 @@
 #include "rlap_cca_api.h"
 #include "rlap_bt.h"
 #include "rlap_bt_api.h"
+#include "rlap_linear.h"
+#include "rlap_linear_api.h"
 #include "rlap_norm.h"
 #include "rlap_norm_api.h"
 #include "rlap_rowops.h"
@@ -2023,6 +2025,47 @@ int rlap_bt_loss_backward(rlap_handle h, const float* d_a, const float* d_b, int
     a.g = d_g; a.ga = d_ga; a.gb = d_gb;
     return poisoned_call(h, [&] { return bt_backward_bytes(N, F); }, {{d_ga, (size_t)(N * F) * 4}, {d_gb, (size_t)(N * F) * 4}},
                          h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) { return bt_backward_run(h->stream, base, have, a); });
+}
+
+static_assert(RLAP_LINEAR_WEIGHT_OUT_IN == linear::WEIGHT_OUT_IN && RLAP_LINEAR_ACT_NONE == linear::ACT_NONE &&
+                  RLAP_LINEAR_ACT_RELU == linear::ACT_RELU && RLAP_LINEAR_ACT_ELU == linear::ACT_ELU, "the header's flag and activations are the rule's");
+
+namespace {
+
+// what both dense-layer exports check (their pointers come before this)
+int linear_check(rlap_handle h, int64_t M, int64_t Fin, int64_t Fout, int act, double alpha, int flags, rlap_linear_info* h_info) {
+    if (h_info) *h_info = rlap_linear_info{};
+    if (!h || M < 1 || !linear::features_ok(Fin) || !linear::features_ok(Fout) || !linear::act_ok(act) || !linear::alpha_ok(alpha) ||
+        !linear::flags_ok(flags))
+        return RLAP_E_BAD_ARG;
+    if (!linear::rows_ok(M)) return RLAP_E_TOO_LARGE;
+    if (h_info) { h_info->rows = M; h_info->fin = Fin; h_info->fout = Fout; h_info->parts = linear::num_parts(M, Fin, Fout); }
+    return RLAP_OK;
+}
+
+}  // namespace
+
+int rlap_linear_act(rlap_handle h, const float* d_x, int64_t M, int64_t Fin, int64_t Fout, const float* d_w, const float* d_b, int act,
+                    double alpha, int flags, float* d_y, rlap_linear_info* h_info) {
+    if (const int rc = linear_check(h, M, Fin, Fout, act, alpha, flags, h_info)) return rc;
+    if (!d_x || !d_w || !d_y) { if (h_info) *h_info = rlap_linear_info{}; return RLAP_E_BAD_ARG; }
+    LinearArgs a{};
+    a.x = d_x; a.w = d_w; a.b = d_b; a.M = M; a.Fin = Fin; a.Fout = Fout; a.act = act; a.alpha = alpha; a.flags = flags; a.y = d_y;
+    return poisoned_call(h, [&] { return linear_bytes(M, Fin, Fout); }, {{d_y, (size_t)(M * Fout) * 4}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) { return linear_run(h->stream, base, have, a); });
+}
+
+int rlap_linear_act_backward(rlap_handle h, const float* d_x, const float* d_w, const float* d_y, const float* d_gy, int64_t M, int64_t Fin,
+                             int64_t Fout, int act, double alpha, int flags, float* d_gx, float* d_gw, float* d_gb,
+                             rlap_linear_info* h_info) {
+    if (const int rc = linear_check(h, M, Fin, Fout, act, alpha, flags, h_info)) return rc;
+    if (!d_x || !d_w || !d_y || !d_gy) { if (h_info) *h_info = rlap_linear_info{}; return RLAP_E_BAD_ARG; }
+    LinearArgs a{};
+    a.x = d_x; a.w = d_w; a.M = M; a.Fin = Fin; a.Fout = Fout; a.act = act; a.alpha = alpha; a.flags = flags;
+    a.y_in = d_y; a.gy = d_gy; a.gx = d_gx; a.gw = d_gw; a.gb = d_gb;
+    return poisoned_call(h, [&] { return linear_backward_bytes(M, Fin, Fout, d_gx != nullptr, d_gw != nullptr, d_gb != nullptr); },
+                         {{d_gx, (size_t)(M * Fin) * 4}, {d_gw, (size_t)(Fin * Fout) * 4}, {d_gb, (size_t)Fout * 4}},
+                         h_info ? &h_info->arena_bytes : nullptr, [&](void* base, size_t have) { return linear_backward_run(h->stream, base, have, a); });
 }
 
 namespace {

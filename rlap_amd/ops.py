@@ -2054,6 +2054,117 @@ def layer_norm(x: Tensor, weight: Optional[Tensor] = None, bias: Optional[Tensor
     return _row_call("rlap_layer_norm", x, (weight, bias, slope), (float(eps),), p, seed, flags)
 
 
+LINEAR_MAX_F = _lib.LINEAR_MAX_F
+LINEAR_ACT = {"none": _lib.LINEAR_ACT_NONE, "relu": _lib.LINEAR_ACT_RELU, "elu": _lib.LINEAR_ACT_ELU}
+LINEAR_LAYOUT = {"in_out": 0, "out_in": _lib.LINEAR_WEIGHT_OUT_IN}
+
+
+def _linear_args(x, weight, bias, act, alpha, weight_layout):
+    """Host-side checks of linear_act, made before the device is touched: (act code, alpha, flags, Fin, Fout)."""
+    if not isinstance(x, Tensor) or x.dim() not in (2, 3):
+        raise ValueError("x: a (N, Fin) or (L, N, Fin) tensor")
+    if x.dtype != torch.float32:
+        raise ValueError(f"x: torch.float32, got {x.dtype}")
+    if not isinstance(weight_layout, str) or weight_layout not in LINEAR_LAYOUT:
+        raise ValueError(f"weight_layout: one of {sorted(LINEAR_LAYOUT)}, got {weight_layout!r}")
+    if not isinstance(weight, Tensor) or weight.dim() != 2:
+        raise ValueError("weight: a (Fin, Fout) tensor, or (Fout, Fin) with weight_layout=\"out_in\"")
+    if weight.dtype != torch.float32:
+        raise ValueError(f"weight: torch.float32, got {weight.dtype}")
+    if weight.device != x.device:
+        raise ValueError(f"weight: on x's device {x.device}, got {weight.device}")
+    flags = LINEAR_LAYOUT[weight_layout]
+    fin, fout = (int(weight.shape[1]), int(weight.shape[0])) if flags else (int(weight.shape[0]), int(weight.shape[1]))
+    rows = int(x.shape[-2]) * (1 if x.dim() == 2 else int(x.shape[0]))
+    if rows < 1:
+        raise ValueError("x: at least one layer and one row")
+    if rows >= 1 << 31:
+        raise ValueError("x: fewer than 2^31 rows in all")
+    if int(x.shape[-1]) != fin:
+        raise ValueError(f"x: {fin} feature columns as the weight's, got {int(x.shape[-1])}")
+    for f, what in ((fin, "Fin"), (fout, "Fout")):
+        if f < 1 or f > LINEAR_MAX_F:
+            raise ValueError(f"{what}: between 1 and {LINEAR_MAX_F}, got {f}")
+    if bias is not None:
+        if not isinstance(bias, Tensor) or bias.dtype != torch.float32 or bias.dim() != 1 or int(bias.shape[0]) != fout:
+            raise ValueError(f"bias: a ({fout},) torch.float32 tensor or None")
+        if bias.device != x.device:
+            raise ValueError(f"bias: on x's device {x.device}, got {bias.device}")
+    if not isinstance(act, str) or act not in LINEAR_ACT:
+        raise ValueError(f"act: one of {sorted(LINEAR_ACT)}, got {act!r}")
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not (0.0 < float(alpha) < float("inf")):
+        raise ValueError(f"alpha: finite and > 0, got {alpha!r}")
+    return LINEAR_ACT[act], float(alpha), flags, fin, fout
+
+
+def _linear_forward(x: Tensor, weight: Tensor, bias: Optional[Tensor], act: int, alpha: float, flags: int, fin: int, fout: int):
+    """The forward export on x (..., Fin): (y (..., Fout), the device copies of x, weight and bias)."""
+    dev = _device_for(x)
+    with torch.cuda.device(dev):
+        put = lambda t: None if t is None else t.detach().to(device=dev).contiguous()
+        d_x, d_w, d_b = put(x), put(weight), put(bias)
+        rows = d_x.numel() // fin
+        y = torch.empty(tuple(d_x.shape[:-1]) + (fout,), dtype=torch.float32, device=dev)
+        _device_call("rlap_linear_act", _lib.LinearInfo, dev, 1, (
+            d_x.data_ptr(), rows, fin, fout, d_w.data_ptr(), _norm_ptr(d_b), act, alpha, flags, y.data_ptr()))
+    return y, d_x, d_w, d_b
+
+
+class _LinearAct(torch.autograd.Function):
+    """y = act(x W + b) by the fused dense layer; the gradients that are required come from the backward export, which reads x, W
+    and y: the pre-activation is never kept."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, act, alpha, flags, fin, fout):
+        y, d_x, d_w, d_b = _linear_forward(x, weight, bias, act, alpha, flags, fin, fout)
+        ctx.save_for_backward(d_x, d_w, y)
+        ctx.call = (act, alpha, flags, fin, fout, x.device, weight.device, None if bias is None else bias.device)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        d_x, d_w, y = ctx.saved_tensors
+        act, alpha, flags, fin, fout, dev_x, dev_w, dev_b = ctx.call
+        dev = d_x.device
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], dev_b is not None and ctx.needs_input_grad[2]
+        with torch.cuda.device(dev):
+            d_gy = gy.detach().to(device=dev, dtype=torch.float32).contiguous()
+            gx = torch.empty_like(d_x) if need_x else None
+            gw = torch.empty_like(d_w) if need_w else None
+            gb = torch.empty(fout, dtype=torch.float32, device=dev) if need_b else None
+            _device_call("rlap_linear_act_backward", _lib.LinearInfo, dev, 1, (
+                d_x.data_ptr(), d_w.data_ptr(), y.data_ptr(), d_gy.data_ptr(), d_x.numel() // fin, fin, fout, act, alpha, flags,
+                _norm_ptr(gx), _norm_ptr(gw), _norm_ptr(gb)))
+        back = lambda g, d: None if g is None else g.to(d)
+        return back(gx, dev_x), back(gw, dev_w), back(gb, dev_b), None, None, None, None, None
+
+
+def linear_act(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, act: str = "none", alpha: float = 1.0,
+               weight_layout: str = "in_out") -> Tensor:
+    """y = act(x @ W + bias) in one pass over x (rlap_linear_act) -- the torch.nn.Linear and the elementwise launches
+    behind it of the encoders, the GIN layers' MLP and the projection heads: the bias and the activation are applied to the
+    accumulator, x is read once and y written once, and nothing but x, W and y is kept for the backward pass.
+
+      x             : (N, Fin) or (L, N, Fin) float32; 1 <= Fin <= 512.  The layers share the weight: the call is the (L N, Fin) one.
+      weight        : (Fin, Fout) float32, 1 <= Fout <= 512; with weight_layout="out_in" (Fout, Fin), torch.nn.Linear's layout
+                      (no transposed copy is made)
+      bias          : (Fout,) float32 or None
+      act           : "none", "relu" or "elu"; `alpha` is ELU's, finite and > 0
+    Returns y of x's leading shape, (..., Fout).  Every value and the order of every sum are fixed (rlap_amd/csrc/rlap_linear.h:
+    float32 fmaf chains over the inner index, what the f32 matrix-core instruction computes; bias, activation and one rounding in
+    float64): the same input gives the same bits, however the tensors are aligned.
+
+    Differentiable in x, weight and bias (rlap_linear_act_backward; only the gradients that are required are computed); double
+    backward is not supported.  Malformed arguments raise ValueError before the device is touched.  No host synchronisation.
+    `last_stats` then holds what the call did (rlap_linear_info: rows, fin, fout, parts, arena_bytes, host_syncs).
+    """
+    args = _linear_args(x, weight, bias, act, alpha, weight_layout)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, bias)):
+        return _LinearAct.apply(x, weight, bias, *args)
+    return _linear_forward(x, weight, bias, *args)[0]
+
+
 G2L_MAX_F = 512
 
 
